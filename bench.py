@@ -26,9 +26,14 @@ traffic) and keep environment groups resident in the 256 MiB Infinity Cache, so 
 committed PMC profile of this command, profiles/pmc_r02.json, over the live launch time; peak = the scalar-fp32
 issue rate measured by tools/valubench.hip, profiles/r02_valubench.txt), `traffic` = measured L2 fabric-side bytes.
 
-After the timed region the line proves its own result (`parity_spot_*`: the same library call on fresh inputs,
-first / last environment of every group against the CPU oracle) and adds `api_value`: env-steps/s through
-VectorPDEEnv.step with the reward and uint8 observations formed on the GPU.
+A plain run sets up, warms up, times the --steps steps and prints the line (headline figures, roofline block from the
+timed region's own events).  With --full the line also proves its own result (`parity_spot_*`: the same library call
+on fresh inputs, first / last environment of every group against the CPU oracle) and adds `api_value`: env-steps/s
+through VectorPDEEnv.step with the reward and uint8 observations formed on the GPU, and `cpu_baseline`; the other
+drivers' parity spots, and the adaptive workloads' device-timed roofline solve, are --full legs too.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (dump_outputs below): the
+same arguments give the same inputs, so two builds can be compared output for output.
 
 Other workloads (--workload) are secondary rows for DESIGN.md, not the bench line.
 """
@@ -452,8 +457,13 @@ def run_decomp(args, P, world, rank, local_rank, dist, make_solver=None):
         per_rank = [float(t_[0]) for t_ in allt]
         elapsed = max(per_rank)
     tile = sol.local_state()
+    if args.dump_outputs:
+        # this process's tiles of the field after the last timed step (virtual ranks: every rank's; torchrun: one file per rank)
+        ranks = range(vranks) if vranks else [rank]
+        dump_outputs(args.dump_outputs, {f"tile_rank{r}" if nranks > 1 else "field": s_.local_state() for r, s_ in zip(ranks, sols)},
+                     budget=DUMP_BYTES // (1 if vranks else nranks))
     spot = None
-    if not args.no_parity_spot:
+    if args.full and not args.no_parity_spot:
         # EVERY rank runs the spot's substeps (they contain collectives); rank 0 alone compares its tile against the
         # C oracle run on the whole periodic field
         nspot = 7
@@ -528,6 +538,30 @@ def run_decomp(args, P, world, rank, local_rank, dist, make_solver=None):
     if spot is not None and not spot["parity_spot_ok"]:
         raise SystemExit(f"parity spot check FAILED: {spot}")
     return spot
+
+
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs DIR: every array of ``arrays`` ({name: array}) as DIR/<name>.npy, float32 kept, anything else
+    as float64.  The arrays share ``budget`` bytes (smallest first, each at most an equal share of what is left); one
+    larger than its share is written as a fixed sample drawn with seed 0, in index order: whole entries of its leading
+    axis (environments) where one entry fits, single elements of the flattened array otherwise."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: kv[1].nbytes)
+    for i, (name, a) in enumerate(items):
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        share = budget // (len(items) - i)
+        if a.nbytes > share:
+            rng = np.random.default_rng(0)
+            if a.ndim > 1 and a[0].nbytes <= share:
+                a = a[np.sort(rng.choice(a.shape[0], share // a[0].nbytes, replace=False))]
+            else:
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
+        print(f"[bench] {os.path.join(out_dir, name + '.npy')}: {a.dtype} {a.shape}", file=sys.stderr)
 
 
 def usable_cores():
@@ -745,7 +779,24 @@ def run_adaptive(args, P):
     trials = int(sol.stats["num_steps"])
     kernel = sol.stats["kernel"]
     us_per_trial = 1e6 * elapsed / (args.steps * trials)
-    # the launch alone (HIP events around one more solve: upload + kernel + read-back on the engine's stream)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ts": sol.ts, "ys": sol.ys})
+    line = {
+        "metric": f"adaptive trial steps/sec ({args.workload}: Tsit5 + PID rtol {w['rtol']:g} atol {w['atol']:g}, t = 0 .. {w['t1']:g})",
+        "value": args.steps * trials / elapsed, "unit": "trial-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if np.dtype(w["dtype"]).itemsize == 4 else "f64", "data": "synthetic",
+        "config": {"workload": args.workload, "grid": [w["n"], w["n"]], "envs_per_gpu": 1, "integrator": "tsit5 + PID controller (in-kernel)",
+                   "trial_steps_per_solve": trials, "accepted": int(sol.stats["num_accepted_steps"]), "rejected": int(sol.stats["num_rejected_steps"]),
+                   "kernel": kernel, "step": "one P.diffeqsolve call over the span: upload, ONE launch, statistics + save points back"},
+        "us_per_trial_step": us_per_trial,
+    }
+    if not args.full:
+        eng.close()
+        print(json.dumps(line))
+        sys.stdout.flush()
+        return line
+    # --full: the launch alone (HIP events around one more solve: upload + kernel + read-back on the engine's stream)
     eng.timer_start()
     solve()
     dev_ms = eng.timer_stop()
@@ -806,19 +857,7 @@ def run_adaptive(args, P):
                                f"largest difference at the save points"}
         cpu = {"value": n_ref / el_c, "unit": "trial-steps/s", "cores": 1, "kind": "port",
                "sample": f"the whole solve ({n_ref} trial steps, 7 right-hand sides each) on the numpy oracle, 1 thread, {el_c:.1f} s"}
-    line = {
-        "metric": f"adaptive trial steps/sec ({args.workload}: Tsit5 + PID rtol {w['rtol']:g} atol {w['atol']:g}, t = 0 .. {w['t1']:g})",
-        "value": args.steps * trials / elapsed, "unit": "trial-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if esize == 4 else "f64", "data": "synthetic",
-        "config": {"workload": args.workload, "grid": [n, n], "envs_per_gpu": 1, "integrator": "tsit5 + PID controller (in-kernel)",
-                   "trial_steps_per_solve": trials, "accepted": int(sol.stats["num_accepted_steps"]), "rejected": int(sol.stats["num_rejected_steps"]),
-                   "kernel": kernel, "step": "one P.diffeqsolve call over the span: upload, ONE launch, statistics + save points back"},
-        "us_per_trial_step": us_per_trial,
-        "roofline": roof,
-        "cpu_baseline": cpu,
-        **spot,
-    }
+    line.update({"roofline": roof, "cpu_baseline": cpu, **spot})
     eng.close()
     print(json.dumps(line))
     sys.stdout.flush()
@@ -872,9 +911,11 @@ def run_single_process(args, P, engines=None):
         per_dev += np.asarray(env.last_step_seconds)
     elapsed = time.perf_counter() - t0
     kernel = env._shards[0].engine.last_kernel
-    # parity: the first and last environment of the job against the C oracle over the steps taken (RK4 workloads)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"reward": rew, "state": env.states})
+    # parity (--full): the first and last environment of the job against the C oracle over the steps taken (RK4 workloads)
     spot = None
-    if not args.no_parity_spot and w["integ"] == "rk4" and w["dtype"] is np.float32:
+    if args.full and not args.no_parity_spot and w["integ"] == "rk4" and w["dtype"] is np.float32:
         from oracle import c_oracle as CO
 
         eq_id, cmu, cmob = _oracle_closures(w)
@@ -927,9 +968,15 @@ def main():
     ap.add_argument("--fuse", type=int, default=0, help="RK4 stage-pair fusion: 0 auto, -1 off")
     ap.add_argument("--group-streams", type=int, default=0, help="environment groups: 0 auto (two side by side on two streams), 1 one at a time")
     ap.add_argument("--ablate", type=int, default=0, help="TIMING ONLY (wrong results): kernel phase ablation bits")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-spot", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the VectorPDEEnv.step throughput leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: parity spot against the CPU oracle, the VectorPDEEnv.step "
+                         "throughput (api_value), the CPU baseline, the adaptive workloads' device-timed roofline solve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed seeded sample of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity-spot", action="store_true", help="--full without the parity spot")
+    ap.add_argument("--no-api", action="store_true", help="--full without the VectorPDEEnv.step throughput leg")
     ap.add_argument("--decomp-mode", default="auto", choices=["auto", "native", "native-overlap", "peer", "plain", "overlap", "graph"],
                     help="ch_rk4_4096_decomp: driver path (auto = native: the library's own RCCL communicator, substep "
                          "loop in C; native-overlap: + collective on a second stream under the interior tiles; "
@@ -1041,8 +1088,10 @@ def main():
 
     # sanity: the timed state is finite (a diverged run would be measuring NaN arithmetic)
     bad = float(eng.reduce(L.RED_NONFINITE).sum())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"state": eng.get_state()})  # what pdeopt_advance left in the batch's states
     spot = None
-    if rank == 0 and not args.no_parity_spot and not args.ablate:
+    if rank == 0 and args.full and not args.no_parity_spot and not args.ablate:
         spot = parity_spot(args.workload, eng, eq, solver, y0, usable_cores())
 
     if rank == 0:
@@ -1088,9 +1137,9 @@ def main():
             **(spot or {}),
             "roofline": roofline_block(args.workload, kernel_name, bytes_per_launch, words, avg_launch_s, launches, concurrent, shader_hz),
         }
-        if args.gpus == 1 and not args.no_api and not args.ablate:
+        if args.full and args.gpus == 1 and not args.no_api and not args.ablate:
             line.update(api_throughput(P, args.workload, rank, args.steps, args.warmup) or {})
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.workload, args.cpu_seconds)
             if cb is not None:
                 line["cpu_baseline"] = cb

@@ -29,6 +29,40 @@ REF = "/root/reference"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
 
 
+PART_BYTES = 900 * 1024  # a committed file stays under 1 MiB
+
+
+def _savez_parts(name, arrays):
+    """np.savez_compressed(tests/golden/<name>.npz, **arrays) -- or, when that would exceed PART_BYTES, the arrays in
+    order over <name>.part0.npz, <name>.part1.npz, ..., each under PART_BYTES (tests/conftest.py reads them as one)"""
+    import glob
+    import io
+
+    stem = os.path.join(OUT, name)
+    for f in glob.glob(stem + ".part*.npz") + glob.glob(stem + ".npz"):
+        os.remove(f)
+
+    def size(d):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **d)
+        return buf.tell()
+
+    if size(arrays) <= PART_BYTES:
+        np.savez_compressed(stem + ".npz", **arrays)
+        return
+    parts, cur, cur_bytes = [], {}, 0
+    for k, v in arrays.items():
+        s = size({k: v})
+        if cur and cur_bytes + s > PART_BYTES:
+            parts.append(cur)
+            cur, cur_bytes = {}, 0
+        cur[k], cur_bytes = v, cur_bytes + s
+    parts.append(cur)
+    for i, d in enumerate(parts):
+        assert size(d) <= PART_BYTES, (name, list(d))
+        np.savez_compressed(f"{stem}.part{i}.npz", **d)
+
+
 def _mod(name, **attrs):
     m = types.ModuleType(name)
     m.__dict__.update(attrs)
@@ -249,7 +283,7 @@ def main():
                 eq = ref.ac.AllenCahn2DPeriodic(dom, kappa, MU["cubic"], MOB["one_plus_sq"], derivs="fourier")
                 cases[f"ac_fourier/cubic/one_plus_sq/{tag}/u"] = u_sym
                 cases[f"ac_fourier/cubic/one_plus_sq/{tag}/rhs"] = np.asarray(eq.rhs(u_sym, 0.0))
-    np.savez_compressed(os.path.join(OUT, "rhs_cases.npz"), **cases)
+    _savez_parts("rhs_cases", cases)
 
     # ---- manufactured solution (tests/test_rhs_convergence.py) ---------------
     import sympy as sp
@@ -401,7 +435,7 @@ def main():
             c3[f"{tag}/rhs"] = np.asarray(eq.rhs(u, 0.0))
             if dtype is np.float64 and nx * ny * nz <= 4096:
                 c3[f"{tag}/symbol"] = np.asarray(eq.fourier_symbol)
-    np.savez_compressed(os.path.join(OUT, "ch3d_cases.npz"), **c3)
+    _savez_parts("ch3d_cases", c3)
 
     round2(ref)
     print("wrote goldens to", os.path.abspath(OUT))
@@ -443,7 +477,7 @@ def round2(ref):
             traj[f"strang_tdep/{n}/{name}/ys"] = np.stack(seq)
         traj[f"strang_tdep/{n}/b_terms_t0"] = np.asarray(geq.B_terms(y0, 0.0))
         traj[f"strang_tdep/{n}/b_terms_t3"] = np.asarray(geq.B_terms(y0, 3e-3))
-    np.savez_compressed(os.path.join(OUT, "trajectories_r2.npz"), **traj)
+    _savez_parts("trajectories_r2", traj)
 
     # ---- CahnHilliard3DPeriodic.rhs_fourier (cahn_hilliard.py:167-175; 9 transforms), fp64 only (the
     # spectral constants are f64 in numpy but f32 in JAX-without-x64)

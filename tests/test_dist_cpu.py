@@ -158,7 +158,7 @@ def _bench_decomp_worker(rank, world, port, q):
             return DecomposedSolver(eq, grid, comm=TorchComm(), dtype=np.float32, backend=be)
 
         args = argparse.Namespace(decomp_grid=32, decomp_substeps=3, virtual_ranks=0, decomp_mode="plain", decomp_halo=0,
-                                  warmup=1, steps=2, no_parity_spot=False)
+                                  warmup=1, steps=2, no_parity_spot=False, full=True, dump_outputs=None)
         spot = bench.run_decomp(args, P, world, rank, 0, dist, make_solver=make_solver)
         q.put((rank, None if spot is None else spot["parity_spot_ok"], None if spot is None else spot["parity_spot_rel_err"]))
         dist.barrier()

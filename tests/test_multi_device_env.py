@@ -222,7 +222,8 @@ def test_bench_single_process_mode_on_engine_doubles():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
 
-    args = argparse.Namespace(workload="ch_rk4_64_f32_small", batch_per_gpu=1, gpus=2, steps=1, warmup=0, no_parity_spot=False)
+    args = argparse.Namespace(workload="ch_rk4_64_f32_small", batch_per_gpu=1, gpus=2, steps=1, warmup=0, no_parity_spot=False,
+                              full=True, dump_outputs=None)
     import contextlib
     import io
 

@@ -4,7 +4,7 @@ LIBS=$1; WL=${2:-"ch_sbm_100_tsit5 ad_64_tsit5"}
 for r in 1 2; do
   for w in $WL; do
     for lib in $LIBS; do
-      PDEOPT_LIB=$PWD/$lib timeout 120 python bench.py --no-cpu-baseline --no-parity-spot --steps 5 --warmup 1 --workload $w 2>&1 | tail -1 | python -c "
+      PDEOPT_LIB=$PWD/$lib timeout 120 python bench.py --full --no-cpu-baseline --no-parity-spot --steps 5 --warmup 1 --workload $w 2>&1 | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1])
