@@ -457,6 +457,30 @@ int pdeopt_tsit5_solve_small_supported(pdeopt_ctx* ctx);
 int pdeopt_tsit5_solve_small(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pdeopt_pid* pid, int64_t max_steps,
                              int n_save, const double* save_ts, void* host_save, pdeopt_tsit5_stats* stats);
 
+/* ---- forward-mode sensitivities of the Cahn-Hilliard solve (PDEModel.train / residuals, pde_opt/pde_model.py:138-460)
+ * The reference differentiates diffeqsolve with diffrax's ForwardMode adjoint (pde_model.py:410-423) to fill the
+ * Jacobian of its Levenberg-Marquardt fit.  Here the P tangent fields du/dp_j ride through the solver as extra
+ * environments: configure the ctx with batch (1 + P) B (periodic 2-D Cahn-Hilliard, derivs "fd"), put the B
+ * trajectories in environments [0, B) and tangent j of trajectory b in environment B + j B + b (zero at t0: the
+ * initial states are data).  pdeopt_get_state / pdeopt_snapshot / pdeopt_get_interpolated read and interpolate the
+ * tangents like any environment. */
+typedef enum { PDEOPT_SENS_MU = 0, PDEOPT_SENS_MOB = 1 } pdeopt_sens_role;
+/* the P parameters: parameter j is coefficient coef_index[j] of the closure roles[j] (mu_h or D) */
+int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32_t* roles, const int32_t* coef_index);
+/* TA = the base slopes f(y) and the tangent slopes J_f(y) du_j + df/dp_j of the current state, copied to host_out
+ * ([(1 + P) B][nx][ny], may be NULL).  The tangent-linear right-hand side of cahn_hilliard.py:89-109 */
+int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out);
+/* n_substeps of state + tangents: IMEX (solvers.py:56-63: du_1 = du_0 + dt L^-1 [J_f du_0 + df/dp], the implicit
+ * operator L shared by base and tangents) or Euler (du_1 = du_0 + dt dk).  Asynchronous like pdeopt_advance. */
+int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps);
+/* the observed frames of a fit, uploaded once: host is [n_frames][B][nx][ny] in the problem dtype */
+int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host);
+/* Gauss-Newton sums of one save point against data frame `frame`: pred = snapshot + theta (state - snapshot) when
+ * interp != 0 (LocalLinearInterpolation, as pdeopt_get_interpolated), else the state; r = data - pred.  out is
+ * [B][1 + P + P (P + 1) / 2] doubles per trajectory: sum r^2, sum r dpred_j (j < P), sum dpred_i dpred_j (i <= j,
+ * row-major upper triangle).  Accumulated in fp64 by a fixed-order reduction: repeated calls give identical bits. */
+int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out);
+
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);
 int pdeopt_timer_start(pdeopt_ctx* ctx);           /* hipEventRecord on the ctx stream */

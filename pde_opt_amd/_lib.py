@@ -28,6 +28,7 @@ EQ_SHAPE_SMOOTH = 7  # Shape.smooth_shape (shapes.py:39-64)
 INT_EULER, INT_RK4, INT_IMEX, INT_STRANG, INT_TSIT5 = 0, 1, 2, 3, 4
 CL_POLY, CL_LEGENDRE, CL_JIT = 0, 1, 2
 CL_LOGIT_PRIOR, CL_EXP_WRAP = 1, 2
+SENS_MU, SENS_MOB = 0, 1  # pdeopt_sens_role
 AUX_VX_FACE, AUX_VY_FACE, AUX_IMEX_SYMBOL, AUX_GPE_A_TERM, AUX_GPE_POTENTIAL = 0, 1, 2, 3, 4
 AUX_SBM_PSI, AUX_SBM_NORM_GRAD, AUX_SBM_MASK = 5, 6, 7
 RED_MEAN, RED_VAR, RED_MIN, RED_MAX, RED_SUMSQ, RED_NONFINITE = 0, 1, 2, 3, 4, 5
@@ -184,6 +185,11 @@ _SIGNATURES = {
     "pdeopt_timer_stop": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "pdeopt_timer_clock": (C.c_int, [_VP, C.POINTER(C.c_double)]),
     "pdeopt_last_kernel": (C.c_char_p, [_VP]),
+    "pdeopt_sens_configure": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP]),
+    "pdeopt_sens_rhs": (C.c_int, [_VP, _VP]),
+    "pdeopt_sens_advance": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.c_int64]),
+    "pdeopt_sens_set_data": (C.c_int, [_VP, C.c_int, _VP]),
+    "pdeopt_sens_accumulate": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
 }
 
 _lib = None

@@ -64,6 +64,7 @@ void free_fields(pdeopt_ctx* ctx) {
   }
   spectral_destroy(ctx);
   strang_fused_destroy(ctx);
+  sens_destroy(ctx);
   graph_destroy(ctx);
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;

@@ -94,6 +94,7 @@ struct AuxField {
 struct CommState;    // RCCL / in-process communicator + strip buffers of the decomposed driver (comm.hip)
 struct Spectral;     // rocFFT plans + work buffers (spectral.hip)
 struct StrangFused;  // LDS-FFT split-step state (strang_fused.hip)
+struct Sens;         // forward-mode sensitivity configuration + Gauss-Newton buffers (sens.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -206,6 +207,7 @@ struct pdeopt_ctx {
   pdeopt::CommState* comm = nullptr;
   pdeopt::Spectral* spectral = nullptr;
   pdeopt::StrangFused* strang_fused = nullptr;
+  pdeopt::Sens* sens = nullptr;
 };
 
 namespace pdeopt {
@@ -333,6 +335,11 @@ bool strang_fused_supported(const pdeopt_ctx* ctx);
 int advance_strang_fused(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
 bool imex_fused_supported(const pdeopt_ctx* ctx);
 int advance_imex_fused(pdeopt_ctx* ctx, double dt, int64_t n);
+// the IMEX step's transforms alone, for callers that form the slope TA themselves (sens.hip): prepare the multiplier
+// of step dt, then y += dt L^-1 TA over the window [win_lo, win_lo + win_n)
+int imex_fused_prepare(pdeopt_ctx* ctx, double dt);
+int imex_fused_passes(pdeopt_ctx* ctx, double dt);
+void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);
 

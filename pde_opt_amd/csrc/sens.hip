@@ -1,0 +1,495 @@
+// Forward-mode sensitivities of the Cahn-Hilliard solve with respect to closure coefficients, and the Gauss-Newton
+// sums of a least-squares fit (the reference's PDEModel.train / residuals, pde_opt/pde_model.py:138-460, which
+// differentiates diffeqsolve with diffrax's ForwardMode adjoint at :410-423).
+//
+// Layout: the ctx is configured with batch (1 + P) B.  Environments [0, B) are the B trajectories; environment
+// B + j B + b holds the tangent du/dp_j of trajectory b.  Per substep
+//   IMEX   k = f(y) for the base block (launch_rhs_slope, the forward solve's own slope kernel),
+//          dk_j = J_f(y) du_j + df/dp_j for the tangent block (sens_tangent_rhs_kernel),
+//          y += dt L^-1 k over the whole (1 + P) B batch (the forward IMEX transforms): L = 1 + A dt fourier_symbol is
+//          linear and independent of the coefficients (kappa is not trainable), so the tangent of the step is the
+//          same implicit solve applied to the linearised slope -- 4 launches + 1.
+//   Euler  the same two slope launches, then y += dt k over the whole batch (3 launches).
+#include <vector>
+
+#include "closures.hpp"
+#include "common.hpp"
+
+namespace pdeopt {
+
+constexpr int kMaxSens = 2 * PDEOPT_CLOSURE_MAX_COEF;
+
+struct Sens {
+  int B = 0, P = 0;
+  int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB
+  int index[kMaxSens] = {};  // coefficient k of that closure
+  void* data = nullptr;      // [n_frames][B][nx][ny] observed frames, problem dtype
+  int n_frames = 0;
+  size_t data_bytes = 0;
+  double* partial = nullptr;  // [B][K][nblk] per-block sums of the accumulation
+  double* sums = nullptr;     // [B][K]
+  size_t partial_bytes = 0, sums_bytes = 0;
+};
+
+namespace {
+
+// ---- closure derivatives (the family of include/pdeopt_hip.h; values from closure_generic) ------------------------
+
+// df/dc at c, where f = closure_generic(s, coef, c) is passed in (the exp-wrapped value when EXP_WRAP is set)
+template <typename T>
+__device__ __forceinline__ T closure_dc(const ClosureSpec& s, const T* __restrict__ coef, T c, T f) {
+  T d = T(0);
+  if (s.kind == PDEOPT_CL_POLY) {
+    for (int k = s.n - 1; k >= 1; --k) d = d * c + T(k) * coef[k];
+  } else {
+    // d/dc sum_k a_k P_k(2c - 1) = 2 sum_k a_k P'_k(x),  P'_{k+1} = P'_{k-1} + (2k + 1) P_k
+    const T x = T(2) * c - T(1);
+    T pm = T(1), pc = x, dpm = T(0), dpc = T(1);
+    if (s.n > 1) d = coef[1];
+    for (int k = 1; k + 1 < s.n; ++k) {
+      const T pn = (T(2 * k + 1) * x * pc - T(k) * pm) / T(k + 1);
+      const T dpn = dpm + T(2 * k + 1) * pc;
+      d += coef[k + 1] * dpn;
+      pm = pc;
+      pc = pn;
+      dpm = dpc;
+      dpc = dpn;
+    }
+    d *= T(2);
+  }
+  if (s.flags & PDEOPT_CL_LOGIT_PRIOR) d += T(1) / (c * (T(1) - c));
+  if (s.flags & PDEOPT_CL_MIX_ENTROPY) d += t_logit<T>(c);
+  if (s.flags & PDEOPT_CL_EXP_WRAP) d *= f;
+  return d;
+}
+
+// 1 / q of the Legendre recurrence below: a multiply per term instead of a division (the tangent kernel evaluates
+// the basis once per cell and tangent)
+__constant__ double kRecip[PDEOPT_CLOSURE_MAX_COEF] = {0.0,       1.0,       1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,
+                                                       1.0 / 6,   1.0 / 7,   1.0 / 8,  1.0 / 9,  1.0 / 10, 1.0 / 11,
+                                                       1.0 / 12,  1.0 / 13,  1.0 / 14, 1.0 / 15};
+
+// df/dcoef[k] at c: the basis function B_k(c) = c^k or P_k(2c - 1), times f under EXP_WRAP
+template <typename T>
+__device__ __forceinline__ T closure_dcoef(const ClosureSpec& s, int k, T c, T f) {
+  T b = T(1);
+  if (s.kind == PDEOPT_CL_POLY) {
+    for (int q = 0; q < k; ++q) b *= c;
+  } else if (k > 0) {
+    const T x = T(2) * c - T(1);
+    T pm = T(1);
+    b = x;
+    for (int q = 2; q <= k; ++q) {
+      const T pn = (T(2 * q - 1) * x * b - T(q - 1) * pm) * T(kRecip[q]);
+      pm = b;
+      b = pn;
+    }
+  }
+  if (s.flags & PDEOPT_CL_EXP_WRAP) b *= f;
+  return b;
+}
+
+template <typename T>
+struct SensArgs {
+  const T* y;  // state [(1 + P) B][nx][ny]
+  T* k;        // slopes, same layout; the kernel writes the tangent block
+  const EnvParams<T>* ep;
+  ClosureSpec mu, mob;
+  int nx, ny, B, P;
+  T rhx, rhy, rhx2, rhy2;
+  int role[kMaxSens];
+  int index[kMaxSens];
+};
+
+// Output tile TR x TC; the stencil reads u on a 2-cell ring (mu at the 1-cell ring needs lap u there).
+constexpr int kTR = 16, kTC = 32, kR2 = kTR + 4, kC2 = kTC + 4, kR1 = kTR + 2, kC1 = kTC + 2;
+
+// periodic index of g in [-2, n + kTC + 1]: one add or subtract, the division only on grids smaller than a tile
+__device__ __forceinline__ int wrap_idx(int g, int n) {
+  g = g < 0 ? g + n : (g >= n ? g - n : g);
+  if ((unsigned)g >= (unsigned)n) g = ((g % n) + n) % n;
+  return g;
+}
+
+// Tangent-linear right-hand side of Cahn-Hilliard with FD derivatives (cahn_hilliard.py:89-109):
+//   f       = div( avg(D(u)) grad(mu) ),                 mu = mu_h(u) - kappa lap u
+//   dmu_j   = mu_h'(u) du_j + dmu_h/dp_j - kappa lap du_j
+//   dD_j    = D'(u) du_j + dD/dp_j
+//   df_j    = div( avg(dD_j) grad(mu) + avg(D) grad(dmu_j) )
+// with the forward kernel's primitives: 5-point Laplacian, face gradients, face averages, face divergence.
+// One workgroup per (tile, trajectory): u, mu, D and their derivatives are formed once, then the P tangents are
+// streamed through the same LDS tile (each tangent field read once, each tangent slope written once).
+template <typename T>
+__global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
+  __shared__ T su[kR2 * kC2], sdu[kR2 * kC2];
+  __shared__ T smu[kR1 * kC1], smuh[kR1 * kC1], sD[kR1 * kC1], smu1[kR1 * kC1], sD1[kR1 * kC1];
+  __shared__ T sdmu[kR1 * kC1], sdD[kR1 * kC1];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.z;
+  const int i0 = blockIdx.y * kTR, j0 = blockIdx.x * kTC;
+  const int nx = a.nx, ny = a.ny;
+  const int64_t cells = (int64_t)nx * ny;
+  const EnvParams<T>& ep = a.ep[b];
+  const T kappa = ep.kappa;
+  const T* __restrict__ u = a.y + (int64_t)b * cells;
+  for (int q = tid; q < kR2 * kC2; q += 256) {
+    const int r = q / kC2, c = q - r * kC2;
+    su[q] = u[(int64_t)wrap_idx(i0 + r - 2, nx) * ny + wrap_idx(j0 + c - 2, ny)];
+  }
+  __syncthreads();
+  for (int q = tid; q < kR1 * kC1; q += 256) {
+    const int r = q / kC1, c = q - r * kC1;
+    const int o = (r + 1) * kC2 + (c + 1);
+    const T uc = su[o];
+    const T lap = (su[o + kC2] - T(2) * uc + su[o - kC2]) * a.rhx2 + (su[o + 1] - T(2) * uc + su[o - 1]) * a.rhy2;
+    const T muh = closure_generic<T>(a.mu, ep.mu, uc);
+    const T D = closure_generic<T>(a.mob, ep.mob, uc);
+    smuh[q] = muh;
+    smu[q] = muh - kappa * lap;
+    sD[q] = D;
+    smu1[q] = closure_dc<T>(a.mu, ep.mu, uc, muh);
+    sD1[q] = closure_dc<T>(a.mob, ep.mob, uc, D);
+  }
+  for (int j = 0; j < a.P; ++j) {
+    __syncthreads();  // the previous tangent's readers are done with sdu / sdmu / sdD (and the base arrays are written)
+    const int64_t env = (int64_t)a.B + (int64_t)j * a.B + b;
+    const T* __restrict__ du = a.y + env * cells;
+    for (int q = tid; q < kR2 * kC2; q += 256) {
+      const int r = q / kC2, c = q - r * kC2;
+      sdu[q] = du[(int64_t)wrap_idx(i0 + r - 2, nx) * ny + wrap_idx(j0 + c - 2, ny)];
+    }
+    __syncthreads();
+    const bool on_mu = a.role[j] == PDEOPT_SENS_MU;
+    const int kc = a.index[j];
+    for (int q = tid; q < kR1 * kC1; q += 256) {
+      const int r = q / kC1, c = q - r * kC1;
+      const int o = (r + 1) * kC2 + (c + 1);
+      const T uc = su[o], d = sdu[o];
+      const T lap = (sdu[o + kC2] - T(2) * d + sdu[o - kC2]) * a.rhx2 + (sdu[o + 1] - T(2) * d + sdu[o - 1]) * a.rhy2;
+      T dmu = smu1[q] * d - kappa * lap;
+      T dD = sD1[q] * d;
+      if (on_mu) dmu += closure_dcoef<T>(a.mu, kc, uc, smuh[q]);
+      else dD += closure_dcoef<T>(a.mob, kc, uc, sD[q]);
+      sdmu[q] = dmu;
+      sdD[q] = dD;
+    }
+    __syncthreads();
+    T* __restrict__ out = a.k + env * cells;
+    for (int q = tid; q < kTR * kTC; q += 256) {
+      const int r = q / kTC, c = q - r * kTC;
+      const int gi = i0 + r, gj = j0 + c;
+      if (gi >= nx || gj >= ny) continue;
+      const int o = (r + 1) * kC1 + (c + 1);
+      const int xp = o + kC1, xm = o - kC1, yp = o + 1, ym = o - 1;
+      // faces +-1/2 along x (axis 0) and y (axis 1): avg(dD) grad(mu) + avg(D) grad(dmu)
+      const T fxp = T(0.5) * (sdD[o] + sdD[xp]) * ((smu[xp] - smu[o]) * a.rhx) +
+                    T(0.5) * (sD[o] + sD[xp]) * ((sdmu[xp] - sdmu[o]) * a.rhx);
+      const T fxm = T(0.5) * (sdD[xm] + sdD[o]) * ((smu[o] - smu[xm]) * a.rhx) +
+                    T(0.5) * (sD[xm] + sD[o]) * ((sdmu[o] - sdmu[xm]) * a.rhx);
+      const T fyp = T(0.5) * (sdD[o] + sdD[yp]) * ((smu[yp] - smu[o]) * a.rhy) +
+                    T(0.5) * (sD[o] + sD[yp]) * ((sdmu[yp] - sdmu[o]) * a.rhy);
+      const T fym = T(0.5) * (sdD[ym] + sdD[o]) * ((smu[o] - smu[ym]) * a.rhy) +
+                    T(0.5) * (sD[ym] + sD[o]) * ((sdmu[o] - sdmu[ym]) * a.rhy);
+      out[(int64_t)gi * ny + gj] = (fxp - fxm) * a.rhx + (fyp - fym) * a.rhy;
+    }
+  }
+}
+
+template <typename T>
+__global__ void sens_axpy_kernel(T* __restrict__ y, const T* __restrict__ k, T dt, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    y[i] += dt * k[i];
+}
+
+// ---- Gauss-Newton sums at one save point ------------------------------------------------------------------------
+// Rows: 0 = the residual r = v - pred, 1..P = the tangent dpred_j; pred = snap + theta (y - snap) (the lerp of
+// pdeopt_get_interpolated) or y.  Output index of the product of rows i <= j:
+//   i = 0:  j (0 = sum r^2, j = sum r dpred_j);   i >= 1: 1 + P + the upper-triangle index of (i - 1, j - 1).
+constexpr int kGnThreads = 256, kGnCellsPerThread = 8, kGnCellsPerBlock = kGnThreads * kGnCellsPerThread;
+
+__host__ __device__ __forceinline__ int gn_index(int i, int j, int P) {
+  if (i == 0) return j;
+  const int a = i - 1, c = j - 1;
+  return 1 + P + a * P - a * (a - 1) / 2 + (c - a);
+}
+
+template <typename T>
+__device__ __forceinline__ double gn_row(const T* __restrict__ y, const T* __restrict__ snap, const T* __restrict__ v,
+                                         int row, int b, int B, int64_t cells, int64_t c, T theta, int interp) {
+  const int64_t env = row == 0 ? b : (int64_t)B + (int64_t)(row - 1) * B + b;
+  const int64_t o = env * cells + c;
+  const T p = interp ? snap[o] + theta * (y[o] - snap[o]) : y[o];
+  return row == 0 ? (double)v[(int64_t)b * cells + c] - (double)p : (double)p;
+}
+
+// grid (blocks per field, B, 1 + P): block (x, b, i) sums row i times rows j >= i over its 2048 cells of trajectory
+// b; the block total (fixed-order tree in LDS) goes to partial[b][index][x].  No atomics: repeated calls give the
+// same bits.
+template <typename T>
+__global__ __launch_bounds__(kGnThreads) void sens_gn_partial_kernel(const T* __restrict__ y, const T* __restrict__ snap,
+                                                                   const T* __restrict__ v, double* __restrict__ partial,
+                                                                   int B, int P, int64_t cells, T theta, int interp) {
+  __shared__ double red[kGnThreads];
+  const int tid = threadIdx.x, blk = blockIdx.x, b = blockIdx.y, i = blockIdx.z;
+  const int nblk = gridDim.x, K = 1 + P + P * (P + 1) / 2;
+  const int64_t c0 = (int64_t)blk * kGnCellsPerBlock + tid;
+  double av[kGnCellsPerThread];
+#pragma unroll
+  for (int m = 0; m < kGnCellsPerThread; ++m) {
+    const int64_t c = c0 + (int64_t)m * kGnThreads;
+    av[m] = c < cells ? gn_row<T>(y, snap, v, i, b, B, cells, c, theta, interp) : 0.0;
+  }
+  for (int j = i; j <= P; ++j) {
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < kGnCellsPerThread; ++m) {
+      const int64_t c = c0 + (int64_t)m * kGnThreads;
+      if (c < cells) acc += av[m] * (j == i ? av[m] : gn_row<T>(y, snap, v, j, b, B, cells, c, theta, interp));
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = kGnThreads / 2; s > 0; s >>= 1) {
+      if (tid < s) red[tid] += red[tid + s];
+      __syncthreads();
+    }
+    if (tid == 0) partial[((int64_t)b * K + gn_index(i, j, P)) * nblk + blk] = red[0];
+    __syncthreads();
+  }
+}
+
+// sums[b][k] = sum over blocks of partial[b][k][.], in block order
+__global__ void sens_gn_final_kernel(const double* __restrict__ partial, double* __restrict__ sums, int n, int nblk) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  const double* p = partial + (int64_t)q * nblk;
+  double s = 0.0;
+  for (int x = 0; x < nblk; ++x) s += p[x];
+  sums[q] = s;
+}
+
+int check_sens(pdeopt_ctx* ctx) {
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  const Sens* s = ctx->sens;
+  if (!s) return fail(ctx, PDEOPT_ESTATE, "pdeopt_sens_configure has not been called");
+  if ((int64_t)(1 + s->P) * s->B != ctx->prob.batch)
+    return fail(ctx, PDEOPT_ESTATE, "batch %d is not (1 + P) B = %d: configure again before pdeopt_sens_configure",
+                ctx->prob.batch, (1 + s->P) * s->B);
+  for (int j = 0; j < s->P; ++j) {
+    const pdeopt_closure& cl = s->role[j] == PDEOPT_SENS_MU ? ctx->prob.mu : ctx->prob.mob;
+    if (s->index[j] >= cl.n)
+      return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: coefficient %d of a closure with %d coefficients", j, s->index[j], cl.n);
+  }
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int launch_tangent_rhs(pdeopt_ctx* ctx) {
+  const pdeopt_problem& p = ctx->prob;
+  const Sens& s = *ctx->sens;
+  SensArgs<T> a{};
+  a.y = static_cast<const T*>(ctx->Y);
+  a.k = static_cast<T*>(ctx->TA);
+  a.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
+  a.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
+  a.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  a.nx = p.nx;
+  a.ny = p.ny;
+  a.B = s.B;
+  a.P = s.P;
+  a.rhx = T(1.0 / p.hx);
+  a.rhy = T(1.0 / p.hy);
+  a.rhx2 = T(1.0 / (p.hx * p.hx));
+  a.rhy2 = T(1.0 / (p.hy * p.hy));
+  for (int j = 0; j < s.P; ++j) {
+    a.role[j] = s.role[j];
+    a.index[j] = s.index[j];
+  }
+  const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, s.B);
+  hipLaunchKernelGGL(sens_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  ctx->n_stage_launches++;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+// TA = (f(y_base), J_f du_j + df/dp_j) for the whole batch
+int sens_slopes(pdeopt_ctx* ctx) {
+  int rc;
+  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  ctx->win_lo = 0;
+  ctx->win_n = ctx->sens->B;
+  rc = launch_rhs_slope(ctx, ctx->Y, ctx->TA, 0.0);
+  ctx->win_n = ctx->prob.batch;
+  if (rc) return rc;
+  return ctx->prob.dtype == PDEOPT_F32 ? launch_tangent_rhs<float>(ctx) : launch_tangent_rhs<double>(ctx);
+}
+
+template <typename T>
+int euler_update(pdeopt_ctx* ctx, double dt) {
+  const int64_t n = (int64_t)ctx->env_elems * ctx->prob.batch;
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(sens_axpy_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<T*>(ctx->Y),
+                     static_cast<const T*>(ctx->TA), (T)dt, n);
+  ctx->n_stage_launches++;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int gn_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
+  Sens& s = *ctx->sens;
+  const int64_t cells = (int64_t)ctx->prob.nx * ctx->prob.ny;
+  const int K = 1 + s.P + s.P * (s.P + 1) / 2;
+  const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
+  const size_t pbytes = (size_t)s.B * K * nblk * sizeof(double), sbytes = (size_t)s.B * K * sizeof(double);
+  int rc;
+  if (s.partial && s.partial_bytes < pbytes) {
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(s.partial);
+    s.partial = nullptr;
+  }
+  if ((rc = ensure_buffer(ctx, (void**)&s.partial, pbytes))) return rc;
+  s.partial_bytes = std::max(s.partial_bytes, pbytes);
+  if (s.sums && s.sums_bytes < sbytes) {
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(s.sums);
+    s.sums = nullptr;
+  }
+  if ((rc = ensure_buffer(ctx, (void**)&s.sums, sbytes))) return rc;
+  s.sums_bytes = std::max(s.sums_bytes, sbytes);
+  const T* v = static_cast<const T*>(s.data) + (int64_t)frame * s.B * cells;
+  hipLaunchKernelGGL(sens_gn_partial_kernel<T>, dim3(nblk, s.B, 1 + s.P), dim3(kGnThreads), 0, ctx->stream,
+                     static_cast<const T*>(ctx->Y), static_cast<const T*>(ctx->SNAP), v, s.partial, s.B, s.P, cells,
+                     (T)theta, interp);
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  const int n = s.B * K;
+  hipLaunchKernelGGL(sens_gn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.partial, s.sums, n, nblk);
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, s.sums, sbytes, hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+}  // namespace
+
+void sens_destroy(pdeopt_ctx* ctx) {
+  Sens* s = ctx->sens;
+  if (!s) return;
+  for (void* p : {s->data, (void*)s->partial, (void*)s->sums})
+    if (p) (void)hipFree(p);
+  delete s;
+  ctx->sens = nullptr;
+}
+
+}  // namespace pdeopt
+
+using namespace pdeopt;
+
+extern "C" {
+
+int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32_t* roles, const int32_t* coef_index) {
+  if (!ctx || (n_params > 0 && (!roles || !coef_index))) return PDEOPT_EINVAL;
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  const pdeopt_problem& p = ctx->prob;
+  if (p.equation != PDEOPT_EQ_CAHN_HILLIARD || p.derivs != PDEOPT_DERIVS_FD || ctx->halo || p.nz > 1)
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D Cahn-Hilliard equation with derivs=\"fd\"");
+  if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT)
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities need closures of the in-kernel family (POLY / LEGENDRE), not run-time-compiled ones");
+  if (n_traj < 1 || n_params < 1 || n_params > kMaxSens)
+    return fail(ctx, PDEOPT_EINVAL, "n_traj = %d, n_params = %d (1 .. %d)", n_traj, n_params, kMaxSens);
+  if ((int64_t)(1 + n_params) * n_traj != p.batch)
+    return fail(ctx, PDEOPT_EINVAL, "batch %d is not (1 + n_params) n_traj = %d", p.batch, (1 + n_params) * n_traj);
+  for (int j = 0; j < n_params; ++j) {
+    if (roles[j] != PDEOPT_SENS_MU && roles[j] != PDEOPT_SENS_MOB)
+      return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: unknown role %d", j, roles[j]);
+    const pdeopt_closure& cl = roles[j] == PDEOPT_SENS_MU ? p.mu : p.mob;
+    if (coef_index[j] < 0 || coef_index[j] >= cl.n)
+      return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: coefficient %d of a closure with %d coefficients", j, coef_index[j], cl.n);
+  }
+  if (!ctx->sens) ctx->sens = new Sens();
+  Sens& s = *ctx->sens;
+  s.B = n_traj;
+  s.P = n_params;
+  for (int j = 0; j < n_params; ++j) {
+    s.role[j] = roles[j];
+    s.index[j] = coef_index[j];
+  }
+  return PDEOPT_OK;
+}
+
+int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out) {
+  if (!ctx) return PDEOPT_EINVAL;
+  int rc = check_sens(ctx);
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if ((rc = sens_slopes(ctx))) return rc;
+  if (host_out)
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps) {
+  (void)t0;  // the Cahn-Hilliard right-hand side is autonomous
+  if (!ctx) return PDEOPT_EINVAL;
+  int rc = check_sens(ctx);
+  if (rc) return rc;
+  if (n_substeps < 0 || !(dt > 0)) return fail(ctx, PDEOPT_EINVAL, "n_substeps = %lld, dt = %g", (long long)n_substeps, dt);
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->tsit5_pending = false;
+  ctx->tsit5_fsal_valid = false;
+  if (integrator == PDEOPT_INT_IMEX) {
+    if (!ctx->aux[PDEOPT_AUX_IMEX_SYMBOL].dev)
+      return fail(ctx, PDEOPT_ESTATE, "IMEX needs the IMEX_SYMBOL aux field (fourier_symbol)");
+    if (!imex_fused_supported(ctx) || ctx->imex_per_env)
+      return fail(ctx, PDEOPT_EINVAL, "IMEX sensitivities need the hand-written FFT passes (power-of-two grids 64..1024, "
+                                      "one shared implicit operator)");
+    if ((rc = imex_fused_prepare(ctx, dt))) return rc;
+  } else if (integrator != PDEOPT_INT_EULER) {
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities support the IMEX and Euler integrators (got %d)", integrator);
+  }
+  ctx->last_kernel = integrator == PDEOPT_INT_IMEX ? "sens_tangent_rhs+imex_fused_lds_fft" : "sens_tangent_rhs+euler";
+  for (int64_t s = 0; s < n_substeps; ++s) {
+    if ((rc = sens_slopes(ctx))) return rc;
+    ctx->win_lo = 0;
+    ctx->win_n = ctx->prob.batch;
+    if (integrator == PDEOPT_INT_IMEX) rc = imex_fused_passes(ctx, dt);
+    else rc = ctx->prob.dtype == PDEOPT_F32 ? euler_update<float>(ctx, dt) : euler_update<double>(ctx, dt);
+    if (rc) return rc;
+  }
+  return PDEOPT_OK;
+}
+
+int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {
+  if (!ctx || n_frames < 1 || !host) return PDEOPT_EINVAL;
+  int rc = check_sens(ctx);
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  Sens& s = *ctx->sens;
+  const size_t bytes = (size_t)n_frames * s.B * ctx->prob.nx * ctx->prob.ny * ctx->esize;
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (s.data && s.data_bytes < bytes) {
+    (void)hipFree(s.data);
+    s.data = nullptr;
+  }
+  if ((rc = ensure_buffer(ctx, &s.data, bytes))) return rc;
+  s.data_bytes = std::max(s.data_bytes, bytes);
+  s.n_frames = n_frames;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.data, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out) {
+  if (!ctx || !out) return PDEOPT_EINVAL;
+  int rc = check_sens(ctx);
+  if (rc) return rc;
+  Sens& s = *ctx->sens;
+  if (!s.data || frame < 0 || frame >= s.n_frames)
+    return fail(ctx, PDEOPT_EINVAL, "frame %d of %d uploaded (pdeopt_sens_set_data)", frame, s.n_frames);
+  if (interp && !ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return ctx->prob.dtype == PDEOPT_F32 ? gn_accumulate<float>(ctx, frame, theta, interp, out)
+                                       : gn_accumulate<double>(ctx, frame, theta, interp, out);
+}
+
+}  // extern "C"

@@ -754,8 +754,9 @@ int imex_cols(pdeopt_ctx* ctx, StrangFused& sf) {
   return PDEOPT_OK;
 }
 
+// twiddle tables, work field and implicit multiplier of the IMEX passes for step dt (kept while dt and A hold)
 template <typename T>
-int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
   if (!ctx->strang_fused) ctx->strang_fused = new StrangFused();
   StrangFused& sf = *ctx->strang_fused;
   const pdeopt_problem& p = ctx->prob;
@@ -814,6 +815,41 @@ int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   }
   if (ctx->imex_per_env && !sf.imex_sym_real)
     return fail(ctx, PDEOPT_EINVAL, "per-environment IMEX scales need a real fourier_symbol");
+  return PDEOPT_OK;
+}
+
+// y += dt L^-1 k on the window [win_lo, win_lo + win_n): row pass, column pass (multiplier), inverse row pass
+template <typename T>
+int imex_passes_t(pdeopt_ctx* ctx, StrangFused& sf, double dt) {
+  const pdeopt_problem& p = ctx->prob;
+  int r = PDEOPT_OK;
+  switch (p.ny) {
+#define X(NN) case NN: r = imex_rows<T, NN>(ctx, sf, true, dt); break;
+    PDEOPT_FFT_SIZES(X)
+#undef X
+  }
+  if (r) return r;
+  switch (p.nx) {
+#define X(NN) case NN: r = imex_cols<T, NN>(ctx, sf); break;
+    PDEOPT_FFT_SIZES(X)
+#undef X
+  }
+  if (r) return r;
+  switch (p.ny) {
+#define X(NN) case NN: r = imex_rows<T, NN>(ctx, sf, false, dt); break;
+    PDEOPT_FFT_SIZES(X)
+#undef X
+  }
+  return r;
+}
+
+template <typename T>
+int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+  int rc = imex_prepare_t<T>(ctx, dt);
+  if (rc) return rc;
+  StrangFused& sf = *ctx->strang_fused;
+  const pdeopt_problem& p = ctx->prob;
+  const int64_t cells = (int64_t)p.nx * p.ny;
   // group by group (an even number of environments each): state + slope + spectrum work field are 12 B/cell
   int group = p.batch;
   if (ctx->opt_group_envs > 0) {
@@ -831,24 +867,7 @@ int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   auto substep = [&]() -> int {
     int r;
     if ((r = launch_rhs_slope(ctx, ctx->Y, ctx->TA, 0.0))) return r;
-    switch (p.ny) {
-#define X(NN) case NN: r = imex_rows<T, NN>(ctx, sf, true, dt); break;
-      PDEOPT_FFT_SIZES(X)
-#undef X
-    }
-    if (r) return r;
-    switch (p.nx) {
-#define X(NN) case NN: r = imex_cols<T, NN>(ctx, sf); break;
-      PDEOPT_FFT_SIZES(X)
-#undef X
-    }
-    if (r) return r;
-    switch (p.ny) {
-#define X(NN) case NN: r = imex_rows<T, NN>(ctx, sf, false, dt); break;
-      PDEOPT_FFT_SIZES(X)
-#undef X
-    }
-    return r;
+    return imex_passes_t<T>(ctx, sf, dt);
   };
   // Two groups in flight on two streams (PDEOPT_OPT_GROUP_STREAMS = 2 only).  Round 2 measured 1445 vs 1443
   // env-steps/s at 2 x 8 environments against 1 x 16, and slower at 2 x 16 / 2 x 4; round 3 re-measured after the
@@ -914,6 +933,15 @@ bool imex_fused_supported(const pdeopt_ctx* ctx) {
 
 int advance_imex_fused(pdeopt_ctx* ctx, double dt, int64_t n) {
   return ctx->prob.dtype == PDEOPT_F32 ? imex_fused_t<float>(ctx, dt, n) : imex_fused_t<double>(ctx, dt, n);
+}
+
+int imex_fused_prepare(pdeopt_ctx* ctx, double dt) {
+  return ctx->prob.dtype == PDEOPT_F32 ? imex_prepare_t<float>(ctx, dt) : imex_prepare_t<double>(ctx, dt);
+}
+
+int imex_fused_passes(pdeopt_ctx* ctx, double dt) {
+  StrangFused& sf = *ctx->strang_fused;
+  return ctx->prob.dtype == PDEOPT_F32 ? imex_passes_t<float>(ctx, sf, dt) : imex_passes_t<double>(ctx, sf, dt);
 }
 
 bool strang_fused_supported(const pdeopt_ctx* ctx) {

@@ -367,6 +367,39 @@ class HipEngine:
         )
         return out
 
+    # -- forward-mode sensitivities (batch = (1 + P) B: trajectories, then tangent j of trajectory b at B + j B + b) --
+    def sens_configure(self, n_traj: int, params):
+        """``params``: P pairs ``(role, coefficient index)`` with role ``L.SENS_MU`` or ``L.SENS_MOB``"""
+        roles = np.ascontiguousarray([int(r) for r, _ in params], dtype=np.int32)
+        index = np.ascontiguousarray([int(k) for _, k in params], dtype=np.int32)
+        self._check(self._lib.pdeopt_sens_configure(self._h, int(n_traj), len(roles), roles.ctypes.data_as(C.c_void_p),
+                                                    index.ctypes.data_as(C.c_void_p)))
+        self.sens_shape = (int(n_traj), len(roles))
+
+    def sens_rhs(self) -> np.ndarray:
+        """base slopes and tangent slopes of the current state, ``(batch, nx, ny)``"""
+        out = np.empty((self.batch,) + self.state_shape, dtype=self.dtype)
+        self._check(self._lib.pdeopt_sens_rhs(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sens_advance(self, integrator: int, dt: float, n_substeps: int, t0: float = 0.0):
+        self._check(self._lib.pdeopt_sens_advance(self._h, int(integrator), float(t0), float(dt), int(n_substeps)))
+
+    def sens_set_data(self, frames):
+        """observed frames ``(n_frames, B, nx, ny)``, uploaded once per fit"""
+        a = np.ascontiguousarray(np.asarray(frames, dtype=self.dtype))
+        if a.ndim != 4 or a.shape[1] != self.sens_shape[0] or a.shape[2:] != self.state_shape:
+            raise ValueError(f"frames of shape {a.shape}: expected (n_frames, {self.sens_shape[0]}) + {self.state_shape}")
+        self._check(self._lib.pdeopt_sens_set_data(self._h, a.shape[0], a.ctypes.data_as(C.c_void_p)))
+
+    def sens_accumulate(self, frame: int, theta: float = 1.0, interp: bool = False) -> np.ndarray:
+        """``(B, 1 + P + P (P + 1) / 2)`` fp64 sums: r^2, r dpred_j, dpred_i dpred_j (i <= j) at one save point"""
+        B, P = self.sens_shape
+        out = np.empty((B, 1 + P + P * (P + 1) // 2), dtype=np.float64)
+        self._check(self._lib.pdeopt_sens_accumulate(self._h, int(frame), float(theta), int(bool(interp)),
+                                                     out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def reduce(self, op: int) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.float64)
         self._check(self._lib.pdeopt_reduce(self._h, int(op), out.ctypes.data_as(C.c_void_p)))

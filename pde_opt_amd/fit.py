@@ -1,0 +1,377 @@
+"""Fitting closure coefficients to trajectories: the machinery behind ``PDEModel.train`` / ``residuals`` / ``mse``
+(the reference's pde_opt/pde_model.py:138-460).
+
+The reference differentiates the solve with diffrax's ``ForwardMode`` adjoint and hands the residuals to
+optimistix (``LevenbergMarquardt`` / ``BFGS``).  Here the forward-mode tangents run on the GPU next to the
+trajectories (``pdeopt_sens_advance``) and only the Gauss-Newton sums come back to the host
+(``pdeopt_sens_accumulate``); the optimisers below work on those sums.
+"""
+
+from __future__ import annotations
+
+import dataclasses
+import math
+from typing import Callable, List, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib as L
+from .integrate import constant_step_plan
+from .numerics.closures import UnsupportedClosureError
+from .numerics.functions.legendre import ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials
+
+RTOL = ATOL = 1e-8  # optimistix tolerances of the reference's train (pde_model.py:398-401, 428-431)
+
+# closure classes whose coefficient arrays are trainable, and the constructor argument that holds their role
+_ROLES = {"mu": L.SENS_MU, "D": L.SENS_MOB}
+
+
+# ---- parameters -----------------------------------------------------------------------------------------------------
+
+
+@dataclasses.dataclass
+class ParamMap:
+    """The trainable leaves of ``opt_parameters`` as one flat vector ``p``.  Entry ``j`` is coefficient ``index[j]``
+    of the closure in role ``role[j]``.  ``closure_desc()`` folds a polynomial ``prior_fn`` into the series, so the
+    kernel's coefficients are ``p`` plus a fixed offset; fitted closures are rebuilt from ``p`` itself (same class,
+    same ``prior_fn``), which keeps the offset out of the returned values."""
+
+    keys: List[str]
+    templates: list
+    sizes: List[int]
+
+    @classmethod
+    def of(cls, opt_parameters: dict) -> "ParamMap":
+        keys, templates, sizes = [], [], []
+        for key, value in opt_parameters.items():
+            if key not in _ROLES or not isinstance(value, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
+                raise ValueError(
+                    f"opt_parameters[{key!r}]: only the coefficient arrays of ChemicalPotentialLegendrePolynomials / "
+                    "DiffusionLegendrePolynomials in the 'mu' and 'D' roles are trainable (kappa and other scalars would "
+                    "move the implicit operator of the solver); pass them in other_parameters")
+            keys.append(key)
+            templates.append(value)
+            sizes.append(len(value.expansion.params))
+        if not keys:
+            raise ValueError("opt_parameters holds no trainable closure")
+        return cls(keys, templates, sizes)
+
+    @property
+    def size(self) -> int:
+        return sum(self.sizes)
+
+    def all_params(self) -> List[Tuple[int, int]]:
+        return [(_ROLES[k], i) for k, n in zip(self.keys, self.sizes) for i in range(n)]
+
+    def active(self) -> np.ndarray:
+        """entries whose tangent is not identically zero.  mu's constant coefficient is not: only grad mu enters the
+        Cahn-Hilliard right-hand side, so its tangent is never solved for (its Jacobian column is exactly 0)"""
+        return np.array([not (role == L.SENS_MU and i == 0) for role, i in self.all_params()])
+
+    def sens_params(self) -> List[Tuple[int, int]]:
+        """the (role, coefficient) pairs of the tangents the GPU advances"""
+        return [q for q, a in zip(self.all_params(), self.active()) if a]
+
+    def expand(self, rdp, G):
+        """the sums of the active tangents as sums over all entries (zero for the inert ones)"""
+        act = np.nonzero(self.active())[0]
+        r = np.zeros(self.size)
+        g = np.zeros((self.size, self.size))
+        r[act] = rdp
+        g[np.ix_(act, act)] = G
+        return r, g
+
+    def flatten(self, params: dict) -> np.ndarray:
+        return np.concatenate([np.asarray(params[k].expansion.params, dtype=np.float64) for k in self.keys])
+
+    def build(self, p: np.ndarray) -> dict:
+        out, o = {}, 0
+        for key, tpl, n in zip(self.keys, self.templates, self.sizes):
+            coef = np.array(p[o:o + n], dtype=np.float64)
+            o += n
+            if isinstance(tpl, ChemicalPotentialLegendrePolynomials):
+                out[key] = ChemicalPotentialLegendrePolynomials(coef, tpl.prior_fn)
+            else:
+                out[key] = DiffusionLegendrePolynomials(coef)
+        return out
+
+
+def _leaves(obj) -> list:
+    """coefficient arrays of a closure, the array / number itself, or nothing (None, callables)"""
+    if obj is None:
+        return []
+    if isinstance(obj, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
+        return [np.asarray(obj.expansion.params, dtype=np.float64)]
+    if isinstance(obj, (int, float, np.ndarray, np.number)):
+        a = np.asarray(obj)
+        return [a.astype(np.float64)] if np.issubdtype(a.dtype, np.inexact) or isinstance(obj, float) else []
+    return []
+
+
+def regularization(parameters: dict, weights: dict, lambda_reg: float) -> float:
+    """``lambda sum_i w_i p_i^2`` over the coefficient arrays named in ``weights`` (pde_model.py:170-214); None
+    leaves are ignored"""
+    reg = 0.0
+    for key, w in weights.items():
+        for wl, pl in zip(_leaves(w), _leaves(parameters.get(key))):
+            reg += float(lambda_reg) * float(np.sum(wl * pl ** 2))
+    return reg
+
+
+def weight_vector(pmap: ParamMap, weights: dict) -> np.ndarray:
+    """the weights of the trainable entries, in ``p`` order (0 where ``weights`` names none)"""
+    w = []
+    for key, n in zip(pmap.keys, pmap.sizes):
+        leaves = _leaves(weights.get(key))
+        a = np.zeros(n)
+        if leaves:
+            src = np.broadcast_to(leaves[0], (n,)) if leaves[0].ndim == 0 else leaves[0][:n]
+            a[: len(src)] = src
+        w.append(a)
+    return np.concatenate(w)
+
+
+# ---- the sensitivity solve ------------------------------------------------------------------------------------------
+
+
+def walk_save_points(t0: float, t1: float, dt: float, ts: Sequence[float], advance: Callable, snapshot: Callable,
+                     visit: Callable):
+    """The constant-step plan and save-point logic of ``integrate.diffeqsolve`` (SaveAt(ts=...), linear dense
+    output): ``advance(dt, n, t)`` runs n substeps, ``snapshot()`` keeps the state at the start of a step that holds
+    a save point, ``visit(q, theta)`` is called at save point q with ``theta = None`` on a step edge, else the
+    position inside the last step."""
+    n_full, rem = constant_step_plan(t0, t1, dt)
+    total = n_full + (1 if rem > 0 else 0)
+
+    def edge(i):
+        return t1 if i >= total else t0 + i * dt
+
+    def steps(first, count):
+        full = max(0, min(first + count, n_full) - first)
+        if full:
+            advance(dt, full, t0 + first * dt)
+        if first + count > n_full and rem > 0:
+            advance(rem, 1, t0 + n_full * dt)  # the remainder step: another dt, another implicit multiplier
+
+    done, inside = 0, None
+    for q, tq in enumerate(float(t) for t in ts):
+        if tq <= t0 or total == 0:
+            k_end = 0
+        else:
+            k_end = min(total, max(1, int(math.ceil((tq - t0) / dt - 1e-9))))
+        if k_end == 0 or abs(edge(k_end) - tq) <= 1e-12 * max(1.0, abs(tq)):
+            steps(done, k_end - done)
+            done, inside = k_end, None
+            visit(q, None)
+        else:
+            a, b = edge(k_end - 1), edge(k_end)
+            if inside != k_end:
+                steps(done, k_end - 1 - done)
+                snapshot()
+                steps(k_end - 1, 1)
+                done, inside = k_end, k_end
+            visit(q, (tq - a) / (b - a))
+
+
+def _configure(eng, equation, solver, y0s, pmap_params, t0, t1):
+    B = y0s.shape[0]
+    P = len(pmap_params)
+    eng.configure(dtype=y0s.dtype, batch=(1 + P) * B, **equation._engine_problem())
+    equation._engine_upload(eng, t0, t1)
+    solver.configure_engine(eng, equation)
+    eng.sens_configure(B, pmap_params)
+    state = np.zeros(((1 + P) * B,) + y0s.shape[1:], dtype=y0s.dtype)
+    state[:B] = y0s  # the tangents start at zero: the initial states are data
+    eng.set_state(state)
+
+
+def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fields=False, frames_key=None, frames=None):
+    """Solve B trajectories and their P tangents through ``ts``.
+
+    ``frames`` ``(T - 1, B, nx, ny)``: the observed values at ``ts[1:]``; they are uploaded when ``frames_key``
+    differs from the engine's last upload.  Returns the Gauss-Newton sums per trajectory summed over the save points,
+    ``(B, 1 + P + P (P + 1) / 2)`` fp64 (None without frames), and with ``fields=True`` the states of all
+    ``(1 + P) B`` environments at every save point, ``(T, (1 + P) B, nx, ny)``."""
+    if solver.integrator not in (L.INT_IMEX, L.INT_EULER):
+        raise NotImplementedError("sensitivities support SemiImplicitFourierSpectral (IMEX) and Euler")
+    y0s = np.asarray(y0s)
+    if y0s.dtype not in (np.float32, np.float64):
+        y0s = y0s.astype(np.float64)
+    ts = np.asarray(ts, dtype=np.float64)
+    t0, t1 = float(ts[0]), float(ts[-1])
+    _configure(eng, equation, solver, y0s, sens_params, t0, t1)
+    if frames is not None and (frames_key is None or getattr(eng, "_sens_frames_key", None) != frames_key):
+        eng.sens_set_data(frames)
+        eng._sens_frames_key = frames_key
+    sums = [None]
+    out = []
+
+    def visit(q, theta):
+        if fields:
+            out.append(eng.get_state() if theta is None else eng.get_interpolated(theta))
+        if frames is not None and q >= 1:
+            s = eng.sens_accumulate(q - 1, 1.0 if theta is None else theta, theta is not None)
+            sums[0] = s if sums[0] is None else sums[0] + s
+
+    walk_save_points(t0, t1, float(dt0), ts,
+                     lambda dt, n, t: eng.sens_advance(solver.integrator, dt, n, t), eng.snapshot, visit)
+    return sums[0], (np.stack(out) if fields else None)
+
+
+def unpack_sums(sums: np.ndarray, P: int):
+    """``(sum r^2, sum_j r dpred_j [P], sum dpred_i dpred_j [P, P])`` of per-trajectory sums ``(B, K)``, summed over
+    the trajectories in order"""
+    tot = np.zeros(sums.shape[1])
+    for row in sums:
+        tot = tot + row
+    ssr = float(tot[0])
+    rdp = tot[1:1 + P].copy()
+    G = np.zeros((P, P))
+    iu = np.triu_indices(P)
+    G[iu] = tot[1 + P:]
+    G = G + np.triu(G, 1).T
+    return ssr, rdp, G
+
+
+# ---- optimisers -------------------------------------------------------------------------------------------------------
+
+
+@dataclasses.dataclass
+class Objective:
+    """What the optimisers need from a model: ``sums(p) -> (sum r^2, sum r dpred [P], sum dpred dpred^T [P, P])``
+    (a sensitivity solve), ``ssr(p) -> sum r^2`` (a forward solve), the number M of residual entries, and the
+    regularisation ``lambda sum w p^2``."""
+
+    sums: Callable
+    ssr: Callable
+    M: int
+    lambda_reg: float = 0.0
+    w: np.ndarray = None
+
+    def reg(self, p):
+        return float(self.lambda_reg * np.sum(self.w * p * p)) if self.w is not None else 0.0
+
+    def reg_grad(self, p):
+        return 2.0 * self.lambda_reg * self.w * p if self.w is not None else np.zeros_like(p)
+
+
+def _converged(p_old, p_new, f_old, f_new, rtol=RTOL, atol=ATOL):
+    dp = np.all(np.abs(p_new - p_old) <= atol + rtol * np.abs(p_new))
+    df = abs(f_new - f_old) <= atol + rtol * abs(f_new)
+    return bool(dp and df)
+
+
+def levenberg_marquardt(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL):
+    """Minimise ``1/2 (sum r^2 + reg^2)`` -- the objective optimistix.least_squares gives the residual pytree
+    ``(batch_residuals, reg)`` -- on the normal equations.  Jacobian of r: ``-dpred``; of reg: ``2 lambda w p``.
+    A column of zeros (mu's constant coefficient: grad of a constant is 0) leaves its entry where it started: the
+    damping keeps the system regular and its right-hand side is 0.  Returns ``(p, history of objectives)``; like the
+    reference's ``throw=False``, the last iterate when ``max_steps`` runs out."""
+    p = np.array(p0, dtype=np.float64)
+
+    def model(p):
+        ssr, rdp, G = obj.sums(p)
+        reg, g = obj.reg(p), obj.reg_grad(p)
+        f = 0.5 * (ssr + reg * reg)
+        JTJ = G + np.outer(g, g)
+        JTr = -rdp + g * reg
+        return f, JTJ, JTr
+
+    f, JTJ, JTr = model(p)
+    hist = [f]
+    lam = 1e-3 * max(float(np.max(np.diag(JTJ))), 1e-300)
+    for _ in range(max_steps):
+        if not np.all(np.isfinite(JTr)) or not math.isfinite(f):
+            break
+        A = JTJ + lam * np.eye(len(p))
+        step = -np.linalg.solve(A, JTr)
+        pred_red = -(JTr @ step + 0.5 * step @ JTJ @ step)
+        p_new = p + step
+        f_new, JTJ_new, JTr_new = model(p_new)
+        rho = (f - f_new) / pred_red if pred_red > 0 else -1.0
+        if math.isfinite(f_new) and f_new <= f and rho > 0:
+            done = _converged(p, p_new, f, f_new, rtol, atol)
+            p, f, JTJ, JTr = p_new, f_new, JTJ_new, JTr_new
+            hist.append(f)
+            lam *= 1.0 / 3.0 if rho > 0.75 else (1.0 if rho > 0.25 else 2.0)
+            if done:
+                break
+        else:
+            lam *= 4.0
+            if np.all(np.abs(step) <= atol + rtol * np.abs(p)):
+                break
+    return p, hist
+
+
+def bfgs(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL):
+    """Minimise ``mean(r^2) + reg`` (the reference's ``mse`` under optimistix.BFGS).  Gradient
+    ``-(2 / M) sum r dpred + 2 lambda w p`` from the tangents; trial points of the backtracking (Armijo) line search
+    are forward-only solves.  The inverse-Hessian estimate starts from the pseudo-inverse of the Gauss-Newton
+    Hessian the same tangents give at the starting point (``2 / M sum dpred dpred^T + 2 lambda diag w``), so a
+    direction with no gradient (mu's constant coefficient) is never moved."""
+    p = np.array(p0, dtype=np.float64)
+
+    def fg(p):
+        ssr, rdp, G = obj.sums(p)
+        return ssr / obj.M + obj.reg(p), -(2.0 / obj.M) * rdp + obj.reg_grad(p), G
+
+    def f_only(p):
+        return obj.ssr(p) / obj.M + obj.reg(p)
+
+    f, g, G = fg(p)
+    w = obj.w if obj.w is not None else np.zeros_like(p)
+    H = np.linalg.pinv((2.0 / obj.M) * G + np.diag(2.0 * obj.lambda_reg * w), rcond=1e-12, hermitian=True)
+    hist = [f]
+    for _ in range(max_steps):
+        if not np.all(np.isfinite(g)) or not math.isfinite(f):
+            break
+        d = -(H @ g)
+        slope = float(g @ d)
+        if slope >= 0:  # not a descent direction: restart from the gradient
+            d, slope = -g, -float(g @ g)
+        if slope == 0.0:
+            break
+        a = 1.0
+        f_new = f_only(p + a * d)
+        while not (math.isfinite(f_new) and f_new <= f + 1e-4 * a * slope) and a > 1e-9:
+            a *= 0.5
+            f_new = f_only(p + a * d)
+        if a <= 1e-9:  # no decrease along d: the objective is at its floating-point floor
+            break
+        p_new = p + a * d
+        f_new, g_new, _ = fg(p_new)
+        s, y = p_new - p, g_new - g
+        sy = float(s @ y)
+        if sy > 0:
+            rho = 1.0 / sy
+            V = np.eye(len(p)) - rho * np.outer(s, y)
+            H = V @ H @ V.T + rho * np.outer(s, s)
+        done = _converged(p, p_new, f, f_new, rtol, atol)
+        p, f, g = p_new, f_new, g_new
+        hist.append(f)
+        if done:
+            break
+    return p, hist
+
+
+def reject_unsupported(model):
+    """the configurations the sensitivity path covers: 2-D periodic Cahn-Hilliard, FD derivatives, IMEX or Euler"""
+    from .numerics.equations.phase_field import CahnHilliard2DPeriodic
+    from .numerics.solvers import Euler, SemiImplicitFourierSpectral
+
+    if model.equation_type is not CahnHilliard2DPeriodic:
+        raise NotImplementedError(f"train / residuals sensitivities support CahnHilliard2DPeriodic only, not "
+                                  f"{model.equation_type.__name__}")
+    if model.solver_type not in (SemiImplicitFourierSpectral, Euler):
+        raise NotImplementedError(f"train / residuals sensitivities support the SemiImplicitFourierSpectral and Euler "
+                                  f"solvers, not {model.solver_type.__name__}")
+
+
+def check_equation(equation):
+    if getattr(equation, "derivs", "fd") != "fd":
+        raise NotImplementedError('train sensitivities support derivs="fd" only (the tangent kernel differentiates the '
+                                  'finite-difference right-hand side)')
+    for d in (equation._mu_desc, equation._mob_desc):
+        if d.kind == L.CL_JIT:
+            raise UnsupportedClosureError("train sensitivities need closures of the in-kernel family (polynomial / "
+                                          "Legendre series with the logit, mixing-entropy and exp forms)")

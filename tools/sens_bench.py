@@ -1,0 +1,100 @@
+"""Cost of forward-mode sensitivities against the forward solve (PDEModel.train's inner loop).
+
+For each case (grid, trajectories B, dtype, P tangents) it times, with device events:
+  fwd_ms_per_substep   a forward IMEX substep of the B trajectories (pdeopt_advance)
+  sens_ms_per_substep  a substep of the B trajectories + their P tangents (pdeopt_sens_advance)
+and, on the host clock around calls that end in a device synchronise,
+  lm_iter_ms           one Levenberg-Marquardt iteration: a sensitivity solve through 2 save points with the
+                       Gauss-Newton sums, plus the normal-equation solve (lm_substeps substeps per solve)
+Prints one JSON line.  usage: python tools/sens_bench.py [--quick]
+"""
+import json
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, ".")
+import pde_opt_amd as P  # noqa: E402
+from pde_opt_amd import _lib as L  # noqa: E402
+from pde_opt_amd import fit  # noqa: E402
+from pde_opt_amd.numerics.functions.legendre import ChemicalPotentialLegendrePolynomials as ChemLeg  # noqa: E402
+from pde_opt_amd.numerics.functions.legendre import DiffusionLegendrePolynomials as DiffLeg  # noqa: E402
+
+KAPPA, DT = 0.002, 1e-6
+
+
+def logit(c):
+    return np.log(c / (1.0 - c))
+
+
+def closures(P_):
+    """P = 3: mu a1, a2 + D c0;  P = 7: mu a1..a5 + D c0, c1 (mu's a0 has no tangent)"""
+    if P_ == 3:
+        return {"mu": ChemLeg(np.array([0.0, -3.0, 0.1]), logit), "D": DiffLeg(np.array([0.0]))}
+    return {"mu": ChemLeg(np.array([0.0, -3.0, 0.1, 0.0, 0.0, 0.0]), logit), "D": DiffLeg(np.array([0.0, 0.1]))}
+
+
+def timed(eng, fn, reps):
+    fn()  # warm-up: code objects, multipliers, buffers
+    eng.timer_start()
+    for _ in range(reps):
+        fn()
+    return eng.timer_stop() / reps
+
+
+def case(n, B, dtype, P_, nsub, lm_substeps):
+    dom = P.Domain((n, n), ((0.0, 1.0), (0.0, 1.0)), "dimensionless")
+    opt = closures(P_)
+    eq = P.CahnHilliard2DPeriodic(dom, KAPPA, **opt)
+    solver = P.SemiImplicitFourierSpectral(A=0.5, fourier_symbol=eq.fourier_symbol)
+    rng = np.random.default_rng(0)
+    y0s = np.clip(0.5 + 0.05 * rng.standard_normal((B, n, n)), 0.05, 0.95).astype(dtype)
+    pm = fit.ParamMap.of(opt)
+    sp = pm.sens_params()
+    assert len(sp) == P_
+
+    fwd = P.HipEngine()
+    fwd.configure(dtype=dtype, batch=B, **eq._engine_problem())
+    eq._engine_upload(fwd, 0.0, 1.0)
+    solver.configure_engine(fwd, eq)
+    fwd.set_state(y0s)
+    t_fwd = timed(fwd, lambda: fwd.advance(L.INT_IMEX, DT, nsub), 3) / nsub
+
+    sens = P.HipEngine()
+    fit._configure(sens, eq, solver, y0s, sp, 0.0, 1.0)
+    t_sens = timed(sens, lambda: sens.sens_advance(L.INT_IMEX, DT, nsub), 3) / nsub
+
+    ts = np.array([0.0, 0.5, 1.0]) * lm_substeps * DT
+    frames = np.stack([y0s, y0s]).astype(dtype)
+    key = object()
+
+    def lm_iteration():
+        s, _ = fit.sensitivity_solve(sens, eq, solver, y0s, ts, sp, dt0=DT, frames=frames, frames_key=key)
+        ssr, rdp, G = fit.unpack_sums(s, P_)
+        np.linalg.solve(G + 1e-3 * np.eye(P_), rdp)
+
+    lm_iteration()
+    t0 = time.perf_counter()
+    for _ in range(2):
+        lm_iteration()
+    t_lm = (time.perf_counter() - t0) / 2 * 1e3
+    return {"n": n, "B": B, "dtype": np.dtype(dtype).name, "P": P_, "fwd_ms_per_substep": t_fwd,
+            "sens_ms_per_substep": t_sens, "sens_over_fwd": t_sens / t_fwd, "lm_iter_ms": t_lm,
+            "lm_substeps": lm_substeps}
+
+
+def main():
+    quick = "--quick" in sys.argv
+    rows = []
+    for n, B, nsub, lm in ((128, 3, 200, 4040), (1024, 8, 20, 100)):
+        for dtype in (np.float32, np.float64):
+            for P_ in (3, 7):
+                if quick and (n > 128 or P_ > 3):
+                    continue
+                rows.append(case(n, B, dtype, P_, nsub, lm))
+    print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": rows}))
+
+
+if __name__ == "__main__":
+    main()
