@@ -460,7 +460,7 @@ int pdeopt_tsit5_solve_small(pdeopt_ctx* ctx, double t0, double t1, double dt0, 
 /* ---- forward-mode sensitivities of the Cahn-Hilliard solve (PDEModel.train / residuals, pde_opt/pde_model.py:138-460)
  * The reference differentiates diffeqsolve with diffrax's ForwardMode adjoint (pde_model.py:410-423) to fill the
  * Jacobian of its Levenberg-Marquardt fit.  Here the P tangent fields du/dp_j ride through the solver as extra
- * environments: configure the ctx with batch (1 + P) B (periodic 2-D Cahn-Hilliard, derivs "fd"), put the B
+ * environments: configure the ctx with batch (1 + P) B (periodic 2-D or 3-D Cahn-Hilliard, derivs "fd"), put the B
  * trajectories in environments [0, B) and tangent j of trajectory b in environment B + j B + b (zero at t0: the
  * initial states are data).  pdeopt_get_state / pdeopt_snapshot / pdeopt_get_interpolated read and interpolate the
  * tangents like any environment. */
@@ -468,12 +468,15 @@ typedef enum { PDEOPT_SENS_MU = 0, PDEOPT_SENS_MOB = 1 } pdeopt_sens_role;
 /* the P parameters: parameter j is coefficient coef_index[j] of the closure roles[j] (mu_h or D) */
 int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32_t* roles, const int32_t* coef_index);
 /* TA = the base slopes f(y) and the tangent slopes J_f(y) du_j + df/dp_j of the current state, copied to host_out
- * ([(1 + P) B][nx][ny], may be NULL).  The tangent-linear right-hand side of cahn_hilliard.py:89-109 */
+ * ([(1 + P) B][nx][ny], or [(1 + P) B][nx][ny][nz] in 3-D; may be NULL).  The tangent-linear right-hand side of
+ * cahn_hilliard.py:89-109 (2-D) and :180-200 (3-D) */
 int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out);
 /* n_substeps of state + tangents: IMEX (solvers.py:56-63: du_1 = du_0 + dt L^-1 [J_f du_0 + df/dp], the implicit
- * operator L shared by base and tangents) or Euler (du_1 = du_0 + dt dk).  Asynchronous like pdeopt_advance. */
+ * operator L shared by base and tangents; the hand-written FFT passes on power-of-two 2-D grids 64..1024, rocFFT's
+ * real transforms on other grids and in 3-D) or Euler (du_1 = du_0 + dt dk).  Asynchronous like pdeopt_advance. */
 int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps);
-/* the observed frames of a fit, uploaded once: host is [n_frames][B][nx][ny] in the problem dtype */
+/* the observed frames of a fit, uploaded once: host is [n_frames][B][nx][ny] (3-D: [n_frames][B][nx][ny][nz]) in the
+ * problem dtype */
 int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host);
 /* Gauss-Newton sums of one save point against data frame `frame`: pred = snapshot + theta (state - snapshot) when
  * interp != 0 (LocalLinearInterpolation, as pdeopt_get_interpolated), else the state; r = data - pred.  out is

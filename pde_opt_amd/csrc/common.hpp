@@ -339,6 +339,10 @@ int advance_imex_fused(pdeopt_ctx* ctx, double dt, int64_t n);
 // of step dt, then y += dt L^-1 TA over the window [win_lo, win_lo + win_n)
 int imex_fused_prepare(pdeopt_ctx* ctx, double dt);
 int imex_fused_passes(pdeopt_ctx* ctx, double dt);
+// the same split of the rocFFT IMEX step (spectral.hip; any grid, 3-D included): plans, work fields and the
+// half-spectrum multiplier of step dt, then y += dt L^-1 TA over the whole batch (r2c, multiply, c2r, axpy)
+int imex_rocfft_prepare(pdeopt_ctx* ctx, double dt);
+int imex_rocfft_solve(pdeopt_ctx* ctx, double dt);
 void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);

@@ -4,12 +4,15 @@
 //
 // Layout: the ctx is configured with batch (1 + P) B.  Environments [0, B) are the B trajectories; environment
 // B + j B + b holds the tangent du/dp_j of trajectory b.  Per substep
-//   IMEX   k = f(y) for the base block (launch_rhs_slope, the forward solve's own slope kernel),
-//          dk_j = J_f(y) du_j + df/dp_j for the tangent block (sens_tangent_rhs_kernel),
+//   IMEX   k = f(y) for the base block (launch_rhs_slope, the forward solve's own slope kernels),
+//          dk_j = J_f(y) du_j + df/dp_j for the tangent block (2-D: sens_tangent_rhs_kernel; 3-D: sens3d_dmu_kernel
+//          and sens3d_flux_kernel),
 //          y += dt L^-1 k over the whole (1 + P) B batch (the forward IMEX transforms): L = 1 + A dt fourier_symbol is
 //          linear and independent of the coefficients (kappa is not trainable), so the tangent of the step is the
-//          same implicit solve applied to the linearised slope -- 4 launches + 1.
-//   Euler  the same two slope launches, then y += dt k over the whole batch (3 launches).
+//          same implicit solve applied to the linearised slope.  2-D power-of-two grids 64..1024 run the hand-written
+//          FFT passes (4 launches + 1); other 2-D grids and the 3-D equation run the rocFFT real transforms, multiply
+//          and axpy of the forward rocFFT IMEX loop.  None of the launch counts depends on P.
+//   Euler  the same slope launches, then y += dt k over the whole batch.
 #include <vector>
 
 #include "closures.hpp"
@@ -23,7 +26,7 @@ struct Sens {
   int B = 0, P = 0;
   int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB
   int index[kMaxSens] = {};  // coefficient k of that closure
-  void* data = nullptr;      // [n_frames][B][nx][ny] observed frames, problem dtype
+  void* data = nullptr;      // [n_frames][B][*spatial] observed frames, problem dtype
   int n_frames = 0;
   size_t data_bytes = 0;
   double* partial = nullptr;  // [B][K][nblk] per-block sums of the accumulation
@@ -91,7 +94,7 @@ __device__ __forceinline__ T closure_dcoef(const ClosureSpec& s, int k, T c, T f
 
 template <typename T>
 struct SensArgs {
-  const T* y;  // state [(1 + P) B][nx][ny]
+  const T* y;  // state [(1 + P) B][nx][ny] (2-D)
   T* k;        // slopes, same layout; the kernel writes the tangent block
   const EnvParams<T>* ep;
   ClosureSpec mu, mob;
@@ -195,6 +198,117 @@ __global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
   }
 }
 
+// ---- 3-D: CahnHilliard3DPeriodic.rhs_fd (cahn_hilliard.py:180-200), fields [env][nx][ny][nz] with z contiguous ----
+// Two passes, as the forward ch3d_mu_kernel / ch3d_stage_kernel (stencil_generic.hpp), with their primitives in their
+// order: 7-point Laplacian, face gradients, face averages, face divergence.
+//   pass 1  dmu_j = mu_h'(u) du_j + [role_j == MU] dmu_h/dp_j - kappa lap7(du_j)  -> the work field KS at the tangent
+//           environments (the base slope launch has left the base mu in KS[0, B))
+//   pass 2  df_j = div( avg_face(dD_j) grad_face(mu) + avg_face(D) grad_face(dmu_j) ),  dD_j = D'(u) du_j + [MOB] dD/dp_j
+// One thread per cell and trajectory, flat over the cells (a 32^3 field fills every lane); the values of u at the
+// stencil points (mu_h', or D and D' at the 7 points) are formed once and the thread then walks the P tangents.
+template <typename T>
+struct Sens3Args {
+  const T* y;  // state [(1 + P) B][nx][ny][nz]
+  T* w;        // work field KS, same layout: base mu in [0, B), pass 1 writes dmu_j at the tangent environments
+  T* k;        // slopes TA, same layout; pass 2 writes the tangent block
+  const EnvParams<T>* ep;
+  ClosureSpec mu, mob;
+  int nx, ny, nz, B, P;
+  T rhx, rhy, rhz, rhx2, rhy2, rhz2;
+  int role[kMaxSens];
+  int index[kMaxSens];
+};
+
+// offsets (within one environment) of cell c and its 6 periodic neighbours: 0 = c, then +x, -x, +y, -y, +z, -z
+template <typename T>
+__device__ __forceinline__ void nb7(const Sens3Args<T>& a, int c, int o[7]) {
+  const int nz = a.nz, ny = a.ny, nx = a.nx;
+  const int k = c % nz, q = c / nz;
+  const int j = q % ny, i = q / ny;
+  const int syz = ny * nz;
+  o[0] = c;
+  o[1] = c + (i + 1 == nx ? -(nx - 1) * syz : syz);
+  o[2] = c + (i == 0 ? (nx - 1) * syz : -syz);
+  o[3] = c + (j + 1 == ny ? -(ny - 1) * nz : nz);
+  o[4] = c + (j == 0 ? (ny - 1) * nz : -nz);
+  o[5] = c + (k + 1 == nz ? -(nz - 1) : 1);
+  o[6] = c + (k == 0 ? nz - 1 : -1);
+}
+
+// grid (cells / 256, B)
+template <typename T>
+__global__ __launch_bounds__(256) void sens3d_dmu_kernel(Sens3Args<T> a) {
+  const int cells = a.nx * a.ny * a.nz;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (c >= cells) return;
+  int o[7];
+  nb7<T>(a, c, o);
+  const EnvParams<T>& ep = a.ep[b];
+  const T kappa = ep.kappa;
+  const T uc = a.y[(int64_t)b * cells + c];
+  const T muh = closure_generic<T>(a.mu, ep.mu, uc);
+  const T mu1 = closure_dc<T>(a.mu, ep.mu, uc, muh);
+  for (int j = 0; j < a.P; ++j) {
+    const int64_t env = (int64_t)a.B + (int64_t)j * a.B + b;
+    const T* __restrict__ du = a.y + env * cells;
+    const T d = du[o[0]];
+    const T lap = (du[o[1]] - T(2) * d + du[o[2]]) * a.rhx2 + (du[o[3]] - T(2) * d + du[o[4]]) * a.rhy2 +
+                  (du[o[5]] - T(2) * d + du[o[6]]) * a.rhz2;
+    T dmu = mu1 * d - kappa * lap;
+    if (a.role[j] == PDEOPT_SENS_MU) dmu += closure_dcoef<T>(a.mu, a.index[j], uc, muh);
+    a.w[env * cells + c] = dmu;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sens3d_flux_kernel(Sens3Args<T> a) {
+  const int cells = a.nx * a.ny * a.nz;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (c >= cells) return;
+  int o[7];
+  nb7<T>(a, c, o);
+  const EnvParams<T>& ep = a.ep[b];
+  const T* __restrict__ u = a.y + (int64_t)b * cells;
+  const T* __restrict__ m = a.w + (int64_t)b * cells;
+  T uu[7], D[7], D1[7], mm[7];
+#pragma unroll
+  for (int q = 0; q < 7; ++q) {
+    uu[q] = u[o[q]];
+    mm[q] = m[o[q]];
+    D[q] = closure_generic<T>(a.mob, ep.mob, uu[q]);
+    D1[q] = closure_dc<T>(a.mob, ep.mob, uu[q], D[q]);
+  }
+  const T rh[3] = {a.rhx, a.rhy, a.rhz};
+  for (int j = 0; j < a.P; ++j) {
+    const int64_t env = (int64_t)a.B + (int64_t)j * a.B + b;
+    const T* __restrict__ du = a.y + env * cells;
+    const T* __restrict__ dm = a.w + env * cells;
+    const bool on_mob = a.role[j] == PDEOPT_SENS_MOB;
+    const int kc = a.index[j];
+    T dD[7], dmu[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+      dmu[q] = dm[o[q]];
+      dD[q] = D1[q] * du[o[q]];
+      if (on_mob) dD[q] += closure_dcoef<T>(a.mob, kc, uu[q], D[q]);
+    }
+    // faces +-1/2 along x, y, z: avg(dD) grad(mu) + avg(D) grad(dmu), then the face divergence
+    T kk = T(0);
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+      const int p = 1 + 2 * ax, n = 2 + 2 * ax;
+      const T fp = T(0.5) * (dD[0] + dD[p]) * ((mm[p] - mm[0]) * rh[ax]) +
+                   T(0.5) * (D[0] + D[p]) * ((dmu[p] - dmu[0]) * rh[ax]);
+      const T fm = T(0.5) * (dD[n] + dD[0]) * ((mm[0] - mm[n]) * rh[ax]) +
+                   T(0.5) * (D[n] + D[0]) * ((dmu[0] - dmu[n]) * rh[ax]);
+      kk += (fp - fm) * rh[ax];
+    }
+    a.k[env * cells + c] = kk;
+  }
+}
+
 template <typename T>
 __global__ void sens_axpy_kernel(T* __restrict__ y, const T* __restrict__ k, T dt, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -267,6 +381,12 @@ __global__ void sens_gn_final_kernel(const double* __restrict__ partial, double*
   sums[q] = s;
 }
 
+// cells of one environment: nx ny, or nx ny nz for the 3-D equation
+inline int64_t sens_cells(const pdeopt_ctx* ctx) {
+  const pdeopt_problem& p = ctx->prob;
+  return (int64_t)p.nx * p.ny * (p.nz > 1 ? p.nz : 1);
+}
+
 int check_sens(pdeopt_ctx* ctx) {
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   const Sens* s = ctx->sens;
@@ -311,6 +431,43 @@ int launch_tangent_rhs(pdeopt_ctx* ctx) {
   return PDEOPT_OK;
 }
 
+// the two 3-D passes over the tangent block; the base slope launch has left the base mu in KS[0, B)
+template <typename T>
+int launch_tangent_rhs3d(pdeopt_ctx* ctx) {
+  const pdeopt_problem& p = ctx->prob;
+  const Sens& s = *ctx->sens;
+  int rc;
+  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+  Sens3Args<T> a{};
+  a.y = static_cast<const T*>(ctx->Y);
+  a.w = static_cast<T*>(ctx->KS);
+  a.k = static_cast<T*>(ctx->TA);
+  a.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
+  a.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
+  a.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  a.nx = p.nx;
+  a.ny = p.ny;
+  a.nz = p.nz;
+  a.B = s.B;
+  a.P = s.P;
+  a.rhx = T(1.0 / p.hx);
+  a.rhy = T(1.0 / p.hy);
+  a.rhz = T(1.0 / p.hz);
+  a.rhx2 = T(1.0 / (p.hx * p.hx));
+  a.rhy2 = T(1.0 / (p.hy * p.hy));
+  a.rhz2 = T(1.0 / (p.hz * p.hz));
+  for (int j = 0; j < s.P; ++j) {
+    a.role[j] = s.role[j];
+    a.index[j] = s.index[j];
+  }
+  const dim3 grid((unsigned)((sens_cells(ctx) + 255) / 256), s.B);
+  hipLaunchKernelGGL(sens3d_dmu_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  hipLaunchKernelGGL(sens3d_flux_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  ctx->n_stage_launches += 2;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
 // TA = (f(y_base), J_f du_j + df/dp_j) for the whole batch
 int sens_slopes(pdeopt_ctx* ctx) {
   int rc;
@@ -320,7 +477,9 @@ int sens_slopes(pdeopt_ctx* ctx) {
   rc = launch_rhs_slope(ctx, ctx->Y, ctx->TA, 0.0);
   ctx->win_n = ctx->prob.batch;
   if (rc) return rc;
-  return ctx->prob.dtype == PDEOPT_F32 ? launch_tangent_rhs<float>(ctx) : launch_tangent_rhs<double>(ctx);
+  const bool f32 = ctx->prob.dtype == PDEOPT_F32;
+  if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D) return f32 ? launch_tangent_rhs3d<float>(ctx) : launch_tangent_rhs3d<double>(ctx);
+  return f32 ? launch_tangent_rhs<float>(ctx) : launch_tangent_rhs<double>(ctx);
 }
 
 template <typename T>
@@ -337,7 +496,7 @@ int euler_update(pdeopt_ctx* ctx, double dt) {
 template <typename T>
 int gn_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
   Sens& s = *ctx->sens;
-  const int64_t cells = (int64_t)ctx->prob.nx * ctx->prob.ny;
+  const int64_t cells = sens_cells(ctx);
   const int K = 1 + s.P + s.P * (s.P + 1) / 2;
   const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
   const size_t pbytes = (size_t)s.B * K * nblk * sizeof(double), sbytes = (size_t)s.B * K * sizeof(double);
@@ -390,8 +549,11 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
   if (!ctx || (n_params > 0 && (!roles || !coef_index))) return PDEOPT_EINVAL;
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   const pdeopt_problem& p = ctx->prob;
-  if (p.equation != PDEOPT_EQ_CAHN_HILLIARD || p.derivs != PDEOPT_DERIVS_FD || ctx->halo || p.nz > 1)
-    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D Cahn-Hilliard equation with derivs=\"fd\"");
+  const bool ch2d = p.equation == PDEOPT_EQ_CAHN_HILLIARD && p.nz <= 1, ch3d = p.equation == PDEOPT_EQ_CAHN_HILLIARD_3D;
+  if (!(ch2d || ch3d) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D or 3-D Cahn-Hilliard equation with derivs=\"fd\"");
+  if (ch3d && sens_cells(ctx) > (int64_t)INT32_MAX / 2)
+    return fail(ctx, PDEOPT_EINVAL, "3-D sensitivities index cells in 32 bits (%dx%dx%d)", p.nx, p.ny, p.nz);
   if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT)
     return fail(ctx, PDEOPT_EINVAL, "sensitivities need closures of the in-kernel family (POLY / LEGENDRE), not run-time-compiled ones");
   if (n_traj < 1 || n_params < 1 || n_params > kMaxSens)
@@ -437,25 +599,37 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
+  bool fused = false;
   if (integrator == PDEOPT_INT_IMEX) {
     if (!ctx->aux[PDEOPT_AUX_IMEX_SYMBOL].dev)
       return fail(ctx, PDEOPT_ESTATE, "IMEX needs the IMEX_SYMBOL aux field (fourier_symbol)");
-    if (!imex_fused_supported(ctx) || ctx->imex_per_env)
-      return fail(ctx, PDEOPT_EINVAL, "IMEX sensitivities need the hand-written FFT passes (power-of-two grids 64..1024, "
-                                      "one shared implicit operator)");
-    if ((rc = imex_fused_prepare(ctx, dt))) return rc;
+    if (ctx->imex_per_env)
+      return fail(ctx, PDEOPT_EINVAL, "IMEX sensitivities need one implicit operator shared by the batch (no per-environment "
+                                      "IMEX scales)");
+    // the hand-written FFT passes where they exist (power-of-two 2-D grids 64..1024), rocFFT's real transforms elsewhere
+    fused = imex_fused_supported(ctx);
+    if ((rc = fused ? imex_fused_prepare(ctx, dt) : imex_rocfft_prepare(ctx, dt))) return rc;
   } else if (integrator != PDEOPT_INT_EULER) {
     return fail(ctx, PDEOPT_EINVAL, "sensitivities support the IMEX and Euler integrators (got %d)", integrator);
   }
-  ctx->last_kernel = integrator == PDEOPT_INT_IMEX ? "sens_tangent_rhs+imex_fused_lds_fft" : "sens_tangent_rhs+euler";
   for (int64_t s = 0; s < n_substeps; ++s) {
     if ((rc = sens_slopes(ctx))) return rc;
     ctx->win_lo = 0;
     ctx->win_n = ctx->prob.batch;
-    if (integrator == PDEOPT_INT_IMEX) rc = imex_fused_passes(ctx, dt);
-    else rc = ctx->prob.dtype == PDEOPT_F32 ? euler_update<float>(ctx, dt) : euler_update<double>(ctx, dt);
+    if (integrator == PDEOPT_INT_IMEX && fused) {
+      rc = imex_fused_passes(ctx, dt);
+    } else if (integrator == PDEOPT_INT_IMEX) {
+      rc = imex_rocfft_solve(ctx, dt);
+      ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls; rocFFT may run more than one kernel per transform)
+    } else {
+      rc = ctx->prob.dtype == PDEOPT_F32 ? euler_update<float>(ctx, dt) : euler_update<double>(ctx, dt);
+    }
     if (rc) return rc;
   }
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  // after the loop: the base slope launches name their own kernel
+  ctx->last_kernel = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : "sens_tangent_rhs";
+  ctx->last_kernel += integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : "+imex_rocfft_r2c");
   return PDEOPT_OK;
 }
 
@@ -465,7 +639,7 @@ int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   Sens& s = *ctx->sens;
-  const size_t bytes = (size_t)n_frames * s.B * ctx->prob.nx * ctx->prob.ny * ctx->esize;
+  const size_t bytes = (size_t)n_frames * s.B * sens_cells(ctx) * ctx->esize;
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if (s.data && s.data_bytes < bytes) {
     (void)hipFree(s.data);

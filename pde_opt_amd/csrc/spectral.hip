@@ -310,18 +310,14 @@ __global__ void axpy_real_kernel(T* __restrict__ y, const T* __restrict__ r, T d
   for (; i < n; i += st) y[i] += dt * r[i];
 }
 
-// IMEX on real <-> hermitian transforms.  The reference runs full complex transforms on the real
-// field (cahn_hilliard.py:72-73) and keeps `.real` of the result (solvers.py:63).  For a real input F
-// is hermitian, so  Re ifft(F m) = ifft(F m_h)  with  m_h(k) = (m(k) + conj(m(-k))) / 2 : the
-// symmetrised multiplier on the half-spectrum reproduces the reference for ANY (also non-even,
-// complex) fourier_symbol while moving half the bytes through rocFFT.
+// plans, work fields and the half-spectrum multiplier of step dt (kept while dt and A hold)
 template <typename T>
-int imex_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
+  if (!ctx->spectral) ctx->spectral = new Spectral();
   Spectral& sp = *ctx->spectral;
   const pdeopt_problem& p = ctx->prob;
   const int nzz = p.nz > 1 ? p.nz : 1;
   const int64_t cells = (int64_t)p.nx * p.ny * nzz;
-  const int64_t total = cells * p.batch;
   int rc;
   if ((rc = ensure_real_plans(ctx))) return rc;
   const int64_t hc = sp.half_cells;
@@ -355,14 +351,39 @@ int imex_t(pdeopt_ctx* ctx, double dt, int64_t n) {
     sp.mult_dt = dt;
     sp.mult_A = ctx->imex_A;
   }
+  return PDEOPT_OK;
+}
+
+// y += dt Re ifftn(fftn(TA) m) over the whole batch: r2c, multiply, c2r, axpy
+template <typename T>
+int imex_rocfft_solve_t(pdeopt_ctx* ctx, double dt) {
+  Spectral& sp = *ctx->spectral;
+  const pdeopt_problem& p = ctx->prob;
+  const int nzz = p.nz > 1 ? p.nz : 1;
+  const int64_t total = (int64_t)p.nx * p.ny * nzz * p.batch;
+  const int64_t hc = sp.half_cells;
+  int rc;
+  if ((rc = real_fft_exec(ctx, true, ctx->TA, sp.hbuf))) return rc;
+  hipLaunchKernelGGL((spectral_mul_kernel<T, false>), dim3(grid_for(hc), p.batch), dim3(256), 0,
+                     ctx->stream, (C2<T>*)sp.hbuf, (const C2<T>*)sp.hmult, nullptr, hc);
+  if ((rc = real_fft_exec(ctx, false, sp.hbuf, ctx->TA))) return rc;
+  hipLaunchKernelGGL(axpy_real_kernel<T>, dim3(grid_for(total)), dim3(256), 0, ctx->stream,
+                     (T*)ctx->Y, (const T*)ctx->TA, (T)dt, total);
+  return PDEOPT_OK;
+}
+
+// IMEX on real <-> hermitian transforms.  The reference runs full complex transforms on the real
+// field (cahn_hilliard.py:72-73) and keeps `.real` of the result (solvers.py:63).  For a real input F
+// is hermitian, so  Re ifft(F m) = ifft(F m_h)  with  m_h(k) = (m(k) + conj(m(-k))) / 2 : the
+// symmetrised multiplier on the half-spectrum reproduces the reference for ANY (also non-even,
+// complex) fourier_symbol while moving half the bytes through rocFFT.
+template <typename T>
+int imex_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+  int rc;
+  if ((rc = imex_rocfft_prepare_t<T>(ctx, dt))) return rc;
   for (int64_t s = 0; s < n; ++s) {
     if ((rc = launch_rhs(ctx, ctx->Y, ctx->TA, 0.0))) return rc;
-    if ((rc = real_fft_exec(ctx, true, ctx->TA, sp.hbuf))) return rc;
-    hipLaunchKernelGGL((spectral_mul_kernel<T, false>), dim3(grid_for(hc), p.batch), dim3(256), 0,
-                       ctx->stream, (C2<T>*)sp.hbuf, (const C2<T>*)sp.hmult, nullptr, hc);
-    if ((rc = real_fft_exec(ctx, false, sp.hbuf, ctx->TA))) return rc;
-    hipLaunchKernelGGL(axpy_real_kernel<T>, dim3(grid_for(total)), dim3(256), 0, ctx->stream,
-                       (T*)ctx->Y, (const T*)ctx->TA, (T)dt, total);
+    if ((rc = imex_rocfft_solve_t<T>(ctx, dt))) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   ctx->last_kernel += "+imex_rocfft_r2c";
@@ -687,6 +708,14 @@ int advance_imex(pdeopt_ctx* ctx, double, double dt, int64_t n) {
   int rc = ensure_plans(ctx);
   if (rc) return rc;
   return ctx->prob.dtype == PDEOPT_F32 ? imex_t<float>(ctx, dt, n) : imex_t<double>(ctx, dt, n);
+}
+
+int imex_rocfft_prepare(pdeopt_ctx* ctx, double dt) {
+  return ctx->prob.dtype == PDEOPT_F32 ? imex_rocfft_prepare_t<float>(ctx, dt) : imex_rocfft_prepare_t<double>(ctx, dt);
+}
+
+int imex_rocfft_solve(pdeopt_ctx* ctx, double dt) {
+  return ctx->prob.dtype == PDEOPT_F32 ? imex_rocfft_solve_t<float>(ctx, dt) : imex_rocfft_solve_t<double>(ctx, dt);
 }
 
 int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {

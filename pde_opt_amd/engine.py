@@ -377,7 +377,7 @@ class HipEngine:
         self.sens_shape = (int(n_traj), len(roles))
 
     def sens_rhs(self) -> np.ndarray:
-        """base slopes and tangent slopes of the current state, ``(batch, nx, ny)``"""
+        """base slopes and tangent slopes of the current state, ``(batch, *spatial)``"""
         out = np.empty((self.batch,) + self.state_shape, dtype=self.dtype)
         self._check(self._lib.pdeopt_sens_rhs(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
@@ -386,9 +386,9 @@ class HipEngine:
         self._check(self._lib.pdeopt_sens_advance(self._h, int(integrator), float(t0), float(dt), int(n_substeps)))
 
     def sens_set_data(self, frames):
-        """observed frames ``(n_frames, B, nx, ny)``, uploaded once per fit"""
+        """observed frames ``(n_frames, B, *spatial)``, uploaded once per fit"""
         a = np.ascontiguousarray(np.asarray(frames, dtype=self.dtype))
-        if a.ndim != 4 or a.shape[1] != self.sens_shape[0] or a.shape[2:] != self.state_shape:
+        if a.ndim != 2 + len(self.state_shape) or a.shape[1] != self.sens_shape[0] or a.shape[2:] != self.state_shape:
             raise ValueError(f"frames of shape {a.shape}: expected (n_frames, {self.sens_shape[0]}) + {self.state_shape}")
         self._check(self._lib.pdeopt_sens_set_data(self._h, a.shape[0], a.ctypes.data_as(C.c_void_p)))
 

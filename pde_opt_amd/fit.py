@@ -188,10 +188,11 @@ def _configure(eng, equation, solver, y0s, pmap_params, t0, t1):
 def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fields=False, frames_key=None, frames=None):
     """Solve B trajectories and their P tangents through ``ts``.
 
-    ``frames`` ``(T - 1, B, nx, ny)``: the observed values at ``ts[1:]``; they are uploaded when ``frames_key``
-    differs from the engine's last upload.  Returns the Gauss-Newton sums per trajectory summed over the save points,
-    ``(B, 1 + P + P (P + 1) / 2)`` fp64 (None without frames), and with ``fields=True`` the states of all
-    ``(1 + P) B`` environments at every save point, ``(T, (1 + P) B, nx, ny)``."""
+    ``y0s`` ``(B, *spatial)``, with ``spatial`` ``(nx, ny)`` or ``(nx, ny, nz)``.  ``frames`` ``(T - 1, B, *spatial)``:
+    the observed values at ``ts[1:]``; they are uploaded when ``frames_key`` differs from the engine's last upload.
+    Returns the Gauss-Newton sums per trajectory summed over the save points, ``(B, 1 + P + P (P + 1) / 2)`` fp64
+    (None without frames), and with ``fields=True`` the states of all ``(1 + P) B`` environments at every save point,
+    ``(T, (1 + P) B, *spatial)``."""
     if solver.integrator not in (L.INT_IMEX, L.INT_EULER):
         raise NotImplementedError("sensitivities support SemiImplicitFourierSpectral (IMEX) and Euler")
     y0s = np.asarray(y0s)
@@ -354,14 +355,22 @@ def bfgs(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL):
     return p, hist
 
 
+_SUPPORTED = "CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain"
+
+
 def reject_unsupported(model):
-    """the configurations the sensitivity path covers: 2-D periodic Cahn-Hilliard, FD derivatives, IMEX or Euler"""
-    from .numerics.equations.phase_field import CahnHilliard2DPeriodic
+    """the configurations the sensitivity path covers: periodic Cahn-Hilliard in 2-D or 3-D, FD derivatives, IMEX or
+    Euler.  The equation / domain pair is checked here, before any equation is built."""
+    from .numerics.equations.phase_field import CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
     from .numerics.solvers import Euler, SemiImplicitFourierSpectral
 
-    if model.equation_type is not CahnHilliard2DPeriodic:
-        raise NotImplementedError(f"train / residuals sensitivities support CahnHilliard2DPeriodic only, not "
+    dims = {CahnHilliard2DPeriodic: 2, CahnHilliard3DPeriodic: 3}.get(model.equation_type)
+    if dims is None:
+        raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
                                   f"{model.equation_type.__name__}")
+    if len(model.domain.points) != dims:
+        raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
+                                  f"{model.equation_type.__name__} on a {len(model.domain.points)}-D domain")
     if model.solver_type not in (SemiImplicitFourierSpectral, Euler):
         raise NotImplementedError(f"train / residuals sensitivities support the SemiImplicitFourierSpectral and Euler "
                                   f"solvers, not {model.solver_type.__name__}")

@@ -7,7 +7,8 @@ ignored: forward solves need no adjoint.
 
 ``train`` / ``residuals`` / ``mse`` / ``regularization`` (pde_model.py:138-460) fit closure coefficients to
 trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
-trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- 2-D periodic Cahn-Hilliard with FD derivatives, IMEX or Euler.
+trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D with FD derivatives, IMEX or
+Euler.
 ``optimize`` (pde_model.py:462-551) keeps raising: its objective is an arbitrary function of the solution.
 """
 
@@ -67,9 +68,9 @@ class PDEModel:
         return np.asarray(values) - pred[1:]
 
     def residuals(self, parameters, y0s__values, solver_parameters, ts, weights, lambda_reg, adjoint=None):
-        """``(batch_residuals (B, T - 1, nx, ny), reg)``: the B trajectories run as one batched solve"""
+        """``(batch_residuals (B, T - 1, *spatial), reg)``: the B trajectories run as one batched solve"""
         y0s, values = y0s__values
-        pred = self.solve(parameters, np.asarray(y0s), ts, solver_parameters, adjoint=adjoint)  # (T, B, nx, ny)
+        pred = self.solve(parameters, np.asarray(y0s), ts, solver_parameters, adjoint=adjoint)  # (T, B, *spatial)
         batch_residuals = np.asarray(values) - np.swapaxes(pred, 0, 1)[:, 1:]
         return batch_residuals, self.regularization(parameters, weights, lambda_reg)
 
@@ -88,8 +89,10 @@ class PDEModel:
         """Fit the closure coefficients in ``opt_parameters`` to ``data`` (pde_model.py:288-460).
 
         ``method="least_squares"``: Levenberg-Marquardt on the Gauss-Newton normal equations (the reference's
-        optimistix.LevenbergMarquardt with ForwardMode); ``"mse"``: BFGS on ``mean(r^2) + reg``.  Returns
-        ``{**fitted, **other_parameters}``; each fitted closure is the class it started as, with its ``prior_fn``."""
+        optimistix.LevenbergMarquardt with ForwardMode); ``"mse"``: BFGS on ``mean(r^2) + reg``.  ``data["ys"][i]``
+        is a state of shape ``spatial``: ``(nx, ny)`` for CahnHilliard2DPeriodic, ``(nx, ny, nz)`` for
+        CahnHilliard3DPeriodic.  Returns ``{**fitted, **other_parameters}``; each fitted closure is the class it
+        started as, with its ``prior_fn``."""
         fit.reject_unsupported(self)
         if method not in ("least_squares", "mse"):
             raise ValueError(f"method must be 'least_squares' or 'mse', got {method!r}")
@@ -97,7 +100,7 @@ class PDEModel:
         y0s, values, ts = stack_training_data(data, inds)
         equation0 = self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters})
         fit.check_equation(equation0)
-        frames = np.ascontiguousarray(np.swapaxes(values, 0, 1))  # (T - 1, B, nx, ny)
+        frames = np.ascontiguousarray(np.swapaxes(values, 0, 1))  # (T - 1, B, *spatial)
         frames_key = object()
         sens_params = pmap.sens_params()
         P = len(sens_params)

@@ -6,6 +6,8 @@ For each case (grid, trajectories B, dtype, P tangents) it times, with device ev
 and, on the host clock around calls that end in a device synchronise,
   lm_iter_ms           one Levenberg-Marquardt iteration: a sensitivity solve through 2 save points with the
                        Gauss-Newton sums, plus the normal-equation solve (lm_substeps substeps per solve)
+2-D cases run CahnHilliard2DPeriodic on [0, 1]^2; 3-D cases run CahnHilliard3DPeriodic on the box of
+docs/notebooks/optimization_3D.ipynb (edge 0.01 n), whose fit spans 40400 substeps per sensitivity solve at 32^3.
 Prints one JSON line.  usage: python tools/sens_bench.py [--quick]
 """
 import json
@@ -29,9 +31,12 @@ def logit(c):
 
 
 def closures(P_):
-    """P = 3: mu a1, a2 + D c0;  P = 7: mu a1..a5 + D c0, c1 (mu's a0 has no tangent)"""
+    """P = 3: mu a1, a2 + D c0;  P = 6: mu a1..a5 + D c0 (the 3-D notebook's fit);  P = 7: mu a1..a5 + D c0, c1
+    (mu's a0 has no tangent)"""
     if P_ == 3:
         return {"mu": ChemLeg(np.array([0.0, -3.0, 0.1]), logit), "D": DiffLeg(np.array([0.0]))}
+    if P_ == 6:
+        return {"mu": ChemLeg(np.array([0.0, -3.0, 0.1, 0.0, 0.0, 0.0]), logit), "D": DiffLeg(np.array([np.log(0.15)]))}
     return {"mu": ChemLeg(np.array([0.0, -3.0, 0.1, 0.0, 0.0, 0.0]), logit), "D": DiffLeg(np.array([0.0, 0.1]))}
 
 
@@ -43,13 +48,16 @@ def timed(eng, fn, reps):
     return eng.timer_stop() / reps
 
 
-def case(n, B, dtype, P_, nsub, lm_substeps):
-    dom = P.Domain((n, n), ((0.0, 1.0), (0.0, 1.0)), "dimensionless")
+def case(n, B, dtype, P_, nsub, lm_substeps, dims=2):
+    if dims == 2:
+        dom = P.Domain((n, n), ((0.0, 1.0), (0.0, 1.0)), "dimensionless")
+    else:
+        dom = P.Domain((n,) * 3, ((-0.005 * n, 0.005 * n),) * 3, "dimensionless")
     opt = closures(P_)
-    eq = P.CahnHilliard2DPeriodic(dom, KAPPA, **opt)
+    eq = (P.CahnHilliard2DPeriodic if dims == 2 else P.CahnHilliard3DPeriodic)(dom, KAPPA, **opt)
     solver = P.SemiImplicitFourierSpectral(A=0.5, fourier_symbol=eq.fourier_symbol)
     rng = np.random.default_rng(0)
-    y0s = np.clip(0.5 + 0.05 * rng.standard_normal((B, n, n)), 0.05, 0.95).astype(dtype)
+    y0s = np.clip(0.5 + 0.05 * rng.standard_normal((B,) + dom.points), 0.05, 0.95).astype(dtype)
     pm = fit.ParamMap.of(opt)
     sp = pm.sens_params()
     assert len(sp) == P_
@@ -79,7 +87,7 @@ def case(n, B, dtype, P_, nsub, lm_substeps):
     for _ in range(2):
         lm_iteration()
     t_lm = (time.perf_counter() - t0) / 2 * 1e3
-    return {"n": n, "B": B, "dtype": np.dtype(dtype).name, "P": P_, "fwd_ms_per_substep": t_fwd,
+    return {"n": n, "dims": dims, "B": B, "dtype": np.dtype(dtype).name, "P": P_, "fwd_ms_per_substep": t_fwd,
             "sens_ms_per_substep": t_sens, "sens_over_fwd": t_sens / t_fwd, "lm_iter_ms": t_lm,
             "lm_substeps": lm_substeps}
 
@@ -93,6 +101,12 @@ def main():
                 if quick and (n > 128 or P_ > 3):
                     continue
                 rows.append(case(n, B, dtype, P_, nsub, lm))
+    # 3-D: the notebook's fit (32^3 x 3, P = 6, 40400 substeps per sensitivity solve) and 64^3 x 3
+    for n, B, nsub, lm in ((32, 3, 200, 40400), (64, 3, 100, 4040)):
+        for dtype in (np.float32, np.float64):
+            if quick and n > 32:
+                continue
+            rows.append(case(n, B, dtype, 6, nsub // 4 if quick else nsub, 404 if quick else lm, dims=3))
     print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": rows}))
 
 
