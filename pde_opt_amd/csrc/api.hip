@@ -389,8 +389,6 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   else
     fill_env_params<double>(ctx);
   if ((rc = ensure_buffer(ctx, &ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
-  ctx->win_lo = 0;
-  ctx->win_n = pr->batch;
   ctx->imex_per_env = false;
   ctx->configured = true;
   return upload_env_params(ctx);
@@ -582,7 +580,7 @@ int pdeopt_rhs(pdeopt_ctx* ctx, double t, void* host_out) {
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes);
   if (rc) return rc;
-  if ((rc = launch_rhs(ctx, ctx->Y, ctx->TA, t))) return rc;
+  if ((rc = launch_rhs(ctx, whole_batch(ctx), ctx->Y, ctx->TA, t))) return rc;
   if (host_out) {
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->total_bytes, hipMemcpyDeviceToHost,
                                          ctx->stream));

@@ -144,8 +144,7 @@ struct pdeopt_ctx {
   bool tsit5_fsal_valid = false;
   bool slope_scaled = false;           // stage launches multiply k by EnvParams::kscale (per-environment dt)
   std::vector<double> kscale_prev;     // scale the FSAL slope K[0] of each environment carries
-  // smoothed-boundary equations: time of the RHS evaluation being launched and its scalar terms
-  double cur_t = 0.0;
+  // smoothed-boundary equations: scalar terms of the right-hand side at the time it is evaluated
   pdeopt_time_fn time_fn = nullptr;
   void* time_user = nullptr;
   double time_const[3] = {0.0, 0.0, 0.0};
@@ -167,11 +166,6 @@ struct pdeopt_ctx {
   int64_t n_stage_launches = 0;  // fused stencil+update launches issued so far
   int64_t opt_halo = 0;          // requested halo width of the NEXT configure (0 periodic, 4 or 8 padded)
   int halo = 0;                  // halo width of the configured layout
-  int pair_ext = 0;              // next PAIR_12 launch covers the tile + this many ring cells (halo-8 layout: 4)
-  void* pair_strip = nullptr;    // next PAIR_34 launch also writes the tile's halo strip here (fused pack)
-  const void* pair_recv = nullptr;  // next PAIR_12 launch reads the halo from these gathered strips (fused unpack)
-  int pair_nbr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const void* pair_peer[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // ... or from the neighbours' own strip buffers (peer-mapped exchange)
   void* halo_scratch = nullptr;  // single-rank loop-back buffer for pack/unpack
   void* halo_scratch2 = nullptr; // second loop-back strip (halo-8 loop: fused pack writes one while the next is read)
   size_t halo_scratch_bytes = 0, halo_scratch2_bytes = 0;
@@ -186,7 +180,9 @@ struct pdeopt_ctx {
   void* adaptive_blk = nullptr;   // save times + statistics + save slots of pdeopt_tsit5_solve_small
   size_t adaptive_cap = 0;
   int64_t opt_group_streams = 0;  // PDEOPT_OPT_GROUP_STREAMS
-  hipStream_t stream2 = nullptr;  // second stream of the two-groups-side-by-side schedule (created on first use)
+  // second stream of the two-groups-side-by-side schedule and its fork / join events (created on first use); only
+  // run_groups (groups.hpp) names them, launch helpers see the stream as part of a Window
+  hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int64_t opt_small_persist = 0; // whole-environment-step kernel for LDS-resident grids: 0 auto, 1 wherever it can, -1 never
   // Gaussian light spots of the GPE (pdeopt_set_gpe_spots)
@@ -195,8 +191,6 @@ struct pdeopt_ctx {
   std::vector<pdeopt_light_spot> spots_host;  // [batch][PDEOPT_MAX_SPOTS]
   double spots_x_first = 0.0, spots_y_first = 0.0;
   bool imex_per_env = false;  // some environment has imex_scale != 1: one environment per complex field
-  int launch_part = 0;        // tiles of the next stage-pair launches: 0 all, 1 interior, 2 edge (pdeopt_rk4_phase_part)
-  int win_lo = 0, win_n = 0;  // environment window the stage launchers operate on
   int64_t last_group_streams = 1;  // PDEOPT_CNT_GROUP_STREAMS
   int64_t last_groups = 1;    // environment groups of the last advance (PDEOPT_CNT_LAST_GROUPS)
   double imex_A = 0.5, ts_re = 1.0, ts_im = 0.0, strang_dx = 1.0;
@@ -251,22 +245,42 @@ int ensure_stream2(pdeopt_ctx* ctx);  // the ctx's second stream + fork / join e
 // api.hip: bring a time-dependent auxiliary field to local time t (no-op for static fields)
 int refresh_time_aux(pdeopt_ctx* ctx, int which, double t);
 inline bool has_time_aux(const pdeopt_ctx* ctx, int which) { return ctx->aux[which].fn != nullptr; }
-// where the next fused-unpack launch finds the strips of its 8 neighbours: slices of the gathered buffer (pair_recv +
-// rank * strip elements), or the neighbours' own buffers (pair_peer, peer-mapped exchange); all nullptr: no fused unpack
+
+// What a launch operates on: the environments [lo, lo + n) of the batch, on this stream.  Launch helpers pre-offset
+// their pointers by lo and size their grid by n; kernels see a batch of n.
+struct Window {
+  int lo, n;
+  hipStream_t stream;
+};
+inline Window whole_batch(const pdeopt_ctx* ctx) { return Window{0, ctx->prob.batch, ctx->stream}; }
+
+// What only the launches on a decomposed field's tile need (stage pairs, the single-pass Cahn-Hilliard RK4 kernel).
+// All zero: periodic field, or the halo is already in place and no strip is wanted.
+struct HaloIo {
+  int part = 0;                // tiles: 0 all, 1 interior, 2 edge (pdeopt_rk4_phase_part)
+  int ext = 0;                 // PAIR_12 covers the tile + this many ring cells (halo-8 layout: 4)
+  void* strip = nullptr;       // fused pack: the new state's halo strip goes here
+  const void* recv = nullptr;  // fused unpack: the halo comes from these gathered strips (of neighbour ranks nbr[8])
+  int nbr[8] = {};
+  const void* peer[8] = {};    // ... or from the neighbours' own strip buffers (peer-mapped exchange)
+};
+
+// where a fused-unpack launch finds the strips of its 8 neighbours: slices of the gathered buffer (recv + rank * strip
+// elements), or the neighbours' own buffers (peer); all nullptr: no fused unpack
 template <typename T>
-inline void fill_neighbour_strips(const pdeopt_ctx* ctx, int64_t strip_rank_elems, const T** nbase) {
+inline void fill_neighbour_strips(const HaloIo& io, int64_t strip_rank_elems, const T** nbase) {
   for (int q = 0; q < 8; ++q) {
-    if (ctx->pair_peer[0]) nbase[q] = static_cast<const T*>(ctx->pair_peer[q]);
-    else if (ctx->pair_recv) nbase[q] = static_cast<const T*>(ctx->pair_recv) + (int64_t)ctx->pair_nbr[q] * strip_rank_elems;
+    if (io.peer[0]) nbase[q] = static_cast<const T*>(io.peer[q]);
+    else if (io.recv) nbase[q] = static_cast<const T*>(io.recv) + (int64_t)io.nbr[q] * strip_rank_elems;
     else nbase[q] = nullptr;
   }
 }
-// light spots of the environments from win_lo on, at local time t
+// light spots of the environments from first_env on, at local time t
 template <typename T>
-inline SpotArgs<T> make_spot_args(const pdeopt_ctx* ctx, double t) {
+inline SpotArgs<T> make_spot_args(const pdeopt_ctx* ctx, int first_env, double t) {
   SpotArgs<T> a{};
   a.n = ctx->n_spots;
-  a.table = a.n ? static_cast<const LightSpot<T>*>(ctx->spots_dev) + (size_t)ctx->win_lo * PDEOPT_MAX_SPOTS : nullptr;
+  a.table = a.n ? static_cast<const LightSpot<T>*>(ctx->spots_dev) + (size_t)first_env * PDEOPT_MAX_SPOTS : nullptr;
   a.t = T(t);
   a.x_first = T(ctx->spots_x_first);
   a.y_first = T(ctx->spots_y_first);
@@ -275,11 +289,11 @@ inline SpotArgs<T> make_spot_args(const pdeopt_ctx* ctx, double t) {
   return a;
 }
 
-// stencil.hip
-int launch_rhs(pdeopt_ctx* ctx, const void* in, void* out, double t);
+// stencil.hip: out = f(t, in) for the environments of the window
+int launch_rhs(pdeopt_ctx* ctx, const Window& w, const void* in, void* out, double t);
 // the same slope for the IMEX step: the stage-B half of the fused pair kernel where it applies (CH, periodic
 // layout, polynomial / logit closures), launch_rhs otherwise; equal to launch_rhs up to rounding
-int launch_rhs_slope(pdeopt_ctx* ctx, const void* in, void* out, double t);
+int launch_rhs_slope(pdeopt_ctx* ctx, const Window& w, const void* in, void* out, double t);
 int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n);
 int tsit5_trial(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol, double* err);
 int tsit5_commit(pdeopt_ctx* ctx, int accept);
@@ -303,6 +317,7 @@ int rk4_loopback_advance(pdeopt_ctx* ctx, double dt, int64_t n);
 // recv != nullptr: the halo of the state is NOT in the field yet -- the first pair's edge tiles read it from the
 // gathered strips `recv` (neighbour ranks nbr[8]) and write the frame cells back (fused unpack)
 int rk4_substep_h8(pdeopt_ctx* ctx, double dt, void* strip, const void* recv = nullptr, const int* nbr = nullptr);
+// the same with the halo taken from the 8 neighbours' OWN strip buffers (peer-mapped exchange: comm.hip)
 int rk4_substep_h8_peer(pdeopt_ctx* ctx, double dt, void* strip, const void* const* peer);
 int rk4_phase_plan(pdeopt_ctx* ctx, int* fields, int* nphases);
 void* field_ptr(pdeopt_ctx* ctx, int field);
@@ -336,9 +351,9 @@ int advance_strang_fused(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
 bool imex_fused_supported(const pdeopt_ctx* ctx);
 int advance_imex_fused(pdeopt_ctx* ctx, double dt, int64_t n);
 // the IMEX step's transforms alone, for callers that form the slope TA themselves (sens.hip): prepare the multiplier
-// of step dt, then y += dt L^-1 TA over the window [win_lo, win_lo + win_n)
+// of step dt, then y += dt L^-1 TA over the environments of the window
 int imex_fused_prepare(pdeopt_ctx* ctx, double dt);
-int imex_fused_passes(pdeopt_ctx* ctx, double dt);
+int imex_fused_passes(pdeopt_ctx* ctx, const Window& w, double dt);
 // the same split of the rocFFT IMEX step (spectral.hip; any grid, 3-D included): plans, work fields and the
 // half-spectrum multiplier of step dt, then y += dt L^-1 TA over the whole batch (r2c, multiply, c2r, axpy)
 int imex_rocfft_prepare(pdeopt_ctx* ctx, double dt);

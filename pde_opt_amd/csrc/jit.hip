@@ -138,7 +138,7 @@ bool jit_closures_active(const pdeopt_ctx* ctx) {
 
 // one fused stencil + update launch of the run-time-compiled kernel (what launch_generic does for the closure family)
 template <typename T>
-int launch_jit_stage(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_jit_stage(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   const pdeopt_problem& p = ctx->prob;
   if (p.equation != PDEOPT_EQ_CAHN_HILLIARD && p.equation != PDEOPT_EQ_ALLEN_CAHN)
     return fail(ctx, PDEOPT_EINVAL, "run-time-compiled closures run the 2-D Cahn-Hilliard / Allen-Cahn finite-difference kernels only");
@@ -146,19 +146,19 @@ int launch_jit_stage(pdeopt_ctx* ctx, const StageArgs<T>& s) {
   int rc = get_module<T>(ctx, &m);
   if (rc) return rc;
   dim3 block(64, 4, 1);
-  dim3 grid((p.ny + 63) / 64, (p.nx + 3) / 4, ctx->win_n);
+  dim3 grid((p.ny + 63) / 64, (p.nx + 3) / 4, w.n);
   if (grid.y > 65535u || grid.z > 65535u) return fail(ctx, PDEOPT_EINVAL, "grid too large for the generic kernel (nx=%d batch=%d)", p.nx, p.batch);
   StageArgs<T> args = s;
   size_t size = sizeof(args);
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   PDEOPT_HIP_CHECK(ctx, hipModuleLaunchKernel(p.equation == PDEOPT_EQ_CAHN_HILLIARD ? m.ch : m.ac, grid.x, grid.y, grid.z, block.x, block.y, block.z, 0,
-                                              ctx->stream, nullptr, config));
+                                              w.stream, nullptr, config));
   ctx->last_kernel = p.equation == PDEOPT_EQ_CAHN_HILLIARD ? "stage_jit<CH,hiprtc closures>" : "stage_jit<AC,hiprtc closures>";
   return PDEOPT_OK;
 }
 
-template int launch_jit_stage<float>(pdeopt_ctx*, const StageArgs<float>&);
-template int launch_jit_stage<double>(pdeopt_ctx*, const StageArgs<double>&);
+template int launch_jit_stage<float>(pdeopt_ctx*, const Window&, const StageArgs<float>&);
+template int launch_jit_stage<double>(pdeopt_ctx*, const Window&, const StageArgs<double>&);
 
 // pdeopt_jit_check: do these bodies compile (for gfx950, no device needed)?
 int jit_check(int dtype, const char* mu_body, const char* mob_body, char* log_out, int log_cap) {

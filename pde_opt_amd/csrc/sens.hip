@@ -472,11 +472,8 @@ int launch_tangent_rhs3d(pdeopt_ctx* ctx) {
 int sens_slopes(pdeopt_ctx* ctx) {
   int rc;
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  ctx->win_lo = 0;
-  ctx->win_n = ctx->sens->B;
-  rc = launch_rhs_slope(ctx, ctx->Y, ctx->TA, 0.0);
-  ctx->win_n = ctx->prob.batch;
-  if (rc) return rc;
+  // the base block's slope; the tangent blocks' slopes come from the kernels below
+  if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, ctx->Y, ctx->TA, 0.0))) return rc;
   const bool f32 = ctx->prob.dtype == PDEOPT_F32;
   if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D) return f32 ? launch_tangent_rhs3d<float>(ctx) : launch_tangent_rhs3d<double>(ctx);
   return f32 ? launch_tangent_rhs<float>(ctx) : launch_tangent_rhs<double>(ctx);
@@ -614,10 +611,8 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   }
   for (int64_t s = 0; s < n_substeps; ++s) {
     if ((rc = sens_slopes(ctx))) return rc;
-    ctx->win_lo = 0;
-    ctx->win_n = ctx->prob.batch;
     if (integrator == PDEOPT_INT_IMEX && fused) {
-      rc = imex_fused_passes(ctx, dt);
+      rc = imex_fused_passes(ctx, whole_batch(ctx), dt);
     } else if (integrator == PDEOPT_INT_IMEX) {
       rc = imex_rocfft_solve(ctx, dt);
       ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls; rocFFT may run more than one kernel per transform)

@@ -382,7 +382,7 @@ int imex_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   int rc;
   if ((rc = imex_rocfft_prepare_t<T>(ctx, dt))) return rc;
   for (int64_t s = 0; s < n; ++s) {
-    if ((rc = launch_rhs(ctx, ctx->Y, ctx->TA, 0.0))) return rc;
+    if ((rc = launch_rhs(ctx, whole_batch(ctx), ctx->Y, ctx->TA, 0.0))) return rc;
     if ((rc = imex_rocfft_solve_t<T>(ctx, dt))) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -428,7 +428,7 @@ int strang_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
     hipLaunchKernelGGL(strang_b_kernel<T>, dim3(kNormBlocks, p.batch), dim3(256), 0, ctx->stream,
                        (C2<T>*)ctx->Y, (const T*)sp.dens, (const T*)pot.dev, pot_stride,
                        (const EnvParams<T>*)ctx->env_params_dev, (T)tau.real(), (T)tau.imag(), cells,
-                       sp.partial, make_spot_args<T>(ctx, t0 + (double)s * dt), p.ny);
+                       sp.partial, make_spot_args<T>(ctx, 0, t0 + (double)s * dt), p.ny);
     hipLaunchKernelGGL(norm_finalize_kernel, dim3((p.batch + 63) / 64), dim3(64), 0, ctx->stream,
                        (const double*)sp.partial, kNormBlocks, ctx->strang_dx * ctx->strang_dx,
                        sp.scale, p.batch);

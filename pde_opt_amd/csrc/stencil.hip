@@ -19,19 +19,20 @@
 #include "stencil_small_adaptive.hpp"
 #include "stencil_coop_adaptive.hpp"
 #include "stencil_sbm_tiled.hpp"
+#include "groups.hpp"
 
 namespace pdeopt {
 
 namespace {
 
 template <typename T>
-StageArgs<T> make_args(pdeopt_ctx* ctx, const void* in, const void* y, void* out, void* acc,
+StageArgs<T> make_args(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* out, void* acc,
                        double a, double b, int out_mode, int acc_mode) {
   const pdeopt_problem& p = ctx->prob;
   StageArgs<T> s{};
-  // environment window [win_lo, win_lo + win_n): pointers are pre-offset, kernels see a batch of win_n
+  // environment window [w.lo, w.lo + w.n): pointers are pre-offset, kernels see a batch of w.n
   s.g = make_geo(ctx);
-  const int64_t woff = (int64_t)ctx->win_lo * s.g.bstride;
+  const int64_t woff = (int64_t)w.lo * s.g.bstride;
   s.in = static_cast<const T*>(in) + woff;
   s.y = static_cast<const T*>(y) + woff;
   s.out = out ? static_cast<T*>(out) + woff : nullptr;
@@ -45,14 +46,14 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const void* in, const void* y, void* out
   s.rhz = p.nz > 1 ? T(1.0 / p.hz) : T(0);
   s.rhz2 = p.nz > 1 ? T(1.0 / (p.hz * p.hz)) : T(0);
   s.mu3 = nullptr;
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + ctx->win_lo;
+  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + w.lo;
   s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
   s.vstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? (int64_t)p.nx * p.ny : 0;
   s.vx = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
   s.vy = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
-  if (s.vx) s.vx += ctx->win_lo * s.vstride;
-  if (s.vy) s.vy += ctx->win_lo * s.vstride;
+  if (s.vx) s.vx += w.lo * s.vstride;
+  if (s.vy) s.vy += w.lo * s.vstride;
   s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
   s.ngp = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
   s.mask = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
@@ -65,13 +66,13 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const void* in, const void* y, void* out
     const size_t nt = ctx->tt_times.size();
     for (size_t q = 0; q < nt && !found; ++q) {
       const size_t i = (ctx->tt_cursor + q) % nt;
-      if (ctx->tt_times[i] == ctx->cur_t) {
+      if (ctx->tt_times[i] == t) {
         for (int c = 0; c < 3; ++c) tv[c] = ctx->tt_terms[3 * i + c];
         ctx->tt_cursor = i;
         found = true;
       }
     }
-    if (!found && ctx->time_fn) ctx->time_fn(ctx->cur_t, tv, ctx->time_user);
+    if (!found && ctx->time_fn) ctx->time_fn(t, tv, ctx->time_user);
     // a table that does not hold this stage time and no callback to ask: the constant terms would be used silently
     // (a caller whose times differ from the library's t0 + s dt, + dt/2 arithmetic by an ulp) -- pdeopt_advance reports it
     if (!found && !ctx->time_fn && nt) ctx->tt_misses++;
@@ -87,37 +88,37 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const void* in, const void* y, void* out
 }
 
 template <typename T>
-int launch_generic(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_generic(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   const pdeopt_problem& p = ctx->prob;
   dim3 block(64, 4, 1);
-  dim3 grid((p.ny + 63) / 64, (p.nx + 3) / 4, ctx->win_n);
+  dim3 grid((p.ny + 63) / 64, (p.nx + 3) / 4, w.n);
   if (grid.y > 65535u || grid.z > 65535u)
     return fail(ctx, PDEOPT_EINVAL, "grid too large for the generic kernel (nx=%d batch=%d)", p.nx,
                 p.batch);
-  if (jit_closures_active(ctx)) return launch_jit_stage<T>(ctx, s);  // closures compiled at run time (jit.hip)
+  if (jit_closures_active(ctx)) return launch_jit_stage<T>(ctx, w, s);  // closures compiled at run time (jit.hip)
   if (p.equation == PDEOPT_EQ_CAHN_HILLIARD_3D) {
     // two passes: chemical potential into the work field, then the flux divergence + stage update
     const int nz = s.g.nz;
-    dim3 g3((nz + 63) / 64, (p.ny + 3) / 4, (unsigned)(p.nx * ctx->win_n));
+    dim3 g3((nz + 63) / 64, (p.ny + 3) / 4, (unsigned)(p.nx * w.n));
     if (g3.y > 65535u || g3.z > 65535u) return fail(ctx, PDEOPT_EINVAL, "grid too large for the 3-D kernels");
     int rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes);
     if (rc) return rc;
     StageArgs<T> s3 = s;
-    s3.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)ctx->win_lo * s.g.bstride;
+    s3.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
     switch (classify_closures(p.mu, p.mob)) {
       case CL_POLY:
-        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_POLY>), g3, block, 0, ctx->stream, s3, const_cast<T*>(s3.mu3));
-        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_POLY>), g3, block, 0, ctx->stream, s3);
+        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_POLY>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
+        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_POLY>), g3, block, 0, w.stream, s3);
         ctx->last_kernel = "stage_generic<CH-3D,poly>";
         break;
       case CL_LOGIT:
-        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_LOGIT>), g3, block, 0, ctx->stream, s3, const_cast<T*>(s3.mu3));
-        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_LOGIT>), g3, block, 0, ctx->stream, s3);
+        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_LOGIT>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
+        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_LOGIT>), g3, block, 0, w.stream, s3);
         ctx->last_kernel = "stage_generic<CH-3D,logit>";
         break;
       default:
-        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_GENERIC>), g3, block, 0, ctx->stream, s3, const_cast<T*>(s3.mu3));
-        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_GENERIC>), g3, block, 0, ctx->stream, s3);
+        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_GENERIC>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
+        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_GENERIC>), g3, block, 0, w.stream, s3);
         ctx->last_kernel = "stage_generic<CH-3D>";
     }
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -126,24 +127,24 @@ int launch_generic(pdeopt_ctx* ctx, const StageArgs<T>& s) {
   switch (p.equation) {
     case PDEOPT_EQ_CAHN_HILLIARD:
       hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_CAHN_HILLIARD>), grid, block, 0,
-                         ctx->stream, s);
+                         w.stream, s);
       ctx->last_kernel = "stage_generic<CH>";
       break;
     case PDEOPT_EQ_ALLEN_CAHN:
       hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ALLEN_CAHN>), grid, block, 0,
-                         ctx->stream, s);
+                         w.stream, s);
       ctx->last_kernel = "stage_generic<AC>";
       break;
     case PDEOPT_EQ_ADVECTION_DIFFUSION:
       if (!s.vx || !s.vy)
         return fail(ctx, PDEOPT_ESTATE, "advection-diffusion needs VX_FACE and VY_FACE aux fields");
       hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ADVECTION_DIFFUSION>), grid, block, 0,
-                         ctx->stream, s);
+                         w.stream, s);
       ctx->last_kernel = "stage_generic<AD>";
       break;
     case PDEOPT_EQ_SHAPE_SMOOTH:
       if (ctx->halo) return fail(ctx, PDEOPT_EINVAL, "shape smoothing needs the periodic layout");
-      hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_SHAPE_SMOOTH>), grid, block, 0, ctx->stream, s);
+      hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_SHAPE_SMOOTH>), grid, block, 0, w.stream, s);
       ctx->last_kernel = "stage_generic<shape-smooth>";
       break;
     case PDEOPT_EQ_ALLEN_CAHN_SBM:
@@ -152,19 +153,19 @@ int launch_generic(pdeopt_ctx* ctx, const StageArgs<T>& s) {
         return fail(ctx, PDEOPT_ESTATE, "smoothed-boundary equations need the SBM_PSI, SBM_NORM_GRAD and SBM_MASK aux fields");
       if (ctx->halo) return fail(ctx, PDEOPT_EINVAL, "smoothed-boundary equations need the periodic layout");
       if (sbm_tiled_supported<T>(ctx)) {
-        const int rc_t = launch_sbm_tiled<T>(ctx, s);
+        const int rc_t = launch_sbm_tiled<T>(ctx, w, s);
         if (rc_t) return rc_t;
         break;
       }
       if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM) {
-        hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ALLEN_CAHN_SBM>), grid, block, 0, ctx->stream, s);
+        hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ALLEN_CAHN_SBM>), grid, block, 0, w.stream, s);
         ctx->last_kernel = "stage_generic<AC-SBM>";
       } else if (ctx->opt_fuse_stages < 0 ||
-                 (ctx->opt_fuse_stages == 0 && (int64_t)p.nx * p.ny * ctx->win_n < (1 << 18))) {
+                 (ctx->opt_fuse_stages == 0 && (int64_t)p.nx * p.ny * w.n < (1 << 18))) {
         // the literal one-pass form (inner re-evaluated at 5 points per cell): one launch instead of two, faster
         // on the notebook-sized grids (128^2: 7.0 vs 7.7 us per evaluation); PDEOPT_OPT_FUSE_STAGES = 1 / -1
         // force the two-pass / the literal form
-        hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_CAHN_HILLIARD_SBM>), grid, block, 0, ctx->stream, s);
+        hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_CAHN_HILLIARD_SBM>), grid, block, 0, w.stream, s);
         ctx->last_kernel = "stage_generic<CH-SBM>";
       } else {
         // two passes: inner once per cell into the work field, then the psi-weighted flux divergence
@@ -172,9 +173,9 @@ int launch_generic(pdeopt_ctx* ctx, const StageArgs<T>& s) {
         int rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes);
         if (rc) return rc;
         StageArgs<T> s2 = s;
-        s2.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)ctx->win_lo * s.g.bstride;
-        hipLaunchKernelGGL(sbm_inner_kernel<T>, grid, block, 0, ctx->stream, s2, const_cast<T*>(s2.mu3));
-        hipLaunchKernelGGL(sbm_ch_stage_kernel<T>, grid, block, 0, ctx->stream, s2);
+        s2.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
+        hipLaunchKernelGGL(sbm_inner_kernel<T>, grid, block, 0, w.stream, s2, const_cast<T*>(s2.mu3));
+        hipLaunchKernelGGL(sbm_ch_stage_kernel<T>, grid, block, 0, w.stream, s2);
         ctx->last_kernel = "stage_two_pass<CH-SBM>";
       }
       break;
@@ -203,8 +204,8 @@ __global__ void env_scale_kernel(T* __restrict__ f, const double* __restrict__ r
 }
 
 template <typename T>
-int launch_stage_fourier(pdeopt_ctx* ctx, const StageArgs<T>& s, const void* in, void* out) {
-  if (ctx->win_lo != 0 || ctx->win_n != ctx->prob.batch)
+int launch_stage_fourier(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s, const void* in, void* out) {
+  if (w.lo != 0 || w.n != ctx->prob.batch)
     return fail(ctx, PDEOPT_EINVAL, "spectral RHS works on the whole batch");
   int rc;
   if (s.out_mode == OUT_K && s.acc_mode == ACC_NONE && !s.scaled) return rhs_fourier(ctx, in, out);
@@ -220,44 +221,44 @@ int launch_stage_fourier(pdeopt_ctx* ctx, const StageArgs<T>& s, const void* in,
 
 // One fused stage: k = rhs(in); out/acc updated per (out_mode, acc_mode).
 template <typename T>
-int launch_stage_t(pdeopt_ctx* ctx, const void* in, const void* y, void* out, void* acc, double a,
+int launch_stage_t(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* out, void* acc, double a,
                    double b, int out_mode, int acc_mode) {
   if (ctx->prob.equation == PDEOPT_EQ_ADVECTION_DIFFUSION) {
-    // velocity_fn(t, x, y): face velocities at the time of THIS right-hand side (ctx->cur_t = stage time)
+    // velocity_fn(t, x, y): face velocities at the time of THIS right-hand side (t = stage time)
     int rc;
-    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VX_FACE, ctx->cur_t))) return rc;
-    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VY_FACE, ctx->cur_t))) return rc;
+    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VX_FACE, t))) return rc;
+    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VY_FACE, t))) return rc;
   }
-  StageArgs<T> s = make_args<T>(ctx, in, y, out, acc, a, b, out_mode, acc_mode);
+  StageArgs<T> s = make_args<T>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
   ctx->n_stage_launches++;
-  if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, s, in, out);
+  if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, w, s, in, out);
   if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) {
-    return launch_tiled<T>(ctx, s);
+    return launch_tiled<T>(ctx, w, s);
   }
   if (ctx->opt_kernel_path == 2)
     return fail(ctx, PDEOPT_EINVAL, "LDS-tiled kernel forced but shape %dx%d / equation %d is not covered",
                 ctx->prob.nx, ctx->prob.ny, ctx->prob.equation);
-  return launch_generic<T>(ctx, s);
+  return launch_generic<T>(ctx, w, s);
 }
 
-int launch_stage(pdeopt_ctx* ctx, const void* in, const void* y, void* out, void* acc, double a,
+int launch_stage(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* out, void* acc, double a,
                  double b, int out_mode, int acc_mode) {
   if (ctx->prob.dtype == PDEOPT_F32)
-    return launch_stage_t<float>(ctx, in, y, out, acc, a, b, out_mode, acc_mode);
-  return launch_stage_t<double>(ctx, in, y, out, acc, a, b, out_mode, acc_mode);
+    return launch_stage_t<float>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
+  return launch_stage_t<double>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
 }
 
 // k = rhs(in) -> kout, and  next = y + sum_{j<n} c[j] K[j] + c[n] k  in the same pass (OUT_K_LC)
 template <typename T>
-int launch_stage_lc(pdeopt_ctx* ctx, const void* in, const void* y, void* kout, void* const* ks, const double* c,
+int launch_stage_lc(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* kout, void* const* ks, const double* c,
                     int n, void* next) {
   if (ctx->prob.equation == PDEOPT_EQ_ADVECTION_DIFFUSION) {
     int rc;
-    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VX_FACE, ctx->cur_t))) return rc;
-    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VY_FACE, ctx->cur_t))) return rc;
+    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VX_FACE, t))) return rc;
+    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VY_FACE, t))) return rc;
   }
-  StageArgs<T> s = make_args<T>(ctx, in, y, kout, nullptr, 0.0, 0.0, OUT_K_LC, ACC_NONE);
-  const int64_t woff = (int64_t)ctx->win_lo * s.g.bstride;
+  StageArgs<T> s = make_args<T>(ctx, w, t, in, y, kout, nullptr, 0.0, 0.0, OUT_K_LC, ACC_NONE);
+  const int64_t woff = (int64_t)w.lo * s.g.bstride;
   for (int j = 0; j < n; ++j) {
     s.lc.k[j] = static_cast<const T*>(ks[j]) + woff;
     s.lc.c[j] = T(c[j]);
@@ -266,16 +267,16 @@ int launch_stage_lc(pdeopt_ctx* ctx, const void* in, const void* y, void* kout, 
   s.lc.n = n;
   s.lc.next = static_cast<T*>(next) + woff;
   ctx->n_stage_launches++;
-  if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, s, in, kout);
-  if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) return launch_tiled<T>(ctx, s);
-  return launch_generic<T>(ctx, s);
+  if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, w, s, in, kout);
+  if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) return launch_tiled<T>(ctx, w, s);
+  return launch_generic<T>(ctx, w, s);
 }
 
-int launch_pair_dt(pdeopt_ctx* ctx, int pair, const void* in, const void* y, const void* acc, void* out,
+int launch_pair_dt(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, int pair, const void* in, const void* y, const void* acc, void* out,
                    void* acc_out, double aA, double bA, double aB, double bB) {
   if (ctx->prob.dtype == PDEOPT_F32)
-    return launch_pair<float>(ctx, pair, in, y, acc, out, acc_out, aA, bA, aB, bB);
-  return launch_pair<double>(ctx, pair, in, y, acc, out, acc_out, aA, bA, aB, bB);
+    return launch_pair<float>(ctx, w, io, pair, in, y, acc, out, acc_out, aA, bA, aB, bB);
+  return launch_pair<double>(ctx, w, io, pair, in, y, acc, out, acc_out, aA, bA, aB, bB);
 }
 
 template <typename T>
@@ -288,23 +289,21 @@ __global__ void lerp_kernel(const T* __restrict__ a, const T* __restrict__ b, T*
 
 }  // namespace
 
-int launch_rhs(pdeopt_ctx* ctx, const void* in, void* out, double t) {
-  ctx->cur_t = t;
-  return launch_stage(ctx, in, in, out, nullptr, 0.0, 0.0, OUT_K, ACC_NONE);
+int launch_rhs(pdeopt_ctx* ctx, const Window& w, const void* in, void* out, double t) {
+  return launch_stage(ctx, w, t, in, in, out, nullptr, 0.0, 0.0, OUT_K, ACC_NONE);
 }
 
 #ifndef PDEOPT_IMEX_SLOPE_PAIR
 #define PDEOPT_IMEX_SLOPE_PAIR 1
 #endif
-int launch_rhs_slope(pdeopt_ctx* ctx, const void* in, void* out, double t) {
-  ctx->cur_t = t;
+int launch_rhs_slope(pdeopt_ctx* ctx, const Window& w, const void* in, void* out, double t) {
 #if PDEOPT_IMEX_SLOPE_PAIR
   if (ctx->prob.derivs == PDEOPT_DERIVS_FD && ctx->prob.nz <= 1 && !ctx->time_fn) {
-    if (ctx->prob.dtype == PDEOPT_F32 && slope_pair_supported<float>(ctx)) return launch_slope_pair<float>(ctx, in, out);
-    if (ctx->prob.dtype == PDEOPT_F64 && slope_pair_supported<double>(ctx)) return launch_slope_pair<double>(ctx, in, out);
+    if (ctx->prob.dtype == PDEOPT_F32 && slope_pair_supported<float>(ctx)) return launch_slope_pair<float>(ctx, w, in, out);
+    if (ctx->prob.dtype == PDEOPT_F64 && slope_pair_supported<double>(ctx)) return launch_slope_pair<double>(ctx, w, in, out);
   }
 #endif
-  return launch_rhs(ctx, in, out, t);
+  return launch_rhs(ctx, w, in, out, t);
 }
 
 namespace {
@@ -347,16 +346,13 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   const bool coop = ctx->prob.dtype == PDEOPT_F32 ? coop_fixed_chosen<float>(ctx, integrator, n) : coop_fixed_chosen<double>(ctx, integrator, n);
   const bool f64 = ctx->prob.dtype == PDEOPT_F64;  // (64^2 fp64: 0.70 ms against the one-CU kernel's 1.14, which small_chosen would pick)
   if (coop && (ctx->opt_small_persist == 2 || f64 || !small_chosen(ctx, integrator, n))) {
-    ctx->win_lo = 0;
-    ctx->win_n = ctx->prob.batch;
     ctx->last_groups = 1;
     return ctx->prob.dtype == PDEOPT_F32 ? coop_fixed_advance<float>(ctx, integrator, t0, dt, n) : coop_fixed_advance<double>(ctx, integrator, t0, dt, n);
   }
+  const Window all = whole_batch(ctx);
   if (small_chosen(ctx, integrator, n)) {
-    ctx->win_lo = 0;
-    ctx->win_n = ctx->prob.batch;
     ctx->last_groups = 1;
-    return ctx->prob.dtype == PDEOPT_F32 ? launch_small<float>(ctx, integrator, dt, n) : launch_small<double>(ctx, integrator, dt, n);
+    return ctx->prob.dtype == PDEOPT_F32 ? launch_small<float>(ctx, all, integrator, dt, n) : launch_small<double>(ctx, all, integrator, dt, n);
   }
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   // Euler: two substeps per launch through the stage-pair kernels where they exist
@@ -391,11 +387,8 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     // auto: largest balanced group whose 4 fields fit the Infinity Cache (measured on MI355X:
     // 32 x 1024^2 fp32 runs 13-16 % faster as 2 groups of 16 = 256 MiB than as one 512 MiB sweep;
     // smaller groups lose more to per-launch ramp/tail than they gain)
-    const size_t field = ctx->env_elems * ctx->esize;
-    const int64_t fit = std::max<int64_t>(1, (int64_t)((256ull << 20) / (4 * field)));
-    if (fit < batch && n > 1) {
-      const int ngroups = (int)((batch + fit - 1) / fit);
-      group = (batch + ngroups - 1) / ngroups;
+    if (n > 1) group = cache_group(batch, 4 * ctx->env_elems * ctx->esize, 256ull << 20, false);
+    if (group < batch) {
       // Two groups side by side on two streams, each half the size (the same resident working set): a launch of the
       // stage kernels is 3-6 rounds of resident workgroups, its ramp and its tail leave compute units idle, and the
       // next launch of the SAME group depends on it -- the other group's does not.
@@ -423,50 +416,44 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   // Cahn-Hilliard fp32, periodic divisible grids: the same (stencil_fused_ch4.hpp); PDEOPT_OPT_FUSE_STAGES = 1 keeps the stage pairs
   const bool chquad = integrator == PDEOPT_INT_RK4 && ch_quad_chosen(ctx);
 
-  // two Euler substeps in one launch (result into TA, TB takes the kernel's unused y + dt k2 output)
-  auto euler_pair = [&](void*& Y, void*& TA) -> int {
-    const int r = launch_pair_dt(ctx, PAIR_12, Y, nullptr, nullptr, ctx->TB, TA, dt, dt, dt, dt);
-    std::swap(Y, TA);
-    return r;
-  };
+  // The state ping-pongs between Y and TA: every launch that advances it (an Euler step or pair, a fused RK4 substep)
+  // writes the other buffer; the per-stage RK4 updates y in place.  Every group performs the same launches, so which
+  // buffer holds the state before substep s depends on s alone: `base` is where the buffers were as the ctx has them.
+  const bool rotates = integrator == PDEOPT_INT_EULER || quad || chquad || fused;
+  void* const Y0 = ctx->Y;
+  void* const TA0 = ctx->TA;
+  auto rotations = [&](int64_t s, int64_t base) -> int64_t { return !rotates ? 0 : euler2 ? (s - base + 1) / 2 : s - base; };
+  const HaloIo none{};
 
-  // one substep on the current window; Y / TA are swapped where the integrator ping-pongs
-  auto substep = [&](void*& Y, void*& TA, int64_t step) -> int {
+  // substep s (and s + 1, where two Euler substeps go into one launch: took = 2) of the window
+  auto step = [&](const Window& w, int64_t s, int64_t base, int& took) -> int {
+    const bool odd = rotations(s, base) & 1;
+    void* const Y = odd ? TA0 : Y0;
+    void* const TA = odd ? Y0 : TA0;
+    const double ts = t0 + (double)s * dt;  // stage times only matter to time-dependent equations
+    if (euler2 && s + 1 < n) {
+      // result into TA, TB takes the kernel's unused y + dt k2 output
+      took = 2;
+      return launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB, TA, dt, dt, dt, dt);
+    }
+    if (integrator == PDEOPT_INT_EULER) return launch_stage(ctx, w, ts, Y, Y, TA, nullptr, dt, 0.0, OUT_Y_PLUS_AK, ACC_NONE);
+    if (quad) return launch_ac_quad(ctx, w, Y, TA, dt);
+    if (chquad) return launch_ch_quad(ctx, w, none, Y, TA, dt);
     int r;
-    const double ts = t0 + (double)step * dt;  // stage times only matter to time-dependent equations
-    ctx->cur_t = ts;
-    if (integrator == PDEOPT_INT_EULER) {
-      r = launch_stage(ctx, Y, Y, TA, nullptr, dt, 0.0, OUT_Y_PLUS_AK, ACC_NONE);
-      std::swap(Y, TA);
-      return r;
-    }
-    if (quad) {
-      r = launch_ac_quad(ctx, Y, TA, dt);
-      std::swap(Y, TA);
-      return r;
-    }
-    if (chquad) {
-      r = launch_ch_quad(ctx, Y, TA, dt);
-      std::swap(Y, TA);
-      return r;
-    }
     if (fused) {
       // stages 1+2 and 3+4 as two temporally fused launches (7 words/cell instead of 16)
-      r = launch_pair_dt(ctx, PAIR_12, Y, nullptr, nullptr, ctx->TB, ctx->ACC, dt / 2, dt / 6, dt / 2, dt / 3);
-      if (!r) r = launch_pair_dt(ctx, PAIR_34, ctx->TB, Y, ctx->ACC, TA, nullptr, dt, dt / 3, 0.0, dt / 6);
-      std::swap(Y, TA);
+      r = launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB, ctx->ACC, dt / 2, dt / 6, dt / 2, dt / 3);
+      if (!r) r = launch_pair_dt(ctx, w, none, PAIR_34, ctx->TB, Y, ctx->ACC, TA, nullptr, dt, dt / 3, 0.0, dt / 6);
       return r;
     }
     // stage 1: k1 = f(y);        TA = y + dt/2 k1;  ACC = y + dt/6 k1
-    r = launch_stage(ctx, Y, Y, TA, ctx->ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
+    r = launch_stage(ctx, w, ts, Y, Y, TA, ctx->ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
     // stage 2: k2 = f(TA);       TB = y + dt/2 k2;  ACC += dt/3 k2
-    ctx->cur_t = ts + dt / 2;
-    if (!r) r = launch_stage(ctx, TA, Y, ctx->TB, ctx->ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    if (!r) r = launch_stage(ctx, w, ts + dt / 2, TA, Y, ctx->TB, ctx->ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
     // stage 3: k3 = f(TB);       TA = y + dt k3;    ACC += dt/3 k3
-    if (!r) r = launch_stage(ctx, ctx->TB, Y, TA, ctx->ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    if (!r) r = launch_stage(ctx, w, ts + dt / 2, ctx->TB, Y, TA, ctx->ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
     // stage 4: k4 = f(TA);       y  = ACC + dt/6 k4   (in place: y is only touched pointwise)
-    ctx->cur_t = ts + dt;
-    if (!r) r = launch_stage(ctx, TA, Y, Y, ctx->ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
+    if (!r) r = launch_stage(ctx, w, ts + dt, TA, Y, Y, ctx->ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
     return r;
   };
 
@@ -479,8 +466,6 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   const bool want_graph = !timed && ctx->opt_graph >= 0 && group >= batch && ctx->prob.derivs == PDEOPT_DERIVS_FD &&
                           n >= 2 * kGraphUnit && (ctx->opt_graph > 0 || cells_per_launch <= (1 << 20));
   if (want_graph) {
-    ctx->win_lo = 0;
-    ctx->win_n = batch;
     GraphKey key;
     memset(&key, 0, sizeof(key));  // padding bytes take part in the memcmp below
     key.integrator = integrator;
@@ -493,18 +478,13 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     key.structure = graph_structure(ctx->prob);
     if (!ctx->graph_exec || memcmp(&key, &ctx->graph_key, sizeof(key)) != 0) {
       graph_destroy(ctx);
-      void* Y = ctx->Y;
-      void* TA = ctx->TA;
       const int64_t launches_before = ctx->n_stage_launches;
       hipGraph_t graph = nullptr;
       PDEOPT_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      for (int u = 0; u < kGraphUnit && !rc; ++u) {
-        if (euler2) {
-          rc = euler_pair(Y, TA);
-          ++u;
-        } else {
-          rc = substep(Y, TA, u);
-        }
+      for (int u = 0; u < kGraphUnit && !rc;) {
+        int took = 1;
+        rc = step(all, u, 0, took);
+        u += took;
       }
       const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
       ctx->graph_launches_per_replay = ctx->n_stage_launches - launches_before;
@@ -528,73 +508,12 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     ctx->last_kernel = ctx->graph_name;
   }
 
-  void* y_final = ctx->Y;
-  void* ta_final = ctx->TA;
-  ctx->last_groups = (batch + group - 1) / group;
-  if (side_by_side && ctx->last_groups >= 2) {
-    ctx->last_group_streams = 2;
-    if ((rc = ensure_stream2(ctx))) return rc;
-    // the second stream starts after everything already queued on the ctx stream (the state upload, the previous call)
-    PDEOPT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    PDEOPT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    for (int lo = 0; lo < batch && !rc; lo += 2 * group) {
-      const int lo2 = lo + group;
-      const bool two = lo2 < batch;
-      void* Y = ctx->Y;
-      void* TA = ctx->TA;
-      for (int64_t s = done; s < n && !rc; ++s) {
-        const bool pair = euler2 && s + 1 < n;
-        void *Ya = Y, *TAa = TA, *Yb = Y, *TAb = TA;
-        ctx->win_lo = lo;
-        ctx->win_n = std::min(group, batch - lo);
-        rc = pair ? euler_pair(Ya, TAa) : substep(Ya, TAa, s);
-        if (two && !rc) {
-          ctx->win_lo = lo2;
-          ctx->win_n = std::min(group, batch - lo2);
-          std::swap(ctx->stream, ctx->stream2);  // the launch helpers take the ctx stream
-          rc = pair ? euler_pair(Yb, TAb) : substep(Yb, TAb, s);
-          std::swap(ctx->stream, ctx->stream2);
-        }
-        Y = Ya;  // both groups rotate their buffers alike
-        TA = TAa;
-        if (pair) ++s;
-      }
-      y_final = Y;
-      ta_final = TA;
-    }
-    const hipError_t e1 = hipEventRecord(ctx->ev_join, ctx->stream2);
-    const hipError_t e2 = hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);  // later work on the ctx stream sees both groups' results
-    ctx->win_lo = 0;
-    ctx->win_n = batch;
-    if (rc) return rc;
-    PDEOPT_HIP_CHECK(ctx, e1);
-    PDEOPT_HIP_CHECK(ctx, e2);
-    ctx->Y = y_final;
-    ctx->TA = ta_final;
-    return rc;
-  }
-  for (int lo = 0; lo < batch; lo += group) {
-    ctx->win_lo = lo;
-    ctx->win_n = std::min(group, batch - lo);
-    void* Y = ctx->Y;
-    void* TA = ctx->TA;
-    for (int64_t s = done; s < n && !rc; ++s) {
-      if (euler2 && s + 1 < n) {
-        rc = euler_pair(Y, TA);
-        ++s;
-      } else {
-        rc = substep(Y, TA, s);
-      }
-    }
-    y_final = Y;  // every group performs the same number of swaps
-    ta_final = TA;
-    if (rc) break;
-  }
-  ctx->win_lo = 0;
-  ctx->win_n = batch;
-  ctx->Y = y_final;
-  ctx->TA = ta_final;
-  return rc;
+  // the substeps the graph did not take, group by group
+  rc = run_groups(ctx, group, side_by_side, done, n, [](const Window&) { return PDEOPT_OK; },
+                  [&](const Window& w, int64_t s, int& took) { return step(w, s, done, took); });
+  if (rc) return rc;
+  if (rotations(n, done) & 1) std::swap(ctx->Y, ctx->TA);
+  return PDEOPT_OK;
 }
 
 void graph_destroy(pdeopt_ctx* ctx) {
@@ -631,7 +550,8 @@ int rk4_phase_plan(pdeopt_ctx* ctx, int* fields, int* nphases) {
 // part: 0 = the whole tile; 1 = interior tiles only, 2 = edge tiles only (fused stage pairs; the caller runs
 // part 1 while the halo exchange of this phase is in flight and part 2 after pdeopt_halo_unpack).  The
 // substep's buffer rotation happens with the LAST launch of the last phase (part 0 or 2).
-int rk4_phase(pdeopt_ctx* ctx, int phase, double dt, int part) {
+// io: where the halo-8 launches find the state's halo and put the new state's strip (rk4_substep_h8)
+static int rk4_phase_io(pdeopt_ctx* ctx, int phase, double dt, int part, HaloIo io) {
   if (ctx->prob.equation == PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "no explicit RHS for the GPE");
   if (part < 0 || part > 2) return fail(ctx, PDEOPT_EINVAL, "part %d outside 0..2", part);
   int rc;
@@ -641,40 +561,39 @@ int rk4_phase(pdeopt_ctx* ctx, int phase, double dt, int part) {
   int fields[4], n = 0;
   rk4_phase_plan(ctx, fields, &n);
   if (phase < 0 || phase >= n) return fail(ctx, PDEOPT_EINVAL, "phase %d outside 0..%d", phase, n - 1);
-  ctx->win_lo = 0;
-  ctx->win_n = ctx->prob.batch;
+  const Window w = whole_batch(ctx);
   if (ctx->halo == 8 && n != 2 && n != 1)
     return fail(ctx, PDEOPT_EINVAL, "the halo-8 layout needs the fused Cahn-Hilliard kernels (closure class / tile shape / "
                                     "PDEOPT_OPT_FUSE_STAGES rule them out here): use halo layout 4");
   if (ctx->halo == 8 && part != 0)
     return fail(ctx, PDEOPT_EINVAL, "interior / edge launches belong to the halo-4 layout (two exchanges per substep)");
   if (n == 1) {  // the whole substep in one pass: y (+ halo) -> y'
-    rc = launch_ch_quad(ctx, ctx->Y, ctx->TA, dt);
+    rc = launch_ch_quad(ctx, w, io, ctx->Y, ctx->TA, dt);
     std::swap(ctx->Y, ctx->TA);
     return rc;
   }
   if (n == 2) {
-    ctx->launch_part = part;
+    io.part = part;
     if (phase == 0) {
-      ctx->pair_ext = ctx->halo == 8 ? 4 : 0;
-      rc = launch_pair_dt(ctx, PAIR_12, ctx->Y, nullptr, nullptr, ctx->TB, ctx->ACC, dt / 2, dt / 6, dt / 2, dt / 3);
-      ctx->pair_ext = 0;
-    } else {
-      rc = launch_pair_dt(ctx, PAIR_34, ctx->TB, ctx->Y, ctx->ACC, ctx->TA, nullptr, dt, dt / 3, 0.0, dt / 6);
-      if (part != 1) std::swap(ctx->Y, ctx->TA);
+      io.ext = ctx->halo == 8 ? 4 : 0;
+      return launch_pair_dt(ctx, w, io, PAIR_12, ctx->Y, nullptr, nullptr, ctx->TB, ctx->ACC, dt / 2, dt / 6, dt / 2, dt / 3);
     }
-    ctx->launch_part = 0;
+    rc = launch_pair_dt(ctx, w, io, PAIR_34, ctx->TB, ctx->Y, ctx->ACC, ctx->TA, nullptr, dt, dt / 3, 0.0, dt / 6);
+    if (part != 1) std::swap(ctx->Y, ctx->TA);
     return rc;
   }
   if (part != 0)
     return fail(ctx, PDEOPT_EINVAL, "interior / edge launches exist for the fused stage pairs only (this problem runs one kernel per stage)");
+  // a phase call carries no time: the decomposed driver runs autonomous equations, t = 0 for any time-dependent term
   switch (phase) {
-    case 0: return launch_stage(ctx, ctx->Y, ctx->Y, ctx->TA, ctx->ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
-    case 1: return launch_stage(ctx, ctx->TA, ctx->Y, ctx->TB, ctx->ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    case 2: return launch_stage(ctx, ctx->TB, ctx->Y, ctx->TA, ctx->ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    default: return launch_stage(ctx, ctx->TA, ctx->Y, ctx->Y, ctx->ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
+    case 0: return launch_stage(ctx, w, 0.0, ctx->Y, ctx->Y, ctx->TA, ctx->ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
+    case 1: return launch_stage(ctx, w, 0.0, ctx->TA, ctx->Y, ctx->TB, ctx->ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    case 2: return launch_stage(ctx, w, 0.0, ctx->TB, ctx->Y, ctx->TA, ctx->ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    default: return launch_stage(ctx, w, 0.0, ctx->TA, ctx->Y, ctx->Y, ctx->ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
   }
 }
+
+int rk4_phase(pdeopt_ctx* ctx, int phase, double dt, int part) { return rk4_phase_io(ctx, phase, dt, part, HaloIo{}); }
 
 // n RK4 substeps of a single-rank padded tile with the loop-back halo exchange, entirely in the library: the
 // per-substep pack -> unpack -> phase sequence of the decomposed driver without a host round trip per call
@@ -718,34 +637,31 @@ int rk4_loopback_advance(pdeopt_ctx* ctx, double dt, int64_t n) {
   return rc;
 }
 
-// halo-8 layout, the state's halo already unpacked: both stage pairs of one substep; the edge tiles of the second
-// write the NEW state's halo strip into `strip` (nullptr: not wanted)
-// the same with the halo taken from the 8 neighbours' OWN strip buffers (peer-mapped exchange: comm.hip)
-int rk4_substep_h8_peer(pdeopt_ctx* ctx, double dt, void* strip, const void* const* peer) {
-  for (int q = 0; q < 8; ++q) ctx->pair_peer[q] = peer[q];
-  const int rc = rk4_substep_h8(ctx, dt, strip, nullptr, nullptr);
-  for (int q = 0; q < 8; ++q) ctx->pair_peer[q] = nullptr;
-  return rc;
+// halo-8 layout: both stage pairs of one substep (or the single-pass kernel).  The first launch reads the state's
+// halo as io says (in the field already, from gathered strips, from the neighbours' own buffers); the last writes the
+// NEW state's halo strip into io.strip (nullptr: not wanted)
+static int rk4_substep_h8_io(pdeopt_ctx* ctx, double dt, const HaloIo& io) {
+  if (ch_quad_chosen(ctx)) return rk4_phase_io(ctx, 0, dt, 0, io);  // one kernel: halo in, the new strip out
+  HaloIo in = io, out{};
+  in.strip = nullptr;
+  out.strip = io.strip;
+  const int rc = rk4_phase_io(ctx, 0, dt, 0, in);
+  return rc ? rc : rk4_phase_io(ctx, 1, dt, 0, out);
 }
 
 int rk4_substep_h8(pdeopt_ctx* ctx, double dt, void* strip, const void* recv, const int* nbr) {
-  ctx->pair_recv = recv;
-  if (recv)
-    for (int q = 0; q < 8; ++q) ctx->pair_nbr[q] = nbr[q];
-  if (ch_quad_chosen(ctx)) {  // one kernel: halo from the gathered strips in, the new strip out
-    ctx->pair_strip = strip;
-    const int rc = rk4_phase(ctx, 0, dt, 0);
-    ctx->pair_recv = nullptr;
-    ctx->pair_strip = nullptr;
-    return rc;
-  }
-  int rc = rk4_phase(ctx, 0, dt, 0);
-  ctx->pair_recv = nullptr;
-  if (rc) return rc;
-  ctx->pair_strip = strip;
-  rc = rk4_phase(ctx, 1, dt, 0);
-  ctx->pair_strip = nullptr;
-  return rc;
+  HaloIo io{};
+  io.strip = strip;
+  io.recv = recv;
+  if (recv) std::copy(nbr, nbr + 8, io.nbr);
+  return rk4_substep_h8_io(ctx, dt, io);
+}
+
+int rk4_substep_h8_peer(pdeopt_ctx* ctx, double dt, void* strip, const void* const* peer) {
+  HaloIo io{};
+  io.strip = strip;
+  std::copy(peer, peer + 8, io.peer);
+  return rk4_substep_h8_io(ctx, dt, io);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -810,10 +726,8 @@ int tsit5_trial_t(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol
   if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
   const int64_t total = (int64_t)(ctx->env_elems * ctx->prob.batch);
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-  if (!ctx->tsit5_fsal_valid) {
-    ctx->cur_t = t;
-    if ((rc = launch_stage(ctx, ctx->Y, ctx->Y, ctx->K[0], nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
-  }
+  const Window w = whole_batch(ctx);
+  if (!ctx->tsit5_fsal_valid && (rc = launch_stage(ctx, w, t, ctx->Y, ctx->Y, ctx->K[0], nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
   // stage 2 input from k1 alone (k1 is the previous step's k7 under FSAL, so nothing could form it earlier)
   {
     LinComb<T> lc{};
@@ -832,11 +746,9 @@ int tsit5_trial_t(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol
     void* in_next = (s & 1) ? ctx->TB : ctx->TA;
     double c[kMaxLc + 1];
     for (int j = 0; j <= s; ++j) c[j] = dt * kTsA[s][j];
-    ctx->cur_t = t + kTsC[s - 1] * dt;
-    if ((rc = launch_stage_lc<T>(ctx, in_s, ctx->Y, ctx->K[s], ctx->K, c, s, in_next))) return rc;
+    if ((rc = launch_stage_lc<T>(ctx, w, t + kTsC[s - 1] * dt, in_s, ctx->Y, ctx->K[s], ctx->K, c, s, in_next))) return rc;
   }
-  ctx->cur_t = t + kTsC[5] * dt;
-  if ((rc = launch_stage(ctx, ctx->TB, ctx->TB, ctx->K[6], nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
+  if ((rc = launch_stage(ctx, w, t + kTsC[5] * dt, ctx->TB, ctx->TB, ctx->K[6], nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
   ctx->tsit5_pending = true;
   if (err) {
     double* part = nullptr;

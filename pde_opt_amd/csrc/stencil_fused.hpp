@@ -721,19 +721,19 @@ bool fused_supported(const pdeopt_ctx* ctx) {
 }
 
 template <typename T, int CL, int PAIR, int RPT>
-int launch_pair_ac_inst(pdeopt_ctx* ctx, const PairArgs<T>& s);  // stencil_fused_ac.hpp
+int launch_pair_ac_inst(pdeopt_ctx* ctx, const Window& w, const PairArgs<T>& s);  // stencil_fused_ac.hpp
 
 template <typename T, int CL, int PAIR, int RPT>
-int launch_pair_ch_inst(pdeopt_ctx* ctx, const PairArgs<T>& s, int ext);
+int launch_pair_ch_inst(pdeopt_ctx* ctx, const Window& w, const PairArgs<T>& s, int ext);
 
 template <typename T, int CL, int PAIR, int RPT>
-int launch_pair_inst(pdeopt_ctx* ctx, const PairArgs<T>& s, int ext = 0) {
-  if (ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN) return launch_pair_ac_inst<T, CL, PAIR, RPT>(ctx, s);
-  return launch_pair_ch_inst<T, CL, PAIR, RPT>(ctx, s, ext);
+int launch_pair_inst(pdeopt_ctx* ctx, const Window& w, const PairArgs<T>& s, int ext = 0) {
+  if (ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN) return launch_pair_ac_inst<T, CL, PAIR, RPT>(ctx, w, s);
+  return launch_pair_ch_inst<T, CL, PAIR, RPT>(ctx, w, s, ext);
 }
 
 template <typename T, int CL, int PAIR, int RPT>
-int launch_pair_ch_inst(pdeopt_ctx* ctx, const PairArgs<T>& s, int ext) {
+int launch_pair_ch_inst(pdeopt_ctx* ctx, const Window& w, const PairArgs<T>& s, int ext) {
   // CH: 2 rows per thread always; 32-row tiles (RPT == 4 on this dispatch axis) are 512-thread blocks
   constexpr int V = VecOf<T>::V;
   constexpr int NT = RPT == 4 ? 512 : 256;
@@ -744,16 +744,16 @@ int launch_pair_ch_inst(pdeopt_ctx* ctx, const PairArgs<T>& s, int ext) {
   // tail margin (common.hpp: pad_rows / pad_ld), nothing is masked
   const int tiles_i = (p.nx + 2 * ext + TX - 1) / TX;
   const int tiles_j = (p.ny + 2 * ext + kLanesPerRow * V - 1) / (kLanesPerRow * V);
-  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * ctx->win_n;
+  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
   const int nblk = (int)nblk64;
   const size_t lds = fused_lds_bytes<T, TX>();
   const bool ragged = ext == 0 && (p.nx % TX != 0 || p.ny % (kLanesPerRow * V) != 0);
   if (ragged)
-    hipLaunchKernelGGL((stage_pair_kernel<T, CL, PAIR, 2, true, NT>), dim3(nblk), dim3(NT), lds, ctx->stream, s, tiles_i,
+    hipLaunchKernelGGL((stage_pair_kernel<T, CL, PAIR, 2, true, NT>), dim3(nblk), dim3(NT), lds, w.stream, s, tiles_i,
                        tiles_j, nblk, tile_flags(nblk, tiles_i, tiles_j));
   else
-    hipLaunchKernelGGL((stage_pair_kernel<T, CL, PAIR, 2, false, NT>), dim3(nblk), dim3(NT), lds, ctx->stream, s, tiles_i,
+    hipLaunchKernelGGL((stage_pair_kernel<T, CL, PAIR, 2, false, NT>), dim3(nblk), dim3(NT), lds, w.stream, s, tiles_i,
                        tiles_j, nblk, tile_flags(nblk, tiles_i, tiles_j));
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;

@@ -162,21 +162,21 @@ __global__ __launch_bounds__(256) void stage_pair_ac_kernel(const PairArgs<T> a,
 }
 
 template <typename T, int CL, int PAIR, int RPT>
-int launch_pair_ac_inst(pdeopt_ctx* ctx, const PairArgs<T>& s) {
+int launch_pair_ac_inst(pdeopt_ctx* ctx, const Window& w, const PairArgs<T>& s) {
   constexpr int V = VecOf<T>::V;
   const pdeopt_problem& p = ctx->prob;
   const int tiles_i = (p.nx + 8 * RPT - 1) / (8 * RPT);
   const int tiles_j = (p.ny + kLanesPerRow * V - 1) / (kLanesPerRow * V);
-  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * ctx->win_n;
+  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
   const int nblk = (int)nblk64;
   const size_t lds = fused_ac_lds_bytes<T, RPT>();
   const bool ragged = p.nx % (8 * RPT) != 0 || p.ny % (kLanesPerRow * V) != 0;
   if (ragged)
-    hipLaunchKernelGGL((stage_pair_ac_kernel<T, CL, PAIR, RPT, true>), dim3(nblk), dim3(256), lds, ctx->stream, s, tiles_i,
+    hipLaunchKernelGGL((stage_pair_ac_kernel<T, CL, PAIR, RPT, true>), dim3(nblk), dim3(256), lds, w.stream, s, tiles_i,
                        tiles_j, nblk, tile_flags(nblk, tiles_i, tiles_j));
   else
-    hipLaunchKernelGGL((stage_pair_ac_kernel<T, CL, PAIR, RPT, false>), dim3(nblk), dim3(256), lds, ctx->stream, s, tiles_i,
+    hipLaunchKernelGGL((stage_pair_ac_kernel<T, CL, PAIR, RPT, false>), dim3(nblk), dim3(256), lds, w.stream, s, tiles_i,
                        tiles_j, nblk, tile_flags(nblk, tiles_i, tiles_j));
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;

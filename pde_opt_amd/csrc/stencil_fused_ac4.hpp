@@ -260,23 +260,23 @@ inline bool ac_quad_supported(const pdeopt_ctx* ctx) {
   return classify_closures(p.mu, p.mob) == CL_POLY;
 }
 
-inline int launch_ac_quad(pdeopt_ctx* ctx, const void* y, void* out, double dt) {
+inline int launch_ac_quad(pdeopt_ctx* ctx, const Window& w, const void* y, void* out, double dt) {
   using G = Ac4Geom;
   const pdeopt_problem& p = ctx->prob;
   QuadArgs<float> s{};
   s.g = make_geo(ctx);
-  const int64_t woff = (int64_t)ctx->win_lo * s.g.bstride;
+  const int64_t woff = (int64_t)w.lo * s.g.bstride;
   s.y = static_cast<const float*>(y) + woff;
   s.out = static_cast<float*>(out) + woff;
   s.dt = (float)dt;
   s.rhx2 = (float)(1.0 / (p.hx * p.hx));
   s.rhy2 = (float)(1.0 / (p.hy * p.hy));
-  s.ep = static_cast<const EnvParams<float>*>(ctx->env_params_dev) + ctx->win_lo;
+  s.ep = static_cast<const EnvParams<float>*>(ctx->env_params_dev) + w.lo;
   s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
   const int tiles_i = (p.nx + G::TX - 1) / G::TX;
   const int tiles_j = (p.ny + G::TY - 1) / G::TY;
-  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * ctx->win_n;
+  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
   const int nblk = (int)nblk64;
   const bool ragged = p.nx % G::TX != 0 || p.ny % G::TY != 0;
@@ -288,7 +288,7 @@ inline int launch_ac_quad(pdeopt_ctx* ctx, const void* y, void* out, double dt) 
 #endif
   const bool m0 = PDEOPT_AC4_M0 && p.mob.n <= 1;  // constant mobility (coefficients past n are stored as zeros)
 #define PDEOPT_QUAD_LAUNCH(CLV, RG) \
-  hipLaunchKernelGGL((ac_rk4_quad_kernel<CLV, RG>), dim3(nblk), dim3(G::NT), G::lds_bytes(), ctx->stream, s, tiles_i, \
+  hipLaunchKernelGGL((ac_rk4_quad_kernel<CLV, RG>), dim3(nblk), dim3(G::NT), G::lds_bytes(), w.stream, s, tiles_i, \
                      tiles_j, nblk, remap)
   if (m0) {
     if (ragged) PDEOPT_QUAD_LAUNCH(CL_POLY_M0, true); else PDEOPT_QUAD_LAUNCH(CL_POLY_M0, false);

@@ -425,21 +425,21 @@ inline bool ch_quad_chosen(const pdeopt_ctx* ctx) {
 }
 
 template <typename G>
-int launch_ch_quad_g(pdeopt_ctx* ctx, const void* y, void* out, double dt) {
+int launch_ch_quad_g(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const void* y, void* out, double dt) {
   const pdeopt_problem& p = ctx->prob;
   Quad4Args<float> s{};
   s.g = make_geo(ctx);
-  const int64_t woff = (int64_t)ctx->win_lo * s.g.bstride;
+  const int64_t woff = (int64_t)w.lo * s.g.bstride;
   s.y = static_cast<const float*>(y) + woff;
   s.out = static_cast<float*>(out) + woff;
   s.dt = (float)dt; s.h2 = (float)(dt / 2); s.h3 = (float)(dt / 3); s.h6 = (float)(dt / 6);
   s.rhx = (float)(0.5 / (p.hx * p.hx)); s.rhy = (float)(0.5 / (p.hy * p.hy));
   s.rhx2 = (float)(1.0 / (p.hx * p.hx)); s.rhy2 = (float)(1.0 / (p.hy * p.hy));
-  s.ep = static_cast<const EnvParams<float>*>(ctx->env_params_dev) + ctx->win_lo;
+  s.ep = static_cast<const EnvParams<float>*>(ctx->env_params_dev) + w.lo;
   s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
   const int tiles_i = p.nx / G::TX, tiles_j = p.ny / G::TY;
-  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * ctx->win_n;
+  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
   const int nblk = (int)nblk64;
   ctx->n_stage_launches++;
@@ -454,16 +454,16 @@ int launch_ch_quad_g(pdeopt_ctx* ctx, const void* y, void* out, double dt) {
       PDEOPT_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       allowed.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(G::NT), lds, ctx->stream, s, tiles_i, tiles_j, nblk, remap);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(G::NT), lds, w.stream, s, tiles_i, tiles_j, nblk, remap);
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     ctx->last_kernel = std::string(name) + (G::TX == 64 ? ",rows64>" : ",rows32>");
     return PDEOPT_OK;
   };
   if (ctx->halo == 8) {
     // decomposed field: halo cells from the gathered strips / the new strip out of the store epilogue (rk4_substep_h8)
-    s.strip = static_cast<float*>(ctx->pair_strip);
+    s.strip = static_cast<float*>(io.strip);
     s.strip_env = 2LL * 8 * p.ny + 2LL * p.nx * 8 + 4LL * 64;
-    fill_neighbour_strips<float>(ctx, s.strip_env * p.batch, s.nbase);
+    fill_neighbour_strips<float>(io, s.strip_env * p.batch, s.nbase);
     if (cl == CL_LOGIT && p.mu.n <= 2) return go(ch_rk4_quad_kernel<CL_LOGIT1, G, true>, "rk4_quad<f32,CH,halo8,logit");
     if (cl == CL_LOGIT) return go(ch_rk4_quad_kernel<CL_LOGIT, G, true>, "rk4_quad<f32,CH,halo8,logit");
     return go(ch_rk4_quad_kernel<CL_POLY, G, true>, "rk4_quad<f32,CH,halo8,poly");
@@ -473,11 +473,11 @@ int launch_ch_quad_g(pdeopt_ctx* ctx, const void* y, void* out, double dt) {
   return go(ch_rk4_quad_kernel<CL_POLY, G>, "rk4_quad<f32,CH,poly");
 }
 
-inline int launch_ch_quad(pdeopt_ctx* ctx, const void* y, void* out, double dt) {
+inline int launch_ch_quad(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const void* y, void* out, double dt) {
 #ifdef PDEOPT_CH4_ROWS16  // A/B build: 16 x 128 tiles, 256 owners + helpers, three workgroups per CU (51.8 KB each)
-  if (ch_quad_tile(ctx) == 32) return launch_ch_quad_g<Ch4GeomT<32, 256, PDEOPT_CH4_ROWS16, 3>>(ctx, y, out, dt);
+  if (ch_quad_tile(ctx) == 32) return launch_ch_quad_g<Ch4GeomT<32, 256, PDEOPT_CH4_ROWS16, 3>>(ctx, w, io, y, out, dt);
 #endif
-  return ch_quad_tile(ctx) == 64 ? launch_ch_quad_g<Ch4GeomT<16>>(ctx, y, out, dt) : launch_ch_quad_g<Ch4GeomT<32>>(ctx, y, out, dt);
+  return ch_quad_tile(ctx) == 64 ? launch_ch_quad_g<Ch4GeomT<16>>(ctx, w, io, y, out, dt) : launch_ch_quad_g<Ch4GeomT<32>>(ctx, w, io, y, out, dt);
 }
 
 }  // namespace pdeopt

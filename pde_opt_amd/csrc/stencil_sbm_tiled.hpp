@@ -225,32 +225,32 @@ bool sbm_tiled_supported(const pdeopt_ctx* ctx) {
 }
 
 template <typename T, int EQ>
-int launch_sbm_tiled_eq(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_sbm_tiled_eq(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   constexpr int V = VecOf<T>::V;
   const pdeopt_problem& p = ctx->prob;
   const int tiles_i = (p.nx + 15) / 16;
   const int tiles_j = (p.ny + kLanesPerRow * V - 1) / (kLanesPerRow * V);
-  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * ctx->win_n;
+  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
   const int nblk = (int)nblk64;
   const size_t lds = sbm_tiled_lds_bytes<T, EQ>();
   const int flags = tile_flags(nblk, tiles_i, tiles_j);
   if (sbm_fast_closures(p))
-    hipLaunchKernelGGL((sbm_tiled_kernel<T, EQ, true>), dim3(nblk), dim3(256), lds, ctx->stream, s, tiles_i, tiles_j, nblk, flags);
+    hipLaunchKernelGGL((sbm_tiled_kernel<T, EQ, true>), dim3(nblk), dim3(256), lds, w.stream, s, tiles_i, tiles_j, nblk, flags);
   else
-    hipLaunchKernelGGL((sbm_tiled_kernel<T, EQ, false>), dim3(nblk), dim3(256), lds, ctx->stream, s, tiles_i, tiles_j, nblk, flags);
+    hipLaunchKernelGGL((sbm_tiled_kernel<T, EQ, false>), dim3(nblk), dim3(256), lds, w.stream, s, tiles_i, tiles_j, nblk, flags);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }
 
 template <typename T>
-int launch_sbm_tiled(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_sbm_tiled(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   if (ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM) {
     ctx->last_kernel = sizeof(T) == 4 ? "sbm_tiled<f32,AC-SBM>" : "sbm_tiled<f64,AC-SBM>";
-    return launch_sbm_tiled_eq<T, PDEOPT_EQ_ALLEN_CAHN_SBM>(ctx, s);
+    return launch_sbm_tiled_eq<T, PDEOPT_EQ_ALLEN_CAHN_SBM>(ctx, w, s);
   }
   ctx->last_kernel = sizeof(T) == 4 ? "sbm_tiled<f32,CH-SBM>" : "sbm_tiled<f64,CH-SBM>";
-  return launch_sbm_tiled_eq<T, PDEOPT_EQ_CAHN_HILLIARD_SBM>(ctx, s);
+  return launch_sbm_tiled_eq<T, PDEOPT_EQ_CAHN_HILLIARD_SBM>(ctx, w, s);
 }
 
 }  // namespace pdeopt

@@ -318,11 +318,11 @@ inline void small_shape(int64_t nvec, int* nt, int* kmax) {
 }
 
 template <typename T, int EQ, int CL>
-int launch_small_k(pdeopt_ctx* ctx, const SmallArgs<T>& s, int nt, int kmax, size_t lds) {
+int launch_small_k(pdeopt_ctx* ctx, const Window& w, const SmallArgs<T>& s, int nt, int kmax, size_t lds) {
   auto go = [&](auto kern) -> int {
     if (lds > 48 * 1024)
       PDEOPT_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(ctx->win_n), dim3(nt), lds, ctx->stream, s);
+    hipLaunchKernelGGL(kern, dim3(w.n), dim3(nt), lds, w.stream, s);
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     return PDEOPT_OK;
   };
@@ -333,14 +333,14 @@ int launch_small_k(pdeopt_ctx* ctx, const SmallArgs<T>& s, int nt, int kmax, siz
   return go(small_persist_kernel<T, EQ, CL, 8, 512>);
 }
 
-// n substeps of Euler / RK4 for the environments of the current window, one launch
+// n substeps of Euler / RK4 for the environments of the window, one launch
 template <typename T>
-int launch_small(pdeopt_ctx* ctx, int integrator, double dt, int64_t n) {
+int launch_small(pdeopt_ctx* ctx, const Window& w, int integrator, double dt, int64_t n) {
   constexpr int V = VecOf<T>::V;
   const pdeopt_problem& p = ctx->prob;
   SmallArgs<T> s{};
   const Geo g = make_geo(ctx);
-  s.y = static_cast<T*>(ctx->Y) + (int64_t)ctx->win_lo * g.bstride;
+  s.y = static_cast<T*>(ctx->Y) + (int64_t)w.lo * g.bstride;
   const SmallDims d = small_dims(p);
   s.nx = d.nx;
   s.ny = d.ny;
@@ -350,7 +350,7 @@ int launch_small(pdeopt_ctx* ctx, int integrator, double dt, int64_t n) {
   s.dt = T(dt); s.h2 = T(dt / 2); s.h3 = T(dt / 3); s.h6 = T(dt / 6);
   s.rhx = T(0.5 * d.rx2); s.rhy = T(0.5 * d.ry2);
   s.rhx2 = T(d.rx2); s.rhy2 = T(d.ry2);
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + ctx->win_lo;
+  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + w.lo;
   s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
   const int64_t nvec = (int64_t)d.nx * (d.ny / V);
@@ -368,12 +368,12 @@ int launch_small(pdeopt_ctx* ctx, int integrator, double dt, int64_t n) {
   ctx->last_kernel = name;
   ctx->n_stage_launches++;
   if (p.equation == PDEOPT_EQ_CAHN_HILLIARD) {
-    if (cl == CL_LOGIT && p.mu.n <= 2) return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT1>(ctx, s, nt, kmax, lds);
-    if (cl == CL_LOGIT) return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT>(ctx, s, nt, kmax, lds);
-    return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_POLY>(ctx, s, nt, kmax, lds);
+    if (cl == CL_LOGIT && p.mu.n <= 2) return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT1>(ctx, w, s, nt, kmax, lds);
+    if (cl == CL_LOGIT) return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT>(ctx, w, s, nt, kmax, lds);
+    return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_POLY>(ctx, w, s, nt, kmax, lds);
   }
-  if (cl == CL_LOGIT) return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_LOGIT>(ctx, s, nt, kmax, lds);
-  return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_POLY>(ctx, s, nt, kmax, lds);
+  if (cl == CL_LOGIT) return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_LOGIT>(ctx, w, s, nt, kmax, lds);
+  return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_POLY>(ctx, w, s, nt, kmax, lds);
 }
 
 }  // namespace pdeopt

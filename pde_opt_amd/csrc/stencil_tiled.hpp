@@ -323,71 +323,71 @@ bool tiled_supported(const pdeopt_ctx* ctx) {
 }
 
 template <typename T, int EQ, int CL, int OUT_MODE, int ACC_MODE, bool Y_FROM_TILE, int RPT>
-int launch_tiled_rpt(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_tiled_rpt(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   constexpr int V = VecOf<T>::V;
   constexpr int kTileRows = 8 * RPT;
   const pdeopt_problem& p = ctx->prob;
   const int tiles_i = (p.nx + kTileRows - 1) / kTileRows;
   const int tiles_j = (p.ny + kLanesPerRow * V - 1) / (kLanesPerRow * V);
-  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * ctx->win_n;
+  const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
   const int nblk = (int)nblk64;
   const size_t lds = tiled_lds_bytes<T, EQ, RPT>();
   hipLaunchKernelGGL((stage_tiled_kernel<T, EQ, CL, OUT_MODE, ACC_MODE, Y_FROM_TILE, RPT>), dim3(nblk),
-                     dim3(RPT == 4 ? 512 : 256), lds, ctx->stream, s, tiles_i, tiles_j, nblk,
+                     dim3(RPT == 4 ? 512 : 256), lds, w.stream, s, tiles_i, tiles_j, nblk,
                      tile_flags(nblk, tiles_i, tiles_j));
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }
 
 template <typename T, int EQ, int CL, int OUT_MODE, int ACC_MODE, bool Y_FROM_TILE>
-int launch_tiled_inst(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_tiled_inst(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   if (tiled_rpt(ctx) == 2)
-    return launch_tiled_rpt<T, EQ, CL, OUT_MODE, ACC_MODE, Y_FROM_TILE, 2>(ctx, s);
-  return launch_tiled_rpt<T, EQ, CL, OUT_MODE, ACC_MODE, Y_FROM_TILE, 4>(ctx, s);
+    return launch_tiled_rpt<T, EQ, CL, OUT_MODE, ACC_MODE, Y_FROM_TILE, 2>(ctx, w, s);
+  return launch_tiled_rpt<T, EQ, CL, OUT_MODE, ACC_MODE, Y_FROM_TILE, 4>(ctx, w, s);
 }
 
 template <typename T, int EQ, int CL>
-int launch_tiled_modes(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_tiled_modes(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   const bool in_is_y = (s.in == s.y);
   // the in-place mobility pass (CH + generic closures) destroys u in the tile
   constexpr bool kCanReuseTile = !(EQ == PDEOPT_EQ_CAHN_HILLIARD && CL == CL_GENERIC);
   const int om = s.out_mode, am = s.acc_mode;
   if (om == OUT_K && am == ACC_NONE)
-    return launch_tiled_inst<T, EQ, CL, OUT_K, ACC_NONE, false>(ctx, s);
+    return launch_tiled_inst<T, EQ, CL, OUT_K, ACC_NONE, false>(ctx, w, s);
   if (om == OUT_K_LC && am == ACC_NONE)
-    return launch_tiled_inst<T, EQ, CL, OUT_K_LC, ACC_NONE, false>(ctx, s);
+    return launch_tiled_inst<T, EQ, CL, OUT_K_LC, ACC_NONE, false>(ctx, w, s);
   if (om == OUT_Y_PLUS_AK && am == ACC_NONE) {
     if constexpr (kCanReuseTile)
-      if (in_is_y) return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_NONE, true>(ctx, s);
-    return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_NONE, false>(ctx, s);
+      if (in_is_y) return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_NONE, true>(ctx, w, s);
+    return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_NONE, false>(ctx, w, s);
   }
   if (om == OUT_Y_PLUS_AK && am == ACC_INIT) {
     if constexpr (kCanReuseTile)
-      if (in_is_y) return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_INIT, true>(ctx, s);
-    return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_INIT, false>(ctx, s);
+      if (in_is_y) return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_INIT, true>(ctx, w, s);
+    return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_INIT, false>(ctx, w, s);
   }
   if (om == OUT_Y_PLUS_AK && am == ACC_ADD)
-    return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_ADD, false>(ctx, s);
+    return launch_tiled_inst<T, EQ, CL, OUT_Y_PLUS_AK, ACC_ADD, false>(ctx, w, s);
   if (om == OUT_ACC_PLUS_BK && am == ACC_NONE)
-    return launch_tiled_inst<T, EQ, CL, OUT_ACC_PLUS_BK, ACC_NONE, false>(ctx, s);
+    return launch_tiled_inst<T, EQ, CL, OUT_ACC_PLUS_BK, ACC_NONE, false>(ctx, w, s);
   return fail(ctx, PDEOPT_EINVAL, "stage mode (%d,%d) has no tiled kernel", om, am);
 }
 
 template <typename T, int EQ>
-int launch_tiled_cl(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_tiled_cl(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   switch (classify_closures(ctx->prob.mu, ctx->prob.mob)) {
     case CL_POLY:
-      return launch_tiled_modes<T, EQ, CL_POLY>(ctx, s);
+      return launch_tiled_modes<T, EQ, CL_POLY>(ctx, w, s);
     case CL_LOGIT:
-      return launch_tiled_modes<T, EQ, CL_LOGIT>(ctx, s);
+      return launch_tiled_modes<T, EQ, CL_LOGIT>(ctx, w, s);
     default:
-      return launch_tiled_modes<T, EQ, CL_GENERIC>(ctx, s);
+      return launch_tiled_modes<T, EQ, CL_GENERIC>(ctx, w, s);
   }
 }
 
 template <typename T>
-int launch_tiled(pdeopt_ctx* ctx, const StageArgs<T>& s) {
+int launch_tiled(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   const int cl = classify_closures(ctx->prob.mu, ctx->prob.mob);
   static const char* kClName[] = {"generic", "poly", "logit"};
   char name[96];
@@ -396,8 +396,8 @@ int launch_tiled(pdeopt_ctx* ctx, const StageArgs<T>& s) {
            8 * tiled_rpt(ctx));
   ctx->last_kernel = name;
   if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD)
-    return launch_tiled_cl<T, PDEOPT_EQ_CAHN_HILLIARD>(ctx, s);
-  return launch_tiled_cl<T, PDEOPT_EQ_ALLEN_CAHN>(ctx, s);
+    return launch_tiled_cl<T, PDEOPT_EQ_CAHN_HILLIARD>(ctx, w, s);
+  return launch_tiled_cl<T, PDEOPT_EQ_ALLEN_CAHN>(ctx, w, s);
 }
 
 }  // namespace pdeopt

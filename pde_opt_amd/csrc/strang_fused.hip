@@ -20,6 +20,7 @@
 #include <complex>
 
 #include "common.hpp"
+#include "groups.hpp"
 #include "fft_lds.hpp"
 #include "fft_reg.hpp"
 #include "fft_reg32.hpp"
@@ -379,7 +380,7 @@ template <typename T>
 int row_pass_rows_rt(int ny) { return ny <= 512 ? 256 / (ny / 8) : 256 / (ny / 16); }
 
 template <typename T, int N, int MODE>
-int launch_row(pdeopt_ctx* ctx, StrangFused& sf, double tr, double ti, double t = 0.0) {
+int launch_row(pdeopt_ctx* ctx, const Window& w, StrangFused& sf, double tr, double ti, double t = 0.0) {
   const pdeopt_problem& p = ctx->prob;
   const AuxField& pot = ctx->aux[PDEOPT_AUX_GPE_POTENTIAL];
   constexpr int F = row_pass_rows<T, N>();
@@ -387,32 +388,32 @@ int launch_row(pdeopt_ctx* ctx, StrangFused& sf, double tr, double ti, double t 
   auto kern = strang_row_reg_kernel<T, N, MODE>;
   int rc = allow_lds(ctx, kern, lds);
   if (rc) return rc;
-  // environment window [win_lo, win_lo + win_n): all pointers pre-offset, the kernel sees win_n environments
-  const int64_t cells = (int64_t)p.nx * p.ny, w0 = ctx->win_lo;
-  const int blocks = (int)((int64_t)ctx->win_n * p.nx / F);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, ctx->stream, (Cx<T>*)ctx->Y + w0 * cells,
+  // environment window [w.lo, w.lo + w.n): all pointers pre-offset, the kernel sees w.n environments
+  const int64_t cells = (int64_t)p.nx * p.ny, w0 = w.lo;
+  const int blocks = (int)((int64_t)w.n * p.nx / F);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (Cx<T>*)ctx->Y + w0 * cells,
                      (T*)sf.dens + w0 * cells, pot.dev ? (const T*)pot.dev + (pot.per_env ? w0 * cells : 0) : nullptr,
                      pot.per_env ? cells : (int64_t)0, (const EnvParams<T>*)ctx->env_params_dev + w0,
                      (const Cx<T>*)sf.tw_y, (T)tr, (T)ti, p.nx, sf.partial + w0 * (p.nx / F),
-                     MODE == ROW_MID ? make_spot_args<T>(ctx, t) : SpotArgs<T>{});
+                     MODE == ROW_MID ? make_spot_args<T>(ctx, w.lo, t) : SpotArgs<T>{});
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }
 
 template <typename T, int N, bool SCALED>
-int launch_col(pdeopt_ctx* ctx, StrangFused& sf) {
+int launch_col(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
   const pdeopt_problem& p = ctx->prob;
   constexpr int C = cols_per_block<T>();
   constexpr int PTS = col_pts<T, N>();
-  const int64_t cells = (int64_t)p.nx * p.ny, w0 = ctx->win_lo;
+  const int64_t cells = (int64_t)p.nx * p.ny, w0 = w.lo;
   const int bpe = p.nx / row_pass_rows_rt<T>(p.ny);  // norm partials per environment
   if constexpr (col_use32<T, N>()) {
     const size_t lds = (size_t)C * kCol32Pitch * sizeof(T);
     auto kern = strang_col32_kernel<T, C, SCALED, false>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ny / C, ctx->win_n), dim3(C * 32), lds, ctx->stream, (Cx<T>*)ctx->Y + w0 * cells,
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * 32), lds, w.stream, (Cx<T>*)ctx->Y + w0 * cells,
                        (const Cx<T>*)sf.mult, (const Cx<T>*)sf.tw_x, p.ny, (const double*)sf.partial + w0 * bpe, bpe,
                        ctx->strang_dx * ctx->strang_dx, (const EnvParams<T>*)nullptr, T(0));
   } else {
@@ -420,7 +421,7 @@ int launch_col(pdeopt_ctx* ctx, StrangFused& sf) {
     auto kern = strang_col_reg_kernel<T, N, C, PTS, SCALED>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ny / C, ctx->win_n), dim3(C * N / PTS), lds, ctx->stream,
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * N / PTS), lds, w.stream,
                        (Cx<T>*)ctx->Y + w0 * cells, (const Cx<T>*)sf.mult, (const Cx<T>*)sf.tw_x, p.ny,
                        (const double*)sf.partial + w0 * bpe, bpe, ctx->strang_dx * ctx->strang_dx,
                        (const EnvParams<T>*)nullptr, T(0));
@@ -434,18 +435,18 @@ int launch_col(pdeopt_ctx* ctx, StrangFused& sf) {
 #define PDEOPT_FFT_SIZES(X) X(64) X(128) X(256) X(512) X(1024)
 
 template <typename T, int MODE>
-int row_dispatch(pdeopt_ctx* ctx, StrangFused& sf, double tr, double ti, double t = 0.0) {
+int row_dispatch(pdeopt_ctx* ctx, const Window& w, StrangFused& sf, double tr, double ti, double t = 0.0) {
   switch (ctx->prob.ny) {
-#define X(NN) case NN: return launch_row<T, NN, MODE>(ctx, sf, tr, ti, t);
+#define X(NN) case NN: return launch_row<T, NN, MODE>(ctx, w, sf, tr, ti, t);
     PDEOPT_FFT_SIZES(X)
 #undef X
     default: return fail(ctx, PDEOPT_EINVAL, "fused Strang: ny=%d is not covered", ctx->prob.ny);
   }
 }
 template <typename T, bool SCALED>
-int col_dispatch(pdeopt_ctx* ctx, StrangFused& sf) {
+int col_dispatch(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
   switch (ctx->prob.nx) {
-#define X(NN) case NN: return launch_col<T, NN, SCALED>(ctx, sf);
+#define X(NN) case NN: return launch_col<T, NN, SCALED>(ctx, w, sf);
     PDEOPT_FFT_SIZES(X)
 #undef X
     default: return fail(ctx, PDEOPT_EINVAL, "fused Strang: nx=%d is not covered", ctx->prob.nx);
@@ -518,13 +519,8 @@ int strang_fused_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
     group = p.batch;
   } else if (ctx->opt_group_envs > 0) {
     group = (int)std::min<int64_t>(ctx->opt_group_envs, p.batch);
-  } else if (ctx->opt_group_envs == 0) {
-    const size_t per_env = (size_t)cells * (sizeof(Cx<T>) + sizeof(T));
-    const int64_t fit = std::max<int64_t>(1, (int64_t)((192ull << 20) / per_env));
-    if (fit < p.batch && n > 1) {
-      const int ngroups = (int)((p.batch + fit - 1) / fit);
-      group = (p.batch + ngroups - 1) / ngroups;
-    }
+  } else if (ctx->opt_group_envs == 0 && n > 1) {
+    group = cache_group(p.batch, (size_t)cells * (sizeof(Cx<T>) + sizeof(T)), 192ull << 20, false);
   }
   // two groups side by side on two streams, each half the size (PDEOPT_OPT_GROUP_STREAMS; stencil.hip:
   // advance_explicit has the reasoning and the measurement for the explicit integrators)
@@ -535,57 +531,16 @@ int strang_fused_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
     if (ctx->opt_group_envs == 0) group = (group + 1) / 2;
     side_by_side = true;
   }
-  ctx->last_groups = (p.batch + group - 1) / group;
-  auto first = [&]() -> int { return row_dispatch<T, ROW_FIRST>(ctx, sf, tr, ti); };
-  auto substep = [&](int64_t s) -> int {
+  auto first = [&](const Window& w) -> int { return row_dispatch<T, ROW_FIRST>(ctx, w, sf, tr, ti); };
+  auto substep = [&](const Window& w, int64_t s, int&) -> int {
     int r;
-    if ((r = col_dispatch<T, false>(ctx, sf))) return r;
+    if ((r = col_dispatch<T, false>(ctx, w, sf))) return r;
     if (timed && (r = refresh_time_aux(ctx, PDEOPT_AUX_GPE_POTENTIAL, t0 + (double)s * dt))) return r;
-    if ((r = row_dispatch<T, ROW_MID>(ctx, sf, tr, ti, t0 + (double)s * dt))) return r;
-    if ((r = col_dispatch<T, true>(ctx, sf))) return r;
-    return s + 1 < n ? row_dispatch<T, ROW_JOIN>(ctx, sf, tr, ti) : row_dispatch<T, ROW_LAST>(ctx, sf, tr, ti);
+    if ((r = row_dispatch<T, ROW_MID>(ctx, w, sf, tr, ti, t0 + (double)s * dt))) return r;
+    if ((r = col_dispatch<T, true>(ctx, w, sf))) return r;
+    return s + 1 < n ? row_dispatch<T, ROW_JOIN>(ctx, w, sf, tr, ti) : row_dispatch<T, ROW_LAST>(ctx, w, sf, tr, ti);
   };
-  if (side_by_side && ctx->last_groups >= 2) {
-    ctx->last_group_streams = 2;
-    if ((rc = ensure_stream2(ctx))) return rc;
-    PDEOPT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    PDEOPT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    auto on = [&](int lo, bool second, auto fn) -> int {
-      ctx->win_lo = lo;
-      ctx->win_n = std::min(group, p.batch - lo);
-      if (second) std::swap(ctx->stream, ctx->stream2);  // the dispatch helpers take the ctx stream
-      const int r = fn();
-      if (second) std::swap(ctx->stream, ctx->stream2);
-      return r;
-    };
-    for (int lo = 0; lo < p.batch && !rc; lo += 2 * group) {
-      const bool two = lo + group < p.batch;
-      rc = on(lo, false, first);
-      if (two && !rc) rc = on(lo + group, true, first);
-      for (int64_t s = 0; s < n && !rc; ++s) {
-        rc = on(lo, false, [&] { return substep(s); });
-        if (two && !rc) rc = on(lo + group, true, [&] { return substep(s); });
-      }
-    }
-    const hipError_t e1 = hipEventRecord(ctx->ev_join, ctx->stream2);
-    const hipError_t e2 = hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
-    ctx->win_lo = 0;
-    ctx->win_n = p.batch;
-    if (rc) return rc;
-    PDEOPT_HIP_CHECK(ctx, e1);
-    PDEOPT_HIP_CHECK(ctx, e2);
-    ctx->last_kernel = "strang_fused_lds_fft";
-    return PDEOPT_OK;
-  }
-  for (int lo = 0; lo < p.batch && !rc; lo += group) {
-    ctx->win_lo = lo;
-    ctx->win_n = std::min(group, p.batch - lo);
-    if ((rc = first())) break;
-    for (int64_t s = 0; s < n && !rc; ++s) rc = substep(s);
-  }
-  ctx->win_lo = 0;
-  ctx->win_n = p.batch;
-  if (rc) return rc;
+  if ((rc = run_groups(ctx, group, side_by_side, 0, n, first, substep))) return rc;
   ctx->last_kernel = "strang_fused_lds_fft";
   return PDEOPT_OK;
 }
@@ -693,14 +648,14 @@ __global__ __launch_bounds__(256, PDEOPT_IMEX_ROW_WAVES(T, N)) void imex_row_inv
 }
 
 template <typename T, int N>
-int imex_rows(pdeopt_ctx* ctx, StrangFused& sf, bool forward, double dt) {
+int imex_rows(pdeopt_ctx* ctx, const Window& w, StrangFused& sf, bool forward, double dt) {
   using E = typename ImexRowEngine<T, N>::type;
   constexpr int F = 256 / E::TT;
   const pdeopt_problem& p = ctx->prob;
-  // environment window (win_lo even): pointers pre-offset, the kernels see win_n environments
-  const int64_t cells = (int64_t)p.nx * p.ny, w0 = ctx->win_lo;
+  // environment window (w.lo even): pointers pre-offset, the kernels see w.n environments
+  const int64_t cells = (int64_t)p.nx * p.ny, w0 = w.lo;
   const int pack = ctx->imex_per_env ? 1 : 2;  // environments per complex field
-  const int npairs = (ctx->win_n + pack - 1) / pack;
+  const int npairs = (w.n + pack - 1) / pack;
   const size_t lds = (size_t)F * E::NP * sizeof(typename E::LdsT);
   const int blocks = (int)((int64_t)npairs * p.nx / F);
   Cx<T>* const cw = (Cx<T>*)sf.cwork + (w0 / pack) * cells;
@@ -708,14 +663,14 @@ int imex_rows(pdeopt_ctx* ctx, StrangFused& sf, bool forward, double dt) {
     auto kern = imex_row_fwd_reg_kernel<T, N>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, ctx->stream, (const T*)ctx->TA + w0 * cells, cw,
-                       (const Cx<T>*)sf.tw_y, p.nx, ctx->win_n, pack);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (const T*)ctx->TA + w0 * cells, cw,
+                       (const Cx<T>*)sf.tw_y, p.nx, w.n, pack);
   } else {
     auto kern = imex_row_inv_reg_kernel<T, N>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, ctx->stream, (const Cx<T>*)cw, (T*)ctx->Y + w0 * cells,
-                       (const Cx<T>*)sf.tw_y, (T)dt, p.nx, ctx->win_n, pack);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (const Cx<T>*)cw, (T*)ctx->Y + w0 * cells,
+                       (const Cx<T>*)sf.tw_y, (T)dt, p.nx, w.n, pack);
   }
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -723,14 +678,14 @@ int imex_rows(pdeopt_ctx* ctx, StrangFused& sf, bool forward, double dt) {
 }
 
 template <typename T, int N>
-int imex_cols(pdeopt_ctx* ctx, StrangFused& sf) {
+int imex_cols(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
   constexpr int C = cols_per_block<T>();
   constexpr int PTS = col_pts<T, N>();
   const pdeopt_problem& p = ctx->prob;
   const int pack = ctx->imex_per_env ? 1 : 2;
-  const int npairs = (ctx->win_n + pack - 1) / pack;
-  Cx<T>* const cw = (Cx<T>*)sf.cwork + (int64_t)(ctx->win_lo / pack) * p.nx * p.ny;
-  const EnvParams<T>* const ep = ctx->imex_per_env ? (const EnvParams<T>*)ctx->env_params_dev + ctx->win_lo : nullptr;
+  const int npairs = (w.n + pack - 1) / pack;
+  Cx<T>* const cw = (Cx<T>*)sf.cwork + (int64_t)(w.lo / pack) * p.nx * p.ny;
+  const EnvParams<T>* const ep = ctx->imex_per_env ? (const EnvParams<T>*)ctx->env_params_dev + w.lo : nullptr;
   const T inv_n = (T)(1.0 / ((double)p.nx * p.ny));
   // FFT_x -> * multiplier -> IFFT_x, in place
   if constexpr (col_use32<T, N>()) {
@@ -738,14 +693,14 @@ int imex_cols(pdeopt_ctx* ctx, StrangFused& sf) {
     auto kern = ep ? strang_col32_kernel<T, C, false, true> : strang_col32_kernel<T, C, false, false>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * 32), lds, ctx->stream, cw, (const Cx<T>*)sf.imex_mult,
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * 32), lds, w.stream, cw, (const Cx<T>*)sf.imex_mult,
                        (const Cx<T>*)sf.tw_x, p.ny, (const double*)nullptr, 0, 1.0, ep, inv_n);
   } else {
     const size_t lds = (size_t)C * fft_lds_pitch<N>() * sizeof(Cx<T>);
     auto kern = ep ? strang_col_reg_kernel<T, N, C, PTS, false, true> : strang_col_reg_kernel<T, N, C, PTS, false, false>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * N / PTS), lds, ctx->stream, cw,
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * N / PTS), lds, w.stream, cw,
                        (const Cx<T>*)sf.imex_mult, (const Cx<T>*)sf.tw_x, p.ny, (const double*)nullptr, 0, 1.0, ep,
                        inv_n);
   }
@@ -818,25 +773,25 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
   return PDEOPT_OK;
 }
 
-// y += dt L^-1 k on the window [win_lo, win_lo + win_n): row pass, column pass (multiplier), inverse row pass
+// y += dt L^-1 k on the environments of the window: row pass, column pass (multiplier), inverse row pass
 template <typename T>
-int imex_passes_t(pdeopt_ctx* ctx, StrangFused& sf, double dt) {
+int imex_passes_t(pdeopt_ctx* ctx, const Window& w, StrangFused& sf, double dt) {
   const pdeopt_problem& p = ctx->prob;
   int r = PDEOPT_OK;
   switch (p.ny) {
-#define X(NN) case NN: r = imex_rows<T, NN>(ctx, sf, true, dt); break;
+#define X(NN) case NN: r = imex_rows<T, NN>(ctx, w, sf, true, dt); break;
     PDEOPT_FFT_SIZES(X)
 #undef X
   }
   if (r) return r;
   switch (p.nx) {
-#define X(NN) case NN: r = imex_cols<T, NN>(ctx, sf); break;
+#define X(NN) case NN: r = imex_cols<T, NN>(ctx, w, sf); break;
     PDEOPT_FFT_SIZES(X)
 #undef X
   }
   if (r) return r;
   switch (p.ny) {
-#define X(NN) case NN: r = imex_rows<T, NN>(ctx, sf, false, dt); break;
+#define X(NN) case NN: r = imex_rows<T, NN>(ctx, w, sf, false, dt); break;
     PDEOPT_FFT_SIZES(X)
 #undef X
   }
@@ -854,65 +809,19 @@ int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   int group = p.batch;
   if (ctx->opt_group_envs > 0) {
     group = (int)std::min<int64_t>((ctx->opt_group_envs + 1) & ~1LL, p.batch);
-  } else if (ctx->opt_group_envs == 0) {
-    const size_t per_env = (size_t)cells * 3 * sizeof(T);
-    const int64_t fit = std::max<int64_t>(2, (int64_t)((192ull << 20) / per_env) & ~1LL);
-    if (fit < p.batch && n > 1) {
-      const int ngroups = (int)((p.batch + fit - 1) / fit);
-      group = ((p.batch + ngroups - 1) / ngroups + 1) & ~1;
-    }
+  } else if (ctx->opt_group_envs == 0 && n > 1) {
+    group = cache_group(p.batch, (size_t)cells * 3 * sizeof(T), 192ull << 20, true);
   }
-  ctx->last_groups = (p.batch + group - 1) / group;
-  // one substep of the window [win_lo, win_lo + win_n) on ctx->stream
-  auto substep = [&]() -> int {
-    int r;
-    if ((r = launch_rhs_slope(ctx, ctx->Y, ctx->TA, 0.0))) return r;
-    return imex_passes_t<T>(ctx, sf, dt);
-  };
   // Two groups in flight on two streams (PDEOPT_OPT_GROUP_STREAMS = 2 only).  Round 2 measured 1445 vs 1443
   // env-steps/s at 2 x 8 environments against 1 x 16, and slower at 2 x 16 / 2 x 4; round 3 re-measured after the
   // explicit and the Strang pipelines gained 6-7 % from it: see profiles/r03_group_streams_ab.txt.
-  if (ctx->opt_group_streams == 2 && n > 1 && group >= 4 && ctx->last_groups >= 1 && p.batch >= 4) {
-    if (ctx->opt_group_envs == 0) group = std::max(2, (group / 2 + 1) & ~1);
-    ctx->last_groups = (p.batch + group - 1) / group;
-  }
-  if (ctx->opt_group_streams == 2 && ctx->last_groups >= 2 && n > 1) {
-    ctx->last_group_streams = 2;
-    if ((rc = ensure_stream2(ctx))) return rc;
-    PDEOPT_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    PDEOPT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    for (int lo = 0; lo < p.batch && !rc; lo += 2 * group) {
-      const bool two = lo + group < p.batch;
-      for (int64_t s = 0; s < n && !rc; ++s) {
-        ctx->win_lo = lo;
-        ctx->win_n = std::min(group, p.batch - lo);
-        rc = substep();
-        if (two && !rc) {
-          ctx->win_lo = lo + group;
-          ctx->win_n = std::min(group, p.batch - lo - group);
-          std::swap(ctx->stream, ctx->stream2);
-          rc = substep();
-          std::swap(ctx->stream, ctx->stream2);
-        }
-      }
-    }
-    const hipError_t e1 = hipEventRecord(ctx->ev_join, ctx->stream2);
-    const hipError_t e2 = hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
-    ctx->win_lo = 0;
-    ctx->win_n = p.batch;
-    if (rc) return rc;
-    PDEOPT_HIP_CHECK(ctx, e1);
-    PDEOPT_HIP_CHECK(ctx, e2);
-    ctx->last_kernel += "+imex_fused_lds_fft";
-    return PDEOPT_OK;
-  }
-  for (int lo = 0; lo < p.batch && !rc; lo += group) {
-    ctx->win_lo = lo;
-    ctx->win_n = std::min(group, p.batch - lo);
-    for (int64_t s = 0; s < n && !rc; ++s) rc = substep();
-  }
-  ctx->win_lo = 0;
-  ctx->win_n = p.batch;
+  const bool side_by_side = ctx->opt_group_streams == 2 && n > 1;
+  if (side_by_side && group >= 4 && p.batch >= 4 && ctx->opt_group_envs == 0) group = std::max(2, (group / 2 + 1) & ~1);
+  rc = run_groups(ctx, group, side_by_side, 0, n, [](const Window&) { return PDEOPT_OK; },
+                  [&](const Window& w, int64_t, int&) -> int {
+                    const int r = launch_rhs_slope(ctx, w, ctx->Y, ctx->TA, 0.0);
+                    return r ? r : imex_passes_t<T>(ctx, w, sf, dt);
+                  });
   if (rc) return rc;
   ctx->last_kernel += "+imex_fused_lds_fft";
   return PDEOPT_OK;
@@ -939,9 +848,9 @@ int imex_fused_prepare(pdeopt_ctx* ctx, double dt) {
   return ctx->prob.dtype == PDEOPT_F32 ? imex_prepare_t<float>(ctx, dt) : imex_prepare_t<double>(ctx, dt);
 }
 
-int imex_fused_passes(pdeopt_ctx* ctx, double dt) {
+int imex_fused_passes(pdeopt_ctx* ctx, const Window& w, double dt) {
   StrangFused& sf = *ctx->strang_fused;
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_passes_t<float>(ctx, sf, dt) : imex_passes_t<double>(ctx, sf, dt);
+  return ctx->prob.dtype == PDEOPT_F32 ? imex_passes_t<float>(ctx, w, sf, dt) : imex_passes_t<double>(ctx, w, sf, dt);
 }
 
 bool strang_fused_supported(const pdeopt_ctx* ctx) {
