@@ -595,6 +595,48 @@ __global__ __launch_bounds__((coop_threads<T, MODE, EQ, FAST>())) void tsit5_coo
     const int ring_n = 2 * H * (tw + 2 * H) + 2 * H * th;
     constexpr int kRing = sizeof(T) == 8 ? 3 : 6;
     __syncthreads();  // y and the static fields are in place
+    // Wait until the workgroups whose tiles this one's ring is read from, and who read this one's tile, have published
+    // `tag`: the 8 neighbours when every tile is at least H cells wide and high (lanes 0 .. 7, one each; workgroups further
+    // away may be a round ahead or behind: no environment-wide rendezvous), else everybody.  false: the solve was aborted.
+    auto wait_partners = [&](const unsigned tag) -> bool {
+      if (tid < 64) {
+        const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
+        bool gave_up = false;
+        const bool near_only = PDEOPT_COOP_FIXED_NEIGHBOURS && nx / a.px >= H && ny / a.py >= H;
+        const int n_wait = near_only ? 8 : nwg;
+        for (int q = tid; q < n_wait; q += 64) {
+          int i = q;
+          if (near_only) {
+            const int di = q < 3 ? -1 : (q < 5 ? 0 : 1);                       // rows of the 3 x 3 block without its centre
+            const int dj = q < 3 ? q - 1 : (q < 5 ? (q == 3 ? -1 : 1) : q - 6);
+            i = wrap1(wi + di, a.px) * a.py + wrap1(wj + dj, a.py);
+          }
+          for (;;) {
+            if (xload(&tags[i]) >= tag) break;
+            if (xload(a.abort_flag) != 0u) {
+              gave_up = true;
+              break;
+            }
+            if (__builtin_amdgcn_s_memrealtime() - t_in > kCoopTimeoutTicks) {
+              xstore(a.abort_flag, 1u);
+              gave_up = true;
+              break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+          }
+        }
+        const bool any = __any(gave_up);
+        if (tid == 0) red[22] = any ? 1.0 : 0.0;
+      }
+      __syncthreads();
+      return red[22] == 0.0;
+    };
+    // A solve that fits in ONE round (n_sub <= S) never reaches the exchange below, whose tag wait is what keeps a
+    // workgroup from writing its tile back into a.y before its neighbours have read it as their initial halo.  Such a
+    // solve publishes "my initial load is done" here -- every wave's loads have returned: their values are in LDS behind
+    // the barrier above -- and waits for its partners' word before the write-back at the end.
+    const bool one_round = a.n_sub <= (int64_t)S;
+    if (one_round && tid == 0) xstore(&tags[w], 1u);
     // one right-hand side on T + e_out from `src`, its update applied per cell
     auto rhs_update = [&](const T* src, const int e_out, const int slot, auto update) {
       T twa, twb, tsrc;
@@ -650,40 +692,7 @@ __global__ __launch_bounds__((coop_threads<T, MODE, EQ, FAST>())) void tsit5_coo
       __syncthreads();  // every wave's exchange stores have been acknowledged
       const unsigned tag = round + 1u;
       if (tid == 0) xstore(&tags[w], tag);
-      if (tid < 64) {
-        const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
-        bool gave_up = false;
-        // Whom to wait for: the workgroups whose tiles this one's ring is read from, and who read this one's tile -- the 8
-        // neighbours when every tile is at least H cells wide and high (lanes 0 .. 7, one each; workgroups further away may
-        // be a round ahead or behind: no environment-wide rendezvous), else everybody.
-        const bool near_only = PDEOPT_COOP_FIXED_NEIGHBOURS && nx / a.px >= H && ny / a.py >= H;
-        const int n_wait = near_only ? 8 : nwg;
-        for (int q = tid; q < n_wait; q += 64) {
-          int i = q;
-          if (near_only) {
-            const int di = q < 3 ? -1 : (q < 5 ? 0 : 1);                       // rows of the 3 x 3 block without its centre
-            const int dj = q < 3 ? q - 1 : (q < 5 ? (q == 3 ? -1 : 1) : q - 6);
-            i = wrap1(wi + di, a.px) * a.py + wrap1(wj + dj, a.py);
-          }
-          for (;;) {
-            if (xload(&tags[i]) >= tag) break;
-            if (xload(a.abort_flag) != 0u) {
-              gave_up = true;
-              break;
-            }
-            if (__builtin_amdgcn_s_memrealtime() - t_in > kCoopTimeoutTicks) {
-              xstore(a.abort_flag, 1u);
-              gave_up = true;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
-        }
-        const bool any = __any(gave_up);
-        if (tid == 0) red[22] = any ? 1.0 : 0.0;
-      }
-      __syncthreads();
-      if (red[22] != 0.0) return;  // (the host reports the abort; the state is then garbage)
+      if (!wait_partners(tag)) return;  // (the host reports the abort; the state is then garbage)
       {
         T ring[kRing];
         const int trips = (ring_n + NT - 1) / NT;
@@ -710,6 +719,7 @@ __global__ __launch_bounds__((coop_threads<T, MODE, EQ, FAST>())) void tsit5_coo
       }
       __syncthreads();
     }
+    if (one_round && !wait_partners(1u)) return;  // every reader of this tile's cells in a.y has loaded them
     region(0, [&](int o, int r, int c) { yg[(int64_t)(i0 + r) * ny + (j0 + c)] = y[o]; });
     return;
   } else {
@@ -1122,6 +1132,9 @@ inline bool coop_problem_supported(const pdeopt_ctx* ctx) {
     // the kernel evaluates theta(t) / flux(t) itself: constants or polynomials (pdeopt_set_time_terms_poly); a host
     // callback per stage time cannot be asked from inside a launch
     if (ctx->time_fn && !ctx->time_poly_valid) return false;
+    // ... and neither can the host's table of sampled stage times (pdeopt_set_time_table without a callback): the tiled
+    // path looks every stage time up in it and reports the ones it misses; here theta and the flux would stay at the constants
+    if (!ctx->tt_times.empty() && !ctx->time_poly_valid) return false;
     if (!ctx->aux[PDEOPT_AUX_SBM_PSI].dev || !ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev || !ctx->aux[PDEOPT_AUX_SBM_MASK].dev) return false;
   }
   if (eq == PDEOPT_EQ_ADVECTION_DIFFUSION) {
