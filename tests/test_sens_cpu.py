@@ -52,6 +52,28 @@ def test_tangent_rhs_matches_central_differences(name, mu, mob, role, k):
     assert _rel(got, want) <= 1e-7
 
 
+@pytest.mark.parametrize("shape", [(40, 72), (17, 33), (6, 10), (96, 80)], ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("closures", ["legendre16", "mix_entropy_exp_poly", "poly"])
+def test_tangent_rhs_reference_on_ragged_anisotropic_grids(closures, shape):
+    """the reference at the closure sets and grids the GPU kernels are held to in tests/test_gpu_sens_shapes.py:
+    hx != hy, Legendre coefficients up to index 15, POLY under EXP_WRAP and with MIX_ENTROPY"""
+    from test_gpu_sens_shapes import CLOSURES
+
+    mu, mob, params = CLOSURES[closures]
+    hx, hy = 1 / 64, 1 / 128
+    rng = np.random.default_rng(5)
+    u = np.clip(0.5 + 0.1 * rng.standard_normal(shape), 0.1, 0.9)
+    du = 0.05 * rng.standard_normal(shape)
+    eps = 1e-6
+    for role, k in params:
+        def f(e):
+            m, d = S.perturbed(mu, mob, role, k, e)
+            return O.ch_rhs_fd(u + e * du, hx, hy, KAPPA, m, d)
+
+        want = (f(eps) - f(-eps)) / (2 * eps)
+        assert _rel(S.tangent_rhs(u, du, hx, hy, KAPPA, mu, mob, role, k), want) <= 1e-8, (role, k)
+
+
 @pytest.mark.parametrize("integrator", ["imex", "euler"])
 def test_tangent_steps_match_central_differences(integrator):
     mu = ClosureDesc(LEGENDRE, LOGIT_PRIOR, (0.0, -3.0, 0.2))
