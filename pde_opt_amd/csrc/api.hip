@@ -33,6 +33,19 @@ int ensure_buffer(pdeopt_ctx* ctx, void** p, size_t bytes) {
   return PDEOPT_OK;
 }
 
+int ensure_adaptive_block(pdeopt_ctx* ctx, size_t bytes) {
+  if (ctx->adaptive_cap >= bytes) return PDEOPT_OK;
+  if (ctx->adaptive_blk) {
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->adaptive_blk);
+    ctx->adaptive_blk = nullptr;
+    ctx->adaptive_cap = 0;
+  }
+  PDEOPT_HIP_CHECK(ctx, hipMalloc(&ctx->adaptive_blk, bytes));
+  ctx->adaptive_cap = bytes;
+  return PDEOPT_OK;
+}
+
 int ensure_stream2(pdeopt_ctx* ctx) {
   if (ctx->stream2) return PDEOPT_OK;
   PDEOPT_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));

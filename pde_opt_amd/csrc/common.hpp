@@ -177,7 +177,10 @@ struct pdeopt_ctx {
   std::string graph_name;
   int64_t opt_fuse_stages = 0;   // RK4 stage-pair fusion: 0 auto, -1 off (one launch per stage), 1 stage pairs (AC: no single-pass kernel)
   int64_t opt_debug_ablate = 0;  // timing-only ablations, results are wrong when set
-  void* adaptive_blk = nullptr;   // save times + statistics + save slots of pdeopt_tsit5_solve_small
+  // device work block of the one-launch solves (ensure_adaptive_block): the adaptive solves' save times, statistics and
+  // save slots (small_tsit5_solve, coop_tsit5_solve; the latter also its barrier words and partial sums), the
+  // multi-workgroup fixed step's tags (coop_fixed_advance)
+  void* adaptive_blk = nullptr;
   size_t adaptive_cap = 0;
   int64_t opt_group_streams = 0;  // PDEOPT_OPT_GROUP_STREAMS
   // second stream of the two-groups-side-by-side schedule and its fork / join events (created on first use); only
@@ -232,6 +235,12 @@ inline Geo make_geo(const pdeopt_ctx* ctx) {
 
 int fail(pdeopt_ctx* ctx, int code, const char* fmt, ...);
 
+// the 2-D stencil equations' short names in the one-launch solves' last_kernel strings
+inline const char* equation_short_name(int eq) {
+  return eq == PDEOPT_EQ_CAHN_HILLIARD ? "CH" : eq == PDEOPT_EQ_ALLEN_CAHN ? "AC" : eq == PDEOPT_EQ_CAHN_HILLIARD_SBM ? "CH-SBM"
+         : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "AC-SBM" : "AD";
+}
+
 #define PDEOPT_HIP_CHECK(ctx, expr)                                                        \
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
@@ -241,6 +250,9 @@ int fail(pdeopt_ctx* ctx, int code, const char* fmt, ...);
   } while (0)
 
 int ensure_buffer(pdeopt_ctx* ctx, void** p, size_t bytes);
+// ctx->adaptive_blk holds at least `bytes` afterwards.  Kept with the ctx, grow-only: a solve of a 64^2 grid is a few
+// hundred microseconds, a hipMalloc / hipFree pair is not free
+int ensure_adaptive_block(pdeopt_ctx* ctx, size_t bytes);
 int ensure_stream2(pdeopt_ctx* ctx);  // the ctx's second stream + fork / join events, created on first use
 // api.hip: bring a time-dependent auxiliary field to local time t (no-op for static fields)
 int refresh_time_aux(pdeopt_ctx* ctx, int which, double t);

@@ -126,6 +126,20 @@ constexpr unsigned long long kCoopTimeoutTicks = 200000000ull;  // 2 s of s_memr
 // partner before another wave's tile data -- seen once in ~10 runs of the fixed-step mode as a stale ring (an error of
 // one round's increment in a few cells), never in the adaptive step, whose reduction sits between data and slot stores.
 __device__ __forceinline__ void coop_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// The bounded wait of every cross-workgroup rendezvous: poll ready() -- the site's agent-scope load(s) -- until it holds.
+// false: gave up, because the abort flag is up or because 2 s have passed since t_in (this lane then raises the flag).
+template <typename Ready>
+__device__ __forceinline__ bool coop_spin(const unsigned long long t_in, unsigned* abort_flag, Ready ready) {
+  for (;;) {
+    if (ready()) return true;
+    if (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
+    if (__builtin_amdgcn_s_memrealtime() - t_in > kCoopTimeoutTicks) {
+      __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return false;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
 // Counter barrier over the nwg workgroups of one environment (the solve's prologue; the step loop's barrier is the slot
 // exchange in the kernel).  false: the solve was aborted (a partner did not arrive).  one_xcd = no fences: the exchange
 // data is written and read with agent-scope accesses (xstore / xload below), which need no cache maintenance -- see the
@@ -140,15 +154,8 @@ __device__ __forceinline__ bool coop_env_barrier(unsigned* bar, unsigned* abort_
       __hip_atomic_store(&bar[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(&bar[1], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     } else {
-      const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
-      while (__hip_atomic_load(&bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) {
-        if (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-        if (__builtin_amdgcn_s_memrealtime() - t_in > kCoopTimeoutTicks) {
-          __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
+      (void)coop_spin(__builtin_amdgcn_s_memrealtime(), abort_flag,
+                      [&] { return __hip_atomic_load(&bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != g; });
     }
   }
   __syncthreads();
@@ -611,19 +618,7 @@ __global__ __launch_bounds__((coop_threads<T, MODE, EQ, FAST>())) void tsit5_coo
             const int dj = q < 3 ? q - 1 : (q < 5 ? (q == 3 ? -1 : 1) : q - 6);
             i = wrap1(wi + di, a.px) * a.py + wrap1(wj + dj, a.py);
           }
-          for (;;) {
-            if (xload(&tags[i]) >= tag) break;
-            if (xload(a.abort_flag) != 0u) {
-              gave_up = true;
-              break;
-            }
-            if (__builtin_amdgcn_s_memrealtime() - t_in > kCoopTimeoutTicks) {
-              xstore(a.abort_flag, 1u);
-              gave_up = true;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
+          if (!coop_spin(t_in, a.abort_flag, [&] { return xload(&tags[i]) >= tag; })) gave_up = true;
         }
         const bool any = __any(gave_up);
         if (tid == 0) red[22] = any ? 1.0 : 0.0;
@@ -884,21 +879,12 @@ __global__ __launch_bounds__((coop_threads<T, MODE, EQ, FAST>())) void tsit5_coo
         for (int i = tid; i < nwg; i += 64) {
           const unsigned long long* const slot = reinterpret_cast<const unsigned long long*>(parts) + 2 * i;
           unsigned long long w0, w1;
-          for (;;) {
+          const bool arrived = coop_spin(t_in, a.abort_flag, [&] {
             w0 = xload(&slot[0]);
             w1 = xload(&slot[1]);
-            if ((unsigned)w0 == tag && (unsigned)w1 == tag) break;
-            if (xload(a.abort_flag) != 0u) {
-              gave_up = true;
-              break;
-            }
-            if (__builtin_amdgcn_s_memrealtime() - t_in > kCoopTimeoutTicks) {
-              xstore(a.abort_flag, 1u);
-              gave_up = true;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
+            return (unsigned)w0 == tag && (unsigned)w1 == tag;
+          });
+          if (!arrived) gave_up = true;
           red[24 + i] = __longlong_as_double((long long)((w0 & 0xffffffff00000000ull) | (w1 >> 32)));
         }
         // The abort flag is only ever looked at while a slot is missing: a step whose slots all arrived needs no
@@ -1016,7 +1002,7 @@ __global__ __launch_bounds__((coop_threads<T, MODE, EQ, FAST>())) void tsit5_coo
 
 constexpr size_t kCoopLdsMax = 160 * 1024;
 
-// launches whose workgroups wait for each other: one at a time per process (coop_tsit5_solve)
+// launches whose workgroups wait for each other: one at a time per process (coop_run)
 inline std::mutex& coop_launch_mutex() {
   static std::mutex m;
   return m;
@@ -1149,24 +1135,53 @@ bool coop_tsit5_supported(const pdeopt_ctx* ctx) {
   return coop_problem_supported(ctx) && coop_plan<T>(ctx->prob, ctx->num_cus, &pl);
 }
 
-template <typename T>
-int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pdeopt_pid* pid, int64_t max_steps, int n_save,
-                     const double* save_ts, void* save_host, pdeopt_tsit5_stats* stats_host) {
+// One instantiation of the kernel as a launch needs it: the entry point and its workgroup size -- coop_threads<>() of
+// the SAME template arguments, i.e. the kernel's __launch_bounds__
+struct CoopKernel {
+  const void* fn;
+  int threads;
+};
+template <typename T, int MODE, int EQ, bool FAST>
+CoopKernel coop_kernel_of() {
+  return CoopKernel{reinterpret_cast<const void*>(tsit5_coop_kernel<T, EQ, FAST, MODE>), coop_threads<T, MODE, EQ, FAST>()};
+}
+template <typename T, int MODE>
+CoopKernel coop_kernel(int eq, bool fast) {
+  auto of = [fast](auto eq_c) {
+    constexpr int EQ = decltype(eq_c)::value;
+    return fast ? coop_kernel_of<T, MODE, EQ, true>() : coop_kernel_of<T, MODE, EQ, false>();
+  };
+  switch (eq) {
+    case PDEOPT_EQ_CAHN_HILLIARD: return of(std::integral_constant<int, PDEOPT_EQ_CAHN_HILLIARD>{});
+    case PDEOPT_EQ_ALLEN_CAHN: return of(std::integral_constant<int, PDEOPT_EQ_ALLEN_CAHN>{});
+    case PDEOPT_EQ_CAHN_HILLIARD_SBM: return of(std::integral_constant<int, PDEOPT_EQ_CAHN_HILLIARD_SBM>{});
+    case PDEOPT_EQ_ALLEN_CAHN_SBM: return of(std::integral_constant<int, PDEOPT_EQ_ALLEN_CAHN_SBM>{});
+    default: return coop_kernel_of<T, MODE, PDEOPT_EQ_ADVECTION_DIFFUSION, true>();  // (no closures: one instantiation)
+  }
+}
+// the instantiation for the ctx's problem; names it in ctx->last_kernel as "<scheme>_coop<...>"
+template <typename T, int MODE>
+CoopKernel coop_select_kernel(pdeopt_ctx* ctx, const CoopPlan& pl, const char* scheme) {
   const pdeopt_problem& p = ctx->prob;
-  const int batch = p.batch;
-  const int64_t cells = (int64_t)p.nx * p.ny;
-  CoopPlan pl;
-  if (!coop_plan<T>(p, ctx->num_cus, &pl)) return fail(ctx, PDEOPT_EINVAL, "the multi-workgroup adaptive kernel does not cover this problem");
-  const int nwg = pl.px * pl.py;
   const int eq = p.equation;
   const bool sbm = eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM;
-  int rc;
-  // exchange buffers: the integrators' work fields
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+  const bool fast = eq == PDEOPT_EQ_ADVECTION_DIFFUSION || coop_fast_closures(p, sbm);
+  char name[112];
+  snprintf(name, sizeof(name), "%s_coop<%s,%s,%s,%dx%d workgroups>", scheme, sizeof(T) == 4 ? "f32" : "f64", equation_short_name(eq),
+           fast ? "fixed closures" : "generic closures", pl.px, pl.py);
+  ctx->last_kernel = name;
+  return coop_kernel<T, MODE>(eq, fast);
+}
 
+// The arguments both modes set the same way: grid and tiling, the closures, the LDS geometry, the spread over the XCDs, the
+// static fields of the batch's first environment, the time terms of the smoothed-boundary forms.
+// fold_const_poly: a theta(t) / flux(t) polynomial that is constant goes in as tmode 0, its cosines taken HERE (the
+// adaptive solve: the notebook's first solve evaluates nothing per stage).  The fixed step does not fold -- it leaves every
+// polynomial to the kernel's cos, which need not agree with the host's in the last bit.
+template <typename T>
+CoopArgs<T> coop_common_args(const pdeopt_ctx* ctx, const CoopPlan& pl, const CoopLaunchShape& sh, bool fold_const_poly) {
+  const pdeopt_problem& p = ctx->prob;
+  const int eq = p.equation;
   CoopArgs<T> s{};
   s.nx = p.nx; s.ny = p.ny; s.px = pl.px; s.py = pl.py;
   s.bstride = make_geo(ctx).bstride;
@@ -1175,22 +1190,15 @@ int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pd
   s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
   s.fe = ClosureSpec{p.fe.kind, p.fe.flags, p.fe.n};
-  s.t0 = t0; s.t1 = t1; s.dt0 = dt0;
-  const double order = 5.0;
-  s.pid.rtol = pid->rtol; s.pid.atol = pid->atol;
-  s.pid.k1 = (pid->icoeff + pid->pcoeff + pid->dcoeff) / order;
-  s.pid.k2 = -(pid->pcoeff + 2 * pid->dcoeff) / order;
-  s.pid.k3 = pid->dcoeff / order;
-  s.pid.factormin = pid->factormin; s.pid.factormax = pid->factormax; s.pid.safety = pid->safety;
-  s.pid.dtmin = pid->dtmin; s.pid.dtmax = pid->dtmax;
-  s.max_steps = max_steps;
-  s.n_save = n_save;
-  s.save_stride = (int64_t)batch * cells;
   s.rows = pl.rows; s.pitch = pl.pitch; s.red_off = pl.red_off;
-  if (sbm) {
+  s.xs = sh.xs; s.wpx = sh.wpx;
+  if (eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM) {
+    s.s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
+    s.s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
+    s.s2 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
     const bool poly_const = ctx->time_poly_valid && ctx->time_theta[1] == 0.0 && ctx->time_theta[2] == 0.0 && ctx->time_theta[3] == 0.0 &&
                             ctx->time_flux[1] == 0.0 && ctx->time_flux[2] == 0.0 && ctx->time_flux[3] == 0.0;
-    if (poly_const) {  // theta, flux constant (the notebook's first solve): the cosines once, here
+    if (fold_const_poly && poly_const) {
       s.tmode = 0;
       s.tw[0] = cos(ctx->time_theta[0]);
       s.tw[1] = eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? 0.0 : cos(3.14159265358979323846 - ctx->time_theta[0]);
@@ -1202,7 +1210,77 @@ int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pd
       s.tmode = 0;
       for (int i = 0; i < 3; ++i) s.tw[i] = ctx->time_const[i];
     }
+  } else if (eq == PDEOPT_EQ_ADVECTION_DIFFUSION) {
+    s.s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
+    s.s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
+    s.sstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? (int64_t)p.nx * p.ny : 0;
   }
+  return s;
+}
+
+// The launches of a solve: the batch in groups of sh.envs_per_launch environments, each launch with the pointers every
+// mode has (state, parameters, static fields) moved to its first environment e0 and the mode's own by per_launch(c, e0);
+// then queue_results() (device -> host copies of what the mode returns), the abort word s.abort_flag, one synchronisation.
+// Every workgroup of a launch must be resident at once (they wait for each other): one workgroup per compute unit, an
+// environment's workgroups on sh.xs XCDs (blocks are dealt round-robin over the 8 XCDs of 32 CUs each).  Two such
+// launches of one process in flight at once (two engines on two host threads) could each hold half of the chip and starve
+// the other until the 2 s abort: one at a time per process (the call is synchronous anyway); other PROCESSES on the same
+// GPU are the caller's to keep apart.
+template <typename T, typename PerLaunch, typename QueueResults>
+int coop_run(pdeopt_ctx* ctx, const CoopKernel& kern, const CoopPlan& pl, const CoopLaunchShape& sh, const CoopArgs<T>& s,
+             const char* what, PerLaunch per_launch, QueueResults queue_results) {
+  const int batch = ctx->prob.batch;
+  PDEOPT_HIP_CHECK(ctx, hipFuncSetAttribute(kern.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  std::lock_guard<std::mutex> coop_lock(coop_launch_mutex());
+  for (int e0 = 0; e0 < batch; e0 += sh.envs_per_launch) {
+    CoopArgs<T> c = s;
+    c.nenv = std::min(sh.envs_per_launch, batch - e0);
+    c.y = static_cast<T*>(ctx->Y) + (int64_t)e0 * s.bstride;
+    c.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + e0;
+    c.s0 = s.s0 ? s.s0 + (int64_t)e0 * s.sstride : nullptr;
+    c.s1 = s.s1 ? s.s1 + (int64_t)e0 * s.sstride : nullptr;
+    per_launch(c, e0);
+    const int rows_used = (c.nenv + 8 / sh.xs - 1) / (8 / sh.xs);
+    void* params[] = {&c};
+    PDEOPT_HIP_CHECK(ctx, hipLaunchKernel(kern.fn, dim3(8 * rows_used * sh.wpx), dim3(kern.threads), params, pl.lds, ctx->stream));
+    ctx->n_stage_launches++;
+  }
+  int rc;
+  if ((rc = queue_results())) return rc;
+  unsigned aborted = 0;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(&aborted, s.abort_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (aborted)
+    return fail(ctx, PDEOPT_ESTATE, "the multi-workgroup %s was aborted: a workgroup waited more than 2 s for its partners "
+                                    "(the launch's workgroups were not all resident, or the device was shared)", what);
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pdeopt_pid* pid, int64_t max_steps, int n_save,
+                     const double* save_ts, void* save_host, pdeopt_tsit5_stats* stats_host) {
+  const pdeopt_problem& p = ctx->prob;
+  const int batch = p.batch;
+  const int64_t cells = (int64_t)p.nx * p.ny;
+  CoopPlan pl;
+  if (!coop_plan<T>(p, ctx->num_cus, &pl)) return fail(ctx, PDEOPT_EINVAL, "the multi-workgroup adaptive kernel does not cover this problem");
+  const int nwg = pl.px * pl.py;
+  CoopLaunchShape sh;  // (fp64 tiles are small: an environment may need two XCDs)
+  if (!coop_launch_shape(nwg, ctx->num_cus, &sh))
+    return fail(ctx, PDEOPT_EINVAL, "%d workgroups per environment exceed the device's %d compute units", nwg, ctx->num_cus);
+  int rc;
+  // exchange buffers: the integrators' work fields
+  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+
+  CoopArgs<T> s = coop_common_args<T>(ctx, pl, sh, /*fold_const_poly=*/true);
+  s.t0 = t0; s.t1 = t1; s.dt0 = dt0;
+  s.pid = make_pid_consts(*pid);
+  s.max_steps = max_steps;
+  s.n_save = n_save;
+  s.save_stride = (int64_t)batch * cells;
 
   // one device block: save times, statistics, barrier words + abort flag, partial sums, save slots
   const size_t ts_bytes = ((size_t)n_save * sizeof(double) + 255) / 256 * 256;
@@ -1210,110 +1288,40 @@ int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pd
   const size_t bar_bytes = ((size_t)(2 * batch + 1) * sizeof(unsigned) + 255) / 256 * 256;
   const size_t part_bytes = ((size_t)2 * batch * nwg * 2 * sizeof(double) + 255) / 256 * 256;  // [parity][env][workgroup][2 words]
   const size_t out_bytes = (size_t)n_save * batch * cells * sizeof(T);
-  const size_t need = ts_bytes + st_bytes + bar_bytes + part_bytes + out_bytes + 256;
-  if (ctx->adaptive_cap < need) {
-    if (ctx->adaptive_blk) {
-      PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(ctx->adaptive_blk);
-      ctx->adaptive_blk = nullptr;
-      ctx->adaptive_cap = 0;
-    }
-    PDEOPT_HIP_CHECK(ctx, hipMalloc(&ctx->adaptive_blk, need));
-    ctx->adaptive_cap = need;
-  }
+  if ((rc = ensure_adaptive_block(ctx, ts_bytes + st_bytes + bar_bytes + part_bytes + out_bytes + 256))) return rc;
   char* const blk = static_cast<char*>(ctx->adaptive_blk);
   s.save_ts = reinterpret_cast<const double*>(blk);
   pdeopt_tsit5_stats* const stats_dev = reinterpret_cast<pdeopt_tsit5_stats*>(blk + ts_bytes);
   unsigned* const bar_dev = reinterpret_cast<unsigned*>(blk + ts_bytes + st_bytes);
   double* const part_dev = reinterpret_cast<double*>(blk + ts_bytes + st_bytes + bar_bytes);
   T* const out_dev = reinterpret_cast<T*>(blk + ts_bytes + st_bytes + bar_bytes + part_bytes);
+  s.abort_flag = bar_dev + 2 * batch;
   if (n_save) {
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(blk, save_ts, (size_t)n_save * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(out_dev, 0xFF, out_bytes, ctx->stream));  // NaN fill
   }
   PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(stats_dev, 0, st_bytes + bar_bytes + part_bytes, ctx->stream));
 
-  char name[112];
-  const char* eqn = eq == PDEOPT_EQ_CAHN_HILLIARD ? "CH" : eq == PDEOPT_EQ_ALLEN_CAHN ? "AC" : eq == PDEOPT_EQ_CAHN_HILLIARD_SBM ? "CH-SBM"
-                    : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "AC-SBM" : "AD";
-  const bool fast = eq == PDEOPT_EQ_ADVECTION_DIFFUSION || coop_fast_closures(p, sbm);
-  snprintf(name, sizeof(name), "tsit5_coop<%s,%s,%s,%dx%d workgroups>", sizeof(T) == 4 ? "f32" : "f64", eqn, fast ? "fixed closures" : "generic closures",
-           pl.px, pl.py);
-  ctx->last_kernel = name;
+  const CoopKernel kern = coop_select_kernel<T, 0>(ctx, pl, "tsit5");
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-
-  auto kern = [&]() -> const void* {
-#define PDEOPT_COOP_K(EQV) (fast ? reinterpret_cast<const void*>(tsit5_coop_kernel<T, EQV, true>) : reinterpret_cast<const void*>(tsit5_coop_kernel<T, EQV, false>))
-    switch (eq) {
-      case PDEOPT_EQ_CAHN_HILLIARD: return PDEOPT_COOP_K(PDEOPT_EQ_CAHN_HILLIARD);
-      case PDEOPT_EQ_ALLEN_CAHN: return PDEOPT_COOP_K(PDEOPT_EQ_ALLEN_CAHN);
-      case PDEOPT_EQ_CAHN_HILLIARD_SBM: return PDEOPT_COOP_K(PDEOPT_EQ_CAHN_HILLIARD_SBM);
-      case PDEOPT_EQ_ALLEN_CAHN_SBM: return PDEOPT_COOP_K(PDEOPT_EQ_ALLEN_CAHN_SBM);
-      default: return reinterpret_cast<const void*>(tsit5_coop_kernel<T, PDEOPT_EQ_ADVECTION_DIFFUSION, true>);
-    }
-#undef PDEOPT_COOP_K
-  }();
-  PDEOPT_HIP_CHECK(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-  // Every workgroup of a launch must be resident at once (they wait for each other): one workgroup per compute unit,
-  // an environment's workgroups on one XCD (blocks are dealt round-robin over the 8 XCDs of 32 CUs each)
-  const int cus_per_xcd = std::max(1, ctx->num_cus / 8);
-  int xs = 1;
-  while (xs < 8 && (nwg + xs - 1) / xs > cus_per_xcd) xs *= 2;  // fp64 tiles are small: an environment may need two XCDs
-  const int wpx = (nwg + xs - 1) / xs;
-  if (wpx > cus_per_xcd) return fail(ctx, PDEOPT_EINVAL, "%d workgroups per environment exceed the device's %d compute units", nwg, ctx->num_cus);
-  const int rows_per_launch = cus_per_xcd / wpx;
-  const int envs_per_launch = rows_per_launch * (8 / xs);
-  s.xs = xs;
-  s.wpx = wpx;
-
-  const T* s0 = nullptr; const T* s1 = nullptr; const T* s2 = nullptr;
-  int64_t sstride = 0;
-  if (sbm) {
-    s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
-    s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
-    s2 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
-  } else if (eq == PDEOPT_EQ_ADVECTION_DIFFUSION) {
-    s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
-    s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
-    sstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? cells : 0;
-  }
-  // The workgroups of a launch wait for each other: two such launches of one process in flight at once (two engines on
-  // two host threads) could each hold half of the chip and starve the other until the 2 s abort.  One at a time per
-  // process (the call is synchronous anyway); other PROCESSES on the same GPU are the caller's to keep apart.
-  std::lock_guard<std::mutex> coop_lock(coop_launch_mutex());
-  for (int e0 = 0; e0 < batch; e0 += envs_per_launch) {
-    const int ne = std::min(envs_per_launch, batch - e0);
-    CoopArgs<T> c = s;
-    c.nenv = ne;
-    c.y = static_cast<T*>(ctx->Y) + (int64_t)e0 * s.bstride;
-    c.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + e0;
-    c.s0 = s0 ? s0 + (int64_t)e0 * sstride : nullptr;
-    c.s1 = s1 ? s1 + (int64_t)e0 * sstride : nullptr;
-    c.s2 = s2;
-    c.sstride = sstride;
-    c.save_out = out_dev + (int64_t)e0 * cells;
-    c.stats = stats_dev + e0;
-    c.xy[0] = static_cast<T*>(ctx->TA) + (int64_t)e0 * cells; c.xy[1] = static_cast<T*>(ctx->TB) + (int64_t)e0 * cells;
-    c.xk[0] = static_cast<T*>(ctx->ACC) + (int64_t)e0 * cells; c.xk[1] = static_cast<T*>(ctx->KS) + (int64_t)e0 * cells;
-    c.part = part_dev + (size_t)2 * e0 * nwg * 2;
-    c.bar = bar_dev + 2 * e0;
-    c.abort_flag = bar_dev + 2 * batch;
-    const int rows_used = (ne + 8 / xs - 1) / (8 / xs);
-    void* params[] = {&c};
-    PDEOPT_HIP_CHECK(ctx, hipLaunchKernel(kern, dim3(8 * rows_used * wpx), dim3(PDEOPT_COOP_THREADS), params, pl.lds, ctx->stream));
-    ctx->n_stage_launches++;
-  }
-  unsigned aborted = 0;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(stats_host, stats_dev, (size_t)batch * sizeof(pdeopt_tsit5_stats), hipMemcpyDeviceToHost, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(&aborted, bar_dev + 2 * batch, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-  if (n_save) PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(save_host, out_dev, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (aborted)
-    return fail(ctx, PDEOPT_ESTATE, "the multi-workgroup adaptive solve was aborted: a workgroup waited more than 2 s for its partners "
-                                    "(the launch's workgroups were not all resident, or the device was shared)");
-  return PDEOPT_OK;
+  return coop_run<T>(
+      ctx, kern, pl, sh, s, "adaptive solve",
+      [&](CoopArgs<T>& c, int e0) {
+        c.save_out = out_dev + (int64_t)e0 * cells;
+        c.stats = stats_dev + e0;
+        c.xy[0] = static_cast<T*>(ctx->TA) + (int64_t)e0 * cells; c.xy[1] = static_cast<T*>(ctx->TB) + (int64_t)e0 * cells;
+        c.xk[0] = static_cast<T*>(ctx->ACC) + (int64_t)e0 * cells; c.xk[1] = static_cast<T*>(ctx->KS) + (int64_t)e0 * cells;
+        c.part = part_dev + (size_t)2 * e0 * nwg * 2;
+        c.bar = bar_dev + 2 * e0;
+      },
+      [&]() -> int {
+        PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(stats_host, stats_dev, (size_t)batch * sizeof(pdeopt_tsit5_stats), hipMemcpyDeviceToHost, ctx->stream));
+        if (n_save) PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(save_host, out_dev, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return PDEOPT_OK;
+      });
 }
+
 
 
 // ------------------------------------------------------------------------------------- fixed step on several CUs
@@ -1357,105 +1365,26 @@ int coop_fixed_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, in
   if (!coop_plan<T>(p, ctx->num_cus, &pl, rk4 ? 2 : 1) || !coop_launch_shape(pl.px * pl.py, ctx->num_cus, &sh))
     return fail(ctx, PDEOPT_EINVAL, "the multi-workgroup fixed-step kernel does not cover this problem");
   const int nwg = pl.px * pl.py;
-  const int eq = p.equation;
-  const bool sbm = eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM;
   int rc;
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
-  CoopArgs<T> s{};
-  s.nx = p.nx; s.ny = p.ny; s.px = pl.px; s.py = pl.py;
-  s.bstride = make_geo(ctx).bstride;
-  s.rhx = T(1.0 / p.hx); s.rhy = T(1.0 / p.hy);
-  s.rhx2 = T(1.0 / (p.hx * p.hx)); s.rhy2 = T(1.0 / (p.hy * p.hy));
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
-  s.fe = ClosureSpec{p.fe.kind, p.fe.flags, p.fe.n};
+  CoopArgs<T> s = coop_common_args<T>(ctx, pl, sh, /*fold_const_poly=*/false);
   s.t0 = t0; s.dt = dt; s.n_sub = n; s.fixed_rk4 = rk4 ? 1 : 0;
-  s.rows = pl.rows; s.pitch = pl.pitch; s.red_off = pl.red_off;
-  s.xs = sh.xs; s.wpx = sh.wpx;
-  if (sbm) {
-    if (ctx->time_poly_valid) {
-      s.tmode = 1;
-      for (int i = 0; i < 4; ++i) { s.theta[i] = ctx->time_theta[i]; s.flux[i] = ctx->time_flux[i]; }
-    } else {
-      s.tmode = 0;
-      for (int i = 0; i < 3; ++i) s.tw[i] = ctx->time_const[i];
-    }
-  }
   // device block: the published round numbers of every workgroup + the abort flag
-  const size_t need = ((size_t)batch * nwg + 1) * sizeof(unsigned) + 256;
-  if (ctx->adaptive_cap < need) {
-    if (ctx->adaptive_blk) {
-      PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(ctx->adaptive_blk);
-      ctx->adaptive_blk = nullptr;
-      ctx->adaptive_cap = 0;
-    }
-    PDEOPT_HIP_CHECK(ctx, hipMalloc(&ctx->adaptive_blk, need));
-    ctx->adaptive_cap = need;
-  }
+  const size_t tag_bytes = ((size_t)batch * nwg + 1) * sizeof(unsigned);
+  if ((rc = ensure_adaptive_block(ctx, tag_bytes + 256))) return rc;
   unsigned* const tags_dev = static_cast<unsigned*>(ctx->adaptive_blk);
-  unsigned* const abort_dev = tags_dev + (size_t)batch * nwg;
-  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(tags_dev, 0, ((size_t)batch * nwg + 1) * sizeof(unsigned), ctx->stream));
+  s.abort_flag = tags_dev + (size_t)batch * nwg;
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(tags_dev, 0, tag_bytes, ctx->stream));
 
-  const char* eqn = eq == PDEOPT_EQ_CAHN_HILLIARD ? "CH" : eq == PDEOPT_EQ_ALLEN_CAHN ? "AC" : eq == PDEOPT_EQ_CAHN_HILLIARD_SBM ? "CH-SBM"
-                    : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "AC-SBM" : "AD";
-  const bool fast = eq == PDEOPT_EQ_ADVECTION_DIFFUSION || coop_fast_closures(p, sbm);
-  char name[112];
-  snprintf(name, sizeof(name), "%s_coop<%s,%s,%s,%dx%d workgroups>", rk4 ? "rk4" : "euler", sizeof(T) == 4 ? "f32" : "f64", eqn,
-           fast ? "fixed closures" : "generic closures", pl.px, pl.py);
-  ctx->last_kernel = name;
-  auto kern = [&]() -> const void* {
-#define PDEOPT_COOP_KF(EQV) (fast ? reinterpret_cast<const void*>(tsit5_coop_kernel<T, EQV, true, 1>) : reinterpret_cast<const void*>(tsit5_coop_kernel<T, EQV, false, 1>))
-    switch (eq) {
-      case PDEOPT_EQ_CAHN_HILLIARD: return PDEOPT_COOP_KF(PDEOPT_EQ_CAHN_HILLIARD);
-      case PDEOPT_EQ_ALLEN_CAHN: return PDEOPT_COOP_KF(PDEOPT_EQ_ALLEN_CAHN);
-      case PDEOPT_EQ_CAHN_HILLIARD_SBM: return PDEOPT_COOP_KF(PDEOPT_EQ_CAHN_HILLIARD_SBM);
-      case PDEOPT_EQ_ALLEN_CAHN_SBM: return PDEOPT_COOP_KF(PDEOPT_EQ_ALLEN_CAHN_SBM);
-      default: return reinterpret_cast<const void*>(tsit5_coop_kernel<T, PDEOPT_EQ_ADVECTION_DIFFUSION, true, 1>);
-    }
-#undef PDEOPT_COOP_KF
-  }();
-  PDEOPT_HIP_CHECK(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-  // (coop_threads<T, 1, EQ, FAST>() of the instantiation picked above)
-  const int nthreads = sizeof(T) == 4 || (fast && !sbm) ? PDEOPT_COOP_FIXED_THREADS_F32 : PDEOPT_COOP_THREADS;
-  const T* s0 = nullptr; const T* s1 = nullptr; const T* s2 = nullptr;
-  int64_t sstride = 0;
-  if (sbm) {
-    s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
-    s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
-    s2 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
-  } else if (eq == PDEOPT_EQ_ADVECTION_DIFFUSION) {
-    s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
-    s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
-    sstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? cells : 0;
-  }
-  std::lock_guard<std::mutex> coop_lock(coop_launch_mutex());  // (see coop_tsit5_solve)
-  for (int e0 = 0; e0 < batch; e0 += sh.envs_per_launch) {
-    const int ne = std::min(sh.envs_per_launch, batch - e0);
-    CoopArgs<T> c = s;
-    c.nenv = ne;
-    c.y = static_cast<T*>(ctx->Y) + (int64_t)e0 * s.bstride;
-    c.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + e0;
-    c.s0 = s0 ? s0 + (int64_t)e0 * sstride : nullptr;
-    c.s1 = s1 ? s1 + (int64_t)e0 * sstride : nullptr;
-    c.s2 = s2;
-    c.sstride = sstride;
-    c.xy[0] = static_cast<T*>(ctx->TA) + (int64_t)e0 * cells; c.xy[1] = static_cast<T*>(ctx->TB) + (int64_t)e0 * cells;
-    c.tags = tags_dev + (size_t)e0 * nwg;
-    c.abort_flag = abort_dev;
-    const int rows_used = (ne + 8 / sh.xs - 1) / (8 / sh.xs);
-    void* params[] = {&c};
-    PDEOPT_HIP_CHECK(ctx, hipLaunchKernel(kern, dim3(8 * rows_used * sh.wpx), dim3(nthreads), params, pl.lds, ctx->stream));
-    ctx->n_stage_launches++;
-  }
-  unsigned aborted = 0;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(&aborted, abort_dev, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (aborted)
-    return fail(ctx, PDEOPT_ESTATE, "the multi-workgroup fixed-step advance was aborted: a workgroup waited more than 2 s for its partners "
-                                    "(the launch's workgroups were not all resident, or the device was shared)");
-  return PDEOPT_OK;
+  const CoopKernel kern = coop_select_kernel<T, 1>(ctx, pl, rk4 ? "rk4" : "euler");
+  return coop_run<T>(
+      ctx, kern, pl, sh, s, "fixed-step advance",
+      [&](CoopArgs<T>& c, int e0) {
+        c.xy[0] = static_cast<T*>(ctx->TA) + (int64_t)e0 * cells; c.xy[1] = static_cast<T*>(ctx->TB) + (int64_t)e0 * cells;
+        c.tags = tags_dev + (size_t)e0 * nwg;
+      },
+      []() -> int { return PDEOPT_OK; });
 }
 
 }  // namespace pdeopt

@@ -50,6 +50,17 @@ struct PidConsts {
   double factormin, factormax, safety;
   double dtmin, dtmax;  // -inf / +inf: none
 };
+inline PidConsts make_pid_consts(const pdeopt_pid& pid) {
+  const double order = 5.0;  // Tsit5
+  PidConsts c;
+  c.rtol = pid.rtol; c.atol = pid.atol;
+  c.k1 = (pid.icoeff + pid.pcoeff + pid.dcoeff) / order;
+  c.k2 = -(pid.pcoeff + 2 * pid.dcoeff) / order;
+  c.k3 = pid.dcoeff / order;
+  c.factormin = pid.factormin; c.factormax = pid.factormax; c.safety = pid.safety;
+  c.dtmin = pid.dtmin; c.dtmax = pid.dtmax;
+  return c;
+}
 
 template <typename T>
 struct SmallTsit5Args {
@@ -316,13 +327,7 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
   s.t0 = t0; s.t1 = t1; s.dt0 = dt0;
-  const double order = 5.0;
-  s.pid.rtol = pid->rtol; s.pid.atol = pid->atol;
-  s.pid.k1 = (pid->icoeff + pid->pcoeff + pid->dcoeff) / order;
-  s.pid.k2 = -(pid->pcoeff + 2 * pid->dcoeff) / order;
-  s.pid.k3 = pid->dcoeff / order;
-  s.pid.factormin = pid->factormin; s.pid.factormax = pid->factormax; s.pid.safety = pid->safety;
-  s.pid.dtmin = pid->dtmin; s.pid.dtmax = pid->dtmax;
+  s.pid = make_pid_consts(*pid);
   s.max_steps = max_steps;
   s.n_save = n_save;
   s.save_stride = (int64_t)batch * cells;
@@ -331,18 +336,8 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   const size_t ts_bytes = ((size_t)n_save * sizeof(double) + 255) / 256 * 256;
   const size_t st_bytes = ((size_t)batch * sizeof(pdeopt_tsit5_stats) + 255) / 256 * 256;
   const size_t out_bytes = (size_t)n_save * batch * cells * sizeof(T);
-  // kept with the ctx (grow-only): a solve of a 64^2 grid is a few hundred microseconds, a hipMalloc / hipFree pair is not free
-  const size_t need = ts_bytes + st_bytes + out_bytes + 256;
-  if (ctx->adaptive_cap < need) {
-    if (ctx->adaptive_blk) {
-      PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(ctx->adaptive_blk);
-      ctx->adaptive_blk = nullptr;
-      ctx->adaptive_cap = 0;
-    }
-    PDEOPT_HIP_CHECK(ctx, hipMalloc(&ctx->adaptive_blk, need));
-    ctx->adaptive_cap = need;
-  }
+  int rc;
+  if ((rc = ensure_adaptive_block(ctx, ts_bytes + st_bytes + out_bytes + 256))) return rc;
   char* const blk = static_cast<char*>(ctx->adaptive_blk);
   s.save_ts = reinterpret_cast<const double*>(blk);
   s.stats = reinterpret_cast<pdeopt_tsit5_stats*>(blk + ts_bytes);
@@ -366,12 +361,11 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   const int cl = classify_closures(p.mu, p.mob);
   char name[96];
   snprintf(name, sizeof(name), "small_tsit5<%s,%s,%s,%d threads,%d vec/thread>", sizeof(T) == 4 ? "f32" : "f64",
-           p.equation == PDEOPT_EQ_ALLEN_CAHN ? "AC" : "CH", cl == CL_LOGIT ? "logit" : "poly", nt, kmax);
+           equation_short_name(p.equation), cl == CL_LOGIT ? "logit" : "poly", nt, kmax);
   ctx->last_kernel = name;
   ctx->n_stage_launches++;
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-  int rc;
   if (p.equation == PDEOPT_EQ_CAHN_HILLIARD) {
     if (cl == CL_LOGIT && p.mu.n <= 2) rc = launch_small_tsit5_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT1>(ctx, s, nt, kmax, lds);
     else if (cl == CL_LOGIT) rc = launch_small_tsit5_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT>(ctx, s, nt, kmax, lds);
