@@ -1,18 +1,22 @@
-// Forward-mode sensitivities of the Cahn-Hilliard solve with respect to closure coefficients, and the Gauss-Newton
-// sums of a least-squares fit (the reference's PDEModel.train / residuals, pde_opt/pde_model.py:138-460, which
+// Forward-mode sensitivities of the Cahn-Hilliard and Allen-Cahn solves with respect to closure coefficients, and the
+// Gauss-Newton sums of a least-squares fit (the reference's PDEModel.train / residuals, pde_opt/pde_model.py:138-460, which
 // differentiates diffeqsolve with diffrax's ForwardMode adjoint at :410-423).
 //
 // Layout: the ctx is configured with batch (1 + P) B.  Environments [0, B) are the B trajectories; environment
 // B + j B + b holds the tangent du/dp_j of trajectory b.  Per substep
 //   IMEX   k = f(y) for the base block (launch_rhs_slope, the forward solve's own slope kernels),
-//          dk_j = J_f(y) du_j + df/dp_j for the tangent block (2-D: sens_tangent_rhs_kernel; 3-D: sens3d_dmu_kernel
-//          and sens3d_flux_kernel),
+//          dk_j = J_f(y) du_j + df/dp_j for the tangent block (2-D Cahn-Hilliard: sens_tangent_rhs_kernel; 3-D:
+//          sens3d_dmu_kernel and sens3d_flux_kernel; Allen-Cahn: sens_ac_tangent_rhs_kernel),
 //          y += dt L^-1 k over the whole (1 + P) B batch (the forward IMEX transforms): L = 1 + A dt fourier_symbol is
 //          linear and independent of the coefficients (kappa is not trainable), so the tangent of the step is the
 //          same implicit solve applied to the linearised slope.  2-D power-of-two grids 64..1024 run the hand-written
 //          FFT passes (4 launches + 1); other 2-D grids and the 3-D equation run the rocFFT real transforms, multiply
 //          and axpy of the forward rocFFT IMEX loop.  None of the launch counts depends on P.
 //   Euler  the same slope launches, then y += dt k over the whole batch.
+//   RK4    (Allen-Cahn) the classical tableau over the whole batch: per stage the slope launches at the stage's base and
+//          tangent values, then one pointwise update of the stage input and the accumulator -- the exact derivative of
+//          the discrete step.  3 launches per stage, 12 per substep, whatever P is.
+// IMEX is Cahn-Hilliard only: Allen-Cahn publishes no fourier_symbol.
 #include <vector>
 
 #include "closures.hpp"
@@ -198,6 +202,114 @@ __global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
   }
 }
 
+// ---- Allen-Cahn (allen_cahn.py:81-84; the forward kernels' EQ_ALLEN_CAHN with derivs = "fd") ----------------------
+//   f     = -R(u) m,                                     m = mu_h(u) - kappa lap5(u)
+//   df_j  = -(R'(u) du_j + dR/dp_j) m - R(u) (mu_h'(u) du_j + dmu_h/dp_j - kappa lap5(du_j))
+// One workgroup per (tile, trajectory), as the Cahn-Hilliard kernel above; the stencil has radius 1, so only u and du_j
+// are staged in LDS (tile + 1-cell ring) and everything else a cell needs -- u, mu_h, m, R, R', mu_h' -- stays in the
+// registers of the thread that owns it.  A thread owns two neighbouring cells of a row.  Each tangent field is read
+// from HBM once and each tangent slope written once; per tangent only the basis function of closure_dcoef is evaluated.
+template <typename T>
+struct AcTile {
+  static constexpr int V = 16 / (int)sizeof(T);  // cells per 16-byte vector
+  static constexpr int kRows = kTR + 2;
+  static constexpr int kLd = kTC + 2 * V;        // the tile's first column sits at V: 16-byte aligned rows in LDS
+  static constexpr int kSize = kRows * kLd;
+};
+template <typename T> struct AcVec;
+template <> struct AcVec<float> { using type = float4; };
+template <> struct AcVec<double> { using type = double2; };
+
+// s[(r, V - 1 + c)] = f[wrap(i0 - 1 + r), wrap(j0 - 1 + c)] for r < kTR + 2, c < kTC + 2.  Tiles whose kTC columns lie
+// inside an aligned row (`wide`) take them as 16-byte row loads and only the two ring columns as single cells.
+template <typename T>
+__device__ __forceinline__ void ac_stage(T* __restrict__ s, const T* __restrict__ f, int i0, int j0, int nx, int ny,
+                                         bool wide, int tid) {
+  using A = AcTile<T>;
+  using Vec = typename AcVec<T>::type;
+  if (wide) {
+    constexpr int kVecRow = kTC / A::V;
+    for (int q = tid; q < A::kRows * kVecRow; q += 256) {
+      const int r = q / kVecRow, c = (q - r * kVecRow) * A::V;
+      const int64_t row = (int64_t)wrap_idx(i0 + r - 1, nx) * ny;
+      *reinterpret_cast<Vec*>(s + r * A::kLd + A::V + c) = *reinterpret_cast<const Vec*>(f + row + j0 + c);
+    }
+    for (int q = tid; q < 2 * A::kRows; q += 256) {
+      const int r = q >> 1, right = q & 1;
+      const int64_t row = (int64_t)wrap_idx(i0 + r - 1, nx) * ny;
+      s[r * A::kLd + (right ? A::V + kTC : A::V - 1)] = f[row + wrap_idx(right ? j0 + kTC : j0 - 1, ny)];
+    }
+  } else {
+    for (int q = tid; q < A::kRows * kC1; q += 256) {
+      const int r = q / kC1, c = q - r * kC1;
+      s[r * A::kLd + A::V - 1 + c] = f[(int64_t)wrap_idx(i0 + r - 1, nx) * ny + wrap_idx(j0 + c - 1, ny)];
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sens_ac_tangent_rhs_kernel(SensArgs<T> a) {
+  using A = AcTile<T>;
+  __shared__ __attribute__((aligned(16))) T su[A::kSize];
+  __shared__ __attribute__((aligned(16))) T sdu[A::kSize];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.z;
+  const int i0 = blockIdx.y * kTR, j0 = blockIdx.x * kTC;
+  const int nx = a.nx, ny = a.ny;
+  const int64_t cells = (int64_t)nx * ny;
+  const EnvParams<T>& ep = a.ep[b];
+  const T kappa = ep.kappa;
+  const bool wide = ny % A::V == 0 && j0 + kTC <= ny;
+  // this thread's cells: row r, columns c and c + 1 of the tile
+  const int r = tid >> 4, c = (tid & 15) * 2;
+  const int gi = i0 + r, gj = j0 + c;
+  const int o = (r + 1) * A::kLd + A::V + c;
+  ac_stage<T>(su, a.y + (int64_t)b * cells, i0, j0, nx, ny, wide, tid);
+  __syncthreads();
+  T uc[2], muh[2], m[2], R[2], R1[2], mu1[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int q = o + e;
+    uc[e] = su[q];
+    const T lap = (su[q + A::kLd] - T(2) * uc[e] + su[q - A::kLd]) * a.rhx2 + (su[q + 1] - T(2) * uc[e] + su[q - 1]) * a.rhy2;
+    muh[e] = closure_generic<T>(a.mu, ep.mu, uc[e]);
+    m[e] = muh[e] - kappa * lap;
+    R[e] = closure_generic<T>(a.mob, ep.mob, uc[e]);
+    mu1[e] = closure_dc<T>(a.mu, ep.mu, uc[e], muh[e]);
+    R1[e] = closure_dc<T>(a.mob, ep.mob, uc[e], R[e]);
+  }
+  for (int j = 0; j < a.P; ++j) {
+    if (j) __syncthreads();  // the previous tangent's readers are done with sdu
+    const int64_t env = (int64_t)a.B + (int64_t)j * a.B + b;
+    ac_stage<T>(sdu, a.y + env * cells, i0, j0, nx, ny, wide, tid);
+    __syncthreads();
+    const bool on_mu = a.role[j] == PDEOPT_SENS_MU;
+    const int kc = a.index[j];
+    T df[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int q = o + e;
+      const T d = sdu[q];
+      const T lap = (sdu[q + A::kLd] - T(2) * d + sdu[q - A::kLd]) * a.rhx2 + (sdu[q + 1] - T(2) * d + sdu[q - 1]) * a.rhy2;
+      T dmu = mu1[e] * d - kappa * lap;
+      T dR = R1[e] * d;
+      if (on_mu) dmu += closure_dcoef<T>(a.mu, kc, uc[e], muh[e]);
+      else dR += closure_dcoef<T>(a.mob, kc, uc[e], R[e]);
+      df[e] = -(dR * m[e]) - R[e] * dmu;
+    }
+    T* __restrict__ out = a.k + env * cells + (int64_t)gi * ny + gj;
+    if (gi < nx) {
+      if (ny % 2 == 0 && gj + 1 < ny) {
+        if constexpr (sizeof(T) == 4) *reinterpret_cast<float2*>(out) = make_float2(df[0], df[1]);
+        else *reinterpret_cast<double2*>(out) = make_double2(df[0], df[1]);
+      } else {
+        if (gj < ny) out[0] = df[0];
+        if (gj + 1 < ny) out[1] = df[1];
+      }
+    }
+  }
+}
+
 // ---- 3-D: CahnHilliard3DPeriodic.rhs_fd (cahn_hilliard.py:180-200), fields [env][nx][ny][nz] with z contiguous ----
 // Two passes, as the forward ch3d_mu_kernel / ch3d_stage_kernel (stencil_generic.hpp), with their primitives in their
 // order: 7-point Laplacian, face gradients, face averages, face divergence.
@@ -315,6 +427,25 @@ __global__ void sens_axpy_kernel(T* __restrict__ y, const T* __restrict__ k, T d
     y[i] += dt * k[i];
 }
 
+// One RK4 stage update of the whole batch, with the forward stage kernels' expressions (stage_update):
+//   mode 0 (stage 1)     next = y + a k,  acc = y + b k
+//   mode 1 (stages 2, 3) next = y + a k,  acc += b k
+//   mode 2 (stage 4)     y = acc + b k
+template <typename T>
+__global__ void sens_rk4_update_kernel(T* __restrict__ y, const T* __restrict__ k, T* __restrict__ next, T* __restrict__ acc,
+                                       T a, T b, int mode, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const T ki = k[i];
+    if (mode == 2) {
+      y[i] = acc[i] + b * ki;
+    } else {
+      const T yi = y[i];
+      acc[i] = (mode == 0 ? yi : acc[i]) + b * ki;
+      next[i] = yi + a * ki;
+    }
+  }
+}
+
 // ---- Gauss-Newton sums at one save point ------------------------------------------------------------------------
 // Rows: 0 = the residual r = v - pred, 1..P = the tangent dpred_j; pred = snap + theta (y - snap) (the lerp of
 // pdeopt_get_interpolated) or y.  Output index of the product of rows i <= j:
@@ -403,12 +534,12 @@ int check_sens(pdeopt_ctx* ctx) {
 }
 
 template <typename T>
-int launch_tangent_rhs(pdeopt_ctx* ctx) {
+int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
   const pdeopt_problem& p = ctx->prob;
   const Sens& s = *ctx->sens;
   SensArgs<T> a{};
-  a.y = static_cast<const T*>(ctx->Y);
-  a.k = static_cast<T*>(ctx->TA);
+  a.y = static_cast<const T*>(in);
+  a.k = static_cast<T*>(out);
   a.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
   a.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   a.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
@@ -425,7 +556,8 @@ int launch_tangent_rhs(pdeopt_ctx* ctx) {
     a.index[j] = s.index[j];
   }
   const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, s.B);
-  hipLaunchKernelGGL(sens_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  if (p.equation == PDEOPT_EQ_ALLEN_CAHN) hipLaunchKernelGGL(sens_ac_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(sens_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -433,15 +565,15 @@ int launch_tangent_rhs(pdeopt_ctx* ctx) {
 
 // the two 3-D passes over the tangent block; the base slope launch has left the base mu in KS[0, B)
 template <typename T>
-int launch_tangent_rhs3d(pdeopt_ctx* ctx) {
+int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
   const pdeopt_problem& p = ctx->prob;
   const Sens& s = *ctx->sens;
   int rc;
   if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
   Sens3Args<T> a{};
-  a.y = static_cast<const T*>(ctx->Y);
+  a.y = static_cast<const T*>(in);
   a.w = static_cast<T*>(ctx->KS);
-  a.k = static_cast<T*>(ctx->TA);
+  a.k = static_cast<T*>(out);
   a.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
   a.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
   a.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
@@ -468,15 +600,15 @@ int launch_tangent_rhs3d(pdeopt_ctx* ctx) {
   return PDEOPT_OK;
 }
 
-// TA = (f(y_base), J_f du_j + df/dp_j) for the whole batch
-int sens_slopes(pdeopt_ctx* ctx) {
+// out = (f(y_base), J_f du_j + df/dp_j) of the whole batch `in` (the state, or an RK4 stage value)
+int sens_slopes(pdeopt_ctx* ctx, const void* in, void* out) {
   int rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   // the base block's slope; the tangent blocks' slopes come from the kernels below
-  if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, ctx->Y, ctx->TA, 0.0))) return rc;
+  if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, in, out, 0.0))) return rc;
   const bool f32 = ctx->prob.dtype == PDEOPT_F32;
-  if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D) return f32 ? launch_tangent_rhs3d<float>(ctx) : launch_tangent_rhs3d<double>(ctx);
-  return f32 ? launch_tangent_rhs<float>(ctx) : launch_tangent_rhs<double>(ctx);
+  if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D)
+    return f32 ? launch_tangent_rhs3d<float>(ctx, in, out) : launch_tangent_rhs3d<double>(ctx, in, out);
+  return f32 ? launch_tangent_rhs<float>(ctx, in, out) : launch_tangent_rhs<double>(ctx, in, out);
 }
 
 template <typename T>
@@ -486,6 +618,27 @@ int euler_update(pdeopt_ctx* ctx, double dt) {
   hipLaunchKernelGGL(sens_axpy_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<T*>(ctx->Y),
                      static_cast<const T*>(ctx->TA), (T)dt, n);
   ctx->n_stage_launches++;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+// One classical RK4 substep of the whole (1 + P) B batch: K = TA, stage input TB, accumulator ACC
+template <typename T>
+int rk4_substep(pdeopt_ctx* ctx, double dt) {
+  const int64_t n = (int64_t)ctx->env_elems * ctx->prob.batch;
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  T* const y = static_cast<T*>(ctx->Y);
+  T* const k = static_cast<T*>(ctx->TA);
+  T* const in = static_cast<T*>(ctx->TB);
+  T* const acc = static_cast<T*>(ctx->ACC);
+  const double a[4] = {dt / 2, dt / 2, dt, 0.0}, b[4] = {dt / 6, dt / 3, dt / 3, dt / 6};
+  for (int st = 0; st < 4; ++st) {
+    int rc;
+    if ((rc = sens_slopes(ctx, st == 0 ? y : in, k))) return rc;
+    hipLaunchKernelGGL(sens_rk4_update_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, y, static_cast<const T*>(k), in, acc,
+                       (T)a[st], (T)b[st], st == 0 ? 0 : (st == 3 ? 2 : 1), n);
+    ctx->n_stage_launches++;
+  }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }
@@ -547,8 +700,10 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   const pdeopt_problem& p = ctx->prob;
   const bool ch2d = p.equation == PDEOPT_EQ_CAHN_HILLIARD && p.nz <= 1, ch3d = p.equation == PDEOPT_EQ_CAHN_HILLIARD_3D;
-  if (!(ch2d || ch3d) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
-    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D or 3-D Cahn-Hilliard equation with derivs=\"fd\"");
+  const bool ac2d = p.equation == PDEOPT_EQ_ALLEN_CAHN && p.nz <= 1;
+  if (!(ch2d || ch3d || ac2d) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D or 3-D Cahn-Hilliard equation or the periodic 2-D Allen-Cahn "
+                                    "equation with derivs=\"fd\"");
   if (ch3d && sens_cells(ctx) > (int64_t)INT32_MAX / 2)
     return fail(ctx, PDEOPT_EINVAL, "3-D sensitivities index cells in 32 bits (%dx%dx%d)", p.nx, p.ny, p.nz);
   if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT)
@@ -580,7 +735,8 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out) {
   int rc = check_sens(ctx);
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if ((rc = sens_slopes(ctx))) return rc;
+  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA))) return rc;
   if (host_out)
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -588,7 +744,7 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out) {
 }
 
 int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps) {
-  (void)t0;  // the Cahn-Hilliard right-hand side is autonomous
+  (void)t0;  // the Cahn-Hilliard and Allen-Cahn right-hand sides are autonomous
   if (!ctx) return PDEOPT_EINVAL;
   int rc = check_sens(ctx);
   if (rc) return rc;
@@ -596,8 +752,10 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
+  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN, f32 = ctx->prob.dtype == PDEOPT_F32;
   bool fused = false;
   if (integrator == PDEOPT_INT_IMEX) {
+    if (ac) return fail(ctx, PDEOPT_EINVAL, "Allen-Cahn sensitivities support the Euler and RK4 integrators (it has no fourier_symbol)");
     if (!ctx->aux[PDEOPT_AUX_IMEX_SYMBOL].dev)
       return fail(ctx, PDEOPT_ESTATE, "IMEX needs the IMEX_SYMBOL aux field (fourier_symbol)");
     if (ctx->imex_per_env)
@@ -606,25 +764,34 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     // the hand-written FFT passes where they exist (power-of-two 2-D grids 64..1024), rocFFT's real transforms elsewhere
     fused = imex_fused_supported(ctx);
     if ((rc = fused ? imex_fused_prepare(ctx, dt) : imex_rocfft_prepare(ctx, dt))) return rc;
+  } else if (integrator == PDEOPT_INT_RK4 && ac) {
+    if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
   } else if (integrator != PDEOPT_INT_EULER) {
-    return fail(ctx, PDEOPT_EINVAL, "sensitivities support the IMEX and Euler integrators (got %d)", integrator);
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities support the IMEX and Euler integrators for Cahn-Hilliard, Euler and RK4 for "
+                                    "Allen-Cahn (got %d)", integrator);
   }
+  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   for (int64_t s = 0; s < n_substeps; ++s) {
-    if ((rc = sens_slopes(ctx))) return rc;
+    if (integrator == PDEOPT_INT_RK4) {
+      if ((rc = f32 ? rk4_substep<float>(ctx, dt) : rk4_substep<double>(ctx, dt))) return rc;
+      continue;
+    }
+    if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA))) return rc;
     if (integrator == PDEOPT_INT_IMEX && fused) {
       rc = imex_fused_passes(ctx, whole_batch(ctx), dt);
     } else if (integrator == PDEOPT_INT_IMEX) {
       rc = imex_rocfft_solve(ctx, dt);
       ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls; rocFFT may run more than one kernel per transform)
     } else {
-      rc = ctx->prob.dtype == PDEOPT_F32 ? euler_update<float>(ctx, dt) : euler_update<double>(ctx, dt);
+      rc = f32 ? euler_update<float>(ctx, dt) : euler_update<double>(ctx, dt);
     }
     if (rc) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   // after the loop: the base slope launches name their own kernel
-  ctx->last_kernel = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : "sens_tangent_rhs";
-  ctx->last_kernel += integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : "+imex_rocfft_r2c");
+  ctx->last_kernel = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : (ac ? "sens_ac_tangent_rhs" : "sens_tangent_rhs");
+  ctx->last_kernel += integrator == PDEOPT_INT_RK4 ? "+rk4" : (integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : "+imex_rocfft_r2c"));
   return PDEOPT_OK;
 }
 

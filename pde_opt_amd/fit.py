@@ -5,6 +5,9 @@ The reference differentiates the solve with diffrax's ``ForwardMode`` adjoint an
 optimistix (``LevenbergMarquardt`` / ``BFGS``).  Here the forward-mode tangents run on the GPU next to the
 trajectories (``pdeopt_sens_advance``) and only the Gauss-Newton sums come back to the host
 (``pdeopt_sens_accumulate``); the optimisers below work on those sums.
+
+Covered: periodic Cahn-Hilliard in 2-D and 3-D (``mu`` / ``D``; IMEX or Euler) and periodic 2-D Allen-Cahn (``mu`` /
+``R``; Euler or RK4), all with ``derivs="fd"``.
 """
 
 from __future__ import annotations
@@ -23,7 +26,8 @@ from .numerics.functions.legendre import ChemicalPotentialLegendrePolynomials, D
 RTOL = ATOL = 1e-8  # optimistix tolerances of the reference's train (pde_model.py:398-401, 428-431)
 
 # closure classes whose coefficient arrays are trainable, and the constructor argument that holds their role
-_ROLES = {"mu": L.SENS_MU, "D": L.SENS_MOB}
+# ("D" is Cahn-Hilliard's mobility, "R" Allen-Cahn's rate: the engine's second closure either way)
+_ROLES = {"mu": L.SENS_MU, "D": L.SENS_MOB, "R": L.SENS_MOB}
 
 
 # ---- parameters -----------------------------------------------------------------------------------------------------
@@ -39,22 +43,25 @@ class ParamMap:
     keys: List[str]
     templates: list
     sizes: List[int]
+    mu_constant_active: bool = False  # Allen-Cahn: mu_h itself, not only its gradient, enters the right-hand side
 
     @classmethod
-    def of(cls, opt_parameters: dict) -> "ParamMap":
+    def of(cls, opt_parameters: dict, equation_type=None) -> "ParamMap":
+        """``equation_type`` decides whether mu's constant coefficient has a tangent (Allen-Cahn) or is inert
+        (Cahn-Hilliard, and the default)"""
         keys, templates, sizes = [], [], []
         for key, value in opt_parameters.items():
             if key not in _ROLES or not isinstance(value, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
                 raise ValueError(
                     f"opt_parameters[{key!r}]: only the coefficient arrays of ChemicalPotentialLegendrePolynomials / "
-                    "DiffusionLegendrePolynomials in the 'mu' and 'D' roles are trainable (kappa and other scalars would "
-                    "move the implicit operator of the solver); pass them in other_parameters")
+                    "DiffusionLegendrePolynomials in the 'mu' and 'D' (Allen-Cahn: 'R') roles are trainable (kappa and other "
+                    "scalars would move the implicit operator of the solver); pass them in other_parameters")
             keys.append(key)
             templates.append(value)
             sizes.append(len(value.expansion.params))
         if not keys:
             raise ValueError("opt_parameters holds no trainable closure")
-        return cls(keys, templates, sizes)
+        return cls(keys, templates, sizes, _is_allen_cahn(equation_type))
 
     @property
     def size(self) -> int:
@@ -64,9 +71,10 @@ class ParamMap:
         return [(_ROLES[k], i) for k, n in zip(self.keys, self.sizes) for i in range(n)]
 
     def active(self) -> np.ndarray:
-        """entries whose tangent is not identically zero.  mu's constant coefficient is not: only grad mu enters the
-        Cahn-Hilliard right-hand side, so its tangent is never solved for (its Jacobian column is exactly 0)"""
-        return np.array([not (role == L.SENS_MU and i == 0) for role, i in self.all_params()])
+        """entries whose tangent is not identically zero.  For Cahn-Hilliard mu's constant coefficient is not: only
+        grad mu enters the right-hand side, so its tangent is never solved for (its Jacobian column is exactly 0).
+        Allen-Cahn's right-hand side holds mu itself: every entry is active"""
+        return np.array([self.mu_constant_active or not (role == L.SENS_MU and i == 0) for role, i in self.all_params()])
 
     def sens_params(self) -> List[Tuple[int, int]]:
         """the (role, coefficient) pairs of the tangents the GPU advances"""
@@ -94,6 +102,12 @@ class ParamMap:
             else:
                 out[key] = DiffusionLegendrePolynomials(coef)
         return out
+
+
+def _is_allen_cahn(equation_type) -> bool:
+    from .numerics.equations.phase_field import AllenCahn2DPeriodic
+
+    return isinstance(equation_type, type) and issubclass(equation_type, AllenCahn2DPeriodic)
 
 
 def _leaves(obj) -> list:
@@ -193,7 +207,10 @@ def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fie
     Returns the Gauss-Newton sums per trajectory summed over the save points, ``(B, 1 + P + P (P + 1) / 2)`` fp64
     (None without frames), and with ``fields=True`` the states of all ``(1 + P) B`` environments at every save point,
     ``(T, (1 + P) B, *spatial)``."""
-    if solver.integrator not in (L.INT_IMEX, L.INT_EULER):
+    if _is_allen_cahn(type(equation)):
+        if solver.integrator not in (L.INT_EULER, L.INT_RK4):
+            raise NotImplementedError("Allen-Cahn sensitivities support Euler and RK4")
+    elif solver.integrator not in (L.INT_IMEX, L.INT_EULER):
         raise NotImplementedError("sensitivities support SemiImplicitFourierSpectral (IMEX) and Euler")
     y0s = np.asarray(y0s)
     if y0s.dtype not in (np.float32, np.float64):
@@ -355,23 +372,29 @@ def bfgs(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL):
     return p, hist
 
 
-_SUPPORTED = "CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain"
+_SUPPORTED = ("CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain, or AllenCahn2DPeriodic on a "
+              "2-D domain")
 
 
 def reject_unsupported(model):
-    """the configurations the sensitivity path covers: periodic Cahn-Hilliard in 2-D or 3-D, FD derivatives, IMEX or
-    Euler.  The equation / domain pair is checked here, before any equation is built."""
-    from .numerics.equations.phase_field import CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
-    from .numerics.solvers import Euler, SemiImplicitFourierSpectral
+    """the configurations the sensitivity path covers: periodic Cahn-Hilliard in 2-D or 3-D with IMEX or Euler,
+    periodic 2-D Allen-Cahn with Euler or RK4, FD derivatives.  The equation / domain pair is checked here, before any
+    equation is built."""
+    from .numerics.equations.phase_field import AllenCahn2DPeriodic, CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
+    from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral
 
-    dims = {CahnHilliard2DPeriodic: 2, CahnHilliard3DPeriodic: 3}.get(model.equation_type)
+    dims = {CahnHilliard2DPeriodic: 2, CahnHilliard3DPeriodic: 3, AllenCahn2DPeriodic: 2}.get(model.equation_type)
     if dims is None:
         raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
                                   f"{model.equation_type.__name__}")
     if len(model.domain.points) != dims:
         raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
                                   f"{model.equation_type.__name__} on a {len(model.domain.points)}-D domain")
-    if model.solver_type not in (SemiImplicitFourierSpectral, Euler):
+    if model.equation_type is AllenCahn2DPeriodic:
+        if model.solver_type not in (Euler, RK4):
+            raise NotImplementedError(f"train / residuals sensitivities of AllenCahn2DPeriodic support the Euler and RK4 "
+                                      f"solvers, not {model.solver_type.__name__}")
+    elif model.solver_type not in (SemiImplicitFourierSpectral, Euler):
         raise NotImplementedError(f"train / residuals sensitivities support the SemiImplicitFourierSpectral and Euler "
                                   f"solvers, not {model.solver_type.__name__}")
 

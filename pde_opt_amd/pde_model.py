@@ -7,8 +7,8 @@ ignored: forward solves need no adjoint.
 
 ``train`` / ``residuals`` / ``mse`` / ``regularization`` (pde_model.py:138-460) fit closure coefficients to
 trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
-trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D with FD derivatives, IMEX or
-Euler.
+trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D (``mu`` / ``D``; IMEX or
+Euler) and periodic 2-D Allen-Cahn (``mu`` / ``R``; Euler or RK4), with FD derivatives.
 ``optimize`` (pde_model.py:462-551) keeps raising: its objective is an arbitrary function of the solution.
 """
 
@@ -90,13 +90,13 @@ class PDEModel:
 
         ``method="least_squares"``: Levenberg-Marquardt on the Gauss-Newton normal equations (the reference's
         optimistix.LevenbergMarquardt with ForwardMode); ``"mse"``: BFGS on ``mean(r^2) + reg``.  ``data["ys"][i]``
-        is a state of shape ``spatial``: ``(nx, ny)`` for CahnHilliard2DPeriodic, ``(nx, ny, nz)`` for
-        CahnHilliard3DPeriodic.  Returns ``{**fitted, **other_parameters}``; each fitted closure is the class it
+        is a state of shape ``spatial``: ``(nx, ny)`` for CahnHilliard2DPeriodic and AllenCahn2DPeriodic,
+        ``(nx, ny, nz)`` for CahnHilliard3DPeriodic.  Returns ``{**fitted, **other_parameters}``; each fitted closure is the class it
         started as, with its ``prior_fn``."""
         fit.reject_unsupported(self)
         if method not in ("least_squares", "mse"):
             raise ValueError(f"method must be 'least_squares' or 'mse', got {method!r}")
-        pmap = fit.ParamMap.of(opt_parameters)
+        pmap = fit.ParamMap.of(opt_parameters, self.equation_type)
         y0s, values, ts = stack_training_data(data, inds)
         equation0 = self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters})
         fit.check_equation(equation0)

@@ -8,7 +8,9 @@ and, on the host clock around calls that end in a device synchronise,
                        Gauss-Newton sums, plus the normal-equation solve (lm_substeps substeps per solve)
 2-D cases run CahnHilliard2DPeriodic on [0, 1]^2; 3-D cases run CahnHilliard3DPeriodic on the box of
 docs/notebooks/optimization_3D.ipynb (edge 0.01 n), whose fit spans 40400 substeps per sensitivity solve at 32^3.
-Prints one JSON line.  usage: python tools/sens_bench.py [--quick]
+Allen-Cahn rows (AllenCahn2DPeriodic on [0, 1]^2, Euler and RK4) time the same two substeps; their forward substep
+is whatever pdeopt_advance picks for the B trajectories.
+Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only]
 """
 import json
 import sys
@@ -92,8 +94,54 @@ def case(n, B, dtype, P_, nsub, lm_substeps, dims=2):
             "lm_substeps": lm_substeps}
 
 
+def ac_closures(P_):
+    """P = 3: mu a0, a1 + R c0;  P = 7: mu a0..a4 + R c0, c1 (for Allen-Cahn mu's a0 has a tangent)"""
+    if P_ == 3:
+        return {"mu": ChemLeg(np.array([0.0, -3.0]), logit), "R": DiffLeg(np.array([0.0]))}
+    return {"mu": ChemLeg(np.array([0.0, -3.0, 0.1, 0.0, 0.0]), logit), "R": DiffLeg(np.array([0.0, 0.1]))}
+
+
+def ac_case(n, B, dtype, P_, integrator, nsub):
+    dom = P.Domain((n, n), ((0.0, 1.0), (0.0, 1.0)), "dimensionless")
+    opt = ac_closures(P_)
+    eq = P.AllenCahn2DPeriodic(dom, KAPPA, **opt)
+    solver = P.Euler() if integrator == "euler" else P.RK4()
+    rng = np.random.default_rng(0)
+    y0s = np.clip(0.5 + 0.05 * rng.standard_normal((B,) + dom.points), 0.05, 0.95).astype(dtype)
+    sp = fit.ParamMap.of(opt, P.AllenCahn2DPeriodic).sens_params()
+    assert len(sp) == P_
+
+    fwd = P.HipEngine()
+    fwd.configure(dtype=dtype, batch=B, **eq._engine_problem())
+    eq._engine_upload(fwd, 0.0, 1.0)
+    fwd.set_state(y0s)
+    t_fwd = timed(fwd, lambda: fwd.advance(solver.integrator, DT, nsub), 3) / nsub
+    kernel = fwd.last_kernel()
+
+    sens = P.HipEngine()
+    fit._configure(sens, eq, solver, y0s, sp, 0.0, 1.0)
+    t_sens = timed(sens, lambda: sens.sens_advance(solver.integrator, DT, nsub), 3) / nsub
+    return {"equation": "allen_cahn", "integrator": integrator, "n": n, "B": B, "dtype": np.dtype(dtype).name, "P": P_,
+            "fwd_ms_per_substep": t_fwd, "fwd_kernel": kernel, "sens_ms_per_substep": t_sens, "sens_over_fwd": t_sens / t_fwd}
+
+
+def ac_rows(quick):
+    rows = []
+    for n, B, nsub, Ps in ((128, 3, 200, (3, 7)), (1024, 8, 20, (3, 7))):
+        for dtype in (np.float32, np.float64):
+            for integrator in ("euler", "rk4"):
+                for P_ in Ps:
+                    if quick and (n > 128 or P_ > 3):
+                        continue
+                    rows.append(ac_case(n, B, dtype, P_, integrator, nsub))
+    return rows
+
+
 def main():
     quick = "--quick" in sys.argv
+    if "--ac-only" in sys.argv:
+        print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": ac_rows(quick)}))
+        return
     rows = []
     for n, B, nsub, lm in ((128, 3, 200, 4040), (1024, 8, 20, 100)):
         for dtype in (np.float32, np.float64):
@@ -107,7 +155,7 @@ def main():
             if quick and n > 32:
                 continue
             rows.append(case(n, B, dtype, 6, nsub // 4 if quick else nsub, 404 if quick else lm, dims=3))
-    print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": rows}))
+    print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": rows + ac_rows(quick)}))
 
 
 if __name__ == "__main__":
