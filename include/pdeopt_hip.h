@@ -484,14 +484,23 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out);
  * (Allen-Cahn has no fourier_symbol).  The number of launches per substep does not depend on P.  Asynchronous like
  * pdeopt_advance. */
 int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps);
-/* the observed frames of a fit, uploaded once: host is [n_frames][B][nx][ny] (3-D: [n_frames][B][nx][ny][nz]) in the
- * problem dtype */
+/* the observed frames of a fit, uploaded once -- or the cotangents of an objective, uploaded per gradient evaluation
+ * (pdeopt_sens_contract): host is [n_frames][B][nx][ny] (3-D: [n_frames][B][nx][ny][nz]) in the problem dtype */
 int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host);
 /* Gauss-Newton sums of one save point against data frame `frame`: pred = snapshot + theta (state - snapshot) when
  * interp != 0 (LocalLinearInterpolation, as pdeopt_get_interpolated), else the state; r = data - pred.  out is
  * [B][1 + P + P (P + 1) / 2] doubles per trajectory: sum r^2, sum r dpred_j (j < P), sum dpred_i dpred_j (i <= j,
  * row-major upper triangle).  Accumulated in fp64 by a fixed-order reduction: repeated calls give identical bits. */
 int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out);
+/* Contraction of a cotangent field with the tangents at one save point (PDEModel.optimize, pde_model.py:462-551: the
+ * gradient of a scalar J(ys) is dJ/dp_j = sum over save points q of <dJ/dys[q], dys[q]/dp_j>).  The cotangents
+ * g = dJ/dys are uploaded with pdeopt_sens_set_data in place of observed frames: the same buffer and layout,
+ * [n_frames][B][cells] in the problem dtype (a later pdeopt_sens_accumulate needs its frames uploaded again).
+ *   out[b][j] = sum over cells of g[frame][b][cell] dpred_j[b][cell],   out is [B][P] doubles,
+ * dpred_j = tangent j of trajectory b (environment B + j B + b): the state, or snapshot + theta (state - snapshot) when
+ * interp != 0, the expression and dtype of pdeopt_get_interpolated.  P reads per cell (not the P^2 products of the
+ * Gauss-Newton sums), accumulated in fp64 by the same fixed-order reduction: repeated calls give identical bits. */
+int pdeopt_sens_contract(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out);
 
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);

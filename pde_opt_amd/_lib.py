@@ -190,6 +190,7 @@ _SIGNATURES = {
     "pdeopt_sens_advance": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.c_int64]),
     "pdeopt_sens_set_data": (C.c_int, [_VP, C.c_int, _VP]),
     "pdeopt_sens_accumulate": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
+    "pdeopt_sens_contract": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
 }
 
 _lib = None

@@ -17,6 +17,10 @@
 //          tangent values, then one pointwise update of the stage input and the accumulator -- the exact derivative of
 //          the discrete step.  3 launches per stage, 12 per substep, whatever P is.
 // IMEX is Cahn-Hilliard only: Allen-Cahn publishes no fourier_symbol.
+//
+// At a save point the tangents are reduced on the device: to the Gauss-Newton sums of a least-squares fit
+// (pdeopt_sens_accumulate) or, for the gradient of a general objective J(ys) (PDEModel.optimize, pde_model.py:462-551),
+// to the P contractions <dJ/dys[q], du/dp_j> (pdeopt_sens_contract).
 #include <vector>
 
 #include "closures.hpp"
@@ -30,10 +34,10 @@ struct Sens {
   int B = 0, P = 0;
   int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB
   int index[kMaxSens] = {};  // coefficient k of that closure
-  void* data = nullptr;      // [n_frames][B][*spatial] observed frames, problem dtype
+  void* data = nullptr;      // [n_frames][B][*spatial] observed frames or cotangents, problem dtype
   int n_frames = 0;
   size_t data_bytes = 0;
-  double* partial = nullptr;  // [B][K][nblk] per-block sums of the accumulation
+  double* partial = nullptr;  // [B][K][nblk] per-block sums of the accumulation (K = P for the contraction)
   double* sums = nullptr;     // [B][K]
   size_t partial_bytes = 0, sums_bytes = 0;
 };
@@ -512,6 +516,42 @@ __global__ void sens_gn_final_kernel(const double* __restrict__ partial, double*
   sums[q] = s;
 }
 
+// ---- contraction of a cotangent field with the tangents at one save point (PDEModel.optimize) ---------------------
+// grid (blocks per field, B): block (x, b) reads its 2048 cells of g[b] once, keeps them in registers and streams the
+// P tangent fields dpred_j past them (gn_row, rows 1..P: the state or the lerp of pdeopt_get_interpolated); the block
+// total of g dpred_j (the same fixed-order tree in LDS) goes to partial[b][j][x].  O(P) reads per cell, no atomics.
+template <typename T>
+__global__ __launch_bounds__(kGnThreads) void sens_contract_partial_kernel(const T* __restrict__ y, const T* __restrict__ snap,
+                                                                         const T* __restrict__ g, double* __restrict__ partial,
+                                                                         int B, int P, int64_t cells, T theta, int interp) {
+  __shared__ double red[kGnThreads];
+  const int tid = threadIdx.x, blk = blockIdx.x, b = blockIdx.y;
+  const int nblk = gridDim.x;
+  const int64_t c0 = (int64_t)blk * kGnCellsPerBlock + tid;
+  double gv[kGnCellsPerThread];
+#pragma unroll
+  for (int m = 0; m < kGnCellsPerThread; ++m) {
+    const int64_t c = c0 + (int64_t)m * kGnThreads;
+    gv[m] = c < cells ? (double)g[(int64_t)b * cells + c] : 0.0;
+  }
+  for (int j = 1; j <= P; ++j) {
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < kGnCellsPerThread; ++m) {
+      const int64_t c = c0 + (int64_t)m * kGnThreads;
+      if (c < cells) acc += gv[m] * gn_row<T>(y, snap, g, j, b, B, cells, c, theta, interp);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = kGnThreads / 2; s > 0; s >>= 1) {
+      if (tid < s) red[tid] += red[tid + s];
+      __syncthreads();
+    }
+    if (tid == 0) partial[((int64_t)b * P + (j - 1)) * nblk + blk] = red[0];
+    __syncthreads();
+  }
+}
+
 // cells of one environment: nx ny, or nx ny nz for the 3-D equation
 inline int64_t sens_cells(const pdeopt_ctx* ctx) {
   const pdeopt_problem& p = ctx->prob;
@@ -643,12 +683,9 @@ int rk4_substep(pdeopt_ctx* ctx, double dt) {
   return PDEOPT_OK;
 }
 
-template <typename T>
-int gn_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
+// the buffers of the two-stage reductions below: partial[B][K][nblk] and sums[B][K]
+int ensure_sums(pdeopt_ctx* ctx, int K, int nblk) {
   Sens& s = *ctx->sens;
-  const int64_t cells = sens_cells(ctx);
-  const int K = 1 + s.P + s.P * (s.P + 1) / 2;
-  const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
   const size_t pbytes = (size_t)s.B * K * nblk * sizeof(double), sbytes = (size_t)s.B * K * sizeof(double);
   int rc;
   if (s.partial && s.partial_bytes < pbytes) {
@@ -665,17 +702,49 @@ int gn_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* 
   }
   if ((rc = ensure_buffer(ctx, (void**)&s.sums, sbytes))) return rc;
   s.sums_bytes = std::max(s.sums_bytes, sbytes);
+  return PDEOPT_OK;
+}
+
+// sums[b][k] = the block totals of partial[b][k][.] in block order, copied to the host
+int finish_sums(pdeopt_ctx* ctx, int K, int nblk, double* host_out) {
+  Sens& s = *ctx->sens;
+  const int n = s.B * K;
+  hipLaunchKernelGGL(sens_gn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.partial, s.sums, n, nblk);
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, s.sums, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int gn_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
+  Sens& s = *ctx->sens;
+  const int64_t cells = sens_cells(ctx);
+  const int K = 1 + s.P + s.P * (s.P + 1) / 2;
+  const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
+  int rc;
+  if ((rc = ensure_sums(ctx, K, nblk))) return rc;
   const T* v = static_cast<const T*>(s.data) + (int64_t)frame * s.B * cells;
   hipLaunchKernelGGL(sens_gn_partial_kernel<T>, dim3(nblk, s.B, 1 + s.P), dim3(kGnThreads), 0, ctx->stream,
                      static_cast<const T*>(ctx->Y), static_cast<const T*>(ctx->SNAP), v, s.partial, s.B, s.P, cells,
                      (T)theta, interp);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  const int n = s.B * K;
-  hipLaunchKernelGGL(sens_gn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.partial, s.sums, n, nblk);
+  return finish_sums(ctx, K, nblk, host_out);
+}
+
+template <typename T>
+int contract(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
+  Sens& s = *ctx->sens;
+  const int64_t cells = sens_cells(ctx);
+  const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
+  int rc;
+  if ((rc = ensure_sums(ctx, s.P, nblk))) return rc;
+  const T* g = static_cast<const T*>(s.data) + (int64_t)frame * s.B * cells;
+  hipLaunchKernelGGL(sens_contract_partial_kernel<T>, dim3(nblk, s.B), dim3(kGnThreads), 0, ctx->stream,
+                     static_cast<const T*>(ctx->Y), static_cast<const T*>(ctx->SNAP), g, s.partial, s.B, s.P, cells,
+                     (T)theta, interp);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, s.sums, sbytes, hipMemcpyDeviceToHost, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return PDEOPT_OK;
+  return finish_sums(ctx, s.P, nblk, host_out);
 }
 
 }  // namespace
@@ -826,6 +895,19 @@ int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp,
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return ctx->prob.dtype == PDEOPT_F32 ? gn_accumulate<float>(ctx, frame, theta, interp, out)
                                        : gn_accumulate<double>(ctx, frame, theta, interp, out);
+}
+
+int pdeopt_sens_contract(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out) {
+  if (!ctx || !out) return PDEOPT_EINVAL;
+  int rc = check_sens(ctx);
+  if (rc) return rc;
+  Sens& s = *ctx->sens;
+  if (!s.data || frame < 0 || frame >= s.n_frames)
+    return fail(ctx, PDEOPT_EINVAL, "frame %d of %d uploaded (pdeopt_sens_set_data)", frame, s.n_frames);
+  if (interp && !ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return ctx->prob.dtype == PDEOPT_F32 ? contract<float>(ctx, frame, theta, interp, out)
+                                       : contract<double>(ctx, frame, theta, interp, out);
 }
 
 }  // extern "C"

@@ -386,7 +386,7 @@ class HipEngine:
         self._check(self._lib.pdeopt_sens_advance(self._h, int(integrator), float(t0), float(dt), int(n_substeps)))
 
     def sens_set_data(self, frames):
-        """observed frames ``(n_frames, B, *spatial)``, uploaded once per fit"""
+        """observed frames ``(n_frames, B, *spatial)``, uploaded once per fit (or the cotangents ``sens_contract`` reads)"""
         a = np.ascontiguousarray(np.asarray(frames, dtype=self.dtype))
         if a.ndim != 2 + len(self.state_shape) or a.shape[1] != self.sens_shape[0] or a.shape[2:] != self.state_shape:
             raise ValueError(f"frames of shape {a.shape}: expected (n_frames, {self.sens_shape[0]}) + {self.state_shape}")
@@ -398,6 +398,14 @@ class HipEngine:
         out = np.empty((B, 1 + P + P * (P + 1) // 2), dtype=np.float64)
         self._check(self._lib.pdeopt_sens_accumulate(self._h, int(frame), float(theta), int(bool(interp)),
                                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sens_contract(self, frame: int, theta: float = 1.0, interp: bool = False) -> np.ndarray:
+        """``(B, P)`` fp64: ``sum_cells g[frame][b] dpred_j[b]`` at one save point, with the cotangents ``g`` uploaded
+        through ``sens_set_data`` (the gradient of a general objective; ``PDEModel.optimize``)"""
+        out = np.empty(self.sens_shape, dtype=np.float64)
+        self._check(self._lib.pdeopt_sens_contract(self._h, int(frame), float(theta), int(bool(interp)),
+                                                   out.ctypes.data_as(C.c_void_p)))
         return out
 
     def reduce(self, op: int) -> np.ndarray:

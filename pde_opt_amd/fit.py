@@ -6,6 +6,12 @@ optimistix (``LevenbergMarquardt`` / ``BFGS``).  Here the forward-mode tangents 
 trajectories (``pdeopt_sens_advance``) and only the Gauss-Newton sums come back to the host
 (``pdeopt_sens_accumulate``); the optimisers below work on those sums.
 
+``PDEModel.optimize`` (pde_model.py:462-551) minimises a scalar objective ``J(ys)`` of the saved solution instead of a
+residual against frames.  Its gradient ``dJ/dp_j = sum_q <dJ/dys[q], dys[q]/dp_j>`` contracts the cotangent field of
+every save point with the same tangents (``pdeopt_sens_contract``): ``SolutionObjective`` / ``as_objective`` turn the
+user's objective into ``(J, dJ/dys)``, ``objective_gradient`` assembles the gradient, ``minimize_bfgs`` is the BFGS of
+``train(method="mse")`` on plain ``value_and_grad`` / ``value`` callables.
+
 Covered: periodic Cahn-Hilliard in 2-D and 3-D (``mu`` / ``D``; IMEX or Euler) and periodic 2-D Allen-Cahn (``mu`` /
 ``R``; Euler or RK4), all with ``derivs="fd"``.
 """
@@ -199,14 +205,21 @@ def _configure(eng, equation, solver, y0s, pmap_params, t0, t1):
     eng.set_state(state)
 
 
-def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fields=False, frames_key=None, frames=None):
+def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fields=False, frames_key=None, frames=None,
+                      cotangents=None):
     """Solve B trajectories and their P tangents through ``ts``.
 
     ``y0s`` ``(B, *spatial)``, with ``spatial`` ``(nx, ny)`` or ``(nx, ny, nz)``.  ``frames`` ``(T - 1, B, *spatial)``:
     the observed values at ``ts[1:]``; they are uploaded when ``frames_key`` differs from the engine's last upload.
     Returns the Gauss-Newton sums per trajectory summed over the save points, ``(B, 1 + P + P (P + 1) / 2)`` fp64
     (None without frames), and with ``fields=True`` the states of all ``(1 + P) B`` environments at every save point,
-    ``(T, (1 + P) B, *spatial)``."""
+    ``(T, (1 + P) B, *spatial)``.
+
+    ``cotangents`` ``(T - 1, B, *spatial)`` instead of ``frames``: ``dJ/dys`` of an objective at ``ts[1:]`` (``ts[0]``
+    contributes nothing: the initial state is data).  They are uploaded at every call -- they change with every
+    evaluation -- and the first return value is ``sum_q <cotangents[q], dys[q]/dp_j>`` per trajectory, ``(B, P)`` fp64."""
+    if frames is not None and cotangents is not None:
+        raise ValueError("frames and cotangents share one device buffer: pass one of them")
     if _is_allen_cahn(type(equation)):
         if solver.integrator not in (L.INT_EULER, L.INT_RK4):
             raise NotImplementedError("Allen-Cahn sensitivities support Euler and RK4")
@@ -221,14 +234,18 @@ def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fie
     if frames is not None and (frames_key is None or getattr(eng, "_sens_frames_key", None) != frames_key):
         eng.sens_set_data(frames)
         eng._sens_frames_key = frames_key
+    if cotangents is not None:
+        eng.sens_set_data(cotangents)
+        eng._sens_frames_key = None  # the frames of a fit are gone from the device
+    reduce_at = eng.sens_accumulate if frames is not None else (eng.sens_contract if cotangents is not None else None)
     sums = [None]
     out = []
 
     def visit(q, theta):
         if fields:
             out.append(eng.get_state() if theta is None else eng.get_interpolated(theta))
-        if frames is not None and q >= 1:
-            s = eng.sens_accumulate(q - 1, 1.0 if theta is None else theta, theta is not None)
+        if reduce_at is not None and q >= 1:
+            s = reduce_at(q - 1, 1.0 if theta is None else theta, theta is not None)
             sums[0] = s if sums[0] is None else sums[0] + s
 
     walk_save_points(t0, t1, float(dt0), ts,
@@ -321,6 +338,43 @@ def levenberg_marquardt(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL)
     return p, hist
 
 
+def _bfgs_loop(value_and_grad, value, p, f, g, H, max_steps, rtol, atol):
+    """BFGS from the point ``p`` with objective ``f``, gradient ``g`` and inverse-Hessian estimate ``H``:
+    ``value_and_grad(p) -> (f, g)`` at accepted points, ``value(p) -> f`` at the trial points of the backtracking
+    (Armijo) line search.  Returns ``(p, history of objectives)``."""
+    hist = [f]
+    for _ in range(max_steps):
+        if not np.all(np.isfinite(g)) or not math.isfinite(f):
+            break
+        d = -(H @ g)
+        slope = float(g @ d)
+        if slope >= 0:  # not a descent direction: restart from the gradient
+            d, slope = -g, -float(g @ g)
+        if slope == 0.0:
+            break
+        a = 1.0
+        f_new = value(p + a * d)
+        while not (math.isfinite(f_new) and f_new <= f + 1e-4 * a * slope) and a > 1e-9:
+            a *= 0.5
+            f_new = value(p + a * d)
+        if a <= 1e-9:  # no decrease along d: the objective is at its floating-point floor
+            break
+        p_new = p + a * d
+        f_new, g_new = value_and_grad(p_new)
+        s, y = p_new - p, g_new - g
+        sy = float(s @ y)
+        if sy > 0:
+            rho = 1.0 / sy
+            V = np.eye(len(p)) - rho * np.outer(s, y)
+            H = V @ H @ V.T + rho * np.outer(s, s)
+        done = _converged(p, p_new, f, f_new, rtol, atol)
+        p, f, g = p_new, f_new, g_new
+        hist.append(f)
+        if done:
+            break
+    return p, hist
+
+
 def bfgs(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL):
     """Minimise ``mean(r^2) + reg`` (the reference's ``mse`` under optimistix.BFGS).  Gradient
     ``-(2 / M) sum r dpred + 2 lambda w p`` from the tangents; trial points of the backtracking (Armijo) line search
@@ -339,37 +393,103 @@ def bfgs(obj: Objective, p0, max_steps=100, rtol=RTOL, atol=ATOL):
     f, g, G = fg(p)
     w = obj.w if obj.w is not None else np.zeros_like(p)
     H = np.linalg.pinv((2.0 / obj.M) * G + np.diag(2.0 * obj.lambda_reg * w), rcond=1e-12, hermitian=True)
-    hist = [f]
-    for _ in range(max_steps):
-        if not np.all(np.isfinite(g)) or not math.isfinite(f):
-            break
-        d = -(H @ g)
-        slope = float(g @ d)
-        if slope >= 0:  # not a descent direction: restart from the gradient
-            d, slope = -g, -float(g @ g)
-        if slope == 0.0:
-            break
-        a = 1.0
-        f_new = f_only(p + a * d)
-        while not (math.isfinite(f_new) and f_new <= f + 1e-4 * a * slope) and a > 1e-9:
-            a *= 0.5
-            f_new = f_only(p + a * d)
-        if a <= 1e-9:  # no decrease along d: the objective is at its floating-point floor
-            break
-        p_new = p + a * d
-        f_new, g_new, _ = fg(p_new)
-        s, y = p_new - p, g_new - g
-        sy = float(s @ y)
-        if sy > 0:
-            rho = 1.0 / sy
-            V = np.eye(len(p)) - rho * np.outer(s, y)
-            H = V @ H @ V.T + rho * np.outer(s, s)
-        done = _converged(p, p_new, f, f_new, rtol, atol)
-        p, f, g = p_new, f_new, g_new
-        hist.append(f)
-        if done:
-            break
-    return p, hist
+    return _bfgs_loop(lambda q: fg(q)[:2], f_only, p, f, g, H, max_steps, rtol, atol)
+
+
+def minimize_bfgs(value_and_grad: Callable, value: Callable, p0, max_steps=100, rtol=RTOL, atol=ATOL):
+    """The BFGS of ``bfgs`` for a general objective: ``value_and_grad(p) -> (f, g)``, ``value(p) -> f``.  There is no
+    Gauss-Newton Hessian to start from: the inverse-Hessian estimate starts at the identity, as optimistix.BFGS does
+    (the reference's ``optimize``, pde_model.py:531-546).  A direction with no gradient is still never moved: the
+    update leaves its row and column of the identity alone."""
+    p = np.array(p0, dtype=np.float64)
+    f, g = value_and_grad(p)
+    return _bfgs_loop(value_and_grad, value, p, f, np.asarray(g, dtype=np.float64), np.eye(len(p)), max_steps, rtol, atol)
+
+
+# ---- a general objective of the solution (PDEModel.optimize) -------------------------------------------------------------
+
+OBJECTIVE_FORMS = ("objective_function must be a torch-differentiable callable (it receives the solution as a float64 "
+                   "torch.Tensor of shape (len(ts), *y0.shape) and returns a 0-d tensor that depends on it) or an object "
+                   "with value_and_grad(ys) -> (float, ndarray of ys.shape) and optionally value(ys) -> float")
+
+
+class SolutionObjective:
+    """``J(ys)`` of the saved solution ``ys`` ``(T, *y0.shape)`` with its cotangent: ``value_and_grad(ys) ->
+    (J, dJ/dys)`` as ``(float, float64 array of ys.shape)``, ``value(ys) -> J``."""
+
+    def __init__(self, value_and_grad: Callable, value: Callable = None):
+        self._vg, self._v = value_and_grad, value
+
+    def value_and_grad(self, ys):
+        ys = np.asarray(ys)
+        J, g = self._vg(ys)
+        g = np.asarray(g, dtype=np.float64)
+        if g.shape != ys.shape:
+            raise ValueError(f"the objective's gradient has shape {g.shape}, the solution {ys.shape}")
+        return float(J), g
+
+    def value(self, ys):
+        return float(self._v(np.asarray(ys))) if self._v is not None else self.value_and_grad(ys)[0]
+
+
+def torch_objective(fn: Callable) -> SolutionObjective:
+    """``fn(torch.Tensor) -> 0-d torch.Tensor`` as a SolutionObjective: the cotangent comes from torch.autograd.  The
+    solution is handed over in float64 whatever the solve's dtype (the values are the solve's own)."""
+    import torch
+
+    def value_and_grad(ys):
+        y = torch.tensor(np.asarray(ys, dtype=np.float64), requires_grad=True)
+        J = fn(y)
+        if not isinstance(J, torch.Tensor) or J.numel() != 1 or not J.requires_grad:
+            raise NotImplementedError(OBJECTIVE_FORMS + f" (the callable returned {type(J).__name__})")
+        (g,) = torch.autograd.grad(J.reshape(()), y)
+        return float(J.detach()), g.numpy()
+
+    def value(ys):
+        with torch.no_grad():
+            return float(fn(torch.tensor(np.asarray(ys, dtype=np.float64))))
+
+    return SolutionObjective(value_and_grad, value)
+
+
+def as_objective(objective_function, probe=None) -> SolutionObjective:
+    """The two accepted forms of ``PDEModel.optimize``'s objective as a SolutionObjective; anything else raises
+    ``NotImplementedError``.  A plain callable is tried once on ``probe`` (an array of the solution's shape) to see
+    that torch can differentiate it."""
+    if objective_function is None:
+        raise NotImplementedError("PDEModel.optimize needs an objective: " + OBJECTIVE_FORMS)
+    if callable(getattr(objective_function, "value_and_grad", None)):
+        value = getattr(objective_function, "value", None)
+        return SolutionObjective(objective_function.value_and_grad, value if callable(value) else None)
+    if not callable(objective_function):
+        raise NotImplementedError(OBJECTIVE_FORMS)
+    obj = torch_objective(objective_function)
+    if probe is not None:
+        try:
+            obj.value_and_grad(probe)
+        except NotImplementedError:
+            raise
+        except Exception as e:  # numpy-only callables fail on a tensor that requires grad
+            raise NotImplementedError(OBJECTIVE_FORMS + f" (torch could not differentiate it: {type(e).__name__}: {e})") from e
+    return obj
+
+
+def objective_gradient(objective: SolutionObjective, ys, spatial_ndim: int, contract: Callable, pmap: ParamMap):
+    """``(J, dJ/dp)`` of ``J(ys)`` over all entries of ``p``, for ``ys`` ``(T, *spatial)`` or ``(T, B, *spatial)``.  The
+    objective gives ``g = dJ/dys``; ``contract(g[1:] as (T - 1, B, *spatial)) -> (B, n active)``, the sums
+    ``sum_q <g_q, dys_q/dp_j>``, is a sensitivity solve (frame 0's cotangent is dropped: the initial state is data); the
+    trajectories are summed in order and the inert entries get 0."""
+    ys = np.asarray(ys)
+    J, g = objective.value_and_grad(ys)
+    n_active = int(np.count_nonzero(pmap.active()))
+    cot = g[1:].reshape((g.shape[0] - 1, -1) + g.shape[g.ndim - spatial_ndim:])
+    per_traj = np.asarray(contract(np.ascontiguousarray(cot)), dtype=np.float64).reshape(-1, n_active)
+    tot = np.zeros(n_active)
+    for row in per_traj:
+        tot = tot + row
+    grad = np.zeros(pmap.size)
+    grad[np.nonzero(pmap.active())[0]] = tot
+    return J, grad
 
 
 _SUPPORTED = ("CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain, or AllenCahn2DPeriodic on a "

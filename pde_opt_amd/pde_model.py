@@ -9,7 +9,10 @@ ignored: forward solves need no adjoint.
 trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
 trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D (``mu`` / ``D``; IMEX or
 Euler) and periodic 2-D Allen-Cahn (``mu`` / ``R``; Euler or RK4), with FD derivatives.
-``optimize`` (pde_model.py:462-551) keeps raising: its objective is an arbitrary function of the solution.
+``optimize`` (pde_model.py:462-551) minimises a scalar objective of the saved solution over the same coefficients with
+BFGS: the objective is a torch-differentiable callable or an object with ``value_and_grad(ys)``; its cotangent
+``dJ/dys`` is contracted with the same tangents on the GPU (``pdeopt_sens_contract``).  Objectives in neither form, and
+the equations / solvers / closures ``train`` refuses, raise ``NotImplementedError``.
 """
 
 from __future__ import annotations
@@ -134,11 +137,70 @@ class PDEModel:
         self.last_train_history = hist
         return {**pmap.build(p), **other_parameters}
 
-    def optimize(self, *a, **k):
-        raise NotImplementedError(
-            "PDEModel.optimize minimises an arbitrary function of the solution and needs its gradient; only "
-            "train / residuals / mse (closure coefficients fitted to trajectories) are provided"
-        )
+    def optimize(self, objective_function=None, y0=None, ts=None, opt_parameters=None, other_parameters=None,
+                 solver_parameters=None, weights=None, lambda_reg=0.0, max_steps=100):
+        """Minimise ``objective_function(solve(...)) + regularization(...)`` over the closure coefficients in
+        ``opt_parameters`` with BFGS (pde_model.py:462-551).
+
+        ``objective_function`` is a scalar function of the saved solution ``ys`` of shape ``(len(ts), *y0.shape)``:
+        either a torch-differentiable callable (it receives ``ys`` as a float64 ``torch.Tensor`` and returns a 0-d
+        tensor; the counterpart of the reference's JAX-compatible objective), or an object with
+        ``value_and_grad(ys) -> (float, ndarray of ys.shape)`` and optionally ``value(ys) -> float`` for numpy users.
+        Anything else raises ``NotImplementedError``.  ``y0`` is one state ``spatial`` or a batch ``(B, *spatial)``.
+
+        One gradient is two passes: ``solve`` gives ``ys``, the objective ``J`` and ``g = dJ/dys``; a sensitivity solve
+        (its base block is bitwise ``solve``) with ``g[1:]`` on the device gives ``dJ/dp_j = sum_q <g_q, dys_q/dp_j>``
+        (``pdeopt_sens_contract``).  Trial points of the line search are forward solves.  The equations, solvers and
+        closures are those of ``train``.  Returns ``{**fitted, **other_parameters}``; the objective after every
+        accepted step is in ``last_optimize_history``."""
+        value_and_grad, value, pmap = self._objective_functions(objective_function, y0, ts, opt_parameters, other_parameters,
+                                                                solver_parameters, weights, lambda_reg)
+        p, hist = fit.minimize_bfgs(value_and_grad, value, pmap.flatten(opt_parameters), max_steps=max_steps)
+        self.last_optimize_history = hist
+        return {**pmap.build(p), **(other_parameters or {})}
+
+    def _objective_functions(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters, weights,
+                             lambda_reg):
+        """``(value_and_grad(p), value(p), ParamMap)`` of ``optimize``'s objective over the flat coefficient vector"""
+        other_parameters, weights = other_parameters or {}, weights or {}
+        probe = None
+        if y0 is not None and ts is not None:
+            y0 = np.asarray(y0)
+            probe = np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape)
+        objective = fit.as_objective(objective_function, probe)  # checked first: optimize() with nothing keeps raising
+        if y0 is None or ts is None or not opt_parameters:
+            raise ValueError("optimize needs y0, ts and opt_parameters")
+        fit.reject_unsupported(self)
+        pmap = fit.ParamMap.of(opt_parameters, self.equation_type)
+        fit.check_equation(self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters}))
+        spatial_ndim = len(self.domain.points)
+        if y0.ndim not in (spatial_ndim, spatial_ndim + 1):
+            raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points)} or (B,) + that")
+        y0s = y0 if y0.ndim == spatial_ndim + 1 else y0[None]
+        ts = np.asarray(ts, dtype=np.float64)
+        sens_params = pmap.sens_params()
+        reg = fit.Objective(sums=None, ssr=None, M=0, lambda_reg=float(lambda_reg), w=fit.weight_vector(pmap, weights))
+
+        def params_of(p):
+            return {**pmap.build(p), **other_parameters}
+
+        def value(p):
+            return objective.value(self.solve(params_of(p), y0, ts, solver_parameters)) + reg.reg(p)
+
+        def value_and_grad(p):
+            params = params_of(p)
+            equation = self.equation_type(domain=self.domain, **params)
+            solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+
+            def contract(cotangents):
+                return fit.sensitivity_solve(self._sens_engine(), equation, solver, y0s, ts, sens_params,
+                                             cotangents=cotangents)[0]
+
+            ys = self.solve(params, y0, ts, solver_parameters)
+            J, grad = fit.objective_gradient(objective, ys, spatial_ndim, contract, pmap)
+            return J + reg.reg(p), grad + reg.reg_grad(p)
+
+        return value_and_grad, value, pmap
 
 
 def stack_training_data(data, inds):

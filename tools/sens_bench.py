@@ -10,7 +10,12 @@ and, on the host clock around calls that end in a device synchronise,
 docs/notebooks/optimization_3D.ipynb (edge 0.01 n), whose fit spans 40400 substeps per sensitivity solve at 32^3.
 Allen-Cahn rows (AllenCahn2DPeriodic on [0, 1]^2, Euler and RK4) time the same two substeps; their forward substep
 is whatever pdeopt_advance picks for the B trajectories.
-Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only]
+``--optimize`` times PDEModel.optimize's inner loop instead, on the host clock around calls that end in a device
+synchronise (CahnHilliard2DPeriodic 128^2 x 1, IMEX, P = 3 / 7, `substeps` substeps to one save point):
+  forward_ms   one forward solve (PDEModel.solve): what a line-search trial point costs
+  gradient_ms  one gradient evaluation: a forward solve, the objective's cotangent, its upload and a sensitivity solve
+               with the contraction (pdeopt_sens_contract)
+Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only | --optimize]
 """
 import json
 import sys
@@ -137,8 +142,43 @@ def ac_rows(quick):
     return rows
 
 
+class _SecondMoment:
+    """J = mean(ys[-1]^2) with its cotangent, in numpy (the objective's own cost stays out of the comparison)"""
+
+    def value_and_grad(self, ys):
+        g = np.zeros(ys.shape)
+        g[-1] = 2.0 * ys[-1] / ys[-1].size
+        return float(np.mean(np.asarray(ys[-1], dtype=np.float64) ** 2)), g
+
+
+def optimize_case(n, dtype, P_, substeps, reps=5):
+    dom = P.Domain((n, n), ((0.0, 1.0), (0.0, 1.0)), "dimensionless")
+    opt = closures(P_)
+    model = P.PDEModel(P.CahnHilliard2DPeriodic, dom, P.SemiImplicitFourierSpectral)
+    y0 = np.clip(0.5 + 0.05 * np.random.default_rng(0).standard_normal(dom.points), 0.05, 0.95).astype(dtype)
+    ts = np.array([0.0, substeps * DT])
+    vg, v, pmap = model._objective_functions(_SecondMoment(), y0, ts, opt, {"kappa": KAPPA}, {"A": 0.5}, {}, 0.0)
+    p = pmap.flatten(opt)
+
+    def clock(fn):
+        fn()  # warm-up: code objects, multipliers, buffers
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        return (time.perf_counter() - t0) / reps * 1e3
+
+    t_fwd, t_grad = clock(lambda: v(p)), clock(lambda: vg(p))
+    return {"n": n, "B": 1, "dtype": np.dtype(dtype).name, "P": P_, "substeps": substeps, "forward_ms": t_fwd,
+            "gradient_ms": t_grad, "gradient_over_forward": t_grad / t_fwd}
+
+
 def main():
     quick = "--quick" in sys.argv
+    if "--optimize" in sys.argv:
+        rows = [optimize_case(128, dtype, P_, 200 if quick else 4040) for dtype in (np.float32, np.float64)
+                for P_ in ((3,) if quick else (3, 7))]
+        print(json.dumps({"tool": "sens_bench", "mode": "optimize", "dt": DT, "cases": rows}))
+        return
     if "--ac-only" in sys.argv:
         print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": ac_rows(quick)}))
         return
