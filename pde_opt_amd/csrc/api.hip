@@ -397,10 +397,7 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   }
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-  if (pr->dtype == PDEOPT_F32)
-    fill_env_params<float>(ctx);
-  else
-    fill_env_params<double>(ctx);
+  with_dtype(ctx, [&](auto t) { fill_env_params<decltype(t)>(ctx); });
   if ((rc = ensure_buffer(ctx, &ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
   ctx->imex_per_env = false;
   ctx->configured = true;
@@ -413,10 +410,7 @@ int pdeopt_set_env_params(pdeopt_ctx* ctx, int env_first, int env_count, const d
   int rc = check_envs(ctx, env_first, env_count);
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->prob.dtype == PDEOPT_F32)
-    patch_env_params<float>(ctx, env_first, env_count, kappa, mu_coef, mob_coef);
-  else
-    patch_env_params<double>(ctx, env_first, env_count, kappa, mu_coef, mob_coef);
+  with_dtype(ctx, [&](auto t) { patch_env_params<decltype(t)>(ctx, env_first, env_count, kappa, mu_coef, mob_coef); });
   return upload_env_params(ctx);
 }
 
@@ -516,8 +510,7 @@ int pdeopt_set_env_imex_scale(pdeopt_ctx* ctx, int env_first, int env_count, con
   for (int i = 0; i < env_count; ++i)
     if (!(sigma[i] > 0.0)) return fail(ctx, PDEOPT_EINVAL, "imex scale %g of environment %d must be positive", sigma[i], env_first + i);
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  ctx->imex_per_env = ctx->prob.dtype == PDEOPT_F32 ? patch_imex_scale<float>(ctx, env_first, env_count, sigma)
-                                                    : patch_imex_scale<double>(ctx, env_first, env_count, sigma);
+  ctx->imex_per_env = with_dtype(ctx, [&](auto t) { return patch_imex_scale<decltype(t)>(ctx, env_first, env_count, sigma); });
   return upload_env_params(ctx);
 }
 
@@ -526,10 +519,7 @@ int pdeopt_set_env_gpe_k(pdeopt_ctx* ctx, int env_first, int env_count, const do
   int rc = check_envs(ctx, env_first, env_count);
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->prob.dtype == PDEOPT_F32)
-    patch_env_gpe_k<float>(ctx, env_first, env_count, k);
-  else
-    patch_env_gpe_k<double>(ctx, env_first, env_count, k);
+  with_dtype(ctx, [&](auto t) { patch_env_gpe_k<decltype(t)>(ctx, env_first, env_count, k); });
   return upload_env_params(ctx);
 }
 
@@ -868,10 +858,7 @@ int pdeopt_tsit5_trial_env(pdeopt_ctx* ctx, double t, const double* dt, double r
   int rc;
   // the FSAL slope K[0] of environment b carries the scale of its previous trial
   if (ctx->tsit5_fsal_valid && rescale && (rc = tsit5_rescale_fsal(ctx, ratio.data()))) return rc;
-  if (ctx->prob.dtype == PDEOPT_F32)
-    patch_kscale<float>(ctx, sc);
-  else
-    patch_kscale<double>(ctx, sc);
+  with_dtype(ctx, [&](auto t) { patch_kscale<decltype(t)>(ctx, sc); });
   if ((rc = upload_env_params(ctx))) return rc;
   ctx->slope_scaled = true;
   rc = tsit5_trial(ctx, t, ref, rtol, atol, err_norm);

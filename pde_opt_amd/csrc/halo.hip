@@ -157,10 +157,10 @@ int halo_pack(pdeopt_ctx* ctx, int field, void* dev_send) {
   }
   const int blocks = (int)std::min<int64_t>((g.per_env + 255) / 256, 1024);
   dim3 grid(blocks, ctx->prob.batch);
-  if (ctx->prob.dtype == PDEOPT_F32)
-    hipLaunchKernelGGL(pack_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)f, (float*)dev_send, g);
-  else
-    hipLaunchKernelGGL(pack_kernel<double>, grid, dim3(256), 0, ctx->stream, (const double*)f, (double*)dev_send, g);
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(256), 0, ctx->stream, (const T*)f, (T*)dev_send, g);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }
@@ -183,10 +183,10 @@ int halo_unpack(pdeopt_ctx* ctx, int field, const void* dev_recv, const int* nbr
   const int64_t strip = (int64_t)halo_strip_elems(ctx);
   const int blocks = (int)std::min<int64_t>((g.per_env + 255) / 256, 1024);
   dim3 grid(blocks, ctx->prob.batch);
-  if (ctx->prob.dtype == PDEOPT_F32)
-    hipLaunchKernelGGL(unpack_kernel<float>, grid, dim3(256), 0, ctx->stream, (float*)f, (const float*)dev_recv, g, nb, strip);
-  else
-    hipLaunchKernelGGL(unpack_kernel<double>, grid, dim3(256), 0, ctx->stream, (double*)f, (const double*)dev_recv, g, nb, strip);
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(unpack_kernel<T>, grid, dim3(256), 0, ctx->stream, (T*)f, (const T*)dev_recv, g, nb, strip);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }

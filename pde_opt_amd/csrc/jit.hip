@@ -171,8 +171,7 @@ int jit_check(int dtype, const char* mu_body, const char* mob_body, char* log_ou
   }
   if (!rc) {
     std::vector<char> code;
-    rc = dtype == PDEOPT_F32 ? compile_bodies<float>(mu_body, mob_body, "gfx950", &code, &log)
-                             : compile_bodies<double>(mu_body, mob_body, "gfx950", &code, &log);
+    rc = with_dtype(dtype, [&](auto t) { return compile_bodies<decltype(t)>(mu_body, mob_body, "gfx950", &code, &log); });
   }
   if (log_out && log_cap > 0) {
     strncpy(log_out, log.c_str(), (size_t)log_cap - 1);

@@ -86,13 +86,11 @@ int run_pass(pdeopt_ctx* ctx, const double* shift_dev, std::vector<Partial>& hos
     ctx->red_cap = need;
   }
   dim3 grid(kChunks, batch), block(256);
-  if (ctx->prob.dtype == PDEOPT_F32) {
-    hipLaunchKernelGGL(reduce_kernel<float>, grid, block, 0, ctx->stream, (const float*)ctx->Y,
-                       (int64_t)ctx->env_elems, shift_dev, (Partial*)ctx->red_dev);
-  } else {
-    hipLaunchKernelGGL(reduce_kernel<double>, grid, block, 0, ctx->stream, (const double*)ctx->Y,
-                       (int64_t)ctx->env_elems, shift_dev, (Partial*)ctx->red_dev);
-  }
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(reduce_kernel<T>, grid, block, 0, ctx->stream, (const T*)ctx->Y, (int64_t)ctx->env_elems, shift_dev,
+                       (Partial*)ctx->red_dev);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   host.resize((size_t)batch * kChunks);
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), ctx->red_dev, need, hipMemcpyDeviceToHost,
@@ -131,12 +129,11 @@ int observe_u8(pdeopt_ctx* ctx, double lo, double hi, int env_first, int env_cou
   const int64_t n4 = n / 4;
   const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 4096);
   const size_t off = (size_t)env_first * ctx->env_elems;
-  if (ctx->prob.dtype == PDEOPT_F32)
-    hipLaunchKernelGGL(observe_u8_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream,
-                       (const float*)ctx->Y + off, (uint32_t*)ctx->obs_dev, n4, (float)lo, (float)(255.0 / (hi - lo)));
-  else
-    hipLaunchKernelGGL(observe_u8_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream,
-                       (const double*)ctx->Y + off, (uint32_t*)ctx->obs_dev, n4, lo, 255.0 / (hi - lo));
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(observe_u8_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, (const T*)ctx->Y + off,
+                       (uint32_t*)ctx->obs_dev, n4, (T)lo, (T)(255.0 / (hi - lo)));
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   if (host_out)  // nullptr: the frames stay in ctx->obs_dev (pdeopt_observe_u8_device)
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->obs_dev, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -234,12 +231,11 @@ int detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int env_firs
   dim3 grid((p.ny + 63) / 64, (p.nx + 3) / 4, env_count), block(256);
   if (grid.y > 65535u || grid.z > 65535u) return fail(ctx, PDEOPT_EINVAL, "grid too large for the vortex kernel");
   const size_t off = (size_t)env_first * ctx->env_elems;
-  if (p.dtype == PDEOPT_F32)
-    hipLaunchKernelGGL(vortex_kernel<float>, grid, block, 0, ctx->stream, (const float*)ctx->Y + off, wdev, counts,
-                       p.nx, p.ny, (float)amp_thresh, (float)tol);
-  else
-    hipLaunchKernelGGL(vortex_kernel<double>, grid, block, 0, ctx->stream, (const double*)ctx->Y + off, wdev, counts,
-                       p.nx, p.ny, amp_thresh, tol);
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(vortex_kernel<T>, grid, block, 0, ctx->stream, (const T*)ctx->Y + off, wdev, counts, p.nx, p.ny,
+                       (T)amp_thresh, (T)tol);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   static_assert(sizeof(long long) == sizeof(int64_t), "counter width");
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_counts, counts, (size_t)env_count * 3 * sizeof(int64_t),
@@ -287,12 +283,10 @@ int probe_state(pdeopt_ctx* ctx, const int32_t* cells, int n_probes, int env_fir
   int64_t* cell_dev = reinterpret_cast<int64_t*>(ctx->red_dev + total);
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(cell_dev, flat.data(), (size_t)n_probes * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   const int blocks = (int)((total + 255) / 256);
-  if (p.dtype == PDEOPT_F32)
-    hipLaunchKernelGGL(probe_kernel<float>, dim3(blocks), dim3(256), 0, ctx->stream, (const float*)ctx->Y, cell_dev, n_probes,
-                       ctx->comps, (int64_t)ctx->env_elems, env_first, out_dev, total);
-  else
-    hipLaunchKernelGGL(probe_kernel<double>, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)ctx->Y, cell_dev, n_probes,
-                       ctx->comps, (int64_t)ctx->env_elems, env_first, out_dev, total);
+  with_dtype(ctx, [&](auto t) {
+    hipLaunchKernelGGL(probe_kernel<decltype(t)>, dim3(blocks), dim3(256), 0, ctx->stream, (const decltype(t)*)ctx->Y, cell_dev,
+                       n_probes, ctx->comps, (int64_t)ctx->env_elems, env_first, out_dev, total);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, out_dev, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // flat[] and host_out are the caller's from here on

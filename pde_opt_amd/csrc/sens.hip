@@ -573,29 +573,31 @@ int check_sens(pdeopt_ctx* ctx) {
   return PDEOPT_OK;
 }
 
-template <typename T>
-int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
+// the members SensArgs and Sens3Args share
+template <typename T, typename Args>
+void fill_tangent_args(Args& a, const pdeopt_ctx* ctx, const void* in, void* out) {
   const pdeopt_problem& p = ctx->prob;
   const Sens& s = *ctx->sens;
-  SensArgs<T> a{};
   a.y = static_cast<const T*>(in);
   a.k = static_cast<T*>(out);
-  a.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
-  a.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  a.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  set_closures<T>(a, ctx, 0);
   a.nx = p.nx;
   a.ny = p.ny;
   a.B = s.B;
   a.P = s.P;
-  a.rhx = T(1.0 / p.hx);
-  a.rhy = T(1.0 / p.hy);
-  a.rhx2 = T(1.0 / (p.hx * p.hx));
-  a.rhy2 = T(1.0 / (p.hy * p.hy));
+  set_recip_plain(a, grid_recip(p));
   for (int j = 0; j < s.P; ++j) {
     a.role[j] = s.role[j];
     a.index[j] = s.index[j];
   }
-  const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, s.B);
+}
+
+template <typename T>
+int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
+  const pdeopt_problem& p = ctx->prob;
+  SensArgs<T> a{};
+  fill_tangent_args<T>(a, ctx, in, out);
+  const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, a.B);
   if (p.equation == PDEOPT_EQ_ALLEN_CAHN) hipLaunchKernelGGL(sens_ac_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   else hipLaunchKernelGGL(sens_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   ctx->n_stage_launches++;
@@ -606,33 +608,16 @@ int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
 // the two 3-D passes over the tangent block; the base slope launch has left the base mu in KS[0, B)
 template <typename T>
 int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
-  const pdeopt_problem& p = ctx->prob;
-  const Sens& s = *ctx->sens;
   int rc;
   if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+  const GridRecip r = grid_recip(ctx->prob);
   Sens3Args<T> a{};
-  a.y = static_cast<const T*>(in);
+  fill_tangent_args<T>(a, ctx, in, out);
   a.w = static_cast<T*>(ctx->KS);
-  a.k = static_cast<T*>(out);
-  a.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
-  a.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  a.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
-  a.nx = p.nx;
-  a.ny = p.ny;
-  a.nz = p.nz;
-  a.B = s.B;
-  a.P = s.P;
-  a.rhx = T(1.0 / p.hx);
-  a.rhy = T(1.0 / p.hy);
-  a.rhz = T(1.0 / p.hz);
-  a.rhx2 = T(1.0 / (p.hx * p.hx));
-  a.rhy2 = T(1.0 / (p.hy * p.hy));
-  a.rhz2 = T(1.0 / (p.hz * p.hz));
-  for (int j = 0; j < s.P; ++j) {
-    a.role[j] = s.role[j];
-    a.index[j] = s.index[j];
-  }
-  const dim3 grid((unsigned)((sens_cells(ctx) + 255) / 256), s.B);
+  a.nz = ctx->prob.nz;
+  a.rhz = T(r.rz);
+  a.rhz2 = T(r.rz2);
+  const dim3 grid((unsigned)((sens_cells(ctx) + 255) / 256), a.B);
   hipLaunchKernelGGL(sens3d_dmu_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   hipLaunchKernelGGL(sens3d_flux_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   ctx->n_stage_launches += 2;
@@ -645,10 +630,10 @@ int sens_slopes(pdeopt_ctx* ctx, const void* in, void* out) {
   int rc;
   // the base block's slope; the tangent blocks' slopes come from the kernels below
   if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, in, out, 0.0))) return rc;
-  const bool f32 = ctx->prob.dtype == PDEOPT_F32;
-  if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D)
-    return f32 ? launch_tangent_rhs3d<float>(ctx, in, out) : launch_tangent_rhs3d<double>(ctx, in, out);
-  return f32 ? launch_tangent_rhs<float>(ctx, in, out) : launch_tangent_rhs<double>(ctx, in, out);
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    return ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? launch_tangent_rhs3d<T>(ctx, in, out) : launch_tangent_rhs<T>(ctx, in, out);
+  });
 }
 
 template <typename T>
@@ -683,26 +668,25 @@ int rk4_substep(pdeopt_ctx* ctx, double dt) {
   return PDEOPT_OK;
 }
 
+// *p holds at least need_bytes afterwards; a block that is too small is freed first (sync_first: after the stream's
+// work, which may still use it) and *have_bytes keeps the largest size asked for
+int grow_device_buffer(pdeopt_ctx* ctx, void** p, size_t* have_bytes, size_t need_bytes, bool sync_first) {
+  if (*p && *have_bytes < need_bytes) {
+    if (sync_first) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(*p);
+    *p = nullptr;
+  }
+  const int rc = ensure_buffer(ctx, p, need_bytes);
+  if (!rc) *have_bytes = std::max(*have_bytes, need_bytes);
+  return rc;
+}
+
 // the buffers of the two-stage reductions below: partial[B][K][nblk] and sums[B][K]
 int ensure_sums(pdeopt_ctx* ctx, int K, int nblk) {
   Sens& s = *ctx->sens;
   const size_t pbytes = (size_t)s.B * K * nblk * sizeof(double), sbytes = (size_t)s.B * K * sizeof(double);
-  int rc;
-  if (s.partial && s.partial_bytes < pbytes) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(s.partial);
-    s.partial = nullptr;
-  }
-  if ((rc = ensure_buffer(ctx, (void**)&s.partial, pbytes))) return rc;
-  s.partial_bytes = std::max(s.partial_bytes, pbytes);
-  if (s.sums && s.sums_bytes < sbytes) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(s.sums);
-    s.sums = nullptr;
-  }
-  if ((rc = ensure_buffer(ctx, (void**)&s.sums, sbytes))) return rc;
-  s.sums_bytes = std::max(s.sums_bytes, sbytes);
-  return PDEOPT_OK;
+  const int rc = grow_device_buffer(ctx, (void**)&s.partial, &s.partial_bytes, pbytes, /*sync_first=*/true);
+  return rc ? rc : grow_device_buffer(ctx, (void**)&s.sums, &s.sums_bytes, sbytes, /*sync_first=*/true);
 }
 
 // sums[b][k] = the block totals of partial[b][k][.] in block order, copied to the host
@@ -716,35 +700,32 @@ int finish_sums(pdeopt_ctx* ctx, int K, int nblk, double* host_out) {
   return PDEOPT_OK;
 }
 
-template <typename T>
-int gn_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
+// One two-stage reduction over frame `frame` of the uploaded data at the current save point: `kernel` on a grid
+// (blocks per field, B, grid_z) leaves K block totals per trajectory, finish_sums adds them up for the host
+template <typename T, typename Kernel>
+int reduce_frame(pdeopt_ctx* ctx, Kernel kernel, int K, int grid_z, int frame, double theta, int interp, double* host_out) {
   Sens& s = *ctx->sens;
   const int64_t cells = sens_cells(ctx);
-  const int K = 1 + s.P + s.P * (s.P + 1) / 2;
   const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
   int rc;
   if ((rc = ensure_sums(ctx, K, nblk))) return rc;
   const T* v = static_cast<const T*>(s.data) + (int64_t)frame * s.B * cells;
-  hipLaunchKernelGGL(sens_gn_partial_kernel<T>, dim3(nblk, s.B, 1 + s.P), dim3(kGnThreads), 0, ctx->stream,
-                     static_cast<const T*>(ctx->Y), static_cast<const T*>(ctx->SNAP), v, s.partial, s.B, s.P, cells,
-                     (T)theta, interp);
+  hipLaunchKernelGGL(kernel, dim3(nblk, s.B, grid_z), dim3(kGnThreads), 0, ctx->stream, static_cast<const T*>(ctx->Y),
+                     static_cast<const T*>(ctx->SNAP), v, s.partial, s.B, s.P, cells, (T)theta, interp);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return finish_sums(ctx, K, nblk, host_out);
 }
 
-template <typename T>
-int contract(pdeopt_ctx* ctx, int frame, double theta, int interp, double* host_out) {
-  Sens& s = *ctx->sens;
-  const int64_t cells = sens_cells(ctx);
-  const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
-  int rc;
-  if ((rc = ensure_sums(ctx, s.P, nblk))) return rc;
-  const T* g = static_cast<const T*>(s.data) + (int64_t)frame * s.B * cells;
-  hipLaunchKernelGGL(sens_contract_partial_kernel<T>, dim3(nblk, s.B), dim3(kGnThreads), 0, ctx->stream,
-                     static_cast<const T*>(ctx->Y), static_cast<const T*>(ctx->SNAP), g, s.partial, s.B, s.P, cells,
-                     (T)theta, interp);
-  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  return finish_sums(ctx, s.P, nblk, host_out);
+// what pdeopt_sens_accumulate and pdeopt_sens_contract ask of their frame and of the snapshot before they launch
+int check_frame(pdeopt_ctx* ctx, int frame, int interp) {
+  const int rc = check_sens(ctx);
+  if (rc) return rc;
+  const Sens& s = *ctx->sens;
+  if (!s.data || frame < 0 || frame >= s.n_frames)
+    return fail(ctx, PDEOPT_EINVAL, "frame %d of %d uploaded (pdeopt_sens_set_data)", frame, s.n_frames);
+  if (interp && !ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return PDEOPT_OK;
 }
 
 }  // namespace
@@ -821,7 +802,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN, f32 = ctx->prob.dtype == PDEOPT_F32;
+  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN;
   bool fused = false;
   if (integrator == PDEOPT_INT_IMEX) {
     if (ac) return fail(ctx, PDEOPT_EINVAL, "Allen-Cahn sensitivities support the Euler and RK4 integrators (it has no fourier_symbol)");
@@ -843,7 +824,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   for (int64_t s = 0; s < n_substeps; ++s) {
     if (integrator == PDEOPT_INT_RK4) {
-      if ((rc = f32 ? rk4_substep<float>(ctx, dt) : rk4_substep<double>(ctx, dt))) return rc;
+      if ((rc = with_dtype(ctx, [&](auto t) { return rk4_substep<decltype(t)>(ctx, dt); }))) return rc;
       continue;
     }
     if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA))) return rc;
@@ -853,7 +834,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
       rc = imex_rocfft_solve(ctx, dt);
       ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls; rocFFT may run more than one kernel per transform)
     } else {
-      rc = f32 ? euler_update<float>(ctx, dt) : euler_update<double>(ctx, dt);
+      rc = with_dtype(ctx, [&](auto t) { return euler_update<decltype(t)>(ctx, dt); });
     }
     if (rc) return rc;
   }
@@ -872,12 +853,7 @@ int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {
   Sens& s = *ctx->sens;
   const size_t bytes = (size_t)n_frames * s.B * sens_cells(ctx) * ctx->esize;
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (s.data && s.data_bytes < bytes) {
-    (void)hipFree(s.data);
-    s.data = nullptr;
-  }
-  if ((rc = ensure_buffer(ctx, &s.data, bytes))) return rc;
-  s.data_bytes = std::max(s.data_bytes, bytes);
+  if ((rc = grow_device_buffer(ctx, &s.data, &s.data_bytes, bytes, /*sync_first=*/false))) return rc;  // (synchronised above)
   s.n_frames = n_frames;
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.data, host, bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -886,28 +862,23 @@ int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {
 
 int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out) {
   if (!ctx || !out) return PDEOPT_EINVAL;
-  int rc = check_sens(ctx);
+  const int rc = check_frame(ctx, frame, interp);
   if (rc) return rc;
-  Sens& s = *ctx->sens;
-  if (!s.data || frame < 0 || frame >= s.n_frames)
-    return fail(ctx, PDEOPT_EINVAL, "frame %d of %d uploaded (pdeopt_sens_set_data)", frame, s.n_frames);
-  if (interp && !ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
-  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return ctx->prob.dtype == PDEOPT_F32 ? gn_accumulate<float>(ctx, frame, theta, interp, out)
-                                       : gn_accumulate<double>(ctx, frame, theta, interp, out);
+  const int P = ctx->sens->P;
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    return reduce_frame<T>(ctx, sens_gn_partial_kernel<T>, 1 + P + P * (P + 1) / 2, 1 + P, frame, theta, interp, out);
+  });
 }
 
 int pdeopt_sens_contract(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out) {
   if (!ctx || !out) return PDEOPT_EINVAL;
-  int rc = check_sens(ctx);
+  const int rc = check_frame(ctx, frame, interp);
   if (rc) return rc;
-  Sens& s = *ctx->sens;
-  if (!s.data || frame < 0 || frame >= s.n_frames)
-    return fail(ctx, PDEOPT_EINVAL, "frame %d of %d uploaded (pdeopt_sens_set_data)", frame, s.n_frames);
-  if (interp && !ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
-  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return ctx->prob.dtype == PDEOPT_F32 ? contract<float>(ctx, frame, theta, interp, out)
-                                       : contract<double>(ctx, frame, theta, interp, out);
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    return reduce_frame<T>(ctx, sens_contract_partial_kernel<T>, ctx->sens->P, 1, frame, theta, interp, out);
+  });
 }
 
 }  // extern "C"

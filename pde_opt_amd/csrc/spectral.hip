@@ -694,9 +694,10 @@ int rhs_fourier(pdeopt_ctx* ctx, const void* in, void* out) {
   if (ctx->halo) return fail(ctx, PDEOPT_EINVAL, "the pseudo-spectral RHS needs the periodic layout");
   int rc = ensure_plans(ctx);
   if (rc) return rc;
-  if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D)
-    return ctx->prob.dtype == PDEOPT_F32 ? rhs_fourier3_t<float>(ctx, in, out) : rhs_fourier3_t<double>(ctx, in, out);
-  return ctx->prob.dtype == PDEOPT_F32 ? rhs_fourier_t<float>(ctx, in, out) : rhs_fourier_t<double>(ctx, in, out);
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    return ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? rhs_fourier3_t<T>(ctx, in, out) : rhs_fourier_t<T>(ctx, in, out);
+  });
 }
 
 int advance_imex(pdeopt_ctx* ctx, double, double dt, int64_t n) {
@@ -707,15 +708,15 @@ int advance_imex(pdeopt_ctx* ctx, double, double dt, int64_t n) {
     return fail(ctx, PDEOPT_EINVAL, "per-environment IMEX scales need the hand-written FFT passes (power-of-two grids 64..1024)");
   int rc = ensure_plans(ctx);
   if (rc) return rc;
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_t<float>(ctx, dt, n) : imex_t<double>(ctx, dt, n);
+  return with_dtype(ctx, [&](auto t) { return imex_t<decltype(t)>(ctx, dt, n); });
 }
 
 int imex_rocfft_prepare(pdeopt_ctx* ctx, double dt) {
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_rocfft_prepare_t<float>(ctx, dt) : imex_rocfft_prepare_t<double>(ctx, dt);
+  return with_dtype(ctx, [&](auto t) { return imex_rocfft_prepare_t<decltype(t)>(ctx, dt); });
 }
 
 int imex_rocfft_solve(pdeopt_ctx* ctx, double dt) {
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_rocfft_solve_t<float>(ctx, dt) : imex_rocfft_solve_t<double>(ctx, dt);
+  return with_dtype(ctx, [&](auto t) { return imex_rocfft_solve_t<decltype(t)>(ctx, dt); });
 }
 
 int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
@@ -724,7 +725,7 @@ int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   if (strang_fused_supported(ctx)) return advance_strang_fused(ctx, t0, dt, n);  // LDS FFTs, fused passes
   int rc = ensure_plans(ctx);
   if (rc) return rc;
-  return ctx->prob.dtype == PDEOPT_F32 ? strang_t<float>(ctx, t0, dt, n) : strang_t<double>(ctx, t0, dt, n);
+  return with_dtype(ctx, [&](auto t) { return strang_t<decltype(t)>(ctx, t0, dt, n); });
 }
 
 void spectral_invalidate(pdeopt_ctx* ctx) {

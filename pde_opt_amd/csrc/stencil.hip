@@ -39,16 +39,12 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const Window& w, double t, const void* i
   s.acc = acc ? static_cast<T*>(acc) + woff : nullptr;
   s.a = T(a);
   s.b = T(b);
-  s.rhx = T(1.0 / p.hx);
-  s.rhy = T(1.0 / p.hy);
-  s.rhx2 = T(1.0 / (p.hx * p.hx));
-  s.rhy2 = T(1.0 / (p.hy * p.hy));
-  s.rhz = p.nz > 1 ? T(1.0 / p.hz) : T(0);
-  s.rhz2 = p.nz > 1 ? T(1.0 / (p.hz * p.hz)) : T(0);
+  const GridRecip r = grid_recip(p);
+  set_recip_plain(s, r);
+  s.rhz = p.nz > 1 ? T(r.rz) : T(0);
+  s.rhz2 = p.nz > 1 ? T(r.rz2) : T(0);
   s.mu3 = nullptr;
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + w.lo;
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  set_closures<T>(s, ctx, w.lo);
   s.vstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? (int64_t)p.nx * p.ny : 0;
   s.vx = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
   s.vy = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
@@ -57,7 +53,7 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const Window& w, double t, const void* i
   s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
   s.ngp = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
   s.mask = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
-  s.fe = ClosureSpec{p.fe.kind, p.fe.flags, p.fe.n};
+  s.fe = closure_spec(p.fe);
   if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || p.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM) {
     double tv[3] = {ctx->time_const[0], ctx->time_const[1], ctx->time_const[2]};
     // the table of pdeopt_set_time_table first (stage times arrive in order: resume at the cursor), the host callback
@@ -105,47 +101,36 @@ int launch_generic(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
     if (rc) return rc;
     StageArgs<T> s3 = s;
     s3.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
-    switch (classify_closures(p.mu, p.mob)) {
-      case CL_POLY:
-        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_POLY>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
-        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_POLY>), g3, block, 0, w.stream, s3);
-        ctx->last_kernel = "stage_generic<CH-3D,poly>";
-        break;
-      case CL_LOGIT:
-        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_LOGIT>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
-        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_LOGIT>), g3, block, 0, w.stream, s3);
-        ctx->last_kernel = "stage_generic<CH-3D,logit>";
-        break;
-      default:
-        hipLaunchKernelGGL((ch3d_mu_kernel<T, CL_GENERIC>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
-        hipLaunchKernelGGL((ch3d_stage_kernel<T, CL_GENERIC>), g3, block, 0, w.stream, s3);
-        ctx->last_kernel = "stage_generic<CH-3D>";
-    }
-    PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-    return PDEOPT_OK;
+    const int cl = classify_closures(p.mu, p.mob);
+    ctx->last_kernel = cl == CL_GENERIC ? "stage_generic<CH-3D>" : std::string("stage_generic<CH-3D,") + closure_class_name(cl) + ">";
+    return with_closure_class<CL_GENERIC, CL_POLY, CL_LOGIT>(cl, [&](auto c) -> int {
+      constexpr int CL = decltype(c)::value;
+      hipLaunchKernelGGL((ch3d_mu_kernel<T, CL>), g3, block, 0, w.stream, s3, const_cast<T*>(s3.mu3));
+      hipLaunchKernelGGL((ch3d_stage_kernel<T, CL>), g3, block, 0, w.stream, s3);
+      PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+      return PDEOPT_OK;
+    });
   }
+  // the one-pass generic kernel of equation EQ; named "stage_generic<short name>"
+  auto generic = [&](auto eq_c, const char* short_name) {
+    hipLaunchKernelGGL((stage_generic_kernel<T, decltype(eq_c)::value>), grid, block, 0, w.stream, s);
+    ctx->last_kernel = std::string("stage_generic<") + short_name + ">";
+  };
   switch (p.equation) {
     case PDEOPT_EQ_CAHN_HILLIARD:
-      hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_CAHN_HILLIARD>), grid, block, 0,
-                         w.stream, s);
-      ctx->last_kernel = "stage_generic<CH>";
+      generic(int_c<PDEOPT_EQ_CAHN_HILLIARD>{}, "CH");
       break;
     case PDEOPT_EQ_ALLEN_CAHN:
-      hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ALLEN_CAHN>), grid, block, 0,
-                         w.stream, s);
-      ctx->last_kernel = "stage_generic<AC>";
+      generic(int_c<PDEOPT_EQ_ALLEN_CAHN>{}, "AC");
       break;
     case PDEOPT_EQ_ADVECTION_DIFFUSION:
       if (!s.vx || !s.vy)
         return fail(ctx, PDEOPT_ESTATE, "advection-diffusion needs VX_FACE and VY_FACE aux fields");
-      hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ADVECTION_DIFFUSION>), grid, block, 0,
-                         w.stream, s);
-      ctx->last_kernel = "stage_generic<AD>";
+      generic(int_c<PDEOPT_EQ_ADVECTION_DIFFUSION>{}, "AD");
       break;
     case PDEOPT_EQ_SHAPE_SMOOTH:
       if (ctx->halo) return fail(ctx, PDEOPT_EINVAL, "shape smoothing needs the periodic layout");
-      hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_SHAPE_SMOOTH>), grid, block, 0, w.stream, s);
-      ctx->last_kernel = "stage_generic<shape-smooth>";
+      generic(int_c<PDEOPT_EQ_SHAPE_SMOOTH>{}, "shape-smooth");
       break;
     case PDEOPT_EQ_ALLEN_CAHN_SBM:
     case PDEOPT_EQ_CAHN_HILLIARD_SBM:
@@ -158,15 +143,13 @@ int launch_generic(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
         break;
       }
       if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM) {
-        hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_ALLEN_CAHN_SBM>), grid, block, 0, w.stream, s);
-        ctx->last_kernel = "stage_generic<AC-SBM>";
+        generic(int_c<PDEOPT_EQ_ALLEN_CAHN_SBM>{}, "AC-SBM");
       } else if (ctx->opt_fuse_stages < 0 ||
                  (ctx->opt_fuse_stages == 0 && (int64_t)p.nx * p.ny * w.n < (1 << 18))) {
         // the literal one-pass form (inner re-evaluated at 5 points per cell): one launch instead of two, faster
         // on the notebook-sized grids (128^2: 7.0 vs 7.7 us per evaluation); PDEOPT_OPT_FUSE_STAGES = 1 / -1
         // force the two-pass / the literal form
-        hipLaunchKernelGGL((stage_generic_kernel<T, PDEOPT_EQ_CAHN_HILLIARD_SBM>), grid, block, 0, w.stream, s);
-        ctx->last_kernel = "stage_generic<CH-SBM>";
+        generic(int_c<PDEOPT_EQ_CAHN_HILLIARD_SBM>{}, "CH-SBM");
       } else {
         // two passes: inner once per cell into the work field, then the psi-weighted flux divergence
         // (1024^2 fp32: 24.8 vs 30.6 us per evaluation; both forms are L2-bound one-thread-per-cell kernels)
@@ -219,10 +202,12 @@ int launch_stage_fourier(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s
   return PDEOPT_OK;
 }
 
-// One fused stage: k = rhs(in); out/acc updated per (out_mode, acc_mode).
-template <typename T>
-int launch_stage_t(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* out, void* acc, double a,
-                   double b, int out_mode, int acc_mode) {
+// What every per-stage launch does: bring the advection velocities to the stage time, fill the arguments (`extra`
+// adds what only one caller sets), count the launch and take the fourier, tiled or generic path.
+// refuse_forced_tiled: PDEOPT_OPT_KERNEL_PATH = 2 on a shape the tiled kernel does not cover is an error (the plain stage launch) or falls through to the generic kernel (the linear-combination launch)
+template <typename T, typename Extra>
+int launch_stage_path(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* out, void* acc, double a,
+                      double b, int out_mode, int acc_mode, bool refuse_forced_tiled, Extra&& extra) {
   if (ctx->prob.equation == PDEOPT_EQ_ADVECTION_DIFFUSION) {
     // velocity_fn(t, x, y): face velocities at the time of THIS right-hand side (t = stage time)
     int rc;
@@ -230,53 +215,44 @@ int launch_stage_t(pdeopt_ctx* ctx, const Window& w, double t, const void* in, c
     if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VY_FACE, t))) return rc;
   }
   StageArgs<T> s = make_args<T>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
+  extra(s);
   ctx->n_stage_launches++;
   if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, w, s, in, out);
-  if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) {
-    return launch_tiled<T>(ctx, w, s);
-  }
-  if (ctx->opt_kernel_path == 2)
+  if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) return launch_tiled<T>(ctx, w, s);
+  if (refuse_forced_tiled && ctx->opt_kernel_path == 2)
     return fail(ctx, PDEOPT_EINVAL, "LDS-tiled kernel forced but shape %dx%d / equation %d is not covered",
                 ctx->prob.nx, ctx->prob.ny, ctx->prob.equation);
   return launch_generic<T>(ctx, w, s);
 }
 
+// One fused stage: k = rhs(in); out/acc updated per (out_mode, acc_mode).
 int launch_stage(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* out, void* acc, double a,
                  double b, int out_mode, int acc_mode) {
-  if (ctx->prob.dtype == PDEOPT_F32)
-    return launch_stage_t<float>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
-  return launch_stage_t<double>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
+  return with_dtype(ctx, [&](auto tag) {
+    using T = decltype(tag);
+    return launch_stage_path<T>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode, /*refuse_forced_tiled=*/true, [](StageArgs<T>&) {});
+  });
 }
 
 // k = rhs(in) -> kout, and  next = y + sum_{j<n} c[j] K[j] + c[n] k  in the same pass (OUT_K_LC)
 template <typename T>
 int launch_stage_lc(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* kout, void* const* ks, const double* c,
                     int n, void* next) {
-  if (ctx->prob.equation == PDEOPT_EQ_ADVECTION_DIFFUSION) {
-    int rc;
-    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VX_FACE, t))) return rc;
-    if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_VY_FACE, t))) return rc;
-  }
-  StageArgs<T> s = make_args<T>(ctx, w, t, in, y, kout, nullptr, 0.0, 0.0, OUT_K_LC, ACC_NONE);
-  const int64_t woff = (int64_t)w.lo * s.g.bstride;
-  for (int j = 0; j < n; ++j) {
-    s.lc.k[j] = static_cast<const T*>(ks[j]) + woff;
-    s.lc.c[j] = T(c[j]);
-  }
-  s.lc.c[n] = T(c[n]);
-  s.lc.n = n;
-  s.lc.next = static_cast<T*>(next) + woff;
-  ctx->n_stage_launches++;
-  if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, w, s, in, kout);
-  if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) return launch_tiled<T>(ctx, w, s);
-  return launch_generic<T>(ctx, w, s);
+  return launch_stage_path<T>(ctx, w, t, in, y, kout, nullptr, 0.0, 0.0, OUT_K_LC, ACC_NONE, /*refuse_forced_tiled=*/false, [&](StageArgs<T>& s) {
+    const int64_t woff = (int64_t)w.lo * s.g.bstride;
+    for (int j = 0; j < n; ++j) {
+      s.lc.k[j] = static_cast<const T*>(ks[j]) + woff;
+      s.lc.c[j] = T(c[j]);
+    }
+    s.lc.c[n] = T(c[n]);
+    s.lc.n = n;
+    s.lc.next = static_cast<T*>(next) + woff;
+  });
 }
 
 int launch_pair_dt(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, int pair, const void* in, const void* y, const void* acc, void* out,
                    void* acc_out, double aA, double bA, double aB, double bB) {
-  if (ctx->prob.dtype == PDEOPT_F32)
-    return launch_pair<float>(ctx, w, io, pair, in, y, acc, out, acc_out, aA, bA, aB, bB);
-  return launch_pair<double>(ctx, w, io, pair, in, y, acc, out, acc_out, aA, bA, aB, bB);
+  return with_dtype(ctx, [&](auto t) { return launch_pair<decltype(t)>(ctx, w, io, pair, in, y, acc, out, acc_out, aA, bA, aB, bB); });
 }
 
 template <typename T>
@@ -299,8 +275,10 @@ int launch_rhs(pdeopt_ctx* ctx, const Window& w, const void* in, void* out, doub
 int launch_rhs_slope(pdeopt_ctx* ctx, const Window& w, const void* in, void* out, double t) {
 #if PDEOPT_IMEX_SLOPE_PAIR
   if (ctx->prob.derivs == PDEOPT_DERIVS_FD && ctx->prob.nz <= 1 && !ctx->time_fn) {
-    if (ctx->prob.dtype == PDEOPT_F32 && slope_pair_supported<float>(ctx)) return launch_slope_pair<float>(ctx, w, in, out);
-    if (ctx->prob.dtype == PDEOPT_F64 && slope_pair_supported<double>(ctx)) return launch_slope_pair<double>(ctx, w, in, out);
+    return with_dtype(ctx, [&](auto tag) {
+      using T = decltype(tag);
+      return slope_pair_supported<T>(ctx) ? launch_slope_pair<T>(ctx, w, in, out) : launch_rhs(ctx, w, in, out, t);
+    });
   }
 #endif
   return launch_rhs(ctx, w, in, out, t);
@@ -320,6 +298,10 @@ GraphStructure graph_structure(const pdeopt_problem& p) {
 }
 }  // namespace
 
+static bool fused_supported_dt(const pdeopt_ctx* ctx) {
+  return with_dtype(ctx, [&](auto t) { return fused_supported<decltype(t)>(ctx); });
+}
+
 // Does the whole-environment-step kernel (stencil_small.hpp) take this advance?  PDEOPT_OPT_SMALL_PERSIST: 1 = wherever
 // it can run, -1 = never, 0 = auto: grids of at most 64^2-class size (<= 4096 cells: one launch instead of 2 n
 // dependent ones, measured 2.7-4.8 x faster per environment step), and larger LDS-resident grids once enough
@@ -328,8 +310,7 @@ GraphStructure graph_structure(const pdeopt_problem& p) {
 static bool small_chosen(const pdeopt_ctx* ctx, int integrator, int64_t n) {
   if (ctx->opt_small_persist < 0 || ctx->opt_kernel_path == 1 || ctx->opt_debug_ablate) return false;
   if (integrator != PDEOPT_INT_EULER && integrator != PDEOPT_INT_RK4) return false;
-  const bool ok = ctx->prob.dtype == PDEOPT_F32 ? small_supported<float>(ctx) : small_supported<double>(ctx);
-  if (!ok) return false;
+  if (!with_dtype(ctx, [&](auto t) { return small_supported<decltype(t)>(ctx); })) return false;
   if (ctx->opt_small_persist > 0) return true;
   // a caller who turned one of the tiled path's knobs is asking for that path
   if (ctx->opt_fuse_stages != 0 || ctx->opt_kernel_path != 0 || ctx->opt_graph != 0 || ctx->opt_group_envs != 0 || ctx->opt_tile_rows != 0)
@@ -343,23 +324,24 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   int rc;
   // one environment (or a few) of a mid-sized grid: several compute units per environment, all substeps in one launch
   // (stencil_coop_adaptive.hpp, MODE 1)
-  const bool coop = ctx->prob.dtype == PDEOPT_F32 ? coop_fixed_chosen<float>(ctx, integrator, n) : coop_fixed_chosen<double>(ctx, integrator, n);
+  const bool coop = with_dtype(ctx, [&](auto t) { return coop_fixed_chosen<decltype(t)>(ctx, integrator, n); });
+  const bool small = small_chosen(ctx, integrator, n);
   const bool f64 = ctx->prob.dtype == PDEOPT_F64;  // (64^2 fp64: 0.70 ms against the one-CU kernel's 1.14, which small_chosen would pick)
-  if (coop && (ctx->opt_small_persist == 2 || f64 || !small_chosen(ctx, integrator, n))) {
+  if (coop && (ctx->opt_small_persist == 2 || f64 || !small)) {
     ctx->last_groups = 1;
-    return ctx->prob.dtype == PDEOPT_F32 ? coop_fixed_advance<float>(ctx, integrator, t0, dt, n) : coop_fixed_advance<double>(ctx, integrator, t0, dt, n);
+    return with_dtype(ctx, [&](auto t) { return coop_fixed_advance<decltype(t)>(ctx, integrator, t0, dt, n); });
   }
   const Window all = whole_batch(ctx);
-  if (small_chosen(ctx, integrator, n)) {
+  if (small) {
     ctx->last_groups = 1;
-    return ctx->prob.dtype == PDEOPT_F32 ? launch_small<float>(ctx, all, integrator, dt, n) : launch_small<double>(ctx, all, integrator, dt, n);
+    return with_dtype(ctx, [&](auto t) { return launch_small<decltype(t)>(ctx, all, integrator, dt, n); });
   }
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   // Euler: two substeps per launch through the stage-pair kernels where they exist
   //   PAIR_12 with aA = bA = bB = dt:  w = y + dt f(y),  ACC = y + dt f(y) + dt f(w) = two Euler steps
   const bool euler2 = integrator == PDEOPT_INT_EULER && ctx->opt_kernel_path != 1 &&
                       ctx->prob.derivs == PDEOPT_DERIVS_FD && n >= 2 &&
-                      (ctx->prob.dtype == PDEOPT_F32 ? fused_supported<float>(ctx) : fused_supported<double>(ctx));
+                      fused_supported_dt(ctx);
   if (integrator == PDEOPT_INT_RK4 || euler2) {
     if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
     if (integrator == PDEOPT_INT_RK4 && (rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
@@ -409,7 +391,7 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   }
   const bool fused = integrator == PDEOPT_INT_RK4 && ctx->opt_kernel_path != 1 &&
                      ctx->prob.derivs == PDEOPT_DERIVS_FD &&
-                     (ctx->prob.dtype == PDEOPT_F32 ? fused_supported<float>(ctx) : fused_supported<double>(ctx));
+                     fused_supported_dt(ctx);
 
   // Allen-Cahn fp32: the whole RK4 substep in one pass (2 words per cell instead of 7)
   const bool quad = integrator == PDEOPT_INT_RK4 && ac_quad_supported(ctx);
@@ -525,7 +507,7 @@ void graph_destroy(pdeopt_ctx* ctx) {
 // domain-decomposed driver exchanges halos of `fields[phase]` before `rk4_phase(phase)`).
 int rk4_phase_plan(pdeopt_ctx* ctx, int* fields, int* nphases) {
   const bool fused = ctx->opt_kernel_path != 1 && ctx->prob.derivs == PDEOPT_DERIVS_FD &&
-                     (ctx->prob.dtype == PDEOPT_F32 ? fused_supported<float>(ctx) : fused_supported<double>(ctx));
+                     fused_supported_dt(ctx);
   if (ctx->halo == 8 && ch_quad_chosen(ctx)) {
     // halo-8 layout, the whole substep in one kernel (stencil_fused_ch4.hpp): its tile + 8 input is the halo
     *nphases = 1;
@@ -787,8 +769,7 @@ int tsit5_trial_t(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol
 }  // namespace
 
 int tsit5_trial(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol, double* err) {
-  return ctx->prob.dtype == PDEOPT_F32 ? tsit5_trial_t<float>(ctx, t, dt, rtol, atol, err)
-                                       : tsit5_trial_t<double>(ctx, t, dt, rtol, atol, err);
+  return with_dtype(ctx, [&](auto tag) { return tsit5_trial_t<decltype(tag)>(ctx, t, dt, rtol, atol, err); });
 }
 
 template <typename T>
@@ -813,8 +794,7 @@ static int tsit5_dense_t(pdeopt_ctx* ctx, double theta, double dt, int env_first
 
 int tsit5_dense(pdeopt_ctx* ctx, double theta, double dt, int env_first, int env_count, void* dev_out) {
   if (!ctx->tsit5_pending) return fail(ctx, PDEOPT_ESTATE, "dense output needs a pending Tsit5 trial step");
-  return ctx->prob.dtype == PDEOPT_F32 ? tsit5_dense_t<float>(ctx, theta, dt, env_first, env_count, dev_out)
-                                       : tsit5_dense_t<double>(ctx, theta, dt, env_first, env_count, dev_out);
+  return with_dtype(ctx, [&](auto t) { return tsit5_dense_t<decltype(t)>(ctx, theta, dt, env_first, env_count, dev_out); });
 }
 
 // FSAL slope of environment b *= ratio[b] (its step size changed between two per-environment trials)
@@ -830,10 +810,10 @@ int tsit5_rescale_fsal(pdeopt_ctx* ctx, const double* ratio) {
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->red_dev, ratio, need, hipMemcpyHostToDevice, ctx->stream));
   const int64_t ee = (int64_t)ctx->env_elems;
   const dim3 grid((unsigned)std::min<int64_t>((ee + 255) / 256, 1024), ctx->prob.batch);
-  if (ctx->prob.dtype == PDEOPT_F32)
-    hipLaunchKernelGGL(env_scale_kernel<float>, grid, dim3(256), 0, ctx->stream, (float*)ctx->K[0], (const double*)ctx->red_dev, ee);
-  else
-    hipLaunchKernelGGL(env_scale_kernel<double>, grid, dim3(256), 0, ctx->stream, (double*)ctx->K[0], (const double*)ctx->red_dev, ee);
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(env_scale_kernel<T>, grid, dim3(256), 0, ctx->stream, (T*)ctx->K[0], (const double*)ctx->red_dev, ee);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // `ratio` is the caller's again
   return PDEOPT_OK;
@@ -872,10 +852,10 @@ int tsit5_commit(pdeopt_ctx* ctx, int accept) {
 // stencil_small_adaptive.hpp) or several cooperating workgroups per environment (larger grids, the smoothed-boundary
 // forms, advection-diffusion: stencil_coop_adaptive.hpp)
 static bool tsit5_single_wg(const pdeopt_ctx* ctx) {
-  return ctx->prob.dtype == PDEOPT_F32 ? small_tsit5_supported<float>(ctx) : small_tsit5_supported<double>(ctx);
+  return with_dtype(ctx, [&](auto t) { return small_tsit5_supported<decltype(t)>(ctx); });
 }
 static bool tsit5_coop(const pdeopt_ctx* ctx) {
-  return ctx->prob.dtype == PDEOPT_F32 ? coop_tsit5_supported<float>(ctx) : coop_tsit5_supported<double>(ctx);
+  return with_dtype(ctx, [&](auto t) { return coop_tsit5_supported<decltype(t)>(ctx); });
 }
 bool tsit5_solve_small_supported(const pdeopt_ctx* ctx) { return tsit5_single_wg(ctx) || tsit5_coop(ctx); }
 
@@ -890,11 +870,11 @@ int tsit5_solve_small(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   constexpr int kV32 = 4, kV64 = 2;
   const int64_t nvec = (int64_t)ctx->prob.nx * ctx->prob.ny / (ctx->prob.dtype == PDEOPT_F32 ? kV32 : kV64);
   const bool prefer_coop = ctx->opt_small_persist == 2 || (ctx->opt_small_persist == 0 && nvec > 1024);
-  if (coop && (!single || prefer_coop))
-    return ctx->prob.dtype == PDEOPT_F32 ? coop_tsit5_solve<float>(ctx, t0, t1, dt0, pid, max_steps, n_save, save_ts, save_host, stats)
-                                         : coop_tsit5_solve<double>(ctx, t0, t1, dt0, pid, max_steps, n_save, save_ts, save_host, stats);
-  return ctx->prob.dtype == PDEOPT_F32 ? small_tsit5_solve<float>(ctx, t0, t1, dt0, pid, max_steps, n_save, save_ts, save_host, stats)
-                                       : small_tsit5_solve<double>(ctx, t0, t1, dt0, pid, max_steps, n_save, save_ts, save_host, stats);
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    if (coop && (!single || prefer_coop)) return coop_tsit5_solve<T>(ctx, t0, t1, dt0, pid, max_steps, n_save, save_ts, save_host, stats);
+    return small_tsit5_solve<T>(ctx, t0, t1, dt0, pid, max_steps, n_save, save_ts, save_host, stats);
+  });
 }
 
 int launch_lerp(pdeopt_ctx* ctx, const void* a, const void* b, void* out, double theta,
@@ -903,13 +883,10 @@ int launch_lerp(pdeopt_ctx* ctx, const void* a, const void* b, void* out, double
   const int64_t n = (int64_t)(env_count * ctx->env_elems);
   const int threads = 256;
   const int blocks = (int)std::min<int64_t>((n + threads - 1) / threads, 2048);
-  if (ctx->prob.dtype == PDEOPT_F32) {
-    hipLaunchKernelGGL(lerp_kernel<float>, dim3(blocks), dim3(threads), 0, ctx->stream,
-                       (const float*)a + off, (const float*)b + off, (float*)out, (float)theta, n);
-  } else {
-    hipLaunchKernelGGL(lerp_kernel<double>, dim3(blocks), dim3(threads), 0, ctx->stream,
-                       (const double*)a + off, (const double*)b + off, (double*)out, theta, n);
-  }
+  with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(lerp_kernel<T>, dim3(blocks), dim3(threads), 0, ctx->stream, (const T*)a + off, (const T*)b + off, (T*)out, (T)theta, n);
+  });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
 }

@@ -1167,7 +1167,7 @@ CoopKernel coop_select_kernel(pdeopt_ctx* ctx, const CoopPlan& pl, const char* s
   const bool sbm = eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM;
   const bool fast = eq == PDEOPT_EQ_ADVECTION_DIFFUSION || coop_fast_closures(p, sbm);
   char name[112];
-  snprintf(name, sizeof(name), "%s_coop<%s,%s,%s,%dx%d workgroups>", scheme, sizeof(T) == 4 ? "f32" : "f64", equation_short_name(eq),
+  snprintf(name, sizeof(name), "%s_coop<%s,%s,%s,%dx%d workgroups>", scheme, dtype_name<T>(), equation_short_name(eq),
            fast ? "fixed closures" : "generic closures", pl.px, pl.py);
   ctx->last_kernel = name;
   return coop_kernel<T, MODE>(eq, fast);
@@ -1185,11 +1185,8 @@ CoopArgs<T> coop_common_args(const pdeopt_ctx* ctx, const CoopPlan& pl, const Co
   CoopArgs<T> s{};
   s.nx = p.nx; s.ny = p.ny; s.px = pl.px; s.py = pl.py;
   s.bstride = make_geo(ctx).bstride;
-  s.rhx = T(1.0 / p.hx); s.rhy = T(1.0 / p.hy);
-  s.rhx2 = T(1.0 / (p.hx * p.hx)); s.rhy2 = T(1.0 / (p.hy * p.hy));
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
-  s.fe = ClosureSpec{p.fe.kind, p.fe.flags, p.fe.n};
+  set_recip_plain(s, grid_recip(p));
+  s.mu = closure_spec(p.mu); s.mob = closure_spec(p.mob); s.fe = closure_spec(p.fe);  // (ep: per launch, coop_run)
   s.rows = pl.rows; s.pitch = pl.pitch; s.red_off = pl.red_off;
   s.xs = sh.xs; s.wpx = sh.wpx;
   if (eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM) {
@@ -1236,7 +1233,7 @@ int coop_run(pdeopt_ctx* ctx, const CoopKernel& kern, const CoopPlan& pl, const 
     CoopArgs<T> c = s;
     c.nenv = std::min(sh.envs_per_launch, batch - e0);
     c.y = static_cast<T*>(ctx->Y) + (int64_t)e0 * s.bstride;
-    c.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + e0;
+    c.ep = env_params<T>(ctx, e0);
     c.s0 = s.s0 ? s.s0 + (int64_t)e0 * s.sstride : nullptr;
     c.s1 = s.s1 ? s.s1 + (int64_t)e0 * s.sstride : nullptr;
     per_launch(c, e0);

@@ -269,11 +269,10 @@ inline int launch_ac_quad(pdeopt_ctx* ctx, const Window& w, const void* y, void*
   s.y = static_cast<const float*>(y) + woff;
   s.out = static_cast<float*>(out) + woff;
   s.dt = (float)dt;
-  s.rhx2 = (float)(1.0 / (p.hx * p.hx));
-  s.rhy2 = (float)(1.0 / (p.hy * p.hy));
-  s.ep = static_cast<const EnvParams<float>*>(ctx->env_params_dev) + w.lo;
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  const GridRecip r = grid_recip(p);
+  s.rhx2 = (float)r.rx2;
+  s.rhy2 = (float)r.ry2;
+  set_closures<float>(s, ctx, w.lo);
   const int tiles_i = (p.nx + G::TX - 1) / G::TX;
   const int tiles_j = (p.ny + G::TY - 1) / G::TY;
   const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
@@ -287,17 +286,15 @@ inline int launch_ac_quad(pdeopt_ctx* ctx, const Window& w, const void* y, void*
 #define PDEOPT_AC4_M0 1
 #endif
   const bool m0 = PDEOPT_AC4_M0 && p.mob.n <= 1;  // constant mobility (coefficients past n are stored as zeros)
-#define PDEOPT_QUAD_LAUNCH(CLV, RG) \
-  hipLaunchKernelGGL((ac_rk4_quad_kernel<CLV, RG>), dim3(nblk), dim3(G::NT), G::lds_bytes(), w.stream, s, tiles_i, \
-                     tiles_j, nblk, remap)
-  if (m0) {
-    if (ragged) PDEOPT_QUAD_LAUNCH(CL_POLY_M0, true); else PDEOPT_QUAD_LAUNCH(CL_POLY_M0, false);
-  } else {
-    if (ragged) PDEOPT_QUAD_LAUNCH(CL_POLY, true); else PDEOPT_QUAD_LAUNCH(CL_POLY, false);
-  }
-#undef PDEOPT_QUAD_LAUNCH
-  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  return PDEOPT_OK;
+  return with_closure_class<CL_POLY, CL_POLY_M0>(m0 ? CL_POLY_M0 : CL_POLY, [&](auto c) {
+    constexpr int CL = decltype(c)::value;
+    auto go = [&](auto kern) -> int {
+      hipLaunchKernelGGL(kern, dim3(nblk), dim3(G::NT), G::lds_bytes(), w.stream, s, tiles_i, tiles_j, nblk, remap);
+      PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+      return PDEOPT_OK;
+    };
+    return ragged ? go(ac_rk4_quad_kernel<CL, true>) : go(ac_rk4_quad_kernel<CL, false>);
+  });
 }
 
 }  // namespace pdeopt

@@ -433,11 +433,9 @@ int launch_ch_quad_g(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const v
   s.y = static_cast<const float*>(y) + woff;
   s.out = static_cast<float*>(out) + woff;
   s.dt = (float)dt; s.h2 = (float)(dt / 2); s.h3 = (float)(dt / 3); s.h6 = (float)(dt / 6);
-  s.rhx = (float)(0.5 / (p.hx * p.hx)); s.rhy = (float)(0.5 / (p.hy * p.hy));
-  s.rhx2 = (float)(1.0 / (p.hx * p.hx)); s.rhy2 = (float)(1.0 / (p.hy * p.hy));
-  s.ep = static_cast<const EnvParams<float>*>(ctx->env_params_dev) + w.lo;
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  const GridRecip r = grid_recip(p);
+  set_recip_halved(s, r.rx2, r.ry2);
+  set_closures<float>(s, ctx, w.lo);
   const int tiles_i = p.nx / G::TX, tiles_j = p.ny / G::TY;
   const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
@@ -446,7 +444,8 @@ int launch_ch_quad_g(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const v
   const int cl = classify_closures(p.mu, p.mob);
   const int remap = tile_flags(nblk, tiles_i, tiles_j);
   const size_t lds = G::lds_bytes();
-  auto go = [&](auto kern, const char* name) -> int {
+  const bool halo8 = ctx->halo == 8;
+  auto go = [&](auto kern) -> int {
     // 75-80 KB of dynamic LDS need the opt-in once per device and kernel (a static per instantiation of this lambda)
     static std::atomic<uint64_t> allowed{0};
     const uint64_t bit = 1ull << (ctx->device & 63);
@@ -456,21 +455,19 @@ int launch_ch_quad_g(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const v
     }
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(G::NT), lds, w.stream, s, tiles_i, tiles_j, nblk, remap);
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-    ctx->last_kernel = std::string(name) + (G::TX == 64 ? ",rows64>" : ",rows32>");
+    ctx->last_kernel = std::string("rk4_quad<f32,CH,") + (halo8 ? "halo8," : "") + closure_class_name(cl) + (G::TX == 64 ? ",rows64>" : ",rows32>");
     return PDEOPT_OK;
   };
-  if (ctx->halo == 8) {
+  if (halo8) {
     // decomposed field: halo cells from the gathered strips / the new strip out of the store epilogue (rk4_substep_h8)
     s.strip = static_cast<float*>(io.strip);
     s.strip_env = 2LL * 8 * p.ny + 2LL * p.nx * 8 + 4LL * 64;
     fill_neighbour_strips<float>(io, s.strip_env * p.batch, s.nbase);
-    if (cl == CL_LOGIT && p.mu.n <= 2) return go(ch_rk4_quad_kernel<CL_LOGIT1, G, true>, "rk4_quad<f32,CH,halo8,logit");
-    if (cl == CL_LOGIT) return go(ch_rk4_quad_kernel<CL_LOGIT, G, true>, "rk4_quad<f32,CH,halo8,logit");
-    return go(ch_rk4_quad_kernel<CL_POLY, G, true>, "rk4_quad<f32,CH,halo8,poly");
   }
-  if (cl == CL_LOGIT && p.mu.n <= 2) return go(ch_rk4_quad_kernel<CL_LOGIT1, G>, "rk4_quad<f32,CH,logit");
-  if (cl == CL_LOGIT) return go(ch_rk4_quad_kernel<CL_LOGIT, G>, "rk4_quad<f32,CH,logit");
-  return go(ch_rk4_quad_kernel<CL_POLY, G>, "rk4_quad<f32,CH,poly");
+  return with_closure_class<CL_POLY, CL_LOGIT, CL_LOGIT1>(narrow_logit1(cl, p.mu), [&](auto c) {
+    constexpr int CL = decltype(c)::value;
+    return halo8 ? go(ch_rk4_quad_kernel<CL, G, true>) : go(ch_rk4_quad_kernel<CL, G>);
+  });
 }
 
 inline int launch_ch_quad(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const void* y, void* out, double dt) {

@@ -20,11 +20,9 @@ int launch_pair(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, int pair, co
   s.out = static_cast<T*>(out) + woff;
   s.acc_out = acc_out ? static_cast<T*>(acc_out) + woff : nullptr;
   s.aA = T(aA); s.bA = T(bA); s.aB = T(aB); s.bB = T(bB);
-  s.rhx = T(0.5 / (p.hx * p.hx)); s.rhy = T(0.5 / (p.hy * p.hy));
-  s.rhx2 = T(1.0 / (p.hx * p.hx)); s.rhy2 = T(1.0 / (p.hy * p.hy));
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + w.lo;
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  const GridRecip r = grid_recip(p);
+  set_recip_halved(s, r.rx2, r.ry2);
+  set_closures<T>(s, ctx, w.lo);
   s.dbg = (int)ctx->opt_debug_ablate;
   s.part = io.part;
   // halo-8 layout of a decomposed field: PAIR_12 on the tile + 4 ring, PAIR_34 with the fused pack
@@ -52,23 +50,21 @@ int launch_pair(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, int pair, co
   int rpt = tiled_rpt(ctx);
   if (p.equation == PDEOPT_EQ_CAHN_HILLIARD && ctx->opt_tile_rows == 0) rpt = (p.nx % 32 == 0) ? 4 : 2;
   char name[96];
-  snprintf(name, sizeof(name), "stage_pair<%s,%s,%s,rows%d>", sizeof(T) == 4 ? "f32" : "f64",
-           p.equation == PDEOPT_EQ_ALLEN_CAHN ? "AC" : "CH", cl == CL_LOGIT ? "logit" : "poly", 8 * rpt);
+  snprintf(name, sizeof(name), "stage_pair<%s,%s,%s,rows%d>", dtype_name<T>(), p.equation == PDEOPT_EQ_ALLEN_CAHN ? "AC" : "CH",
+           closure_class_name(cl), 8 * rpt);
   ctx->last_kernel = name;
-  if (cl == CL_LOGIT && p.mu.n <= 2 && p.equation == PDEOPT_EQ_CAHN_HILLIARD) {
-    // linear polynomial part: the shorter closure (same bits, see closures.hpp)
-    if (rpt == 2)
-      return pair == PAIR_12 ? launch_pair_ch_inst<T, CL_LOGIT1, PAIR_12, 2>(ctx, w, s, ext)
-                             : launch_pair_ch_inst<T, CL_LOGIT1, PAIR_34, 2>(ctx, w, s, 0);
-    return pair == PAIR_12 ? launch_pair_ch_inst<T, CL_LOGIT1, PAIR_12, 4>(ctx, w, s, ext)
-                           : launch_pair_ch_inst<T, CL_LOGIT1, PAIR_34, 4>(ctx, w, s, 0);
-  }
-#define PDEOPT_PAIR_DISPATCH(CLV, PAIRV)                                             \
-  (rpt == 2 ? launch_pair_inst<T, CLV, PAIRV, 2>(ctx, w, s, ext) : launch_pair_inst<T, CLV, PAIRV, 4>(ctx, w, s, ext))
-  if (cl == CL_LOGIT)
-    return pair == PAIR_12 ? PDEOPT_PAIR_DISPATCH(CL_LOGIT, PAIR_12) : PDEOPT_PAIR_DISPATCH(CL_LOGIT, PAIR_34);
-  return pair == PAIR_12 ? PDEOPT_PAIR_DISPATCH(CL_POLY, PAIR_12) : PDEOPT_PAIR_DISPATCH(CL_POLY, PAIR_34);
-#undef PDEOPT_PAIR_DISPATCH
+  // CH with a linear polynomial part: the shorter closure (same bits, see closures.hpp); ext is 0 outside PAIR_12
+  const int cl1 = p.equation == PDEOPT_EQ_CAHN_HILLIARD ? narrow_logit1(cl, p.mu) : cl;
+  return with_closure_class<CL_POLY, CL_LOGIT, CL_LOGIT1>(cl1, [&](auto c) {
+    constexpr int CL = decltype(c)::value;
+    auto go = [&](auto pr, auto rows) {
+      constexpr int PAIR = decltype(pr)::value, RPT = decltype(rows)::value;
+      if constexpr (CL == CL_LOGIT1) return launch_pair_ch_inst<T, CL, PAIR, RPT>(ctx, w, s, ext);
+      else return launch_pair_inst<T, CL, PAIR, RPT>(ctx, w, s, ext);
+    };
+    if (pair == PAIR_12) return rpt == 2 ? go(int_c<PAIR_12>{}, int_c<2>{}) : go(int_c<PAIR_12>{}, int_c<4>{});
+    return rpt == 2 ? go(int_c<PAIR_34>{}, int_c<2>{}) : go(int_c<PAIR_34>{}, int_c<4>{});
+  });
 }
 
 // out = f(in) for every environment of the window through the stage-B half of the fused kernel
@@ -88,20 +84,17 @@ int launch_slope_pair(pdeopt_ctx* ctx, const Window& w, const void* in, void* ou
   const int64_t woff = (int64_t)w.lo * s.g.bstride;
   s.in = static_cast<const T*>(in) + woff;
   s.out = static_cast<T*>(out) + woff;
-  s.rhx = T(0.5 / (p.hx * p.hx)); s.rhy = T(0.5 / (p.hy * p.hy));
-  s.rhx2 = T(1.0 / (p.hx * p.hx)); s.rhy2 = T(1.0 / (p.hy * p.hy));
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + w.lo;
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  const GridRecip r = grid_recip(p);
+  set_recip_halved(s, r.rx2, r.ry2);
+  set_closures<T>(s, ctx, w.lo);
   ctx->n_stage_launches++;
   const int cl = classify_closures(p.mu, p.mob);
   const bool rows32 = ctx->opt_tile_rows == 32 || (ctx->opt_tile_rows == 0 && p.nx % 32 == 0);
   ctx->last_kernel = rows32 ? "slope_pair<CH,rows32>" : "slope_pair<CH,rows16>";
-#define PDEOPT_SLOPE(CLV) \
-  (rows32 ? launch_pair_ch_inst<T, CLV, PAIR_K, 4>(ctx, w, s, 0) : launch_pair_ch_inst<T, CLV, PAIR_K, 2>(ctx, w, s, 0))
-  if (cl == CL_LOGIT) return p.mu.n <= 2 ? PDEOPT_SLOPE(CL_LOGIT1) : PDEOPT_SLOPE(CL_LOGIT);
-  return PDEOPT_SLOPE(CL_POLY);
-#undef PDEOPT_SLOPE
+  return with_closure_class<CL_POLY, CL_LOGIT, CL_LOGIT1>(narrow_logit1(cl, p.mu), [&](auto c) {
+    constexpr int CL = decltype(c)::value;
+    return rows32 ? launch_pair_ch_inst<T, CL, PAIR_K, 4>(ctx, w, s, 0) : launch_pair_ch_inst<T, CL, PAIR_K, 2>(ctx, w, s, 0);
+  });
 }
 
 }  // namespace pdeopt

@@ -291,8 +291,9 @@ struct SmallDims {
   double rx2, ry2;  // 1 / hx^2, 1 / hy^2
 };
 inline SmallDims small_dims(const pdeopt_problem& p) {
-  if (p.ny == 1 && p.nx > 1) return {1, p.nx, 0.0, 1.0 / (p.hx * p.hx)};
-  return {p.nx, p.ny, p.nx > 1 ? 1.0 / (p.hx * p.hx) : 0.0, p.ny > 1 ? 1.0 / (p.hy * p.hy) : 0.0};
+  const GridRecip r = grid_recip(p);
+  if (p.ny == 1 && p.nx > 1) return {1, p.nx, 0.0, r.rx2};
+  return {p.nx, p.ny, p.nx > 1 ? r.rx2 : 0.0, p.ny > 1 ? r.ry2 : 0.0};
 }
 
 // can the whole-step kernel run this problem at all?
@@ -348,11 +349,8 @@ int launch_small(pdeopt_ctx* ctx, const Window& w, int integrator, double dt, in
   s.n = n;
   s.rk4 = integrator == PDEOPT_INT_RK4 ? 1 : 0;
   s.dt = T(dt); s.h2 = T(dt / 2); s.h3 = T(dt / 3); s.h6 = T(dt / 6);
-  s.rhx = T(0.5 * d.rx2); s.rhy = T(0.5 * d.ry2);
-  s.rhx2 = T(d.rx2); s.rhy2 = T(d.ry2);
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev) + w.lo;
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  set_recip_halved(s, d.rx2, d.ry2);
+  set_closures<T>(s, ctx, w.lo);
   const int64_t nvec = (int64_t)d.nx * (d.ny / V);
   int nt, kmax;
   small_shape(nvec, &nt, &kmax);
@@ -363,17 +361,17 @@ int launch_small(pdeopt_ctx* ctx, const Window& w, int integrator, double dt, in
   const size_t lds = db ? lds3 : small_lds_bytes<T>(ctx);
   const int cl = classify_closures(p.mu, p.mob);
   char name[112];
-  snprintf(name, sizeof(name), "small_persist<%s,%s,%s,%dx%d threads,%d vec/thread%s>", sizeof(T) == 4 ? "f32" : "f64",
-           p.equation == PDEOPT_EQ_ALLEN_CAHN ? "AC" : "CH", cl == CL_LOGIT ? "logit" : "poly", 1, nt, kmax, db ? ",2 inputs" : "");
+  snprintf(name, sizeof(name), "small_persist<%s,%s,%s,%dx%d threads,%d vec/thread%s>", dtype_name<T>(),
+           p.equation == PDEOPT_EQ_ALLEN_CAHN ? "AC" : "CH", closure_class_name(cl), 1, nt, kmax, db ? ",2 inputs" : "");
   ctx->last_kernel = name;
   ctx->n_stage_launches++;
-  if (p.equation == PDEOPT_EQ_CAHN_HILLIARD) {
-    if (cl == CL_LOGIT && p.mu.n <= 2) return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT1>(ctx, w, s, nt, kmax, lds);
-    if (cl == CL_LOGIT) return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT>(ctx, w, s, nt, kmax, lds);
-    return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_POLY>(ctx, w, s, nt, kmax, lds);
-  }
-  if (cl == CL_LOGIT) return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_LOGIT>(ctx, w, s, nt, kmax, lds);
-  return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_POLY>(ctx, w, s, nt, kmax, lds);
+  if (p.equation == PDEOPT_EQ_CAHN_HILLIARD)
+    return with_closure_class<CL_POLY, CL_LOGIT, CL_LOGIT1>(narrow_logit1(cl, p.mu), [&](auto c) {
+      return launch_small_k<T, PDEOPT_EQ_CAHN_HILLIARD, decltype(c)::value>(ctx, w, s, nt, kmax, lds);
+    });
+  return with_closure_class<CL_POLY, CL_LOGIT>(cl, [&](auto c) {  // (Allen-Cahn has no CL_LOGIT1 kernels)
+    return launch_small_k<T, PDEOPT_EQ_ALLEN_CAHN, decltype(c)::value>(ctx, w, s, nt, kmax, lds);
+  });
 }
 
 }  // namespace pdeopt

@@ -321,11 +321,8 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   s.nx = d.nx;
   s.ny = d.ny;
   s.bstride = g.bstride;
-  s.rhx = T(0.5 * d.rx2); s.rhy = T(0.5 * d.ry2);
-  s.rhx2 = T(d.rx2); s.rhy2 = T(d.ry2);
-  s.ep = static_cast<const EnvParams<T>*>(ctx->env_params_dev);
-  s.mu = ClosureSpec{p.mu.kind, p.mu.flags, p.mu.n};
-  s.mob = ClosureSpec{p.mob.kind, p.mob.flags, p.mob.n};
+  set_recip_halved(s, d.rx2, d.ry2);
+  set_closures<T>(s, ctx, 0);
   s.t0 = t0; s.t1 = t1; s.dt0 = dt0;
   s.pid = make_pid_consts(*pid);
   s.max_steps = max_steps;
@@ -360,21 +357,20 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   const size_t lds = tile_bytes + 16 * sizeof(double);
   const int cl = classify_closures(p.mu, p.mob);
   char name[96];
-  snprintf(name, sizeof(name), "small_tsit5<%s,%s,%s,%d threads,%d vec/thread>", sizeof(T) == 4 ? "f32" : "f64",
-           equation_short_name(p.equation), cl == CL_LOGIT ? "logit" : "poly", nt, kmax);
+  snprintf(name, sizeof(name), "small_tsit5<%s,%s,%s,%d threads,%d vec/thread>", dtype_name<T>(),
+           equation_short_name(p.equation), closure_class_name(cl), nt, kmax);
   ctx->last_kernel = name;
   ctx->n_stage_launches++;
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-  if (p.equation == PDEOPT_EQ_CAHN_HILLIARD) {
-    if (cl == CL_LOGIT && p.mu.n <= 2) rc = launch_small_tsit5_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT1>(ctx, s, nt, kmax, lds);
-    else if (cl == CL_LOGIT) rc = launch_small_tsit5_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_LOGIT>(ctx, s, nt, kmax, lds);
-    else rc = launch_small_tsit5_k<T, PDEOPT_EQ_CAHN_HILLIARD, CL_POLY>(ctx, s, nt, kmax, lds);
-  } else if (cl == CL_LOGIT) {
-    rc = launch_small_tsit5_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_LOGIT>(ctx, s, nt, kmax, lds);
-  } else {
-    rc = launch_small_tsit5_k<T, PDEOPT_EQ_ALLEN_CAHN, CL_POLY>(ctx, s, nt, kmax, lds);
-  }
+  if (p.equation == PDEOPT_EQ_CAHN_HILLIARD)
+    rc = with_closure_class<CL_POLY, CL_LOGIT, CL_LOGIT1>(narrow_logit1(cl, p.mu), [&](auto c) {
+      return launch_small_tsit5_k<T, PDEOPT_EQ_CAHN_HILLIARD, decltype(c)::value>(ctx, s, nt, kmax, lds);
+    });
+  else  // (Allen-Cahn has no CL_LOGIT1 kernels)
+    rc = with_closure_class<CL_POLY, CL_LOGIT>(cl, [&](auto c) {
+      return launch_small_tsit5_k<T, PDEOPT_EQ_ALLEN_CAHN, decltype(c)::value>(ctx, s, nt, kmax, lds);
+    });
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(stats_host, s.stats, (size_t)batch * sizeof(pdeopt_tsit5_stats), hipMemcpyDeviceToHost, ctx->stream));
   if (n_save) PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(save_host, s.save_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -376,24 +376,17 @@ int launch_tiled_modes(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) 
 
 template <typename T, int EQ>
 int launch_tiled_cl(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
-  switch (classify_closures(ctx->prob.mu, ctx->prob.mob)) {
-    case CL_POLY:
-      return launch_tiled_modes<T, EQ, CL_POLY>(ctx, w, s);
-    case CL_LOGIT:
-      return launch_tiled_modes<T, EQ, CL_LOGIT>(ctx, w, s);
-    default:
-      return launch_tiled_modes<T, EQ, CL_GENERIC>(ctx, w, s);
-  }
+  return with_closure_class<CL_GENERIC, CL_POLY, CL_LOGIT>(classify_closures(ctx->prob.mu, ctx->prob.mob), [&](auto c) {
+    return launch_tiled_modes<T, EQ, decltype(c)::value>(ctx, w, s);
+  });
 }
 
 template <typename T>
 int launch_tiled(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   const int cl = classify_closures(ctx->prob.mu, ctx->prob.mob);
-  static const char* kClName[] = {"generic", "poly", "logit"};
   char name[96];
-  snprintf(name, sizeof(name), "stage_tiled<%s,%s,%s,rows%d>", sizeof(T) == 4 ? "f32" : "f64",
-           ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD ? "CH" : "AC", kClName[cl],
-           8 * tiled_rpt(ctx));
+  snprintf(name, sizeof(name), "stage_tiled<%s,%s,%s,rows%d>", dtype_name<T>(),
+           ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD ? "CH" : "AC", closure_class_name(cl), 8 * tiled_rpt(ctx));
   ctx->last_kernel = name;
   if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD)
     return launch_tiled_cl<T, PDEOPT_EQ_CAHN_HILLIARD>(ctx, w, s);

@@ -841,16 +841,16 @@ bool imex_fused_supported(const pdeopt_ctx* ctx) {
 }
 
 int advance_imex_fused(pdeopt_ctx* ctx, double dt, int64_t n) {
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_fused_t<float>(ctx, dt, n) : imex_fused_t<double>(ctx, dt, n);
+  return with_dtype(ctx, [&](auto t) { return imex_fused_t<decltype(t)>(ctx, dt, n); });
 }
 
 int imex_fused_prepare(pdeopt_ctx* ctx, double dt) {
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_prepare_t<float>(ctx, dt) : imex_prepare_t<double>(ctx, dt);
+  return with_dtype(ctx, [&](auto t) { return imex_prepare_t<decltype(t)>(ctx, dt); });
 }
 
 int imex_fused_passes(pdeopt_ctx* ctx, const Window& w, double dt) {
   StrangFused& sf = *ctx->strang_fused;
-  return ctx->prob.dtype == PDEOPT_F32 ? imex_passes_t<float>(ctx, w, sf, dt) : imex_passes_t<double>(ctx, w, sf, dt);
+  return with_dtype(ctx, [&](auto t) { return imex_passes_t<decltype(t)>(ctx, w, sf, dt); });
 }
 
 bool strang_fused_supported(const pdeopt_ctx* ctx) {
@@ -863,7 +863,7 @@ bool strang_fused_supported(const pdeopt_ctx* ctx) {
 }
 
 int advance_strang_fused(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
-  return ctx->prob.dtype == PDEOPT_F32 ? strang_fused_t<float>(ctx, t0, dt, n) : strang_fused_t<double>(ctx, t0, dt, n);
+  return with_dtype(ctx, [&](auto t) { return strang_fused_t<decltype(t)>(ctx, t0, dt, n); });
 }
 
 void strang_fused_invalidate(pdeopt_ctx* ctx) {
