@@ -502,6 +502,30 @@ int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp,
  * Gauss-Newton sums), accumulated in fp64 by the same fixed-order reduction: repeated calls give identical bits. */
 int pdeopt_sens_contract(pdeopt_ctx* ctx, int frame, double theta, int interp, double* out);
 
+/* ---- Cahn-Hilliard with mu_h given as a field, and its discrete adjoint (train(method="mse") with a neural-network
+ * mu: docs/notebooks/optimization_neural_network.ipynb, pde_opt/numerics/functions/cnn.py; the reference differentiates
+ * the solve in reverse mode with diffrax's RecursiveCheckpointAdjoint, pde_model.py:429-460)
+ * The network runs in the caller's framework on the ctx's device and stream (pdeopt_ctx_create_on_stream) and hands
+ * mu_h = N(u) over as a device field; the library never sees it.  Periodic 2-D Cahn-Hilliard, derivs "fd", no halo
+ * layout, a mobility of the in-kernel family; the problem's own mu closure is not read.  Every *_dev argument is a
+ * device field [batch][nx][ny] in the problem dtype, aligned to it; all work is ordered on the ctx's stream and
+ * nothing below synchronises the host (IMEX: but for the multiplier upload when dt or A changes). */
+/* out_dev = f(Y, mu_h) = div( avg(D(Y)) grad( mu_h - kappa lap5(Y) ) ), the slope of the state (cahn_hilliard.py:89-109
+ * with mu(c) replaced by the field) */
+int pdeopt_fieldmu_rhs(pdeopt_ctx* ctx, const void* mu_dev, void* out_dev);
+/* one substep Y += dt S f(Y, mu_h): S = I for PDEOPT_INT_EULER, S = Re ifft(fft(.) / (1 + A dt fourier_symbol)) for
+ * PDEOPT_INT_IMEX (solvers.py:56-70; rocFFT's real transforms, one implicit operator shared by the batch) */
+int pdeopt_fieldmu_step(pdeopt_ctx* ctx, int integrator, double dt, const void* mu_dev);
+/* the adjoint of that substep at the state u_dev it started from, with mu_dev = N(u_dev): lam_dev holds the cotangent
+ * of the new state on entry.  With lambda_f = dt S lam (S is real-symmetric for a real even fourier_symbol, as
+ * Cahn-Hilliard's kappa k^4: the same transforms serve) and m = mu_h - kappa lap5(u):
+ *   gmu_dev  = div( avg(D(u)) grad(lambda_f) )                              the cotangent of mu_h
+ *   lam_dev += -kappa lap5(gmu) + D'(u) g_D,   g_D = -1/2 sum over the 4 faces of grad(lambda_f) grad(m)
+ * The caller then adds the network's vector-Jacobian product N'(u)^T gmu to lam_dev and to its parameters' gradient.
+ * lam_dev and gmu_dev must not overlap each other or the inputs (refused).  Gather form, no atomics: identical bits on a repeat. */
+int pdeopt_fieldmu_adjoint_step(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, const void* mu_dev,
+                                void* lam_dev, void* gmu_dev);
+
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);
 int pdeopt_timer_start(pdeopt_ctx* ctx);           /* hipEventRecord on the ctx stream */

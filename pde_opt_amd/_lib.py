@@ -191,6 +191,9 @@ _SIGNATURES = {
     "pdeopt_sens_set_data": (C.c_int, [_VP, C.c_int, _VP]),
     "pdeopt_sens_accumulate": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
     "pdeopt_sens_contract": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
+    "pdeopt_fieldmu_rhs": (C.c_int, [_VP, _VP, _VP]),
+    "pdeopt_fieldmu_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP]),
+    "pdeopt_fieldmu_adjoint_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

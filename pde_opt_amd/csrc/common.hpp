@@ -382,6 +382,10 @@ int imex_fused_passes(pdeopt_ctx* ctx, const Window& w, double dt);
 // half-spectrum multiplier of step dt, then y += dt L^-1 TA over the whole batch (r2c, multiply, c2r, axpy)
 int imex_rocfft_prepare(pdeopt_ctx* ctx, double dt);
 int imex_rocfft_solve(pdeopt_ctx* ctx, double dt);
+// the two halves of imex_rocfft_solve for callers that need them apart (fieldmu.hip): TA = L^-1 TA (r2c, multiply,
+// c2r; the multiplier of the last imex_rocfft_prepare), and y += dt TA
+int imex_rocfft_apply(pdeopt_ctx* ctx);
+int axpy_state(pdeopt_ctx* ctx, double dt);
 void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);

@@ -354,22 +354,33 @@ int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
   return PDEOPT_OK;
 }
 
-// y += dt Re ifftn(fftn(TA) m) over the whole batch: r2c, multiply, c2r, axpy
+// TA = Re ifftn(fftn(TA) m) over the whole batch: r2c, multiply, c2r
 template <typename T>
-int imex_rocfft_solve_t(pdeopt_ctx* ctx, double dt) {
+int imex_rocfft_apply_t(pdeopt_ctx* ctx) {
   Spectral& sp = *ctx->spectral;
-  const pdeopt_problem& p = ctx->prob;
-  const int nzz = p.nz > 1 ? p.nz : 1;
-  const int64_t total = (int64_t)p.nx * p.ny * nzz * p.batch;
   const int64_t hc = sp.half_cells;
   int rc;
   if ((rc = real_fft_exec(ctx, true, ctx->TA, sp.hbuf))) return rc;
-  hipLaunchKernelGGL((spectral_mul_kernel<T, false>), dim3(grid_for(hc), p.batch), dim3(256), 0,
+  hipLaunchKernelGGL((spectral_mul_kernel<T, false>), dim3(grid_for(hc), ctx->prob.batch), dim3(256), 0,
                      ctx->stream, (C2<T>*)sp.hbuf, (const C2<T>*)sp.hmult, nullptr, hc);
-  if ((rc = real_fft_exec(ctx, false, sp.hbuf, ctx->TA))) return rc;
+  return real_fft_exec(ctx, false, sp.hbuf, ctx->TA);
+}
+
+// y += dt TA over the whole batch
+template <typename T>
+int axpy_state_t(pdeopt_ctx* ctx, double dt) {
+  const pdeopt_problem& p = ctx->prob;
+  const int64_t total = (int64_t)p.nx * p.ny * (p.nz > 1 ? p.nz : 1) * p.batch;
   hipLaunchKernelGGL(axpy_real_kernel<T>, dim3(grid_for(total)), dim3(256), 0, ctx->stream,
                      (T*)ctx->Y, (const T*)ctx->TA, (T)dt, total);
   return PDEOPT_OK;
+}
+
+// y += dt Re ifftn(fftn(TA) m) over the whole batch: r2c, multiply, c2r, axpy
+template <typename T>
+int imex_rocfft_solve_t(pdeopt_ctx* ctx, double dt) {
+  const int rc = imex_rocfft_apply_t<T>(ctx);
+  return rc ? rc : axpy_state_t<T>(ctx, dt);
 }
 
 // IMEX on real <-> hermitian transforms.  The reference runs full complex transforms on the real
@@ -717,6 +728,14 @@ int imex_rocfft_prepare(pdeopt_ctx* ctx, double dt) {
 
 int imex_rocfft_solve(pdeopt_ctx* ctx, double dt) {
   return with_dtype(ctx, [&](auto t) { return imex_rocfft_solve_t<decltype(t)>(ctx, dt); });
+}
+
+int imex_rocfft_apply(pdeopt_ctx* ctx) {
+  return with_dtype(ctx, [&](auto t) { return imex_rocfft_apply_t<decltype(t)>(ctx); });
+}
+
+int axpy_state(pdeopt_ctx* ctx, double dt) {
+  return with_dtype(ctx, [&](auto t) { return axpy_state_t<decltype(t)>(ctx, dt); });
 }
 
 int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {

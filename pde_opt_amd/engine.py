@@ -408,6 +408,20 @@ class HipEngine:
                                                    out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # -- Cahn-Hilliard with mu_h as a device field (pde_opt_amd.fieldmu; arguments are device pointers of fields
+    #    (batch, nx, ny) in the engine's dtype, e.g. ``tensor.data_ptr()``; nothing here synchronises) --------------
+    def fieldmu_rhs(self, mu_ptr: int, out_ptr: int):
+        self._check(self._lib.pdeopt_fieldmu_rhs(self._h, C.c_void_p(mu_ptr), C.c_void_p(out_ptr)))
+
+    def fieldmu_step(self, integrator: int, dt: float, mu_ptr: int):
+        """one substep ``Y += dt S f(Y, mu_h)`` of the state"""
+        self._check(self._lib.pdeopt_fieldmu_step(self._h, int(integrator), float(dt), C.c_void_p(mu_ptr)))
+
+    def fieldmu_adjoint_step(self, integrator: int, dt: float, u_ptr: int, mu_ptr: int, lam_ptr: int, gmu_ptr: int):
+        """the adjoint of that substep at fixed ``mu_h``: ``lam += g_u`` in place, ``g_mu`` written to ``gmu_ptr``"""
+        self._check(self._lib.pdeopt_fieldmu_adjoint_step(self._h, int(integrator), float(dt), C.c_void_p(u_ptr),
+                                                          C.c_void_p(mu_ptr), C.c_void_p(lam_ptr), C.c_void_p(gmu_ptr)))
+
     def reduce(self, op: int) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.float64)
         self._check(self._lib.pdeopt_reduce(self._h, int(op), out.ctypes.data_as(C.c_void_p)))

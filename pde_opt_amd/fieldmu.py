@@ -1,0 +1,324 @@
+"""Cahn-Hilliard with a neural-network chemical potential: the forward solve and the reverse-mode (discrete adjoint)
+gradient of ``mean(r^2)`` over the network's parameters (the reference's ``train(method="mse")`` with a periodic CNN as
+``mu``: docs/notebooks/optimization_neural_network.ipynb, notebooks/optimize_nn_script.py; it differentiates the solve
+with diffrax's ``RecursiveCheckpointAdjoint``, pde_model.py:429-460).
+
+The split: the network ``N`` and its vector-Jacobian products belong to torch on the device; the stencil, its transpose
+and the IMEX operator are HIP kernels (csrc/fieldmu.hip).  Per substep torch evaluates ``mu_h = N(u)`` and the library
+advances ``u += dt S f(u, mu_h)`` (``pdeopt_fieldmu_step``).  Going back, the library turns the cotangent ``lam`` of the
+new state into ``lam += g_u`` and the cotangent ``g_mu`` of ``mu_h`` (``pdeopt_fieldmu_adjoint_step``), and
+``mu_h.backward(g_mu)`` adds the network's share to ``lam`` and to the parameters' ``.grad``.  The cost does not depend
+on the number of parameters.  The engine and the solver's torch work share one stream, so nothing synchronises inside
+the substep loop; the caller's own stream is ordered against it on entry and exit of every call (``FieldMuSolver``).
+
+Substep and save-point schedule: ``fit.walk_save_points``, the one of ``integrate.diffeqsolve`` and of the forward-mode
+sensitivities (constant steps, a clipped last step, save points inside a step interpolated linearly).  The backward
+sweep needs the state at the start of every substep: the forward pass keeps one state per chunk of substeps, and each
+chunk is run again and held before its sweep.  A chunk holds at most ``PDEOPT_FIELDMU_CHUNK_BYTES`` (default 1 GiB;
+``FieldMuSolver.chunk_bytes`` overrides it), so a long solve costs one extra forward pass instead of unbounded memory.
+
+Covered: ``CahnHilliard2DPeriodic`` with ``derivs="fd"``, ``SemiImplicitFourierSpectral`` or ``Euler`` with
+``ConstantStepSize``, fp32 and fp64, ``D`` a closure of the in-kernel family, ``D`` and ``kappa`` fixed.
+
+torch is imported when a solver is built, not with the package.
+"""
+
+from __future__ import annotations
+
+import contextlib
+import os
+
+import numpy as np
+
+from . import _lib as L
+from .fit import walk_save_points
+from .numerics.closures import is_torch_module as is_module  # noqa: F401  (the detection, for callers of this module)
+from .numerics.equations.phase_field import FIELD_MU_SUPPORT
+
+CHUNK_BYTES_ENV = "PDEOPT_FIELDMU_CHUNK_BYTES"
+DEFAULT_CHUNK_BYTES = 1 << 30
+
+
+# ---- parameters as one flat vector --------------------------------------------------------------------------------------
+
+
+def flatten_params(module) -> np.ndarray:
+    """the module's parameters, in ``module.parameters()`` order, as one fp64 vector"""
+    parts = [p.detach().double().reshape(-1).cpu().numpy() for p in module.parameters()]
+    return np.concatenate(parts) if parts else np.zeros(0)
+
+
+def flatten_grads(module) -> np.ndarray:
+    """the parameters' ``.grad`` in the same order (zeros where a parameter has none)"""
+    parts = [(p.grad if p.grad is not None else p.new_zeros(p.shape)).detach().double().reshape(-1).cpu().numpy()
+             for p in module.parameters()]
+    return np.concatenate(parts) if parts else np.zeros(0)
+
+
+def unflatten_params(module, p) -> None:
+    """write the flat vector back into the module's parameters (their dtype and device)"""
+    import torch
+
+    p = np.asarray(p, dtype=np.float64)
+    n = sum(q.numel() for q in module.parameters())
+    if p.shape != (n,):
+        raise ValueError(f"flat parameter vector of shape {p.shape}: the module has {n} parameters")
+    o = 0
+    with torch.no_grad():
+        for q in module.parameters():
+            q.copy_(torch.as_tensor(p[o:o + q.numel()]).reshape(q.shape))
+            o += q.numel()
+
+
+def add_flat_grad(module, g) -> None:
+    """add the flat vector ``g`` to the parameters' ``.grad``"""
+    import torch
+
+    o = 0
+    for q in module.parameters():
+        part = torch.as_tensor(np.asarray(g[o:o + q.numel()], dtype=np.float64)).reshape(q.shape).to(device=q.device, dtype=q.dtype)
+        q.grad = part if q.grad is None else q.grad + part
+        o += q.numel()
+
+
+def weight_vector(module, w) -> np.ndarray:
+    """regularisation weights of the flat vector: ``w`` is None (zeros), a number, a flat array, or a module of the same
+    structure whose parameters are the weights"""
+    n = sum(q.numel() for q in module.parameters())
+    if w is None:
+        return np.zeros(n)
+    w = flatten_params(w) if is_module(w) else np.asarray(w, dtype=np.float64)
+    return np.broadcast_to(w, (n,)).copy()
+
+
+# ---- schedule ---------------------------------------------------------------------------------------------------------
+
+
+def schedule(ts, dt0):
+    """``(steps, saves)``: the step sizes of the substeps in order, and per save point ``(i, theta)``: the save is the
+    state after ``i`` substeps (``theta`` None), or ``y[i - 1] + theta (y[i] - y[i - 1])`` inside substep ``i``"""
+    ts = np.asarray(ts, dtype=np.float64)
+    steps, saves = [], []
+    walk_save_points(float(ts[0]), float(ts[-1]), float(dt0), ts,
+                     lambda dt, n, t: steps.extend([float(dt)] * int(n)), lambda: None,
+                     lambda q, theta: saves.append((len(steps), theta)))
+    return steps, saves
+
+
+def split_save_cotangent(g, theta):
+    """cotangents ``(of y[i - 1], of y[i])`` of a save ``(1 - theta) y[i - 1] + theta y[i]`` with cotangent ``g``; a save on
+    a step edge (``theta`` None) belongs to ``y[i]`` alone"""
+    if theta is None:
+        return None, g
+    return (1.0 - theta) * g, theta * g
+
+
+def chunk_length(n_steps: int, state_bytes: int, cap_bytes: int) -> int:
+    """substeps per chunk: as many start states as ``cap_bytes`` holds, at least one"""
+    return max(1, min(max(1, n_steps), int(cap_bytes) // max(1, int(state_bytes))))
+
+
+# ---- the solver ---------------------------------------------------------------------------------------------------------
+
+
+def _reject(equation, solver, controller=None):
+    from .numerics.solvers import ConstantStepSize
+
+    if getattr(equation, "_mu_module", None) is None:
+        raise NotImplementedError("a torch.nn.Module as mu is supported for " + FIELD_MU_SUPPORT)
+    if equation.derivs != "fd":
+        raise NotImplementedError(f'a torch.nn.Module as mu needs derivs="fd", not {equation.derivs!r}: ' + FIELD_MU_SUPPORT)
+    if solver.integrator not in (L.INT_IMEX, L.INT_EULER):
+        raise NotImplementedError(f"a torch.nn.Module as mu does not run with {type(solver).__name__}: " + FIELD_MU_SUPPORT)
+    if controller is not None and not isinstance(controller, ConstantStepSize):
+        raise NotImplementedError("a torch.nn.Module as mu needs ConstantStepSize: " + FIELD_MU_SUPPORT)
+    if solver.integrator == L.INT_IMEX and np.any(np.imag(np.asarray(solver.fourier_symbol)) != 0.0):
+        raise NotImplementedError("the adjoint of the IMEX step reuses its operator, which needs a real fourier_symbol")
+
+
+class FieldMuSolver:
+    """One engine for solves whose ``mu`` is a ``torch.nn.Module``, on one torch stream.
+
+    Stream rule.  The engine is bound to ``self.stream`` for its lifetime: torch's current stream at construction, or a
+    stream of the solver's own when that is the legacy default stream (it has no handle the library could borrow).  All
+    of the solver's torch work and every library launch of a call run on ``self.stream``, so nothing synchronises inside
+    the substep loop.  Every call reads the caller's current stream anew: on entry ``self.stream`` waits for it (what
+    the caller has enqueued -- an optimiser step on the parameters, a module it has just modified -- is finished before
+    the solver reads it), on exit it waits for ``self.stream`` (the ``.grad`` the solver wrote is ready for what the
+    caller enqueues next).  Both are device-side waits (``Stream.wait_stream``), not host synchronisation."""
+
+    def __init__(self, device: int = 0):
+        import torch
+
+        from .engine import HipEngine
+
+        self.torch = torch
+        self.device = torch.device("cuda", int(device))
+        cur = torch.cuda.current_stream(self.device)
+        self.stream = cur if cur.cuda_stream else torch.cuda.Stream(self.device)
+        self.engine = HipEngine(int(device), stream=self.stream.cuda_stream)
+        self.chunk_bytes = None  # None: PDEOPT_FIELDMU_CHUNK_BYTES, else 1 GiB
+        self.last_chunks = 0     # chunks of the last backward sweep
+
+    @contextlib.contextmanager
+    def _ordered(self):
+        """run the body on ``self.stream``, ordered after and before the caller's current stream (the stream rule)"""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.device)
+        if caller != self.stream:
+            self.stream.wait_stream(caller)
+        try:
+            with torch.cuda.stream(self.stream):
+                yield
+        finally:
+            if caller != self.stream:
+                caller.wait_stream(self.stream)
+
+    def _cap(self) -> int:
+        if self.chunk_bytes is not None:
+            return int(self.chunk_bytes)
+        return int(os.environ.get(CHUNK_BYTES_ENV, DEFAULT_CHUNK_BYTES))
+
+    # -- set-up ---------------------------------------------------------------------------------------------------------
+    def _prepare(self, equation, solver, y0s, t0, t1):
+        """configure the engine, upload the state; returns ``(Y, mu_of)``: the state as a tensor ``(B, nx, ny)`` over the
+        engine's own buffer, and ``mu_of(u) -> mu_h`` ``(B, nx, ny)``, contiguous"""
+        torch = self.torch
+        eng = self.engine
+        eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem(field_mu=True))
+        equation._engine_upload(eng, t0, t1)
+        solver.configure_engine(eng, equation)
+        eng.set_state(y0s)
+        Y = eng.state_device_array().torch()
+        module = equation._mu_module
+        for name, p in module.named_parameters():
+            if p.dtype != Y.dtype or p.device != Y.device:
+                raise ValueError(f"mu's parameter {name} is {p.dtype} on {p.device}; the solve runs in {Y.dtype} on {Y.device}")
+        call = as_field_call(module, Y)
+        return Y, lambda u: call(u).reshape(u.shape).contiguous()
+
+    # -- forward --------------------------------------------------------------------------------------------------------
+    def solve(self, equation, solver, y0s, ts, dt0, controller=None) -> np.ndarray:
+        """the saved states ``(len(ts), B, nx, ny)`` in the dtype of ``y0s``"""
+        _reject(equation, solver, controller)
+        torch = self.torch
+        steps, saves = schedule(ts, dt0)
+        need_prev = {i - 1 for i, theta in saves if theta is not None}
+        by_index = {}
+        for q, (i, theta) in enumerate(saves):
+            by_index.setdefault(i, []).append((q, theta))
+        out = [None] * len(saves)
+        with self._ordered(), torch.no_grad():
+            Y, mu_of = self._prepare(equation, solver, y0s, float(ts[0]), float(ts[-1]))
+            prev = None
+            for i in range(len(steps) + 1):
+                for q, theta in by_index.get(i, ()):
+                    out[q] = Y.clone() if theta is None else prev + theta * (Y - prev)
+                if i == len(steps):
+                    break
+                if i in need_prev:
+                    prev = Y.clone()
+                self.engine.fieldmu_step(solver.integrator, steps[i], mu_of(Y).data_ptr())
+            res = torch.stack(out).cpu().numpy()
+        return res
+
+    # -- reverse ----------------------------------------------------------------------------------------------------------
+    def mse_backward(self, equation, solver, y0s, values, ts, dt0) -> float:
+        """``mean(r^2)`` of ``r = values - solve(...)[1:]`` (``values`` ``(B, T - 1, nx, ny)``), summed in fp64; the
+        gradient is ADDED to ``.grad`` of the module's parameters"""
+        _reject(equation, solver)
+        torch = self.torch
+        integ = solver.integrator
+        steps, saves = schedule(ts, dt0)
+        N = len(steps)
+        need_prev = {i - 1 for i, theta in saves if theta is not None}
+        by_index = {}
+        for q, (i, theta) in enumerate(saves):
+            if q >= 1:  # ts[0] is the initial state: data
+                by_index.setdefault(i, []).append((q, theta))
+        with self._ordered(), torch.no_grad(), _deterministic(torch):
+            Y, mu_of = self._prepare(equation, solver, y0s, float(ts[0]), float(ts[-1]))
+            vals = torch.as_tensor(np.ascontiguousarray(np.swapaxes(values, 0, 1)), dtype=Y.dtype).to(Y.device)  # (T - 1, B, ...)
+            M = vals.numel()
+            chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
+            starts, cot = {}, {}
+            ssr = torch.zeros((), dtype=torch.float64, device=Y.device)
+            prev = None
+            for i in range(N + 1):
+                for q, theta in by_index.get(i, ()):
+                    pred = Y if theta is None else prev + theta * (Y - prev)
+                    r = vals[q - 1] - pred
+                    ssr += (r.double() ** 2).sum()
+                    g_prev, g_cur = split_save_cotangent(r * (-2.0 / M), theta)  # d mean(r^2) / d pred
+                    for k, g in ((i - 1, g_prev), (i, g_cur)):
+                        if g is not None:
+                            cot[k] = g if k not in cot else cot[k] + g
+                if i == N:
+                    break
+                if i % chunk == 0:
+                    starts[i] = Y.clone()
+                if i in need_prev:
+                    prev = Y.clone()
+                self.engine.fieldmu_step(integ, steps[i], mu_of(Y).data_ptr())
+            lam = cot[N].clone() if N in cot else torch.zeros_like(Y)
+            gmu = torch.empty_like(Y)
+            self.last_chunks = len(starts)
+            for s0 in sorted(starts, reverse=True):
+                s1 = min(N, s0 + chunk)
+                Y.copy_(starts.pop(s0))
+                held = []
+                for s in range(s0, s1):
+                    held.append(Y.clone())
+                    if s + 1 < s1:
+                        self.engine.fieldmu_step(integ, steps[s], mu_of(Y).data_ptr())
+                for s in range(s1 - 1, s0 - 1, -1):
+                    u = held.pop().requires_grad_(True)
+                    with torch.enable_grad():
+                        mu = mu_of(u)
+                    self.engine.fieldmu_adjoint_step(integ, steps[s], u.data_ptr(), mu.data_ptr(), lam.data_ptr(), gmu.data_ptr())
+                    mu.backward(gmu)
+                    lam += u.grad
+                    if s in cot and s > 0:
+                        lam += cot[s]
+            loss = float(ssr.item()) / M
+        return loss
+
+
+class _deterministic:
+    """torch's deterministic convolution algorithms for the duration (identical bits on a repeat), then as before"""
+
+    def __init__(self, torch):
+        self.b = torch.backends.cudnn
+
+    def __enter__(self):
+        self.saved = (self.b.deterministic, self.b.benchmark)
+        self.b.deterministic, self.b.benchmark = True, False
+
+    def __exit__(self, *exc):
+        self.b.deterministic, self.b.benchmark = self.saved
+
+
+def as_field_call(module, like):
+    """``call(u (B, nx, ny)) -> mu_h`` with ``B nx ny`` entries: the module applied to ``(B, 1, nx, ny)``, or -- a module
+    written for one field ``(nx, ny)`` -- to every trajectory in turn.  Decided by one trial call on a constant field shaped like ``like``."""
+    import torch
+
+    B, nx, ny = like.shape
+    probe = torch.full((B, 1, nx, ny), 0.5, dtype=like.dtype, device=like.device)
+    want = "mu must map a (B, 1, nx, ny) tensor (or one (nx, ny) field) to the same shape"
+    with torch.no_grad():
+        try:
+            batched = tuple(module(probe).shape)
+        except Exception as e:  # a module written for one field may fail in any way on four axes: kept for the message
+            batched = e
+        if batched == (B, 1, nx, ny):
+            return lambda u: module(u[:, None])
+        first = (f"the batched call raised {type(batched).__name__}: {batched}" if isinstance(batched, Exception)
+                 else f"the batched call returned shape {batched}")
+        try:
+            single = tuple(module(probe[0, 0]).shape)
+        except Exception as e:
+            raise ValueError(f"{want}; {first}; the call on one field raised {type(e).__name__}: {e}") from e
+    if single != (nx, ny):
+        raise ValueError(f"{want}; {first}; the call on one field returned shape {single}")
+    return lambda u: torch.stack([module(u[b]) for b in range(u.shape[0])])

@@ -26,10 +26,15 @@ import numpy as np
 
 from . import _lib as L
 from .integrate import constant_step_plan
-from .numerics.closures import UnsupportedClosureError
+from .numerics.closures import UnsupportedClosureError, is_torch_module
 from .numerics.functions.legendre import ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials
 
 RTOL = ATOL = 1e-8  # optimistix tolerances of the reference's train (pde_model.py:398-401, 428-431)
+
+# train(method="mse") with a torch.nn.Module as mu runs BFGS over the module's flattened parameters: the inverse-Hessian
+# estimate is dense (8 n^2 bytes, O(n^2) work per step).  Above this many parameters train refuses and points to
+# PDEModel.mse_backward, which fills .grad for any torch.optim optimiser.
+MAX_DENSE_BFGS_PARAMS = 4096
 
 # closure classes whose coefficient arrays are trainable, and the constructor argument that holds their role
 # ("D" is Cahn-Hilliard's mobility, "R" Allen-Cahn's rate: the engine's second closure either way)
@@ -117,9 +122,14 @@ def _is_allen_cahn(equation_type) -> bool:
 
 
 def _leaves(obj) -> list:
-    """coefficient arrays of a closure, the array / number itself, or nothing (None, callables)"""
+    """coefficient arrays of a closure, the flattened parameters of a torch.nn.Module, the array / number itself, or
+    nothing (None, callables)"""
     if obj is None:
         return []
+    if is_torch_module(obj):
+        from .fieldmu import flatten_params
+
+        return [flatten_params(obj)]
     if isinstance(obj, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
         return [np.asarray(obj.expansion.params, dtype=np.float64)]
     if isinstance(obj, (int, float, np.ndarray, np.number)):
@@ -520,6 +530,12 @@ def reject_unsupported(model):
 
 
 def check_equation(equation):
+    if getattr(equation, "_mu_module", None) is not None:
+        from .numerics.equations.phase_field import FIELD_MU_SUPPORT
+
+        raise NotImplementedError("forward-mode sensitivities (train of closure coefficients, optimize) do not run with a "
+                                  "torch.nn.Module as mu: the module itself is trained, by train(opt_parameters={'mu': module}, "
+                                  "method='mse') or mse_backward, on " + FIELD_MU_SUPPORT)
     if getattr(equation, "derivs", "fd") != "fd":
         raise NotImplementedError('train sensitivities support derivs="fd" only (the tangent kernel differentiates the '
                                   'finite-difference right-hand side)')

@@ -29,6 +29,16 @@ class UnsupportedClosureError(ValueError):
     pass
 
 
+def is_torch_module(obj) -> bool:
+    """is ``obj`` a ``torch.nn.Module``?  Asked before a closure is traced (a network is not pointwise: as ``mu`` of
+    CahnHilliard2DPeriodic it takes the field path, ``pde_opt_amd.fieldmu``).  Never imports torch: an object can only be
+    a Module if its creator has imported torch already."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(obj, torch.nn.Module)
+
+
 @dataclasses.dataclass(frozen=True)
 class ClosureDesc:
     """A member of the in-kernel closure family.  Callable on numpy arrays (host utility only)."""

@@ -18,7 +18,7 @@ from typing import Any
 import numpy as np
 
 from ... import _lib as L
-from ..closures import as_closure
+from ..closures import UnsupportedClosureError, as_closure, is_torch_module
 from ..domains import Domain
 from .base_eq import BaseEquation
 
@@ -86,6 +86,11 @@ def _install_spectral(cls):
     return cls
 
 
+# what a torch.nn.Module as mu runs on (pde_opt_amd.fieldmu)
+FIELD_MU_SUPPORT = ('CahnHilliard2DPeriodic with derivs="fd", SemiImplicitFourierSpectral or Euler with ConstantStepSize, '
+                    'fp32 / fp64, D and kappa fixed')
+
+
 def _select_rhs(eq):
     if eq.derivs == "fd":
         eq.rhs = eq.rhs_fd
@@ -125,11 +130,19 @@ class CahnHilliard2DPeriodic(BaseEquation):
     def __post_init__(self):
         if len(self.domain.points) != 2:
             raise ValueError("CahnHilliard2DPeriodic needs a 2-D domain")
-        self._mu_desc = as_closure(self.mu)
+        if is_torch_module(self.D):
+            raise UnsupportedClosureError("a torch.nn.Module is supported as mu only; D stays a closure of the in-kernel family")
+        # a network as mu is no closure: the kernels take the field it returns (pde_opt_amd.fieldmu)
+        self._mu_module = self.mu if is_torch_module(self.mu) else None
+        self._mu_desc = None if self._mu_module is not None else as_closure(self.mu)
         self._mob_desc = as_closure(self.D)
         _select_rhs(self)
 
-    def _engine_problem(self):
+    def _engine_problem(self, field_mu: bool = False):
+        """``field_mu``: the caller feeds mu_h to the kernels as a field (the problem's own mu closure is not read)"""
+        if self._mu_module is not None and not field_mu:
+            raise UnsupportedClosureError("mu is a torch.nn.Module: it runs through PDEModel.solve / residuals / mse / "
+                                          "mse_backward / train(method='mse') (" + FIELD_MU_SUPPORT + "), not through rhs or diffeqsolve")
         nx, ny = self.domain.points
         hx, hy = self.domain.dx
         return dict(equation=L.EQ_CAHN_HILLIARD, nx=nx, ny=ny, hx=hx, hy=hy, kappa=float(self.kappa),

@@ -1,4 +1,5 @@
-"""Function representations used as closures (Legendre family; CNN/Mixer are out of scope)."""
+"""Function representations used as closures: the Legendre family, light spots; ``cnn.PeriodicCNN`` (a torch module, imported on
+demand: ``from pde_opt_amd.numerics.functions.cnn import PeriodicCNN``) as ``mu`` of CahnHilliard2DPeriodic.  Mixers are out of scope."""
 
 from .lights import GaussianSpot, GaussianSpots
 from .legendre import (

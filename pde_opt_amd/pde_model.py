@@ -9,6 +9,9 @@ ignored: forward solves need no adjoint.
 trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
 trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D (``mu`` / ``D``; IMEX or
 Euler) and periodic 2-D Allen-Cahn (``mu`` / ``R``; Euler or RK4), with FD derivatives.
+A ``torch.nn.Module`` as ``mu`` of CahnHilliard2DPeriodic (the reference's periodic CNN, optimization_neural_network.ipynb)
+takes the field path of ``pde_opt_amd.fieldmu``: ``solve`` / ``residuals`` / ``mse`` run it forward, ``mse_backward``
+fills the parameters' ``.grad`` by a discrete adjoint on the GPU, ``train(method="mse")`` drives BFGS with it.
 ``optimize`` (pde_model.py:462-551) minimises a scalar objective of the saved solution over the same coefficients with
 BFGS: the objective is a torch-differentiable callable or an object with ``value_and_grad(ys)``; its cotangent
 ``dJ/dys`` is contracted with the same tangents on the GPU (``pdeopt_sens_contract``).  Objectives in neither form, and
@@ -50,6 +53,8 @@ class PDEModel:
     ):
         equation = self.equation_type(domain=self.domain, **parameters)
         solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+        if getattr(equation, "_mu_module", None) is not None:  # a network as mu: torch evaluates it, the kernels take the field
+            return self._fieldmu_solve(equation, solver, y0, ts, dt0, stepsize_controller)
         if self._engine is None:
             self._engine = HipEngine(self.device)
         ts = np.asarray(ts, dtype=np.float64)
@@ -82,6 +87,89 @@ class PDEModel:
         r, reg = self.residuals(parameters, y0s__values, solver_parameters, ts, weights, lambda_reg, adjoint)
         return float(np.mean(np.asarray(r, dtype=np.float64) ** 2)) + reg
 
+    # -- a torch.nn.Module as mu (pde_opt_amd.fieldmu) -----------------------------------------------------------------
+    def fieldmu_solver(self):
+        """the solver of the module path (its ``chunk_bytes`` caps the states the backward sweep holds)"""
+        if getattr(self, "_fieldmu", None) is None:
+            from .fieldmu import FieldMuSolver
+
+            self._fieldmu = FieldMuSolver(self.device)
+        return self._fieldmu
+
+    def _fieldmu_solve(self, equation, solver, y0, ts, dt0, stepsize_controller):
+        y0 = np.asarray(y0)
+        if y0.dtype not in (np.float32, np.float64):
+            y0 = y0.astype(np.float64)
+        single = y0.ndim == 2
+        yb = y0[None] if single else y0
+        if yb.ndim != 3 or tuple(yb.shape[1:]) != tuple(self.domain.points):
+            raise ValueError(f"y0 shape {y0.shape} does not match domain points {self.domain.points}")
+        ys = self.fieldmu_solver().solve(equation, solver, yb, np.asarray(ts, dtype=np.float64), float(dt0), stepsize_controller)
+        return ys[:, 0] if single else ys
+
+    def mse_backward(self, parameters, y0s__values, solver_parameters, ts, weights, lambda_reg, dt0=0.000001) -> float:
+        """``mse(...)`` for a ``torch.nn.Module`` as ``parameters["mu"]``, and its gradient: ``.grad`` of the module's
+        parameters is set to the gradient of ``mean(r^2) + reg`` (a discrete adjoint of the solve on the GPU, see
+        ``pde_opt_amd.fieldmu``; the loss is summed in fp64).  The entry for ``torch.optim`` users:
+
+            opt.zero_grad(); loss = model.mse_backward(params, (y0s, values), sp, ts, weights, lam); opt.step()
+
+        ``weights["mu"]``: None, a number, a flat array or a module of the same structure (the weights of
+        ``lambda sum w p^2``).  Returns the loss as a float."""
+        from . import fieldmu
+
+        module = parameters.get("mu")
+        if not fieldmu.is_module(module):
+            raise NotImplementedError("mse_backward differentiates a solve whose mu is a torch.nn.Module (" + fieldmu.FIELD_MU_SUPPORT
+                                      + "); closure coefficients are fitted by train / optimize")
+        equation = self.equation_type(domain=self.domain, **parameters)
+        solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+        y0s, values = y0s__values
+        y0s = np.asarray(y0s)
+        if y0s.dtype not in (np.float32, np.float64):
+            y0s = y0s.astype(np.float64)
+        for q in module.parameters():
+            q.grad = None
+        loss = self.fieldmu_solver().mse_backward(equation, solver, y0s, np.asarray(values), np.asarray(ts, dtype=np.float64), float(dt0))
+        w = fieldmu.weight_vector(module, (weights or {}).get("mu"))
+        if lambda_reg and np.any(w != 0.0):
+            p = fieldmu.flatten_params(module)
+            loss += float(lambda_reg * np.sum(w * p * p))
+            fieldmu.add_flat_grad(module, 2.0 * float(lambda_reg) * w * p)
+        return loss
+
+    def _train_module(self, data, inds, opt_parameters, other_parameters, solver_parameters, weights, lambda_reg, method,
+                      max_steps):
+        """``train`` for a ``torch.nn.Module`` as ``opt_parameters["mu"]``: BFGS over its flattened parameters"""
+        from . import fieldmu
+
+        if method == "least_squares":
+            raise NotImplementedError("a torch.nn.Module as mu is trained with method='mse' (reverse mode gives the gradient of "
+                                      "the loss, not the Jacobian Levenberg-Marquardt needs)")
+        if set(opt_parameters) != {"mu"}:
+            raise ValueError("with a torch.nn.Module as mu, opt_parameters holds mu alone: " + fieldmu.FIELD_MU_SUPPORT)
+        module = opt_parameters["mu"]
+        p0 = fieldmu.flatten_params(module)
+        if len(p0) > fit.MAX_DENSE_BFGS_PARAMS:
+            raise ValueError(f"mu has {len(p0)} parameters: train's BFGS keeps a dense inverse Hessian and takes at most "
+                             f"{fit.MAX_DENSE_BFGS_PARAMS}; use PDEModel.mse_backward with a torch.optim optimiser")
+        y0s, values, ts = stack_training_data(data, inds)
+        params = {"mu": module, **other_parameters}
+
+        def value_and_grad(p):
+            fieldmu.unflatten_params(module, p)
+            f = self.mse_backward(params, (y0s, values), solver_parameters, ts, weights, lambda_reg)
+            return f, fieldmu.flatten_grads(module)
+
+        def value(p):
+            fieldmu.unflatten_params(module, p)
+            return self.mse(params, (y0s, values), solver_parameters, ts, weights or {}, lambda_reg)
+
+        p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
+        fieldmu.unflatten_params(module, p)
+        self.last_train_history = hist
+        return {"mu": module, **other_parameters}
+
     def _sens_engine(self):
         if getattr(self, "_sens_eng", None) is None:
             self._sens_eng = HipEngine(self.device)
@@ -95,10 +183,17 @@ class PDEModel:
         optimistix.LevenbergMarquardt with ForwardMode); ``"mse"``: BFGS on ``mean(r^2) + reg``.  ``data["ys"][i]``
         is a state of shape ``spatial``: ``(nx, ny)`` for CahnHilliard2DPeriodic and AllenCahn2DPeriodic,
         ``(nx, ny, nz)`` for CahnHilliard3DPeriodic.  Returns ``{**fitted, **other_parameters}``; each fitted closure is the class it
-        started as, with its ``prior_fn``."""
+        started as, with its ``prior_fn``.
+
+        ``opt_parameters = {"mu": torch.nn.Module}`` (CahnHilliard2DPeriodic, ``method="mse"``): BFGS over the module's
+        flattened parameters with the reverse-mode gradient of ``mse_backward``, for up to ``fit.MAX_DENSE_BFGS_PARAMS``
+        parameters; the returned dict holds the trained module (the one passed in, updated in place)."""
         fit.reject_unsupported(self)
         if method not in ("least_squares", "mse"):
             raise ValueError(f"method must be 'least_squares' or 'mse', got {method!r}")
+        if fit.is_torch_module(opt_parameters.get("mu")) and len(self.domain.points) == 2 and not fit._is_allen_cahn(self.equation_type):
+            return self._train_module(data, inds, opt_parameters, other_parameters, solver_parameters, weights, lambda_reg,
+                                      method, max_steps)
         pmap = fit.ParamMap.of(opt_parameters, self.equation_type)
         y0s, values, ts = stack_training_data(data, inds)
         equation0 = self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters})
