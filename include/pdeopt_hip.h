@@ -526,6 +526,20 @@ int pdeopt_fieldmu_step(pdeopt_ctx* ctx, int integrator, double dt, const void* 
 int pdeopt_fieldmu_adjoint_step(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, const void* mu_dev,
                                 void* lam_dev, void* gmu_dev);
 
+/* ---- the discrete adjoint of one Strang substep of the GPE whose control is a sum of Gaussian spots
+ * (pdeopt_set_gpe_spots): the reverse-mode gradient of a scalar objective of the solution over the spots' numbers (the
+ * reference's PDEModel.optimize, pde_model.py:462-551, differentiates the same solve with generic reverse-mode AD).
+ * psi0_dev: the state the substep (local time t0, size dt) STARTED from; lam_dev: the cotangent dJ/dRe + i dJ/dIm of
+ * the state it ended in, replaced by the cotangent of psi0 (both device fields [batch][nx][ny][2] in the problem dtype;
+ * a caller keeps the start states it needs through pdeopt_state_device_ptr + its own copies).  grad: [batch][n_spots][7]
+ * doubles in the order of pdeopt_light_spot, device OR host memory, ADDED into: every environment gets its own sums
+ * (the last entry is the derivative with respect to inv_two_w2).  Three transform round trips (rocFFT: every grid
+ * the forward step takes) and three passes over the field per call; reductions in a fixed order, no atomics: a repeat
+ * gives identical bits.  A device grad keeps the call asynchronous on the ctx's stream; a host grad synchronises.
+ * Refused (PDEOPT_EINVAL / PDEOPT_ESTATE): an equation other than the GPE, no spots set, a per-environment A_term, a
+ * potential registered through pdeopt_set_aux_time_fn, overlapping lam_dev / psi0_dev / grad. */
+int pdeopt_gpe_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* psi0_dev, void* lam_dev, double* grad);
+
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);
 int pdeopt_timer_start(pdeopt_ctx* ctx);           /* hipEventRecord on the ctx stream */

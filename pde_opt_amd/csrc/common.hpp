@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
+#include <complex>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -60,6 +61,22 @@ __device__ __forceinline__ T spots_value(const SpotArgs<T>& a, int env, T x, T y
   }
   return w;
 }
+// The sibling of spots_value for the adjoint of the Strang step (gpe_adjoint.hip): the four independent partial
+// derivatives of spot s of lights(t, x, y) at one cell,
+//   d[0] = d/d amp0 = G;  d[1] = d/d x0 = amp G dx 2c;  d[2] = d/d y0 = amp G dy 2c;  d[3] = d/d c = -amp G (dx^2 + dy^2)
+// (amp, dx, dy and G as spots_value forms them).  The rates' partials are t times those of amp0, x0, y0.
+template <typename T>
+__device__ __forceinline__ void spot_partials(const SpotArgs<T>& a, int env, int s, T x, T y, T* d) {
+  const LightSpot<T> q = a.table[(size_t)env * PDEOPT_MAX_SPOTS + s];
+  const T dx = x - (q.x0 + q.x_rate * a.t), dy = y - (q.y0 + q.y_rate * a.t);
+  const T r2 = dx * dx + dy * dy;
+  const T g = t_exp_neg<T>(r2 * q.c);
+  const T ag = (q.amp0 + q.amp_rate * a.t) * g;
+  d[0] = g;
+  d[1] = ag * dx * (T(2) * q.c);
+  d[2] = ag * dy * (T(2) * q.c);
+  d[3] = -ag * r2;
+}
 
 // structure of a closure (shared by the whole batch; only coefficient VALUES vary per env)
 struct ClosureSpec {
@@ -107,6 +124,7 @@ struct CommState;    // RCCL / in-process communicator + strip buffers of the de
 struct Spectral;     // rocFFT plans + work buffers (spectral.hip)
 struct StrangFused;  // LDS-FFT split-step state (strang_fused.hip)
 struct Sens;         // forward-mode sensitivity configuration + Gauss-Newton buffers (sens.hip)
+struct GpeAdjoint;   // work fields + multiplier of the Strang step's adjoint (gpe_adjoint.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -217,6 +235,7 @@ struct pdeopt_ctx {
   pdeopt::Spectral* spectral = nullptr;
   pdeopt::StrangFused* strang_fused = nullptr;
   pdeopt::Sens* sens = nullptr;
+  pdeopt::GpeAdjoint* gpe_adjoint = nullptr;
 };
 
 namespace pdeopt {
@@ -386,6 +405,13 @@ int imex_rocfft_solve(pdeopt_ctx* ctx, double dt);
 // c2r; the multiplier of the last imex_rocfft_prepare), and y += dt TA
 int imex_rocfft_apply(pdeopt_ctx* ctx);
 int axpy_state(pdeopt_ctx* ctx, double dt);
+// one unnormalised complex transform of a whole-batch field [batch][nx][ny], in place, on the ctx's stream (the C2C
+// plans of the library Strang path: any grid); host copy of a shared complex aux field
+int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf);
+int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<double>>& out);
+// gpe_adjoint.hip: its buffers live and die with the spectral state (spectral_destroy / spectral_invalidate)
+void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
+void gpe_adjoint_destroy(pdeopt_ctx* ctx);
 void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);

@@ -738,6 +738,15 @@ int axpy_state(pdeopt_ctx* ctx, double dt) {
   return with_dtype(ctx, [&](auto t) { return axpy_state_t<decltype(t)>(ctx, dt); });
 }
 
+int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf) {
+  const int rc = ensure_plans(ctx);
+  return rc ? rc : fft_exec(ctx, forward, buf);
+}
+
+int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<double>>& out) {
+  return fetch_complex_aux(ctx, which, out);
+}
+
 int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   if (!ctx->aux[PDEOPT_AUX_GPE_A_TERM].dev)
     return fail(ctx, PDEOPT_ESTATE, "Strang splitting needs the GPE_A_TERM aux field");
@@ -750,9 +759,11 @@ int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
 void spectral_invalidate(pdeopt_ctx* ctx) {
   if (ctx->spectral) ctx->spectral->mult_kind = -1;
   strang_fused_invalidate(ctx);
+  gpe_adjoint_invalidate(ctx);
 }
 
 void spectral_destroy(pdeopt_ctx* ctx) {
+  gpe_adjoint_destroy(ctx);
   Spectral* sp = ctx->spectral;
   if (!sp) return;
   if (sp->r2c) rocfft_plan_destroy(sp->r2c);

@@ -472,6 +472,13 @@ class HipEngine:
                                                        C.byref(p), C.byref(nbytes)))
         return DeviceArray(p.value, (n,) + self.state_shape, np.uint8, self.device, owner=self)
 
+    def gpe_adjoint_step(self, t0: float, dt: float, psi0_ptr: int, lam_ptr: int, grad_ptr: int):
+        """the adjoint of one Strang substep of the GPE with Gaussian spots (``pdeopt_gpe_adjoint_step``): ``lam`` goes
+        from the cotangent of the substep's end state to that of its start state ``psi0`` in place, the spots'
+        gradient block ``(batch, n_spots, 7)`` of doubles (device or host memory) is added into"""
+        self._check(self._lib.pdeopt_gpe_adjoint_step(self._h, float(t0), float(dt), C.c_void_p(psi0_ptr), C.c_void_p(lam_ptr),
+                                                      C.c_void_p(grad_ptr)))
+
     def state_device_array(self) -> "DeviceArray":
         """The state field itself as a ``DeviceArray`` (batch,) + state_shape in the engine's dtype: valid until the
         next ``configure`` with another shape; ``advance`` updates it in place (synchronise with ``sync()``)."""

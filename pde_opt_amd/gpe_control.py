@@ -1,0 +1,193 @@
+"""Gradient-based control of the Gross-Pitaevskii equation: the reverse-mode (discrete adjoint) gradient of a scalar
+objective of the saved solution over the numbers of the laser spots (``GaussianSpots``) that steer it -- the
+reference's ``PDEModel.optimize`` on ``GPE2DTSControl`` + ``StrangSplitting``, which it differentiates with generic
+reverse-mode AD (pde_model.py:462-551).
+
+One scalar objective, a field-sized state, a few control numbers: reverse mode.  The forward pass is the library's Strang
+step (``pdeopt_advance``), the backward sweep ``pdeopt_gpe_adjoint_step`` (csrc/gpe_adjoint.hip), one call per substep:
+it takes the cotangent of a substep's end state to that of its start state and adds the spots' gradient on the device.
+The backward sweep needs the state every substep started from: substep and save-point schedule, the split of a save
+point's cotangent and the chunked recomputation are those of ``pde_opt_amd.fieldmu`` (one state kept per chunk, each
+chunk run again and held before its sweep).  A chunk holds at most ``PDEOPT_GPE_ADJOINT_CHUNK_BYTES`` (default 1 GiB;
+``GpeControlSolver.chunk_bytes`` overrides it).
+
+Covered: ``GPE2DTSControl`` whose ``lights`` is a ``GaussianSpots`` evaluated in-kernel, ``StrangSplitting`` with
+``ConstantStepSize``, fp32 and fp64, one state or a batch sharing the spots.  torch (device tensors for the held states
+and cotangents) is imported when a solver is built, not with the package.
+"""
+
+from __future__ import annotations
+
+import contextlib
+import os
+
+import numpy as np
+
+from . import _lib as L
+from .fieldmu import chunk_length, schedule, split_save_cotangent
+from .numerics.functions.lights import SPOT_NUMBERS, GaussianSpot, GaussianSpots
+
+CHUNK_BYTES_ENV = "PDEOPT_GPE_ADJOINT_CHUNK_BYTES"
+DEFAULT_CHUNK_BYTES = 1 << 30
+
+GPE_CONTROL_SUPPORT = ("gradients of the GPE support GPE2DTSControl whose lights is a GaussianSpots (evaluated in-kernel: "
+                       "time_dependent is not False) with StrangSplitting and ConstantStepSize; the optimisation variables are "
+                       "the spots' numbers (opt_parameters = {'lights': GaussianSpots}), not k, e, trap_factor or another "
+                       "lights callable")
+
+
+class SpotMap:
+    """The numbers of a ``GaussianSpots`` as one flat fp64 vector, ``SPOT_NUMBERS`` per spot in user units (the
+    counterpart of ``fit.ParamMap``).  Entries that are not ``free`` keep a zero gradient, so BFGS never moves them."""
+
+    def __init__(self, n_spots: int, free=None):
+        self.n_spots = int(n_spots)
+        self.free = None if free is None else tuple(n for n in SPOT_NUMBERS if n in free)
+
+    @classmethod
+    def of(cls, spots: GaussianSpots) -> "SpotMap":
+        if not isinstance(spots, GaussianSpots):
+            raise NotImplementedError(f"lights of type {type(spots).__name__}: " + GPE_CONTROL_SUPPORT)
+        return cls(len(spots.spots), spots.free)
+
+    @property
+    def size(self) -> int:
+        return 7 * self.n_spots
+
+    def active(self) -> np.ndarray:
+        """(S, 7) mask of the entries an optimiser may move"""
+        row = np.array([self.free is None or n in self.free for n in SPOT_NUMBERS])
+        return np.broadcast_to(row, (self.n_spots, 7)).copy()
+
+    def flatten(self, spots: GaussianSpots) -> np.ndarray:
+        if len(spots.spots) != self.n_spots:
+            raise ValueError(f"{len(spots.spots)} spots, the map was built for {self.n_spots}")
+        return np.array([[getattr(s, n) for n in SPOT_NUMBERS] for s in spots.spots], dtype=np.float64).reshape(-1)
+
+    def build(self, p) -> GaussianSpots:
+        p = np.asarray(p, dtype=np.float64)
+        if p.shape != (self.size,):
+            raise ValueError(f"flat spot vector of shape {p.shape}: {self.n_spots} spots have {self.size} numbers")
+        return GaussianSpots([GaussianSpot(*(float(v) for v in row)) for row in p.reshape(self.n_spots, 7)], free=self.free)
+
+    @staticmethod
+    def user_gradient(spots: GaussianSpots, raw) -> np.ndarray:
+        """the library's gradient block ``(..., S, 7)`` (last entry: d/d inv_two_w2) in user units (last entry: d/d width;
+        inv_two_w2 = 1 / (2 w^2), so d inv_two_w2 / dw = -1 / w^3)"""
+        g = np.array(raw, dtype=np.float64)
+        w = np.array([s.width for s in spots.spots])
+        g[..., 6] = g[..., 6] * (-1.0 / w**3)
+        return g
+
+    def weight_vector(self, w) -> np.ndarray:
+        """regularisation weights of the flat vector: None (zeros), a number or an (S, 7) array"""
+        if w is None:
+            return np.zeros(self.size)
+        return np.broadcast_to(np.asarray(w, dtype=np.float64), (self.n_spots, 7)).reshape(-1).copy()
+
+
+def reject_unsupported(equation_type, solver_type, parameters=None, opt_names=None):
+    """``NotImplementedError`` for what the GPE gradient does not cover; needs no engine and no GPU"""
+    from .numerics.equations.gross_pitaevskii import GPE2DTSControl
+    from .numerics.solvers import StrangSplitting
+
+    if equation_type is not GPE2DTSControl:
+        raise NotImplementedError(f"{equation_type.__name__}: " + GPE_CONTROL_SUPPORT)
+    if solver_type is not StrangSplitting:
+        raise NotImplementedError(f"{solver_type.__name__}: " + GPE_CONTROL_SUPPORT)
+    if opt_names is not None and set(opt_names) != {"lights"}:
+        raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + GPE_CONTROL_SUPPORT)
+    if parameters is not None:
+        if not isinstance(parameters.get("lights"), GaussianSpots):
+            raise NotImplementedError(f"lights of type {type(parameters.get('lights')).__name__}: " + GPE_CONTROL_SUPPORT)
+        if parameters.get("time_dependent") is False:
+            raise NotImplementedError("time_dependent=False folds the spots into the potential: " + GPE_CONTROL_SUPPORT)
+
+
+class GpeControlSolver:
+    """One engine for the backward sweeps, bound to one torch stream (the stream rule of ``fieldmu.FieldMuSolver``:
+    every call orders that stream after the caller's current stream on entry and the caller's after it on exit)."""
+
+    def __init__(self, device: int = 0):
+        import torch
+
+        from .engine import HipEngine
+
+        self.torch = torch
+        self.device = torch.device("cuda", int(device))
+        cur = torch.cuda.current_stream(self.device)
+        self.stream = cur if cur.cuda_stream else torch.cuda.Stream(self.device)
+        self.engine = HipEngine(int(device), stream=self.stream.cuda_stream)
+        self.chunk_bytes = None  # None: PDEOPT_GPE_ADJOINT_CHUNK_BYTES, else 1 GiB
+        self.last_chunks = 0     # chunks of the last backward sweep
+
+    @contextlib.contextmanager
+    def _ordered(self):
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.device)
+        if caller != self.stream:
+            self.stream.wait_stream(caller)
+        try:
+            with torch.cuda.stream(self.stream):
+                yield
+        finally:
+            if caller != self.stream:
+                caller.wait_stream(self.stream)
+
+    def _cap(self) -> int:
+        if self.chunk_bytes is not None:
+            return int(self.chunk_bytes)
+        return int(os.environ.get(CHUNK_BYTES_ENV, DEFAULT_CHUNK_BYTES))
+
+    def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
+        """``(grad (B, S, 7), lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys`` ``(len(ts), B, nx, ny, 2)`` of the saved
+        solution: ``grad`` is the library's block (per environment; last entry d/d inv_two_w2), ``lam0`` is ``dJ/dy0``.
+        Both fp64 on the host; the sweep itself runs in the dtype of ``y0s``."""
+        torch = self.torch
+        eng = self.engine
+        ts = np.asarray(ts, dtype=np.float64)
+        steps, saves = schedule(ts, dt0)
+        N = len(steps)
+        t_of = lambda i: float(ts[0]) + i * float(dt0)  # start time of substep i (integrate.diffeqsolve)
+        cot = {}
+        for q, (i, theta) in enumerate(saves):
+            g_prev, g_cur = split_save_cotangent(np.asarray(cotangents[q], dtype=np.float64), theta)
+            for k, g in ((i - 1, g_prev), (i, g_cur)):
+                if g is not None:
+                    cot[k] = g if k not in cot else cot[k] + g
+        S = len(equation.lights.spots)
+        with self._ordered(), torch.no_grad():
+            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem())
+            equation._engine_upload(eng, float(ts[0]), float(ts[-1]))
+            solver.configure_engine(eng, equation)
+            eng.set_state(y0s)
+            Y = eng.state_device_array().torch()
+            up = lambda g: torch.as_tensor(np.ascontiguousarray(g)).to(device=Y.device, dtype=Y.dtype)
+            chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
+            first = list(range(0, max(N, 1), chunk))  # first substep of every chunk
+            starts = {}
+            for i in range(first[-1] + 1):  # the forward pass ends where the last chunk starts
+                if i % chunk == 0:
+                    starts[i] = Y.clone()
+                if i < first[-1]:
+                    eng.advance(solver.integrator, steps[i], 1, t_of(i))
+            lam = up(cot[N]) if N in cot and N > 0 else torch.zeros_like(Y)
+            grad = torch.zeros((y0s.shape[0], S, 7), dtype=torch.float64, device=Y.device)
+            self.last_chunks = len(first)
+            for s0 in reversed(first):
+                s1 = min(N, s0 + chunk)
+                Y.copy_(starts.pop(s0))
+                held = []
+                for s in range(s0, s1):
+                    held.append(Y.clone())
+                    if s + 1 < s1:
+                        eng.advance(solver.integrator, steps[s], 1, t_of(s))
+                for s in range(s1 - 1, s0 - 1, -1):
+                    psi0 = held.pop()
+                    eng.gpe_adjoint_step(t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(), grad.data_ptr())
+                    if s in cot:
+                        lam += up(cot[s])
+            if N == 0 and 0 in cot:
+                lam += up(cot[0])
+            out = grad.cpu().numpy(), lam.double().cpu().numpy()
+        return out

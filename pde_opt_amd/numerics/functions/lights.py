@@ -23,6 +23,8 @@ MAX_SPOTS = 4  # PDEOPT_MAX_SPOTS
 
 Linear = Union[float, Tuple[float, float]]  # value, or (value at t = 0, rate of change)
 
+SPOT_NUMBERS = ("amp0", "amp_rate", "x0", "x_rate", "y0", "y_rate", "width")  # the fields of a GaussianSpot, in order
+
 
 def _lin(v: Linear) -> Tuple[float, float]:
     if isinstance(v, (tuple, list)):
@@ -59,11 +61,20 @@ class GaussianSpot:
 class GaussianSpots:
     """A sum of up to ``MAX_SPOTS`` Gaussian light spots; ``lights(t, X, Y)`` of ``GPE2DTSControl``."""
 
-    def __init__(self, spots: Sequence[GaussianSpot]):
+    def __init__(self, spots: Sequence[GaussianSpot], free=None):
+        """``free``: which of ``SPOT_NUMBERS`` an optimiser may change, the same names for every spot (``None``: all
+        seven).  Only the optimiser reads it (``PDEModel.optimize``); evaluating the spots does not."""
         spots = tuple(spots)
         if not 1 <= len(spots) <= MAX_SPOTS:
             raise ValueError(f"1..{MAX_SPOTS} spots, got {len(spots)}")
         self.spots = spots
+        if free is not None:
+            free = tuple(free)
+            unknown = [n for n in free if n not in SPOT_NUMBERS]
+            if unknown:
+                raise ValueError(f"free names {unknown}: a spot's numbers are {SPOT_NUMBERS}")
+            free = tuple(n for n in SPOT_NUMBERS if n in free)
+        self.free = free
 
     @classmethod
     def single(cls, amplitude: Linear, x: Linear, y: Linear, width: float) -> "GaussianSpots":
@@ -80,7 +91,9 @@ class GaussianSpots:
                                  float(width))])
 
     def __add__(self, other: "GaussianSpots") -> "GaussianSpots":
-        return GaussianSpots(self.spots + other.spots)
+        if self.free != other.free:
+            raise ValueError(f"the operands disagree on the free numbers ({self.free} and {other.free}): free is shared by all spots")
+        return GaussianSpots(self.spots + other.spots, free=self.free)
 
     def __call__(self, t, x, y):
         out = 0.0
