@@ -7,7 +7,9 @@ the frames that follow.  The CNN runs in torch on the GPU; the stencil, the IMEX
 kernels (pde_opt_amd.fieldmu).  ``PDEModel.mse_backward`` fills ``.grad`` of the CNN's parameters by a discrete adjoint
 of the solve, whose cost does not depend on the number of parameters, and ``torch.optim.Adam`` takes the step.
 
-``--quick`` runs 32^2 with a small CNN for 20 optimiser steps instead of 64^2 with the notebook's CNN for 200."""
+``--quick`` runs 32^2 with a small CNN for 20 optimiser steps instead of 64^2 with the notebook's CNN for 200.
+``--native-cnn`` evaluates and differentiates the CNN in the library's own HIP kernels instead of torch
+(``model.fieldmu_solver().native_cnn = True``; experimental, off by default)."""
 import os
 import sys
 
@@ -47,6 +49,8 @@ ts = np.array([0.0, 5e-5, 1e-4])
 
 torch.manual_seed(0)
 cnn = PeriodicCNN(1, HIDDEN, 1).double().to("cuda")
+if "--native-cnn" in sys.argv:
+    model.fieldmu_solver().native_cnn = True
 params = {"kappa": KAPPA, "mu": cnn, "D": D}
 opt = torch.optim.Adam(cnn.parameters(), lr=1e-2)
 n_par = sum(p.numel() for p in cnn.parameters())

@@ -526,6 +526,33 @@ int pdeopt_fieldmu_step(pdeopt_ctx* ctx, int integrator, double dt, const void* 
 int pdeopt_fieldmu_adjoint_step(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, const void* mu_dev,
                                 void* lam_dev, void* gmu_dev);
 
+/* ---- a periodic CNN as mu_h, evaluated and differentiated inside the library (pde_opt/numerics/functions/cnn.py:
+ * a stack of 3 x 3 convolutions with circular "same" padding and stride 1).  Supported, anything else is refused:
+ * one input and one output channel, 1 to 6 hidden layers of width 1 ... 64, one activation for all hidden layers,
+ * fp32 and fp64 (the dtype of the ctx's configured problem), periodic 2-D real fields with nx, ny >= 4, any batch.
+ * A handle belongs to its ctx and is destroyed before it.  Every *_dev argument is a device field [batch][nx][ny] in the
+ * problem dtype; all work is ordered on the ctx's stream.  pdeopt_cnn_grad_read synchronises the host, and so does the
+ * first forward / vjp after pdeopt_cnn_set_params (it packs and uploads the parameters); nothing else does. */
+typedef struct pdeopt_cnn pdeopt_cnn;
+typedef enum {
+  PDEOPT_CNN_GELU = 0,      /* 0.5 z (1 + erf(z / sqrt 2)): torch's default */
+  PDEOPT_CNN_GELU_TANH = 1, /* 0.5 z (1 + tanh(sqrt(2 / pi) (z + 0.044715 z^3))): jax.nn.gelu's default */
+  PDEOPT_CNN_TANH = 2
+} pdeopt_cnn_activation;
+/* n_layers convolutions (hidden layers + 1), channels[0 ... n_layers] with channels[0] = channels[n_layers] = 1 */
+int pdeopt_cnn_create(pdeopt_ctx* ctx, int n_layers, const int* channels, int activation, pdeopt_cnn** cnn);
+/* n doubles in torch's parameter order: per layer the weight (O, I, 3, 3), then the bias (O) */
+int pdeopt_cnn_set_params(pdeopt_cnn* cnn, const double* params_host, int64_t n);
+/* mu_dev = N(u_dev) */
+int pdeopt_cnn_forward(pdeopt_cnn* cnn, const void* u_dev, void* mu_dev);
+/* lam_dev += N'(u_dev)^T gmu_dev, and the gradient of <gmu, N(u)> over the parameters is added to a fp64 buffer kept
+ * on the device (the hidden layers are evaluated again; nothing is kept between calls).  lam_dev must not overlap
+ * u_dev or gmu_dev (refused).  Sums run in a fixed order without atomics: identical bits on a repeat. */
+int pdeopt_cnn_vjp(pdeopt_cnn* cnn, const void* u_dev, const void* gmu_dev, void* lam_dev);
+/* the accumulated parameter gradient, n doubles in the order of pdeopt_cnn_set_params; reset != 0 zeroes it */
+int pdeopt_cnn_grad_read(pdeopt_cnn* cnn, double* out_host, int64_t n, int reset);
+int pdeopt_cnn_destroy(pdeopt_cnn* cnn);
+
 /* ---- the discrete adjoint of one Strang substep of the GPE whose control is a sum of Gaussian spots
  * (pdeopt_set_gpe_spots): the reverse-mode gradient of a scalar objective of the solution over the spots' numbers (the
  * reference's PDEModel.optimize, pde_model.py:462-551, differentiates the same solve with generic reverse-mode AD).

@@ -49,6 +49,7 @@ COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 FIELD_Y, FIELD_TA, FIELD_TB, FIELD_ACC = 0, 1, 2, 3
 PATH_AUTO, PATH_GENERIC, PATH_TILED = 0, 1, 2
 PART_ALL, PART_INTERIOR, PART_EDGE = 0, 1, 2
+CNN_GELU, CNN_GELU_TANH, CNN_TANH = 0, 1, 2  # pdeopt_cnn_activation
 
 
 class HipUnavailableError(RuntimeError):
@@ -195,6 +196,12 @@ _SIGNATURES = {
     "pdeopt_fieldmu_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP]),
     "pdeopt_fieldmu_adjoint_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),
     "pdeopt_gpe_adjoint_step": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP, _VP]),
+    "pdeopt_cnn_create": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(_VP)]),
+    "pdeopt_cnn_set_params": (C.c_int, [_VP, _VP, C.c_int64]),
+    "pdeopt_cnn_forward": (C.c_int, [_VP, _VP, _VP]),
+    "pdeopt_cnn_vjp": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pdeopt_cnn_grad_read": (C.c_int, [_VP, _VP, C.c_int64, C.c_int]),
+    "pdeopt_cnn_destroy": (C.c_int, [_VP]),
 }
 
 _lib = None

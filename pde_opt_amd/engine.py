@@ -59,6 +59,7 @@ class HipEngine:
         self._aux_thunks: dict = {}
         self._aux_keys: dict = {}
         self._callback_error = None
+        self._cnns: list = []  # open NativeCNN handles: closed before the ctx they belong to
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -73,6 +74,8 @@ class HipEngine:
 
     def close(self):
         if getattr(self, "_h", None):
+            for cnn in list(getattr(self, "_cnns", ())):
+                cnn.close()
             self._lib.pdeopt_ctx_destroy(self._h)
             self._h = None
 
@@ -422,6 +425,11 @@ class HipEngine:
         self._check(self._lib.pdeopt_fieldmu_adjoint_step(self._h, int(integrator), float(dt), C.c_void_p(u_ptr),
                                                           C.c_void_p(mu_ptr), C.c_void_p(lam_ptr), C.c_void_p(gmu_ptr)))
 
+    def cnn(self, channels, activation: int) -> "NativeCNN":
+        """a periodic CNN evaluated by the library on this engine's fields (``pdeopt_cnn_*``); ``channels`` are
+        ``(1, hidden..., 1)``, ``activation`` one of ``_lib.CNN_*``"""
+        return NativeCNN(self, channels, activation)
+
     def reduce(self, op: int) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.float64)
         self._check(self._lib.pdeopt_reduce(self._h, int(op), out.ctypes.data_as(C.c_void_p)))
@@ -695,6 +703,55 @@ class LocalGroup:
         if getattr(self, "_h", None):
             self._lib.pdeopt_local_group_destroy(self._h)
             self._h = None
+
+
+class NativeCNN:
+    """Handle of a periodic CNN inside the library (csrc/cnn.hip), bound to one ``HipEngine``.  Field arguments are
+    device pointers of ``(batch, nx, ny)`` fields in the engine's dtype; everything is ordered on the engine's stream
+    and only ``grad_read`` waits for it.  ``created`` counts the handles ever made (tests of the opt-in switch)."""
+
+    created = 0
+
+    def __init__(self, engine: "HipEngine", channels, activation: int):
+        self.engine = engine
+        self.channels = tuple(int(c) for c in channels)
+        self.activation = int(activation)
+        self.n_params = sum(9 * i * o + o for i, o in zip(self.channels[:-1], self.channels[1:]))
+        ch = (C.c_int * len(self.channels))(*self.channels)
+        h = C.c_void_p()
+        engine._check(engine._lib.pdeopt_cnn_create(engine._h, len(self.channels) - 1, ch, self.activation, C.byref(h)))
+        self._h = h
+        engine._cnns.append(self)
+        NativeCNN.created += 1
+
+    def set_params(self, flat):
+        """the parameters as one flat fp64 vector in torch's order (``fieldmu.flatten_params``)"""
+        p = np.ascontiguousarray(flat, dtype=np.float64)
+        self.engine._check(self.engine._lib.pdeopt_cnn_set_params(self._h, p.ctypes.data_as(C.c_void_p), p.size))
+
+    def forward(self, u_ptr: int, mu_ptr: int):
+        self.engine._check(self.engine._lib.pdeopt_cnn_forward(self._h, C.c_void_p(u_ptr), C.c_void_p(mu_ptr)))
+
+    def vjp(self, u_ptr: int, gmu_ptr: int, lam_ptr: int):
+        """``lam += N'(u)^T gmu``; the parameter gradient accumulates on the device until ``grad_read``"""
+        self.engine._check(self.engine._lib.pdeopt_cnn_vjp(self._h, C.c_void_p(u_ptr), C.c_void_p(gmu_ptr), C.c_void_p(lam_ptr)))
+
+    def grad_read(self, reset: bool = True) -> np.ndarray:
+        out = np.empty(self.n_params, dtype=np.float64)
+        self.engine._check(self.engine._lib.pdeopt_cnn_grad_read(self._h, out.ctypes.data_as(C.c_void_p), out.size, int(bool(reset))))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.engine._lib.pdeopt_cnn_destroy(self._h)
+            self._h = None
+            self.engine._cnns.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default_engines: dict = {}

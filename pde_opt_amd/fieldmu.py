@@ -20,6 +20,12 @@ chunk is run again and held before its sweep.  A chunk holds at most ``PDEOPT_FI
 Covered: ``CahnHilliard2DPeriodic`` with ``derivs="fd"``, ``SemiImplicitFourierSpectral`` or ``Euler`` with
 ``ConstantStepSize``, fp32 and fp64, ``D`` a closure of the in-kernel family, ``D`` and ``kappa`` fixed.
 
+``FieldMuSolver.native_cnn`` (off by default; ``PDEOPT_FIELDMU_NATIVE_CNN=1`` sets the default) moves the network into
+the library as well: a ``PeriodicCNN`` of the family ``numerics.functions.cnn.native_spec`` accepts is evaluated by
+``pdeopt_cnn_forward`` and differentiated by ``pdeopt_cnn_vjp`` (csrc/cnn.hip), no autograd graph is built, and the
+parameter gradient accumulates in fp64 on the device over the sweep and is read once.  A module outside that family is
+refused while the switch is on; there is no fallback to torch.
+
 torch is imported when a solver is built, not with the package.
 """
 
@@ -37,6 +43,7 @@ from .numerics.equations.phase_field import FIELD_MU_SUPPORT
 
 CHUNK_BYTES_ENV = "PDEOPT_FIELDMU_CHUNK_BYTES"
 DEFAULT_CHUNK_BYTES = 1 << 30
+NATIVE_CNN_ENV = "PDEOPT_FIELDMU_NATIVE_CNN"
 
 
 # ---- parameters as one flat vector --------------------------------------------------------------------------------------
@@ -159,6 +166,10 @@ class FieldMuSolver:
         self.engine = HipEngine(int(device), stream=self.stream.cuda_stream)
         self.chunk_bytes = None  # None: PDEOPT_FIELDMU_CHUNK_BYTES, else 1 GiB
         self.last_chunks = 0     # chunks of the last backward sweep
+        # evaluate and differentiate a PeriodicCNN mu in the library (csrc/cnn.hip) instead of in torch
+        self.native_cnn = os.environ.get(NATIVE_CNN_ENV, "0") not in ("", "0")
+        self._cnn = None         # the library's handle of the last native network
+        self._cnn_pending = False  # its gradient buffer holds sums of a sweep that did not finish
 
     @contextlib.contextmanager
     def _ordered(self):
@@ -182,7 +193,8 @@ class FieldMuSolver:
     # -- set-up ---------------------------------------------------------------------------------------------------------
     def _prepare(self, equation, solver, y0s, t0, t1):
         """configure the engine, upload the state; returns ``(Y, mu_of)``: the state as a tensor ``(B, nx, ny)`` over the
-        engine's own buffer, and ``mu_of(u) -> mu_h`` ``(B, nx, ny)``, contiguous"""
+        engine's own buffer, and ``mu_of(u) -> mu_h`` ``(B, nx, ny)``, contiguous.  With ``native_cnn`` the library
+        evaluates the network: ``mu_of`` fills and returns one buffer, and ``self._cnn`` holds this call's parameters"""
         torch = self.torch
         eng = self.engine
         eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem(field_mu=True))
@@ -194,8 +206,33 @@ class FieldMuSolver:
         for name, p in module.named_parameters():
             if p.dtype != Y.dtype or p.device != Y.device:
                 raise ValueError(f"mu's parameter {name} is {p.dtype} on {p.device}; the solve runs in {Y.dtype} on {Y.device}")
+        if self.native_cnn:
+            cnn = self._native(module)
+            mu_h = torch.empty_like(Y)
+
+            def native_mu(u):
+                cnn.forward(u.data_ptr(), mu_h.data_ptr())
+                return mu_h
+
+            return Y, native_mu
         call = as_field_call(module, Y)
         return Y, lambda u: call(u).reshape(u.shape).contiguous()
+
+    def _native(self, module):
+        """the library's handle of ``module`` with its current parameters uploaded; refuses what csrc/cnn.hip does not cover"""
+        from .numerics.functions import cnn as C
+
+        spec = C.native_spec(module)
+        if spec is None:
+            raise NotImplementedError(f"native_cnn is on and mu is not a network the library evaluates: {C.native_refusal(module)} "
+                                      "(there is no fallback to torch: set native_cnn = False)")
+        channels, act = spec[0], C.NATIVE_ACTIVATIONS.index(spec[1])
+        if self._cnn is None or (self._cnn.channels, self._cnn.activation) != (channels, act):
+            if self._cnn is not None:
+                self._cnn.close()
+            self._cnn, self._cnn_pending = self.engine.cnn(channels, act), False
+        self._cnn.set_params(flatten_params(module))
+        return self._cnn
 
     # -- forward --------------------------------------------------------------------------------------------------------
     def solve(self, equation, solver, y0s, ts, dt0, controller=None) -> np.ndarray:
@@ -238,6 +275,11 @@ class FieldMuSolver:
                 by_index.setdefault(i, []).append((q, theta))
         with self._ordered(), torch.no_grad(), _deterministic(torch):
             Y, mu_of = self._prepare(equation, solver, y0s, float(ts[0]), float(ts[-1]))
+            cnn = self._cnn if self.native_cnn else None
+            if cnn is not None:
+                if self._cnn_pending:
+                    cnn.grad_read(reset=True)
+                self._cnn_pending = True
             vals = torch.as_tensor(np.ascontiguousarray(np.swapaxes(values, 0, 1)), dtype=Y.dtype).to(Y.device)  # (T - 1, B, ...)
             M = vals.numel()
             chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
@@ -272,6 +314,13 @@ class FieldMuSolver:
                     if s + 1 < s1:
                         self.engine.fieldmu_step(integ, steps[s], mu_of(Y).data_ptr())
                 for s in range(s1 - 1, s0 - 1, -1):
+                    if cnn is not None:
+                        u = held.pop()
+                        self.engine.fieldmu_adjoint_step(integ, steps[s], u.data_ptr(), mu_of(u).data_ptr(), lam.data_ptr(), gmu.data_ptr())
+                        cnn.vjp(u.data_ptr(), gmu.data_ptr(), lam.data_ptr())
+                        if s in cot and s > 0:
+                            lam += cot[s]
+                        continue
                     u = held.pop().requires_grad_(True)
                     with torch.enable_grad():
                         mu = mu_of(u)
@@ -281,6 +330,9 @@ class FieldMuSolver:
                     if s in cot and s > 0:
                         lam += cot[s]
             loss = float(ssr.item()) / M
+            if cnn is not None:
+                add_flat_grad(equation._mu_module, cnn.grad_read(reset=True))
+                self._cnn_pending = False
         return loss
 
 

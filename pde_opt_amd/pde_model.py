@@ -92,7 +92,8 @@ class PDEModel:
 
     # -- a torch.nn.Module as mu (pde_opt_amd.fieldmu) -----------------------------------------------------------------
     def fieldmu_solver(self):
-        """the solver of the module path (its ``chunk_bytes`` caps the states the backward sweep holds)"""
+        """the solver of the module path (its ``chunk_bytes`` caps the states the backward sweep holds; its
+        ``native_cnn = True`` evaluates and differentiates a ``PeriodicCNN`` in the library's own kernels, csrc/cnn.hip)"""
         if getattr(self, "_fieldmu", None) is None:
             from .fieldmu import FieldMuSolver
 

@@ -6,6 +6,11 @@ HIP events on the stream the engine and torch share; the first rounds are discar
 timed window is set per case from a trial window so that the window lasts about 50 ms.  Needs an MI355X.
 
     PYTHONPATH=. python tools/fieldmu_bench.py [--json out.json]
+
+``--native-cnn``: instead, the CNN's share of a forward and of a backward substep at 128^2 x 3, evaluated by torch and by
+the library's own kernels (csrc/cnn.hip, ``FieldMuSolver.native_cnn``) on the same state in one run, fp32 and fp64, with
+the shader clock held during the native windows.  The backward share is what the sweep runs per substep: torch's forward
+under autograd + backward, or ``pdeopt_cnn_forward`` (mu_h for the adjoint kernel) + ``pdeopt_cnn_vjp``.
 """
 import json
 import sys
@@ -73,9 +78,56 @@ def case(n, B, dtype):
     return res
 
 
+def native_case(n, B, dtype):
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
+    dom = P.Domain((n, n), ((0.0, 0.01 * n), (0.0, 0.01 * n)), "dimensionless")
+    cnn = PeriodicCNN(1, (32, 64, 64), 1).to(tdt).to("cuda")
+    eq = P.CahnHilliard2DPeriodic(dom, 0.002, cnn, DiffusionLegendrePolynomials(np.array([0.0])))
+    solver = P.SemiImplicitFourierSpectral(A=0.5, fourier_symbol=eq.fourier_symbol)
+    fm = FieldMuSolver(0)
+    y0 = np.clip(0.5 + 0.05 * np.random.default_rng(0).standard_normal((B, n, n)), 0.05, 0.95).astype(dtype)
+    res = {}
+    with torch.cuda.stream(fm.stream):
+        Y, mu_of = fm._prepare(eq, solver, y0, 0.0, 1.0)
+        u0 = Y.clone()
+        gmu, lam = torch.randn_like(Y), torch.zeros_like(Y)
+        with torch.no_grad():
+            res["forward: torch"] = timed(fm.stream, lambda: mu_of(u0))
+        u = u0.clone().requires_grad_(True)
+
+        def torch_backward():
+            u.grad = None
+            mu_of(u).backward(gmu)
+
+        res["backward: torch (forward + backward)"] = timed(fm.stream, torch_backward)
+        fm.native_cnn = True
+        _, native_mu = fm._prepare(eq, solver, y0, 0.0, 1.0)
+        net = fm._cnn
+
+        def native_backward():
+            native_mu(u0)
+            net.vjp(u0.data_ptr(), gmu.data_ptr(), lam.data_ptr())
+
+        fm.engine.timer_start()
+        res["forward: native"] = timed(fm.stream, lambda: native_mu(u0))
+        res["backward: native (forward + vjp)"] = timed(fm.stream, native_backward)
+        res["backward: native (vjp alone)"] = timed(fm.stream, lambda: net.vjp(u0.data_ptr(), gmu.data_ptr(), lam.data_ptr()))
+        fm.engine.timer_stop()
+        res["shader clock during the native windows, MHz"] = fm.engine.timer_clock_hz() / 1e6
+        net.grad_read(reset=True)
+    return res
+
+
 if __name__ == "__main__":
     results = {}
-    for n in (32, 128):
+    if "--native-cnn" in sys.argv:
+        for dtype in (np.float32, np.float64):
+            key = f"128x128x3 {np.dtype(dtype).name}"
+            results[key] = native_case(128, 3, dtype)
+            for name, v in results[key].items():
+                print(f"{key:18s} {name:45s} " + (f"{v:9.0f}" if np.isscalar(v) else f"{v[0]:9.1f} us  (min {v[1]:.1f}, max {v[2]:.1f})"),
+                      flush=True)
+    for n in () if "--native-cnn" in sys.argv else (32, 128):
         for dtype in (np.float32, np.float64):
             key = f"{n}x{n}x3 {np.dtype(dtype).name}"
             results[key] = case(n, 3, dtype)
