@@ -69,7 +69,10 @@ typedef enum {
   PDEOPT_INT_RK4 = 1,     /* classical RK4 (new; BASELINE.json configs 2,3,5)              */
   PDEOPT_INT_IMEX = 2,    /* SemiImplicitFourierSpectral.step   numerics/solvers.py:56-70  */
   PDEOPT_INT_STRANG = 3,  /* StrangSplitting.step               numerics/solvers.py:99-122 */
-  PDEOPT_INT_TSIT5 = 4    /* diffrax.Tsit5 fixed step (adaptive PID driven from the host)  */
+  PDEOPT_INT_TSIT5 = 4,   /* diffrax.Tsit5 fixed step (adaptive PID driven from the host)  */
+  /* alternating-direction split step of the rotating-frame GPE (GPE2DTSRot.A_terms,
+   * gross_pitaevskii.py:122-126; Bao & Wang 2006); new, DESIGN.md section 4.10 defines the step */
+  PDEOPT_INT_STRANG_ROT = 5
 } pdeopt_integrator;
 
 /* Pointwise closure family standing in for the reference's Python callables mu(u), D(u), R(u)
@@ -218,6 +221,12 @@ int pdeopt_set_env_imex_scale(pdeopt_ctx* ctx, int env_first, int env_count, con
 /* per-environment GPE interaction strength k (gross_pitaevskii.py:38-39): with a batch every
  * environment carries its own control value (BASELINE config 4 is an RL environment whose agent may act on k) */
 int pdeopt_set_env_gpe_k(pdeopt_ctx* ctx, int env_first, int env_count, const double* k);
+/* rotating-frame GPE (PDEOPT_INT_STRANG_ROT): rotation frequency Omega of every environment and the coordinates of
+ * cell (0, 0) (cell (i, j) sits at x_first + i hx, y_first + j hy, as in pdeopt_set_gpe_spots): the line operators
+ * exp(-/+ Omega coord (2 pi i k) tau / 2) are evaluated in-kernel from them.  Needs PDEOPT_EQ_GPE. */
+int pdeopt_set_gpe_rotation(pdeopt_ctx* ctx, double omega, double x_first, double y_first);
+/* per-environment Omega (after pdeopt_set_gpe_rotation, which also resets every environment to its omega) */
+int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, const double* omega);
 /* shared (per_env = 0: [nx][ny]) or per-environment (per_env = 1: [batch][nx][ny]) auxiliary
  * field, host pointer, element type = problem dtype (complex = 2 elements).  Replaces a time-dependent
  * source registered with pdeopt_set_aux_time_fn for the same field. */

@@ -20,6 +20,7 @@ from .numerics.equations import (
     CahnHilliard2DSmoothedBoundary,
     CahnHilliard3DPeriodic,
     GPE2DTSControl,
+    GPE2DTSRot,
 )
 from .numerics.functions import (
     ChemicalPotentialLegendrePolynomials,
@@ -37,6 +38,7 @@ from .numerics.solvers import (
     SaveAt,
     SemiImplicitFourierSpectral,
     StrangSplitting,
+    RotatingStrangSplitting,
     Tsit5,
 )
 from .pde_env import PDEEnv, VectorPDEEnv
@@ -45,6 +47,7 @@ from .pde_model import PDEModel
 __all__ = [
     "PDEModel", "PDEEnv", "VectorPDEEnv", "HipEngine", "diffeqsolve", "Solution",
     "BaseEquation", "AllenCahn2DPeriodic", "CahnHilliard2DPeriodic", "AdvectionDiffusion2D", "GPE2DTSControl",
+    "GPE2DTSRot", "RotatingStrangSplitting",
     "AllenCahn2DSmoothedBoundary", "CahnHilliard2DSmoothedBoundary", "CahnHilliard3DPeriodic",
     "Domain", "Shape", "LegendrePolynomialExpansion", "DiffusionLegendrePolynomials", "ChemicalPotentialLegendrePolynomials",
     "GaussianSpot", "GaussianSpots",

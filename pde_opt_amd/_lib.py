@@ -26,6 +26,7 @@ EQ_ALLEN_CAHN_SBM, EQ_CAHN_HILLIARD_SBM = 4, 5
 EQ_CAHN_HILLIARD_3D = 6
 EQ_SHAPE_SMOOTH = 7  # Shape.smooth_shape (shapes.py:39-64)
 INT_EULER, INT_RK4, INT_IMEX, INT_STRANG, INT_TSIT5 = 0, 1, 2, 3, 4
+INT_STRANG_ROT = 5  # rotating-frame alternating-direction split step (GPE2DTSRot)
 CL_POLY, CL_LEGENDRE, CL_JIT = 0, 1, 2
 CL_LOGIT_PRIOR, CL_EXP_WRAP = 1, 2
 SENS_MU, SENS_MOB = 0, 1  # pdeopt_sens_role
@@ -132,6 +133,8 @@ _SIGNATURES = {
     "pdeopt_set_aux_time_fn": (C.c_int, [_VP, C.c_int, AUX_FN, _VP, C.c_int]),
     "pdeopt_set_env_gpe_k": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_set_env_imex_scale": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "pdeopt_set_gpe_rotation": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double]),
+    "pdeopt_set_env_gpe_omega": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_set_gpe_spots": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_double, C.c_double]),
     "pdeopt_set_state": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_get_state": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),

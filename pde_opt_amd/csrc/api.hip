@@ -109,6 +109,7 @@ void fill_env_params(pdeopt_ctx* ctx) {
     e[b].gpe_k = T(p.gpe_k);
     e[b].kscale = T(1);
     e[b].imex_scale = T(1);
+    e[b].gpe_omega = T(0);
     for (int k = 0; k < kMaxCoef; ++k) {
       e[b].mu[k] = k < p.mu.n ? T(p.mu.coef[k]) : T(0);
       e[b].mob[k] = k < p.mob.n ? T(p.mob.coef[k]) : T(0);
@@ -135,6 +136,12 @@ template <typename T>
 void patch_env_gpe_k(pdeopt_ctx* ctx, int first, int count, const double* k) {
   auto* e = reinterpret_cast<EnvParams<T>*>(ctx->env_params_host.data());
   for (int i = 0; i < count; ++i) e[first + i].gpe_k = T(k[i]);
+}
+
+template <typename T>
+void patch_env_gpe_omega(pdeopt_ctx* ctx, int first, int count, const double* omega, double all) {
+  auto* e = reinterpret_cast<EnvParams<T>*>(ctx->env_params_host.data());
+  for (int i = 0; i < count; ++i) e[first + i].gpe_omega = T(omega ? omega[i] : all);
 }
 
 template <typename T>
@@ -400,6 +407,7 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   with_dtype(ctx, [&](auto t) { fill_env_params<decltype(t)>(ctx); });
   if ((rc = ensure_buffer(ctx, &ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
   ctx->imex_per_env = false;
+  ctx->rot_set = false;
   ctx->configured = true;
   return upload_env_params(ctx);
 }
@@ -520,6 +528,28 @@ int pdeopt_set_env_gpe_k(pdeopt_ctx* ctx, int env_first, int env_count, const do
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   with_dtype(ctx, [&](auto t) { patch_env_gpe_k<decltype(t)>(ctx, env_first, env_count, k); });
+  return upload_env_params(ctx);
+}
+
+int pdeopt_set_gpe_rotation(pdeopt_ctx* ctx, double omega, double x_first, double y_first) {
+  if (!ctx) return PDEOPT_EINVAL;
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  if (ctx->prob.equation != PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "the rotation frequency belongs to the GPE");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->rot_set = true;
+  ctx->rot_x_first = x_first;
+  ctx->rot_y_first = y_first;
+  with_dtype(ctx, [&](auto t) { patch_env_gpe_omega<decltype(t)>(ctx, 0, ctx->prob.batch, nullptr, omega); });
+  return upload_env_params(ctx);
+}
+
+int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, const double* omega) {
+  if (!ctx || !omega) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  if (ctx->prob.equation != PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "the rotation frequency belongs to the GPE");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  with_dtype(ctx, [&](auto t) { patch_env_gpe_omega<decltype(t)>(ctx, env_first, env_count, omega, 0.0); });
   return upload_env_params(ctx);
 }
 
@@ -694,6 +724,9 @@ int pdeopt_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_
     case PDEOPT_INT_STRANG:
       if (eq != PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "Strang splitting needs the GPE");
       return advance_strang(ctx, t0, dt, n_substeps);
+    case PDEOPT_INT_STRANG_ROT:
+      if (eq != PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step needs the GPE");
+      return advance_strang_rot(ctx, t0, dt, n_substeps);
     case PDEOPT_INT_TSIT5: {
       if (eq == PDEOPT_EQ_GPE)
         return fail(ctx, PDEOPT_EINVAL, "the GPE is integrated by Strang splitting only");

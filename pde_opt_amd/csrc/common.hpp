@@ -30,6 +30,7 @@ struct EnvParams {
   T mu[kMaxCoef];
   T mob[kMaxCoef];
   T fe[kMaxCoef];  // free-energy density closure (smoothed-boundary equations)
+  T gpe_omega;     // rotation frequency of the rotating-frame GPE (pdeopt_set_gpe_rotation / pdeopt_set_env_gpe_omega)
 };
 
 // Gaussian light spots of the GPE control field (pdeopt_set_gpe_spots), in the arithmetic type of the path;
@@ -125,6 +126,7 @@ struct Spectral;     // rocFFT plans + work buffers (spectral.hip)
 struct StrangFused;  // LDS-FFT split-step state (strang_fused.hip)
 struct Sens;         // forward-mode sensitivity configuration + Gauss-Newton buffers (sens.hip)
 struct GpeAdjoint;   // work fields + multiplier of the Strang step's adjoint (gpe_adjoint.hip)
+struct GpeRot;       // tables + work fields of the rotating-frame ADI split step (gpe_rot.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -236,6 +238,10 @@ struct pdeopt_ctx {
   pdeopt::StrangFused* strang_fused = nullptr;
   pdeopt::Sens* sens = nullptr;
   pdeopt::GpeAdjoint* gpe_adjoint = nullptr;
+  // rotating-frame GPE (pdeopt_set_gpe_rotation): coordinates of cell (0, 0); Omega itself lives in EnvParams
+  bool rot_set = false;
+  double rot_x_first = 0.0, rot_y_first = 0.0;
+  pdeopt::GpeRot* gpe_rot = nullptr;
 };
 
 namespace pdeopt {
@@ -409,6 +415,13 @@ int axpy_state(pdeopt_ctx* ctx, double dt);
 // plans of the library Strang path: any grid); host copy of a shared complex aux field
 int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf);
 int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<double>>& out);
+// one unnormalised complex transform along ONE axis (0: x, lines of stride ny; 1: y, contiguous lines) of a
+// whole-batch field [batch][nx][ny], in place, on the ctx's stream: rocFFT batched 1-D plans, any grid
+int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf);
+// gpe_rot.hip: the rotating-frame ADI split step (PDEOPT_INT_STRANG_ROT); buffers live and die with the spectral state
+int advance_strang_rot(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
+void gpe_rot_invalidate(pdeopt_ctx* ctx);
+void gpe_rot_destroy(pdeopt_ctx* ctx);
 // gpe_adjoint.hip: its buffers live and die with the spectral state (spectral_destroy / spectral_invalidate)
 void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_adjoint_destroy(pdeopt_ctx* ctx);

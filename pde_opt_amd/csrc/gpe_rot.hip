@@ -1,0 +1,538 @@
+// Alternating-direction split step of the rotating-frame GPE (PDEOPT_INT_STRANG_ROT).
+//
+// The two operators GPE2DTSRot.A_terms publishes (gross_pitaevskii.py:122-126),
+//   Ax(kx, y) = 0.5j (2 pi i kx)^2 - Omega y (2 pi i kx),     Ay(x, ky) = 0.5j (2 pi i ky)^2 + Omega x (2 pi i ky),
+// are diagonal under a transform along ONE axis at a fixed coordinate of the other (Bao & Wang 2006):
+//   Lx(s) v = ifft_x[exp(s Ax) fft_x v],   Ly(s) v = ifft_y[exp(s Ay) fft_y v].
+// Step, tau = dt * time_scale, h^2 = strang_dx^2 (the two quirks of StrangSplitting.step kept: b from the state
+// BEFORE the half step, renormalisation every step):
+//   psi1 = Ly(tau/2) Lx(tau/2) psi0;   b = -i (V + k |psi0|^2);   psi2 = psi1 exp(b tau)
+//   psi3 = psi2 / sqrt(h^2 sum |psi2|^2);   psi4 = Lx(tau/2) Ly(tau/2) psi3
+//
+// Every line is independent, so a pass loads a line, transforms it, multiplies, transforms back -- in registers / LDS
+// (fft_reg.hpp) -- and two line operators of neighbouring half steps along the same axis share a pass:
+//   col FIRST :                               |psi0|^2 -> Lx(tau/2)
+//   row       : Ly(tau/2) -> * exp(b tau), partial sums of |psi2|^2 -> Ly(tau/2)
+//   col JOIN  : Lx(tau/2) * scale -> |psi|^2 of the next step -> Lx(tau/2)          (col LAST: the first half only)
+// = 2 passes per step in steady state.  The norm of psi2 is not known inside the row pass; the transforms are
+// linear, so the scale is applied by the column pass that follows (fixed-order fp64 partial sums, no atomics).
+//
+// The multiplier of a line is a 1-D kinetic table per axis, exp(tau/2 0.5j (2 pi i k)^2) / N, times the rotation
+// factor exp(-/+ Omega coord (2 pi i k) tau/2), evaluated in-kernel from Omega (EnvParams: one per environment),
+// the line's coordinate and k: no N^2 table.
+//
+// Grids outside nx, ny in {64 .. 1024} run the same step on rocFFT's batched 1-D plans (spectral_c2c_axis) with the
+// pointwise kernels below.
+#include <algorithm>
+#include <cmath>
+#include <complex>
+
+#include "common.hpp"
+#include "groups.hpp"
+#include "fft_lds.hpp"
+#include "fft_reg.hpp"
+#include "split_step_util.hpp"
+
+namespace pdeopt {
+
+struct GpeRot {
+  void* tw_x = nullptr;   // twiddle tables exp(-2 pi i n / N) in the problem dtype
+  void* tw_y = nullptr;
+  void* kin_x = nullptr;  // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
+  void* kin_y = nullptr;
+  void* dens = nullptr;   // |psi0|^2, real [batch][nx][ny]
+  double* partial = nullptr;
+  int partial_per_env = 0;
+  double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
+  bool valid = false;
+};
+
+namespace {
+
+// one axis's line operator: theta = a k_signed with a = w Omega coord, w = -/+ 2 pi / (N h) (the sign of the
+// rotation term: - for lines along x, + for lines along y), s = tau / 2 = sr + i si
+template <typename T>
+struct RotAxis {
+  T w, c_first, c_step, sr, si;
+};
+
+// kin * exp(i theta s) = kin * exp(-theta si) (cos(theta sr) + i sin(theta sr)),  theta = a * fftfreq index of f
+template <typename T>
+__device__ __forceinline__ Cx<T> rot_mult(Cx<T> kin, T a, int f, int n, T sr, T si) {
+  const int ks = f < (n + 1) / 2 ? f : f - n;
+  const T th = a * T(ks);
+  T sn, cs;
+  sincos_t<T>(th * sr, &sn, &cs);
+  const T mag = (si == T(0)) ? T(1) : exp_t<T>(-th * si);
+  return cmul(kin, Cx<T>{mag * cs, mag * sn});
+}
+
+// fp64 and 16-point threads: one factor's sincos at a time (interleaved, their temporaries cost more registers than
+// the line itself)
+template <typename T, int PTS>
+constexpr bool kOneFactorAtATime = sizeof(T) == 8 || PTS > 8;
+
+// The row pass: lines along y (contiguous), N/PTS threads per line, 256/(N/PTS) lines per workgroup, every line in
+// one wave (the exchanges need no s_barrier).  Ly(tau/2) -> exp(b tau) + norm partial -> Ly(tau/2).
+template <typename T, int N>
+__global__ __launch_bounds__(256) void rot_row_kernel(Cx<T>* __restrict__ psi, const T* __restrict__ dens,
+                                                      const T* __restrict__ pot, int64_t pot_env_stride,
+                                                      const EnvParams<T>* __restrict__ ep,
+                                                      const Cx<T>* __restrict__ tw, const Cx<T>* __restrict__ kin,
+                                                      T tr, T ti, const RotAxis<T> ax, int nx,
+                                                      double* __restrict__ partial) {
+  using E = RegFft<T, N>;
+  constexpr int PTS = E::kPts, TT = E::TT, F = 256 / TT, NP = E::NP;
+  static_assert(E::kWaveLocal, "a line lives in one wave");
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int tid = threadIdx.x;
+  const int f = tid / TT, j = tid - f * TT;
+  Cx<T>* const seq = reinterpret_cast<Cx<T>*>(smem_raw) + f * NP;
+  const int64_t row = (int64_t)blockIdx.x * F + f;
+  const int env = (int)(row / nx);
+  const int ix = (int)(row - (int64_t)env * nx);
+  Cx<T>* const g = psi + row * N;
+  const T a = ax.w * ep[env].gpe_omega * (ax.c_first + T(ix) * ax.c_step);
+  Cx<T> v[PTS];
+#pragma unroll
+  for (int m = 0; m < PTS; ++m) v[m] = g[E::natural(j, m)];
+  E::template dif<-1>(v, seq, tw, j);
+#pragma unroll
+  for (int sl = 0; sl < PTS; ++sl) {
+    const int fr = E::freq(j, sl);
+    v[sl] = cmul(v[sl], rot_mult<T>(kin[fr], a, fr, N, ax.sr, ax.si));
+    if constexpr (kOneFactorAtATime<T, PTS>) __builtin_amdgcn_sched_barrier(0);
+  }
+  E::template dit<+1>(v, seq, tw, j);
+  // psi2 = psi1 exp(b tau), b = -i (V + k |psi0|^2): exp(-i w (tr + i ti)) = exp(w ti) (cos(w tr) - i sin(w tr)).
+  // |psi2|^2 of the thread's points in the working precision, the sums across threads / workgroups in fp64
+  const T kk = ep[env].gpe_k;
+  const T* const vrow = pot ? pot + (int64_t)env * pot_env_stride + (int64_t)ix * N : nullptr;
+  T accp = T(0);
+#pragma unroll
+  for (int m = 0; m < PTS; ++m) {
+    const int n = E::natural(j, m);
+    const T w = (vrow ? vrow[n] : T(0)) + kk * dens[row * N + n];
+    T sn, cs;
+    sincos_t<T>(w * tr, &sn, &cs);
+    const T mag = (ti == T(0)) ? T(1) : exp_t<T>(w * ti);
+    v[m] = cmul(v[m], Cx<T>{mag * cs, -mag * sn});
+    accp += v[m].re * v[m].re + v[m].im * v[m].im;
+  }
+  double acc = (double)accp;
+  __shared__ double red[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  E::template dif<-1>(v, seq, tw, j);
+#pragma unroll
+  for (int sl = 0; sl < PTS; ++sl) {
+    const int fr = E::freq(j, sl);
+    v[sl] = cmul(v[sl], rot_mult<T>(kin[fr], a, fr, N, ax.sr, ax.si));
+    if constexpr (kOneFactorAtATime<T, PTS>) __builtin_amdgcn_sched_barrier(0);
+  }
+  E::template dit<+1>(v, seq, tw, j);
+#pragma unroll
+  for (int m = 0; m < PTS; ++m) g[E::natural(j, m)] = v[m];
+}
+
+// Column-pass geometry: C adjacent columns x N/PTS threads per workgroup, the column index fastest across lanes on
+// the global side (strang_fused.hip has the measurements behind 128-byte segments).  Up to N = 512 stages 1.. of a
+// transform run with a column per wave (RegFft::dif_split / dit_split: one workgroup barrier per transform); at
+// N = 1024 the barrier form.  Workgroups of at most 512 (fp32) / 256 (fp64) threads: the JOIN form holds a line's
+// points, the twiddles of a butterfly and a sincos in flight, and at more threads the compiler's register cap
+// (128 VGPRs at 1024 threads) spills the fp64 instantiations to scratch.
+constexpr bool rot_col_wave_local(int n) { return n <= 512; }
+template <typename T, int N>
+constexpr int rot_cols() {
+  constexpr int c = sizeof(T) == 4 ? 16 : 8, cap = sizeof(T) == 4 ? 512 : 256, tt = N / reg_default_pts<N>();
+  return c * tt > cap ? cap / tt : c;
+}
+
+// The column pass: lines along x (stride ny).  PRE: Lx(tau/2) * scale, the second half of a step (scale =
+// 1 / sqrt(h^2 sum |psi2|^2) from the row pass's partial sums).  POST: |psi|^2 of the state, then Lx(tau/2), the
+// first half of a step.  FIRST = POST, JOIN = PRE + POST, LAST = PRE.
+template <typename T, int N, int C, bool PRE, bool POST>
+__global__ __launch_bounds__(C* N / reg_default_pts<N>()) void rot_col_kernel(
+    Cx<T>* __restrict__ psi, T* __restrict__ dens, const EnvParams<T>* __restrict__ ep, const Cx<T>* __restrict__ tw,
+    const Cx<T>* __restrict__ kin, const RotAxis<T> ax, int ny, const double* __restrict__ partial, int blocks_per_env,
+    double dx2) {
+  using E = RegFft<T, N>;
+  constexpr int PTS = E::kPts, NP = E::NP;
+  constexpr bool WL = rot_col_wave_local(N);
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int tid = threadIdx.x;
+  const int j = tid / C, c = tid - j * C;
+  Cx<T>* const seq = reinterpret_cast<Cx<T>*>(smem_raw) + c * NP;
+  const int env = blockIdx.y;
+  const int col0 = blockIdx.x * C;
+  // uniform base pointers + 32-bit per-thread offsets
+  Cx<T>* const gb = psi + (int64_t)env * N * ny + col0;
+  T* const db = dens + (int64_t)env * N * ny + col0;
+  Cx<T> v[PTS];
+#pragma unroll
+  for (int m = 0; m < PTS; ++m) v[m] = gb[E::natural(j, m) * ny + c];
+  __shared__ double scale_sh;  // published by the barrier(s) of the first transform
+  if constexpr (PRE) {
+    if (tid < 64) {
+      double sum = 0.0;
+      for (int q = tid; q < blocks_per_env; q += 64) sum += partial[(int64_t)env * blocks_per_env + q];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
+      if (tid == 0) scale_sh = 1.0 / sqrt(sum * dx2);
+    }
+  }
+  // spectrum side: with WL the thread serves column tid / TT as its thread ji, else column c as thread j
+  const int ji = WL ? tid % E::TT : j;
+  const int cs = WL ? tid / E::TT : c;
+  Cx<T>* const seqi = reinterpret_cast<Cx<T>*>(smem_raw) + cs * NP;
+  const T a = ax.w * ep[env].gpe_omega * (ax.c_first + T(col0 + cs) * ax.c_step);
+  // One line operator.  Two in a row need no barrier in between: the last exchange of the inverse reads, and the
+  // first exchange of the next forward transform writes, only the thread's OWN stage-0 positions of the image.
+  auto line_op = [&](auto scaled) {
+    if constexpr (WL)
+      E::template dif_split<-1>(v, seq, j, seqi, ji, tw);
+    else
+      E::template dif<-1, false>(v, seq, tw, j);
+    T scale = T(1);
+    if constexpr (decltype(scaled)::value) scale = (T)scale_sh;  // read behind the transform's barrier
+#pragma unroll
+    for (int sl = 0; sl < PTS; ++sl) {
+      const int fr = E::freq(ji, sl);
+      Cx<T> m = rot_mult<T>(kin[fr], a, fr, N, ax.sr, ax.si);
+      if constexpr (decltype(scaled)::value) {
+        m.re *= scale;
+        m.im *= scale;
+      }
+      v[sl] = cmul(v[sl], m);
+      if constexpr (kOneFactorAtATime<T, PTS>) __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (WL)
+      E::template dit_split<+1>(v, seqi, ji, seq, j, tw);
+    else
+      E::template dit<+1, false>(v, seq, tw, j);
+  };
+  if constexpr (PRE) line_op(std::true_type{});
+  if constexpr (POST) {
+#pragma unroll
+    for (int m = 0; m < PTS; ++m) db[E::natural(j, m) * ny + c] = v[m].re * v[m].re + v[m].im * v[m].im;
+    line_op(std::false_type{});
+  }
+#pragma unroll
+  for (int m = 0; m < PTS; ++m) gb[E::natural(j, m) * ny + c] = v[m];
+}
+
+// ---- pointwise kernels of the library path (any grid) ------------------------------------------------------------
+
+// psi[b][ix][iy] *= kin[k] * rotation factor (* the norm scale of environment b).  AXIS 0: the field is transformed
+// along x, k = ix, the line's coordinate is y of iy; AXIS 1: transformed along y, k = iy, coordinate x of ix.
+template <typename T, int AXIS, bool SCALED>
+__global__ __launch_bounds__(256) void rot_mul_kernel(Cx<T>* __restrict__ psi, const Cx<T>* __restrict__ kin,
+                                                      const EnvParams<T>* __restrict__ ep, const RotAxis<T> ax, int nx,
+                                                      int ny, const double* __restrict__ partial, int nblocks, double dx2) {
+  const int b = blockIdx.y;
+  const int64_t cells = (int64_t)nx * ny;
+  Cx<T>* const pb = psi + (int64_t)b * cells;
+  T scale = T(1);
+  if constexpr (SCALED) {
+    double s = 0.0;
+    for (int q = 0; q < nblocks; ++q) s += partial[(int64_t)b * nblocks + q];
+    scale = (T)(1.0 / sqrt(s * dx2));
+  }
+  const T om = ax.w * ep[b].gpe_omega;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (int64_t)gridDim.x * 256) {
+    const int ix = (int)(i / ny), iy = (int)(i - (int64_t)ix * ny);
+    const int k = AXIS == 0 ? ix : iy, n = AXIS == 0 ? nx : ny, line = AXIS == 0 ? iy : ix;
+    Cx<T> m = rot_mult<T>(kin[k], om * (ax.c_first + T(line) * ax.c_step), k, n, ax.sr, ax.si);
+    m.re *= scale;
+    m.im *= scale;
+    pb[i] = cmul(pb[i], m);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rot_density_kernel(const Cx<T>* __restrict__ psi, T* __restrict__ d, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const Cx<T> v = psi[i];
+    d[i] = v.re * v.re + v.im * v.im;
+  }
+}
+
+// psi *= exp(b tau);  partial[b][block] = sum |psi|^2 (fixed partition, fixed order)
+template <typename T>
+__global__ __launch_bounds__(256) void rot_b_kernel(Cx<T>* __restrict__ psi, const T* __restrict__ dens,
+                                                    const T* __restrict__ pot, int64_t pot_stride,
+                                                    const EnvParams<T>* __restrict__ ep, T tr, T ti, int64_t cells,
+                                                    double* __restrict__ partial) {
+  const int b = blockIdx.y;
+  Cx<T>* const pb = psi + (int64_t)b * cells;
+  const T* const db = dens + (int64_t)b * cells;
+  const T* const vb = pot ? pot + (int64_t)b * pot_stride : nullptr;
+  const T kk = ep[b].gpe_k;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (int64_t)gridDim.x * 256) {
+    const T w = (vb ? vb[i] : T(0)) + kk * db[i];
+    T sn, cs;
+    sincos_t<T>(w * tr, &sn, &cs);
+    const T mag = (ti == T(0)) ? T(1) : exp_t<T>(w * ti);
+    const Cx<T> r = cmul(pb[i], Cx<T>{mag * cs, -mag * sn});
+    pb[i] = r;
+    acc += (double)(r.re * r.re + r.im * r.im);
+  }
+  __shared__ double sh[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(int64_t)b * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------
+
+constexpr int kLibNormBlocks = 64;
+
+bool rot_size_ok(int n) { return n == 64 || n == 128 || n == 256 || n == 512 || n == 1024; }
+
+template <typename T, int N>
+constexpr int rot_row_lines() { return 256 / RegFft<T, N>::TT; }
+int rot_row_lines_rt(int ny) { return 256 / (ny / (ny > 512 ? 16 : 8)); }
+
+template <typename T>
+RotAxis<T> rot_axis(const pdeopt_ctx* ctx, int axis, std::complex<double> half_tau) {
+  const pdeopt_problem& p = ctx->prob;
+  RotAxis<T> a;
+  if (axis == 0) {  // lines along x: -Omega y (2 pi i kx)
+    a.w = (T)(-2.0 * M_PI / ((double)p.nx * p.hx));
+    a.c_first = (T)ctx->rot_y_first;
+    a.c_step = (T)p.hy;
+  } else {          // lines along y: +Omega x (2 pi i ky)
+    a.w = (T)(2.0 * M_PI / ((double)p.ny * p.hy));
+    a.c_first = (T)ctx->rot_x_first;
+    a.c_step = (T)p.hx;
+  }
+  a.sr = (T)half_tau.real();
+  a.si = (T)half_tau.imag();
+  return a;
+}
+
+template <typename T>
+int upload_kinetic(pdeopt_ctx* ctx, void** dev, int n, double h, std::complex<double> half_tau) {
+  std::vector<Cx<T>> t((size_t)n);
+  for (int f = 0; f < n; ++f) {
+    const int ks = f < (n + 1) / 2 ? f : f - n;
+    const double k = (double)ks / ((double)n * h);
+    const std::complex<double> ik(0.0, 2.0 * M_PI * k);
+    const std::complex<double> e = std::exp(half_tau * std::complex<double>(0.0, 0.5) * ik * ik) / (double)n;
+    t[f] = Cx<T>{(T)e.real(), (T)e.imag()};
+  }
+  int rc = ensure_buffer(ctx, dev, t.size() * sizeof(Cx<T>));
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(*dev, t.data(), t.size() * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+template <typename T, int N>
+int launch_rot_row(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {
+  const pdeopt_problem& p = ctx->prob;
+  const AuxField& pot = ctx->aux[PDEOPT_AUX_GPE_POTENTIAL];
+  constexpr int F = rot_row_lines<T, N>();
+  const size_t lds = (size_t)F * RegFft<T, N>::NP * sizeof(Cx<T>);
+  auto kern = rot_row_kernel<T, N>;
+  int rc = allow_lds(ctx, kern, lds);
+  if (rc) return rc;
+  const int64_t cells = (int64_t)p.nx * p.ny, w0 = w.lo;
+  const int blocks = (int)((int64_t)w.n * p.nx / F);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (Cx<T>*)ctx->Y + w0 * cells,
+                     (const T*)gr.dens + w0 * cells, pot.dev ? (const T*)pot.dev + (pot.per_env ? w0 * cells : 0) : nullptr,
+                     pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, w.lo), (const Cx<T>*)gr.tw_y,
+                     (const Cx<T>*)gr.kin_y, (T)tau.real(), (T)tau.imag(), rot_axis<T>(ctx, 1, 0.5 * tau), p.nx,
+                     gr.partial + w0 * gr.partial_per_env);
+  ctx->n_stage_launches++;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+// fp64 at N = 1024 runs JOIN as LAST + FIRST (3 passes per step): that one JOIN instantiation does not fit the
+// register file (28 bytes of scratch per lane at 256 threads), every other one does
+template <typename T, int N>
+constexpr bool rot_join_fits() { return !(sizeof(T) == 8 && N == 1024); }
+
+template <typename T, int N, bool PRE, bool POST>
+int launch_rot_col(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {
+  if constexpr (PRE && POST && !rot_join_fits<T, N>()) {
+    const int rc = launch_rot_col<T, N, true, false>(ctx, w, gr, tau);
+    return rc ? rc : launch_rot_col<T, N, false, true>(ctx, w, gr, tau);
+  }
+  const pdeopt_problem& p = ctx->prob;
+  constexpr int C = rot_cols<T, N>();
+  const int64_t cells = (int64_t)p.nx * p.ny, w0 = w.lo;
+  const size_t lds = (size_t)C * RegFft<T, N>::NP * sizeof(Cx<T>);
+  if constexpr (!(PRE && POST) || rot_join_fits<T, N>()) {
+    auto kern = rot_col_kernel<T, N, C, PRE, POST>;
+    int rc = allow_lds(ctx, kern, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * N / reg_default_pts<N>()), lds, w.stream,
+                       (Cx<T>*)ctx->Y + w0 * cells, (T*)gr.dens + w0 * cells, env_params<T>(ctx, w.lo),
+                       (const Cx<T>*)gr.tw_x, (const Cx<T>*)gr.kin_x, rot_axis<T>(ctx, 0, 0.5 * tau), p.ny,
+                       (const double*)gr.partial + w0 * gr.partial_per_env, gr.partial_per_env,
+                       ctx->strang_dx * ctx->strang_dx);
+    ctx->n_stage_launches++;
+    PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  }
+  return PDEOPT_OK;
+}
+
+#define PDEOPT_ROT_SIZES(X) X(64) X(128) X(256) X(512) X(1024)
+
+template <typename T>
+int rot_row_dispatch(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {
+  switch (ctx->prob.ny) {
+#define X(NN) case NN: return launch_rot_row<T, NN>(ctx, w, gr, tau);
+    PDEOPT_ROT_SIZES(X)
+#undef X
+    default: return fail(ctx, PDEOPT_EINVAL, "rotating split step: ny=%d is not covered", ctx->prob.ny);
+  }
+}
+template <typename T, bool PRE, bool POST>
+int rot_col_dispatch(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {
+  switch (ctx->prob.nx) {
+#define X(NN) case NN: return launch_rot_col<T, NN, PRE, POST>(ctx, w, gr, tau);
+    PDEOPT_ROT_SIZES(X)
+#undef X
+    default: return fail(ctx, PDEOPT_EINVAL, "rotating split step: nx=%d is not covered", ctx->prob.nx);
+  }
+}
+
+// the same step on rocFFT's 1-D plans, whole batch, one substep
+template <typename T>
+int rot_library_step(pdeopt_ctx* ctx, GpeRot& gr, std::complex<double> tau) {
+  const pdeopt_problem& p = ctx->prob;
+  const int64_t cells = (int64_t)p.nx * p.ny, total = cells * p.batch;
+  const AuxField& pot = ctx->aux[PDEOPT_AUX_GPE_POTENTIAL];
+  const int g1 = (int)std::min<int64_t>(4096, (cells + 255) / 256);
+  const dim3 mgrid(g1, p.batch);
+  const EnvParams<T>* ep = env_params<T>(ctx, 0);
+  const RotAxis<T> ax = rot_axis<T>(ctx, 0, 0.5 * tau), ay = rot_axis<T>(ctx, 1, 0.5 * tau);
+  const double dx2 = ctx->strang_dx * ctx->strang_dx;
+  Cx<T>* const y = (Cx<T>*)ctx->Y;
+  int rc;
+  auto lx = [&](bool scaled) -> int {
+    int r = spectral_c2c_axis(ctx, 0, true, y);
+    if (r) return r;
+    if (scaled)
+      hipLaunchKernelGGL((rot_mul_kernel<T, 0, true>), mgrid, dim3(256), 0, ctx->stream, y, (const Cx<T>*)gr.kin_x, ep, ax,
+                         p.nx, p.ny, (const double*)gr.partial, kLibNormBlocks, dx2);
+    else
+      hipLaunchKernelGGL((rot_mul_kernel<T, 0, false>), mgrid, dim3(256), 0, ctx->stream, y, (const Cx<T>*)gr.kin_x, ep,
+                         ax, p.nx, p.ny, (const double*)nullptr, 0, dx2);
+    return spectral_c2c_axis(ctx, 0, false, y);
+  };
+  auto ly = [&]() -> int {
+    int r = spectral_c2c_axis(ctx, 1, true, y);
+    if (r) return r;
+    hipLaunchKernelGGL((rot_mul_kernel<T, 1, false>), mgrid, dim3(256), 0, ctx->stream, y, (const Cx<T>*)gr.kin_y, ep, ay,
+                       p.nx, p.ny, (const double*)nullptr, 0, dx2);
+    return spectral_c2c_axis(ctx, 1, false, y);
+  };
+  hipLaunchKernelGGL(rot_density_kernel<T>, dim3((int)std::min<int64_t>(4096, (total + 255) / 256)), dim3(256), 0,
+                     ctx->stream, (const Cx<T>*)y, (T*)gr.dens, total);
+  if ((rc = lx(false))) return rc;
+  if ((rc = ly())) return rc;
+  hipLaunchKernelGGL(rot_b_kernel<T>, dim3(kLibNormBlocks, p.batch), dim3(256), 0, ctx->stream, y, (const T*)gr.dens,
+                     (const T*)pot.dev, pot.per_env ? cells : (int64_t)0, ep, (T)tau.real(), (T)tau.imag(), cells,
+                     gr.partial);
+  if ((rc = ly())) return rc;
+  if ((rc = lx(true))) return rc;
+  ctx->n_stage_launches += 6;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int strang_rot_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+  if (!ctx->gpe_rot) ctx->gpe_rot = new GpeRot();
+  GpeRot& gr = *ctx->gpe_rot;
+  const pdeopt_problem& p = ctx->prob;
+  const int64_t cells = (int64_t)p.nx * p.ny;
+  const bool fused = ctx->opt_kernel_path != 1 && rot_size_ok(p.nx) && rot_size_ok(p.ny);
+  int rc;
+  if (!gr.dens) {
+    if (fused) {
+      if ((rc = upload_table<T>(ctx, &gr.tw_x, p.nx))) return rc;
+      if ((rc = upload_table<T>(ctx, &gr.tw_y, p.ny))) return rc;
+    }
+    if ((rc = ensure_buffer(ctx, &gr.dens, (size_t)cells * p.batch * sizeof(T)))) return rc;
+    const size_t np = (size_t)std::max(p.nx, kLibNormBlocks);
+    if ((rc = ensure_buffer(ctx, (void**)&gr.partial, sizeof(double) * (size_t)p.batch * np))) return rc;
+  }
+  if (fused && !gr.tw_x) {  // the library path ran first (PDEOPT_OPT_KERNEL_PATH changed in between)
+    if ((rc = upload_table<T>(ctx, &gr.tw_x, p.nx))) return rc;
+    if ((rc = upload_table<T>(ctx, &gr.tw_y, p.ny))) return rc;
+  }
+  gr.partial_per_env = fused ? p.nx / rot_row_lines_rt(p.ny) : kLibNormBlocks;
+  const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
+  if (!gr.valid || gr.key_dt != dt || gr.key_tr != ctx->ts_re || gr.key_ti != ctx->ts_im || gr.key_hx != p.hx ||
+      gr.key_hy != p.hy) {
+    if ((rc = upload_kinetic<T>(ctx, &gr.kin_x, p.nx, p.hx, 0.5 * tau))) return rc;
+    if ((rc = upload_kinetic<T>(ctx, &gr.kin_y, p.ny, p.hy, 0.5 * tau))) return rc;
+    gr.valid = true;
+    gr.key_dt = dt;
+    gr.key_tr = ctx->ts_re;
+    gr.key_ti = ctx->ts_im;
+    gr.key_hx = p.hx;
+    gr.key_hy = p.hy;
+  }
+  if (!fused) {
+    for (int64_t s = 0; s < n; ++s)
+      if ((rc = rot_library_step<T>(ctx, gr, tau))) return rc;
+    ctx->last_kernel = "strang_rot_rocfft_1d";
+    return PDEOPT_OK;
+  }
+  // environments are independent: the n-step pipeline group by group, a group's wavefunction + density sized to
+  // stay in the Infinity Cache between its passes (as the non-rotating fused step)
+  int group = p.batch;
+  if (ctx->opt_group_envs > 0)
+    group = (int)std::min<int64_t>(ctx->opt_group_envs, p.batch);
+  else if (ctx->opt_group_envs == 0 && n > 1)
+    group = cache_group(p.batch, (size_t)cells * (sizeof(Cx<T>) + sizeof(T)), 192ull << 20, false);
+  auto first = [&](const Window& w) -> int { return rot_col_dispatch<T, false, true>(ctx, w, gr, tau); };
+  auto substep = [&](const Window& w, int64_t s, int&) -> int {
+    int r;
+    if ((r = rot_row_dispatch<T>(ctx, w, gr, tau))) return r;
+    return s + 1 < n ? rot_col_dispatch<T, true, true>(ctx, w, gr, tau) : rot_col_dispatch<T, true, false>(ctx, w, gr, tau);
+  };
+  if ((rc = run_groups(ctx, group, false, 0, n, first, substep))) return rc;
+  ctx->last_kernel = "strang_rot_fused_lds_fft";
+  return PDEOPT_OK;
+}
+
+}  // namespace
+
+int advance_strang_rot(pdeopt_ctx* ctx, double, double dt, int64_t n) {
+  if (!ctx->rot_set)
+    return fail(ctx, PDEOPT_ESTATE, "the rotating-frame split step needs pdeopt_set_gpe_rotation (Omega and the mesh origin)");
+  if (has_time_aux(ctx, PDEOPT_AUX_GPE_POTENTIAL))
+    return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step takes a static potential");
+  if (ctx->n_spots)
+    return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step has no light spots");
+  return with_dtype(ctx, [&](auto t) { return strang_rot_t<decltype(t)>(ctx, dt, n); });
+}
+
+void gpe_rot_invalidate(pdeopt_ctx* ctx) {
+  if (ctx->gpe_rot) ctx->gpe_rot->valid = false;
+}
+
+void gpe_rot_destroy(pdeopt_ctx* ctx) {
+  GpeRot* gr = ctx->gpe_rot;
+  if (!gr) return;
+  void* bufs[] = {gr->tw_x, gr->tw_y, gr->kin_x, gr->kin_y, gr->dens, gr->partial};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  delete gr;
+  ctx->gpe_rot = nullptr;
+}
+
+}  // namespace pdeopt

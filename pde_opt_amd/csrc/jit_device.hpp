@@ -26,6 +26,7 @@ struct Geo {
 struct EnvParams {
   T kappa, gpe_k, kscale, imex_scale;
   T mu[16], mob[16], fe[16];
+  T gpe_omega;
 };
 struct ClosureSpec {
   int kind, flags, n;

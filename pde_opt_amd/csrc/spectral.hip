@@ -11,6 +11,7 @@
 // rocFFT transforms are unnormalised; the 1/N of ifft is folded into the spectral multipliers,
 // and the per-environment normalisation scalar of psi3 is folded into the second spectral
 // multiply (the FFT is linear), which saves one pass over the field.
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <mutex>
@@ -40,6 +41,11 @@ struct Spectral {
   void* hbuf = nullptr;    // hermitian half-spectrum work field
   void* hmult = nullptr;   // multiplier on the half-spectrum
   int64_t half_cells = 0;  // complex elements of one half-spectrum
+  // batched 1-D complex plans along one axis of a [batch][nx][ny] field (the rotating-frame split step on grids the
+  // hand-written passes do not cover): [0] along x (stride ny, one environment per execution), [1] along y
+  rocfft_plan ax_fwd[2] = {nullptr, nullptr}, ax_inv[2] = {nullptr, nullptr};
+  rocfft_execution_info ax_info = nullptr;
+  void* ax_work = nullptr;
   // cache key of `mult` / `hmult`
   int mult_kind = -1;
   double mult_dt = NAN, mult_A = NAN, mult_tr = NAN, mult_ti = NAN;
@@ -136,6 +142,47 @@ int real_fft_exec(pdeopt_ctx* ctx, bool forward, void* in, void* out) {
   void* ib[1] = {in};
   void* ob[1] = {out};
   PDEOPT_FFT_CHECK(ctx, rocfft_execute(forward ? sp.r2c : sp.c2r, ib, ob, sp.rinfo));
+  return PDEOPT_OK;
+}
+
+// 1-D plans of spectral_c2c_axis.  Along y the lines are contiguous: one plan over all nx * batch of them.  Along x a
+// line has stride ny and the ny lines of an environment start one element apart; the next environment's do not
+// continue that pattern, so the plan covers one environment and is executed once per environment.
+int ensure_axis_plans(pdeopt_ctx* ctx) {
+  if (!ctx->spectral) ctx->spectral = new Spectral();
+  Spectral& sp = *ctx->spectral;
+  if (sp.ax_info) return PDEOPT_OK;
+  std::call_once(g_rocfft_once, [] { rocfft_setup(); });
+  const pdeopt_problem& p = ctx->prob;
+  const rocfft_precision prec = p.dtype == PDEOPT_F32 ? rocfft_precision_single : rocfft_precision_double;
+  size_t wmax = 0;
+  for (int axis = 0; axis < 2; ++axis) {
+    size_t len[1] = {(size_t)(axis == 0 ? p.nx : p.ny)};
+    size_t stride[1] = {(size_t)(axis == 0 ? p.ny : 1)};
+    const size_t dist = axis == 0 ? 1 : (size_t)p.ny;
+    const size_t count = axis == 0 ? (size_t)p.ny : (size_t)p.nx * p.batch;
+    rocfft_plan_description desc = nullptr;
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_description_create(&desc));
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_description_set_data_layout(desc, rocfft_array_type_complex_interleaved,
+                                                                  rocfft_array_type_complex_interleaved, nullptr, nullptr,
+                                                                  1, stride, dist, 1, stride, dist));
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_create(&sp.ax_fwd[axis], rocfft_placement_inplace,
+                                             rocfft_transform_type_complex_forward, prec, 1, len, count, desc));
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_create(&sp.ax_inv[axis], rocfft_placement_inplace,
+                                             rocfft_transform_type_complex_inverse, prec, 1, len, count, desc));
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_description_destroy(desc));
+    size_t w1 = 0, w2 = 0;
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_get_work_buffer_size(sp.ax_fwd[axis], &w1));
+    PDEOPT_FFT_CHECK(ctx, rocfft_plan_get_work_buffer_size(sp.ax_inv[axis], &w2));
+    wmax = std::max(wmax, std::max(w1, w2));
+  }
+  PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_create(&sp.ax_info));
+  if (wmax) {
+    int rc = ensure_buffer(ctx, &sp.ax_work, wmax);
+    if (rc) return rc;
+    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.ax_info, sp.ax_work, wmax));
+  }
+  PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_stream(sp.ax_info, ctx->stream));
   return PDEOPT_OK;
 }
 
@@ -743,6 +790,20 @@ int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf) {
   return rc ? rc : fft_exec(ctx, forward, buf);
 }
 
+int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf) {
+  int rc = ensure_axis_plans(ctx);
+  if (rc) return rc;
+  Spectral& sp = *ctx->spectral;
+  const pdeopt_problem& p = ctx->prob;
+  rocfft_plan plan = forward ? sp.ax_fwd[axis] : sp.ax_inv[axis];
+  const size_t env_bytes = (size_t)p.nx * p.ny * 2 * ctx->esize;
+  for (int b = 0; b < (axis == 0 ? p.batch : 1); ++b) {
+    void* in[1] = {static_cast<char*>(buf) + (size_t)b * env_bytes};
+    PDEOPT_FFT_CHECK(ctx, rocfft_execute(plan, in, nullptr, sp.ax_info));
+  }
+  return PDEOPT_OK;
+}
+
 int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<double>>& out) {
   return fetch_complex_aux(ctx, which, out);
 }
@@ -760,12 +821,20 @@ void spectral_invalidate(pdeopt_ctx* ctx) {
   if (ctx->spectral) ctx->spectral->mult_kind = -1;
   strang_fused_invalidate(ctx);
   gpe_adjoint_invalidate(ctx);
+  gpe_rot_invalidate(ctx);
 }
 
 void spectral_destroy(pdeopt_ctx* ctx) {
   gpe_adjoint_destroy(ctx);
+  gpe_rot_destroy(ctx);
   Spectral* sp = ctx->spectral;
   if (!sp) return;
+  for (int a = 0; a < 2; ++a) {
+    if (sp->ax_fwd[a]) rocfft_plan_destroy(sp->ax_fwd[a]);
+    if (sp->ax_inv[a]) rocfft_plan_destroy(sp->ax_inv[a]);
+  }
+  if (sp->ax_info) rocfft_execution_info_destroy(sp->ax_info);
+  if (sp->ax_work) (void)hipFree(sp->ax_work);
   if (sp->r2c) rocfft_plan_destroy(sp->r2c);
   if (sp->c2r) rocfft_plan_destroy(sp->c2r);
   if (sp->rinfo) rocfft_execution_info_destroy(sp->rinfo);

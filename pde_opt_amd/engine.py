@@ -276,6 +276,16 @@ class HipEngine:
         a = np.ascontiguousarray(np.atleast_1d(np.asarray(k, dtype=np.float64)))
         self._check(self._lib.pdeopt_set_env_gpe_k(self._h, int(env_first), a.shape[0], a.ctypes.data_as(C.c_void_p)))
 
+    def set_gpe_rotation(self, omega: float, x_first: float, y_first: float):
+        """rotating-frame GPE: rotation frequency of every environment and the coordinates of cell (0, 0) -- the line
+        operators of the rotating split step are evaluated in-kernel from them (``pdeopt_set_gpe_rotation``)"""
+        self._check(self._lib.pdeopt_set_gpe_rotation(self._h, float(omega), float(x_first), float(y_first)))
+
+    def set_env_gpe_omega(self, env_first: int, omega):
+        """per-environment rotation frequency (after ``set_gpe_rotation``)"""
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(omega, dtype=np.float64)))
+        self._check(self._lib.pdeopt_set_env_gpe_omega(self._h, int(env_first), a.shape[0], a.ctypes.data_as(C.c_void_p)))
+
     def set_integrator_params(self, imex_A=0.5, time_scale=1.0, strang_dx=1.0):
         ts = complex(time_scale)
         self._check(

@@ -33,7 +33,7 @@ DEFAULT_CHUNK_BYTES = 1 << 30
 GPE_CONTROL_SUPPORT = ("gradients of the GPE support GPE2DTSControl whose lights is a GaussianSpots (evaluated in-kernel: "
                        "time_dependent is not False) with StrangSplitting and ConstantStepSize; the optimisation variables are "
                        "the spots' numbers (opt_parameters = {'lights': GaussianSpots}), not k, e, trap_factor or another "
-                       "lights callable")
+                       "lights callable; the rotating-frame GPE2DTSRot has no gradients")
 
 
 class SpotMap:
@@ -86,11 +86,23 @@ class SpotMap:
         return np.broadcast_to(np.asarray(w, dtype=np.float64), (self.n_spots, 7)).reshape(-1).copy()
 
 
+ROTATING_GRADIENTS = ("gradients of the rotating-frame GPE (GPE2DTSRot + RotatingStrangSplitting) are not implemented: "
+                      "control_gradient, optimize and train cover it in no form yet (the adjoint of the "
+                      "alternating-direction split step does not exist); solve, diffeqsolve and PDEEnv do")
+
+
+def reject_rotating(equation_type, solver_type=None):
+    """``NotImplementedError`` for any gradient of the rotating-frame GPE; needs no engine and no GPU"""
+    if getattr(equation_type, "_rotating_frame", False) or getattr(solver_type, "integrator", None) == L.INT_STRANG_ROT:
+        raise NotImplementedError(ROTATING_GRADIENTS)
+
+
 def reject_unsupported(equation_type, solver_type, parameters=None, opt_names=None):
     """``NotImplementedError`` for what the GPE gradient does not cover; needs no engine and no GPU"""
     from .numerics.equations.gross_pitaevskii import GPE2DTSControl
     from .numerics.solvers import StrangSplitting
 
+    reject_rotating(equation_type, solver_type)
     if equation_type is not GPE2DTSControl:
         raise NotImplementedError(f"{equation_type.__name__}: " + GPE_CONTROL_SUPPORT)
     if solver_type is not StrangSplitting:

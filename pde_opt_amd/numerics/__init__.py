@@ -7,6 +7,7 @@ from .equations import (
     BaseEquation,
     CahnHilliard2DPeriodic,
     GPE2DTSControl,
+    GPE2DTSRot,
 )
 from .functions import (
     ChemicalPotentialLegendrePolynomials,
@@ -22,5 +23,6 @@ from .solvers import (
     SaveAt,
     SemiImplicitFourierSpectral,
     StrangSplitting,
+    RotatingStrangSplitting,
     Tsit5,
 )

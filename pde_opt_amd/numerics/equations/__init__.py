@@ -2,7 +2,7 @@
 
 from .advection_diffusion import AdvectionDiffusion2D
 from .base_eq import BaseEquation, TimeSplittingEquation
-from .gross_pitaevskii import GPE2DTSControl
+from .gross_pitaevskii import GPE2DTSControl, GPE2DTSRot
 from .phase_field import AllenCahn2DPeriodic, CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
 from .smoothed_boundary import AllenCahn2DSmoothedBoundary, CahnHilliard2DSmoothedBoundary
 
@@ -16,4 +16,5 @@ __all__ = [
     "CahnHilliard2DSmoothedBoundary",
     "AdvectionDiffusion2D",
     "GPE2DTSControl",
+    "GPE2DTSRot",
 ]

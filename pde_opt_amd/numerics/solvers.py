@@ -102,9 +102,49 @@ class StrangSplitting(AbstractSolver):
     def order(self, terms=None):
         return 1
 
+    @classmethod
+    def check_equation_type(cls, equation_type):
+        if getattr(equation_type, "_rotating_frame", False):
+            raise ValueError(f"{equation_type.__name__} publishes the operator pair A_terms of the alternating-direction "
+                             f"splitting, not one A_term: integrate it with RotatingStrangSplitting, not {cls.__name__}")
+
     def configure_engine(self, engine, equation):
         engine.set_integrator_params(time_scale=complex(self.time_scale), strang_dx=float(self.dx))
         engine.set_aux(L.AUX_GPE_A_TERM, self.A_term, key=getattr(self.A_term, "key", None))
+
+
+@dataclasses.dataclass
+class RotatingStrangSplitting(AbstractSolver):
+    """Alternating-direction split step of the rotating-frame GPE (``GPE2DTSRot``), new relative to the reference, which
+    publishes the operator pair ``A_terms`` but no solver for it.  With tau = dt * time_scale and
+    ``L_x(s) v = ifft_x[exp(s A_x) fft_x v]``, ``L_y`` alike (transforms along ONE axis; ``(A_x, A_y) = A_terms``):
+
+        psi1 = L_y(tau/2) L_x(tau/2) psi0;   b = B(psi0);   psi2 = psi1 exp(b tau)
+        psi3 = psi2 / sqrt(dx^2 sum |psi2|^2);   psi4 = L_x(tau/2) L_y(tau/2) psi3
+
+    ``b`` from the state before the half step and the renormalisation of every step are ``StrangSplitting``'s, so
+    with ``omega = 0`` this is that solver's step with the kinetic ``A_term``.  DESIGN.md section 4.10."""
+
+    dx: float
+    time_scale: complex = 1.0
+    A_terms: Any = None  # pulled off the equation like every required attribute; the kernels form the pair themselves
+
+    required_equation_attrs = ["A_terms", "dx"]
+    integrator = L.INT_STRANG_ROT
+
+    def order(self, terms=None):
+        return 1
+
+    @classmethod
+    def check_equation_type(cls, equation_type):
+        if not getattr(equation_type, "_rotating_frame", False):
+            raise ValueError(f"{cls.__name__} integrates the rotating-frame operator pair of GPE2DTSRot; "
+                             f"{equation_type.__name__} does not publish one: "
+                             + ("integrate it with StrangSplitting" if hasattr(equation_type, "A_term")
+                                else "it has no split-step form"))
+
+    def configure_engine(self, engine, equation):
+        engine.set_integrator_params(time_scale=complex(self.time_scale), strang_dx=float(self.dx))
 
 
 # ---- step-size controllers / save specification (diffrax stand-ins) ---------------------------

@@ -192,6 +192,7 @@ class PDEModel:
         ``opt_parameters = {"mu": torch.nn.Module}`` (CahnHilliard2DPeriodic, ``method="mse"``): BFGS over the module's
         flattened parameters with the reverse-mode gradient of ``mse_backward``, for up to ``fit.MAX_DENSE_BFGS_PARAMS``
         parameters; the returned dict holds the trained module (the one passed in, updated in place)."""
+        _reject_rotating(self)
         fit.reject_unsupported(self)
         if method not in ("least_squares", "mse"):
             raise ValueError(f"method must be 'least_squares' or 'mse', got {method!r}")
@@ -252,6 +253,7 @@ class PDEModel:
         (``pdeopt_sens_contract``).  Trial points of the line search are forward solves.  The equations, solvers and
         closures are those of ``train``.  Returns ``{**fitted, **other_parameters}``; the objective after every
         accepted step is in ``last_optimize_history``."""
+        _reject_rotating(self)
         if _is_gpe(self.equation_type):
             return self._optimize_gpe(objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters, weights,
                                       lambda_reg, max_steps)
@@ -383,6 +385,13 @@ class PDEModel:
             return J + reg.reg(p), grad + reg.reg_grad(p)
 
         return value_and_grad, value, pmap
+
+
+def _reject_rotating(model) -> None:
+    """gradients of the rotating-frame GPE are out of scope: say so before anything else does"""
+    from .gpe_control import reject_rotating
+
+    reject_rotating(model.equation_type, model.solver_type)
 
 
 def _is_gpe(equation_type) -> bool:

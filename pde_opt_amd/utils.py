@@ -3,6 +3,9 @@
 
 def check_equation_solver_compatibility(solver_type, equation_type):
     """``ValueError`` when the equation class lacks an attribute the solver will ask for."""
+    check = getattr(solver_type, "check_equation_type", None)
+    if check is not None:  # a solver that can name the right partner of an equation says so before anything else
+        check(equation_type)
     wanted = getattr(solver_type, "required_equation_attrs", None)
     if not wanted:
         return
