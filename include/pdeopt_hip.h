@@ -335,6 +335,35 @@ int pdeopt_observe_u8_device(pdeopt_ctx* ctx, double lo, double hi, int env_firs
  * when only the counts are wanted (24 bytes per environment instead of the field). */
 int pdeopt_detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int env_first, int env_count,
                            int32_t* host_winding, int64_t* host_counts);
+/* Energy terms, angular momentum and second moments of the resident GPE wavefunction (Bao & Cai 2012; Bao & Wang
+ * 2006 for the rotating frame), per environment, computed on the device: host_out is [env_count][PDEOPT_GPE_OBS_COUNT].
+ * With psi^x / psi^y the unnormalised transforms along x / y, Px = |psi^x|^2 / nx, Py = |psi^y|^2 / ny, kx / ky the
+ * signed frequencies (cycles per unit length) and h^2 = hx hy:
+ *   NORM  h^2 sum |psi|^2          E_POT  h^2 sum V |psi|^2          E_INT  h^2 sum k/2 |psi|^4
+ *   E_KIN h^2 [sum 1/2 (2 pi kx)^2 Px + sum 1/2 (2 pi ky)^2 Py]
+ *   L_Z   h^2 [sum x (2 pi ky) Py - sum y (2 pi kx) Px]              X2, Y2  h^2 sum x^2 |psi|^2, h^2 sum y^2 |psi|^2
+ * (entry 7 is reserved and zero).  V is the potential a substep starting at local time t would use: the GPE_POTENTIAL
+ * aux field (a source registered through pdeopt_set_aux_time_fn is sampled at t) plus the spots of pdeopt_set_gpe_spots
+ * at t; k per environment as pdeopt_set_env_gpe_k left it.  Cell (i, j) sits at x_first + i hx, y_first + j hy: the
+ * coordinates of cell (0, 0) are ALWAYS arguments of this call (pdeopt_set_gpe_spots with n_spots = 0 forgets the
+ * ones it was given, and a problem with neither spots nor rotation never had any).  The caller derives
+ *   energy = (E_KIN + E_POT + E_INT - Omega L_Z) / NORM,   mu = (E_KIN + E_POT + 2 E_INT - Omega L_Z) / NORM.
+ * The state is not modified; sums in fp64 in a fixed order, no atomics: a repeat gives identical bits, and a
+ * sub-range gives the rows of the full call.  Any grid: axes of length 64 .. 1024 (powers of two) run hand-written
+ * transforms, others rocFFT.  PDEOPT_EINVAL: an equation other than the GPE, the padded layout, a range outside the
+ * batch. */
+enum {
+  PDEOPT_GPE_OBS_NORM = 0,
+  PDEOPT_GPE_OBS_E_KIN = 1,
+  PDEOPT_GPE_OBS_E_POT = 2,
+  PDEOPT_GPE_OBS_E_INT = 3,
+  PDEOPT_GPE_OBS_L_Z = 4,
+  PDEOPT_GPE_OBS_X2 = 5,
+  PDEOPT_GPE_OBS_Y2 = 6,
+  PDEOPT_GPE_OBS_COUNT = 8
+};
+int pdeopt_gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
+                           double* host_out);
 
 /* ---- domain decomposition of one large field (BASELINE config 5; no reference counterpart) -----
  * With PDEOPT_OPT_HALO_LAYOUT = 4 a ctx holds one rank's tile.  Per RK4 substep the caller runs

@@ -8,6 +8,7 @@ constructing an engine / environment / model does, and fails loudly otherwise.
 
 from ._lib import HipUnavailableError, PdeoptError
 from .engine import HipEngine
+from .gpe_observables import OBSERVABLE_NAMES, GpeObservables, GroundState
 from .integrate import Solution, diffeqsolve
 from .numerics.closures import ClosureDesc, UnsupportedClosureError, as_closure, polynomial
 from .numerics.domains import Domain
@@ -47,7 +48,7 @@ from .pde_model import PDEModel
 __all__ = [
     "PDEModel", "PDEEnv", "VectorPDEEnv", "HipEngine", "diffeqsolve", "Solution",
     "BaseEquation", "AllenCahn2DPeriodic", "CahnHilliard2DPeriodic", "AdvectionDiffusion2D", "GPE2DTSControl",
-    "GPE2DTSRot", "RotatingStrangSplitting",
+    "GPE2DTSRot", "RotatingStrangSplitting", "OBSERVABLE_NAMES", "GpeObservables", "GroundState",
     "AllenCahn2DSmoothedBoundary", "CahnHilliard2DSmoothedBoundary", "CahnHilliard3DPeriodic",
     "Domain", "Shape", "LegendrePolynomialExpansion", "DiffusionLegendrePolynomials", "ChemicalPotentialLegendrePolynomials",
     "GaussianSpot", "GaussianSpots",

@@ -822,6 +822,18 @@ int pdeopt_detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int e
   return detect_vortices(ctx, amp_thresh, tol, env_first, env_count, host_winding, host_counts);
 }
 
+int pdeopt_gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
+                           double* host_out) {
+  if (!ctx || !host_out) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  if (ctx->prob.equation != PDEOPT_EQ_GPE)
+    return fail(ctx, PDEOPT_EINVAL, "gpe_observables needs a complex (GPE) state");
+  if (ctx->halo) return fail(ctx, PDEOPT_EINVAL, "gpe_observables is not available in the padded layout");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return env_count ? gpe_observables(ctx, t, env_first, env_count, x_first, y_first, host_out) : PDEOPT_OK;
+}
+
 int pdeopt_tsit5_trial(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol,
                        double* err_norm) {
   if (!ctx) return PDEOPT_EINVAL;

@@ -827,6 +827,7 @@ void spectral_invalidate(pdeopt_ctx* ctx) {
 void spectral_destroy(pdeopt_ctx* ctx) {
   gpe_adjoint_destroy(ctx);
   gpe_rot_destroy(ctx);
+  gpe_obs_destroy(ctx);
   Spectral* sp = ctx->spectral;
   if (!sp) return;
   for (int a = 0; a < 2; ++a) {

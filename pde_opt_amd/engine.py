@@ -60,6 +60,7 @@ class HipEngine:
         self._aux_keys: dict = {}
         self._callback_error = None
         self._cnns: list = []  # open NativeCNN handles: closed before the ctx they belong to
+        self.gpe_origin: Optional[tuple] = None  # coordinates of cell (0, 0) of a GPE problem (gpe_observables)
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -163,6 +164,7 @@ class HipEngine:
             self.problem = None
             raise
         self.problem = p
+        self.gpe_origin = None
         self.dtype = L.np_dtype(p.dtype)
         self.batch = int(batch)
         comps = (2,) if equation == L.EQ_GPE else ((int(nz),) if equation == L.EQ_CAHN_HILLIARD_3D else ())
@@ -264,6 +266,8 @@ class HipEngine:
             raise ValueError(f"spot tables have shape (envs, n_spots, 7), got {a.shape}")
         self._check(self._lib.pdeopt_set_gpe_spots(self._h, int(env_first), a.shape[0], a.shape[1],
                                                    a.ctypes.data_as(C.c_void_p), float(x_first), float(y_first)))
+        if a.shape[1]:
+            self.gpe_origin = (float(x_first), float(y_first))
 
     def set_env_imex_scale(self, env_first: int, sigma):
         """IMEX: environment b integrates with ``sigma[b] x`` the uploaded ``fourier_symbol`` (a per-environment
@@ -280,6 +284,7 @@ class HipEngine:
         """rotating-frame GPE: rotation frequency of every environment and the coordinates of cell (0, 0) -- the line
         operators of the rotating split step are evaluated in-kernel from them (``pdeopt_set_gpe_rotation``)"""
         self._check(self._lib.pdeopt_set_gpe_rotation(self._h, float(omega), float(x_first), float(y_first)))
+        self.gpe_origin = (float(x_first), float(y_first))
 
     def set_env_gpe_omega(self, env_first: int, omega):
         """per-environment rotation frequency (after ``set_gpe_rotation``)"""
@@ -515,6 +520,21 @@ class HipEngine:
             self._h, float(amp_thresh), float(tol), int(env_first), int(n),
             winding.ctypes.data_as(C.c_void_p) if want_winding else None, counts.ctypes.data_as(C.c_void_p)))
         return counts, winding
+
+    def gpe_observables(self, t: float = 0.0, env_first: int = 0, env_count: Optional[int] = None) -> np.ndarray:
+        """Energy terms, angular momentum and second moments of the resident GPE state (``pdeopt_gpe_observables``),
+        summed on the device: ``(envs, 8)`` float64 in the order of ``gpe_observables.OBSERVABLE_NAMES`` (the last
+        entry is reserved), 64 bytes per environment instead of the field.  ``t``: the local time the potential is
+        taken at, as a substep starting there would.  The mesh needs the coordinates of cell (0, 0): ``gpe_origin``,
+        which ``set_gpe_rotation`` and ``set_gpe_spots`` (with spots) leave behind and a caller may set itself."""
+        if self.gpe_origin is None:
+            raise ValueError("gpe_observables needs the coordinates of cell (0, 0): set engine.gpe_origin = (x_first, y_first) "
+                             "(set_gpe_rotation and set_gpe_spots record them)")
+        n = self.batch - env_first if env_count is None else env_count
+        out = np.zeros((n, L.GPE_OBS_COUNT), dtype=np.float64)
+        self._check(self._lib.pdeopt_gpe_observables(self._h, float(t), int(env_first), int(n), float(self.gpe_origin[0]),
+                                                     float(self.gpe_origin[1]), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def tsit5_trial(self, t: float, dt: float, rtol: float, atol: float) -> np.ndarray:
         err = np.empty(self.batch, dtype=np.float64)

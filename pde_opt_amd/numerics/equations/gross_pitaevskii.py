@@ -103,6 +103,7 @@ class GPE2DTSControl(TimeSplittingEquation):
         return depends_on_time(self.control, t, t_end)
 
     def _engine_upload(self, engine, t: float = 0.0, t_end=None):
+        engine.gpe_origin = self._cell0()  # the observables' mesh (HipEngine.gpe_observables)
         if self._spots_in_kernel(t_end):
             engine.set_aux(L.AUX_GPE_POTENTIAL, self.trap_potential())
             tab = self.lights.table(len(self.lights.spots))
@@ -121,6 +122,7 @@ class GPE2DTSControl(TimeSplittingEquation):
         eq0 = eqs[0]
         if any(e.kinetic != eq0.kinetic for e in eqs):
             raise ValueError("all environments of a batch must share A_term (the `kinetic` switch)")
+        engine.gpe_origin = eq0._cell0()
         engine.set_env_gpe_k(0, [float(e.k) for e in eqs])
         same_trap = all(e.e == eq0.e and e.trap_factor == eq0.trap_factor for e in eqs)
         shared = same_trap and all(e.lights is eq0.lights for e in eqs)

@@ -268,7 +268,19 @@ class _EnvShard:
         if rem > 0:
             eng.advance(solver.integrator, rem, 1, n_full * env.numeric_dt)
         rewards = None
-        if isinstance(env.device_reward, tuple):
+        if isinstance(env.device_reward, tuple) and env.device_reward[0] == "gpe":
+            # ("gpe", name): an observable of the GPE state, summed on the device (64 bytes per environment come back);
+            # the potential is the one a substep starting at the end of this step would use
+            from .gpe_observables import GpeObservables, equation_weights
+
+            if isinstance(eqs, _ScalarControlBatch):
+                omega, kappa = equation_weights([eq0])
+                if eqs.name == "omega":
+                    omega = np.asarray(eqs.values, dtype=np.float64)
+            else:
+                omega, kappa = equation_weights(eqs)
+            rewards = GpeObservables.from_raw(eng.gpe_observables(float(env.step_dt)), omega, kappa)[env.device_reward[1]]
+        elif isinstance(env.device_reward, tuple):
             # ("vortices", amp_thresh, tol): rl_utils.detect_vortices' num_vortices per environment, counted on the
             # device (pde_opt/rl_utils.py:19-84): 24 bytes per environment cross PCIe instead of the wavefunction
             amp, tol = (tuple(env.device_reward[1:]) + (0.0, 0.5))[:2]
@@ -327,8 +339,9 @@ class VectorPDEEnv:
 
     ``reward`` / observations: ``reward_function`` and ``state_to_observation_func`` are applied
     per environment on host copies unless ``device_reward`` names an on-device reduction
-    (``"var"``, ``"mean"``, ``"min"``, ``"max"``, or ``("vortices", amp_thresh, tol)`` = the number of quantised
-    vortices of a GPE state, ``rl_utils.detect_vortices`` on the device), which avoids the D2H of full fields;
+    (``"var"``, ``"mean"``, ``"min"``, ``"max"``, ``("vortices", amp_thresh, tol)`` = the number of quantised
+    vortices of a GPE state, ``rl_utils.detect_vortices`` on the device, or ``("gpe", name)`` = an observable of a GPE
+    state, ``name`` in ``gpe_observables.OBSERVABLE_NAMES + ("energy", "mu")``), which avoids the D2H of full fields;
     ``device_observation=(lo, hi)`` forms the uint8 image observations of the declared
     observation space on the GPU (1 byte per cell crosses PCIe instead of 4 or 8);
     ``device_observation=("probes", cells)`` returns the state at the listed grid cells instead (sensor-style
@@ -373,7 +386,13 @@ class VectorPDEEnv:
             raise ValueError("observations_on_device needs device_observation=(lo, hi)")
         if device_observation is not None and isinstance(device_observation[0], str) and device_observation[0] != "probes":
             raise ValueError(f"unknown device observation {device_observation[0]!r}")
-        if isinstance(device_reward, tuple) and device_reward[0] != "vortices":
+        if isinstance(device_reward, tuple) and device_reward[0] == "gpe":
+            from .gpe_observables import DERIVED_NAMES, OBSERVABLE_NAMES, reject_unsupported
+
+            if len(device_reward) != 2 or device_reward[1] not in OBSERVABLE_NAMES + DERIVED_NAMES:
+                raise ValueError(f"unknown device reward {device_reward!r} (\"gpe\" takes one of {OBSERVABLE_NAMES + DERIVED_NAMES})")
+            reject_unsupported(equation_type)
+        elif isinstance(device_reward, tuple) and device_reward[0] != "vortices":
             raise ValueError(f"unknown device reward {device_reward[0]!r}")
         if isinstance(device_reward, str) and device_reward not in self._RED:
             raise ValueError(f"unknown device reward {device_reward!r} (one of {sorted(self._RED)} or (\"vortices\", amp, tol))")

@@ -68,6 +68,31 @@ class PDEModel:
         )
         return sol.ys
 
+    # -- observables of the GPE and the ground-state solve (pde_opt_amd.gpe_observables) ---------------------------------
+    def observables(self, parameters, state, t=0.0):
+        """Norm, energy terms, angular momentum, second moments, ``energy`` and ``mu`` of a GPE state (``GpeObservables``,
+        every entry ``(B,)``), summed on the GPU: ``state`` is one ``(nx, ny, 2)`` field or a batch, ``parameters`` one
+        dict shared by the batch or a sequence with one dict per state; the potential is taken at local time ``t`` as a
+        substep starting there would.  ``GPE2DTSControl`` and ``GPE2DTSRot`` only.  After a ``solve``,
+        ``model._engine.gpe_observables()`` reads the resident final state without an upload."""
+        from . import gpe_observables
+
+        return gpe_observables.observables(self, parameters, state, t)
+
+    def ground_state(self, parameters, y0, dt, tol=1e-8, max_steps=100_000, check_every=25, solver_parameters=None):
+        """Relax ``y0`` (one state or a batch; ``parameters`` as in ``observables``) in imaginary time
+        (``time_scale=-1j``; any other ``solver_parameters["time_scale"]`` raises ``ValueError``) until the energy per
+        particle stands still: blocks of ``check_every`` steps of ``dt``, one ``advance`` and one ``gpe_observables``
+        call each (64 bytes per environment come back); environment b is converged when
+        ``|energy_now - energy_prev| / (check_every dt) <= tol``.  The loop ends when every environment is, or at
+        ``max_steps`` with ``converged=False`` where it is not.  Returns ``GroundState(state, observables, steps,
+        converged, history)``.  A ``lights`` that depends on time is frozen at ``t = 0``, for the steps and for the energy
+        alike: a ground state belongs to one potential.  The split step renormalises BETWEEN its half steps, so the returned state has
+        ``norm = 1 + O(dt)``; ``energy`` and ``mu`` are already divided by it."""
+        from . import gpe_observables
+
+        return gpe_observables.ground_state(self, parameters, y0, dt, tol, max_steps, check_every, solver_parameters)
+
     # -- fitting (pde_model.py:138-460) ----------------------------------------------------------------------------
     def regularization(self, parameters, weights, lambda_reg):
         """``lambda sum_i w_i p_i^2`` over the coefficient arrays named in ``weights``; None leaves are ignored"""
