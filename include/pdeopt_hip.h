@@ -605,6 +605,20 @@ int pdeopt_cnn_destroy(pdeopt_cnn* cnn);
  * potential registered through pdeopt_set_aux_time_fn, overlapping lam_dev / psi0_dev / grad. */
 int pdeopt_gpe_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* psi0_dev, void* lam_dev, double* grad);
 
+/* ---- the discrete adjoint of one substep of the rotating-frame split step (PDEOPT_INT_STRANG_ROT): the reverse-mode
+ * gradient of a scalar objective of the solution over the interaction strength k, the trap anisotropy e and the
+ * rotation frequency Omega.  psi0_dev: the state the substep (size dt) STARTED from; lam_dev: the cotangent
+ * dJ/dRe + i dJ/dIm of the state it ended in, replaced by the cotangent of psi0 (both device fields
+ * [batch][nx][ny][2] in the problem dtype).  grad: [batch][3] doubles in the order (k, e, Omega), device OR host
+ * memory, ADDED into; every environment uses its own k, Omega and potential and gets its own sums.  "d/de" is the
+ * derivative along (x^2 - y^2) / 2 of the uploaded potential: that of e in V = ((1 + e) x^2 + (1 - e) y^2) / 2, the
+ * potential GPE2DTSRot uploads.  15 batched 1-D transforms (rocFFT: every grid the forward step takes) and 11 passes
+ * over the field per call, five field-sized work buffers kept with the ctx; reductions in a fixed order, no atomics:
+ * a repeat gives identical bits.  A device grad keeps the call asynchronous on the ctx's stream; a host grad
+ * synchronises.  Refused (PDEOPT_EINVAL / PDEOPT_ESTATE): an equation other than the GPE, pdeopt_set_gpe_rotation not
+ * called, spots set, a potential registered through pdeopt_set_aux_time_fn, overlapping lam_dev / psi0_dev / grad. */
+int pdeopt_gpe_rot_adjoint_step(pdeopt_ctx* ctx, double dt, const void* psi0_dev, void* lam_dev, double* grad);
+
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);
 int pdeopt_timer_start(pdeopt_ctx* ctx);           /* hipEventRecord on the ctx stream */

@@ -128,6 +128,7 @@ struct Sens;         // forward-mode sensitivity configuration + Gauss-Newton bu
 struct GpeAdjoint;   // work fields + multiplier of the Strang step's adjoint (gpe_adjoint.hip)
 struct GpeRot;       // tables + work fields of the rotating-frame ADI split step (gpe_rot.hip)
 struct GpeObs;       // tables + partial sums of the GPE observables (gpe_obs.hip)
+struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint (gpe_rot_adjoint.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -244,6 +245,7 @@ struct pdeopt_ctx {
   double rot_x_first = 0.0, rot_y_first = 0.0;
   pdeopt::GpeRot* gpe_rot = nullptr;
   pdeopt::GpeObs* gpe_obs = nullptr;
+  pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
 };
 
 namespace pdeopt {
@@ -424,6 +426,9 @@ int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf);
 int advance_strang_rot(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
 void gpe_rot_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_destroy(pdeopt_ctx* ctx);
+// gpe_rot_adjoint.hip: the adjoint of that step; its buffers live and die with the spectral state too
+void gpe_rot_adjoint_invalidate(pdeopt_ctx* ctx);
+void gpe_rot_adjoint_destroy(pdeopt_ctx* ctx);
 // gpe_obs.hip: energy terms, angular momentum and moments of the resident GPE state, [env_count][PDEOPT_GPE_OBS_COUNT]
 // doubles; its buffers live and die with the spectral state
 int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,

@@ -32,6 +32,7 @@
 #include "fft_lds.hpp"
 #include "fft_reg.hpp"
 #include "split_step_util.hpp"
+#include "gpe_rot_line.hpp"
 
 namespace pdeopt {
 
@@ -49,23 +50,7 @@ struct GpeRot {
 
 namespace {
 
-// one axis's line operator: theta = a k_signed with a = w Omega coord, w = -/+ 2 pi / (N h) (the sign of the
-// rotation term: - for lines along x, + for lines along y), s = tau / 2 = sr + i si
-template <typename T>
-struct RotAxis {
-  T w, c_first, c_step, sr, si;
-};
-
-// kin * exp(i theta s) = kin * exp(-theta si) (cos(theta sr) + i sin(theta sr)),  theta = a * fftfreq index of f
-template <typename T>
-__device__ __forceinline__ Cx<T> rot_mult(Cx<T> kin, T a, int f, int n, T sr, T si) {
-  const int ks = f < (n + 1) / 2 ? f : f - n;
-  const T th = a * T(ks);
-  T sn, cs;
-  sincos_t<T>(th * sr, &sn, &cs);
-  const T mag = (si == T(0)) ? T(1) : exp_t<T>(-th * si);
-  return cmul(kin, Cx<T>{mag * cs, mag * sn});
-}
+// RotAxis, rot_mult, rot_axis, upload_kinetic: gpe_rot_line.hpp (shared with the adjoint, gpe_rot_adjoint.hip)
 
 // fp64 and 16-point threads: one factor's sincos at a time (interleaved, their temporaries cost more registers than
 // the line itself)
@@ -298,41 +283,6 @@ bool rot_size_ok(int n) { return n == 64 || n == 128 || n == 256 || n == 512 || 
 template <typename T, int N>
 constexpr int rot_row_lines() { return 256 / RegFft<T, N>::TT; }
 int rot_row_lines_rt(int ny) { return 256 / (ny / (ny > 512 ? 16 : 8)); }
-
-template <typename T>
-RotAxis<T> rot_axis(const pdeopt_ctx* ctx, int axis, std::complex<double> half_tau) {
-  const pdeopt_problem& p = ctx->prob;
-  RotAxis<T> a;
-  if (axis == 0) {  // lines along x: -Omega y (2 pi i kx)
-    a.w = (T)(-2.0 * M_PI / ((double)p.nx * p.hx));
-    a.c_first = (T)ctx->rot_y_first;
-    a.c_step = (T)p.hy;
-  } else {          // lines along y: +Omega x (2 pi i ky)
-    a.w = (T)(2.0 * M_PI / ((double)p.ny * p.hy));
-    a.c_first = (T)ctx->rot_x_first;
-    a.c_step = (T)p.hx;
-  }
-  a.sr = (T)half_tau.real();
-  a.si = (T)half_tau.imag();
-  return a;
-}
-
-template <typename T>
-int upload_kinetic(pdeopt_ctx* ctx, void** dev, int n, double h, std::complex<double> half_tau) {
-  std::vector<Cx<T>> t((size_t)n);
-  for (int f = 0; f < n; ++f) {
-    const int ks = f < (n + 1) / 2 ? f : f - n;
-    const double k = (double)ks / ((double)n * h);
-    const std::complex<double> ik(0.0, 2.0 * M_PI * k);
-    const std::complex<double> e = std::exp(half_tau * std::complex<double>(0.0, 0.5) * ik * ik) / (double)n;
-    t[f] = Cx<T>{(T)e.real(), (T)e.imag()};
-  }
-  int rc = ensure_buffer(ctx, dev, t.size() * sizeof(Cx<T>));
-  if (rc) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(*dev, t.data(), t.size() * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return PDEOPT_OK;
-}
 
 template <typename T, int N>
 int launch_rot_row(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {

@@ -502,6 +502,13 @@ class HipEngine:
         self._check(self._lib.pdeopt_gpe_adjoint_step(self._h, float(t0), float(dt), C.c_void_p(psi0_ptr), C.c_void_p(lam_ptr),
                                                       C.c_void_p(grad_ptr)))
 
+    def gpe_rot_adjoint_step(self, dt: float, psi0_ptr: int, lam_ptr: int, grad_ptr: int):
+        """the adjoint of one substep of the rotating-frame split step (``pdeopt_gpe_rot_adjoint_step``): ``lam`` goes
+        from the cotangent of the substep's end state to that of its start state ``psi0`` in place, the gradient block
+        ``(batch, 3)`` of doubles in the order (k, e, omega) (device or host memory) is added into"""
+        self._check(self._lib.pdeopt_gpe_rot_adjoint_step(self._h, float(dt), C.c_void_p(psi0_ptr), C.c_void_p(lam_ptr),
+                                                          C.c_void_p(grad_ptr)))
+
     def state_device_array(self) -> "DeviceArray":
         """The state field itself as a ``DeviceArray`` (batch,) + state_shape in the engine's dtype: valid until the
         next ``configure`` with another shape; ``advance`` updates it in place (synchronise with ``sync()``)."""

@@ -14,6 +14,11 @@ chunk run again and held before its sweep).  A chunk holds at most ``PDEOPT_GPE_
 Covered: ``GPE2DTSControl`` whose ``lights`` is a ``GaussianSpots`` evaluated in-kernel, ``StrangSplitting`` with
 ``ConstantStepSize``, fp32 and fp64, one state or a batch sharing the spots.  torch (device tensors for the held states
 and cotangents) is imported when a solver is built, not with the package.
+
+The rotating-frame pair ``GPE2DTSRot`` + ``RotatingStrangSplitting`` has its own backward substep,
+``pdeopt_gpe_rot_adjoint_step`` (csrc/gpe_rot_adjoint.hip): the gradient over k, e and omega of every environment and
+over the start state.  ``RotControlSolver`` drives it with the same sweep (``GpeControlSolver._sweep``: schedule, cotangent
+split, chunked recomputation, chunk cap); ``PDEModel.rotation_gradient`` / ``optimize_rotation`` are its public entries.
 """
 
 from __future__ import annotations
@@ -33,7 +38,7 @@ DEFAULT_CHUNK_BYTES = 1 << 30
 GPE_CONTROL_SUPPORT = ("gradients of the GPE support GPE2DTSControl whose lights is a GaussianSpots (evaluated in-kernel: "
                        "time_dependent is not False) with StrangSplitting and ConstantStepSize; the optimisation variables are "
                        "the spots' numbers (opt_parameters = {'lights': GaussianSpots}), not k, e, trap_factor or another "
-                       "lights callable; the rotating-frame GPE2DTSRot has no gradients")
+                       "lights callable; the rotating-frame GPE2DTSRot has its own entries, rotation_gradient and optimize_rotation")
 
 
 class SpotMap:
@@ -86,9 +91,13 @@ class SpotMap:
         return np.broadcast_to(np.asarray(w, dtype=np.float64), (self.n_spots, 7)).reshape(-1).copy()
 
 
-ROTATING_GRADIENTS = ("gradients of the rotating-frame GPE (GPE2DTSRot + RotatingStrangSplitting) are not implemented: "
-                      "control_gradient, optimize and train cover it in no form yet (the adjoint of the "
-                      "alternating-direction split step does not exist); solve, diffeqsolve and PDEEnv do")
+ROTATING_GRADIENTS = ("control_gradient, optimize and train do not cover the rotating-frame GPE (GPE2DTSRot + "
+                      "RotatingStrangSplitting): its gradients over k, e and omega and over the start state are "
+                      "PDEModel.rotation_gradient, its optimisation over them PDEModel.optimize_rotation (the adjoint of the "
+                      "alternating-direction split step, pde_opt_amd.gpe_control.RotControlSolver)")
+
+ROTATION_GRADIENT_SUPPORT = ("rotation_gradient and optimize_rotation support GPE2DTSRot with RotatingStrangSplitting and "
+                             "ConstantStepSize; the optimisation variables are a non-empty subset of k, e and omega")
 
 
 def reject_rotating(equation_type, solver_type=None):
@@ -151,10 +160,11 @@ class GpeControlSolver:
             return int(self.chunk_bytes)
         return int(os.environ.get(CHUNK_BYTES_ENV, DEFAULT_CHUNK_BYTES))
 
-    def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
-        """``(grad (B, S, 7), lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys`` ``(len(ts), B, nx, ny, 2)`` of the saved
-        solution: ``grad`` is the library's block (per environment; last entry d/d inv_two_w2), ``lam0`` is ``dJ/dy0``.
-        Both fp64 on the host; the sweep itself runs in the dtype of ``y0s``."""
+    def _sweep(self, configure, integrator, y0s, ts, dt0, cotangents, grad_tail, adjoint_step):
+        """The backward sweep both GPE adjoints share: ``configure(engine)`` sets the problem up, the forward pass keeps
+        one state per chunk, every chunk is run again and held, and ``adjoint_step(engine, t0, dt, psi0_ptr, lam_ptr,
+        grad_ptr)`` takes ``lam`` back one substep while it adds into the device block ``grad`` ``(B,) + grad_tail``.
+        Returns ``(grad, lam0)``, fp64 on the host."""
         torch = self.torch
         eng = self.engine
         ts = np.asarray(ts, dtype=np.float64)
@@ -167,11 +177,8 @@ class GpeControlSolver:
             for k, g in ((i - 1, g_prev), (i, g_cur)):
                 if g is not None:
                     cot[k] = g if k not in cot else cot[k] + g
-        S = len(equation.lights.spots)
         with self._ordered(), torch.no_grad():
-            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem())
-            equation._engine_upload(eng, float(ts[0]), float(ts[-1]))
-            solver.configure_engine(eng, equation)
+            configure(eng)
             eng.set_state(y0s)
             Y = eng.state_device_array().torch()
             up = lambda g: torch.as_tensor(np.ascontiguousarray(g)).to(device=Y.device, dtype=Y.dtype)
@@ -182,9 +189,9 @@ class GpeControlSolver:
                 if i % chunk == 0:
                     starts[i] = Y.clone()
                 if i < first[-1]:
-                    eng.advance(solver.integrator, steps[i], 1, t_of(i))
+                    eng.advance(integrator, steps[i], 1, t_of(i))
             lam = up(cot[N]) if N in cot and N > 0 else torch.zeros_like(Y)
-            grad = torch.zeros((y0s.shape[0], S, 7), dtype=torch.float64, device=Y.device)
+            grad = torch.zeros((y0s.shape[0],) + tuple(grad_tail), dtype=torch.float64, device=Y.device)
             self.last_chunks = len(first)
             for s0 in reversed(first):
                 s1 = min(N, s0 + chunk)
@@ -193,13 +200,72 @@ class GpeControlSolver:
                 for s in range(s0, s1):
                     held.append(Y.clone())
                     if s + 1 < s1:
-                        eng.advance(solver.integrator, steps[s], 1, t_of(s))
+                        eng.advance(integrator, steps[s], 1, t_of(s))
                 for s in range(s1 - 1, s0 - 1, -1):
                     psi0 = held.pop()
-                    eng.gpe_adjoint_step(t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(), grad.data_ptr())
+                    adjoint_step(eng, t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(), grad.data_ptr())
                     if s in cot:
                         lam += up(cot[s])
             if N == 0 and 0 in cot:
                 lam += up(cot[0])
             out = grad.cpu().numpy(), lam.double().cpu().numpy()
         return out
+
+    def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
+        """``(grad (B, S, 7), lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys`` ``(len(ts), B, nx, ny, 2)`` of the saved
+        solution: ``grad`` is the library's block (per environment; last entry d/d inv_two_w2), ``lam0`` is ``dJ/dy0``.
+        Both fp64 on the host; the sweep itself runs in the dtype of ``y0s``."""
+        ts = np.asarray(ts, dtype=np.float64)
+
+        def configure(eng):
+            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem())
+            equation._engine_upload(eng, float(ts[0]), float(ts[-1]))
+            solver.configure_engine(eng, equation)
+
+        return self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, (len(equation.lights.spots), 7),
+                           lambda eng, t0, dt, psi0, lam, grad: eng.gpe_adjoint_step(t0, dt, psi0, lam, grad))
+
+
+ROT_NAMES = ("k", "e", "omega")  # the order of the library's gradient block (pdeopt_gpe_rot_adjoint_step)
+
+
+def reject_unsupported_rotation(equation_type, solver_type, opt_names=None, stepsize_controller=None):
+    """``NotImplementedError`` for what the rotating-frame gradient does not cover; needs no engine and no GPU"""
+    from .numerics.solvers import ConstantStepSize, RotatingStrangSplitting
+
+    if not getattr(equation_type, "_rotating_frame", False):
+        raise NotImplementedError(f"{equation_type.__name__}: " + ROTATION_GRADIENT_SUPPORT)
+    if solver_type is not RotatingStrangSplitting:
+        raise NotImplementedError(f"{solver_type.__name__}: " + ROTATION_GRADIENT_SUPPORT)
+    if opt_names is not None and (not set(opt_names) or not set(opt_names) <= set(ROT_NAMES)):
+        raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + ROTATION_GRADIENT_SUPPORT)
+    if stepsize_controller is not None and not isinstance(stepsize_controller, ConstantStepSize):
+        raise NotImplementedError(f"{type(stepsize_controller).__name__}: " + ROTATION_GRADIENT_SUPPORT)
+
+
+class RotControlSolver(GpeControlSolver):
+    """The backward sweeps of the rotating-frame GPE (``pdeopt_gpe_rot_adjoint_step``, csrc/gpe_rot_adjoint.hip): the
+    stream rule, the schedule, the chunked recomputation and ``PDEOPT_GPE_ADJOINT_CHUNK_BYTES`` of
+    ``GpeControlSolver``."""
+
+    def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
+        """``(grad (B, 3), lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys`` ``(len(ts), B, nx, ny, 2)`` of the saved
+        solution: row b of ``grad`` is ``dJ/d(k, e, omega)`` of environment b, ``lam0`` is ``dJ/dy0``.  ``equation`` is
+        one ``GPE2DTSRot`` shared by the batch or a list with one per environment (its own k, e, omega).  Both fp64 on
+        the host; the sweep itself runs in the dtype of ``y0s``.  Constant steps only."""
+        ts = np.asarray(ts, dtype=np.float64)
+        eqs = list(equation) if isinstance(equation, (list, tuple)) else None
+        eq0 = eqs[0] if eqs else equation
+        if eqs is not None and len(eqs) != y0s.shape[0]:
+            raise ValueError(f"{len(eqs)} equations for a batch of {y0s.shape[0]} states")
+
+        def configure(eng):
+            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **eq0._engine_problem())
+            if eqs is None:
+                eq0._engine_upload(eng, float(ts[0]), float(ts[-1]))
+            else:
+                type(eq0)._engine_upload_batch(eng, eqs, float(ts[0]), float(ts[-1]))
+            solver.configure_engine(eng, eq0)
+
+        return self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, (3,),
+                           lambda eng, t0, dt, psi0, lam, grad: eng.gpe_rot_adjoint_step(dt, psi0, lam, grad))

@@ -19,6 +19,9 @@ the equations / solvers / closures ``train`` refuses, raise ``NotImplementedErro
 ``GPE2DTSControl`` + ``StrangSplitting`` with ``GaussianSpots`` as ``lights``: ``control_gradient`` returns the
 reverse-mode gradient of such an objective over the spots' numbers (a discrete adjoint of the Strang step on the GPU,
 ``pde_opt_amd.gpe_control``; csrc/gpe_adjoint.hip) and ``optimize(opt_parameters={"lights": spots})`` drives BFGS with it.
+``GPE2DTSRot`` + ``RotatingStrangSplitting``: ``rotation_gradient`` returns the reverse-mode gradient over ``k``, ``e``,
+``omega`` and the start state (a discrete adjoint of the alternating-direction split step, csrc/gpe_rot_adjoint.hip) and
+``optimize_rotation`` drives BFGS with it; ``control_gradient``, ``optimize`` and ``train`` refuse that pair.
 """
 
 from __future__ import annotations
@@ -367,6 +370,87 @@ class PDEModel:
         p, hist = fit.minimize_bfgs(value_and_grad, value, smap.flatten(opt_parameters["lights"]), max_steps=max_steps)
         self.last_optimize_history = hist
         return {"lights": smap.build(p), **other_parameters}
+
+    # -- gradients of the rotating-frame GPE (pde_opt_amd.gpe_control.RotControlSolver) -------------------------------
+    def rot_control_solver(self):
+        """the solver of the rotating-frame GPE's backward sweeps (its ``chunk_bytes`` caps the states a sweep holds)"""
+        if getattr(self, "_rot_control", None) is None:
+            from .gpe_control import RotControlSolver
+
+            self._rot_control = RotControlSolver(self.device)
+        return self._rot_control
+
+    def rotation_gradient(self, objective_function, y0, ts, parameters, solver_parameters=None, dt0=0.000001,
+                          per_environment=False, stepsize_controller=None):
+        """``(J, {"k": ..., "e": ..., "omega": ...}, lam0)`` of ``J = objective_function(solve(parameters, y0, ts, ...))``
+        for ``GPE2DTSRot`` + ``RotatingStrangSplitting``: the derivatives of ``J`` with respect to the interaction
+        strength, the trap anisotropy and the rotation frequency (scalars; ``(B,)`` arrays, one entry per state of a
+        batch, with ``per_environment=True``; summed in order otherwise) and ``lam0 = dJ/dy0`` in the shape of ``y0``
+        (``(N, M, 2)`` or ``(B, N, M, 2)``).  The objective takes the forms of ``optimize``; ``ys`` is the array ``solve``
+        returns, bit for bit.  A discrete adjoint of the solve on the GPU (csrc/gpe_rot_adjoint.hip), constant steps only.
+
+        Because ``lam0`` comes back, segments with different ``omega`` chain: solve the segments forward, then call this
+        on the last one with the real objective and on each earlier one with the linear objective ``<lam0 of the next
+        segment, ys[-1]>`` -- the gradient of a piecewise-constant rotation schedule."""
+        from . import gpe_control
+
+        gpe_control.reject_unsupported_rotation(self.equation_type, self.solver_type, stepsize_controller=stepsize_controller)
+        y0 = np.asarray(y0)
+        if y0.dtype not in (np.float32, np.float64):
+            y0 = y0.astype(np.float64)
+        ts = np.asarray(ts, dtype=np.float64)
+        objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
+        if y0.ndim not in (3, 4) or tuple(y0.shape[-3:]) != tuple(self.domain.points) + (2,):
+            raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points) + (2,)} or (B,) + that")
+        equation = self.equation_type(domain=self.domain, **parameters)
+        solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+        ys = self.solve(parameters, y0, ts, solver_parameters, dt0=dt0)
+        J, g = objective.value_and_grad(ys)
+        single = y0.ndim == 3
+        cot = g[:, None] if single else g
+        grad, lam0 = self.rot_control_solver().gradient(equation, solver, y0[None] if single else y0, ts, float(dt0), cot)
+        if not per_environment:
+            tot = np.zeros(grad.shape[1:])
+            for row in grad:
+                tot = tot + row
+            grad = tot
+        out = {name: (grad[..., j].copy() if per_environment else float(grad[j])) for j, name in enumerate(gpe_control.ROT_NAMES)}
+        return J, out, (lam0[0] if single else lam0)
+
+    def optimize_rotation(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters=None,
+                          weights=None, lambda_reg=0.0, max_steps=100, dt0=0.000001, stepsize_controller=None):
+        """Minimise ``objective_function(solve(...)) + lambda_reg sum_n weights[n] p_n^2`` over the numbers in
+        ``opt_parameters``, any non-empty subset of ``{"k", "e", "omega"}`` of ``GPE2DTSRot`` (the rest fixed in
+        ``other_parameters``), with BFGS (``fit.minimize_bfgs``) on the gradient of ``rotation_gradient``; trial points
+        of the line search are forward solves.  Returns ``{**fitted, **other_parameters}``; the objective after every
+        accepted step is in ``last_optimize_history``."""
+        from . import gpe_control
+
+        other_parameters, weights = other_parameters or {}, weights or {}
+        gpe_control.reject_unsupported_rotation(self.equation_type, self.solver_type, opt_names=opt_parameters or {},
+                                                stepsize_controller=stepsize_controller)
+        if y0 is None or ts is None:
+            raise ValueError("optimize_rotation needs y0 and ts")
+        y0 = np.asarray(y0)
+        objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
+        names = [n for n in gpe_control.ROT_NAMES if n in opt_parameters]
+        w = np.array([float(weights.get(n, 0.0)) for n in names])
+        lam = float(lambda_reg)
+
+        def params_of(p):
+            return {**other_parameters, **{n: float(v) for n, v in zip(names, p)}}
+
+        def value(p):
+            return objective.value(self.solve(params_of(p), y0, ts, solver_parameters, dt0=dt0)) + lam * float(np.sum(w * p * p))
+
+        def value_and_grad(p):
+            J, grad, _ = self.rotation_gradient(objective, y0, ts, params_of(p), solver_parameters, dt0=dt0)
+            return J + lam * float(np.sum(w * p * p)), np.array([grad[n] for n in names]) + 2.0 * lam * w * p
+
+        p0 = np.array([float(opt_parameters[n]) for n in names], dtype=np.float64)
+        p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
+        self.last_optimize_history = hist
+        return params_of(p)
 
     def _objective_functions(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters, weights,
                              lambda_reg):
