@@ -227,6 +227,11 @@ int pdeopt_set_env_gpe_k(pdeopt_ctx* ctx, int env_first, int env_count, const do
 int pdeopt_set_gpe_rotation(pdeopt_ctx* ctx, double omega, double x_first, double y_first);
 /* per-environment Omega (after pdeopt_set_gpe_rotation, which also resets every environment to its omega) */
 int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, const double* omega);
+/* per-environment rate of change of Omega: the step of PDEOPT_INT_STRANG_ROT that starts at local time t (the t of
+ * pdeopt_advance's substep, t0 + s dt) uses Omega(t) = omega + rate t in all four of its line operators.
+ * pdeopt_set_gpe_rotation resets every rate to 0.  With light spots (pdeopt_set_gpe_spots) or a nonzero rate the step
+ * runs its stirred kernels (csrc/gpe_rot_stir.hip); pdeopt_gpe_rot_adjoint_step refuses both. */
+int pdeopt_set_env_gpe_omega_rate(pdeopt_ctx* ctx, int env_first, int env_count, const double* rate);
 /* shared (per_env = 0: [nx][ny]) or per-environment (per_env = 1: [batch][nx][ny]) auxiliary
  * field, host pointer, element type = problem dtype (complex = 2 elements).  Replaces a time-dependent
  * source registered with pdeopt_set_aux_time_fn for the same field. */

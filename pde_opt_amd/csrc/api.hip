@@ -110,6 +110,7 @@ void fill_env_params(pdeopt_ctx* ctx) {
     e[b].kscale = T(1);
     e[b].imex_scale = T(1);
     e[b].gpe_omega = T(0);
+    e[b].gpe_omega_rate = T(0);
     for (int k = 0; k < kMaxCoef; ++k) {
       e[b].mu[k] = k < p.mu.n ? T(p.mu.coef[k]) : T(0);
       e[b].mob[k] = k < p.mob.n ? T(p.mob.coef[k]) : T(0);
@@ -142,6 +143,16 @@ template <typename T>
 void patch_env_gpe_omega(pdeopt_ctx* ctx, int first, int count, const double* omega, double all) {
   auto* e = reinterpret_cast<EnvParams<T>*>(ctx->env_params_host.data());
   for (int i = 0; i < count; ++i) e[first + i].gpe_omega = T(omega ? omega[i] : all);
+}
+
+// returns whether any environment of the batch has a nonzero rate afterwards
+template <typename T>
+bool patch_env_gpe_omega_rate(pdeopt_ctx* ctx, int first, int count, const double* rate) {
+  auto* e = reinterpret_cast<EnvParams<T>*>(ctx->env_params_host.data());
+  for (int i = 0; i < count; ++i) e[first + i].gpe_omega_rate = T(rate ? rate[i] : 0.0);
+  bool any = false;
+  for (int b = 0; b < ctx->prob.batch; ++b) any = any || e[b].gpe_omega_rate != T(0);
+  return any;
 }
 
 template <typename T>
@@ -408,6 +419,7 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   if ((rc = ensure_buffer(ctx, &ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
   ctx->imex_per_env = false;
   ctx->rot_set = false;
+  ctx->rot_any_rate = false;
   ctx->configured = true;
   return upload_env_params(ctx);
 }
@@ -540,6 +552,7 @@ int pdeopt_set_gpe_rotation(pdeopt_ctx* ctx, double omega, double x_first, doubl
   ctx->rot_x_first = x_first;
   ctx->rot_y_first = y_first;
   with_dtype(ctx, [&](auto t) { patch_env_gpe_omega<decltype(t)>(ctx, 0, ctx->prob.batch, nullptr, omega); });
+  ctx->rot_any_rate = with_dtype(ctx, [&](auto t) { return patch_env_gpe_omega_rate<decltype(t)>(ctx, 0, ctx->prob.batch, nullptr); });
   return upload_env_params(ctx);
 }
 
@@ -550,6 +563,16 @@ int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, cons
   if (ctx->prob.equation != PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "the rotation frequency belongs to the GPE");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   with_dtype(ctx, [&](auto t) { patch_env_gpe_omega<decltype(t)>(ctx, env_first, env_count, omega, 0.0); });
+  return upload_env_params(ctx);
+}
+
+int pdeopt_set_env_gpe_omega_rate(pdeopt_ctx* ctx, int env_first, int env_count, const double* rate) {
+  if (!ctx || !rate) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  if (ctx->prob.equation != PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "the rotation frequency belongs to the GPE");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->rot_any_rate = with_dtype(ctx, [&](auto t) { return patch_env_gpe_omega_rate<decltype(t)>(ctx, env_first, env_count, rate); });
   return upload_env_params(ctx);
 }
 

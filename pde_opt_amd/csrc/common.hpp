@@ -31,6 +31,7 @@ struct EnvParams {
   T mob[kMaxCoef];
   T fe[kMaxCoef];  // free-energy density closure (smoothed-boundary equations)
   T gpe_omega;     // rotation frequency of the rotating-frame GPE (pdeopt_set_gpe_rotation / pdeopt_set_env_gpe_omega)
+  T gpe_omega_rate;  // its rate of change: Omega(t) = gpe_omega + gpe_omega_rate t (pdeopt_set_env_gpe_omega_rate)
 };
 
 // Gaussian light spots of the GPE control field (pdeopt_set_gpe_spots), in the arithmetic type of the path;
@@ -242,6 +243,7 @@ struct pdeopt_ctx {
   pdeopt::GpeAdjoint* gpe_adjoint = nullptr;
   // rotating-frame GPE (pdeopt_set_gpe_rotation): coordinates of cell (0, 0); Omega itself lives in EnvParams
   bool rot_set = false;
+  bool rot_any_rate = false;  // some environment's gpe_omega_rate is not 0: the step runs gpe_rot_stir.hip
   double rot_x_first = 0.0, rot_y_first = 0.0;
   pdeopt::GpeRot* gpe_rot = nullptr;
   pdeopt::GpeObs* gpe_obs = nullptr;

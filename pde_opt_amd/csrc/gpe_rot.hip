@@ -33,29 +33,14 @@
 #include "fft_reg.hpp"
 #include "split_step_util.hpp"
 #include "gpe_rot_line.hpp"
+#include "gpe_rot_step.hpp"
 
 namespace pdeopt {
 
-struct GpeRot {
-  void* tw_x = nullptr;   // twiddle tables exp(-2 pi i n / N) in the problem dtype
-  void* tw_y = nullptr;
-  void* kin_x = nullptr;  // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
-  void* kin_y = nullptr;
-  void* dens = nullptr;   // |psi0|^2, real [batch][nx][ny]
-  double* partial = nullptr;
-  int partial_per_env = 0;
-  double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
-  bool valid = false;
-};
-
 namespace {
 
-// RotAxis, rot_mult, rot_axis, upload_kinetic: gpe_rot_line.hpp (shared with the adjoint, gpe_rot_adjoint.hip)
-
-// fp64 and 16-point threads: one factor's sincos at a time (interleaved, their temporaries cost more registers than
-// the line itself)
-template <typename T, int PTS>
-constexpr bool kOneFactorAtATime = sizeof(T) == 8 || PTS > 8;
+// RotAxis, rot_mult, rot_axis, upload_kinetic: gpe_rot_line.hpp (shared with the adjoint, gpe_rot_adjoint.hip);
+// GpeRot, the pass geometry and rot_density_kernel: gpe_rot_step.hpp (shared with gpe_rot_stir.hip)
 
 // The row pass: lines along y (contiguous), N/PTS threads per line, 256/(N/PTS) lines per workgroup, every line in
 // one wave (the exchanges need no s_barrier).  Ly(tau/2) -> exp(b tau) + norm partial -> Ly(tau/2).
@@ -121,19 +106,6 @@ __global__ __launch_bounds__(256) void rot_row_kernel(Cx<T>* __restrict__ psi, c
   E::template dit<+1>(v, seq, tw, j);
 #pragma unroll
   for (int m = 0; m < PTS; ++m) g[E::natural(j, m)] = v[m];
-}
-
-// Column-pass geometry: C adjacent columns x N/PTS threads per workgroup, the column index fastest across lanes on
-// the global side (strang_fused.hip has the measurements behind 128-byte segments).  Up to N = 512 stages 1.. of a
-// transform run with a column per wave (RegFft::dif_split / dit_split: one workgroup barrier per transform); at
-// N = 1024 the barrier form.  Workgroups of at most 512 (fp32) / 256 (fp64) threads: the JOIN form holds a line's
-// points, the twiddles of a butterfly and a sincos in flight, and at more threads the compiler's register cap
-// (128 VGPRs at 1024 threads) spills the fp64 instantiations to scratch.
-constexpr bool rot_col_wave_local(int n) { return n <= 512; }
-template <typename T, int N>
-constexpr int rot_cols() {
-  constexpr int c = sizeof(T) == 4 ? 16 : 8, cap = sizeof(T) == 4 ? 512 : 256, tt = N / reg_default_pts<N>();
-  return c * tt > cap ? cap / tt : c;
 }
 
 // The column pass: lines along x (stride ny).  PRE: Lx(tau/2) * scale, the second half of a step (scale =
@@ -237,14 +209,6 @@ __global__ __launch_bounds__(256) void rot_mul_kernel(Cx<T>* __restrict__ psi, c
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void rot_density_kernel(const Cx<T>* __restrict__ psi, T* __restrict__ d, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const Cx<T> v = psi[i];
-    d[i] = v.re * v.re + v.im * v.im;
-  }
-}
-
 // psi *= exp(b tau);  partial[b][block] = sum |psi|^2 (fixed partition, fixed order)
 template <typename T>
 __global__ __launch_bounds__(256) void rot_b_kernel(Cx<T>* __restrict__ psi, const T* __restrict__ dens,
@@ -275,14 +239,6 @@ __global__ __launch_bounds__(256) void rot_b_kernel(Cx<T>* __restrict__ psi, con
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-
-constexpr int kLibNormBlocks = 64;
-
-bool rot_size_ok(int n) { return n == 64 || n == 128 || n == 256 || n == 512 || n == 1024; }
-
-template <typename T, int N>
-constexpr int rot_row_lines() { return 256 / RegFft<T, N>::TT; }
-int rot_row_lines_rt(int ny) { return 256 / (ny / (ny > 512 ? 16 : 8)); }
 
 template <typename T, int N>
 int launch_rot_row(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {
@@ -334,8 +290,6 @@ int launch_rot_col(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<do
   }
   return PDEOPT_OK;
 }
-
-#define PDEOPT_ROT_SIZES(X) X(64) X(128) X(256) X(512) X(1024)
 
 template <typename T>
 int rot_row_dispatch(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<double> tau) {
@@ -401,13 +355,15 @@ int rot_library_step(pdeopt_ctx* ctx, GpeRot& gr, std::complex<double> tau) {
   return PDEOPT_OK;
 }
 
+// buffers, twiddles and the kinetic tables of a step of dt (rebuilt when dt, time_scale or the mesh changed)
 template <typename T>
-int strang_rot_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+int rot_prepare_t(pdeopt_ctx* ctx, double dt, bool* fused_out) {
   if (!ctx->gpe_rot) ctx->gpe_rot = new GpeRot();
   GpeRot& gr = *ctx->gpe_rot;
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   const bool fused = ctx->opt_kernel_path != 1 && rot_size_ok(p.nx) && rot_size_ok(p.ny);
+  *fused_out = fused;
   int rc;
   if (!gr.dens) {
     if (fused) {
@@ -435,6 +391,18 @@ int strang_rot_t(pdeopt_ctx* ctx, double dt, int64_t n) {
     gr.key_hx = p.hx;
     gr.key_hy = p.hy;
   }
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int strang_rot_t(pdeopt_ctx* ctx, double dt, int64_t n) {
+  bool fused;
+  int rc = rot_prepare_t<T>(ctx, dt, &fused);
+  if (rc) return rc;
+  GpeRot& gr = *ctx->gpe_rot;
+  const pdeopt_problem& p = ctx->prob;
+  const int64_t cells = (int64_t)p.nx * p.ny;
+  const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
   if (!fused) {
     for (int64_t s = 0; s < n; ++s)
       if ((rc = rot_library_step<T>(ctx, gr, tau))) return rc;
@@ -461,13 +429,19 @@ int strang_rot_t(pdeopt_ctx* ctx, double dt, int64_t n) {
 
 }  // namespace
 
-int advance_strang_rot(pdeopt_ctx* ctx, double, double dt, int64_t n) {
+int gpe_rot_prepare(pdeopt_ctx* ctx, double dt, bool* fused) {
+  return with_dtype(ctx, [&](auto t) { return rot_prepare_t<decltype(t)>(ctx, dt, fused); });
+}
+
+int advance_strang_rot(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   if (!ctx->rot_set)
     return fail(ctx, PDEOPT_ESTATE, "the rotating-frame split step needs pdeopt_set_gpe_rotation (Omega and the mesh origin)");
   if (has_time_aux(ctx, PDEOPT_AUX_GPE_POTENTIAL))
-    return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step takes a static potential");
-  if (ctx->n_spots)
-    return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step has no light spots");
+    return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step takes a static potential plus Gaussian light spots "
+                                    "(pdeopt_set_gpe_spots), no host-sampled potential");
+  // light spots or a rotation ramp: the stirred variants of the passes (gpe_rot_stir.hip); without either, the
+  // kernels below, whose results do not change
+  if (ctx->n_spots || ctx->rot_any_rate) return advance_strang_rot_stir(ctx, t0, dt, n);
   return with_dtype(ctx, [&](auto t) { return strang_rot_t<decltype(t)>(ctx, dt, n); });
 }
 

@@ -385,6 +385,9 @@ int pdeopt_gpe_rot_adjoint_step(pdeopt_ctx* ctx, double dt, const void* psi0_dev
   if (ctx->n_spots)
     return fail(ctx, PDEOPT_EINVAL, "the rotating-frame split step has no light spots: their gradient is "
                                     "pdeopt_gpe_adjoint_step's");
+  if (ctx->rot_any_rate)
+    return fail(ctx, PDEOPT_EINVAL, "the adjoint of the rotating-frame split step takes a constant Omega: an environment has "
+                                    "a nonzero rate (pdeopt_set_env_gpe_omega_rate)");
   if (has_time_aux(ctx, PDEOPT_AUX_GPE_POTENTIAL))
     return fail(ctx, PDEOPT_EINVAL, "a potential registered through pdeopt_set_aux_time_fn is a host callable: the "
                                     "rotating-frame split step takes a static potential");

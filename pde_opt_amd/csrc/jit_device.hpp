@@ -26,7 +26,7 @@ struct Geo {
 struct EnvParams {
   T kappa, gpe_k, kscale, imex_scale;
   T mu[16], mob[16], fe[16];
-  T gpe_omega;
+  T gpe_omega, gpe_omega_rate;
 };
 struct ClosureSpec {
   int kind, flags, n;

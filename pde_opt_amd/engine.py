@@ -291,6 +291,12 @@ class HipEngine:
         a = np.ascontiguousarray(np.atleast_1d(np.asarray(omega, dtype=np.float64)))
         self._check(self._lib.pdeopt_set_env_gpe_omega(self._h, int(env_first), a.shape[0], a.ctypes.data_as(C.c_void_p)))
 
+    def set_env_gpe_omega_rate(self, env_first: int, rate):
+        """per-environment rate of change of the rotation frequency: the step starting at local time t uses
+        ``omega + rate t`` (after ``set_gpe_rotation``, which resets every rate to 0)"""
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(rate, dtype=np.float64)))
+        self._check(self._lib.pdeopt_set_env_gpe_omega_rate(self._h, int(env_first), a.shape[0], a.ctypes.data_as(C.c_void_p)))
+
     def set_integrator_params(self, imex_A=0.5, time_scale=1.0, strang_dx=1.0):
         ts = complex(time_scale)
         self._check(

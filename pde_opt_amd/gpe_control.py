@@ -97,7 +97,8 @@ ROTATING_GRADIENTS = ("control_gradient, optimize and train do not cover the rot
                       "alternating-direction split step, pde_opt_amd.gpe_control.RotControlSolver)")
 
 ROTATION_GRADIENT_SUPPORT = ("rotation_gradient and optimize_rotation support GPE2DTSRot with RotatingStrangSplitting and "
-                             "ConstantStepSize; the optimisation variables are a non-empty subset of k, e and omega")
+                             "ConstantStepSize, without lights and with omega_rate = 0 (a frozen potential and a constant "
+                             "Omega); the optimisation variables are a non-empty subset of k, e and omega")
 
 
 def reject_rotating(equation_type, solver_type=None):
@@ -229,7 +230,7 @@ class GpeControlSolver:
 ROT_NAMES = ("k", "e", "omega")  # the order of the library's gradient block (pdeopt_gpe_rot_adjoint_step)
 
 
-def reject_unsupported_rotation(equation_type, solver_type, opt_names=None, stepsize_controller=None):
+def reject_unsupported_rotation(equation_type, solver_type, opt_names=None, stepsize_controller=None, parameters=None):
     """``NotImplementedError`` for what the rotating-frame gradient does not cover; needs no engine and no GPU"""
     from .numerics.solvers import ConstantStepSize, RotatingStrangSplitting
 
@@ -241,6 +242,11 @@ def reject_unsupported_rotation(equation_type, solver_type, opt_names=None, step
         raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + ROTATION_GRADIENT_SUPPORT)
     if stepsize_controller is not None and not isinstance(stepsize_controller, ConstantStepSize):
         raise NotImplementedError(f"{type(stepsize_controller).__name__}: " + ROTATION_GRADIENT_SUPPORT)
+    if parameters is not None:
+        if parameters.get("lights") is not None:
+            raise NotImplementedError("an equation with lights: " + ROTATION_GRADIENT_SUPPORT)
+        if parameters.get("omega_rate"):
+            raise NotImplementedError(f"omega_rate={parameters['omega_rate']!r}: " + ROTATION_GRADIENT_SUPPORT)
 
 
 class RotControlSolver(GpeControlSolver):

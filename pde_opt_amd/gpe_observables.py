@@ -80,6 +80,19 @@ class GroundState:
     history: np.ndarray
 
 
+GROUND_STATE_SUPPORT = ("ground_state relaxes in ONE potential and ONE rotating frame: it supports omega_rate = 0 and lights "
+                        "that do not depend on time (GaussianSpots with zero rates: a pinning beam, folded into the potential)")
+
+
+def reject_moving_frame(parameters) -> None:
+    """``ValueError`` for parameter sets a ground state does not belong to; needs no engine and no GPU"""
+    for p in ([parameters] if isinstance(parameters, dict) else list(parameters)):
+        if p.get("omega_rate"):
+            raise ValueError(f"omega_rate={p['omega_rate']!r}: " + GROUND_STATE_SUPPORT)
+        if getattr(p.get("lights"), "time_dependent", False):
+            raise ValueError("time-dependent spots: " + GROUND_STATE_SUPPORT)
+
+
 def reject_unsupported(equation_type) -> None:
     """the observables are those of the two GPE classes: say so before an engine exists"""
     from .numerics.equations.gross_pitaevskii import GPE2DTSControl, GPE2DTSRot
@@ -89,9 +102,10 @@ def reject_unsupported(equation_type) -> None:
                                   f"{getattr(equation_type, '__name__', equation_type)} has none")
 
 
-def equation_weights(eqs):
-    """``(omega (B,), kappa)`` of the equations of a batch"""
-    omega = np.asarray([float(getattr(e, "omega", 0.0)) for e in eqs])
+def equation_weights(eqs, t: float = 0.0):
+    """``(omega (B,), kappa)`` of the equations of a batch at local time ``t`` (a ``GPE2DTSRot`` with an ``omega_rate``
+    rotates with ``omega + omega_rate t``)"""
+    omega = np.asarray([float(getattr(e, "omega", 0.0)) + float(getattr(e, "omega_rate", 0.0)) * float(t) for e in eqs])
     kinetic = {bool(getattr(e, "kinetic", True)) for e in eqs}
     if len(kinetic) != 1:
         raise ValueError("all environments of a batch must share A_term (the `kinetic` switch)")
@@ -142,7 +156,7 @@ def observables(model, parameters: Union[Dict[str, Any], Sequence[Dict[str, Any]
     reject_unsupported(model.equation_type)
     yb, _ = _states(model, state)
     eqs = _equations(model, parameters, yb.shape[0])
-    omega, kappa = equation_weights(eqs)
+    omega, kappa = equation_weights(eqs, float(t))
     # t_end = t: a GaussianSpots control stays in its in-kernel form and is evaluated at t on the device
     eng = _load(model, eqs, None, yb, float(t), float(t))
     return GpeObservables.from_raw(eng.gpe_observables(float(t)), omega, kappa)
@@ -151,6 +165,8 @@ def observables(model, parameters: Union[Dict[str, Any], Sequence[Dict[str, Any]
 def ground_state(model, parameters, y0, dt, tol=1e-8, max_steps=100_000, check_every=25, solver_parameters=None) -> GroundState:
     """``PDEModel.ground_state``"""
     reject_unsupported(model.equation_type)
+    if getattr(model.equation_type, "_rotating_frame", False):
+        reject_moving_frame(parameters)
     solver_parameters = dict(solver_parameters or {})
     if complex(solver_parameters.setdefault("time_scale", -1j)) != -1j:
         raise ValueError(f"ground_state integrates in imaginary time (time_scale=-1j), got time_scale={solver_parameters['time_scale']!r}")

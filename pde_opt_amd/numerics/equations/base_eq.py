@@ -28,6 +28,12 @@ class BaseEquation(ABC):
     # names of constructor parameters whose VALUE may differ between the environments of one batch
     # (VectorPDEEnv): they travel with the environment (per-environment scalars / auxiliary fields)
     _per_env_controls: frozenset = frozenset()
+    # further names of the same kind, kept apart where the first set is pinned as an interface (GPE2DTSRot)
+    _per_env_controls_more: frozenset = frozenset()
+
+    @classmethod
+    def _all_per_env_controls(cls) -> frozenset:
+        return cls._per_env_controls | cls._per_env_controls_more
 
     # the subset of those that are PLAIN NUMBERS the constructor stores untouched (nothing in __post_init__ derives
     # from them): an equation that differs from another in such a field only is that equation with the attribute

@@ -171,13 +171,19 @@ class GPE2DTSRot(TimeSplittingEquation):
 
     Deviation from the reference: its ``B_terms`` takes a complex state, and so does the host diagnostic
     ``B_terms`` here, but the state of a SOLVE is ``(nx, ny, 2)`` = (re, im) like ``GPE2DTSControl``'s (the engine's
-    layout; snapshots, reductions and the vortex count carry over).  New: ``dx`` (the solver's norm weight).
+    layout; snapshots, reductions and the vortex count carry over).  New: ``dx`` (the solver's norm weight), and two
+    optional fields that stir and spin up the condensate: ``lights(t, X, Y)`` is added to the
+    trap -- a ``GaussianSpots`` is evaluated in-kernel at the start of every step, a callable that does not depend on
+    time is folded into the potential, any other callable of time is refused -- and ``omega_rate`` ramps the rotation:
+    the step starting at local time ``t`` uses ``omega + omega_rate t`` in all four of its line operators.
     """
 
     domain: Domain
     k: float
     e: float
     omega: float
+    lights: Optional[Callable] = None
+    omega_rate: float = 0.0
     fft = None
     ifft = None
     dx = None
@@ -185,6 +191,7 @@ class GPE2DTSRot(TimeSplittingEquation):
     _state_trailing = (2,)
     _rotating_frame = True
     _per_env_controls = frozenset({"k", "e", "omega"})
+    _per_env_controls_more = frozenset({"lights", "omega_rate"})  # the stirred step's
 
     def __post_init__(self):
         if len(self.domain.points) != 2:
@@ -198,21 +205,35 @@ class GPE2DTSRot(TimeSplittingEquation):
         self.fft = np.fft.fftn
         self.ifft = np.fft.ifftn
         self.xmesh, self.ymesh = tab["rot_mesh"]
+        if self.lights is not None and not callable(self.lights):
+            raise ValueError("GPE2DTSRot.lights is a callable lights(t, X, Y) (GaussianSpots: evaluated in-kernel) or None")
+
+    def omega_at(self, t: float) -> float:
+        """the rotation frequency of the step that starts at local time ``t``: ``omega + omega_rate t``"""
+        return float(self.omega) + float(self.omega_rate) * float(t)
 
     def A_terms(self, state_hat, t):
+        omega = self.omega_at(t) if self.omega_rate else self.omega
         return (
-            0.5j * self.two_pi_i_kx_2 - self.omega * self.ymesh * self.two_pi_i_kx,
-            0.5j * self.two_pi_i_ky_2 + self.omega * self.xmesh * self.two_pi_i_ky,
+            0.5j * self.two_pi_i_kx_2 - omega * self.ymesh * self.two_pi_i_kx,
+            0.5j * self.two_pi_i_ky_2 + omega * self.xmesh * self.two_pi_i_ky,
         )
 
     def trap_potential(self) -> np.ndarray:
         """V = 1/2 ((1 + e) X^2 + (1 - e) Y^2)"""
         return 0.5 * ((1 + self.e) * self.xmesh**2 + (1 - self.e) * self.ymesh**2)
 
+    def potential(self, t: float) -> np.ndarray:
+        """V of the step that starts at local time ``t``: the trap plus ``lights(t, X, Y)``"""
+        trap = self.trap_potential()
+        if self.lights is None:
+            return trap
+        return trap + np.broadcast_to(np.asarray(self.lights(t, self.xmesh, self.ymesh), dtype=np.float64), trap.shape)
+
     def B_terms(self, state, t):
         """Host evaluation on a COMPLEX state, as the reference's (diagnostics only; the integrator forms b
         in-kernel)."""
-        return -1j * self.trap_potential() - self.k * 1j * (np.abs(state) ** 2)
+        return -1j * self.potential(t) - self.k * 1j * (np.abs(state) ** 2)
 
     def rhs(self, state, t):
         return self.B_terms(state, t)
@@ -226,20 +247,62 @@ class GPE2DTSRot(TimeSplittingEquation):
         hx, hy = self.domain.dx
         return dict(equation=L.EQ_GPE, nx=nx, ny=ny, hx=hx, hy=hy, gpe_k=float(self.k))
 
+    def _lights_kind(self, t: float, t_end) -> str:
+        """how ``lights`` reaches the engine over local times ``[t, t_end]``: "none", "spots" (a GaussianSpots the kernels
+        evaluate at every step's start) or "static" (folded into the uploaded potential at ``t``).  A callable of time
+        that is no GaussianSpots is refused: this integrator samples nothing on the host."""
+        if self.lights is None:
+            return "none"
+        if isinstance(self.lights, GaussianSpots):
+            # t_end None: one potential at t (a ground state, an evaluation) -- frozen spots are a static potential
+            return "spots" if t_end is not None else "static"
+        if depends_on_time(lambda tt: self.lights(tt, self.xmesh, self.ymesh), t, t_end):
+            raise ValueError("GPE2DTSRot: a time-dependent lights must be a GaussianSpots (evaluated in-kernel at every "
+                             "step's start); the rotating-frame split step samples no host callable per substep. "
+                             "A callable that does not depend on time is folded into the potential.")
+        return "static"
+
+    def _stirred(self) -> bool:
+        """lights or a rotation ramp: what the gradients of the rotating frame do not cover"""
+        return self.lights is not None or bool(self.omega_rate)
+
     def _engine_upload(self, engine, t: float = 0.0, t_end=None):
-        engine.set_gpe_spots(None)
-        engine.set_aux(L.AUX_GPE_POTENTIAL, self.trap_potential())
+        kind = self._lights_kind(t, t_end)
+        if kind == "spots":
+            tab = self.lights.table(len(self.lights.spots))
+            engine.set_gpe_spots(np.broadcast_to(tab, (engine.batch,) + tab.shape), *self._cell0())
+        else:
+            engine.set_gpe_spots(None)
+        engine.set_aux(L.AUX_GPE_POTENTIAL, self.potential(t) if kind == "static" else self.trap_potential())
         engine.set_gpe_rotation(float(self.omega), *self._cell0())
+        if self.omega_rate:
+            engine.set_env_gpe_omega_rate(0, [float(self.omega_rate)] * engine.batch)
 
     @classmethod
     def _engine_upload_batch(cls, engine, eqs, t: float = 0.0, t_end=None):
-        """Per-environment k, e (a per-environment potential) and omega (``VectorPDEEnv``)."""
+        """Per-environment k, e (a per-environment potential), omega, omega_rate and lights (``VectorPDEEnv``): spots
+        travel as one table per environment, padded to the largest count; static lights join the potential."""
         eq0 = eqs[0]
-        engine.set_gpe_spots(None)
-        engine.set_env_gpe_k(0, [float(e.k) for e in eqs])
-        if all(e.e == eq0.e for e in eqs):
-            engine.set_aux(L.AUX_GPE_POTENTIAL, eq0.trap_potential())
+        kinds = [e._lights_kind(t, t_end) for e in eqs]
+        if all(k == "spots" for k in kinds):
+            n = max(len(e.lights.spots) for e in eqs)
+            engine.set_gpe_spots(np.stack([e.lights.table(n) for e in eqs]), *eq0._cell0())
+            fields = [e.trap_potential for e in eqs]
+            shared = all(e.e == eq0.e for e in eqs)
         else:
-            engine.set_aux(L.AUX_GPE_POTENTIAL, np.stack([e.trap_potential() for e in eqs]), per_env=True)
+            engine.set_gpe_spots(None)
+            # environments without spots of their own: every light is taken at t and folded into the potential
+            fields = [(lambda e=e: e.potential(t)) if k != "none" else e.trap_potential for e, k in zip(eqs, kinds)]
+            shared = all(e.e == eq0.e and e.lights is eq0.lights for e in eqs)
+            if any(k == "spots" for k in kinds) and any(e.lights.time_dependent for e, k in zip(eqs, kinds) if k == "spots"):
+                raise ValueError("GPE2DTSRot: moving GaussianSpots in some environments of a batch need GaussianSpots in "
+                                 "every environment (a zero-amplitude spot stands for none)")
+        engine.set_env_gpe_k(0, [float(e.k) for e in eqs])
+        if shared:
+            engine.set_aux(L.AUX_GPE_POTENTIAL, fields[0]())
+        else:
+            engine.set_aux(L.AUX_GPE_POTENTIAL, np.stack([f() for f in fields]), per_env=True)
         engine.set_gpe_rotation(float(eq0.omega), *eq0._cell0())
         engine.set_env_gpe_omega(0, [float(e.omega) for e in eqs])
+        if any(e.omega_rate for e in eqs):
+            engine.set_env_gpe_omega_rate(0, [float(e.omega_rate) for e in eqs])

@@ -273,12 +273,13 @@ class _EnvShard:
             # the potential is the one a substep starting at the end of this step would use
             from .gpe_observables import GpeObservables, equation_weights
 
+            # energy and mu in the frame of the step's end: Omega(step_dt) of an equation with an omega_rate
             if isinstance(eqs, _ScalarControlBatch):
-                omega, kappa = equation_weights([eq0])
+                omega, kappa = equation_weights([eq0], float(env.step_dt))
                 if eqs.name == "omega":
                     omega = np.asarray(eqs.values, dtype=np.float64)
             else:
-                omega, kappa = equation_weights(eqs)
+                omega, kappa = equation_weights(eqs, float(env.step_dt))
             rewards = GpeObservables.from_raw(eng.gpe_observables(float(env.step_dt)), omega, kappa)[env.device_reward[1]]
         elif isinstance(env.device_reward, tuple):
             # ("vortices", amp_thresh, tol): rl_utils.detect_vortices' num_vortices per environment, counted on the
@@ -525,10 +526,10 @@ class VectorPDEEnv:
         eq0 = eqs[0]
         if isinstance(eqs, _ScalarControlBatch):
             # one equation with a per-environment number: the closure structure is shared by construction
-            if eqs.name not in type(eq0)._per_env_controls and any(v != eqs.values[0] for v in eqs.values):
+            if eqs.name not in type(eq0)._all_per_env_controls() and any(v != eqs.values[0] for v in eqs.values):
                 raise ValueError(
                     f"{type(eq0).__name__}: the control parameter {eqs.name!r} cannot differ between the environments "
-                    f"of one VectorPDEEnv (per-environment controls: {sorted(type(eq0)._per_env_controls)})")
+                    f"of one VectorPDEEnv (per-environment controls: {sorted(type(eq0)._all_per_env_controls())})")
             return
         prob = eq0._engine_problem()
         for e in eqs[1:]:
@@ -541,10 +542,10 @@ class VectorPDEEnv:
         if all(self._same(c, controls[0]) for c in controls[1:]):
             return
         name = self.control_equation_parameter_name
-        if name not in type(eq0)._per_env_controls:
+        if name not in type(eq0)._all_per_env_controls():
             raise ValueError(
                 f"{type(eq0).__name__}: the control parameter {name!r} cannot differ between the environments "
-                f"of one VectorPDEEnv (per-environment controls: {sorted(type(eq0)._per_env_controls)})")
+                f"of one VectorPDEEnv (per-environment controls: {sorted(type(eq0)._all_per_env_controls())})")
 
     def _imex_scales(self, eqs):
         """sigma_b of ``pdeopt_set_env_imex_scale`` for the environments ``eqs`` of one engine: fourier_symbol =

@@ -61,9 +61,11 @@ class PDEModel:
         solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
         if getattr(equation, "_mu_module", None) is not None:  # a network as mu: torch evaluates it, the kernels take the field
             return self._fieldmu_solve(equation, solver, y0, ts, dt0, stepsize_controller)
+        ts = np.asarray(ts, dtype=np.float64)
+        if getattr(equation, "_rotating_frame", False):
+            equation._lights_kind(float(ts[0]), float(ts[-1]))  # refuses a host-sampled lights before an engine exists
         if self._engine is None:
             self._engine = HipEngine(self.device)
-        ts = np.asarray(ts, dtype=np.float64)
         sol = diffeqsolve(
             equation, solver, t0=ts[0], t1=ts[-1], dt0=dt0, y0=y0, saveat=SaveAt(ts=ts),
             stepsize_controller=stepsize_controller or ConstantStepSize(), max_steps=max_steps,
@@ -90,7 +92,8 @@ class PDEModel:
         ``|energy_now - energy_prev| / (check_every dt) <= tol``.  The loop ends when every environment is, or at
         ``max_steps`` with ``converged=False`` where it is not.  Returns ``GroundState(state, observables, steps,
         converged, history)``.  A ``lights`` that depends on time is frozen at ``t = 0``, for the steps and for the energy
-        alike: a ground state belongs to one potential.  The split step renormalises BETWEEN its half steps, so the returned state has
+        alike: a ground state belongs to one potential.  ``GPE2DTSRot`` takes static spots (a pinning beam) and refuses
+        moving spots and a nonzero ``omega_rate``.  The split step renormalises BETWEEN its half steps, so the returned state has
         ``norm = 1 + O(dt)``; ``energy`` and ``mu`` are already divided by it."""
         from . import gpe_observables
 
@@ -394,7 +397,8 @@ class PDEModel:
         segment, ys[-1]>`` -- the gradient of a piecewise-constant rotation schedule."""
         from . import gpe_control
 
-        gpe_control.reject_unsupported_rotation(self.equation_type, self.solver_type, stepsize_controller=stepsize_controller)
+        gpe_control.reject_unsupported_rotation(self.equation_type, self.solver_type, stepsize_controller=stepsize_controller,
+                                                parameters=parameters)
         y0 = np.asarray(y0)
         if y0.dtype not in (np.float32, np.float64):
             y0 = y0.astype(np.float64)
@@ -428,7 +432,7 @@ class PDEModel:
 
         other_parameters, weights = other_parameters or {}, weights or {}
         gpe_control.reject_unsupported_rotation(self.equation_type, self.solver_type, opt_names=opt_parameters or {},
-                                                stepsize_controller=stepsize_controller)
+                                                stepsize_controller=stepsize_controller, parameters=other_parameters)
         if y0 is None or ts is None:
             raise ValueError("optimize_rotation needs y0 and ts")
         y0 = np.asarray(y0)

@@ -1,0 +1,19 @@
+"""examples/gpe_rotating_stirring.py (a ground state at rest, then a rotation ramp with a circling laser spot in the
+rotating frame) runs end to end on the GPU."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_gpe_rotating_stirring_example_runs():
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "gpe_rotating_stirring.py"), "--quick"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert r.stdout.strip().splitlines()[-1] == "ok", r.stdout[-2000:]
+    assert "strang_rot_stir_fused_lds_fft" in r.stdout

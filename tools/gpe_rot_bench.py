@@ -3,6 +3,11 @@ non-rotating step (GPE2DTSControl(kinetic=True) + StrangSplitting) on the same s
 environments fp32 and 256^2 x 1.  HIP events around STEPS steps, WARMUP + ROUNDS windows, the median reported.
 
     python tools/gpe_rot_bench.py [--out profiles/gpe_rot.json]
+
+``--stir``: the stirred, ramped step (two moving ``GaussianSpots`` plus an ``omega_rate``, csrc/gpe_rot_stir.hip) next
+to the plain rotating step instead, same shapes, same run:
+
+    python tools/gpe_rot_bench.py --stir [--out profiles/gpe_rot_stir.json]
 """
 import json
 import os
@@ -28,16 +33,26 @@ def timed(eng, integrator):
     return float(np.median(out[WARMUP:]))
 
 
-def case(n, batch):
+def stir_lights():
+    from pde_opt_amd.numerics.functions.lights import GaussianSpot, GaussianSpots
+
+    return GaussianSpots([GaussianSpot(4.0, 0.5, -1.5, 2.0, 0.8, -1.0, 0.6), GaussianSpot(-3.0, 1.0, 1.2, -1.5, -0.9, 2.5, 0.5)])
+
+
+def case(n, batch, stir=False):
     dom = P.Domain((n, n), ((-12.0, 12.0), (-12.0, 12.0)), "dimensionless")
     x, y = dom.mesh()
     psi = np.exp(-(x**2 + y**2) / 32.0)
     psi = psi / np.sqrt(np.sum(psi**2) * dom.dx[0] ** 2)
     y0 = np.broadcast_to(np.stack([psi, 0 * psi], axis=-1), (batch, n, n, 2)).astype(np.float32).copy()
     row = {"shape": [n, n], "batch": batch, "dtype": "float32", "steps_per_window": STEPS}
-    for name, eq, solver in (
-            ("rotating", P.GPE2DTSRot(dom, K, E, OMEGA), P.RotatingStrangSplitting(dom.dx[0])),
-            ("strang", (c := P.GPE2DTSControl(dom, K, E, lambda t, xx, yy: 0.0 * xx, kinetic=True)), P.StrangSplitting(c.A_term, c.dx))):
+    rotating = ("rotating", P.GPE2DTSRot(dom, K, E, OMEGA), P.RotatingStrangSplitting(dom.dx[0]))
+    if stir:
+        other = ("stirred", P.GPE2DTSRot(dom, K, E, OMEGA, stir_lights(), 0.3), P.RotatingStrangSplitting(dom.dx[0]))
+    else:
+        c = P.GPE2DTSControl(dom, K, E, lambda t, xx, yy: 0.0 * xx, kinetic=True)
+        other = ("strang", c, P.StrangSplitting(c.A_term, c.dx))
+    for name, eq, solver in (rotating, other):
         eng = HipEngine(0)
         eng.configure(dtype=np.float32, batch=batch, **eq._engine_problem())
         eq._engine_upload(eng, 0.0, 1.0)
@@ -45,14 +60,18 @@ def case(n, batch):
         eng.set_state(y0)
         row[name + "_us_per_step"] = timed(eng, solver.integrator)
         row[name + "_kernel"] = eng.last_kernel
-    row["ratio"] = row["rotating_us_per_step"] / row["strang_us_per_step"]
+    if stir:
+        row["ratio"] = row["stirred_us_per_step"] / row["rotating_us_per_step"]
+    else:
+        row["ratio"] = row["rotating_us_per_step"] / row["strang_us_per_step"]
     return row
 
 
 if __name__ == "__main__":
-    rows = [case(512, 128), case(256, 1)]
+    stir = "--stir" in sys.argv
+    rows = [case(512, 128, stir), case(256, 1, stir)]
     for r in rows:
         print(json.dumps(r))
     if "--out" in sys.argv:
         with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:
-            json.dump({"tool": "tools/gpe_rot_bench.py", "rows": rows}, f, indent=1)
+            json.dump({"tool": "tools/gpe_rot_bench.py" + (" --stir" if stir else ""), "rows": rows}, f, indent=1)
