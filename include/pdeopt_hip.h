@@ -230,7 +230,8 @@ int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, cons
 /* per-environment rate of change of Omega: the step of PDEOPT_INT_STRANG_ROT that starts at local time t (the t of
  * pdeopt_advance's substep, t0 + s dt) uses Omega(t) = omega + rate t in all four of its line operators.
  * pdeopt_set_gpe_rotation resets every rate to 0.  With light spots (pdeopt_set_gpe_spots) or a nonzero rate the step
- * runs its stirred kernels (csrc/gpe_rot_stir.hip); pdeopt_gpe_rot_adjoint_step refuses both. */
+ * runs its stirred kernels (csrc/gpe_rot_stir.hip); pdeopt_gpe_rot_adjoint_step refuses both, their gradients are
+ * pdeopt_gpe_rot_stir_adjoint_step's. */
 int pdeopt_set_env_gpe_omega_rate(pdeopt_ctx* ctx, int env_first, int env_count, const double* rate);
 /* shared (per_env = 0: [nx][ny]) or per-environment (per_env = 1: [batch][nx][ny]) auxiliary
  * field, host pointer, element type = problem dtype (complex = 2 elements).  Replaces a time-dependent
@@ -623,6 +624,22 @@ int pdeopt_gpe_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* p
  * synchronises.  Refused (PDEOPT_EINVAL / PDEOPT_ESTATE): an equation other than the GPE, pdeopt_set_gpe_rotation not
  * called, spots set, a potential registered through pdeopt_set_aux_time_fn, overlapping lam_dev / psi0_dev / grad. */
 int pdeopt_gpe_rot_adjoint_step(pdeopt_ctx* ctx, double dt, const void* psi0_dev, void* lam_dev, double* grad);
+
+/* ---- the same for the stirred, ramped step (light spots from pdeopt_set_gpe_spots in the potential,
+ * Omega(t) = omega + rate t from pdeopt_set_env_gpe_omega_rate): one backward substep of the step that STARTED at local
+ * time t0 (the t of pdeopt_advance's substep) from psi0_dev.  t0, psi0_dev, lam_dev, "added into", device or host
+ * memory, the overlap checks and the asynchrony with device blocks are those of pdeopt_gpe_adjoint_step /
+ * pdeopt_gpe_rot_adjoint_step.  grad: [batch][4] doubles in the order (k, e, omega, omega_rate).  spot_grad:
+ * [batch][n_spots][7] doubles in the order of pdeopt_light_spot (the last entry is the derivative with respect to
+ * inv_two_w2), NULL if and only if no spots are set.  grad and spot_grad are both device memory or both host memory.
+ * Every state the stirred forward step takes is accepted: spots only, a ramp only, both, neither (then lam and
+ * (k, e, omega) are pdeopt_gpe_rot_adjoint_step's up to rounding and the rate entry is t0 x the omega entry).  15 batched
+ * 1-D transforms and 11 passes per call, five field-sized work buffers of its own; reductions in a fixed order, no
+ * atomics.  Refused (PDEOPT_EINVAL / PDEOPT_ESTATE): an equation other than the GPE, pdeopt_set_gpe_rotation not called,
+ * a potential registered through pdeopt_set_aux_time_fn, spot_grad NULL with spots set or non-NULL without, dt <= 0,
+ * a device / host mix of the two blocks, misaligned or overlapping pointers. */
+int pdeopt_gpe_rot_stir_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* psi0_dev, void* lam_dev, double* grad,
+                                     double* spot_grad);
 
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);

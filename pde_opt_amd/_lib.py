@@ -205,6 +205,7 @@ _SIGNATURES = {
     "pdeopt_fieldmu_adjoint_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),
     "pdeopt_gpe_adjoint_step": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP, _VP]),
     "pdeopt_gpe_rot_adjoint_step": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP]),
+    "pdeopt_gpe_rot_stir_adjoint_step": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP, _VP, _VP]),
     "pdeopt_cnn_create": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(_VP)]),
     "pdeopt_cnn_set_params": (C.c_int, [_VP, _VP, C.c_int64]),
     "pdeopt_cnn_forward": (C.c_int, [_VP, _VP, _VP]),

@@ -130,6 +130,7 @@ struct GpeAdjoint;   // work fields + multiplier of the Strang step's adjoint (g
 struct GpeRot;       // tables + work fields of the rotating-frame ADI split step (gpe_rot.hip)
 struct GpeObs;       // tables + partial sums of the GPE observables (gpe_obs.hip)
 struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint (gpe_rot_adjoint.hip)
+struct GpeRotStirAdjoint;  // the same of the stirred, ramped step's adjoint (gpe_rot_stir_adjoint.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -248,6 +249,7 @@ struct pdeopt_ctx {
   pdeopt::GpeRot* gpe_rot = nullptr;
   pdeopt::GpeObs* gpe_obs = nullptr;
   pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
+  pdeopt::GpeRotStirAdjoint* gpe_rot_stir_adjoint = nullptr;
 };
 
 namespace pdeopt {
@@ -431,6 +433,9 @@ void gpe_rot_destroy(pdeopt_ctx* ctx);
 // gpe_rot_adjoint.hip: the adjoint of that step; its buffers live and die with the spectral state too
 void gpe_rot_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_adjoint_destroy(pdeopt_ctx* ctx);
+// gpe_rot_stir_adjoint.hip: the adjoint of the stirred, ramped step (spots and Omega(t)); buffers as above
+void gpe_rot_stir_adjoint_invalidate(pdeopt_ctx* ctx);
+void gpe_rot_stir_adjoint_destroy(pdeopt_ctx* ctx);
 // gpe_obs.hip: energy terms, angular momentum and moments of the resident GPE state, [env_count][PDEOPT_GPE_OBS_COUNT]
 // doubles; its buffers live and die with the spectral state
 int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,

@@ -43,6 +43,7 @@
 #include <complex>
 
 #include "common.hpp"
+#include "gpe_rot_adjoint_sums.hpp"
 #include "gpe_rot_line.hpp"
 
 namespace pdeopt {
@@ -61,28 +62,13 @@ struct GpeRotAdjoint {
 
 namespace {
 
-constexpr int kBlocks = 128;  // workgroups per environment: the fixed partition of every reduction
+constexpr int kBlocks = kRadjBlocks;  // the fixed partition of every reduction (gpe_rot_adjoint_sums.hpp)
 // the sums of one environment
 enum { kNorm = 0, kSigma = 1, kGradK = 2, kGradE = 3, kOmega1 = 4, kOmega2 = 5, kOmega3 = 6, kOmega4 = 7, kSlots = 8 };
 
-// sum over the workgroup (256 threads), valid in thread 0
-__device__ __forceinline__ double radj_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();  // sh may still be read from the previous sum
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// the sum of one slot over the partition, every caller in the same order (one wave: threads 0 .. 63); valid in lane 0
+// radj_block_sum, radj_slot_total: gpe_rot_adjoint_sums.hpp (shared with gpe_rot_stir_adjoint.hip)
 __device__ __forceinline__ double radj_slot_total(const double* part, int b, int slot, int lane) {
-  const double* p = part + (int64_t)b * kBlocks * kSlots + slot;
-  double v = 0.0;
-  for (int q = lane; q < kBlocks; q += 64) v += p[(int64_t)q * kSlots];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
+  return pdeopt::radj_slot_total(part, kSlots, b, slot, lane);
 }
 
 // The primal's multiply: buf[b][ix][iy] *= kin[k] * rotation factor, the product kept in `save` too (nullptr: not).

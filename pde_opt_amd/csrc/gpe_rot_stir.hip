@@ -27,13 +27,7 @@ namespace pdeopt {
 
 namespace {
 
-// Omega(t) of an environment: one fused multiply-add everywhere, so every kernel forms the same number
-__device__ __forceinline__ float rstir_omega(const EnvParams<float>& e, float t) {
-  return __builtin_fmaf(e.gpe_omega_rate, t, e.gpe_omega);
-}
-__device__ __forceinline__ double rstir_omega(const EnvParams<double>& e, double t) {
-  return __builtin_fma(e.gpe_omega_rate, t, e.gpe_omega);
-}
+// Omega(t) of an environment: rot_omega_at (gpe_rot_line.hpp), shared with the adjoint
 
 // The row pass of gpe_rot.hip with Omega(t) and the spots at t (sa.t) in b.
 template <typename T, int N>
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(256) void rstir_row_kernel(Cx<T>* __restrict__ psi,
   const int env = (int)(row / nx);
   const int ix = (int)(row - (int64_t)env * nx);
   Cx<T>* const g = psi + row * N;
-  const T a = ax.w * rstir_omega(ep[env], sa.t) * (ax.c_first + T(ix) * ax.c_step);
+  const T a = ax.w * rot_omega_at(ep[env], sa.t) * (ax.c_first + T(ix) * ax.c_step);
   Cx<T> v[PTS];
 #pragma unroll
   for (int m = 0; m < PTS; ++m) v[m] = g[E::natural(j, m)];
@@ -162,11 +156,11 @@ __global__ __launch_bounds__(C* N / reg_default_pts<N>()) void rstir_col_kernel(
     else
       E::template dit<+1, false>(v, seq, tw, j);
   };
-  if constexpr (PRE) line_op(std::true_type{}, rstir_omega(ep[env], t_pre) * wy);
+  if constexpr (PRE) line_op(std::true_type{}, rot_omega_at(ep[env], t_pre) * wy);
   if constexpr (POST) {
 #pragma unroll
     for (int m = 0; m < PTS; ++m) db[E::natural(j, m) * ny + c] = v[m].re * v[m].re + v[m].im * v[m].im;
-    line_op(std::false_type{}, rstir_omega(ep[env], t_post) * wy);
+    line_op(std::false_type{}, rot_omega_at(ep[env], t_post) * wy);
   }
 #pragma unroll
   for (int m = 0; m < PTS; ++m) gb[E::natural(j, m) * ny + c] = v[m];
@@ -189,7 +183,7 @@ __global__ __launch_bounds__(256) void rstir_mul_kernel(Cx<T>* __restrict__ psi,
     for (int q = 0; q < nblocks; ++q) s += partial[(int64_t)b * nblocks + q];
     scale = (T)(1.0 / sqrt(s * dx2));
   }
-  const T om = rstir_omega(ep[b], t);
+  const T om = rot_omega_at(ep[b], t);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (int64_t)gridDim.x * 256) {
     const int ix = (int)(i / ny), iy = (int)(i - (int64_t)ix * ny);
     const int k = AXIS == 0 ? ix : iy, n = AXIS == 0 ? nx : ny, line = AXIS == 0 ? iy : ix;

@@ -823,12 +823,14 @@ void spectral_invalidate(pdeopt_ctx* ctx) {
   gpe_adjoint_invalidate(ctx);
   gpe_rot_invalidate(ctx);
   gpe_rot_adjoint_invalidate(ctx);
+  gpe_rot_stir_adjoint_invalidate(ctx);
 }
 
 void spectral_destroy(pdeopt_ctx* ctx) {
   gpe_adjoint_destroy(ctx);
   gpe_rot_destroy(ctx);
   gpe_rot_adjoint_destroy(ctx);
+  gpe_rot_stir_adjoint_destroy(ctx);
   gpe_obs_destroy(ctx);
   Spectral* sp = ctx->spectral;
   if (!sp) return;

@@ -515,6 +515,16 @@ class HipEngine:
         self._check(self._lib.pdeopt_gpe_rot_adjoint_step(self._h, float(dt), C.c_void_p(psi0_ptr), C.c_void_p(lam_ptr),
                                                           C.c_void_p(grad_ptr)))
 
+    def gpe_rot_stir_adjoint_step(self, t0: float, dt: float, psi0_ptr: int, lam_ptr: int, grad_ptr: int, spot_grad_ptr):
+        """the adjoint of one substep of the stirred, ramped rotating-frame split step that started at local time ``t0``
+        (``pdeopt_gpe_rot_stir_adjoint_step``): ``lam`` goes from the cotangent of the substep's end state to that of its
+        start state ``psi0`` in place; the block ``(batch, 4)`` of doubles in the order (k, e, omega, omega_rate) and the
+        spots' block ``(batch, n_spots, 7)`` (``None`` / 0 when no spots are set) are added into, both in device or both
+        in host memory"""
+        self._check(self._lib.pdeopt_gpe_rot_stir_adjoint_step(self._h, float(t0), float(dt), C.c_void_p(psi0_ptr),
+                                                               C.c_void_p(lam_ptr), C.c_void_p(grad_ptr),
+                                                               C.c_void_p(spot_grad_ptr or None)))
+
     def state_device_array(self) -> "DeviceArray":
         """The state field itself as a ``DeviceArray`` (batch,) + state_shape in the engine's dtype: valid until the
         next ``configure`` with another shape; ``advance`` updates it in place (synchronise with ``sync()``)."""

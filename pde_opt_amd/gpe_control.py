@@ -19,6 +19,11 @@ The rotating-frame pair ``GPE2DTSRot`` + ``RotatingStrangSplitting`` has its own
 ``pdeopt_gpe_rot_adjoint_step`` (csrc/gpe_rot_adjoint.hip): the gradient over k, e and omega of every environment and
 over the start state.  ``RotControlSolver`` drives it with the same sweep (``GpeControlSolver._sweep``: schedule, cotangent
 split, chunked recomputation, chunk cap); ``PDEModel.rotation_gradient`` / ``optimize_rotation`` are its public entries.
+
+With ``lights`` (Gaussian spots evaluated in-kernel) or ``omega_rate`` the backward substep is
+``pdeopt_gpe_rot_stir_adjoint_step`` (csrc/gpe_rot_stir_adjoint.hip): it adds the gradient over the rate and over the
+seven numbers of every spot.  ``RotStirControlSolver`` drives it, the sweep carrying the spots' block as a second device
+block; ``PDEModel.stirring_gradient`` / ``optimize_stirring`` are its public entries.
 """
 
 from __future__ import annotations
@@ -98,7 +103,8 @@ ROTATING_GRADIENTS = ("control_gradient, optimize and train do not cover the rot
 
 ROTATION_GRADIENT_SUPPORT = ("rotation_gradient and optimize_rotation support GPE2DTSRot with RotatingStrangSplitting and "
                              "ConstantStepSize, without lights and with omega_rate = 0 (a frozen potential and a constant "
-                             "Omega); the optimisation variables are a non-empty subset of k, e and omega")
+                             "Omega); the optimisation variables are a non-empty subset of k, e and omega; a stirred or ramped "
+                             "equation has PDEModel.stirring_gradient and optimize_stirring")
 
 
 def reject_rotating(equation_type, solver_type=None):
@@ -124,6 +130,9 @@ def reject_unsupported(equation_type, solver_type, parameters=None, opt_names=No
             raise NotImplementedError(f"lights of type {type(parameters.get('lights')).__name__}: " + GPE_CONTROL_SUPPORT)
         if parameters.get("time_dependent") is False:
             raise NotImplementedError("time_dependent=False folds the spots into the potential: " + GPE_CONTROL_SUPPORT)
+
+
+_ONE_BLOCK = object()  # GpeControlSolver._sweep: no second gradient block
 
 
 class GpeControlSolver:
@@ -161,11 +170,13 @@ class GpeControlSolver:
             return int(self.chunk_bytes)
         return int(os.environ.get(CHUNK_BYTES_ENV, DEFAULT_CHUNK_BYTES))
 
-    def _sweep(self, configure, integrator, y0s, ts, dt0, cotangents, grad_tail, adjoint_step):
-        """The backward sweep both GPE adjoints share: ``configure(engine)`` sets the problem up, the forward pass keeps
+    def _sweep(self, configure, integrator, y0s, ts, dt0, cotangents, grad_tail, adjoint_step, second_tail=_ONE_BLOCK):
+        """The backward sweep the GPE adjoints share: ``configure(engine)`` sets the problem up, the forward pass keeps
         one state per chunk, every chunk is run again and held, and ``adjoint_step(engine, t0, dt, psi0_ptr, lam_ptr,
         grad_ptr)`` takes ``lam`` back one substep while it adds into the device block ``grad`` ``(B,) + grad_tail``.
-        Returns ``(grad, lam0)``, fp64 on the host."""
+        Returns ``(grad, lam0)``, fp64 on the host.  With ``second_tail`` the sweep carries a second device block
+        ``(B,) + second_tail`` (``None``: no such block, a null pointer): ``adjoint_step`` gets its pointer as a seventh
+        argument and the sweep returns ``(grad, second or None, lam0)``."""
         torch = self.torch
         eng = self.engine
         ts = np.asarray(ts, dtype=np.float64)
@@ -193,6 +204,12 @@ class GpeControlSolver:
                     eng.advance(integrator, steps[i], 1, t_of(i))
             lam = up(cot[N]) if N in cot and N > 0 else torch.zeros_like(Y)
             grad = torch.zeros((y0s.shape[0],) + tuple(grad_tail), dtype=torch.float64, device=Y.device)
+            blocks = (grad.data_ptr(),)
+            second = None
+            if second_tail is not _ONE_BLOCK:
+                if second_tail is not None:
+                    second = torch.zeros((y0s.shape[0],) + tuple(second_tail), dtype=torch.float64, device=Y.device)
+                blocks += (second.data_ptr() if second is not None else 0,)
             self.last_chunks = len(first)
             for s0 in reversed(first):
                 s1 = min(N, s0 + chunk)
@@ -204,12 +221,14 @@ class GpeControlSolver:
                         eng.advance(integrator, steps[s], 1, t_of(s))
                 for s in range(s1 - 1, s0 - 1, -1):
                     psi0 = held.pop()
-                    adjoint_step(eng, t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(), grad.data_ptr())
+                    adjoint_step(eng, t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(), *blocks)
                     if s in cot:
                         lam += up(cot[s])
             if N == 0 and 0 in cot:
                 lam += up(cot[0])
             out = grad.cpu().numpy(), lam.double().cpu().numpy()
+            if second_tail is not _ONE_BLOCK:
+                out = out[0], (second.cpu().numpy() if second is not None else None), out[1]
         return out
 
     def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
@@ -275,3 +294,80 @@ class RotControlSolver(GpeControlSolver):
 
         return self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, (3,),
                            lambda eng, t0, dt, psi0, lam, grad: eng.gpe_rot_adjoint_step(dt, psi0, lam, grad))
+
+
+STIR_NAMES = ("k", "e", "omega", "omega_rate")  # the order of pdeopt_gpe_rot_stir_adjoint_step's gradient block
+
+STIRRING_GRADIENT_SUPPORT = ("stirring_gradient and optimize_stirring support GPE2DTSRot with RotatingStrangSplitting and "
+                             "ConstantStepSize; lights is None, a GaussianSpots (evaluated in-kernel, differentiated) or a "
+                             "callable that does not depend on time (folded into the potential, not differentiated); the "
+                             "optimisation variables are a non-empty subset of k, e, omega, omega_rate and lights (a "
+                             "GaussianSpots)")
+
+
+def reject_unsupported_stirring(equation_type, solver_type, opt_names=None, stepsize_controller=None, parameters=None,
+                                opt_parameters=None):
+    """``NotImplementedError`` for what the stirred rotating-frame gradient does not cover; needs no engine and no GPU"""
+    from .numerics.solvers import ConstantStepSize, RotatingStrangSplitting
+
+    if not getattr(equation_type, "_rotating_frame", False):
+        raise NotImplementedError(f"{equation_type.__name__}: " + STIRRING_GRADIENT_SUPPORT)
+    if solver_type is not RotatingStrangSplitting:
+        raise NotImplementedError(f"{solver_type.__name__}: " + STIRRING_GRADIENT_SUPPORT)
+    if opt_names is not None and (not set(opt_names) or not set(opt_names) <= set(STIR_NAMES) | {"lights"}):
+        raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + STIRRING_GRADIENT_SUPPORT)
+    if stepsize_controller is not None and not isinstance(stepsize_controller, ConstantStepSize):
+        raise NotImplementedError(f"{type(stepsize_controller).__name__}: " + STIRRING_GRADIENT_SUPPORT)
+    if opt_parameters is not None and "lights" in opt_parameters and not isinstance(opt_parameters["lights"], GaussianSpots):
+        raise NotImplementedError(f"lights of type {type(opt_parameters['lights']).__name__} as an optimisation variable: "
+                                  + STIRRING_GRADIENT_SUPPORT)
+    lights = (parameters or {}).get("lights")
+    if lights is not None and not isinstance(lights, GaussianSpots) and not callable(lights):
+        raise NotImplementedError(f"lights of type {type(lights).__name__}: " + STIRRING_GRADIENT_SUPPORT)
+
+
+def reject_time_dependent_lights(equation, t0, t1):
+    """a callable ``lights`` of time that is no ``GaussianSpots`` has no gradient here (the forward solve raises
+    ``ValueError`` for it; that stays): ``NotImplementedError`` before any engine work"""
+    try:
+        equation._lights_kind(float(t0), float(t1))
+    except ValueError as e:
+        raise NotImplementedError(f"{e} " + STIRRING_GRADIENT_SUPPORT) from None
+
+
+class RotStirControlSolver(RotControlSolver):
+    """The backward sweeps of the stirred, ramped rotating-frame GPE (``pdeopt_gpe_rot_stir_adjoint_step``,
+    csrc/gpe_rot_stir_adjoint.hip): ``GpeControlSolver._sweep`` with a second device block for the spots."""
+
+    def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
+        """``(grad (B, 4), spot_grad (B, S, 7) or None, lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys``
+        ``(len(ts), B, nx, ny, 2)`` of the saved solution: row b of ``grad`` is ``dJ/d(k, e, omega, omega_rate)`` of
+        environment b, ``spot_grad`` the library's block (last entry d/d inv_two_w2; ``None`` when no spots reach the
+        kernels), ``lam0`` is ``dJ/dy0``.  ``equation`` is one ``GPE2DTSRot`` shared by the batch or a list with one per
+        environment (its own k, e, omega, omega_rate and spots): spot tables travel padded to the largest count; where
+        the counts differ the padding's rows are dropped and ``spot_grad`` is a list of ``(S_b, 7)`` arrays.  All fp64 on the host;
+        the sweep itself runs in the dtype of ``y0s``.  Constant steps only."""
+        ts = np.asarray(ts, dtype=np.float64)
+        eqs = list(equation) if isinstance(equation, (list, tuple)) else None
+        eq0 = eqs[0] if eqs else equation
+        if eqs is not None and len(eqs) != y0s.shape[0]:
+            raise ValueError(f"{len(eqs)} equations for a batch of {y0s.shape[0]} states")
+        t_first, t_last = float(ts[0]), float(ts[-1])
+        kinds = [e._lights_kind(t_first, t_last) for e in (eqs or [eq0])]
+        counts = [len(e.lights.spots) for e in (eqs or [eq0])] if all(k == "spots" for k in kinds) else None
+
+        def configure(eng):
+            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **eq0._engine_problem())
+            if eqs is None:
+                eq0._engine_upload(eng, t_first, t_last)
+            else:
+                type(eq0)._engine_upload_batch(eng, eqs, t_first, t_last)
+            solver.configure_engine(eng, eq0)
+
+        grad, spot_grad, lam0 = self._sweep(
+            configure, solver.integrator, y0s, ts, dt0, cotangents, (4,),
+            lambda eng, t0, dt, psi0, lam, g, sg: eng.gpe_rot_stir_adjoint_step(t0, dt, psi0, lam, g, sg),
+            second_tail=(max(counts), 7) if counts else None)
+        if counts and len(set(counts)) > 1:  # drop the padding: zero-amplitude spots that stand for none
+            spot_grad = [spot_grad[b, :n].copy() for b, n in enumerate(counts)]
+        return grad, spot_grad, lam0

@@ -22,6 +22,8 @@ reverse-mode gradient of such an objective over the spots' numbers (a discrete a
 ``GPE2DTSRot`` + ``RotatingStrangSplitting``: ``rotation_gradient`` returns the reverse-mode gradient over ``k``, ``e``,
 ``omega`` and the start state (a discrete adjoint of the alternating-direction split step, csrc/gpe_rot_adjoint.hip) and
 ``optimize_rotation`` drives BFGS with it; ``control_gradient``, ``optimize`` and ``train`` refuse that pair.
+With ``lights`` or ``omega_rate`` (a stirred or ramped problem) ``stirring_gradient`` adds the gradient over ``omega_rate``
+and the spots' numbers (csrc/gpe_rot_stir_adjoint.hip) and ``optimize_stirring`` drives BFGS with it.
 """
 
 from __future__ import annotations
@@ -452,6 +454,116 @@ class PDEModel:
             return J + lam * float(np.sum(w * p * p)), np.array([grad[n] for n in names]) + 2.0 * lam * w * p
 
         p0 = np.array([float(opt_parameters[n]) for n in names], dtype=np.float64)
+        p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
+        self.last_optimize_history = hist
+        return params_of(p)
+
+    # -- gradients of the stirred, ramped rotating-frame GPE (pde_opt_amd.gpe_control.RotStirControlSolver) ------------
+    def rot_stir_control_solver(self):
+        """the solver of the stirred rotating-frame GPE's backward sweeps (its ``chunk_bytes`` caps the states a sweep
+        holds)"""
+        if getattr(self, "_rot_stir_control", None) is None:
+            from .gpe_control import RotStirControlSolver
+
+            self._rot_stir_control = RotStirControlSolver(self.device)
+        return self._rot_stir_control
+
+    def stirring_gradient(self, objective_function, y0, ts, parameters, solver_parameters=None, dt0=0.000001,
+                          per_environment=False, stepsize_controller=None):
+        """``(J, grad, lam0)`` of ``J = objective_function(solve(parameters, y0, ts, ...))`` for ``GPE2DTSRot`` +
+        ``RotatingStrangSplitting`` with or without ``lights`` and ``omega_rate``: ``grad`` is a dict with ``"k"``, ``"e"``,
+        ``"omega"``, ``"omega_rate"`` (floats; ``(B,)`` arrays, one entry per state of a batch, with
+        ``per_environment=True``; summed in order otherwise) and, when ``parameters["lights"]`` is a ``GaussianSpots``,
+        ``"lights"``: ``(S, 7)`` (``(B, S, 7)`` per environment), ``dJ/d`` (amp0, amp_rate, x0, x_rate, y0, y_rate, width)
+        of every spot in user units.  A callable ``lights`` that does not depend on time is folded into the potential as
+        the forward solve does and gets no entry; one that does is refused.  ``lam0 = dJ/dy0`` in the shape of ``y0``: it
+        chains segments as in ``rotation_gradient``.  The objective takes the forms of ``optimize``; ``ys`` is the array
+        ``solve`` returns, bit for bit.  A discrete adjoint of the solve on the GPU (csrc/gpe_rot_stir_adjoint.hip),
+        constant steps only."""
+        from . import gpe_control
+        from .numerics.functions.lights import GaussianSpots
+
+        gpe_control.reject_unsupported_stirring(self.equation_type, self.solver_type, stepsize_controller=stepsize_controller,
+                                                parameters=parameters)
+        y0 = np.asarray(y0)
+        if y0.dtype not in (np.float32, np.float64):
+            y0 = y0.astype(np.float64)
+        ts = np.asarray(ts, dtype=np.float64)
+        objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
+        if y0.ndim not in (3, 4) or tuple(y0.shape[-3:]) != tuple(self.domain.points) + (2,):
+            raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points) + (2,)} or (B,) + that")
+        equation = self.equation_type(domain=self.domain, **parameters)
+        gpe_control.reject_time_dependent_lights(equation, ts[0], ts[-1])
+        solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+        ys = self.solve(parameters, y0, ts, solver_parameters, dt0=dt0)
+        J, g = objective.value_and_grad(ys)
+        single = y0.ndim == 3
+        cot = g[:, None] if single else g
+        grad, spot_grad, lam0 = self.rot_stir_control_solver().gradient(equation, solver, y0[None] if single else y0, ts,
+                                                                        float(dt0), cot)
+
+        def total(rows):  # summed in order
+            tot = np.zeros(rows.shape[1:])
+            for row in rows:
+                tot = tot + row
+            return tot
+
+        if not per_environment:
+            grad = total(grad)
+        out = {name: (grad[..., j].copy() if per_environment else float(grad[j])) for j, name in enumerate(gpe_control.STIR_NAMES)}
+        if isinstance(parameters.get("lights"), GaussianSpots):
+            user = gpe_control.SpotMap.user_gradient(parameters["lights"], spot_grad)
+            out["lights"] = user if per_environment else total(user)
+        return J, out, (lam0[0] if single else lam0)
+
+    def optimize_stirring(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters=None,
+                          weights=None, lambda_reg=0.0, max_steps=100, dt0=0.000001, stepsize_controller=None):
+        """Minimise ``objective_function(solve(...)) + lambda_reg sum w p^2`` over ``opt_parameters``, any non-empty
+        subset of ``{"k", "e", "omega", "omega_rate", "lights"}`` of ``GPE2DTSRot`` (the rest fixed in
+        ``other_parameters``), with BFGS (``fit.minimize_bfgs``) on the gradient of ``stirring_gradient``.  ``"lights"``
+        must be a ``GaussianSpots``; its ``free`` names the numbers that move.  The flat vector is the scalars in that
+        order, then ``SpotMap.flatten``; ``weights[name]`` is a number (``weights["lights"]``: a number or ``(S, 7)``).
+        Trial points of the line search are forward solves.  Returns ``{**fitted, **other_parameters}``; the objective
+        after every accepted step is in ``last_optimize_history``."""
+        from . import gpe_control
+
+        other_parameters, weights = other_parameters or {}, weights or {}
+        gpe_control.reject_unsupported_stirring(self.equation_type, self.solver_type, opt_names=opt_parameters or {},
+                                                stepsize_controller=stepsize_controller,
+                                                parameters={**other_parameters, **(opt_parameters or {})},
+                                                opt_parameters=opt_parameters or {})
+        if y0 is None or ts is None:
+            raise ValueError("optimize_stirring needs y0 and ts")
+        y0 = np.asarray(y0)
+        objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
+        names = [n for n in gpe_control.STIR_NAMES if n in opt_parameters]
+        smap = gpe_control.SpotMap.of(opt_parameters["lights"]) if "lights" in opt_parameters else None
+        ns = len(names)
+        w = np.array([float(weights.get(n, 0.0)) for n in names])
+        active = np.ones(ns, dtype=bool)
+        p0 = np.array([float(opt_parameters[n]) for n in names], dtype=np.float64)
+        if smap is not None:
+            w = np.concatenate([w, smap.weight_vector(weights.get("lights"))])
+            active = np.concatenate([active, smap.active().reshape(-1)])
+            p0 = np.concatenate([p0, smap.flatten(opt_parameters["lights"])])
+        lam = float(lambda_reg)
+
+        def params_of(p):
+            out = {**other_parameters, **{n: float(v) for n, v in zip(names, p[:ns])}}
+            if smap is not None:
+                out["lights"] = smap.build(p[ns:])
+            return out
+
+        def value(p):
+            return objective.value(self.solve(params_of(p), y0, ts, solver_parameters, dt0=dt0)) + lam * float(np.sum(w * p * p))
+
+        def value_and_grad(p):
+            J, grad, _ = self.stirring_gradient(objective, y0, ts, params_of(p), solver_parameters, dt0=dt0)
+            g = np.array([grad[n] for n in names], dtype=np.float64)
+            if smap is not None:
+                g = np.concatenate([g, np.asarray(grad["lights"]).reshape(-1)])
+            return J + lam * float(np.sum(w * p * p)), (g + 2.0 * lam * w * p) * active
+
         p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
         self.last_optimize_history = hist
         return params_of(p)

@@ -1,0 +1,89 @@
+"""Reference for the adjoint of the stirred, ramped rotating-frame split step (csrc/gpe_rot_stir_adjoint.hip):
+``gpe_rot_adjoint_ref.py``'s torch step on the CPU with light spots in the potential and Omega(t0) = omega + rate t0 in
+the line operators, at complex128 or complex64, differentiated by torch.autograd.  A helper, not a test.
+
+    Omega0 = omega + rate t0;  w = V + spots(t0, X, Y) + k |psi0|^2
+    u1 = Lx(s) psi0;  a = Ly(s) u1;  c = a exp(-i w tau);  psi1 = Lx(s) Ly(s) (c / sqrt(h^2 sum |c|^2))
+
+States and cotangents are real arrays (B, nx, ny, 2) = (re, im).  The parameters are ``p`` (B, 4) = (k, e, omega, rate)
+and ``spots`` (B, S, 7) in the library's order (amp0, amp_rate, x0, x_rate, y0, y_rate, inv_two_w2), or None: one row
+per environment.  tests/gpe_rot_stir_ref.py is the same step in numpy, written independently."""
+import numpy as np
+import torch
+
+from pde_opt_amd.fieldmu import schedule
+
+from gpe_rot_adjoint_ref import Case  # grid and integrator numbers as torch constants of one precision
+
+
+def spots_value(case, spots, t0):
+    """sum over the spots of (amp0 + amp_rate t0) exp(-((X - x0 - x_rate t0)^2 + (Y - y0 - y_rate t0)^2) inv_two_w2): (B, nx, ny)"""
+    q = [spots[:, :, j].reshape(spots.shape[0], spots.shape[1], 1, 1) for j in range(7)]
+    dx, dy = case.X - (q[2] + q[3] * t0), case.Y - (q[4] + q[5] * t0)
+    return ((q[0] + q[1] * t0) * torch.exp(-(dx * dx + dy * dy) * q[6])).sum(dim=1)
+
+
+def step(case, y, p, spots, dt, t0):
+    """one substep from local time t0 of the real state y (B, nx, ny, 2) -> the same shape"""
+    psi = torch.view_as_complex(y.contiguous())
+    k, e, om, rate = (p[:, j].reshape(-1, 1, 1) for j in range(4))
+    om = om + rate * t0
+    tau = torch.tensor(dt * case.time_scale, dtype=case.cplx)
+    s = 0.5 * tau
+    ex = torch.exp(s * (0.5j * case.ikx**2 - (om * case.Y).to(case.cplx) * case.ikx))
+    ey = torch.exp(s * (0.5j * case.iky**2 + (om * case.X).to(case.cplx) * case.iky))
+    lx = lambda v: torch.fft.ifft(torch.fft.fft(v, dim=-2) * ex, dim=-2)
+    ly = lambda v: torch.fft.ifft(torch.fft.fft(v, dim=-1) * ey, dim=-1)
+    w = 0.5 * ((1 + e) * case.X**2 + (1 - e) * case.Y**2) + k * (psi.real**2 + psi.imag**2)
+    if spots is not None:
+        w = w + spots_value(case, spots, t0)
+    c = ly(lx(psi)) * torch.exp(-1j * w.to(case.cplx) * tau)
+    n = torch.sqrt(case.h2 * torch.sum(c.real**2 + c.imag**2, dim=(-2, -1), keepdim=True))
+    return torch.view_as_real(lx(ly(c / n)))
+
+
+def solve(case, y0, p, spots, ts, dt0):
+    """the saved states (len(ts), *y0.shape): constant steps, step i starts at ts[0] + i dt0, a clipped last step,
+    linear interpolation inside a step (the schedule of integrate.diffeqsolve)"""
+    steps, saves = schedule(ts, dt0)
+    by_index = {}
+    for q, (i, theta) in enumerate(saves):
+        by_index.setdefault(i, []).append((q, theta))
+    out = [None] * len(saves)
+    y, prev = y0, None
+    for i in range(len(steps) + 1):
+        for q, theta in by_index.get(i, ()):
+            out[q] = y if theta is None else prev + theta * (y - prev)
+        if i == len(steps):
+            break
+        prev = y
+        y = step(case, y, p, spots, steps[i], float(ts[0]) + i * float(dt0))
+    return torch.stack(out)
+
+
+def leaves(case, y0, p, spots):
+    y = torch.tensor(np.asarray(y0), dtype=case.real, requires_grad=True)
+    q = torch.tensor(np.asarray(p, dtype=np.float64), dtype=case.real, requires_grad=True)
+    s = None if spots is None else torch.tensor(np.asarray(spots, dtype=np.float64), dtype=case.real, requires_grad=True)
+    return y, q, s
+
+
+def _grads(J, y, q, s):
+    g = torch.autograd.grad(J, (y, q) if s is None else (y, q, s))
+    return g[1].double().numpy(), (None if s is None else g[2].double().numpy()), g[0].double().numpy()
+
+
+def step_vjp(case, y0, p, spots, dt, t0, lam1):
+    """(gradient (B, 4) over (k, e, omega, rate), spot gradient (B, S, 7) or None, lam0) of <lam1, step(y0)>"""
+    y, q, s = leaves(case, y0, p, spots)
+    out = step(case, y, q, s, dt, t0)
+    return _grads((out * torch.as_tensor(np.asarray(lam1), dtype=case.real)).sum(), y, q, s)
+
+
+def solve_grad(case, y0, p, spots, ts, dt0, objective):
+    """(J, ys, dJ/dp (B, 4), dJ/dspots (B, S, 7) or None, dJ/dy0) for objective(ys tensor) -> 0-d tensor"""
+    y, q, s = leaves(case, y0, p, spots)
+    ys = solve(case, y, q, s, ts, dt0)
+    J = objective(ys.double())
+    gp, gs, gy = _grads(J, y, q, s)
+    return float(J.detach()), ys.detach().double().numpy(), gp, gs, gy
