@@ -60,7 +60,13 @@ typedef enum {
   /* shapes.py:39-64, Shape.smooth_shape: u_t = 2 (c lap u + (1 - c) u_nn) - 18 u (1 - u)(1 - 2u) / eps^2 with centred
    * differences, u_nn the second derivative along grad u.  pdeopt_problem.kappa carries c (smooth_curvature),
    * pdeopt_problem.gpe_k carries eps (smooth_epsilon); no closures */
-  PDEOPT_EQ_SHAPE_SMOOTH = 7
+  PDEOPT_EQ_SHAPE_SMOOTH = 7,
+  /* Allen-Cahn with Butler-Volmer kinetics (allen_cahn.py:162-395): du/dt = j0(u) (exp(-alpha eta) - exp((1 - alpha) eta)),
+   * eta = mu + v, at a given voltage v or at constant current C (v solves the constraint from two sums over the whole
+   * environment; pdeopt_set_bv_params).  pdeopt_problem.mob carries the exchange current j0.  Explicit integrators and
+   * Tsit5, derivs "fd", periodic layout, closures of the in-kernel family only (csrc/butler_volmer.hip) */
+  PDEOPT_EQ_ALLEN_CAHN_BV = 8,     /* mu = mu_h(u) - kappa lap u, weight 1                                            */
+  PDEOPT_EQ_ALLEN_CAHN_SBM_BV = 9  /* mu = mu_h(u) - kappa/psi div(psi grad u), weight psi (SBM_PSI aux field; no wall term) */
 } pdeopt_equation;
 
 /* which solver.step() is fused around it */
@@ -93,6 +99,8 @@ typedef enum {
 #define PDEOPT_CL_EXP_WRAP 2
 #define PDEOPT_CL_MIX_ENTROPY 4  /* + c log c + (1 - c) log(1 - c): ideal mixing entropy of the regular-
                                     solution free energy f(c) (notebooks/smooth_boundary.ipynb)          */
+#define PDEOPT_CL_SQRT_WRAP 8    /* then sqrt(.): the exchange current sqrt(c (1 - c)) of notebooks/run_butler_volmer_sbm.ipynb.
+                                    Evaluated by the Butler-Volmer kernels only: any other equation refuses it */
 
 typedef struct {
   int32_t kind;   /* pdeopt_closure_kind */
@@ -233,6 +241,19 @@ int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, cons
  * runs its stirred kernels (csrc/gpe_rot_stir.hip); pdeopt_gpe_rot_adjoint_step refuses both, their gradients are
  * pdeopt_gpe_rot_stir_adjoint_step's. */
 int pdeopt_set_env_gpe_omega_rate(pdeopt_ctx* ctx, int env_first, int env_count, const double* rate);
+/* Butler-Volmer equations (PDEOPT_EQ_ALLEN_CAHN_BV / _SBM_BV), after pdeopt_configure: the symmetry factor alpha (shared),
+ * mode 0 = the voltage is given, 1 = constant current, and per_env [batch][2] doubles whose column 0 is v (mode 0) or the
+ * current C (mode 1) of every environment (column 1 is reserved).  In mode 0 the scalar out[0] of pdeopt_set_time_terms /
+ * pdeopt_set_time_table, where one is registered, is ADDED to v at every right-hand-side evaluation time (a voltage
+ * protocol v(t)).  Kept in a device array of its own; pdeopt_problem and the per-environment table are unchanged. */
+int pdeopt_set_bv_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env);
+/* The voltage v = 2 log y of the constant-current constraint on the RESIDENT state, host_out[env_count]: the first pass of
+ * the right-hand side plus a one-wave-per-environment finish that adds the partial sums in the order the right-hand
+ * side does -- bitwise the v a pdeopt_rhs of that state uses.  The state is not modified.  Mode 1 only. */
+int pdeopt_bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
+/* DIAGNOSTIC HOOK (tests): the v the LAST right-hand-side evaluation (or pdeopt_bv_voltage) of these environments used, as
+ * its kernel recorded it on the device, host_out[env_count].  Not needed to use the equations; may change. */
+int pdeopt_bv_last_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 /* shared (per_env = 0: [nx][ny]) or per-environment (per_env = 1: [batch][nx][ny]) auxiliary
  * field, host pointer, element type = problem dtype (complex = 2 elements).  Replaces a time-dependent
  * source registered with pdeopt_set_aux_time_fn for the same field. */

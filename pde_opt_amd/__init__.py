@@ -15,7 +15,10 @@ from .numerics.domains import Domain
 from .numerics.equations import (
     AdvectionDiffusion2D,
     AllenCahn2DPeriodic,
+    AllenCahn2DPeriodicButlerVolmer,
+    AllenCahn2DPeriodicButlerVolmerConstantCurrent,
     AllenCahn2DSmoothedBoundary,
+    AllenCahn2DSmoothedBoundaryButlerVolmerConstantCurrent,
     BaseEquation,
     CahnHilliard2DPeriodic,
     CahnHilliard2DSmoothedBoundary,
@@ -50,6 +53,8 @@ __all__ = [
     "BaseEquation", "AllenCahn2DPeriodic", "CahnHilliard2DPeriodic", "AdvectionDiffusion2D", "GPE2DTSControl",
     "GPE2DTSRot", "RotatingStrangSplitting", "OBSERVABLE_NAMES", "GpeObservables", "GroundState",
     "AllenCahn2DSmoothedBoundary", "CahnHilliard2DSmoothedBoundary", "CahnHilliard3DPeriodic",
+    "AllenCahn2DPeriodicButlerVolmer", "AllenCahn2DPeriodicButlerVolmerConstantCurrent",
+    "AllenCahn2DSmoothedBoundaryButlerVolmerConstantCurrent",
     "Domain", "Shape", "LegendrePolynomialExpansion", "DiffusionLegendrePolynomials", "ChemicalPotentialLegendrePolynomials",
     "GaussianSpot", "GaussianSpots",
     "SemiImplicitFourierSpectral", "StrangSplitting", "Euler", "RK4", "Tsit5",

@@ -25,10 +25,13 @@ EQ_CAHN_HILLIARD, EQ_ALLEN_CAHN, EQ_ADVECTION_DIFFUSION, EQ_GPE = 0, 1, 2, 3
 EQ_ALLEN_CAHN_SBM, EQ_CAHN_HILLIARD_SBM = 4, 5
 EQ_CAHN_HILLIARD_3D = 6
 EQ_SHAPE_SMOOTH = 7  # Shape.smooth_shape (shapes.py:39-64)
+EQ_ALLEN_CAHN_BV, EQ_ALLEN_CAHN_SBM_BV = 8, 9  # Butler-Volmer kinetics (allen_cahn.py:162-395; csrc/butler_volmer.hip)
+BV_VOLTAGE, BV_CONSTANT_CURRENT = 0, 1  # mode of pdeopt_set_bv_params
 INT_EULER, INT_RK4, INT_IMEX, INT_STRANG, INT_TSIT5 = 0, 1, 2, 3, 4
 INT_STRANG_ROT = 5  # rotating-frame alternating-direction split step (GPE2DTSRot)
 CL_POLY, CL_LEGENDRE, CL_JIT = 0, 1, 2
 CL_LOGIT_PRIOR, CL_EXP_WRAP = 1, 2
+CL_SQRT_WRAP = 8  # the Butler-Volmer kernels only
 SENS_MU, SENS_MOB = 0, 1  # pdeopt_sens_role
 AUX_VX_FACE, AUX_VY_FACE, AUX_IMEX_SYMBOL, AUX_GPE_A_TERM, AUX_GPE_POTENTIAL = 0, 1, 2, 3, 4
 AUX_SBM_PSI, AUX_SBM_NORM_GRAD, AUX_SBM_MASK = 5, 6, 7
@@ -133,6 +136,9 @@ _SIGNATURES = {
     "pdeopt_configure": (C.c_int, [_VP, C.POINTER(Problem)]),
     "pdeopt_set_env_params": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     "pdeopt_set_aux": (C.c_int, [_VP, C.c_int, _VP, C.c_int]),
+    "pdeopt_set_bv_params": (C.c_int, [_VP, C.c_double, C.c_int, _VP]),
+    "pdeopt_bv_voltage": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "pdeopt_bv_last_voltage": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_set_aux_time_fn": (C.c_int, [_VP, C.c_int, AUX_FN, _VP, C.c_int]),
     "pdeopt_set_env_gpe_k": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_set_env_imex_scale": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),

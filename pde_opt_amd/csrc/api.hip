@@ -78,13 +78,14 @@ void free_fields(pdeopt_ctx* ctx) {
   spectral_destroy(ctx);
   strang_fused_destroy(ctx);
   sens_destroy(ctx);
+  bv_destroy(ctx);
   graph_destroy(ctx);
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
   ctx->configured = false;
 }
 
-int check_closure(pdeopt_ctx* ctx, const pdeopt_closure& c, const char* name, const std::string* jit_body = nullptr) {
+int check_closure(pdeopt_ctx* ctx, const pdeopt_closure& c, const char* name, const std::string* jit_body = nullptr, int more_flags = 0) {
   if (c.kind == PDEOPT_CL_JIT) {  // compiled at run time from the body handed over by pdeopt_set_jit_closures
     if (!jit_body || jit_body->empty())
       return fail(ctx, PDEOPT_EINVAL, "closure %s has kind PDEOPT_CL_JIT but pdeopt_set_jit_closures gave no body for it", name);
@@ -94,7 +95,9 @@ int check_closure(pdeopt_ctx* ctx, const pdeopt_closure& c, const char* name, co
     return fail(ctx, PDEOPT_EINVAL, "closure %s: unknown kind %d", name, c.kind);
   if (c.n < 1 || c.n > kMaxCoef)
     return fail(ctx, PDEOPT_EINVAL, "closure %s: n=%d outside 1..%d", name, c.n, kMaxCoef);
-  if (c.flags & ~(PDEOPT_CL_LOGIT_PRIOR | PDEOPT_CL_EXP_WRAP | PDEOPT_CL_MIX_ENTROPY))
+  if ((c.flags & PDEOPT_CL_SQRT_WRAP) && !(more_flags & PDEOPT_CL_SQRT_WRAP))
+    return fail(ctx, PDEOPT_EINVAL, "closure %s: PDEOPT_CL_SQRT_WRAP is evaluated by the Butler-Volmer kernels only", name);
+  if (c.flags & ~(PDEOPT_CL_LOGIT_PRIOR | PDEOPT_CL_EXP_WRAP | PDEOPT_CL_MIX_ENTROPY | more_flags))
     return fail(ctx, PDEOPT_EINVAL, "closure %s: unknown flags 0x%x", name, c.flags);
   return PDEOPT_OK;
 }
@@ -361,7 +364,7 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   ctx->configured = false;
   if (pr->dtype != PDEOPT_F32 && pr->dtype != PDEOPT_F64)
     return fail(ctx, PDEOPT_EINVAL, "unknown dtype %d", pr->dtype);
-  if (pr->equation < PDEOPT_EQ_CAHN_HILLIARD || pr->equation > PDEOPT_EQ_SHAPE_SMOOTH)
+  if (pr->equation < PDEOPT_EQ_CAHN_HILLIARD || pr->equation > PDEOPT_EQ_ALLEN_CAHN_SBM_BV)
     return fail(ctx, PDEOPT_EINVAL, "unknown equation %d", pr->equation);
   if (pr->nx < 1 || pr->ny < 1 || pr->batch < 1)
     return fail(ctx, PDEOPT_EINVAL, "bad extents nx=%d ny=%d batch=%d", pr->nx, pr->ny, pr->batch);
@@ -386,6 +389,17 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
     // compiled kernel, which has no closure_generic: the host emits a body for both roles whenever one needs it
     if ((pr->mu.kind == PDEOPT_CL_JIT) != (pr->mob.kind == PDEOPT_CL_JIT))
       return fail(ctx, PDEOPT_EINVAL, "run-time-compiled closures: hand over bodies for mu AND the mobility (kind PDEOPT_CL_JIT for both)");
+  }
+  if (bv_equation(pr->equation)) {
+    int rc;
+    if (pr->mu.kind == PDEOPT_CL_JIT || pr->mob.kind == PDEOPT_CL_JIT)
+      return fail(ctx, PDEOPT_EINVAL, "the Butler-Volmer kernels evaluate closures of the in-kernel family only (no run-time-compiled closures)");
+    if ((rc = check_closure(ctx, pr->mu, "mu"))) return rc;  // (SQRT_WRAP is the exchange current's: the kernels evaluate mu_h without it)
+    if ((rc = check_closure(ctx, pr->mob, "j0", nullptr, PDEOPT_CL_SQRT_WRAP))) return rc;
+    if (pr->derivs != PDEOPT_DERIVS_FD)
+      return fail(ctx, PDEOPT_EINVAL, "the Butler-Volmer equations have a finite-difference right-hand side only (derivs = \"fd\")");
+    if (ctx->opt_halo)
+      return fail(ctx, PDEOPT_EINVAL, "the Butler-Volmer equations need the periodic layout (their sums run over the whole environment)");
   }
   if (pr->equation == PDEOPT_EQ_SHAPE_SMOOTH && !(pr->gpe_k > 0))
     return fail(ctx, PDEOPT_EINVAL, "shape smoothing needs smooth_epsilon (gpe_k) > 0");
@@ -432,6 +446,29 @@ int pdeopt_set_env_params(pdeopt_ctx* ctx, int env_first, int env_count, const d
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   with_dtype(ctx, [&](auto t) { patch_env_params<decltype(t)>(ctx, env_first, env_count, kappa, mu_coef, mob_coef); });
   return upload_env_params(ctx);
+}
+
+int pdeopt_set_bv_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env) {
+  if (!ctx || !per_env) return PDEOPT_EINVAL;
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return bv_set_params(ctx, alpha, mode, per_env);
+}
+
+int pdeopt_bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out) {
+  if (!ctx || !host_out) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return env_count ? bv_voltage(ctx, env_first, env_count, host_out, true) : PDEOPT_OK;
+}
+
+int pdeopt_bv_last_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out) {
+  if (!ctx || !host_out) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return env_count ? bv_voltage(ctx, env_first, env_count, host_out, false) : PDEOPT_OK;
 }
 
 int pdeopt_set_aux(pdeopt_ctx* ctx, int which, const void* host, int per_env) {

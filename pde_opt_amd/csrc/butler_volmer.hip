@@ -1,0 +1,392 @@
+// Allen-Cahn with Butler-Volmer kinetics, at a given voltage or at constant current, as a stage right-hand side.
+//
+// Replaces rhs_fd / get_voltage of pde_opt/numerics/equations/allen_cahn.py:162-395
+// (AllenCahn2DPeriodicButlerVolmer, ...ConstantCurrent, AllenCahn2DSmoothedBoundaryButlerVolmerConstantCurrent):
+//
+//   mu  = mu_h(u) - kappa lap(u)                                        periodic            (w = 1)
+//   mu  = mu_h(u) - kappa/psi [divx(avgx(psi) gradx u) + divy(...)]     smoothed boundary   (w = psi; no wall term)
+//   I+- = hx hy sum w j0(u) exp(+- mu / 2),   y = (-C + sqrt(C^2 + 4 I+ I-)) / (2 I+),   v = 2 log y     constant current
+//   du/dt = j0(u) (exp(-alpha eta) - exp((1 - alpha) eta)),   eta = mu + v
+//
+// The constant-current right-hand side is not local: v needs two sums over the whole environment.  Two launches:
+//   pass 1  bv_mu_sums_kernel   mu of every cell into a work field, and the workgroup's two weighted sums -- per thread in
+//                               fp64, reduced over the workgroup in a fixed order -- into partials[env][workgroup][2]
+//   pass 2  bv_rate_kernel      EVERY workgroup adds its environment's partials itself, in one fixed order in fp64
+//                               (bv_sum_partials), so all of them hold the same bits of v; then the rate and the stage
+//                               launcher's output modes (stage_update).  Workgroup 0 of an environment records v in bv_v.
+// No atomics, no finish kernel between the passes, nothing waits for another workgroup.  At a given voltage pass 2 is
+// the only launch and evaluates the stencil itself.  pdeopt_bv_voltage runs pass 1 on the resident state and a
+// one-wave-per-environment finish that calls the same bv_sum_partials / bv_voltage_of: bitwise the v of a right-hand side.
+#include <cmath>
+
+#include "stencil_generic.hpp"
+
+namespace pdeopt {
+
+namespace {
+
+constexpr int kBvRows = 16, kBvCols = 64;      // cells per workgroup tile; 256 threads as (64, 4), four rows each
+constexpr int kBvPitch = kBvCols + 2;          // LDS row pitch: the tile and its one-cell ring
+constexpr int kBvLdsRows = kBvRows + 2;
+constexpr int kBvRpt = kBvRows / 4;
+
+template <typename T>
+struct BvArgs {
+  StageArgs<T> s;
+  T* mu;              // work field [env][nx][ny] (constant current)
+  double* partials;   // [env][nwg][2]
+  double* bv_v;       // [env]
+  const double* par;  // [env][2]: column 0 = v (mode 0) or C (mode 1)
+  double alpha, h2, v_shift;
+  int nwg, mode;
+};
+
+// a closure of the in-kernel family, then sqrt(.) if SQRT_WRAP: the exchange current sqrt(c (1 - c))
+template <typename T>
+__device__ __forceinline__ T bv_closure(const ClosureSpec& s, const T* __restrict__ coef, T c) {
+  const T r = closure_generic<T>(s, coef, c);
+  return (s.flags & PDEOPT_CL_SQRT_WRAP) ? t_sqrt<T>(r) : r;
+}
+
+// tile of `f` with its periodic ring -> LDS: LDS (r, c) holds cell (wrap(i0 - 1 + r), wrap(j0 - 1 + c)); any nx, ny
+template <typename T>
+__device__ __forceinline__ void bv_load_tile(T* __restrict__ lds, const T* __restrict__ f, int nx, int ny, int i0, int j0, int tid) {
+  for (int e = tid; e < kBvLdsRows * kBvPitch; e += 256) {
+    const int r = e / kBvPitch, c = e - r * kBvPitch;
+    lds[e] = f[(int64_t)wrap_idx(i0 - 1 + r, nx) * ny + wrap_idx(j0 - 1 + c, ny)];
+  }
+}
+
+// mu of the cell at LDS position (r, c), from the tile(s)
+template <typename T, bool SBM>
+__device__ __forceinline__ T bv_mu_at(const StageArgs<T>& a, const EnvParams<T>& p, const T* __restrict__ su, const T* __restrict__ sp,
+                                      int r, int c) {
+  const int o = r * kBvPitch + c;
+  const T u0 = su[o], xp = su[o + kBvPitch], xm = su[o - kBvPitch], yp = su[o + 1], ym = su[o - 1];
+  if constexpr (SBM) {
+    // the expression of INNER in rhs_generic_point without its wall term (allen_cahn.py:323-339 has it commented out)
+    const T pc = sp[o], pxp = sp[o + kBvPitch], pxm = sp[o - kBvPitch], pyp = sp[o + 1], pym = sp[o - 1];
+    const T dx_hi = (T(0.5) * (pc + pxp)) * ((xp - u0) * a.rhx), dx_lo = (T(0.5) * (pxm + pc)) * ((u0 - xm) * a.rhx);
+    const T dy_hi = (T(0.5) * (pc + pyp)) * ((yp - u0) * a.rhy), dy_lo = (T(0.5) * (pym + pc)) * ((u0 - ym) * a.rhy);
+    const T lap = (dx_hi - dx_lo) * a.rhx + (dy_hi - dy_lo) * a.rhy;
+    return closure_generic<T>(a.mu, p.mu, u0) - (p.kappa / pc) * lap;
+  } else {
+    return closure_generic<T>(a.mu, p.mu, u0) - p.kappa * lap_at<T>(u0, xp, xm, yp, ym, a.rhx2, a.rhy2);
+  }
+}
+
+// The sum of an environment's n partial pairs by ONE wave, in one fixed order: lane l adds pairs l, l + 64, ... in index
+// order, then the shuffle tree.  Every caller -- each workgroup of pass 2, the finish kernel -- gets the same bits.
+__device__ __forceinline__ void bv_sum_partials(const double* __restrict__ part, int n, int lane, double* sp, double* sm) {
+  double a = 0.0, b = 0.0;
+  for (int q = lane; q < n; q += 64) {
+    a += part[2 * q];
+    b += part[2 * q + 1];
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    a += __shfl_down(a, s, 64);
+    b += __shfl_down(b, s, 64);
+  }
+  *sp = a;  // lane 0 holds the sums
+  *sm = b;
+}
+
+// v = 2 log y of the constant-current constraint (the 1/2 in I+- is fixed upstream, it is not alpha)
+__device__ __forceinline__ double bv_voltage_of(double sp, double sm, double h2, double C) {
+  const double ip = h2 * sp, im = h2 * sm;
+  const double y = (-C + sqrt(C * C + 4.0 * ip * im)) / (2.0 * ip);
+  return 2.0 * log(y);
+}
+
+template <typename T>
+__device__ __forceinline__ T bv_rate(T j0, T eta, T alpha) {
+  return j0 * (t_exp<T>(-alpha * eta) - t_exp<T>((T(1) - alpha) * eta));
+}
+
+}  // namespace
+
+// pass 1 (constant current): mu -> work field, the workgroup's two weighted sums -> partials
+template <typename T, bool SBM>
+__global__ __launch_bounds__(256) void bv_mu_sums_kernel(const BvArgs<T> a) {
+  __shared__ T su[kBvLdsRows * kBvPitch];
+  __shared__ T sp[SBM ? kBvLdsRows * kBvPitch : 1];
+  __shared__ double red[8];
+  const int nx = a.s.g.nx, ny = a.s.g.ny;
+  const int b = blockIdx.z, i0 = blockIdx.y * kBvRows, j0 = blockIdx.x * kBvCols;
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  const EnvParams<T>& p = a.s.ep[b];
+  const int64_t base = (int64_t)b * a.s.g.bstride;
+  bv_load_tile<T>(su, a.s.in + base, nx, ny, i0, j0, tid);
+  if constexpr (SBM) bv_load_tile<T>(sp, a.s.psi, nx, ny, i0, j0, tid);
+  __syncthreads();
+  double accp = 0.0, accm = 0.0;
+  const int j = j0 + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < kBvRpt; ++q) {
+    const int ri = threadIdx.y + 4 * q, i = i0 + ri;
+    if (i < nx && j < ny) {
+      const int r = ri + 1, c = threadIdx.x + 1;
+      const T mu = bv_mu_at<T, SBM>(a.s, p, su, sp, r, c);
+      a.mu[base + (int64_t)i * ny + j] = mu;
+      const T j0v = bv_closure<T>(a.s.mob, p.mob, su[r * kBvPitch + c]);
+      const T ep = t_exp<T>(T(0.5) * mu), em = t_exp<T>(T(-0.5) * mu);
+      double wj = (double)j0v;  // products in fp64 from the T values
+      if constexpr (SBM) wj *= (double)sp[r * kBvPitch + c];
+      accp += wj * (double)ep;
+      accm += wj * (double)em;
+    }
+  }
+  // fixed order: the shuffle tree of each wave, then the four waves in index order
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    accp += __shfl_down(accp, s, 64);
+    accm += __shfl_down(accm, s, 64);
+  }
+  if (threadIdx.x == 0) {
+    red[2 * threadIdx.y] = accp;
+    red[2 * threadIdx.y + 1] = accm;
+  }
+  __syncthreads();
+  if (tid < 2) {  // lane 0: I+, lane 1: I-; one plain store each
+    const double v = ((red[tid] + red[2 + tid]) + red[4 + tid]) + red[6 + tid];
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
+    a.partials[((int64_t)b * a.nwg + wg) * 2 + tid] = v;
+  }
+}
+
+// pass 2 (STENCIL 0: constant current, mu from the work field), or the only launch at a given voltage (STENCIL 1: the
+// periodic stencil, 2: the smoothed-boundary one)
+template <typename T, int STENCIL>
+__global__ __launch_bounds__(256) void bv_rate_kernel(const BvArgs<T> a) {
+  __shared__ T su[STENCIL ? kBvLdsRows * kBvPitch : 1];
+  __shared__ T sp[STENCIL == 2 ? kBvLdsRows * kBvPitch : 1];
+  __shared__ double sv;
+  const int nx = a.s.g.nx, ny = a.s.g.ny;
+  const int b = blockIdx.z, i0 = blockIdx.y * kBvRows, j0 = blockIdx.x * kBvCols;
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  const EnvParams<T>& p = a.s.ep[b];
+  const int64_t base = (int64_t)b * a.s.g.bstride;
+  double vd;
+  if constexpr (STENCIL == 0) {
+    if (threadIdx.y == 0) {  // wave 0 adds the environment's partials; the other waves wait at the barrier
+      double s_p, s_m;
+      bv_sum_partials(a.partials + (int64_t)b * a.nwg * 2, a.nwg, threadIdx.x, &s_p, &s_m);
+      if (threadIdx.x == 0) {
+        const double v = bv_voltage_of(s_p, s_m, a.h2, a.par[2 * b]);
+        sv = v;
+        if (blockIdx.x == 0 && blockIdx.y == 0) a.bv_v[b] = v;
+      }
+    }
+    __syncthreads();
+    vd = sv;
+  } else {
+    vd = a.par[2 * b] + a.v_shift;
+    bv_load_tile<T>(su, a.s.in + base, nx, ny, i0, j0, tid);
+    if constexpr (STENCIL == 2) bv_load_tile<T>(sp, a.s.psi, nx, ny, i0, j0, tid);
+    __syncthreads();
+    if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) a.bv_v[b] = vd;
+  }
+  const T v = T(vd), alpha = T(a.alpha);
+  const int j = j0 + threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < kBvRpt; ++q) {
+    const int ri = threadIdx.y + 4 * q, i = i0 + ri;
+    if (i < nx && j < ny) {
+      const int64_t idx = base + (int64_t)i * ny + j;
+      T mu, u0;
+      if constexpr (STENCIL == 0) {
+        mu = a.mu[idx];
+        u0 = a.s.in[idx];
+      } else {
+        mu = bv_mu_at<T, STENCIL == 2>(a.s, p, su, sp, ri + 1, threadIdx.x + 1);
+        u0 = su[(ri + 1) * kBvPitch + threadIdx.x + 1];
+      }
+      T k = bv_rate<T>(bv_closure<T>(a.s.mob, p.mob, u0), mu + v, alpha);
+      if (a.s.scaled) k *= p.kscale;
+      stage_update<T>(a.s, idx, k);
+    }
+  }
+}
+
+// pdeopt_bv_voltage: one wave per environment, the summation of pass 2
+__global__ __launch_bounds__(64) void bv_finish_kernel(const double* __restrict__ partials, const double* __restrict__ par, int nwg,
+                                                       double h2, double* __restrict__ bv_v) {
+  const int b = blockIdx.x;
+  double s_p, s_m;
+  bv_sum_partials(partials + (int64_t)b * nwg * 2, nwg, threadIdx.x, &s_p, &s_m);
+  if (threadIdx.x == 0) bv_v[b] = bv_voltage_of(s_p, s_m, h2, par[2 * b]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+struct BvState {
+  double alpha = 0.5;
+  int mode = 0;
+  bool set = false;
+  void* par = nullptr;       // [batch][2] doubles
+  void* partials = nullptr;  // [batch][nwg][2] doubles
+  void* v = nullptr;         // [batch] doubles
+  int nwg = 0, batch = 0;
+};
+
+namespace {
+
+int bv_ensure(pdeopt_ctx* ctx) {
+  if (!ctx->bv) ctx->bv = new BvState;
+  BvState* st = ctx->bv;
+  const pdeopt_problem& p = ctx->prob;
+  const int nwg = ((p.nx + kBvRows - 1) / kBvRows) * ((p.ny + kBvCols - 1) / kBvCols);
+  if (st->par && st->nwg == nwg && st->batch == p.batch) return PDEOPT_OK;
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  for (void** q : {&st->par, &st->partials, &st->v}) {
+    if (*q) (void)hipFree(*q);
+    *q = nullptr;
+  }
+  st->nwg = nwg;
+  st->batch = p.batch;
+  st->set = false;
+  int rc;
+  if ((rc = ensure_buffer(ctx, &st->par, sizeof(double) * 2 * (size_t)p.batch))) return rc;
+  if ((rc = ensure_buffer(ctx, &st->partials, sizeof(double) * 2 * (size_t)nwg * p.batch))) return rc;
+  if ((rc = ensure_buffer(ctx, &st->v, sizeof(double) * (size_t)p.batch))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(st->par, 0, sizeof(double) * 2 * (size_t)p.batch, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(st->v, 0, sizeof(double) * (size_t)p.batch, ctx->stream));
+  return PDEOPT_OK;
+}
+
+int bv_check(pdeopt_ctx* ctx) {
+  const pdeopt_problem& p = ctx->prob;
+  if (!bv_equation(p.equation)) return fail(ctx, PDEOPT_EINVAL, "equation %d is not a Butler-Volmer equation", p.equation);
+  if (!ctx->bv || !ctx->bv->set || ctx->bv->batch != p.batch)
+    return fail(ctx, PDEOPT_ESTATE, "the Butler-Volmer equations need pdeopt_set_bv_params after pdeopt_configure");
+  if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV && !ctx->aux[PDEOPT_AUX_SBM_PSI].dev)
+    return fail(ctx, PDEOPT_ESTATE, "the smoothed-boundary Butler-Volmer equation needs the SBM_PSI aux field");
+  if (p.batch > 65535 || (p.nx + kBvRows - 1) / kBvRows > 65535)
+    return fail(ctx, PDEOPT_EINVAL, "grid too large for the Butler-Volmer kernels (nx=%d batch=%d)", p.nx, p.batch);
+  return PDEOPT_OK;
+}
+
+template <typename T>
+BvArgs<T> bv_args(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
+  BvState* st = ctx->bv;
+  BvArgs<T> a{};
+  a.s = s;
+  a.mu = static_cast<T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
+  a.partials = static_cast<double*>(st->partials) + (int64_t)w.lo * st->nwg * 2;
+  a.bv_v = static_cast<double*>(st->v) + w.lo;
+  a.par = static_cast<const double*>(st->par) + 2 * (int64_t)w.lo;
+  a.alpha = st->alpha;
+  a.h2 = ctx->prob.hx * ctx->prob.hy;
+  a.v_shift = (double)s.tw_a;
+  a.nwg = st->nwg;
+  a.mode = st->mode;
+  return a;
+}
+
+dim3 bv_grid(const pdeopt_ctx* ctx, int n_env) {
+  return dim3((ctx->prob.ny + kBvCols - 1) / kBvCols, (ctx->prob.nx + kBvRows - 1) / kBvRows, n_env);
+}
+
+template <typename T>
+void bv_launch_pass1(pdeopt_ctx* ctx, const Window& w, const BvArgs<T>& a) {
+  const dim3 grid = bv_grid(ctx, w.n), block(64, 4, 1);
+  if (ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV)
+    hipLaunchKernelGGL((bv_mu_sums_kernel<T, true>), grid, block, 0, w.stream, a);
+  else
+    hipLaunchKernelGGL((bv_mu_sums_kernel<T, false>), grid, block, 0, w.stream, a);
+}
+
+}  // namespace
+
+template <typename T>
+int launch_bv_stage(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
+  int rc;
+  if ((rc = bv_check(ctx))) return rc;
+  const bool sbm = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV;
+  const dim3 grid = bv_grid(ctx, w.n), block(64, 4, 1);
+  if (ctx->bv->mode == 1) {
+    if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+    const BvArgs<T> a = bv_args<T>(ctx, w, s);
+    bv_launch_pass1<T>(ctx, w, a);
+    hipLaunchKernelGGL((bv_rate_kernel<T, 0>), grid, block, 0, w.stream, a);
+    ctx->last_kernel = sbm ? "bv_mu_sums<SBM>+bv_rate" : "bv_mu_sums+bv_rate";
+  } else {
+    const BvArgs<T> a = bv_args<T>(ctx, w, s);
+    if (sbm)
+      hipLaunchKernelGGL((bv_rate_kernel<T, 2>), grid, block, 0, w.stream, a);
+    else
+      hipLaunchKernelGGL((bv_rate_kernel<T, 1>), grid, block, 0, w.stream, a);
+    ctx->last_kernel = sbm ? "bv_rate<SBM,voltage>" : "bv_rate<voltage>";
+  }
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+template int launch_bv_stage<float>(pdeopt_ctx*, const Window&, const StageArgs<float>&);
+template int launch_bv_stage<double>(pdeopt_ctx*, const Window&, const StageArgs<double>&);
+
+int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env) {
+  if (!bv_equation(ctx->prob.equation)) return fail(ctx, PDEOPT_EINVAL, "pdeopt_set_bv_params belongs to the Butler-Volmer equations");
+  if (mode != 0 && mode != 1) return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer mode %d: 0 = voltage given, 1 = constant current", mode);
+  if (!std::isfinite(alpha)) return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer symmetry factor alpha must be finite");
+  int rc;
+  const void* const par_before = ctx->bv ? ctx->bv->par : nullptr;
+  if ((rc = bv_ensure(ctx))) return rc;
+  BvState* st = ctx->bv;
+  // alpha, the mode and the buffers are kernel arguments of a captured substep graph (the per-environment values are not)
+  if (st->par != par_before || st->alpha != alpha || st->mode != mode) graph_destroy(ctx);
+  st->alpha = alpha;
+  st->mode = mode;
+  const size_t bytes = sizeof(double) * 2 * (size_t)ctx->prob.batch;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(st->par, per_env, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // `per_env` is the caller's again
+  st->set = true;
+  ctx->tsit5_fsal_valid = false;
+  return PDEOPT_OK;
+}
+
+int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, bool recompute) {
+  int rc;
+  if ((rc = bv_check(ctx))) return rc;
+  BvState* st = ctx->bv;
+  if (recompute) {
+    if (st->mode != 1) return fail(ctx, PDEOPT_EINVAL, "pdeopt_bv_voltage solves the constant-current constraint: set mode 1");
+    if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+    const Window w{env_first, env_count, ctx->stream};
+    rc = with_dtype(ctx, [&](auto tag) -> int {
+      using T = decltype(tag);
+      StageArgs<T> s{};
+      s.g = make_geo(ctx);
+      s.in = static_cast<const T*>(ctx->Y) + (int64_t)w.lo * s.g.bstride;
+      set_recip_plain(s, grid_recip(ctx->prob));
+      set_closures<T>(s, ctx, w.lo);
+      s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
+      const BvArgs<T> a = bv_args<T>(ctx, w, s);
+      bv_launch_pass1<T>(ctx, w, a);
+      hipLaunchKernelGGL(bv_finish_kernel, dim3(w.n), dim3(64), 0, w.stream, a.partials, a.par, a.nwg, a.h2, a.bv_v);
+      return PDEOPT_OK;
+    });
+    if (rc) return rc;
+    PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+    ctx->last_kernel = "bv_mu_sums+bv_finish";
+  }
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, static_cast<const double*>(st->v) + env_first, sizeof(double) * (size_t)env_count,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+bool bv_time_dependent(const pdeopt_ctx* ctx) {
+  return bv_equation(ctx->prob.equation) && ctx->bv && ctx->bv->mode == 0 && (ctx->time_fn != nullptr || !ctx->tt_times.empty());
+}
+
+void bv_destroy(pdeopt_ctx* ctx) {
+  if (!ctx->bv) return;
+  for (void* q : {ctx->bv->par, ctx->bv->partials, ctx->bv->v})
+    if (q) (void)hipFree(q);
+  delete ctx->bv;
+  ctx->bv = nullptr;
+}
+
+}  // namespace pdeopt

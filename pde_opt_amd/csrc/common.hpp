@@ -131,6 +131,7 @@ struct GpeRot;       // tables + work fields of the rotating-frame ADI split ste
 struct GpeObs;       // tables + partial sums of the GPE observables (gpe_obs.hip)
 struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint (gpe_rot_adjoint.hip)
 struct GpeRotStirAdjoint;  // the same of the stirred, ramped step's adjoint (gpe_rot_stir_adjoint.hip)
+struct BvState;      // parameters, partial sums and voltages of the Butler-Volmer equations (butler_volmer.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -250,6 +251,7 @@ struct pdeopt_ctx {
   pdeopt::GpeObs* gpe_obs = nullptr;
   pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
   pdeopt::GpeRotStirAdjoint* gpe_rot_stir_adjoint = nullptr;
+  pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; lives and dies with the field buffers
 };
 
 namespace pdeopt {
@@ -283,8 +285,10 @@ int fail(pdeopt_ctx* ctx, int code, const char* fmt, ...);
 // the 2-D stencil equations' short names in the one-launch solves' last_kernel strings
 inline const char* equation_short_name(int eq) {
   return eq == PDEOPT_EQ_CAHN_HILLIARD ? "CH" : eq == PDEOPT_EQ_ALLEN_CAHN ? "AC" : eq == PDEOPT_EQ_CAHN_HILLIARD_SBM ? "CH-SBM"
-         : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "AC-SBM" : "AD";
+         : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "AC-SBM" : eq == PDEOPT_EQ_ALLEN_CAHN_BV ? "AC-BV" : eq == PDEOPT_EQ_ALLEN_CAHN_SBM_BV ? "AC-SBM-BV" : "AD";
 }
+// the Butler-Volmer equations run their own two kernels (butler_volmer.hip) behind the stage launcher and nothing else
+inline bool bv_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_BV || eq == PDEOPT_EQ_ALLEN_CAHN_SBM_BV; }
 
 #define PDEOPT_HIP_CHECK(ctx, expr)                                                        \
   do {                                                                                      \
@@ -444,6 +448,13 @@ void gpe_obs_destroy(pdeopt_ctx* ctx);
 // gpe_adjoint.hip: its buffers live and die with the spectral state (spectral_destroy / spectral_invalidate)
 void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_adjoint_destroy(pdeopt_ctx* ctx);
+// butler_volmer.hip: parameters of the Butler-Volmer equations; the voltage of the resident state (recompute) or the one
+// the last right-hand side used; its buffers live and die with the field buffers
+int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env);
+int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, bool recompute);
+void bv_destroy(pdeopt_ctx* ctx);
+// does the right-hand side depend on t?  (a voltage protocol v(t) registered for the given-voltage mode)
+bool bv_time_dependent(const pdeopt_ctx* ctx);
 void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);

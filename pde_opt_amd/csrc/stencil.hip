@@ -54,7 +54,8 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const Window& w, double t, const void* i
   s.ngp = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
   s.mask = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
   s.fe = closure_spec(p.fe);
-  if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || p.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM) {
+  // (Butler-Volmer at a given voltage: tv[0] is the voltage protocol's v(t), added to the per-environment v)
+  if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || p.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM || bv_equation(p.equation)) {
     double tv[3] = {ctx->time_const[0], ctx->time_const[1], ctx->time_const[2]};
     // the table of pdeopt_set_time_table first (stage times arrive in order: resume at the cursor), the host callback
     // for times it does not hold
@@ -217,6 +218,11 @@ int launch_stage_path(pdeopt_ctx* ctx, const Window& w, double t, const void* in
   StageArgs<T> s = make_args<T>(ctx, w, t, in, y, out, acc, a, b, out_mode, acc_mode);
   extra(s);
   ctx->n_stage_launches++;
+  if (bv_equation(ctx->prob.equation)) {
+    if (ctx->prob.derivs != PDEOPT_DERIVS_FD || ctx->halo)
+      return fail(ctx, PDEOPT_EINVAL, "the Butler-Volmer equations run finite differences on the periodic layout only");
+    return launch_bv_stage<T>(ctx, w, s);
+  }
   if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER) return launch_stage_fourier<T>(ctx, w, s, in, out);
   if (ctx->opt_kernel_path != 1 && tiled_supported<T>(ctx)) return launch_tiled<T>(ctx, w, s);
   if (refuse_forced_tiled && ctx->opt_kernel_path == 2)
@@ -349,7 +355,8 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     return fail(ctx, PDEOPT_EINVAL, "integrator %d is not an explicit fixed-step integrator", integrator);
   }
   // work field of the two-pass 3-D right-hand side: allocated here, never inside a stream capture
-  if (ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D && (rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes)))
+  if ((ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D || bv_equation(ctx->prob.equation)) &&
+      (rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes)))
     return rc;
   // Environments are independent, so the substep loop may run group by group: a group whose
   // working set (4 fields x group x nx x ny) fits the 256 MiB Infinity Cache keeps every stage's
@@ -358,7 +365,8 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   const int batch = ctx->prob.batch;
   // time-dependent terms evaluated by the host per stage (smoothed-boundary scalars, advection velocities)
   const bool timed = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM ||
-                     has_time_aux(ctx, PDEOPT_AUX_VX_FACE) || has_time_aux(ctx, PDEOPT_AUX_VY_FACE);
+                     has_time_aux(ctx, PDEOPT_AUX_VX_FACE) || has_time_aux(ctx, PDEOPT_AUX_VY_FACE) ||
+                     bv_time_dependent(ctx);  // (a voltage protocol v(t): the whole batch per sweep, no graph)
   int group = batch;
   bool side_by_side = false;
   if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER || timed) {

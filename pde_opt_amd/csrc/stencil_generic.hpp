@@ -407,4 +407,9 @@ bool jit_closures_active(const pdeopt_ctx* ctx);
 template <typename T>
 int launch_jit_stage(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s);
 
+// butler_volmer.hip: the right-hand side of the Butler-Volmer equations (two launches at constant current, one at a
+// given voltage), the stage update fused into its last kernel
+template <typename T>
+int launch_bv_stage(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s);
+
 }  // namespace pdeopt

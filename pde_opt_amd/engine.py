@@ -297,6 +297,24 @@ class HipEngine:
         a = np.ascontiguousarray(np.atleast_1d(np.asarray(rate, dtype=np.float64)))
         self._check(self._lib.pdeopt_set_env_gpe_omega_rate(self._h, int(env_first), a.shape[0], a.ctypes.data_as(C.c_void_p)))
 
+    def set_bv_params(self, alpha: float, mode: int, values):
+        """Butler-Volmer equations: the shared symmetry factor, ``mode`` (``L.BV_VOLTAGE`` / ``L.BV_CONSTANT_CURRENT``)
+        and one number per environment -- the voltage v or the current C (a scalar is broadcast)"""
+        v = np.broadcast_to(np.asarray(values, dtype=np.float64).reshape(-1), (self.batch,))
+        per_env = np.zeros((self.batch, 2), dtype=np.float64)
+        per_env[:, 0] = v
+        self._check(self._lib.pdeopt_set_bv_params(self._h, float(alpha), int(mode), per_env.ctypes.data_as(C.c_void_p)))
+
+    def bv_voltage(self, env_first: int = 0, env_count: Optional[int] = None, last: bool = False) -> np.ndarray:
+        """the voltage of the constant-current constraint on the resident state, per environment (``pdeopt_bv_voltage``):
+        bitwise the v a right-hand side of that state uses; ``last=True``: the v the last right-hand side used, as left
+        on the device"""
+        n = self.batch - env_first if env_count is None else env_count
+        out = np.empty(n, dtype=np.float64)
+        fn = self._lib.pdeopt_bv_last_voltage if last else self._lib.pdeopt_bv_voltage
+        self._check(fn(self._h, int(env_first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def set_integrator_params(self, imex_A=0.5, time_scale=1.0, strang_dx=1.0):
         ts = complex(time_scale)
         self._check(

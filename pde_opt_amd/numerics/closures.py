@@ -4,7 +4,7 @@ Upstream these are arbitrary Python callables traced by ``jax.jit`` into the RHS
 fields pde_opt/numerics/equations/cahn_hilliard.py:51-54, allen_cahn.py:47-50).  A HIP kernel
 needs a closed family; the one implemented (include/pdeopt_hip.h) is
 
-    f(c) = series(c) [+ log(c / (1 - c))] [+ c log c + (1 - c) log(1 - c)]  [then exp(.)]
+    f(c) = series(c) [+ log(c / (1 - c))] [+ c log c + (1 - c) log(1 - c)]  [then exp(.)]  [then sqrt(.)]
 
 with ``series`` a polynomial in ``c`` or a Legendre series in ``2c - 1``.  ``as_closure`` turns a
 user callable into a descriptor by evaluating it once on a symbolic variable (sympy) and matching
@@ -22,6 +22,7 @@ import numpy as np
 
 POLY, LEGENDRE, JIT = 0, 1, 2
 LOGIT_PRIOR, EXP_WRAP, MIX_ENTROPY = 1, 2, 4
+SQRT_WRAP = 8  # then sqrt(.): evaluated by the Butler-Volmer kernels only (csrc/butler_volmer.hip)
 MAX_COEF = 16
 
 
@@ -73,6 +74,8 @@ class ClosureDesc:
             r = r + c * np.log(c) + (1 - c) * np.log(1 - c)
         if self.flags & EXP_WRAP:
             r = np.exp(r)
+        if self.flags & SQRT_WRAP:
+            r = np.sqrt(r)
         return r
 
     def with_coef(self, coef: Sequence[float]) -> "ClosureDesc":
@@ -165,9 +168,30 @@ class _Sym:
     def exp(self): return np.exp(self)
 
 
-def _match(expr, c):
+def _match_sqrt(expr, c):
+    """``a sqrt(p(c))`` with a polynomial p and a number a > 0 -> the family member of p(c) a^2 with SQRT_WRAP, else None
+    (the exchange current sqrt((1 - c) c) of notebooks/run_butler_volmer_sbm.ipynb)"""
     import sympy as sp
 
+    a, root = sp.sympify(expr).as_coeff_Mul()
+    if not (isinstance(root, sp.Pow) and root.exp == sp.Rational(1, 2) and a.is_number and a > 0):
+        return None
+    inner = sp.expand(a**2 * root.base)
+    if not inner.is_polynomial(c) or inner.free_symbols - {c}:
+        return None
+    coef = [float(v) for v in reversed(sp.Poly(inner, c).all_coeffs())]
+    if len(coef) > MAX_COEF:
+        return None
+    return ClosureDesc(POLY, SQRT_WRAP, tuple(coef))
+
+
+def _match(expr, c, sqrt_wrap: bool = False):
+    import sympy as sp
+
+    if sqrt_wrap:
+        hit = _match_sqrt(expr, c)
+        if hit is not None:
+            return hit
     flags = 0
     e = sp.expand(sp.expand_log(sp.sympify(expr), force=True))
     if e.has(sp.exp):
@@ -304,28 +328,33 @@ def _cache_key(fn):
     return (code, tuple(cells), tuple(defaults))
 
 
-def as_closure(fn) -> ClosureDesc:
-    """Descriptor for a user closure: ``ClosureDesc``, number, Legendre object or callable."""
+def as_closure(fn, sqrt_wrap: bool = False) -> ClosureDesc:
+    """Descriptor for a user closure: ``ClosureDesc``, number, Legendre object or callable.  ``sqrt_wrap``: the caller's
+    kernels evaluate ``SQRT_WRAP`` (the Butler-Volmer equations): ``sqrt(polynomial)`` is recognised as that member;
+    everywhere else a descriptor carrying the flag is refused."""
     if isinstance(fn, ClosureDesc):
+        if fn.flags & SQRT_WRAP and not sqrt_wrap:
+            raise UnsupportedClosureError("SQRT_WRAP closures are evaluated by the Butler-Volmer kernels only")
         return fn
     key = _cache_key(fn) if callable(fn) else None
     if key is not None:
+        key = key + (bool(sqrt_wrap),)
         hit = _trace_cache.get(key)
         if hit is not None:
             return hit
-        desc = _as_closure_uncached(fn)
+        desc = _as_closure_uncached(fn, sqrt_wrap)
         if len(_trace_cache) > 512:
             _trace_cache.clear()
         _trace_cache[key] = desc
         return desc
-    return _as_closure_uncached(fn)
+    return _as_closure_uncached(fn, sqrt_wrap)
 
 
-def _as_closure_uncached(fn) -> ClosureDesc:
+def _as_closure_uncached(fn, sqrt_wrap: bool = False) -> ClosureDesc:
     if isinstance(fn, ClosureDesc):
-        return fn
+        return as_closure(fn, sqrt_wrap)
     if hasattr(fn, "closure_desc"):
-        return fn.closure_desc()
+        return as_closure(fn.closure_desc(), sqrt_wrap)
     if isinstance(fn, numbers.Real):
         return constant(float(fn))
     if not callable(fn):
@@ -343,7 +372,7 @@ def _as_closure_uncached(fn) -> ClosureDesc:
             "use operators / numpy ufuncs (np.log, np.exp) on the argument, or pass a ClosureDesc"
         ) from e
     if isinstance(out, _Sym):
-        return _match(out.e, c)
+        return _match(out.e, c, sqrt_wrap)
     if isinstance(out, numbers.Real):
         return constant(float(out))
     if isinstance(out, np.ndarray) and out.ndim == 0:
