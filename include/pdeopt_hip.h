@@ -549,6 +549,14 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out);
  * (Allen-Cahn has no fourier_symbol).  The number of launches per substep does not depend on P.  Asynchronous like
  * pdeopt_advance. */
 int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps);
+/* Butler-Volmer Allen-Cahn (PDEOPT_EQ_ALLEN_CAHN_BV / _SBM_BV) rides the same calls: pdeopt_set_bv_params comes BEFORE
+ * pdeopt_sens_configure, its per_env holds the B trajectories' currents (or voltages) and zeros for the tangent
+ * environments, which never read theirs; PDEOPT_SENS_MOB is the exchange current j0; Euler and RK4 as for Allen-Cahn; a
+ * voltage protocol v(t) is refused (the advance is autonomous).  At constant current the tangent of the voltage couples
+ * every cell of a trajectory: 2 P more fixed-order fp64 sums per right-hand side, two launches whatever P is, no atomics.
+ * pdeopt_sens_bv_voltage: v and dv/dp_j of the constant-current constraint on the RESIDENT state, out [B][1 + P]
+ * doubles; out[b][0] is bitwise the v of pdeopt_bv_voltage.  Mode 1 only.  The state is not modified. */
+int pdeopt_sens_bv_voltage(pdeopt_ctx* ctx, double* out);
 /* the observed frames of a fit, uploaded once -- or the cotangents of an objective, uploaded per gradient evaluation
  * (pdeopt_sens_contract): host is [n_frames][B][nx][ny] (3-D: [n_frames][B][nx][ny][nz]) in the problem dtype */
 int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host);

@@ -203,6 +203,7 @@ _SIGNATURES = {
     "pdeopt_sens_configure": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP]),
     "pdeopt_sens_rhs": (C.c_int, [_VP, _VP]),
     "pdeopt_sens_advance": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.c_int64]),
+    "pdeopt_sens_bv_voltage": (C.c_int, [_VP, _VP]),
     "pdeopt_sens_set_data": (C.c_int, [_VP, C.c_int, _VP]),
     "pdeopt_sens_accumulate": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
     "pdeopt_sens_contract": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),

@@ -219,6 +219,282 @@ __global__ __launch_bounds__(64) void bv_finish_kernel(const double* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Tangent-linear right-hand side (forward-mode sensitivities: sens.hip; PDEModel.train on the Butler-Volmer classes).
+// The batch is [(1 + P) B][nx][ny]: tangent j of trajectory b is environment B + j B + b.  For the state tangent du of
+// parameter p_j (a coefficient of mu_h, or of the exchange current j0):
+//   dmu   = mu_h'(u) du - kappa L(du) + [role_j = MU] dmu_h/dp_j          L: the forward stencil (bv_stencil_lap)
+//   dj0   = j0'(u) du + [role_j = MOB] dj0/dp_j                            (SQRT_WRAP: j0 = sqrt(r), dj0 = dr / (2 sqrt r))
+//   dS+-  = sum w (dj0 exp(+-mu/2) +- 1/2 j0 exp(+-mu/2) dmu)              fp64, the order of the forward sums
+//   dy    = (dI+ I- + I+ dI-) / (s I+) - y dI+ / I+,   dv = 2 dy / y       s = sqrt(C^2 + 4 I+ I-), I+- = h2 S+-
+//   drate = dj0 (e^{-alpha eta} - e^{(1-alpha) eta}) - j0 (alpha e^{-alpha eta} + (1-alpha) e^{(1-alpha) eta}) (dmu + dv)
+// Constant current, two launches over the tangent block whatever P is (the base block's slope, mu and partials come from
+// launch_bv_stage over the window [0, B), so the base trajectory keeps the bits of a plain solve):
+//   pass 1  bvsens_tile_kernel<.., 1>  grid (tiles, B): the base tile once, then per tangent the du tile -> dmu_j into the
+//                                      work field at the tangent environment, the workgroup's two sums -> dpart[b][j][wg][2]
+//   pass 2  bvsens_rate_kernel         every workgroup adds the base partials and its trajectory's tangent partials itself
+//                                      (bv_sum_partials), forms v and dv_j, writes drate_j
+// Given voltage (dv = 0): bvsens_tile_kernel<.., 0> alone, drate_j straight from the tiles.  Each tangent is reduced
+// inside the tangent loop: P is a run-time value and no per-thread array is indexed by j.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+struct BvSensArgs {
+  BvArgs<T> f;     // window [0, B) of the forward arguments; f.s.in is the whole batch (the state or a stage value)
+  T* out;          // slopes of the whole batch: the kernels write the tangent block
+  double* dpart;   // [B][P][nwg][2]
+  double* dv;      // [B][1 + P]: v and dv_j (bvsens_finish_kernel)
+  int B, P;
+  int role[kMaxSens], index[kMaxSens];
+};
+
+namespace {
+
+// the basis function of coefficient k at c: c^k or P_k(2c - 1) (the recurrence of series_generic)
+template <typename T>
+__device__ __forceinline__ T bv_basis(const ClosureSpec& s, int k, T c) {
+  T b = T(1);
+  if (s.kind == PDEOPT_CL_POLY) {
+    for (int q = 0; q < k; ++q) b *= c;
+  } else if (k > 0) {
+    const T x = T(2) * c - T(1);
+    T pm = T(1);
+    b = x;
+    for (int q = 2; q <= k; ++q) {
+      const T pn = (T(2 * q - 1) * x * b - T(q - 1) * pm) / T(q);
+      pm = b;
+      b = pn;
+    }
+  }
+  return b;
+}
+
+// what a cell keeps of a closure for the tangent loop: the value f, df/dc, and g with df/dcoef[k] = g B_k(c)
+template <typename T>
+struct BvClosureJet {
+  T f, dc, g;
+};
+template <typename T>
+__device__ __forceinline__ BvClosureJet<T> bv_closure_jet(const ClosureSpec& s, const T* __restrict__ coef, T c) {
+  const T r = closure_generic<T>(s, coef, c);  // before the square root
+  BvClosureJet<T> o;
+  o.dc = closure_dc<T>(s, coef, c, r);
+  o.g = (s.flags & PDEOPT_CL_EXP_WRAP) ? r : T(1);
+  o.f = r;
+  if (s.flags & PDEOPT_CL_SQRT_WRAP) {
+    o.f = t_sqrt<T>(r);
+    const T h = T(0.5) / o.f;
+    o.dc *= h;
+    o.g *= h;
+  }
+  return o;
+}
+
+// L(du) at LDS position o: lap5, or (1/psi) div(psi_face grad) with the expressions of bv_mu_at
+template <typename T, bool SBM>
+__device__ __forceinline__ T bv_stencil_lap(const StageArgs<T>& a, const T* __restrict__ sd, const T* __restrict__ sp, int o) {
+  const T u0 = sd[o], xp = sd[o + kBvPitch], xm = sd[o - kBvPitch], yp = sd[o + 1], ym = sd[o - 1];
+  if constexpr (SBM) {
+    const T pc = sp[o], pxp = sp[o + kBvPitch], pxm = sp[o - kBvPitch], pyp = sp[o + 1], pym = sp[o - 1];
+    const T dx_hi = (T(0.5) * (pc + pxp)) * ((xp - u0) * a.rhx), dx_lo = (T(0.5) * (pxm + pc)) * ((u0 - xm) * a.rhx);
+    const T dy_hi = (T(0.5) * (pc + pyp)) * ((yp - u0) * a.rhy), dy_lo = (T(0.5) * (pym + pc)) * ((u0 - ym) * a.rhy);
+    return ((dx_hi - dx_lo) * a.rhx + (dy_hi - dy_lo) * a.rhy) / pc;
+  } else {
+    return lap_at<T>(u0, xp, xm, yp, ym, a.rhx2, a.rhy2);
+  }
+}
+
+// dv = 2 dy / y of the constant-current constraint, from the sums and their tangents
+__device__ __forceinline__ double bv_dvoltage_of(double sp, double sm, double dsp, double dsm, double h2, double C) {
+  const double ip = h2 * sp, im = h2 * sm, dip = h2 * dsp, dim = h2 * dsm;
+  const double s = sqrt(C * C + 4.0 * ip * im);
+  const double y = (s - C) / (2.0 * ip);
+  const double dy = (dip * im + ip * dim) / (s * ip) - y * dip / ip;
+  return 2.0 * dy / y;
+}
+
+}  // namespace
+
+// CURRENT 1: pass 1 of the constant-current tangents; CURRENT 0: the only launch at a given voltage.  grid (tiles, B)
+template <typename T, bool SBM, int CURRENT>
+__global__ __launch_bounds__(256) void bvsens_tile_kernel(const BvSensArgs<T> a) {
+  __shared__ T su[kBvLdsRows * kBvPitch];
+  __shared__ T sdu[kBvLdsRows * kBvPitch];
+  __shared__ T sp[SBM ? kBvLdsRows * kBvPitch : 1];
+  __shared__ double red[8];
+  const StageArgs<T>& s = a.f.s;
+  const int nx = s.g.nx, ny = s.g.ny;
+  const int b = blockIdx.z, i0 = blockIdx.y * kBvRows, j0 = blockIdx.x * kBvCols;
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  const EnvParams<T>& p = s.ep[b];
+  const T kappa = p.kappa;
+  bv_load_tile<T>(su, s.in + (int64_t)b * s.g.bstride, nx, ny, i0, j0, tid);
+  if constexpr (SBM) bv_load_tile<T>(sp, s.psi, nx, ny, i0, j0, tid);
+  __syncthreads();
+  const int j = j0 + threadIdx.x, c = threadIdx.x + 1;
+  // this thread's four cells: what the tangent loop needs of the base state
+  T u0[kBvRpt], mu1[kBvRpt], mug[kBvRpt], j0f[kBvRpt], j0dc[kBvRpt], j0g[kBvRpt];
+  T ca[kBvRpt], cb[kBvRpt];  // CURRENT: w exp(+mu/2), w exp(-mu/2); else the two factors of drate
+  const T alpha = T(a.f.alpha);
+  const T v = CURRENT ? T(0) : T(a.f.par[2 * b] + a.f.v_shift);
+#pragma unroll
+  for (int q = 0; q < kBvRpt; ++q) {
+    const int ri = threadIdx.y + 4 * q, i = i0 + ri;
+    u0[q] = T(0.5);
+    if (i < nx && j < ny) u0[q] = su[(ri + 1) * kBvPitch + c];
+    const BvClosureJet<T> jm = bv_closure_jet<T>(s.mu, p.mu, u0[q]), jj = bv_closure_jet<T>(s.mob, p.mob, u0[q]);
+    mu1[q] = jm.dc;
+    mug[q] = jm.g;
+    j0f[q] = jj.f;
+    j0dc[q] = jj.dc;
+    j0g[q] = jj.g;
+    T mu = T(0);
+    if (i < nx && j < ny) mu = bv_mu_at<T, SBM>(s, p, su, sp, ri + 1, c);
+    if constexpr (CURRENT) {
+      T w = T(1);
+      if constexpr (SBM) w = sp[(ri + 1) * kBvPitch + c];
+      ca[q] = w * t_exp<T>(T(0.5) * mu);
+      cb[q] = w * t_exp<T>(T(-0.5) * mu);
+    } else {
+      const T eta = mu + v;
+      const T e1 = t_exp<T>(-alpha * eta), e2 = t_exp<T>((T(1) - alpha) * eta);
+      ca[q] = e1 - e2;
+      cb[q] = -(j0f[q] * (alpha * e1 + (T(1) - alpha) * e2));
+    }
+  }
+  for (int t = 0; t < a.P; ++t) {
+    if (t) __syncthreads();  // the previous tangent's readers are done with sdu (and with red)
+    const int64_t ebase = ((int64_t)a.B + (int64_t)t * a.B + b) * s.g.bstride;
+    bv_load_tile<T>(sdu, s.in + ebase, nx, ny, i0, j0, tid);
+    __syncthreads();
+    const bool on_mu = a.role[t] == PDEOPT_SENS_MU;
+    const int kc = a.index[t];
+    double accp = 0.0, accm = 0.0;
+#pragma unroll
+    for (int q = 0; q < kBvRpt; ++q) {
+      const int ri = threadIdx.y + 4 * q, i = i0 + ri;
+      if (i < nx && j < ny) {
+        const int o = (ri + 1) * kBvPitch + c;
+        const T d = sdu[o];
+        T dmu = mu1[q] * d - kappa * bv_stencil_lap<T, SBM>(s, sdu, sp, o);
+        T dj0 = j0dc[q] * d;
+        if (on_mu) dmu += mug[q] * bv_basis<T>(s.mu, kc, u0[q]);
+        else dj0 += j0g[q] * bv_basis<T>(s.mob, kc, u0[q]);
+        const int64_t idx = ebase + (int64_t)i * ny + j;
+        if constexpr (CURRENT) {
+          a.f.mu[idx] = dmu;
+          const double hp = 0.5 * (double)j0f[q] * (double)dmu;  // products in fp64 from the T values
+          accp += (double)ca[q] * ((double)dj0 + hp);
+          accm += (double)cb[q] * ((double)dj0 - hp);
+        } else {
+          a.out[idx] = dj0 * ca[q] + cb[q] * dmu;
+        }
+      }
+    }
+    if constexpr (CURRENT) {
+      // the fixed order of bv_mu_sums_kernel: the shuffle tree of each wave, then the four waves in index order
+#pragma unroll
+      for (int sh = 32; sh > 0; sh >>= 1) {
+        accp += __shfl_down(accp, sh, 64);
+        accm += __shfl_down(accm, sh, 64);
+      }
+      if (threadIdx.x == 0) {
+        red[2 * threadIdx.y] = accp;
+        red[2 * threadIdx.y + 1] = accm;
+      }
+      __syncthreads();
+      if (tid < 2) {
+        const double tot = ((red[tid] + red[2 + tid]) + red[4 + tid]) + red[6 + tid];
+        const int wg = blockIdx.y * gridDim.x + blockIdx.x;
+        a.dpart[(((int64_t)b * a.P + t) * a.f.nwg + wg) * 2 + tid] = tot;
+      }
+    }
+  }
+}
+
+// pass 2 of the constant-current tangents, grid (tiles, B): base mu from the work field, dmu_j from its tangent environments
+template <typename T>
+__global__ __launch_bounds__(256) void bvsens_rate_kernel(const BvSensArgs<T> a) {
+  __shared__ double ssum[2];
+  __shared__ double sdv[kMaxSens + 1];  // v, then dv_j
+  const StageArgs<T>& s = a.f.s;
+  const int nx = s.g.nx, ny = s.g.ny;
+  const int b = blockIdx.z, i0 = blockIdx.y * kBvRows, j0 = blockIdx.x * kBvCols;
+  const EnvParams<T>& p = s.ep[b];
+  const double C = a.f.par[2 * b];
+  if (threadIdx.y == 0) {  // wave 0 adds the base partials, as in bv_rate_kernel
+    double s_p, s_m;
+    bv_sum_partials(a.f.partials + (int64_t)b * a.f.nwg * 2, a.f.nwg, threadIdx.x, &s_p, &s_m);
+    if (threadIdx.x == 0) {
+      ssum[0] = s_p;
+      ssum[1] = s_m;
+      sdv[0] = a.f.bv_v[b];  // the v the base block's bv_rate_kernel used and recorded: the same bits, whatever the compiler
+                             // makes of bv_voltage_of next to bv_dvoltage_of here
+    }
+  }
+  __syncthreads();
+  for (int t = threadIdx.y; t < a.P; t += 4) {  // wave w adds the partials of tangents w, w + 4, ...
+    double d_p, d_m;
+    bv_sum_partials(a.dpart + ((int64_t)b * a.P + t) * a.f.nwg * 2, a.f.nwg, threadIdx.x, &d_p, &d_m);
+    if (threadIdx.x == 0) sdv[1 + t] = bv_dvoltage_of(ssum[0], ssum[1], d_p, d_m, a.f.h2, C);
+  }
+  __syncthreads();
+  const T v = T(sdv[0]), alpha = T(a.f.alpha);
+  const int j = j0 + threadIdx.x;
+  int64_t cell[kBvRpt];
+  T u0[kBvRpt], j0dc[kBvRpt], j0g[kBvRpt], ca[kBvRpt], cb[kBvRpt];
+#pragma unroll
+  for (int q = 0; q < kBvRpt; ++q) {
+    const int i = i0 + threadIdx.y + 4 * q;
+    cell[q] = (i < nx && j < ny) ? (int64_t)i * ny + j : -1;
+    T mu = T(0);
+    u0[q] = T(0.5);
+    if (cell[q] >= 0) {
+      const int64_t idx = (int64_t)b * s.g.bstride + cell[q];
+      mu = a.f.mu[idx];
+      u0[q] = s.in[idx];
+    }
+    const BvClosureJet<T> jj = bv_closure_jet<T>(s.mob, p.mob, u0[q]);
+    j0dc[q] = jj.dc;
+    j0g[q] = jj.g;
+    const T eta = mu + v;
+    const T e1 = t_exp<T>(-alpha * eta), e2 = t_exp<T>((T(1) - alpha) * eta);
+    ca[q] = e1 - e2;
+    cb[q] = -(jj.f * (alpha * e1 + (T(1) - alpha) * e2));
+  }
+  for (int t = 0; t < a.P; ++t) {
+    const int64_t ebase = ((int64_t)a.B + (int64_t)t * a.B + b) * s.g.bstride;
+    const bool on_mob = a.role[t] != PDEOPT_SENS_MU;
+    const int kc = a.index[t];
+    const T dv = T(sdv[1 + t]);
+#pragma unroll
+    for (int q = 0; q < kBvRpt; ++q) {
+      if (cell[q] >= 0) {
+        const int64_t idx = ebase + cell[q];
+        T dj0 = j0dc[q] * s.in[idx];
+        if (on_mob) dj0 += j0g[q] * bv_basis<T>(s.mob, kc, u0[q]);
+        a.out[idx] = dj0 * ca[q] + cb[q] * (a.f.mu[idx] + dv);
+      }
+    }
+  }
+}
+
+// pdeopt_sens_bv_voltage: one wave per trajectory, the summation of pass 2 -> dv[b][0] = v, dv[b][1 + j] = dv/dp_j.  v itself
+// is bv_finish_kernel's (launched before this one): pdeopt_bv_voltage's bits by construction
+__global__ __launch_bounds__(64) void bvsens_finish_kernel(const double* __restrict__ partials, const double* __restrict__ dpart,
+                                                           const double* __restrict__ par, int nwg, int P, double h2,
+                                                           const double* __restrict__ bv_v, double* __restrict__ dv) {
+  const int b = blockIdx.x;
+  double s_p, s_m;
+  bv_sum_partials(partials + (int64_t)b * nwg * 2, nwg, threadIdx.x, &s_p, &s_m);  // lane 0 holds the sums
+  const double C = par[2 * b];
+  if (threadIdx.x == 0) dv[(int64_t)b * (1 + P)] = bv_v[b];
+  for (int t = 0; t < P; ++t) {
+    double d_p, d_m;
+    bv_sum_partials(dpart + ((int64_t)b * P + t) * nwg * 2, nwg, threadIdx.x, &d_p, &d_m);
+    if (threadIdx.x == 0) dv[(int64_t)b * (1 + P) + 1 + t] = bv_dvoltage_of(s_p, s_m, d_p, d_m, h2, C);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 struct BvState {
@@ -229,6 +505,10 @@ struct BvState {
   void* partials = nullptr;  // [batch][nwg][2] doubles
   void* v = nullptr;         // [batch] doubles
   int nwg = 0, batch = 0;
+  // tangents (bv_sens_slopes / bv_sens_voltage): [B][P][nwg][2] partial sums and [B][1 + P] voltages, grown on demand
+  void* dpart = nullptr;
+  void* dv = nullptr;
+  size_t dpart_bytes = 0, dv_bytes = 0;
 };
 
 namespace {
@@ -377,13 +657,132 @@ int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, 
   return PDEOPT_OK;
 }
 
+// ---- tangents --------------------------------------------------------------------------------------------------------
+namespace {
+
+int bv_sens_check(pdeopt_ctx* ctx, const BvSensSpec& sp) {
+  int rc;
+  if ((rc = bv_check(ctx))) return rc;
+  if (sp.B < 1 || sp.P < 1 || sp.P > kMaxSens || (int64_t)(1 + sp.P) * sp.B != ctx->prob.batch)
+    return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer tangents: batch %d is not (1 + %d) %d", ctx->prob.batch, sp.P, sp.B);
+  if (bv_time_dependent(ctx))
+    return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer sensitivities are autonomous: a voltage protocol v(t) is not supported");
+  return PDEOPT_OK;
+}
+
+// a buffer of at least `bytes`; a block that is too small is freed after the stream's work, which may still use it
+int bv_grow(pdeopt_ctx* ctx, void** p, size_t* have, size_t bytes) {
+  if (*p && *have >= bytes) return PDEOPT_OK;
+  if (*p) {
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(*p);
+    *p = nullptr;
+    graph_destroy(ctx);
+  }
+  const int rc = ensure_buffer(ctx, p, bytes);
+  if (!rc) *have = bytes;
+  return rc;
+}
+
+template <typename T>
+int bv_sens_args(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out, BvSensArgs<T>* a) {
+  BvState* st = ctx->bv;
+  int rc;
+  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+  if ((rc = bv_grow(ctx, &st->dpart, &st->dpart_bytes, sizeof(double) * 2 * (size_t)st->nwg * sp.B * sp.P))) return rc;
+  if ((rc = bv_grow(ctx, &st->dv, &st->dv_bytes, sizeof(double) * (size_t)sp.B * (1 + sp.P)))) return rc;
+  StageArgs<T> s{};
+  s.g = make_geo(ctx);
+  s.in = static_cast<const T*>(in);
+  set_recip_plain(s, grid_recip(ctx->prob));
+  set_closures<T>(s, ctx, 0);
+  s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
+  *a = BvSensArgs<T>{};
+  a->f = bv_args<T>(ctx, Window{0, sp.B, ctx->stream}, s);
+  a->out = static_cast<T*>(out);
+  a->dpart = static_cast<double*>(st->dpart);
+  a->dv = static_cast<double*>(st->dv);
+  a->B = sp.B;
+  a->P = sp.P;
+  for (int j = 0; j < sp.P; ++j) {
+    a->role[j] = sp.role[j];
+    a->index[j] = sp.index[j];
+  }
+  return PDEOPT_OK;
+}
+
+template <typename T, int CURRENT>
+void bv_sens_launch_tiles(pdeopt_ctx* ctx, const BvSensArgs<T>& a) {
+  const dim3 grid = bv_grid(ctx, a.B), block(64, 4, 1);
+  if (ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV)
+    hipLaunchKernelGGL((bvsens_tile_kernel<T, true, CURRENT>), grid, block, 0, ctx->stream, a);
+  else
+    hipLaunchKernelGGL((bvsens_tile_kernel<T, false, CURRENT>), grid, block, 0, ctx->stream, a);
+}
+
+}  // namespace
+
+// the tangent block of `out` = J_f(in) du_j + df/dp_j.  Constant current: the base block's launch_bv_stage of the same
+// `in` has left mu in KS[0, B) and the base partials (sens_slopes runs it first)
+int bv_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out) {
+  int rc;
+  if ((rc = bv_sens_check(ctx, sp))) return rc;
+  const bool current = ctx->bv->mode == 1;
+  rc = with_dtype(ctx, [&](auto tag) -> int {
+    using T = decltype(tag);
+    BvSensArgs<T> a;
+    const int r = bv_sens_args<T>(ctx, sp, in, out, &a);
+    if (r) return r;
+    if (current) {
+      bv_sens_launch_tiles<T, 1>(ctx, a);
+      hipLaunchKernelGGL(bvsens_rate_kernel<T>, bv_grid(ctx, a.B), dim3(64, 4, 1), 0, ctx->stream, a);
+    } else {
+      bv_sens_launch_tiles<T, 0>(ctx, a);
+    }
+    return PDEOPT_OK;
+  });
+  if (rc) return rc;
+  ctx->n_stage_launches += current ? 2 : 1;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+// v and dv/dp_j of the resident state, host_out [B][1 + P]: forward pass 1 on the base block, tangent pass 1, one wave per
+// trajectory (bv_finish_kernel for v, bvsens_finish_kernel for dv_j).  The work field KS is overwritten; the state is not
+int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out) {
+  int rc;
+  if ((rc = bv_sens_check(ctx, sp))) return rc;
+  BvState* st = ctx->bv;
+  if (st->mode != 1) return fail(ctx, PDEOPT_EINVAL, "pdeopt_sens_bv_voltage differentiates the constant-current constraint: set mode 1");
+  rc = with_dtype(ctx, [&](auto tag) -> int {
+    using T = decltype(tag);
+    BvSensArgs<T> a;
+    const int r = bv_sens_args<T>(ctx, sp, ctx->Y, nullptr, &a);
+    if (r) return r;
+    bv_launch_pass1<T>(ctx, Window{0, sp.B, ctx->stream}, a.f);
+    bv_sens_launch_tiles<T, 1>(ctx, a);
+    hipLaunchKernelGGL(bv_finish_kernel, dim3(sp.B), dim3(64), 0, ctx->stream, a.f.partials, a.f.par, a.f.nwg, a.f.h2, a.f.bv_v);
+    hipLaunchKernelGGL(bvsens_finish_kernel, dim3(sp.B), dim3(64), 0, ctx->stream, a.f.partials, a.dpart, a.f.par, a.f.nwg, a.P, a.f.h2,
+                       a.f.bv_v, a.dv);
+    return PDEOPT_OK;
+  });
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->last_kernel = "bv_mu_sums+bvsens_tile+bv_finish+bvsens_finish";
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, st->dv, sizeof(double) * (size_t)sp.B * (1 + sp.P), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+bool bv_params_set(const pdeopt_ctx* ctx) { return ctx->bv && ctx->bv->set && ctx->bv->batch == ctx->prob.batch; }
+
 bool bv_time_dependent(const pdeopt_ctx* ctx) {
   return bv_equation(ctx->prob.equation) && ctx->bv && ctx->bv->mode == 0 && (ctx->time_fn != nullptr || !ctx->tt_times.empty());
 }
 
 void bv_destroy(pdeopt_ctx* ctx) {
   if (!ctx->bv) return;
-  for (void* q : {ctx->bv->par, ctx->bv->partials, ctx->bv->v})
+  for (void* q : {ctx->bv->par, ctx->bv->partials, ctx->bv->v, ctx->bv->dpart, ctx->bv->dv})
     if (q) (void)hipFree(q);
   delete ctx->bv;
   ctx->bv = nullptr;

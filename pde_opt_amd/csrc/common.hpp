@@ -455,6 +455,19 @@ int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, 
 void bv_destroy(pdeopt_ctx* ctx);
 // does the right-hand side depend on t?  (a voltage protocol v(t) registered for the given-voltage mode)
 bool bv_time_dependent(const pdeopt_ctx* ctx);
+// the tangent-linear right-hand side of those equations (sens.hip drives it): the P parameters of B trajectories in the
+// layout of pdeopt_sens_configure.  bv_sens_slopes writes the tangent block of `out` for the whole-batch field `in` (at
+// constant current after the base block's own slope launch of the same `in`); bv_sens_voltage returns v and dv/dp_j of the
+// resident state, [B][1 + P]
+constexpr int kMaxSens = 2 * PDEOPT_CLOSURE_MAX_COEF;
+struct BvSensSpec {
+  int B, P;
+  const int* role;
+  const int* index;
+};
+int bv_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out);
+int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out);
+bool bv_params_set(const pdeopt_ctx* ctx);  // has pdeopt_set_bv_params been called for this batch?
 void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);

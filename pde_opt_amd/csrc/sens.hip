@@ -17,6 +17,9 @@
 //          tangent values, then one pointwise update of the stage input and the accumulator -- the exact derivative of
 //          the discrete step.  3 launches per stage, 12 per substep, whatever P is.
 // IMEX is Cahn-Hilliard only: Allen-Cahn publishes no fourier_symbol.
+// The Butler-Volmer Allen-Cahn equations (PDEOPT_EQ_ALLEN_CAHN_BV / _SBM_BV; Euler and RK4 like Allen-Cahn) take their
+// tangent slopes from butler_volmer.hip (bv_sens_slopes): at constant current the voltage couples every cell of a
+// trajectory, so the tangent of a slope needs 2 P more global sums -- two launches over the tangent block, whatever P is.
 //
 // At a save point the tangents are reduced on the device: to the Gauss-Newton sums of a least-squares fit
 // (pdeopt_sens_accumulate) or, for the gradient of a general objective J(ys) (PDEModel.optimize, pde_model.py:462-551),
@@ -28,8 +31,6 @@
 #include "sens_tile.hpp"
 
 namespace pdeopt {
-
-constexpr int kMaxSens = 2 * PDEOPT_CLOSURE_MAX_COEF;
 
 struct Sens {
   int B = 0, P = 0;
@@ -593,6 +594,10 @@ int sens_slopes(pdeopt_ctx* ctx, const void* in, void* out) {
   int rc;
   // the base block's slope; the tangent blocks' slopes come from the kernels below
   if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, in, out, 0.0))) return rc;
+  if (bv_equation(ctx->prob.equation)) {
+    const Sens& s = *ctx->sens;
+    return bv_sens_slopes(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, in, out);
+  }
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
     return ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? launch_tangent_rhs3d<T>(ctx, in, out) : launch_tangent_rhs<T>(ctx, in, out);
@@ -714,9 +719,12 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
   const pdeopt_problem& p = ctx->prob;
   const bool ch2d = p.equation == PDEOPT_EQ_CAHN_HILLIARD && p.nz <= 1, ch3d = p.equation == PDEOPT_EQ_CAHN_HILLIARD_3D;
   const bool ac2d = p.equation == PDEOPT_EQ_ALLEN_CAHN && p.nz <= 1;
-  if (!(ch2d || ch3d || ac2d) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
-    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D or 3-D Cahn-Hilliard equation or the periodic 2-D Allen-Cahn "
-                                    "equation with derivs=\"fd\"");
+  const bool bv = bv_equation(p.equation) && p.nz <= 1;
+  if (!(ch2d || ch3d || ac2d || bv) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
+    return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D or 3-D Cahn-Hilliard equation, the periodic 2-D Allen-Cahn "
+                                    "equation or a Butler-Volmer Allen-Cahn equation, with derivs=\"fd\"");
+  if (bv && !bv_params_set(ctx))
+    return fail(ctx, PDEOPT_ESTATE, "Butler-Volmer sensitivities need pdeopt_set_bv_params before pdeopt_sens_configure");
   if (ch3d && sens_cells(ctx) > (int64_t)INT32_MAX / 2)
     return fail(ctx, PDEOPT_EINVAL, "3-D sensitivities index cells in 32 bits (%dx%dx%d)", p.nx, p.ny, p.nz);
   if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT)
@@ -765,7 +773,8 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN;
+  const bool bv = bv_equation(ctx->prob.equation);
+  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN || bv;  // Euler and RK4, no fourier_symbol
   bool fused = false;
   if (integrator == PDEOPT_INT_IMEX) {
     if (ac) return fail(ctx, PDEOPT_EINVAL, "Allen-Cahn sensitivities support the Euler and RK4 integrators (it has no fourier_symbol)");
@@ -803,9 +812,19 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   // after the loop: the base slope launches name their own kernel
-  ctx->last_kernel = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : (ac ? "sens_ac_tangent_rhs" : "sens_tangent_rhs");
+  ctx->last_kernel = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : (bv ? "bvsens_tangent_rhs" : (ac ? "sens_ac_tangent_rhs" : "sens_tangent_rhs"));
   ctx->last_kernel += integrator == PDEOPT_INT_RK4 ? "+rk4" : (integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : "+imex_rocfft_r2c"));
   return PDEOPT_OK;
+}
+
+int pdeopt_sens_bv_voltage(pdeopt_ctx* ctx, double* out) {
+  if (!ctx || !out) return PDEOPT_EINVAL;
+  const int rc = check_sens(ctx);
+  if (rc) return rc;
+  if (!bv_equation(ctx->prob.equation)) return fail(ctx, PDEOPT_EINVAL, "pdeopt_sens_bv_voltage belongs to the Butler-Volmer equations");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const Sens& s = *ctx->sens;
+  return bv_sens_voltage(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, out);
 }
 
 int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {

@@ -299,10 +299,14 @@ class HipEngine:
 
     def set_bv_params(self, alpha: float, mode: int, values):
         """Butler-Volmer equations: the shared symmetry factor, ``mode`` (``L.BV_VOLTAGE`` / ``L.BV_CONSTANT_CURRENT``)
-        and one number per environment -- the voltage v or the current C (a scalar is broadcast)"""
-        v = np.broadcast_to(np.asarray(values, dtype=np.float64).reshape(-1), (self.batch,))
+        and one number per environment -- the voltage v or the current C (a scalar is broadcast; fewer than ``batch``
+        numbers are those of the trajectories of a sensitivity batch, whose tangent environments read none)"""
+        v = np.asarray(values, dtype=np.float64).reshape(-1)
         per_env = np.zeros((self.batch, 2), dtype=np.float64)
-        per_env[:, 0] = v
+        if 1 < v.size < self.batch:  # a sensitivity batch: the B trajectories' numbers, zeros for the tangent environments
+            per_env[:v.size, 0] = v
+        else:
+            per_env[:, 0] = np.broadcast_to(v, (self.batch,))
         self._check(self._lib.pdeopt_set_bv_params(self._h, float(alpha), int(mode), per_env.ctypes.data_as(C.c_void_p)))
 
     def bv_voltage(self, env_first: int = 0, env_count: Optional[int] = None, last: bool = False) -> np.ndarray:
@@ -426,6 +430,14 @@ class HipEngine:
 
     def sens_advance(self, integrator: int, dt: float, n_substeps: int, t0: float = 0.0):
         self._check(self._lib.pdeopt_sens_advance(self._h, int(integrator), float(t0), float(dt), int(n_substeps)))
+
+    def sens_bv_voltage(self) -> np.ndarray:
+        """``(B, 1 + P)`` fp64: the voltage of the constant-current constraint on the resident state and its tangents
+        ``dv/dp_j`` (``pdeopt_sens_bv_voltage``); column 0 is bitwise ``bv_voltage()`` of the trajectories"""
+        B, P = self.sens_shape
+        out = np.empty((B, 1 + P), dtype=np.float64)
+        self._check(self._lib.pdeopt_sens_bv_voltage(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def sens_set_data(self, frames):
         """observed frames ``(n_frames, B, *spatial)``, uploaded once per fit (or the cotangents ``sens_contract`` reads)"""

@@ -12,8 +12,11 @@ every save point with the same tangents (``pdeopt_sens_contract``): ``SolutionOb
 user's objective into ``(J, dJ/dys)``, ``objective_gradient`` assembles the gradient, ``minimize_bfgs`` is the BFGS of
 ``train(method="mse")`` on plain ``value_and_grad`` / ``value`` callables.
 
-Covered: periodic Cahn-Hilliard in 2-D and 3-D (``mu`` / ``D``; IMEX or Euler) and periodic 2-D Allen-Cahn (``mu`` /
-``R``; Euler or RK4), all with ``derivs="fd"``.
+Covered: periodic Cahn-Hilliard in 2-D and 3-D (``mu`` / ``D``; IMEX or Euler), periodic 2-D Allen-Cahn (``mu`` /
+``R``; Euler or RK4) and the three Butler-Volmer Allen-Cahn classes (``mu`` / ``j0``; Euler or RK4; at constant current
+the voltage and its tangents are available at the save points, and ``train`` can fit a voltage curve next to the frames:
+``add_voltage_sums``), all with ``derivs="fd"``.  The scalars of the Butler-Volmer classes (``alpha``, ``kappa``, ``Crate``,
+``v``) are not trainable entries: they go in ``other_parameters``.
 """
 
 from __future__ import annotations
@@ -37,11 +40,19 @@ RTOL = ATOL = 1e-8  # optimistix tolerances of the reference's train (pde_model.
 MAX_DENSE_BFGS_PARAMS = 4096
 
 # closure classes whose coefficient arrays are trainable, and the constructor argument that holds their role
-# ("D" is Cahn-Hilliard's mobility, "R" Allen-Cahn's rate: the engine's second closure either way)
-_ROLES = {"mu": L.SENS_MU, "D": L.SENS_MOB, "R": L.SENS_MOB}
+# ("D" is Cahn-Hilliard's mobility, "R" Allen-Cahn's rate, "j0" the Butler-Volmer exchange current: the engine's second
+# closure every time).  A scalar role (alpha, kappa, Crate) would be a new entry here and a new pdeopt_sens_role.
+_ROLES = {"mu": L.SENS_MU, "D": L.SENS_MOB, "R": L.SENS_MOB, "j0": L.SENS_MOB}
 
 
 # ---- parameters -----------------------------------------------------------------------------------------------------
+
+
+class NotTrainableError(ValueError, NotImplementedError):
+    """``opt_parameters`` names something the sensitivity path cannot train, or nothing at all.  A ``ValueError`` -- the
+    argument is wrong -- and a ``NotImplementedError`` -- training that entry (a scalar such as kappa, alpha or Crate, a plain
+    callable where a Legendre closure belongs) is not implemented: fits of equations without any sensitivity support have
+    always been refused with the latter, and a caller who catches either keeps working as support grows."""
 
 
 @dataclasses.dataclass
@@ -63,16 +74,16 @@ class ParamMap:
         keys, templates, sizes = [], [], []
         for key, value in opt_parameters.items():
             if key not in _ROLES or not isinstance(value, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
-                raise ValueError(
+                raise NotTrainableError(
                     f"opt_parameters[{key!r}]: only the coefficient arrays of ChemicalPotentialLegendrePolynomials / "
-                    "DiffusionLegendrePolynomials in the 'mu' and 'D' (Allen-Cahn: 'R') roles are trainable (kappa and other "
-                    "scalars would move the implicit operator of the solver); pass them in other_parameters")
+                    "DiffusionLegendrePolynomials in the 'mu' and 'D' (Allen-Cahn: 'R', Butler-Volmer: 'j0') roles are trainable "
+                    "(kappa and other scalars would move the implicit operator of the solver); pass them in other_parameters")
             keys.append(key)
             templates.append(value)
             sizes.append(len(value.expansion.params))
         if not keys:
-            raise ValueError("opt_parameters holds no trainable closure")
-        return cls(keys, templates, sizes, _is_allen_cahn(equation_type))
+            raise NotTrainableError("opt_parameters holds no trainable closure")
+        return cls(keys, templates, sizes, _is_allen_cahn(equation_type) or _is_butler_volmer(equation_type))
 
     @property
     def size(self) -> int:
@@ -119,6 +130,14 @@ def _is_allen_cahn(equation_type) -> bool:
     from .numerics.equations.phase_field import AllenCahn2DPeriodic
 
     return isinstance(equation_type, type) and issubclass(equation_type, AllenCahn2DPeriodic)
+
+
+def _is_butler_volmer(equation_type, constant_current_only=False) -> bool:
+    from .numerics.equations import butler_volmer as bv
+
+    if not (isinstance(equation_type, type) and issubclass(equation_type, bv._ButlerVolmer)):
+        return False
+    return not constant_current_only or equation_type._mode == L.BV_CONSTANT_CURRENT
 
 
 def _leaves(obj) -> list:
@@ -216,7 +235,7 @@ def _configure(eng, equation, solver, y0s, pmap_params, t0, t1):
 
 
 def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fields=False, frames_key=None, frames=None,
-                      cotangents=None):
+                      cotangents=None, voltages=None):
     """Solve B trajectories and their P tangents through ``ts``.
 
     ``y0s`` ``(B, *spatial)``, with ``spatial`` ``(nx, ny)`` or ``(nx, ny, nz)``.  ``frames`` ``(T - 1, B, *spatial)``:
@@ -227,14 +246,27 @@ def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fie
 
     ``cotangents`` ``(T - 1, B, *spatial)`` instead of ``frames``: ``dJ/dys`` of an objective at ``ts[1:]`` (``ts[0]``
     contributes nothing: the initial state is data).  They are uploaded at every call -- they change with every
-    evaluation -- and the first return value is ``sum_q <cotangents[q], dys[q]/dp_j>`` per trajectory, ``(B, P)`` fp64."""
+    evaluation -- and the first return value is ``sum_q <cotangents[q], dys[q]/dp_j>`` per trajectory, ``(B, P)`` fp64.
+
+    ``voltages``: a list that receives, per save point (``ts[0]`` included), the ``(B, 1 + P)`` array of the voltage of the
+    constant-current constraint and its tangents ``dv/dp_j`` (``pdeopt_sens_bv_voltage``; the constant-current
+    Butler-Volmer classes).  Every save point must then fall on a step edge -- the voltage of a linearly interpolated
+    state is not the interpolated voltage -- otherwise ``ValueError``."""
     if frames is not None and cotangents is not None:
         raise ValueError("frames and cotangents share one device buffer: pass one of them")
-    if _is_allen_cahn(type(equation)):
+    if _is_butler_volmer(type(equation)):
+        if solver.integrator not in (L.INT_EULER, L.INT_RK4):
+            raise NotImplementedError("Butler-Volmer sensitivities support Euler and RK4")
+        if callable(getattr(equation, "v", None)):
+            raise NotImplementedError("Butler-Volmer sensitivities are autonomous: a voltage protocol v(t) is not supported")
+    elif _is_allen_cahn(type(equation)):
         if solver.integrator not in (L.INT_EULER, L.INT_RK4):
             raise NotImplementedError("Allen-Cahn sensitivities support Euler and RK4")
     elif solver.integrator not in (L.INT_IMEX, L.INT_EULER):
         raise NotImplementedError("sensitivities support SemiImplicitFourierSpectral (IMEX) and Euler")
+    if voltages is not None and not _is_butler_volmer(type(equation), constant_current_only=True):
+        raise ValueError(f"{type(equation).__name__} has no voltage to differentiate: only the constant-current Butler-Volmer "
+                         "classes solve for one")
     y0s = np.asarray(y0s)
     if y0s.dtype not in (np.float32, np.float64):
         y0s = y0s.astype(np.float64)
@@ -252,6 +284,11 @@ def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fie
     out = []
 
     def visit(q, theta):
+        if voltages is not None:
+            if theta is not None:
+                raise ValueError(f"ts[{q}] = {ts[q]!r} is not on a step edge (dt0 = {dt0!r}): the voltage of an interpolated "
+                                 "state is not the interpolated voltage; choose ts on multiples of dt0")
+            voltages.append(eng.sens_bv_voltage())
         if fields:
             out.append(eng.get_state() if theta is None else eng.get_interpolated(theta))
         if reduce_at is not None and q >= 1:
@@ -276,6 +313,17 @@ def unpack_sums(sums: np.ndarray, P: int):
     G[iu] = tot[1 + P:]
     G = G + np.triu(G, 1).T
     return ssr, rdp, G
+
+
+def add_voltage_sums(ssr: float, rdp: np.ndarray, G: np.ndarray, r_v, dv, weight: float):
+    """The Gauss-Newton sums of a fit with the voltage residuals added: ``r_v`` ``(n,)`` = observed - predicted voltage
+    per trajectory and save point, ``dv`` ``(n, P)`` the predicted voltage's tangents, both in fp64; every voltage term
+    is multiplied by ``weight`` (``train`` folds ``voltage_weight M / M_V`` into it, so that ``Objective.M`` stays the
+    number of field residuals).  Returns ``(ssr + w sum r_v^2, rdp + w sum r_v dv_j, G + w sum dv_i dv_j)``."""
+    r_v = np.asarray(r_v, dtype=np.float64).reshape(-1)
+    dv = np.asarray(dv, dtype=np.float64).reshape(r_v.size, -1)
+    w = float(weight)
+    return ssr + w * float(r_v @ r_v), np.asarray(rdp) + w * (dv.T @ r_v), np.asarray(G) + w * (dv.T @ dv)
 
 
 # ---- optimisers -------------------------------------------------------------------------------------------------------
@@ -502,28 +550,30 @@ def objective_gradient(objective: SolutionObjective, ys, spatial_ndim: int, cont
     return J, grad
 
 
-_SUPPORTED = ("CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain, or AllenCahn2DPeriodic on a "
-              "2-D domain")
+_SUPPORTED = ("CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain, or AllenCahn2DPeriodic or a "
+              "Butler-Volmer Allen-Cahn class on a 2-D domain")
 
 
 def reject_unsupported(model):
     """the configurations the sensitivity path covers: periodic Cahn-Hilliard in 2-D or 3-D with IMEX or Euler,
-    periodic 2-D Allen-Cahn with Euler or RK4, FD derivatives.  The equation / domain pair is checked here, before any
+    periodic 2-D Allen-Cahn and the Butler-Volmer Allen-Cahn classes with Euler or RK4, FD derivatives.  The equation / domain pair is checked here, before any
     equation is built."""
     from .numerics.equations.phase_field import AllenCahn2DPeriodic, CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
     from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral
 
     dims = {CahnHilliard2DPeriodic: 2, CahnHilliard3DPeriodic: 3, AllenCahn2DPeriodic: 2}.get(model.equation_type)
+    if _is_butler_volmer(model.equation_type):
+        dims = 2
     if dims is None:
         raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
                                   f"{model.equation_type.__name__}")
     if len(model.domain.points) != dims:
         raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
                                   f"{model.equation_type.__name__} on a {len(model.domain.points)}-D domain")
-    if model.equation_type is AllenCahn2DPeriodic:
+    if model.equation_type is AllenCahn2DPeriodic or _is_butler_volmer(model.equation_type):
         if model.solver_type not in (Euler, RK4):
-            raise NotImplementedError(f"train / residuals sensitivities of AllenCahn2DPeriodic support the Euler and RK4 "
-                                      f"solvers, not {model.solver_type.__name__}")
+            raise NotImplementedError(f"train / residuals sensitivities of {model.equation_type.__name__} support the Euler and "
+                                      f"RK4 solvers, not {model.solver_type.__name__}")
     elif model.solver_type not in (SemiImplicitFourierSpectral, Euler):
         raise NotImplementedError(f"train / residuals sensitivities support the SemiImplicitFourierSpectral and Euler "
                                   f"solvers, not {model.solver_type.__name__}")
@@ -536,6 +586,9 @@ def check_equation(equation):
         raise NotImplementedError("forward-mode sensitivities (train of closure coefficients, optimize) do not run with a "
                                   "torch.nn.Module as mu: the module itself is trained, by train(opt_parameters={'mu': module}, "
                                   "method='mse') or mse_backward, on " + FIELD_MU_SUPPORT)
+    if _is_butler_volmer(type(equation)) and callable(getattr(equation, "v", None)):
+        raise NotImplementedError("Butler-Volmer sensitivities are autonomous: a voltage protocol v(t) is not supported; pass a "
+                                  "number as v")
     if getattr(equation, "derivs", "fd") != "fd":
         raise NotImplementedError('train sensitivities support derivs="fd" only (the tangent kernel differentiates the '
                                   'finite-difference right-hand side)')

@@ -8,7 +8,9 @@ ignored: forward solves need no adjoint.
 ``train`` / ``residuals`` / ``mse`` / ``regularization`` (pde_model.py:138-460) fit closure coefficients to
 trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
 trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D (``mu`` / ``D``; IMEX or
-Euler) and periodic 2-D Allen-Cahn (``mu`` / ``R``; Euler or RK4), with FD derivatives.
+Euler), periodic 2-D Allen-Cahn (``mu`` / ``R``; Euler or RK4) and the Butler-Volmer Allen-Cahn classes (``mu`` / ``j0``;
+Euler or RK4; ``voltage_sensitivities`` and ``train(..., voltage_weight=...)`` add the voltage of a constant-current run), with
+FD derivatives.
 A ``torch.nn.Module`` as ``mu`` of CahnHilliard2DPeriodic (the reference's periodic CNN, optimization_neural_network.ipynb)
 takes the field path of ``pde_opt_amd.fieldmu``: ``solve`` / ``residuals`` / ``mse`` run it forward, ``mse_backward``
 fills the parameters' ``.grad`` by a discrete adjoint on the GPU, ``train(method="mse")`` drives BFGS with it.
@@ -213,7 +215,7 @@ class PDEModel:
         return self._sens_eng
 
     def train(self, data, inds, opt_parameters, other_parameters, solver_parameters, weights, lambda_reg,
-              method="least_squares", max_steps=100):
+              method="least_squares", max_steps=100, voltage_weight=0.0):
         """Fit the closure coefficients in ``opt_parameters`` to ``data`` (pde_model.py:288-460).
 
         ``method="least_squares"``: Levenberg-Marquardt on the Gauss-Newton normal equations (the reference's
@@ -221,6 +223,13 @@ class PDEModel:
         is a state of shape ``spatial``: ``(nx, ny)`` for CahnHilliard2DPeriodic and AllenCahn2DPeriodic,
         ``(nx, ny, nz)`` for CahnHilliard3DPeriodic.  Returns ``{**fitted, **other_parameters}``; each fitted closure is the class it
         started as, with its ``prior_fn``.
+
+        The Butler-Volmer Allen-Cahn classes train ``"mu"`` and ``"j0"`` (Legendre closures; Euler or RK4); their scalars
+        ``alpha``, ``kappa``, ``Crate`` / ``v`` are not trainable and go in ``other_parameters``.  With ``data["vs"]`` -- the cell
+        voltages aligned with ``data["ys"]`` -- and ``voltage_weight > 0`` a constant-current class fits the voltage curve
+        too: the loss is ``mean(r_field^2) + voltage_weight mean(r_V^2) + reg`` with ``r_V`` at the same save points as the
+        frames (``inds[b][1:]``), which must then fall on multiples of the step ``dt0 = 1e-6``.  Without ``"vs"`` or with
+        weight 0 nothing changes; ``"vs"`` with a weight on a given-voltage class raises ``ValueError``.
 
         ``opt_parameters = {"mu": torch.nn.Module}`` (CahnHilliard2DPeriodic, ``method="mse"``): BFGS over the module's
         flattened parameters with the reverse-mode gradient of ``mse_backward``, for up to ``fit.MAX_DENSE_BFGS_PARAMS``
@@ -234,6 +243,14 @@ class PDEModel:
                                       method, max_steps)
         pmap = fit.ParamMap.of(opt_parameters, self.equation_type)
         y0s, values, ts = stack_training_data(data, inds)
+        v_obs = None  # (T - 1, B) observed voltages
+        if voltage_weight and data.get("vs") is not None:
+            if not fit._is_butler_volmer(self.equation_type, constant_current_only=True):
+                raise ValueError(f"data['vs'] with voltage_weight = {voltage_weight!r}: {self.equation_type.__name__} does not solve "
+                                 "for a voltage (only the constant-current Butler-Volmer classes do)")
+            vs = data["vs"]
+            v_obs = np.array([[float(vs[ind[i]]) for ind in inds] for i in range(1, len(inds[0]))], dtype=np.float64)
+            w_v = float(voltage_weight) * values.size / v_obs.size  # mean(r_V^2) weighed against mean(r_field^2) = ssr / M
         equation0 = self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters})
         fit.check_equation(equation0)
         frames = np.ascontiguousarray(np.swapaxes(values, 0, 1))  # (T - 1, B, *spatial)
@@ -250,15 +267,24 @@ class PDEModel:
 
         def sums(p):
             _, equation, solver = setup(p)
+            volt = [] if v_obs is not None else None
             s, _ = fit.sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, frames=frames,
-                                         frames_key=frames_key)
+                                         frames_key=frames_key, voltages=volt)
             ssr, rdp, G = fit.unpack_sums(s, P)
+            if volt is not None:
+                vd = np.stack(volt[1:])  # (T - 1, B, 1 + P)
+                ssr, rdp, G = fit.add_voltage_sums(ssr, rdp, G, v_obs - vd[..., 0], vd[..., 1:], w_v)
             return (ssr,) + pmap.expand(rdp, G)
 
         def ssr(p):
-            params, _, _ = setup(p)
-            r, _ = self.residuals(params, (y0s, values), solver_parameters, ts, {}, 0.0)
-            return float(np.sum(np.asarray(r, dtype=np.float64) ** 2))
+            params, equation, _ = setup(p)
+            if v_obs is None:
+                r, _ = self.residuals(params, (y0s, values), solver_parameters, ts, {}, 0.0)
+                return float(np.sum(np.asarray(r, dtype=np.float64) ** 2))
+            pred = self.solve(params, y0s, ts, solver_parameters)  # (T, B, nx, ny)
+            r = values - np.swapaxes(pred, 0, 1)[:, 1:]
+            r_v = v_obs - np.asarray(equation.get_voltage(pred[1:].reshape((-1,) + pred.shape[2:]))).reshape(v_obs.shape)
+            return float(np.sum(np.asarray(r, dtype=np.float64) ** 2)) + w_v * float(np.sum(r_v ** 2))
 
         obj = fit.Objective(sums=sums, ssr=ssr, M=int(values.size), lambda_reg=float(lambda_reg),
                             w=fit.weight_vector(pmap, weights or {}))
@@ -269,6 +295,34 @@ class PDEModel:
             p, hist = fit.bfgs(obj, p0, max_steps=max_steps)
         self.last_train_history = hist
         return {**pmap.build(p), **other_parameters}
+
+    def voltage_sensitivities(self, opt_parameters, other_parameters, y0s, ts, solver_parameters=None, dt0=0.000001):
+        """``(V (T, B), dV (T, B, P_all))``: the voltage of the constant-current constraint at every ``ts[q]`` (``ts[0]``, the
+        start, included) of the B trajectories from ``y0s`` ``(B, nx, ny)``, and its derivative with respect to every entry
+        of ``opt_parameters`` (``"mu"`` / ``"j0"`` Legendre closures, in ``fit.ParamMap`` order), from the forward-mode
+        tangents advanced on the GPU (``pdeopt_sens_bv_voltage``).  The constant-current Butler-Volmer classes only; the
+        scalars (``alpha``, ``kappa``, ``Crate``) go in ``other_parameters``.  Every ``ts[q]`` must fall on a step edge
+        (``ts[0] + k dt0``, or ``ts[-1]``), otherwise ``ValueError``: the voltage of a linearly interpolated state is not the
+        interpolated voltage."""
+        _reject_rotating(self)
+        fit.reject_unsupported(self)
+        if not fit._is_butler_volmer(self.equation_type, constant_current_only=True):
+            raise NotImplementedError(f"voltage_sensitivities differentiates the constant-current constraint: "
+                                      f"{self.equation_type.__name__} does not solve for a voltage")
+        other_parameters = other_parameters or {}
+        pmap = fit.ParamMap.of(opt_parameters, self.equation_type)
+        equation = self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters})
+        fit.check_equation(equation)
+        solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+        y0s = np.asarray(y0s)
+        if y0s.ndim != 3 or tuple(y0s.shape[1:]) != tuple(self.domain.points):
+            raise ValueError(f"y0s of shape {y0s.shape}: expected (B,) + {tuple(self.domain.points)}")
+        volt = []
+        fit.sensitivity_solve(self._sens_engine(), equation, solver, y0s, ts, pmap.sens_params(), dt0=dt0, voltages=volt)
+        vd = np.stack(volt)  # (T, B, 1 + n active)
+        dV = np.zeros(vd.shape[:2] + (pmap.size,))
+        dV[..., np.nonzero(pmap.active())[0]] = vd[..., 1:]
+        return vd[..., 0].copy(), dV
 
     def optimize(self, objective_function=None, y0=None, ts=None, opt_parameters=None, other_parameters=None,
                  solver_parameters=None, weights=None, lambda_reg=0.0, max_steps=100):

@@ -4,6 +4,12 @@ and microseconds per right-hand side at 1024^2 x 8 next to the Allen-Cahn stage 
 window of calls, WARMUP + ROUNDS windows, the medians reported.
 
     python tools/bv_bench.py [--out profiles/butler_volmer.json]
+
+``--sens``: microseconds per RK4 substep of the forward-mode sensitivity advance (state + P tangents, P = 3 and P = 7:
+Legendre coefficients of mu and j0) next to microseconds per RK4 substep of the plain forward advance of the same B
+trajectories in the same run, at constant current, for 128^2 x 3 and 1024^2 x 8.
+
+    python tools/bv_bench.py --sens [--out profiles/butler_volmer_sens.json]
 """
 import json
 import os
@@ -99,7 +105,44 @@ def rhs_case(dtype, n=1024, batch=8):
     return row
 
 
+def sens_case(dtype, n, batch, substeps):
+    """a smooth state (rates of order one), RK4 substeps of 1e-6: windows of `substeps` substeps, forward and with tangents"""
+    from pde_opt_amd import _lib as L
+    from pde_opt_amd.numerics.closures import EXP_WRAP, LEGENDRE, LOGIT_PRIOR, ClosureDesc
+
+    mu = ClosureDesc(LEGENDRE, LOGIT_PRIOR, (0.1, -3.0, 0.2, 0.05))
+    j0 = ClosureDesc(LEGENDRE, EXP_WRAP, (-0.9, 0.15, 0.05))
+    x = np.arange(n) / n
+    u = 0.15 + 0.05 * np.sin(2 * np.pi * x)[:, None] * np.cos(2 * np.pi * x)[None, :]
+    y0 = np.stack([u + 0.01 * b for b in range(batch)]).astype(dtype)
+    eq = P.AllenCahn2DPeriodicButlerVolmerConstantCurrent(domain(n), KAPPA, mu, j0, 0.5, 0.02)
+    eng = HipEngine(0)
+    row = {"shape": [n, n], "batch": batch, "dtype": np.dtype(dtype).name, "substeps_per_window": substeps, "integrator": "rk4"}
+    load(eng, eq, y0)
+    row["forward_substep_us"] = windows(eng, lambda: eng.advance(L.INT_RK4, 1e-6, substeps), substeps)
+    row["forward_kernel"] = eng.last_kernel
+    for params in ([(0, 0), (0, 1), (1, 0)], [(0, k) for k in range(4)] + [(1, k) for k in range(3)]):
+        Pn = len(params)
+        eng.configure(dtype=y0.dtype, batch=(1 + Pn) * batch, **eq._engine_problem())
+        eq._engine_upload(eng, 0.0, 1.0)
+        eng.sens_configure(batch, params)
+        eng.set_state(np.concatenate([y0, np.zeros((Pn * batch, n, n), dtype=dtype)]))
+        row[f"sens_substep_us_P{Pn}"] = windows(eng, lambda: eng.sens_advance(L.INT_RK4, 1e-6, substeps), substeps)
+        row[f"sens_over_forward_P{Pn}"] = row[f"sens_substep_us_P{Pn}"] / row["forward_substep_us"]
+    row["sens_kernel"] = eng.last_kernel
+    eng.close()
+    return row
+
+
 if __name__ == "__main__":
+    if "--sens" in sys.argv:
+        rows = [sens_case(dt, n, b, k) for n, b, k in ((128, 3, 50), (1024, 8, 10)) for dt in (np.float32, np.float64)]
+        for r in rows:
+            print(json.dumps(r))
+        if "--out" in sys.argv:
+            with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:
+                json.dump({"tool": "tools/bv_bench.py --sens", "rows": rows}, f, indent=1)
+        sys.exit(0)
     rows = [trial_case(np.float32), trial_case(np.float64), rhs_case(np.float32), rhs_case(np.float64)]
     for r in rows:
         print(json.dumps(r))
