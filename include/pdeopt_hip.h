@@ -526,28 +526,40 @@ int pdeopt_tsit5_solve_small(pdeopt_ctx* ctx, double t0, double t1, double dt0, 
  * pde_opt/pde_model.py:138-460)
  * The reference differentiates diffeqsolve with diffrax's ForwardMode adjoint (pde_model.py:410-423) to fill the
  * Jacobian of its Levenberg-Marquardt fit.  Here the P tangent fields du/dp_j ride through the solver as extra
- * environments: configure the ctx with batch (1 + P) B (periodic 2-D or 3-D Cahn-Hilliard, or periodic 2-D Allen-Cahn
- * PDEOPT_EQ_ALLEN_CAHN; derivs "fd"), put the B
+ * environments: configure the ctx with batch (1 + P) B (periodic 2-D or 3-D Cahn-Hilliard, periodic 2-D Allen-Cahn
+ * PDEOPT_EQ_ALLEN_CAHN, or the smoothed-boundary equations PDEOPT_EQ_ALLEN_CAHN_SBM / PDEOPT_EQ_CAHN_HILLIARD_SBM, whose
+ * three SBM aux fields must be uploaded before pdeopt_sens_configure; derivs "fd"), put the B
  * trajectories in environments [0, B) and tangent j of trajectory b in environment B + j B + b (zero at t0: the
  * initial states are data).  pdeopt_get_state / pdeopt_snapshot / pdeopt_get_interpolated read and interpolate the
  * tangents like any environment. */
 typedef enum { PDEOPT_SENS_MU = 0, PDEOPT_SENS_MOB = 1 } pdeopt_sens_role;
 /* the P parameters: parameter j is coefficient coef_index[j] of the closure roles[j]: mu_h, or the problem's second
  * closure (PDEOPT_SENS_MOB: Cahn-Hilliard's mobility D, Allen-Cahn's rate R).  For Allen-Cahn the constant coefficient
- * of mu_h has a tangent like any other (mu_h itself enters the right-hand side); for Cahn-Hilliard it is identically 0 */
+ * of mu_h has a tangent like any other (mu_h itself enters the right-hand side); for Cahn-Hilliard it is identically 0.
+ * The same holds for the smoothed-boundary forms: active for PDEOPT_EQ_ALLEN_CAHN_SBM, identically 0 for
+ * PDEOPT_EQ_CAHN_HILLIARD_SBM (grad(inner) drops a constant).  Their free energy f (the closure `fe`), kappa, theta(t) and
+ * flux(t) are fixed data; all three closures must be of the in-kernel family. */
 int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32_t* roles, const int32_t* coef_index);
 /* TA = the base slopes f(y) and the tangent slopes J_f(y) du_j + df/dp_j of the current state, copied to host_out
  * ([(1 + P) B][nx][ny], or [(1 + P) B][nx][ny][nz] in 3-D; may be NULL).  The tangent-linear right-hand side of
  * cahn_hilliard.py:89-109 (2-D) and :180-200 (3-D), or of allen_cahn.py:81-84:
- *   df_j = -(R'(u) du_j + dR/dp_j) m - R(u) (mu_h'(u) du_j + dmu_h/dp_j - kappa lap5(du_j)),  m = mu_h(u) - kappa lap5(u) */
+ *   df_j = -(R'(u) du_j + dR/dp_j) m - R(u) (mu_h'(u) du_j + dmu_h/dp_j - kappa lap5(du_j)),  m = mu_h(u) - kappa lap5(u)
+ * or of the smoothed-boundary forms (allen_cahn.py:142-159, cahn_hilliard.py:260-289; csrc/sens_sbm.hip), evaluated at
+ * time 0: with the time terms a pdeopt_set_time_terms constant gives, or its callback at t = 0. */
 int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out);
 /* n_substeps of state + tangents: IMEX (solvers.py:56-63: du_1 = du_0 + dt L^-1 [J_f du_0 + df/dp], the implicit
  * operator L shared by base and tangents; the hand-written FFT passes on power-of-two 2-D grids 64..1024, rocFFT's
  * real transforms on other grids and in 3-D), Euler (du_1 = du_0 + dt dk), or -- Allen-Cahn only -- PDEOPT_INT_RK4: the
  * classical tableau over the whole (1 + P) B batch, every stage evaluating the base slope and the tangent slope at the
  * stage's own base and tangent values (the exact derivative of the discrete step).  IMEX is Cahn-Hilliard only
- * (Allen-Cahn has no fourier_symbol).  The number of launches per substep does not depend on P.  Asynchronous like
- * pdeopt_advance. */
+ * (Allen-Cahn has no fourier_symbol).  The smoothed-boundary equations take Euler and RK4 (both of them; the psi-weighted
+ * operator has no fourier_symbol either).  The number of launches per substep does not depend on P.  Asynchronous like
+ * pdeopt_advance.
+ * t0 is the time of the first substep.  The smoothed-boundary equations use it: theta(t) and flux(t) are evaluated at
+ * the stage times t0 + (double) s dt (RK4: + dt / 2, + dt), formed as pdeopt_advance forms them, from the source
+ * pdeopt_advance would ask (constant, pdeopt_set_time_table, pdeopt_set_time_terms callback), once per stage: the base
+ * launch resolves them and the tangent kernel is handed the same numbers.  A table is consumed by the call.  The other
+ * equations are autonomous and ignore t0. */
 int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps);
 /* Butler-Volmer Allen-Cahn (PDEOPT_EQ_ALLEN_CAHN_BV / _SBM_BV) rides the same calls: pdeopt_set_bv_params comes BEFORE
  * pdeopt_sens_configure, its per_env holds the B trajectories' currents (or voltages) and zeros for the tangent

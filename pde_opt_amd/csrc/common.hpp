@@ -193,6 +193,9 @@ struct pdeopt_ctx {
   std::vector<double> tt_times, tt_terms;
   size_t tt_cursor = 0;
   int64_t tt_misses = 0;  // stage times a non-empty table did not hold while no callback was registered
+  // the three scalars the last right-hand-side launch of a time-dependent equation resolved (make_args): the tangent
+  // kernels of the smoothed-boundary equations take theirs from here, so tangent and base see identical numbers
+  double time_last[3] = {0.0, 0.0, 0.0};
   void* env_params_dev = nullptr;
   std::vector<char> env_params_host;
   pdeopt::AuxField aux[pdeopt::kNumAux];
@@ -468,6 +471,11 @@ struct BvSensSpec {
 int bv_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out);
 int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out);
 bool bv_params_set(const pdeopt_ctx* ctx);  // has pdeopt_set_bv_params been called for this batch?
+// sens_sbm.hip: the tangent-linear right-hand side of the smoothed-boundary equations (PDEOPT_EQ_ALLEN_CAHN_SBM /
+// _CAHN_HILLIARD_SBM), same layout: writes the tangent block of `out` for the whole-batch field `in`, with the time terms
+// ctx->time_last of the base block's own slope launch of the same `in` (which sens.hip issues first)
+int sbm_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out);
+inline bool sbm_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM; }
 void sens_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);

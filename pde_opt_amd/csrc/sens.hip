@@ -20,6 +20,9 @@
 // The Butler-Volmer Allen-Cahn equations (PDEOPT_EQ_ALLEN_CAHN_BV / _SBM_BV; Euler and RK4 like Allen-Cahn) take their
 // tangent slopes from butler_volmer.hip (bv_sens_slopes): at constant current the voltage couples every cell of a
 // trajectory, so the tangent of a slope needs 2 P more global sums -- two launches over the tangent block, whatever P is.
+// The smoothed-boundary equations (PDEOPT_EQ_ALLEN_CAHN_SBM / _CAHN_HILLIARD_SBM; Euler and RK4, both of them) take theirs
+// from sens_sbm.hip (sbm_sens_slopes).  They are the one time-dependent case: every slope is evaluated at its stage time
+// t0 + s dt + c_i dt, the base launch resolves theta(t) and flux(t) and the tangent kernel is handed the same numbers.
 //
 // At a save point the tangents are reduced on the device: to the Gauss-Newton sums of a least-squares fit
 // (pdeopt_sens_accumulate) or, for the gradient of a general objective J(ys) (PDEModel.optimize, pde_model.py:462-551),
@@ -46,33 +49,7 @@ struct Sens {
 
 namespace {
 
-// ---- closure derivatives (the family of include/pdeopt_hip.h; values from closure_generic) ------------------------
-
-// 1 / q of the Legendre recurrence below: a multiply per term instead of a division (the tangent kernel evaluates
-// the basis once per cell and tangent)
-__constant__ double kRecip[PDEOPT_CLOSURE_MAX_COEF] = {0.0,       1.0,       1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,
-                                                       1.0 / 6,   1.0 / 7,   1.0 / 8,  1.0 / 9,  1.0 / 10, 1.0 / 11,
-                                                       1.0 / 12,  1.0 / 13,  1.0 / 14, 1.0 / 15};
-
-// df/dcoef[k] at c: the basis function B_k(c) = c^k or P_k(2c - 1), times f under EXP_WRAP
-template <typename T>
-__device__ __forceinline__ T closure_dcoef(const ClosureSpec& s, int k, T c, T f) {
-  T b = T(1);
-  if (s.kind == PDEOPT_CL_POLY) {
-    for (int q = 0; q < k; ++q) b *= c;
-  } else if (k > 0) {
-    const T x = T(2) * c - T(1);
-    T pm = T(1);
-    b = x;
-    for (int q = 2; q <= k; ++q) {
-      const T pn = (T(2 * q - 1) * x * b - T(q - 1) * pm) * T(kRecip[q]);
-      pm = b;
-      b = pn;
-    }
-  }
-  if (s.flags & PDEOPT_CL_EXP_WRAP) b *= f;
-  return b;
-}
+// (closure derivatives: closure_dc in closures.hpp, closure_dcoef in sens_tile.hpp)
 
 template <typename T>
 struct SensArgs {
@@ -589,11 +566,17 @@ int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
   return PDEOPT_OK;
 }
 
-// out = (f(y_base), J_f du_j + df/dp_j) of the whole batch `in` (the state, or an RK4 stage value)
-int sens_slopes(pdeopt_ctx* ctx, const void* in, void* out) {
+// out = (f(t, y_base), J_f du_j + df/dp_j) of the whole batch `in` (the state, or an RK4 stage value).  t matters to the
+// smoothed-boundary equations only (theta(t), flux(t)); callers pass 0.0 for the autonomous ones
+int sens_slopes(pdeopt_ctx* ctx, const void* in, void* out, double t) {
   int rc;
   // the base block's slope; the tangent blocks' slopes come from the kernels below
-  if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, in, out, 0.0))) return rc;
+  if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, in, out, t))) return rc;
+  if (sbm_equation(ctx->prob.equation)) {
+    // the tangent kernel reads the time terms that launch resolved (ctx->time_last): the same numbers, whatever their source
+    const Sens& s = *ctx->sens;
+    return sbm_sens_slopes(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, in, out);
+  }
   if (bv_equation(ctx->prob.equation)) {
     const Sens& s = *ctx->sens;
     return bv_sens_slopes(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, in, out);
@@ -615,9 +598,11 @@ int euler_update(pdeopt_ctx* ctx, double dt) {
   return PDEOPT_OK;
 }
 
-// One classical RK4 substep of the whole (1 + P) B batch: K = TA, stage input TB, accumulator ACC
+// One classical RK4 substep of the whole (1 + P) B batch: K = TA, stage input TB, accumulator ACC.  ts: the substep's
+// start time for the time-dependent equations (stage times ts, ts + dt / 2, ts + dt / 2, ts + dt, formed as
+// advance_explicit forms them), `timed` false: every stage passes 0.0
 template <typename T>
-int rk4_substep(pdeopt_ctx* ctx, double dt) {
+int rk4_substep(pdeopt_ctx* ctx, double dt, double ts, bool timed) {
   const int64_t n = (int64_t)ctx->env_elems * ctx->prob.batch;
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
   T* const y = static_cast<T*>(ctx->Y);
@@ -625,9 +610,10 @@ int rk4_substep(pdeopt_ctx* ctx, double dt) {
   T* const in = static_cast<T*>(ctx->TB);
   T* const acc = static_cast<T*>(ctx->ACC);
   const double a[4] = {dt / 2, dt / 2, dt, 0.0}, b[4] = {dt / 6, dt / 3, dt / 3, dt / 6};
+  const double tst[4] = {ts, ts + dt / 2, ts + dt / 2, ts + dt};
   for (int st = 0; st < 4; ++st) {
     int rc;
-    if ((rc = sens_slopes(ctx, st == 0 ? y : in, k))) return rc;
+    if ((rc = sens_slopes(ctx, st == 0 ? y : in, k, timed ? tst[st] : 0.0))) return rc;
     hipLaunchKernelGGL(sens_rk4_update_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, y, static_cast<const T*>(k), in, acc,
                        (T)a[st], (T)b[st], st == 0 ? 0 : (st == 3 ? 2 : 1), n);
     ctx->n_stage_launches++;
@@ -720,14 +706,19 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
   const bool ch2d = p.equation == PDEOPT_EQ_CAHN_HILLIARD && p.nz <= 1, ch3d = p.equation == PDEOPT_EQ_CAHN_HILLIARD_3D;
   const bool ac2d = p.equation == PDEOPT_EQ_ALLEN_CAHN && p.nz <= 1;
   const bool bv = bv_equation(p.equation) && p.nz <= 1;
-  if (!(ch2d || ch3d || ac2d || bv) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
+  const bool sbm = sbm_equation(p.equation) && p.nz <= 1;
+  if (!(ch2d || ch3d || ac2d || bv || sbm) || p.derivs != PDEOPT_DERIVS_FD || ctx->halo)
     return fail(ctx, PDEOPT_EINVAL, "sensitivities need the periodic 2-D or 3-D Cahn-Hilliard equation, the periodic 2-D Allen-Cahn "
-                                    "equation or a Butler-Volmer Allen-Cahn equation, with derivs=\"fd\"");
+                                    "equation or a Butler-Volmer Allen-Cahn equation, with derivs=\"fd\" (or a 2-D smoothed-boundary "
+                                    "Allen-Cahn / Cahn-Hilliard equation)");
+  if (sbm && (!ctx->aux[PDEOPT_AUX_SBM_PSI].dev || !ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev || !ctx->aux[PDEOPT_AUX_SBM_MASK].dev))
+    return fail(ctx, PDEOPT_ESTATE, "smoothed-boundary sensitivities need the SBM_PSI, SBM_NORM_GRAD and SBM_MASK aux fields before "
+                                    "pdeopt_sens_configure");
   if (bv && !bv_params_set(ctx))
     return fail(ctx, PDEOPT_ESTATE, "Butler-Volmer sensitivities need pdeopt_set_bv_params before pdeopt_sens_configure");
   if (ch3d && sens_cells(ctx) > (int64_t)INT32_MAX / 2)
     return fail(ctx, PDEOPT_EINVAL, "3-D sensitivities index cells in 32 bits (%dx%dx%d)", p.nx, p.ny, p.nz);
-  if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT)
+  if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT || (sbm && p.fe.kind == PDEOPT_CL_JIT))
     return fail(ctx, PDEOPT_EINVAL, "sensitivities need closures of the in-kernel family (POLY / LEGENDRE), not run-time-compiled ones");
   if (n_traj < 1 || n_params < 1 || n_params > kMaxSens)
     return fail(ctx, PDEOPT_EINVAL, "n_traj = %d, n_params = %d (1 .. %d)", n_traj, n_params, kMaxSens);
@@ -757,7 +748,7 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out) {
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA))) return rc;
+  if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA, 0.0))) return rc;
   if (host_out)
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -765,7 +756,6 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out) {
 }
 
 int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n_substeps) {
-  (void)t0;  // the Cahn-Hilliard and Allen-Cahn right-hand sides are autonomous
   if (!ctx) return PDEOPT_EINVAL;
   int rc = check_sens(ctx);
   if (rc) return rc;
@@ -774,9 +764,27 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
   const bool bv = bv_equation(ctx->prob.equation);
-  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN || bv;  // Euler and RK4, no fourier_symbol
+  // the smoothed-boundary equations: theta(t) and flux(t) at every stage time t0 + s dt (+ dt / 2, + dt); all others
+  // are autonomous and keep passing 0.0
+  const bool sbm = sbm_equation(ctx->prob.equation);
+  // a table of pdeopt_set_time_table belongs to the advance it was sampled for, as in pdeopt_advance: it is gone when
+  // this call returns, however it returns (a table left behind would override the constants of a later pdeopt_sens_rhs)
+  struct TableGuard {
+    pdeopt_ctx* c;
+    bool on;
+    ~TableGuard() {
+      if (!on) return;
+      c->tt_times.clear();
+      c->tt_terms.clear();
+      c->tt_cursor = 0;
+    }
+  } table_guard{ctx, sbm};
+  const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN || bv || sbm;  // Euler and RK4, no fourier_symbol
   bool fused = false;
   if (integrator == PDEOPT_INT_IMEX) {
+    if (sbm)
+      return fail(ctx, PDEOPT_EINVAL, "AllenCahn2DSmoothedBoundary / CahnHilliard2DSmoothedBoundary sensitivities support the Euler "
+                                      "and RK4 integrators (the psi-weighted operator has no fourier_symbol)");
     if (ac) return fail(ctx, PDEOPT_EINVAL, "Allen-Cahn sensitivities support the Euler and RK4 integrators (it has no fourier_symbol)");
     if (!ctx->aux[PDEOPT_AUX_IMEX_SYMBOL].dev)
       return fail(ctx, PDEOPT_ESTATE, "IMEX needs the IMEX_SYMBOL aux field (fourier_symbol)");
@@ -794,12 +802,14 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
                                     "Allen-Cahn (got %d)", integrator);
   }
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if (sbm) ctx->tt_misses = 0;
   for (int64_t s = 0; s < n_substeps; ++s) {
+    const double ts = t0 + (double)s * dt;
     if (integrator == PDEOPT_INT_RK4) {
-      if ((rc = with_dtype(ctx, [&](auto t) { return rk4_substep<decltype(t)>(ctx, dt); }))) return rc;
+      if ((rc = with_dtype(ctx, [&](auto t) { return rk4_substep<decltype(t)>(ctx, dt, ts, sbm); }))) return rc;
       continue;
     }
-    if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA))) return rc;
+    if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA, sbm ? ts : 0.0))) return rc;
     if (integrator == PDEOPT_INT_IMEX && fused) {
       rc = imex_fused_passes(ctx, whole_batch(ctx), dt);
     } else if (integrator == PDEOPT_INT_IMEX) {
@@ -811,8 +821,14 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     if (rc) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  if (sbm && !ctx->tt_times.empty() && ctx->tt_misses)
+      return fail(ctx, PDEOPT_EINVAL, "pdeopt_set_time_table: %lld stage time(s) of this advance are not in the table and no "
+                  "pdeopt_set_time_terms callback is registered (times must be formed as t0 + (double) s * dt, + dt / 2, + dt)",
+                  (long long)ctx->tt_misses);
   // after the loop: the base slope launches name their own kernel
-  ctx->last_kernel = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : (bv ? "bvsens_tangent_rhs" : (ac ? "sens_ac_tangent_rhs" : "sens_tangent_rhs"));
+  const int eq = ctx->prob.equation;
+  ctx->last_kernel = eq == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "sens_sbm_ac_tangent_rhs"
+                     : eq == PDEOPT_EQ_CAHN_HILLIARD_SBM ? "sens_sbm_ch_tangent_rhs" : (bv ? "bvsens_tangent_rhs" : (ac ? "sens_ac_tangent_rhs" : "sens_tangent_rhs"));
   ctx->last_kernel += integrator == PDEOPT_INT_RK4 ? "+rk4" : (integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : "+imex_rocfft_r2c"));
   return PDEOPT_OK;
 }

@@ -1,5 +1,6 @@
-// What the tangent kernels (sens.hip) and the field-mu kernels (fieldmu.hip) share: the geometry of the 16 x 32 tile with
-// its 2-cell ring (the derivative of a closure with respect to its argument, closure_dc, is in closures.hpp).
+// What the tangent kernels (sens.hip, sens_sbm.hip) and the field-mu kernels (fieldmu.hip) share: the geometry of the
+// 16 x 32 tile with its 2-cell ring, and the derivative of a closure with respect to one of its coefficients (the
+// derivative with respect to its argument, closure_dc, is in closures.hpp).
 #pragma once
 
 #include "closures.hpp"
@@ -15,6 +16,34 @@ __device__ __forceinline__ int wrap_idx(int g, int n) {
   g = g < 0 ? g + n : (g >= n ? g - n : g);
   if ((unsigned)g >= (unsigned)n) g = ((g % n) + n) % n;
   return g;
+}
+
+// ---- closure derivatives (the family of include/pdeopt_hip.h; values from closure_generic) ------------------------
+
+// 1 / q of the Legendre recurrence below: a multiply per term instead of a division (the tangent kernels evaluate
+// the basis once per cell and tangent)
+[[maybe_unused]] static __constant__ double kRecip[PDEOPT_CLOSURE_MAX_COEF] = {
+    0.0,     1.0,     1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,  1.0 / 6,  1.0 / 7,
+    1.0 / 8, 1.0 / 9, 1.0 / 10, 1.0 / 11, 1.0 / 12, 1.0 / 13, 1.0 / 14, 1.0 / 15};
+
+// df/dcoef[k] at c: the basis function B_k(c) = c^k or P_k(2c - 1), times f under EXP_WRAP
+template <typename T>
+__device__ __forceinline__ T closure_dcoef(const ClosureSpec& s, int k, T c, T f) {
+  T b = T(1);
+  if (s.kind == PDEOPT_CL_POLY) {
+    for (int q = 0; q < k; ++q) b *= c;
+  } else if (k > 0) {
+    const T x = T(2) * c - T(1);
+    T pm = T(1);
+    b = x;
+    for (int q = 2; q <= k; ++q) {
+      const T pn = (T(2 * q - 1) * x * b - T(q - 1) * pm) * T(kRecip[q]);
+      pm = b;
+      b = pn;
+    }
+  }
+  if (s.flags & PDEOPT_CL_EXP_WRAP) b *= f;
+  return b;
 }
 
 }  // namespace pdeopt

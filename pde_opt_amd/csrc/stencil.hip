@@ -76,6 +76,7 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const Window& w, double t, const void* i
     s.tw_a = T(tv[0]);
     s.tw_b = T(tv[1]);
     s.tsrc = T(tv[2]);
+    for (int c = 0; c < 3; ++c) ctx->time_last[c] = tv[c];
   }
   s.out_mode = out_mode;
   s.acc_mode = acc_mode;

@@ -429,6 +429,10 @@ class HipEngine:
         return out
 
     def sens_advance(self, integrator: int, dt: float, n_substeps: int, t0: float = 0.0):
+        """``t0``: the time of the first substep; the smoothed-boundary equations evaluate theta(t) and flux(t) at the stage
+        times ``t0 + s dt`` (``+ dt / 2``, ``+ dt``), sampled up front like ``advance`` does; the other equations ignore it"""
+        if self.problem.equation in (L.EQ_ALLEN_CAHN_SBM, L.EQ_CAHN_HILLIARD_SBM):
+            self._upload_time_table(int(integrator), dt, int(n_substeps), t0)
         self._check(self._lib.pdeopt_sens_advance(self._h, int(integrator), float(t0), float(dt), int(n_substeps)))
 
     def sens_bv_voltage(self) -> np.ndarray:

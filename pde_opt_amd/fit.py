@@ -17,6 +17,12 @@ Covered: periodic Cahn-Hilliard in 2-D and 3-D (``mu`` / ``D``; IMEX or Euler), 
 the voltage and its tangents are available at the save points, and ``train`` can fit a voltage curve next to the frames:
 ``add_voltage_sums``), all with ``derivs="fd"``.  The scalars of the Butler-Volmer classes (``alpha``, ``kappa``, ``Crate``,
 ``v``) are not trainable entries: they go in ``other_parameters``.
+
+Also covered: the smoothed-boundary classes ``AllenCahn2DSmoothedBoundary`` (``mu`` / ``R``) and
+``CahnHilliard2DSmoothedBoundary`` (``mu`` / ``D``) on a 2-D domain with Euler or RK4.  Their right-hand sides depend on
+time through ``theta(t)`` and ``flux(t)``: every advance is told its start time, and the tangent kernel evaluates the
+wall term at the stage times of the base solve.  ``f``, ``kappa``, ``theta`` and ``flux`` are fixed data
+(``other_parameters``).
 """
 
 from __future__ import annotations
@@ -65,14 +71,21 @@ class ParamMap:
     keys: List[str]
     templates: list
     sizes: List[int]
-    mu_constant_active: bool = False  # Allen-Cahn: mu_h itself, not only its gradient, enters the right-hand side
+    # Allen-Cahn (periodic, Butler-Volmer, smoothed-boundary): mu_h itself, not only its gradient, enters the right-hand side
+    mu_constant_active: bool = False
 
     @classmethod
     def of(cls, opt_parameters: dict, equation_type=None) -> "ParamMap":
-        """``equation_type`` decides whether mu's constant coefficient has a tangent (Allen-Cahn) or is inert
-        (Cahn-Hilliard, and the default)"""
+        """``equation_type`` decides whether mu's constant coefficient has a tangent (Allen-Cahn, smoothed-boundary
+        Allen-Cahn included) or is inert (Cahn-Hilliard -- the smoothed-boundary form too: a constant added to ``inner``
+        drops out of ``grad(inner)`` -- and the default)"""
         keys, templates, sizes = [], [], []
         for key, value in opt_parameters.items():
+            if key in _SBM_FIXED and _is_smoothed_boundary(equation_type):
+                raise NotTrainableError(
+                    f"opt_parameters[{key!r}]: {key} of {equation_type.__name__} is fixed data of the fit (the free energy of "
+                    "the wall term, the gradient coefficient, the contact angle theta(t) and the boundary flux flux(t) have "
+                    "no tangent kernel); pass it in other_parameters")
             if key not in _ROLES or not isinstance(value, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
                 raise NotTrainableError(
                     f"opt_parameters[{key!r}]: only the coefficient arrays of ChemicalPotentialLegendrePolynomials / "
@@ -83,7 +96,8 @@ class ParamMap:
             sizes.append(len(value.expansion.params))
         if not keys:
             raise NotTrainableError("opt_parameters holds no trainable closure")
-        return cls(keys, templates, sizes, _is_allen_cahn(equation_type) or _is_butler_volmer(equation_type))
+        return cls(keys, templates, sizes, _is_allen_cahn(equation_type) or _is_butler_volmer(equation_type)
+                   or _is_smoothed_boundary(equation_type, allen_cahn_only=True))
 
     @property
     def size(self) -> int:
@@ -130,6 +144,16 @@ def _is_allen_cahn(equation_type) -> bool:
     from .numerics.equations.phase_field import AllenCahn2DPeriodic
 
     return isinstance(equation_type, type) and issubclass(equation_type, AllenCahn2DPeriodic)
+
+
+_SBM_FIXED = ("f", "kappa", "theta", "flux")  # constructor arguments of the smoothed-boundary classes that are never trainable
+
+
+def _is_smoothed_boundary(equation_type, allen_cahn_only=False) -> bool:
+    from .numerics.equations.smoothed_boundary import AllenCahn2DSmoothedBoundary, CahnHilliard2DSmoothedBoundary
+
+    classes = (AllenCahn2DSmoothedBoundary,) if allen_cahn_only else (AllenCahn2DSmoothedBoundary, CahnHilliard2DSmoothedBoundary)
+    return isinstance(equation_type, type) and issubclass(equation_type, classes)
 
 
 def _is_butler_volmer(equation_type, constant_current_only=False) -> bool:
@@ -262,6 +286,9 @@ def sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, dt0=1e-6, fie
     elif _is_allen_cahn(type(equation)):
         if solver.integrator not in (L.INT_EULER, L.INT_RK4):
             raise NotImplementedError("Allen-Cahn sensitivities support Euler and RK4")
+    elif _is_smoothed_boundary(type(equation)):
+        if solver.integrator not in (L.INT_EULER, L.INT_RK4):
+            raise NotImplementedError(f"{type(equation).__name__} sensitivities support Euler and RK4")
     elif solver.integrator not in (L.INT_IMEX, L.INT_EULER):
         raise NotImplementedError("sensitivities support SemiImplicitFourierSpectral (IMEX) and Euler")
     if voltages is not None and not _is_butler_volmer(type(equation), constant_current_only=True):
@@ -551,18 +578,20 @@ def objective_gradient(objective: SolutionObjective, ys, spatial_ndim: int, cont
 
 
 _SUPPORTED = ("CahnHilliard2DPeriodic on a 2-D domain or CahnHilliard3DPeriodic on a 3-D domain, or AllenCahn2DPeriodic or a "
-              "Butler-Volmer Allen-Cahn class on a 2-D domain")
+              "Butler-Volmer Allen-Cahn class on a 2-D domain"
+              ", or AllenCahn2DSmoothedBoundary or CahnHilliard2DSmoothedBoundary on a 2-D domain")
 
 
 def reject_unsupported(model):
     """the configurations the sensitivity path covers: periodic Cahn-Hilliard in 2-D or 3-D with IMEX or Euler,
-    periodic 2-D Allen-Cahn and the Butler-Volmer Allen-Cahn classes with Euler or RK4, FD derivatives.  The equation / domain pair is checked here, before any
-    equation is built."""
+    periodic 2-D Allen-Cahn, the Butler-Volmer Allen-Cahn classes and the two smoothed-boundary classes with Euler or RK4,
+    FD derivatives.  The equation / domain pair is checked here, before any equation is built.  The tangents always
+    advance with constant steps: train / residuals / optimize take no step-size controller."""
     from .numerics.equations.phase_field import AllenCahn2DPeriodic, CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
     from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral
 
     dims = {CahnHilliard2DPeriodic: 2, CahnHilliard3DPeriodic: 3, AllenCahn2DPeriodic: 2}.get(model.equation_type)
-    if _is_butler_volmer(model.equation_type):
+    if _is_butler_volmer(model.equation_type) or _is_smoothed_boundary(model.equation_type):
         dims = 2
     if dims is None:
         raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
@@ -570,7 +599,8 @@ def reject_unsupported(model):
     if len(model.domain.points) != dims:
         raise NotImplementedError(f"train / residuals sensitivities support {_SUPPORTED}, not "
                                   f"{model.equation_type.__name__} on a {len(model.domain.points)}-D domain")
-    if model.equation_type is AllenCahn2DPeriodic or _is_butler_volmer(model.equation_type):
+    if (model.equation_type is AllenCahn2DPeriodic or _is_butler_volmer(model.equation_type)
+            or _is_smoothed_boundary(model.equation_type)):
         if model.solver_type not in (Euler, RK4):
             raise NotImplementedError(f"train / residuals sensitivities of {model.equation_type.__name__} support the Euler and "
                                       f"RK4 solvers, not {model.solver_type.__name__}")
@@ -592,7 +622,8 @@ def check_equation(equation):
     if getattr(equation, "derivs", "fd") != "fd":
         raise NotImplementedError('train sensitivities support derivs="fd" only (the tangent kernel differentiates the '
                                   'finite-difference right-hand side)')
-    for d in (equation._mu_desc, equation._mob_desc):
-        if d.kind == L.CL_JIT:
+    # (the smoothed-boundary classes: the free energy f of the wall term is differentiated in the kernel too)
+    for d in (equation._mu_desc, equation._mob_desc, getattr(equation, "_f_desc", None)):
+        if d is not None and d.kind == L.CL_JIT:
             raise UnsupportedClosureError("train sensitivities need closures of the in-kernel family (polynomial / "
                                           "Legendre series with the logit, mixing-entropy and exp forms)")

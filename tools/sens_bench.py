@@ -15,7 +15,10 @@ synchronise (CahnHilliard2DPeriodic 128^2 x 1, IMEX, P = 3 / 7, `substeps` subst
   forward_ms   one forward solve (PDEModel.solve): what a line-search trial point costs
   gradient_ms  one gradient evaluation: a forward solve, the objective's cotangent, its upload and a sensitivity solve
                with the contraction (pdeopt_sens_contract)
-Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only | --optimize]
+``--sbm`` times the smoothed-boundary classes (AllenCahn2DSmoothedBoundary, CahnHilliard2DSmoothedBoundary inside a disc,
+ramped theta(t), RK4): an RK4 sensitivity substep at P = 3 and P = 7 next to the forward RK4 substep of the same problem
+in the same run, 128^2 x 3 and 1024^2 x 8.
+Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only | --optimize | --sbm]
 """
 import json
 import sys
@@ -142,6 +145,58 @@ def ac_rows(quick):
     return rows
 
 
+def sbm_case(kind, n, B, dtype, P_, nsub):
+    import types
+
+    x = np.arange(n) + 0.5
+    X, Y = np.meshgrid(x, x, indexing="ij")
+    psi = 0.05 + 0.95 * 0.5 * (1.0 + np.tanh((0.3 * n - np.sqrt((X - 0.5 * n) ** 2 + (Y - 0.5 * n) ** 2)) / 2.5))
+    dom = P.Domain((n, n), ((0.0, float(n)), (0.0, float(n))), "dimensionless", geometry=types.SimpleNamespace(smooth=psi))
+    f = lambda c: c * np.log(c) + (1.0 - c) * np.log(1.0 - c) + 3.0 * c * (1.0 - c) + 0.059  # noqa: E731
+    theta = lambda t: np.pi / 2 - 10.0 * t  # noqa: E731
+    # P = 3 / 7 active tangents: Allen-Cahn counts mu's a0, Cahn-Hilliard does not
+    n_mu = {("ac", 3): 2, ("ac", 7): 5, ("ch", 3): 3, ("ch", 7): 6}[kind, P_]
+    mu = ChemLeg(np.array([0.0, -3.0, 0.1, 0.0, 0.0, 0.0][:n_mu]), logit)
+    mob = DiffLeg(np.array([0.8] if P_ == 3 else [0.8, 0.1]))
+    if kind == "ac":
+        cls, opt = P.AllenCahn2DSmoothedBoundary, {"mu": mu, "R": mob}
+        eq = cls(dom, 1.5, f, mu, mob, theta)
+    else:
+        cls, opt = P.CahnHilliard2DSmoothedBoundary, {"mu": mu, "D": mob}
+        eq = cls(dom, 1.5, f, mu, mob, theta, lambda t: 0.02)
+    solver, dt = P.RK4(), 1e-3
+    rng = np.random.default_rng(0)
+    y0s = np.clip(0.5 + 0.05 * rng.standard_normal((B, n, n)), 0.1, 0.9).astype(dtype)
+    sp = fit.ParamMap.of(opt, cls).sens_params()
+    assert len(sp) == P_
+
+    fwd = P.HipEngine()
+    fwd.configure(dtype=dtype, batch=B, **eq._engine_problem())
+    eq._engine_upload(fwd, 0.0, 1.0)
+    fwd.set_state(y0s)
+    t_fwd = timed(fwd, lambda: fwd.advance(solver.integrator, dt, nsub), 3) / nsub
+    kernel = fwd.last_kernel
+
+    sens = P.HipEngine()
+    fit._configure(sens, eq, solver, y0s, sp, 0.0, 1.0)
+    t_sens = timed(sens, lambda: sens.sens_advance(solver.integrator, dt, nsub), 3) / nsub
+    return {"equation": kind + "_sbm", "integrator": "rk4", "n": n, "B": B, "dtype": np.dtype(dtype).name, "P": P_,
+            "fwd_us_per_substep": 1e3 * t_fwd, "fwd_kernel": kernel, "sens_us_per_substep": 1e3 * t_sens,
+            "sens_kernel": sens.last_kernel, "sens_over_fwd": t_sens / t_fwd}
+
+
+def sbm_rows(quick):
+    rows = []
+    for n, B, nsub in ((128, 3, 100), (1024, 8, 10)):
+        for kind in ("ac", "ch"):
+            for dtype in (np.float32, np.float64):
+                for P_ in (3, 7):
+                    if quick and (n > 128 or P_ > 3):
+                        continue
+                    rows.append(sbm_case(kind, n, B, dtype, P_, nsub))
+    return rows
+
+
 class _SecondMoment:
     """J = mean(ys[-1]^2) with its cotangent, in numpy (the objective's own cost stays out of the comparison)"""
 
@@ -178,6 +233,9 @@ def main():
         rows = [optimize_case(128, dtype, P_, 200 if quick else 4040) for dtype in (np.float32, np.float64)
                 for P_ in ((3,) if quick else (3, 7))]
         print(json.dumps({"tool": "sens_bench", "mode": "optimize", "dt": DT, "cases": rows}))
+        return
+    if "--sbm" in sys.argv:
+        print(json.dumps({"tool": "sens_bench", "mode": "sbm", "cases": sbm_rows(quick)}))
         return
     if "--ac-only" in sys.argv:
         print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": ac_rows(quick)}))
