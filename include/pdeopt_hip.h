@@ -638,6 +638,39 @@ int pdeopt_cnn_vjp(pdeopt_cnn* cnn, const void* u_dev, const void* gmu_dev, void
 int pdeopt_cnn_grad_read(pdeopt_cnn* cnn, double* out_host, int64_t n, int reset);
 int pdeopt_cnn_destroy(pdeopt_cnn* cnn);
 
+/* ---- an MLP-mixer as mu_h, evaluated and differentiated inside the library (pde_opt/numerics/functions/mixer_mlp.py:
+ * a p x p patch convolution to C = hidden channels of P patches, blocks of a patch-mixing and a channel-mixing MLP of
+ * one hidden layer, each behind a layer norm over the whole (C, P) array and with a residual, a final layer norm and the
+ * transposed patch convolution).  Supported, anything else is refused: one channel in and out, patch 1 ... 16 dividing
+ * both sides of the grid, hidden 1 ... 64, mix sizes 1 ... 256, 1 ... 4096 patches, 1 ... 8 blocks, fp32 and fp64 (the dtype of
+ * the ctx's configured problem), periodic 2-D real fields, any batch.  The parameter shapes depend on the grid: a handle
+ * is bound to the grid the ctx is configured with when it is created, belongs to its ctx and is destroyed before it.
+ * Every *_dev argument is a device field [batch][nx][ny] in the problem dtype; all work is ordered on the ctx's stream.
+ * pdeopt_mixer_grad_read synchronises the host, and so does the first forward / vjp after pdeopt_mixer_set_params (it
+ * packs and uploads the parameters); nothing else does. */
+typedef struct pdeopt_mixer pdeopt_mixer;
+typedef enum {
+  PDEOPT_MIXER_GELU = 0,      /* as PDEOPT_CNN_GELU */
+  PDEOPT_MIXER_GELU_TANH = 1, /* as PDEOPT_CNN_GELU_TANH */
+  PDEOPT_MIXER_TANH = 2,
+  PDEOPT_MIXER_RELU = 3       /* the reference's: equinox.nn.MLP's default */
+} pdeopt_mixer_activation;
+int pdeopt_mixer_create(pdeopt_ctx* ctx, int patch, int hidden, int mix_patch, int mix_hidden, int blocks, int activation,
+                        pdeopt_mixer** mixer);
+/* n doubles in the order of the torch mirror's parameters(): conv_in weight (C, 1, p, p) and bias (C), conv_out weight
+ * (C, 1, p, p) and bias (1); per block the patch mixer's W1 (mix_patch, P), b1, W2 (P, mix_patch), b2, the hidden mixer's
+ * W3 (mix_hidden, C), b3, W4 (C, mix_hidden), b4, norm1's weight and bias (C, P), norm2's (P, C); the final norm's (C, P) */
+int pdeopt_mixer_set_params(pdeopt_mixer* mixer, const double* params_host, int64_t n);
+/* mu_dev = N(u_dev) */
+int pdeopt_mixer_forward(pdeopt_mixer* mixer, const void* u_dev, void* mu_dev);
+/* lam_dev += N'(u_dev)^T gmu_dev, and the gradient of <gmu, N(u)> over the parameters is added to a fp64 buffer kept
+ * on the device (the activations are evaluated again into the handle's workspace; nothing is kept between calls).
+ * lam_dev must not overlap u_dev or gmu_dev (refused).  Sums run in a fixed order without atomics: identical bits on a repeat. */
+int pdeopt_mixer_vjp(pdeopt_mixer* mixer, const void* u_dev, const void* gmu_dev, void* lam_dev);
+/* the accumulated parameter gradient, n doubles in the order of pdeopt_mixer_set_params; reset != 0 zeroes it */
+int pdeopt_mixer_grad_read(pdeopt_mixer* mixer, double* out_host, int64_t n, int reset);
+int pdeopt_mixer_destroy(pdeopt_mixer* mixer);
+
 /* ---- the discrete adjoint of one Strang substep of the GPE whose control is a sum of Gaussian spots
  * (pdeopt_set_gpe_spots): the reverse-mode gradient of a scalar objective of the solution over the spots' numbers (the
  * reference's PDEModel.optimize, pde_model.py:462-551, differentiates the same solve with generic reverse-mode AD).

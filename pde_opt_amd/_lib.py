@@ -57,6 +57,7 @@ FIELD_Y, FIELD_TA, FIELD_TB, FIELD_ACC = 0, 1, 2, 3
 PATH_AUTO, PATH_GENERIC, PATH_TILED = 0, 1, 2
 PART_ALL, PART_INTERIOR, PART_EDGE = 0, 1, 2
 CNN_GELU, CNN_GELU_TANH, CNN_TANH = 0, 1, 2  # pdeopt_cnn_activation
+MIXER_GELU, MIXER_GELU_TANH, MIXER_TANH, MIXER_RELU = 0, 1, 2, 3  # pdeopt_mixer_activation
 
 
 class HipUnavailableError(RuntimeError):
@@ -219,6 +220,12 @@ _SIGNATURES = {
     "pdeopt_cnn_vjp": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pdeopt_cnn_grad_read": (C.c_int, [_VP, _VP, C.c_int64, C.c_int]),
     "pdeopt_cnn_destroy": (C.c_int, [_VP]),
+    "pdeopt_mixer_create": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "pdeopt_mixer_set_params": (C.c_int, [_VP, _VP, C.c_int64]),
+    "pdeopt_mixer_forward": (C.c_int, [_VP, _VP, _VP]),
+    "pdeopt_mixer_vjp": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pdeopt_mixer_grad_read": (C.c_int, [_VP, _VP, C.c_int64, C.c_int]),
+    "pdeopt_mixer_destroy": (C.c_int, [_VP]),
 }
 
 _lib = None

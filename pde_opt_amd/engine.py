@@ -59,7 +59,7 @@ class HipEngine:
         self._aux_thunks: dict = {}
         self._aux_keys: dict = {}
         self._callback_error = None
-        self._cnns: list = []  # open NativeCNN handles: closed before the ctx they belong to
+        self._cnns: list = []  # open NativeCNN and NativeMixer handles: closed before the ctx they belong to
         self.gpe_origin: Optional[tuple] = None  # coordinates of cell (0, 0) of a GPE problem (gpe_observables)
 
     # -- plumbing ---------------------------------------------------------------------------
@@ -485,6 +485,11 @@ class HipEngine:
         ``(1, hidden..., 1)``, ``activation`` one of ``_lib.CNN_*``"""
         return NativeCNN(self, channels, activation)
 
+    def mixer(self, patch: int, hidden: int, mix_patch: int, mix_hidden: int, blocks: int, activation: int) -> "NativeMixer":
+        """an MLP-mixer evaluated by the library on this engine's fields (``pdeopt_mixer_*``), for the grid the engine is
+        configured with; ``activation`` one of ``_lib.MIXER_*``"""
+        return NativeMixer(self, patch, hidden, mix_patch, mix_hidden, blocks, activation)
+
     def reduce(self, op: int) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.float64)
         self._check(self._lib.pdeopt_reduce(self._h, int(op), out.ctypes.data_as(C.c_void_p)))
@@ -831,6 +836,57 @@ class NativeCNN:
     def close(self):
         if getattr(self, "_h", None):
             self.engine._lib.pdeopt_cnn_destroy(self._h)
+            self._h = None
+            self.engine._cnns.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeMixer:
+    """Handle of an MLP-mixer inside the library (csrc/mixer.hip), bound to one ``HipEngine`` and to the grid it is
+    configured with.  Field arguments are device pointers of ``(batch, nx, ny)`` fields in the engine's dtype; everything
+    is ordered on the engine's stream and only ``grad_read`` waits for it.  ``created`` counts the handles ever made."""
+
+    created = 0
+
+    def __init__(self, engine: "HipEngine", patch: int, hidden: int, mix_patch: int, mix_hidden: int, blocks: int, activation: int):
+        self.engine = engine
+        self.sizes = tuple(int(v) for v in (patch, hidden, mix_patch, mix_hidden, blocks))
+        self.activation = int(activation)
+        h = C.c_void_p()
+        engine._check(engine._lib.pdeopt_mixer_create(engine._h, *self.sizes, self.activation, C.byref(h)))
+        self._h = h
+        self.grid = (int(engine.problem.nx), int(engine.problem.ny))
+        p, c, mp, mh, k = self.sizes
+        P = (self.grid[0] // p) * (self.grid[1] // p)
+        self.n_params = 2 * c * p * p + c + 1 + k * (2 * mp * P + mp + P + 2 * mh * c + mh + c + 4 * c * P) + 2 * c * P
+        engine._cnns.append(self)
+        NativeMixer.created += 1
+
+    def set_params(self, flat):
+        """the parameters as one flat fp64 vector in torch's order (``fieldmu.flatten_params``)"""
+        p = np.ascontiguousarray(flat, dtype=np.float64)
+        self.engine._check(self.engine._lib.pdeopt_mixer_set_params(self._h, p.ctypes.data_as(C.c_void_p), p.size))
+
+    def forward(self, u_ptr: int, mu_ptr: int):
+        self.engine._check(self.engine._lib.pdeopt_mixer_forward(self._h, C.c_void_p(u_ptr), C.c_void_p(mu_ptr)))
+
+    def vjp(self, u_ptr: int, gmu_ptr: int, lam_ptr: int):
+        """``lam += N'(u)^T gmu``; the parameter gradient accumulates on the device until ``grad_read``"""
+        self.engine._check(self.engine._lib.pdeopt_mixer_vjp(self._h, C.c_void_p(u_ptr), C.c_void_p(gmu_ptr), C.c_void_p(lam_ptr)))
+
+    def grad_read(self, reset: bool = True) -> np.ndarray:
+        out = np.empty(self.n_params, dtype=np.float64)
+        self.engine._check(self.engine._lib.pdeopt_mixer_grad_read(self._h, out.ctypes.data_as(C.c_void_p), out.size, int(bool(reset))))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.engine._lib.pdeopt_mixer_destroy(self._h)
             self._h = None
             self.engine._cnns.remove(self)
 

@@ -26,6 +26,11 @@ the library as well: a ``PeriodicCNN`` of the family ``numerics.functions.cnn.na
 parameter gradient accumulates in fp64 on the device over the sweep and is read once.  A module outside that family is
 refused while the switch is on; there is no fallback to torch.
 
+``FieldMuSolver.native_mixer`` (off by default; ``PDEOPT_FIELDMU_NATIVE_MIXER=1`` sets the default) is the same switch for
+a ``Mixer2d`` of the family ``numerics.functions.mixer.native_spec`` accepts (``pdeopt_mixer_forward``,
+``pdeopt_mixer_vjp``, csrc/mixer.hip).  ``native_cnn`` is asked first: with both on, a module that is not a
+``PeriodicCNN`` is refused.
+
 torch is imported when a solver is built, not with the package.
 """
 
@@ -44,6 +49,7 @@ from .numerics.equations.phase_field import FIELD_MU_SUPPORT
 CHUNK_BYTES_ENV = "PDEOPT_FIELDMU_CHUNK_BYTES"
 DEFAULT_CHUNK_BYTES = 1 << 30
 NATIVE_CNN_ENV = "PDEOPT_FIELDMU_NATIVE_CNN"
+NATIVE_MIXER_ENV = "PDEOPT_FIELDMU_NATIVE_MIXER"
 
 
 # ---- parameters as one flat vector --------------------------------------------------------------------------------------
@@ -170,6 +176,10 @@ class FieldMuSolver:
         self.native_cnn = os.environ.get(NATIVE_CNN_ENV, "0") not in ("", "0")
         self._cnn = None         # the library's handle of the last native network
         self._cnn_pending = False  # its gradient buffer holds sums of a sweep that did not finish
+        # the same for a Mixer2d mu (csrc/mixer.hip)
+        self.native_mixer = os.environ.get(NATIVE_MIXER_ENV, "0") not in ("", "0")
+        self._mixer = None
+        self._mixer_pending = False
 
     @contextlib.contextmanager
     def _ordered(self):
@@ -193,8 +203,9 @@ class FieldMuSolver:
     # -- set-up ---------------------------------------------------------------------------------------------------------
     def _prepare(self, equation, solver, y0s, t0, t1):
         """configure the engine, upload the state; returns ``(Y, mu_of)``: the state as a tensor ``(B, nx, ny)`` over the
-        engine's own buffer, and ``mu_of(u) -> mu_h`` ``(B, nx, ny)``, contiguous.  With ``native_cnn`` the library
-        evaluates the network: ``mu_of`` fills and returns one buffer, and ``self._cnn`` holds this call's parameters"""
+        engine's own buffer, and ``mu_of(u) -> mu_h`` ``(B, nx, ny)``, contiguous.  With ``native_cnn`` or ``native_mixer`` the
+        library evaluates the network: ``mu_of`` fills and returns one buffer, and ``self._cnn`` or ``self._mixer`` holds
+        this call's parameters"""
         torch = self.torch
         eng = self.engine
         eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem(field_mu=True))
@@ -206,8 +217,8 @@ class FieldMuSolver:
         for name, p in module.named_parameters():
             if p.dtype != Y.dtype or p.device != Y.device:
                 raise ValueError(f"mu's parameter {name} is {p.dtype} on {p.device}; the solve runs in {Y.dtype} on {Y.device}")
-        if self.native_cnn:
-            cnn = self._native(module)
+        if self.native_cnn or self.native_mixer:
+            cnn = self._native(module) if self.native_cnn else self._native_mixer(module)
             mu_h = torch.empty_like(Y)
 
             def native_mu(u):
@@ -233,6 +244,35 @@ class FieldMuSolver:
             self._cnn, self._cnn_pending = self.engine.cnn(channels, act), False
         self._cnn.set_params(flatten_params(module))
         return self._cnn
+
+    def _native_mixer(self, module):
+        """the library's handle of ``module`` with its current parameters uploaded; refuses what csrc/mixer.hip does not
+        cover and a module made for another grid than the engine's"""
+        from .numerics.functions import mixer as M
+
+        spec = M.native_spec(module)
+        if spec is None:
+            raise NotImplementedError(f"native_mixer is on and mu is not a network the library evaluates: {M.native_refusal(module)} "
+                                      "(there is no fallback to torch: set native_mixer = False)")
+        grid, sizes, act = spec[0], spec[1:6], M.NATIVE_ACTIVATIONS.index(spec[6])
+        if self._mixer is None or (self._mixer.grid, self._mixer.sizes, self._mixer.activation) != (grid, sizes, act):
+            if self._mixer is not None:
+                self._mixer.close()
+                self._mixer = None
+            if grid != (self.engine.problem.nx, self.engine.problem.ny):
+                raise ValueError(f"mu is a Mixer2d for a {grid[0]} x {grid[1]} grid; the solve runs on "
+                                 f"{self.engine.problem.nx} x {self.engine.problem.ny}")
+            self._mixer, self._mixer_pending = self.engine.mixer(*sizes, act), False
+        self._mixer.set_params(flatten_params(module))
+        return self._mixer
+
+    def _native_handle(self):
+        """``(handle, name of its pending flag)`` of the network the library differentiates in this call, or ``(None, None)``"""
+        if self.native_cnn:
+            return self._cnn, "_cnn_pending"
+        if self.native_mixer:
+            return self._mixer, "_mixer_pending"
+        return None, None
 
     # -- forward --------------------------------------------------------------------------------------------------------
     def solve(self, equation, solver, y0s, ts, dt0, controller=None) -> np.ndarray:
@@ -275,11 +315,11 @@ class FieldMuSolver:
                 by_index.setdefault(i, []).append((q, theta))
         with self._ordered(), torch.no_grad(), _deterministic(torch):
             Y, mu_of = self._prepare(equation, solver, y0s, float(ts[0]), float(ts[-1]))
-            cnn = self._cnn if self.native_cnn else None
+            cnn, pending = self._native_handle()
             if cnn is not None:
-                if self._cnn_pending:
+                if getattr(self, pending):
                     cnn.grad_read(reset=True)
-                self._cnn_pending = True
+                setattr(self, pending, True)
             vals = torch.as_tensor(np.ascontiguousarray(np.swapaxes(values, 0, 1)), dtype=Y.dtype).to(Y.device)  # (T - 1, B, ...)
             M = vals.numel()
             chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
@@ -332,7 +372,7 @@ class FieldMuSolver:
             loss = float(ssr.item()) / M
             if cnn is not None:
                 add_flat_grad(equation._mu_module, cnn.grad_read(reset=True))
-                self._cnn_pending = False
+                setattr(self, pending, False)
         return loss
 
 

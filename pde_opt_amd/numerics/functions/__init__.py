@@ -1,5 +1,6 @@
 """Function representations used as closures: the Legendre family, light spots; ``cnn.PeriodicCNN`` (a torch module, imported on
-demand: ``from pde_opt_amd.numerics.functions.cnn import PeriodicCNN``) as ``mu`` of CahnHilliard2DPeriodic.  Mixers are out of scope."""
+demand: ``from pde_opt_amd.numerics.functions.cnn import PeriodicCNN``) and ``mixer.Mixer2d`` (likewise:
+``from pde_opt_amd.numerics.functions.mixer import Mixer2d``) as ``mu`` of CahnHilliard2DPeriodic."""
 
 from .lights import GaussianSpot, GaussianSpots
 from .legendre import (

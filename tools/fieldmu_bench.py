@@ -11,6 +11,9 @@ timed window is set per case from a trial window so that the window lasts about 
 the library's own kernels (csrc/cnn.hip, ``FieldMuSolver.native_cnn``) on the same state in one run, fp32 and fp64, with
 the shader clock held during the native windows.  The backward share is what the sweep runs per substep: torch's forward
 under autograd + backward, or ``pdeopt_cnn_forward`` (mu_h for the adjoint kernel) + ``pdeopt_cnn_vjp``.
+
+``--native-mixer``: the same comparison for ``Mixer2d((1, 128, 128), 8, 32, 128, 64, 4)`` (patch 8: 32 x 256 activations),
+torch against csrc/mixer.hip (``FieldMuSolver.native_mixer``).
 """
 import json
 import sys
@@ -23,6 +26,7 @@ from pde_opt_amd import _lib as L
 from pde_opt_amd.fieldmu import FieldMuSolver
 from pde_opt_amd.numerics.functions.cnn import PeriodicCNN
 from pde_opt_amd.numerics.functions.legendre import DiffusionLegendrePolynomials
+from pde_opt_amd.numerics.functions.mixer import Mixer2d
 
 WARMUP, ROUNDS, WINDOW_MS = 3, 7, 50.0
 
@@ -78,10 +82,10 @@ def case(n, B, dtype):
     return res
 
 
-def native_case(n, B, dtype):
+def native_case(n, B, dtype, mixer=False):
     tdt = torch.float32 if dtype == np.float32 else torch.float64
     dom = P.Domain((n, n), ((0.0, 0.01 * n), (0.0, 0.01 * n)), "dimensionless")
-    cnn = PeriodicCNN(1, (32, 64, 64), 1).to(tdt).to("cuda")
+    cnn = (Mixer2d((1, n, n), 8, 32, 128, 64, 4) if mixer else PeriodicCNN(1, (32, 64, 64), 1)).to(tdt).to("cuda")
     eq = P.CahnHilliard2DPeriodic(dom, 0.002, cnn, DiffusionLegendrePolynomials(np.array([0.0])))
     solver = P.SemiImplicitFourierSpectral(A=0.5, fourier_symbol=eq.fourier_symbol)
     fm = FieldMuSolver(0)
@@ -100,9 +104,9 @@ def native_case(n, B, dtype):
             mu_of(u).backward(gmu)
 
         res["backward: torch (forward + backward)"] = timed(fm.stream, torch_backward)
-        fm.native_cnn = True
+        fm.native_cnn, fm.native_mixer = not mixer, mixer
         _, native_mu = fm._prepare(eq, solver, y0, 0.0, 1.0)
-        net = fm._cnn
+        net = fm._mixer if mixer else fm._cnn
 
         def native_backward():
             native_mu(u0)
@@ -120,14 +124,15 @@ def native_case(n, B, dtype):
 
 if __name__ == "__main__":
     results = {}
-    if "--native-cnn" in sys.argv:
+    native = "--native-cnn" in sys.argv or "--native-mixer" in sys.argv
+    if native:
         for dtype in (np.float32, np.float64):
             key = f"128x128x3 {np.dtype(dtype).name}"
-            results[key] = native_case(128, 3, dtype)
+            results[key] = native_case(128, 3, dtype, mixer="--native-mixer" in sys.argv)
             for name, v in results[key].items():
                 print(f"{key:18s} {name:45s} " + (f"{v:9.0f}" if np.isscalar(v) else f"{v[0]:9.1f} us  (min {v[1]:.1f}, max {v[2]:.1f})"),
                       flush=True)
-    for n in () if "--native-cnn" in sys.argv else (32, 128):
+    for n in () if native else (32, 128):
         for dtype in (np.float32, np.float64):
             key = f"{n}x{n}x3 {np.dtype(dtype).name}"
             results[key] = case(n, 3, dtype)
