@@ -610,6 +610,20 @@ int pdeopt_fieldmu_step(pdeopt_ctx* ctx, int integrator, double dt, const void* 
  * lam_dev and gmu_dev must not overlap each other or the inputs (refused).  Gather form, no atomics: identical bits on a repeat. */
 int pdeopt_fieldmu_adjoint_step(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, const void* mu_dev,
                                 void* lam_dev, void* gmu_dev);
+/* pdeopt_fieldmu_adjoint_step with the same checks and the same bits in lam_dev and gmu_dev, and on top the substep's
+ * share of the gradient over the mobility's coefficients (training D together with a network mu): for every cell o and
+ * k < mob.n, g_D(o) dD/dcoef_k(u(o)) -- the basis c^k or P_k(2c - 1), times D(u) under PDEOPT_CL_EXP_WRAP -- is summed in
+ * fp64 whatever the problem dtype, per workgroup in a fixed order, and added to a slot of the ctx that this workgroup
+ * alone owns (no atomics: identical bits on a repeat; no launch more than pdeopt_fieldmu_adjoint_step).  The sums stay
+ * on the device and accumulate over calls until pdeopt_fieldmu_coef_grad_read.  Refused: a mobility outside the
+ * POLY / LEGENDRE family, and mobility coefficients that differ between environments (pdeopt_set_env_params): the
+ * gradient is of ONE mobility shared by the batch. */
+int pdeopt_fieldmu_adjoint_step_coef(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, const void* mu_dev,
+                                     void* lam_dev, void* gmu_dev);
+/* out_host[k], k < n = mob.n (anything else is refused): the accumulated sums over all trajectories and tiles, added in
+ * one fixed order on the host.  Synchronises the host with the ctx's stream, as pdeopt_cnn_grad_read does.  reset != 0
+ * zeroes the slots; pdeopt_configure zeroes them too. */
+int pdeopt_fieldmu_coef_grad_read(pdeopt_ctx* ctx, double* out_host, int n, int reset);
 
 /* ---- a periodic CNN as mu_h, evaluated and differentiated inside the library (pde_opt/numerics/functions/cnn.py:
  * a stack of 3 x 3 convolutions with circular "same" padding and stride 1).  Supported, anything else is refused:

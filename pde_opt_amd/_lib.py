@@ -211,6 +211,8 @@ _SIGNATURES = {
     "pdeopt_fieldmu_rhs": (C.c_int, [_VP, _VP, _VP]),
     "pdeopt_fieldmu_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP]),
     "pdeopt_fieldmu_adjoint_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),
+    "pdeopt_fieldmu_adjoint_step_coef": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),
+    "pdeopt_fieldmu_coef_grad_read": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pdeopt_gpe_adjoint_step": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP, _VP]),
     "pdeopt_gpe_rot_adjoint_step": (C.c_int, [_VP, C.c_double, _VP, _VP, _VP]),
     "pdeopt_gpe_rot_stir_adjoint_step": (C.c_int, [_VP, C.c_double, C.c_double, _VP, _VP, _VP, _VP]),

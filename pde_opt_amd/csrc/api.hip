@@ -70,6 +70,9 @@ void free_fields(pdeopt_ctx* ctx) {
     if (k) (void)hipFree(k);
     k = nullptr;
   }
+  if (ctx->fieldmu_coef) (void)hipFree(ctx->fieldmu_coef);
+  ctx->fieldmu_coef = nullptr;
+  ctx->fieldmu_coef_slots = 0;
   for (auto& a : ctx->aux) {
     if (a.dev) (void)hipFree(a.dev);
     if (a.stage) (void)hipHostFree(a.stage);
@@ -429,6 +432,8 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   }
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
+  if (ctx->fieldmu_coef)  // a coefficient gradient belongs to one problem: a new one starts from zero
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef, 0, ctx->fieldmu_coef_slots * sizeof(double), ctx->stream));
   with_dtype(ctx, [&](auto t) { fill_env_params<decltype(t)>(ctx); });
   if ((rc = ensure_buffer(ctx, &ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
   ctx->imex_per_env = false;

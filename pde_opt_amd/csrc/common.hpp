@@ -255,6 +255,10 @@ struct pdeopt_ctx {
   pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
   pdeopt::GpeRotStirAdjoint* gpe_rot_stir_adjoint = nullptr;
   pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; lives and dies with the field buffers
+  // pdeopt_fieldmu_adjoint_step_coef: fp64 partial sums of the mobility's coefficient gradient, one slot per
+  // (trajectory, tile, coefficient); lives with the field buffers, zeroed by pdeopt_configure
+  double* fieldmu_coef = nullptr;
+  size_t fieldmu_coef_slots = 0;
 };
 
 namespace pdeopt {

@@ -480,6 +480,18 @@ class HipEngine:
         self._check(self._lib.pdeopt_fieldmu_adjoint_step(self._h, int(integrator), float(dt), C.c_void_p(u_ptr),
                                                           C.c_void_p(mu_ptr), C.c_void_p(lam_ptr), C.c_void_p(gmu_ptr)))
 
+    def fieldmu_adjoint_step_coef(self, integrator: int, dt: float, u_ptr: int, mu_ptr: int, lam_ptr: int, gmu_ptr: int):
+        """``fieldmu_adjoint_step``, and the substep's share of the gradient over the mobility's coefficients added to
+        the sums ``fieldmu_coef_grad_read`` returns"""
+        self._check(self._lib.pdeopt_fieldmu_adjoint_step_coef(self._h, int(integrator), float(dt), C.c_void_p(u_ptr),
+                                                               C.c_void_p(mu_ptr), C.c_void_p(lam_ptr), C.c_void_p(gmu_ptr)))
+
+    def fieldmu_coef_grad_read(self, n: int, reset: bool = True) -> np.ndarray:
+        """the ``n`` accumulated sums (``n``: the mobility's coefficient count), fp64; synchronises; ``reset`` zeroes them"""
+        out = np.empty(int(n), dtype=np.float64)
+        self._check(self._lib.pdeopt_fieldmu_coef_grad_read(self._h, out.ctypes.data_as(C.c_void_p), int(n), int(bool(reset))))
+        return out
+
     def cnn(self, channels, activation: int) -> "NativeCNN":
         """a periodic CNN evaluated by the library on this engine's fields (``pdeopt_cnn_*``); ``channels`` are
         ``(1, hidden..., 1)``, ``activation`` one of ``_lib.CNN_*``"""

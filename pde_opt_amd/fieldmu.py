@@ -18,7 +18,17 @@ chunk is run again and held before its sweep.  A chunk holds at most ``PDEOPT_FI
 ``FieldMuSolver.chunk_bytes`` overrides it), so a long solve costs one extra forward pass instead of unbounded memory.
 
 Covered: ``CahnHilliard2DPeriodic`` with ``derivs="fd"``, ``SemiImplicitFourierSpectral`` or ``Euler`` with
-``ConstantStepSize``, fp32 and fp64, ``D`` a closure of the in-kernel family, ``D`` and ``kappa`` fixed.
+``ConstantStepSize``, fp32 and fp64, ``D`` a closure of the in-kernel family, ``kappa`` fixed.
+
+Joint training of ``D``.  With ``D`` a ``DiffusionLegendrePolynomials``, ``mse_backward(..., coef_grad=True)`` also returns
+the gradient over its coefficients (the reference's ``train`` with ``init_params = {"mu": model, "D": ...}``: both are
+leaves of one pytree there).  The adjoint kernel already forms the cotangent ``g_D`` of ``D`` at every cell; a variant of
+it (``pdeopt_fieldmu_adjoint_step_coef``) also sums ``g_D(o) dD/dcoef_k(u(o))`` over the cells in fp64, one partial sum
+per workgroup and coefficient, added to a slot that workgroup alone owns; the slots are summed in a fixed order when the
+gradient is read (``pdeopt_fieldmu_coef_grad_read``).  No extra forward pass, no tangent fields, no launch more per
+substep, no atomics: the bits do not depend on the run or on the chunking, and the cost does not depend on the network.
+``PDEModel.mse_backward(..., closure_grads={})`` and ``PDEModel.train`` with ``opt_parameters = {"mu": module, "D":
+DiffusionLegendrePolynomials}`` build on it.  ``kappa`` stays fixed: it would move the implicit operator of the IMEX step.
 
 ``FieldMuSolver.native_cnn`` (off by default; ``PDEOPT_FIELDMU_NATIVE_CNN=1`` sets the default) moves the network into
 the library as well: a ``PeriodicCNN`` of the family ``numerics.functions.cnn.native_spec`` accepts is evaluated by
@@ -180,6 +190,7 @@ class FieldMuSolver:
         self.native_mixer = os.environ.get(NATIVE_MIXER_ENV, "0") not in ("", "0")
         self._mixer = None
         self._mixer_pending = False
+        self._coef_pending = False  # the engine's coefficient-gradient slots hold sums of a sweep that did not finish
 
     @contextlib.contextmanager
     def _ordered(self):
@@ -300,10 +311,20 @@ class FieldMuSolver:
         return res
 
     # -- reverse ----------------------------------------------------------------------------------------------------------
-    def mse_backward(self, equation, solver, y0s, values, ts, dt0) -> float:
+    def mse_backward(self, equation, solver, y0s, values, ts, dt0, coef_grad: bool = False):
         """``mean(r^2)`` of ``r = values - solve(...)[1:]`` (``values`` ``(B, T - 1, nx, ny)``), summed in fp64; the
-        gradient is ADDED to ``.grad`` of the module's parameters"""
+        gradient is ADDED to ``.grad`` of the module's parameters.  With ``coef_grad`` the return value is ``(loss,
+        grad_D)``: ``grad_D`` is the gradient over the coefficients of ``equation.D``, a ``DiffusionLegendrePolynomials``, as
+        an fp64 array in the order of ``D.expansion.params``"""
         _reject(equation, solver)
+        if coef_grad:
+            from .numerics.functions.legendre import DiffusionLegendrePolynomials
+
+            if not isinstance(equation.D, DiffusionLegendrePolynomials):
+                raise NotImplementedError(f"coef_grad differentiates over the coefficients of a DiffusionLegendrePolynomials as D, "
+                                          f"not {type(equation.D).__name__}")
+            n_coef = len(equation.D.expansion.params)
+        adjoint_step = self.engine.fieldmu_adjoint_step_coef if coef_grad else self.engine.fieldmu_adjoint_step
         torch = self.torch
         integ = solver.integrator
         steps, saves = schedule(ts, dt0)
@@ -320,6 +341,10 @@ class FieldMuSolver:
                 if getattr(self, pending):
                     cnn.grad_read(reset=True)
                 setattr(self, pending, True)
+            if coef_grad:  # (a configure zeroes the slots too; this does not rely on _prepare being one)
+                if self._coef_pending:
+                    self.engine.fieldmu_coef_grad_read(n_coef, reset=True)
+                self._coef_pending = True
             vals = torch.as_tensor(np.ascontiguousarray(np.swapaxes(values, 0, 1)), dtype=Y.dtype).to(Y.device)  # (T - 1, B, ...)
             M = vals.numel()
             chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
@@ -356,7 +381,7 @@ class FieldMuSolver:
                 for s in range(s1 - 1, s0 - 1, -1):
                     if cnn is not None:
                         u = held.pop()
-                        self.engine.fieldmu_adjoint_step(integ, steps[s], u.data_ptr(), mu_of(u).data_ptr(), lam.data_ptr(), gmu.data_ptr())
+                        adjoint_step(integ, steps[s], u.data_ptr(), mu_of(u).data_ptr(), lam.data_ptr(), gmu.data_ptr())
                         cnn.vjp(u.data_ptr(), gmu.data_ptr(), lam.data_ptr())
                         if s in cot and s > 0:
                             lam += cot[s]
@@ -364,7 +389,7 @@ class FieldMuSolver:
                     u = held.pop().requires_grad_(True)
                     with torch.enable_grad():
                         mu = mu_of(u)
-                    self.engine.fieldmu_adjoint_step(integ, steps[s], u.data_ptr(), mu.data_ptr(), lam.data_ptr(), gmu.data_ptr())
+                    adjoint_step(integ, steps[s], u.data_ptr(), mu.data_ptr(), lam.data_ptr(), gmu.data_ptr())
                     mu.backward(gmu)
                     lam += u.grad
                     if s in cot and s > 0:
@@ -373,7 +398,10 @@ class FieldMuSolver:
             if cnn is not None:
                 add_flat_grad(equation._mu_module, cnn.grad_read(reset=True))
                 setattr(self, pending, False)
-        return loss
+            if coef_grad:
+                grad_D = self.engine.fieldmu_coef_grad_read(n_coef, reset=True)
+                self._coef_pending = False
+        return (loss, grad_D) if coef_grad else loss
 
 
 class _deterministic:

@@ -614,8 +614,9 @@ def check_equation(equation):
         from .numerics.equations.phase_field import FIELD_MU_SUPPORT
 
         raise NotImplementedError("forward-mode sensitivities (train of closure coefficients, optimize) do not run with a "
-                                  "torch.nn.Module as mu: the module itself is trained, by train(opt_parameters={'mu': module}, "
-                                  "method='mse') or mse_backward, on " + FIELD_MU_SUPPORT)
+                                  "torch.nn.Module as mu, not even one held fixed among other_parameters: the module itself is "
+                                  "trained, alone with D and kappa fixed or together with D, by train(opt_parameters={'mu': "
+                                  "module[, 'D': DiffusionLegendrePolynomials]}, method='mse') or mse_backward, on " + FIELD_MU_SUPPORT)
     if _is_butler_volmer(type(equation)) and callable(getattr(equation, "v", None)):
         raise NotImplementedError("Butler-Volmer sensitivities are autonomous: a voltage protocol v(t) is not supported; pass a "
                                   "number as v")

@@ -88,7 +88,7 @@ def _install_spectral(cls):
 
 # what a torch.nn.Module as mu runs on (pde_opt_amd.fieldmu)
 FIELD_MU_SUPPORT = ('CahnHilliard2DPeriodic with derivs="fd", SemiImplicitFourierSpectral or Euler with ConstantStepSize, '
-                    'fp32 / fp64, D and kappa fixed')
+                    'fp32 / fp64, D a DiffusionLegendrePolynomials (trainable) or a fixed in-kernel closure, kappa fixed')
 
 
 def _select_rhs(eq):

@@ -146,7 +146,8 @@ class PDEModel:
         ys = self.fieldmu_solver().solve(equation, solver, yb, np.asarray(ts, dtype=np.float64), float(dt0), stepsize_controller)
         return ys[:, 0] if single else ys
 
-    def mse_backward(self, parameters, y0s__values, solver_parameters, ts, weights, lambda_reg, dt0=0.000001) -> float:
+    def mse_backward(self, parameters, y0s__values, solver_parameters, ts, weights, lambda_reg, dt0=0.000001,
+                     closure_grads=None) -> float:
         """``mse(...)`` for a ``torch.nn.Module`` as ``parameters["mu"]``, and its gradient: ``.grad`` of the module's
         parameters is set to the gradient of ``mean(r^2) + reg`` (a discrete adjoint of the solve on the GPU, see
         ``pde_opt_amd.fieldmu``; the loss is summed in fp64).  The entry for ``torch.optim`` users:
@@ -154,7 +155,13 @@ class PDEModel:
             opt.zero_grad(); loss = model.mse_backward(params, (y0s, values), sp, ts, weights, lam); opt.step()
 
         ``weights["mu"]``: None, a number, a flat array or a module of the same structure (the weights of
-        ``lambda sum w p^2``).  Returns the loss as a float."""
+        ``lambda sum w p^2``).  Returns the loss as a float.
+
+        ``closure_grads``: a dict asks for the joint gradient.  ``parameters["D"]`` must then be a
+        ``DiffusionLegendrePolynomials``; on return ``closure_grads["D"]`` is the gradient of ``mean(r^2) + reg`` over its
+        coefficients (fp64, in the order of ``D.expansion.params``), from the same backward sweep.  ``weights["D"]`` has
+        the meaning ``fit.weight_vector`` gives a closure's weights; its share ``lambda sum w p^2`` is in the loss and
+        ``2 lambda w p`` in the gradient.  ``.grad`` of the module is the same, bit for bit, with and without."""
         from . import fieldmu
 
         module = parameters.get("mu")
@@ -169,45 +176,69 @@ class PDEModel:
             y0s = y0s.astype(np.float64)
         for q in module.parameters():
             q.grad = None
-        loss = self.fieldmu_solver().mse_backward(equation, solver, y0s, np.asarray(values), np.asarray(ts, dtype=np.float64), float(dt0))
+        loss = self.fieldmu_solver().mse_backward(equation, solver, y0s, np.asarray(values), np.asarray(ts, dtype=np.float64), float(dt0),
+                                                  coef_grad=closure_grads is not None)
+        if closure_grads is not None:
+            loss, grad_D = loss
         w = fieldmu.weight_vector(module, (weights or {}).get("mu"))
         if lambda_reg and np.any(w != 0.0):
             p = fieldmu.flatten_params(module)
             loss += float(lambda_reg * np.sum(w * p * p))
             fieldmu.add_flat_grad(module, 2.0 * float(lambda_reg) * w * p)
+        if closure_grads is not None:
+            w_D = fit.weight_vector(fit.ParamMap.of({"D": parameters["D"]}, self.equation_type), _array_weights(weights))
+            p_D = np.asarray(parameters["D"].expansion.params, dtype=np.float64)
+            if lambda_reg and np.any(w_D != 0.0):
+                loss += float(lambda_reg * np.sum(w_D * p_D * p_D))
+                grad_D = grad_D + 2.0 * float(lambda_reg) * w_D * p_D
+            closure_grads["D"] = grad_D
         return loss
 
     def _train_module(self, data, inds, opt_parameters, other_parameters, solver_parameters, weights, lambda_reg, method,
                       max_steps):
-        """``train`` for a ``torch.nn.Module`` as ``opt_parameters["mu"]``: BFGS over its flattened parameters"""
+        """``train`` for a ``torch.nn.Module`` as ``opt_parameters["mu"]``: BFGS over its flattened parameters, followed by
+        the coefficients of ``opt_parameters["D"]`` (a ``DiffusionLegendrePolynomials``) when that is given too"""
         from . import fieldmu
+        from .numerics.functions.legendre import DiffusionLegendrePolynomials
 
         if method == "least_squares":
             raise NotImplementedError("a torch.nn.Module as mu is trained with method='mse' (reverse mode gives the gradient of "
                                       "the loss, not the Jacobian Levenberg-Marquardt needs)")
-        if set(opt_parameters) != {"mu"}:
-            raise ValueError("with a torch.nn.Module as mu, opt_parameters holds mu alone: " + fieldmu.FIELD_MU_SUPPORT)
+        joint = "D" in opt_parameters
+        if not set(opt_parameters) <= {"mu", "D"} or (joint and not isinstance(opt_parameters["D"], DiffusionLegendrePolynomials)):
+            raise ValueError("with a torch.nn.Module as mu, opt_parameters holds mu alone, or mu and D as a "
+                             "DiffusionLegendrePolynomials: " + fieldmu.FIELD_MU_SUPPORT)
         module = opt_parameters["mu"]
         p0 = fieldmu.flatten_params(module)
+        n_mu = len(p0)
+        if joint:
+            p0 = np.concatenate([p0, np.asarray(opt_parameters["D"].expansion.params, dtype=np.float64)])
         if len(p0) > fit.MAX_DENSE_BFGS_PARAMS:
-            raise ValueError(f"mu has {len(p0)} parameters: train's BFGS keeps a dense inverse Hessian and takes at most "
+            raise ValueError(f"mu{' and D have' if joint else ' has'} {len(p0)} parameters: train's BFGS keeps a dense inverse Hessian and takes at most "
                              f"{fit.MAX_DENSE_BFGS_PARAMS}; use PDEModel.mse_backward with a torch.optim optimiser")
         y0s, values, ts = stack_training_data(data, inds)
-        params = {"mu": module, **other_parameters}
+        weights = _array_weights(weights)  # mse and mse_backward must see the same regularisation
+
+        def params_of(p):
+            """the module updated in place, D rebuilt from the tail of the flat vector"""
+            fieldmu.unflatten_params(module, p[:n_mu])
+            fitted = {"mu": module}
+            if joint:
+                fitted["D"] = DiffusionLegendrePolynomials(np.array(p[n_mu:], dtype=np.float64))
+            return {**fitted, **other_parameters}
 
         def value_and_grad(p):
-            fieldmu.unflatten_params(module, p)
-            f = self.mse_backward(params, (y0s, values), solver_parameters, ts, weights, lambda_reg)
-            return f, fieldmu.flatten_grads(module)
+            grads = {} if joint else None
+            f = self.mse_backward(params_of(p), (y0s, values), solver_parameters, ts, weights, lambda_reg, closure_grads=grads)
+            g = fieldmu.flatten_grads(module)
+            return f, (np.concatenate([g, grads["D"]]) if joint else g)
 
         def value(p):
-            fieldmu.unflatten_params(module, p)
-            return self.mse(params, (y0s, values), solver_parameters, ts, weights or {}, lambda_reg)
+            return self.mse(params_of(p), (y0s, values), solver_parameters, ts, weights or {}, lambda_reg)
 
         p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
-        fieldmu.unflatten_params(module, p)
         self.last_train_history = hist
-        return {"mu": module, **other_parameters}
+        return params_of(p)
 
     def _sens_engine(self):
         if getattr(self, "_sens_eng", None) is None:
@@ -233,7 +264,11 @@ class PDEModel:
 
         ``opt_parameters = {"mu": torch.nn.Module}`` (CahnHilliard2DPeriodic, ``method="mse"``): BFGS over the module's
         flattened parameters with the reverse-mode gradient of ``mse_backward``, for up to ``fit.MAX_DENSE_BFGS_PARAMS``
-        parameters; the returned dict holds the trained module (the one passed in, updated in place)."""
+        parameters; the returned dict holds the trained module (the one passed in, updated in place).  With ``"D":
+        DiffusionLegendrePolynomials`` next to it the mobility is trained too: the flat vector is the module's parameters
+        followed by ``D``'s coefficients (the cap applies to the total), the gradient over both comes from one backward
+        sweep (``mse_backward(..., closure_grads={})``), and the returned ``"D"`` is a new ``DiffusionLegendrePolynomials``.
+        ``kappa`` stays in ``other_parameters``."""
         _reject_rotating(self)
         fit.reject_unsupported(self)
         if method not in ("least_squares", "mse"):
@@ -664,6 +699,15 @@ class PDEModel:
             return J + reg.reg(p), grad + reg.reg_grad(p)
 
         return value_and_grad, value, pmap
+
+
+def _array_weights(weights) -> dict:
+    """``weights`` with a list or tuple under ``"D"`` as an array, which is what ``fit.regularization`` and
+    ``fit.weight_vector`` take for a closure's coefficients"""
+    weights = dict(weights or {})
+    if isinstance(weights.get("D"), (list, tuple)):
+        weights["D"] = np.asarray(weights["D"], dtype=np.float64)
+    return weights
 
 
 def _reject_rotating(model) -> None:
