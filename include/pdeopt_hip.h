@@ -532,9 +532,20 @@ int pdeopt_tsit5_solve_small(pdeopt_ctx* ctx, double t0, double t1, double dt0, 
  * trajectories in environments [0, B) and tangent j of trajectory b in environment B + j B + b (zero at t0: the
  * initial states are data).  pdeopt_get_state / pdeopt_snapshot / pdeopt_get_interpolated read and interpolate the
  * tangents like any environment. */
-typedef enum { PDEOPT_SENS_MU = 0, PDEOPT_SENS_MOB = 1 } pdeopt_sens_role;
+typedef enum { PDEOPT_SENS_MU = 0, PDEOPT_SENS_MOB = 1, PDEOPT_SENS_KAPPA = 2 } pdeopt_sens_role;
 /* the P parameters: parameter j is coefficient coef_index[j] of the closure roles[j]: mu_h, or the problem's second
- * closure (PDEOPT_SENS_MOB: Cahn-Hilliard's mobility D, Allen-Cahn's rate R).  For Allen-Cahn the constant coefficient
+ * closure (PDEOPT_SENS_MOB: Cahn-Hilliard's mobility D, Allen-Cahn's rate R).  PDEOPT_SENS_KAPPA is the scalar kappa, the
+ * gradient-energy coefficient: coef_index 0, at most once, the three periodic equations only (PDEOPT_EQ_CAHN_HILLIARD in
+ * 2-D, PDEOPT_EQ_CAHN_HILLIARD_3D, PDEOPT_EQ_ALLEN_CAHN; any other equation: PDEOPT_EINVAL), and the B trajectories
+ * must share one kappa (pdeopt_set_env_params values that differ between them: PDEOPT_EINVAL) -- the derivative is of
+ * one scalar.  Its tangent's direct term is d(mu_h - kappa lap u)/dkappa = -lap(u).  Under IMEX kappa also moves the
+ * implicit operator: with m = (1/n) / (1 + A dt s), s = fourier_symbol,
+ *   dy1 = dy0 + dt Re F^-1[ F[df] m + F[f_base] m' ],   m' = -(1/n) A dt (s / kappa) / (1 + A dt s)^2.
+ * THE SYMBOL IS TAKEN TO BE LINEAR IN KAPPA (ds/dkappa = s / kappa): the equation classes publish kappa K2^2; a symbol
+ * with another dependence on kappa gives a wrong kappa tangent.  The cross term needs the base spectrum next to the
+ * tangent's, so with a kappa role every grid runs rocFFT's real transforms (the base block then agrees with
+ * pdeopt_advance to rounding, not bit for bit, on the grids where that runs the hand-written passes).
+ * For Allen-Cahn the constant coefficient
  * of mu_h has a tangent like any other (mu_h itself enters the right-hand side); for Cahn-Hilliard it is identically 0.
  * The same holds for the smoothed-boundary forms: active for PDEOPT_EQ_ALLEN_CAHN_SBM, identically 0 for
  * PDEOPT_EQ_CAHN_HILLIARD_SBM (grad(inner) drops a constant).  Their free energy f (the closure `fe`), kappa, theta(t) and

@@ -33,6 +33,7 @@ CL_POLY, CL_LEGENDRE, CL_JIT = 0, 1, 2
 CL_LOGIT_PRIOR, CL_EXP_WRAP = 1, 2
 CL_SQRT_WRAP = 8  # the Butler-Volmer kernels only
 SENS_MU, SENS_MOB = 0, 1  # pdeopt_sens_role
+SENS_KAPPA = 2
 AUX_VX_FACE, AUX_VY_FACE, AUX_IMEX_SYMBOL, AUX_GPE_A_TERM, AUX_GPE_POTENTIAL = 0, 1, 2, 3, 4
 AUX_SBM_PSI, AUX_SBM_NORM_GRAD, AUX_SBM_MASK = 5, 6, 7
 RED_MEAN, RED_VAR, RED_MIN, RED_MAX, RED_SUMSQ, RED_NONFINITE = 0, 1, 2, 3, 4, 5

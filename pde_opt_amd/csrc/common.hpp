@@ -430,6 +430,13 @@ int imex_rocfft_solve(pdeopt_ctx* ctx, double dt);
 // c2r; the multiplier of the last imex_rocfft_prepare), and y += dt TA
 int imex_rocfft_apply(pdeopt_ctx* ctx);
 int axpy_state(pdeopt_ctx* ctx, double dt);
+// The rocFFT IMEX step of a sensitivity batch (B trajectories, then tangent j of trajectory b at B + j B + b) with a
+// kappa tangent among its P roles (sens.hip).  prepare_kappa, after imex_rocfft_prepare: the derivative of the
+// half-spectrum multiplier, m' = -(1/n) A dt (s / kappa) / (1 + A dt s)^2, built in double and symmetrised like m; the
+// symbol s is taken to be LINEAR in kappa (the equation classes publish kappa K2^2), so ds/dkappa = s / kappa.
+// solve_kappa: r2c, sens_imex_mul_kappa_kernel (c_j m, plus c_base m' for the kappa tangent), c2r, axpy
+int imex_rocfft_prepare_kappa(pdeopt_ctx* ctx, double dt, double kappa);
+int imex_rocfft_solve_kappa(pdeopt_ctx* ctx, double dt, int B, int P, const int* role);
 // one unnormalised complex transform of a whole-batch field [batch][nx][ny], in place, on the ctx's stream (the C2C
 // plans of the library Strang path: any grid); host copy of a shared complex aux field
 int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf);

@@ -8,10 +8,18 @@
 //          dk_j = J_f(y) du_j + df/dp_j for the tangent block (2-D Cahn-Hilliard: sens_tangent_rhs_kernel; 3-D:
 //          sens3d_dmu_kernel and sens3d_flux_kernel; Allen-Cahn: sens_ac_tangent_rhs_kernel),
 //          y += dt L^-1 k over the whole (1 + P) B batch (the forward IMEX transforms): L = 1 + A dt fourier_symbol is
-//          linear and independent of the coefficients (kappa is not trainable), so the tangent of the step is the
-//          same implicit solve applied to the linearised slope.  2-D power-of-two grids 64..1024 run the hand-written
+//          linear and independent of the closure coefficients, so their tangent of the step is the same implicit
+//          solve applied to the linearised slope.  2-D power-of-two grids 64..1024 run the hand-written
 //          FFT passes (4 launches + 1); other 2-D grids and the 3-D equation run the rocFFT real transforms, multiply
 //          and axpy of the forward rocFFT IMEX loop.  None of the launch counts depends on P.
+//          kappa (PDEOPT_SENS_KAPPA, the three periodic equations) moves L: with m = (1/n) / (1 + A dt s) and
+//          s = fourier_symbol = kappa K2^2 (taken to be linear in kappa: the equation classes publish nothing else),
+//            dy1 = dy0 + dt Re F^-1[ F[df] m + F[f_base] m' ],   m' = -(1/n) A dt (s / kappa) / (1 + A dt s)^2.
+//          The second term couples a tangent environment to its trajectory's spectrum, which the hand-written passes
+//          (two real environments packed into one complex field, multiply inside the column pass) cannot hold: with a
+//          kappa role configured every grid takes the rocFFT loop, whose multiply becomes sens_imex_mul_kappa_kernel
+//          (spectral.hip).  The slope kernels add d m / d kappa = -lap(u) to dmu of that tangent (template parameter
+//          KAPPA; the false instantiations are the kernels of a configuration without kappa, instruction for instruction).
 //   Euler  the same slope launches, then y += dt k over the whole batch.
 //   RK4    (Allen-Cahn) the classical tableau over the whole batch: per stage the slope launches at the stage's base and
 //          tangent values, then one pointwise update of the stage input and the accumulator -- the exact derivative of
@@ -37,7 +45,7 @@ namespace pdeopt {
 
 struct Sens {
   int B = 0, P = 0;
-  int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB
+  int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB / PDEOPT_SENS_KAPPA
   int index[kMaxSens] = {};  // coefficient k of that closure
   void* data = nullptr;      // [n_frames][B][*spatial] observed frames or cotangents, problem dtype
   int n_frames = 0;
@@ -45,6 +53,7 @@ struct Sens {
   double* partial = nullptr;  // [B][K][nblk] per-block sums of the accumulation (K = P for the contraction)
   double* sums = nullptr;     // [B][K]
   size_t partial_bytes = 0, sums_bytes = 0;
+  bool has_kappa = false;  // some role is PDEOPT_SENS_KAPPA: the KAPPA kernels, and IMEX through the rocFFT loop
 };
 
 namespace {
@@ -71,7 +80,9 @@ struct SensArgs {
 // with the forward kernel's primitives: 5-point Laplacian, face gradients, face averages, face divergence.
 // One workgroup per (tile, trajectory): u, mu, D and their derivatives are formed once, then the P tangents are
 // streamed through the same LDS tile (each tangent field read once, each tangent slope written once).
-template <typename T>
+// KAPPA: some role is PDEOPT_SENS_KAPPA; that tangent's direct term is dmu += d(mu_h - kappa lap u)/dkappa = -lap5(u),
+// recomputed from su, which is still resident (one more LDS array would take the fp64 kernel from 45.8 to 50.7 KB).
+template <typename T, bool KAPPA>
 __global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
   __shared__ T su[kR2 * kC2], sdu[kR2 * kC2];
   __shared__ T smu[kR1 * kC1], smuh[kR1 * kC1], sD[kR1 * kC1], smu1[kR1 * kC1], sD1[kR1 * kC1];
@@ -112,6 +123,7 @@ __global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
     }
     __syncthreads();
     const bool on_mu = a.role[j] == PDEOPT_SENS_MU;
+    const bool on_kappa = KAPPA && a.role[j] == PDEOPT_SENS_KAPPA;
     const int kc = a.index[j];
     for (int q = tid; q < kR1 * kC1; q += 256) {
       const int r = q / kC1, c = q - r * kC1;
@@ -121,6 +133,7 @@ __global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
       T dmu = smu1[q] * d - kappa * lap;
       T dD = sD1[q] * d;
       if (on_mu) dmu += closure_dcoef<T>(a.mu, kc, uc, smuh[q]);
+      else if (on_kappa) dmu -= (su[o + kC2] - T(2) * uc + su[o - kC2]) * a.rhx2 + (su[o + 1] - T(2) * uc + su[o - 1]) * a.rhy2;
       else dD += closure_dcoef<T>(a.mob, kc, uc, sD[q]);
       sdmu[q] = dmu;
       sdD[q] = dD;
@@ -154,6 +167,7 @@ __global__ __launch_bounds__(256) void sens_tangent_rhs_kernel(SensArgs<T> a) {
 // are staged in LDS (tile + 1-cell ring) and everything else a cell needs -- u, mu_h, m, R, R', mu_h' -- stays in the
 // registers of the thread that owns it.  A thread owns two neighbouring cells of a row.  Each tangent field is read
 // from HBM once and each tangent slope written once; per tangent only the basis function of closure_dcoef is evaluated.
+// KAPPA: the base Laplacian of the thread's two cells stays in registers too; the kappa tangent's dmu += -lap5(u).
 template <typename T>
 struct AcTile {
   static constexpr int V = 16 / (int)sizeof(T);  // cells per 16-byte vector
@@ -192,7 +206,7 @@ __device__ __forceinline__ void ac_stage(T* __restrict__ s, const T* __restrict_
   }
 }
 
-template <typename T>
+template <typename T, bool KAPPA>
 __global__ __launch_bounds__(256) void sens_ac_tangent_rhs_kernel(SensArgs<T> a) {
   using A = AcTile<T>;
   __shared__ __attribute__((aligned(16))) T su[A::kSize];
@@ -212,11 +226,13 @@ __global__ __launch_bounds__(256) void sens_ac_tangent_rhs_kernel(SensArgs<T> a)
   ac_stage<T>(su, a.y + (int64_t)b * cells, i0, j0, nx, ny, wide, tid);
   __syncthreads();
   T uc[2], muh[2], m[2], R[2], R1[2], mu1[2];
+  T lapu[2];  // KAPPA only
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int q = o + e;
     uc[e] = su[q];
     const T lap = (su[q + A::kLd] - T(2) * uc[e] + su[q - A::kLd]) * a.rhx2 + (su[q + 1] - T(2) * uc[e] + su[q - 1]) * a.rhy2;
+    if constexpr (KAPPA) lapu[e] = lap;
     muh[e] = closure_generic<T>(a.mu, ep.mu, uc[e]);
     m[e] = muh[e] - kappa * lap;
     R[e] = closure_generic<T>(a.mob, ep.mob, uc[e]);
@@ -229,6 +245,7 @@ __global__ __launch_bounds__(256) void sens_ac_tangent_rhs_kernel(SensArgs<T> a)
     ac_stage<T>(sdu, a.y + env * cells, i0, j0, nx, ny, wide, tid);
     __syncthreads();
     const bool on_mu = a.role[j] == PDEOPT_SENS_MU;
+    const bool on_kappa = KAPPA && a.role[j] == PDEOPT_SENS_KAPPA;
     const int kc = a.index[j];
     T df[2];
 #pragma unroll
@@ -239,7 +256,10 @@ __global__ __launch_bounds__(256) void sens_ac_tangent_rhs_kernel(SensArgs<T> a)
       T dmu = mu1[e] * d - kappa * lap;
       T dR = R1[e] * d;
       if (on_mu) dmu += closure_dcoef<T>(a.mu, kc, uc[e], muh[e]);
-      else dR += closure_dcoef<T>(a.mob, kc, uc[e], R[e]);
+      else if constexpr (KAPPA) {
+        if (on_kappa) dmu -= lapu[e];
+        else dR += closure_dcoef<T>(a.mob, kc, uc[e], R[e]);
+      } else dR += closure_dcoef<T>(a.mob, kc, uc[e], R[e]);
       df[e] = -(dR * m[e]) - R[e] * dmu;
     }
     T* __restrict__ out = a.k + env * cells + (int64_t)gi * ny + gj;
@@ -258,8 +278,9 @@ __global__ __launch_bounds__(256) void sens_ac_tangent_rhs_kernel(SensArgs<T> a)
 // ---- 3-D: CahnHilliard3DPeriodic.rhs_fd (cahn_hilliard.py:180-200), fields [env][nx][ny][nz] with z contiguous ----
 // Two passes, as the forward ch3d_mu_kernel / ch3d_stage_kernel (stencil_generic.hpp), with their primitives in their
 // order: 7-point Laplacian, face gradients, face averages, face divergence.
-//   pass 1  dmu_j = mu_h'(u) du_j + [role_j == MU] dmu_h/dp_j - kappa lap7(du_j)  -> the work field KS at the tangent
-//           environments (the base slope launch has left the base mu in KS[0, B))
+//   pass 1  dmu_j = mu_h'(u) du_j + [role_j == MU] dmu_h/dp_j - [role_j == KAPPA] lap7(u) - kappa lap7(du_j)  -> the work
+//           field KS at the tangent environments (the base slope launch has left the base mu in KS[0, B)); lap7(u), six
+//           more reads, is formed once before the loop and only in the KAPPA instantiation
 //   pass 2  df_j = div( avg_face(dD_j) grad_face(mu) + avg_face(D) grad_face(dmu_j) ),  dD_j = D'(u) du_j + [MOB] dD/dp_j
 // One thread per cell and trajectory, flat over the cells (a 32^3 field fills every lane); the values of u at the
 // stencil points (mu_h', or D and D' at the 7 points) are formed once and the thread then walks the P tangents.
@@ -293,7 +314,7 @@ __device__ __forceinline__ void nb7(const Sens3Args<T>& a, int c, int o[7]) {
 }
 
 // grid (cells / 256, B)
-template <typename T>
+template <typename T, bool KAPPA>
 __global__ __launch_bounds__(256) void sens3d_dmu_kernel(Sens3Args<T> a) {
   const int cells = a.nx * a.ny * a.nz;
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -306,6 +327,12 @@ __global__ __launch_bounds__(256) void sens3d_dmu_kernel(Sens3Args<T> a) {
   const T uc = a.y[(int64_t)b * cells + c];
   const T muh = closure_generic<T>(a.mu, ep.mu, uc);
   const T mu1 = closure_dc<T>(a.mu, ep.mu, uc, muh);
+  T lapu = T(0);
+  if constexpr (KAPPA) {
+    const T* __restrict__ u = a.y + (int64_t)b * cells;
+    lapu = (u[o[1]] - T(2) * uc + u[o[2]]) * a.rhx2 + (u[o[3]] - T(2) * uc + u[o[4]]) * a.rhy2 +
+           (u[o[5]] - T(2) * uc + u[o[6]]) * a.rhz2;
+  }
   for (int j = 0; j < a.P; ++j) {
     const int64_t env = (int64_t)a.B + (int64_t)j * a.B + b;
     const T* __restrict__ du = a.y + env * cells;
@@ -314,6 +341,7 @@ __global__ __launch_bounds__(256) void sens3d_dmu_kernel(Sens3Args<T> a) {
                   (du[o[5]] - T(2) * d + du[o[6]]) * a.rhz2;
     T dmu = mu1 * d - kappa * lap;
     if (a.role[j] == PDEOPT_SENS_MU) dmu += closure_dcoef<T>(a.mu, a.index[j], uc, muh);
+    else if (KAPPA && a.role[j] == PDEOPT_SENS_KAPPA) dmu -= lapu;
     a.w[env * cells + c] = dmu;
   }
 }
@@ -499,6 +527,36 @@ inline int64_t sens_cells(const pdeopt_ctx* ctx) {
   return (int64_t)p.nx * p.ny * (p.nz > 1 ? p.nz : 1);
 }
 
+// the equations whose tangent kernels have the kappa term
+inline bool sens_kappa_equation(const pdeopt_problem& p) {
+  return (p.equation == PDEOPT_EQ_CAHN_HILLIARD && p.nz <= 1) || p.equation == PDEOPT_EQ_CAHN_HILLIARD_3D ||
+         (p.equation == PDEOPT_EQ_ALLEN_CAHN && p.nz <= 1);
+}
+
+// A kappa role differentiates with respect to ONE scalar: the B trajectories must share it (as mobility coefficients
+// that differ between environments are refused).  *kappa: that value in double -- the problem's own when the
+// environments still hold it, else what pdeopt_set_env_params gave them
+int sens_kappa_check(pdeopt_ctx* ctx, int B, double* kappa) {
+  const pdeopt_problem& p = ctx->prob;
+  if (!sens_kappa_equation(p))
+    return fail(ctx, PDEOPT_EINVAL, "PDEOPT_SENS_KAPPA belongs to the periodic 2-D / 3-D Cahn-Hilliard and the periodic 2-D "
+                                    "Allen-Cahn equations: the smoothed-boundary and Butler-Volmer tangent kernels have no kappa "
+                                    "term (equation %d)", p.equation);
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    const auto* e = reinterpret_cast<const EnvParams<T>*>(ctx->env_params_host.data());
+    for (int b = 1; b < B; ++b)
+      if (e[b].kappa != e[0].kappa)
+        return fail(ctx, PDEOPT_EINVAL, "PDEOPT_SENS_KAPPA: trajectory %d has kappa = %g, trajectory 0 has %g; the derivative is "
+                                        "of one scalar shared by the trajectories", b, (double)e[b].kappa, (double)e[0].kappa);
+    if (!(e[0].kappa != T(0)))
+      return fail(ctx, PDEOPT_EINVAL, "PDEOPT_SENS_KAPPA: kappa = %g (the implicit operator's derivative divides the symbol by it)",
+                  (double)e[0].kappa);
+    if (kappa) *kappa = T(p.kappa) == e[0].kappa ? p.kappa : (double)e[0].kappa;
+    return (int)PDEOPT_OK;
+  });
+}
+
 int check_sens(pdeopt_ctx* ctx) {
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   const Sens* s = ctx->sens;
@@ -507,11 +565,12 @@ int check_sens(pdeopt_ctx* ctx) {
     return fail(ctx, PDEOPT_ESTATE, "batch %d is not (1 + P) B = %d: configure again before pdeopt_sens_configure",
                 ctx->prob.batch, (1 + s->P) * s->B);
   for (int j = 0; j < s->P; ++j) {
+    if (s->role[j] == PDEOPT_SENS_KAPPA) continue;  // a scalar: no closure behind it (sens_kappa_check below)
     const pdeopt_closure& cl = s->role[j] == PDEOPT_SENS_MU ? ctx->prob.mu : ctx->prob.mob;
     if (s->index[j] >= cl.n)
       return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: coefficient %d of a closure with %d coefficients", j, s->index[j], cl.n);
   }
-  return PDEOPT_OK;
+  return s->has_kappa ? sens_kappa_check(ctx, s->B, nullptr) : PDEOPT_OK;
 }
 
 // the members SensArgs and Sens3Args share
@@ -539,8 +598,15 @@ int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
   SensArgs<T> a{};
   fill_tangent_args<T>(a, ctx, in, out);
   const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, a.B);
-  if (p.equation == PDEOPT_EQ_ALLEN_CAHN) hipLaunchKernelGGL(sens_ac_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(sens_tangent_rhs_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  // the KAPPA instantiations only when a kappa role is configured: every other fit runs the kernels it always ran
+  const bool kap = ctx->sens->has_kappa;
+  if (p.equation == PDEOPT_EQ_ALLEN_CAHN) {
+    if (kap) hipLaunchKernelGGL((sens_ac_tangent_rhs_kernel<T, true>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((sens_ac_tangent_rhs_kernel<T, false>), grid, dim3(256), 0, ctx->stream, a);
+  } else {
+    if (kap) hipLaunchKernelGGL((sens_tangent_rhs_kernel<T, true>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((sens_tangent_rhs_kernel<T, false>), grid, dim3(256), 0, ctx->stream, a);
+  }
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -559,7 +625,8 @@ int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
   a.rhz = T(r.rz);
   a.rhz2 = T(r.rz2);
   const dim3 grid((unsigned)((sens_cells(ctx) + 255) / 256), a.B);
-  hipLaunchKernelGGL(sens3d_dmu_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  if (ctx->sens->has_kappa) hipLaunchKernelGGL((sens3d_dmu_kernel<T, true>), grid, dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((sens3d_dmu_kernel<T, false>), grid, dim3(256), 0, ctx->stream, a);
   hipLaunchKernelGGL(sens3d_flux_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   ctx->n_stage_launches += 2;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -724,7 +791,17 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
     return fail(ctx, PDEOPT_EINVAL, "n_traj = %d, n_params = %d (1 .. %d)", n_traj, n_params, kMaxSens);
   if ((int64_t)(1 + n_params) * n_traj != p.batch)
     return fail(ctx, PDEOPT_EINVAL, "batch %d is not (1 + n_params) n_traj = %d", p.batch, (1 + n_params) * n_traj);
+  bool has_kappa = false;
   for (int j = 0; j < n_params; ++j) {
+    if (roles[j] == PDEOPT_SENS_KAPPA) {
+      if (coef_index[j] != 0)
+        return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: PDEOPT_SENS_KAPPA is a scalar, its coef_index must be 0 (got %d)", j, coef_index[j]);
+      if (has_kappa) return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: PDEOPT_SENS_KAPPA given twice", j);
+      int rc;
+      if ((rc = sens_kappa_check(ctx, n_traj, nullptr))) return rc;
+      has_kappa = true;
+      continue;
+    }
     if (roles[j] != PDEOPT_SENS_MU && roles[j] != PDEOPT_SENS_MOB)
       return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: unknown role %d", j, roles[j]);
     const pdeopt_closure& cl = roles[j] == PDEOPT_SENS_MU ? p.mu : p.mob;
@@ -735,6 +812,7 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
   Sens& s = *ctx->sens;
   s.B = n_traj;
   s.P = n_params;
+  s.has_kappa = has_kappa;
   for (int j = 0; j < n_params; ++j) {
     s.role[j] = roles[j];
     s.index[j] = coef_index[j];
@@ -780,7 +858,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     }
   } table_guard{ctx, sbm};
   const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN || bv || sbm;  // Euler and RK4, no fourier_symbol
-  bool fused = false;
+  bool fused = false, kap = false;
   if (integrator == PDEOPT_INT_IMEX) {
     if (sbm)
       return fail(ctx, PDEOPT_EINVAL, "AllenCahn2DSmoothedBoundary / CahnHilliard2DSmoothedBoundary sensitivities support the Euler "
@@ -791,9 +869,16 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     if (ctx->imex_per_env)
       return fail(ctx, PDEOPT_EINVAL, "IMEX sensitivities need one implicit operator shared by the batch (no per-environment "
                                       "IMEX scales)");
-    // the hand-written FFT passes where they exist (power-of-two 2-D grids 64..1024), rocFFT's real transforms elsewhere
-    fused = imex_fused_supported(ctx);
+    // the hand-written FFT passes where they exist (power-of-two 2-D grids 64..1024), rocFFT's real transforms elsewhere;
+    // a kappa tangent needs the base spectrum next to its own (m'), which only the rocFFT loop's multiply can give it
+    kap = ctx->sens->has_kappa;
+    fused = !kap && imex_fused_supported(ctx);
     if ((rc = fused ? imex_fused_prepare(ctx, dt) : imex_rocfft_prepare(ctx, dt))) return rc;
+    if (kap) {
+      double kappa = 0.0;
+      if ((rc = sens_kappa_check(ctx, ctx->sens->B, &kappa))) return rc;
+      if ((rc = imex_rocfft_prepare_kappa(ctx, dt, kappa))) return rc;
+    }
   } else if (integrator == PDEOPT_INT_RK4 && ac) {
     if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
     if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
@@ -813,7 +898,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     if (integrator == PDEOPT_INT_IMEX && fused) {
       rc = imex_fused_passes(ctx, whole_batch(ctx), dt);
     } else if (integrator == PDEOPT_INT_IMEX) {
-      rc = imex_rocfft_solve(ctx, dt);
+      rc = kap ? imex_rocfft_solve_kappa(ctx, dt, ctx->sens->B, ctx->sens->P, ctx->sens->role) : imex_rocfft_solve(ctx, dt);
       ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls; rocFFT may run more than one kernel per transform)
     } else {
       rc = with_dtype(ctx, [&](auto t) { return euler_update<decltype(t)>(ctx, dt); });
@@ -829,7 +914,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   const int eq = ctx->prob.equation;
   ctx->last_kernel = eq == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "sens_sbm_ac_tangent_rhs"
                      : eq == PDEOPT_EQ_CAHN_HILLIARD_SBM ? "sens_sbm_ch_tangent_rhs" : (bv ? "bvsens_tangent_rhs" : (ac ? "sens_ac_tangent_rhs" : "sens_tangent_rhs"));
-  ctx->last_kernel += integrator == PDEOPT_INT_RK4 ? "+rk4" : (integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : "+imex_rocfft_r2c"));
+  ctx->last_kernel += integrator == PDEOPT_INT_RK4 ? "+rk4" : (integrator != PDEOPT_INT_IMEX ? "+euler" : (fused ? "+imex_fused_lds_fft" : (kap ? "+imex_rocfft_r2c_kappa" : "+imex_rocfft_r2c")));
   return PDEOPT_OK;
 }
 

@@ -40,6 +40,8 @@ struct Spectral {
   void* rwork = nullptr;
   void* hbuf = nullptr;    // hermitian half-spectrum work field
   void* hmult = nullptr;   // multiplier on the half-spectrum
+  void* hmultk = nullptr;  // d hmult / d kappa (sensitivities of kappa), cached on (dt, A, kappa)
+  double multk_dt = NAN, multk_A = NAN, multk_kappa = NAN;
   int64_t half_cells = 0;  // complex elements of one half-spectrum
   // batched 1-D complex plans along one axis of a [batch][nx][ny] field (the rotating-frame split step on grids the
   // hand-written passes do not cover): [0] along x (stride ny, one environment per execution), [1] along y
@@ -357,6 +359,28 @@ __global__ void axpy_real_kernel(T* __restrict__ y, const T* __restrict__ r, T d
   for (; i < n; i += st) y[i] += dt * r[i];
 }
 
+// A full-spectrum multiplier m(cell q of [nx][ny][nz]) in double, symmetrised onto the half spectrum of the real
+// transforms: h(k) = (m(k) + conj m(-k)) / 2 (see imex_t).  Half-spectrum layout [slow ...][fast/2+1]: the halved axis is
+// the fastest non-trivial one (z for the 3-D equations, else y, else x for the ny == 1 "1-D" runs)
+template <typename T, typename F>
+std::vector<C2<T>> half_spectrum(const pdeopt_problem& p, int64_t hc, F m) {
+  const int nzz = p.nz > 1 ? p.nz : 1;
+  const int n3[3] = {p.nx, p.ny, nzz};
+  auto at = [&](int i, int j, int k) -> std::complex<double> { return m(((size_t)i * p.ny + j) * nzz + k); };
+  std::vector<C2<T>> h((size_t)hc);
+  const int fast = nzz > 1 ? 2 : (p.ny > 1 ? 1 : 0);
+  const int nh = n3[fast] / 2 + 1;
+  int64_t o = 0;
+  for (int i = 0; i < (fast == 0 ? nh : p.nx); ++i)
+    for (int j = 0; j < (fast == 1 ? nh : (fast == 0 ? 1 : p.ny)); ++j)
+      for (int k = 0; k < (fast == 2 ? nh : 1); ++k) {
+        const std::complex<double> v =
+            0.5 * (at(i, j, k) + std::conj(at((p.nx - i) % p.nx, (p.ny - j) % p.ny, (nzz - k) % nzz)));
+        h[(size_t)o++] = C2<T>{(T)v.real(), (T)v.imag()};
+      }
+  return h;
+}
+
 // plans, work fields and the half-spectrum multiplier of step dt (kept while dt and A hold)
 template <typename T>
 int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
@@ -374,23 +398,7 @@ int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
     std::vector<std::complex<double>> sym;
     if ((rc = fetch_complex_aux(ctx, PDEOPT_AUX_IMEX_SYMBOL, sym))) return rc;
     const double inv_n = 1.0 / (double)cells;
-    const int n3[3] = {p.nx, p.ny, nzz};
-    auto m = [&](int i, int j, int k) {
-      return inv_n / (1.0 + ctx->imex_A * dt * sym[((size_t)i * p.ny + j) * nzz + k]);
-    };
-    std::vector<C2<T>> h((size_t)hc);
-    // half-spectrum layout [slow ...][fast/2+1]: the halved axis is the fastest non-trivial one
-    // (z for the 3-D equations, else y, else x for the ny == 1 "1-D" runs)
-    const int fast = nzz > 1 ? 2 : (p.ny > 1 ? 1 : 0);
-    const int nh = n3[fast] / 2 + 1;
-    int64_t o = 0;
-    for (int i = 0; i < (fast == 0 ? nh : p.nx); ++i)
-      for (int j = 0; j < (fast == 1 ? nh : (fast == 0 ? 1 : p.ny)); ++j)
-        for (int k = 0; k < (fast == 2 ? nh : 1); ++k) {
-          const std::complex<double> v =
-              0.5 * (m(i, j, k) + std::conj(m((p.nx - i) % p.nx, (p.ny - j) % p.ny, (nzz - k) % nzz)));
-          h[(size_t)o++] = C2<T>{(T)v.real(), (T)v.imag()};
-        }
+    const std::vector<C2<T>> h = half_spectrum<T>(p, hc, [&](size_t q) { return inv_n / (1.0 + ctx->imex_A * dt * sym[q]); });
     if ((rc = ensure_buffer(ctx, &sp.hmult, (size_t)hc * sizeof(C2<T>)))) return rc;
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.hmult, h.data(), (size_t)hc * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -428,6 +436,97 @@ template <typename T>
 int imex_rocfft_solve_t(pdeopt_ctx* ctx, double dt) {
   const int rc = imex_rocfft_apply_t<T>(ctx);
   return rc ? rc : axpy_state_t<T>(ctx, dt);
+}
+
+// ---- the IMEX multiply of a sensitivity batch whose operator moves with a parameter (kappa) -------------------------
+//   dy1 = dy0 + dt Re F^-1[ F[df] m + F[f_base] m' ]
+// grid (cells of the half spectrum, B): one thread takes spectrum cell i of trajectory b.  It reads the base value v0
+// once, writes c[env_j][i] m[i] for every tangent j (plus v0 m'[i] where role[j] is kappa) and, last, v0 m[i] into the
+// base: no other thread reads that base value, nothing is overwritten before it is used, no atomics, no extra launch.
+// The products by m are spectral_mul_kernel<T, false>'s expression in its order: the bits of the base and of the other
+// tangents do not depend on a kappa tangent being there.
+template <typename T>
+struct KappaMulArgs {
+  C2<T>* c;             // [(1 + P) B][cells] half spectra
+  const C2<T>* m;       // [cells]
+  const C2<T>* mk;      // [cells] dm / dkappa
+  int64_t cells;
+  int B, P;
+  int role[kMaxSens];
+};
+
+template <typename T>
+__device__ __forceinline__ C2<T> spectral_mul1(const C2<T> v, const C2<T> w) {
+  C2<T> r;
+  r.re = (v.re * w.re - v.im * w.im) * T(1);
+  r.im = (v.re * w.im + v.im * w.re) * T(1);
+  return r;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sens_imex_mul_kappa_kernel(KappaMulArgs<T> a) {
+  const int b = blockIdx.y;
+  const int64_t st = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.cells; i += st) {
+    const C2<T> w = a.m[i];
+    C2<T>* base = a.c + (int64_t)b * a.cells + i;
+    const C2<T> v0 = *base;
+    for (int j = 0; j < a.P; ++j) {
+      C2<T>* cj = a.c + ((int64_t)a.B + (int64_t)j * a.B + b) * a.cells + i;
+      C2<T> r = spectral_mul1<T>(*cj, w);
+      if (a.role[j] == PDEOPT_SENS_KAPPA) {
+        const C2<T> wk = a.mk[i];
+        r.re += v0.re * wk.re - v0.im * wk.im;
+        r.im += v0.re * wk.im + v0.im * wk.re;
+      }
+      *cj = r;
+    }
+    *base = spectral_mul1<T>(v0, w);
+  }
+}
+
+template <typename T>
+int imex_rocfft_prepare_kappa_t(pdeopt_ctx* ctx, double dt, double kappa) {
+  Spectral& sp = *ctx->spectral;  // (imex_rocfft_prepare has run: plans, hbuf, hmult)
+  const pdeopt_problem& p = ctx->prob;
+  const int64_t hc = sp.half_cells;
+  if (sp.hmultk && sp.multk_dt == dt && sp.multk_A == ctx->imex_A && sp.multk_kappa == kappa) return PDEOPT_OK;
+  int rc;
+  std::vector<std::complex<double>> sym;
+  if ((rc = fetch_complex_aux(ctx, PDEOPT_AUX_IMEX_SYMBOL, sym))) return rc;
+  const double inv_n = 1.0 / (double)sym.size(), adt = ctx->imex_A * dt;
+  const std::vector<C2<T>> h = half_spectrum<T>(p, hc, [&](size_t q) {
+    const std::complex<double> L = 1.0 + adt * sym[q];
+    return -inv_n * adt * (sym[q] / kappa) / (L * L);
+  });
+  if ((rc = ensure_buffer(ctx, &sp.hmultk, (size_t)hc * sizeof(C2<T>)))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.hmultk, h.data(), (size_t)hc * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  sp.multk_dt = dt;
+  sp.multk_A = ctx->imex_A;
+  sp.multk_kappa = kappa;
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int imex_rocfft_solve_kappa_t(pdeopt_ctx* ctx, double dt, int B, int P, const int* role) {
+  Spectral& sp = *ctx->spectral;
+  const int64_t hc = sp.half_cells;
+  if (P < 1 || P > kMaxSens || (int64_t)(1 + P) * B != ctx->prob.batch)
+    return fail(ctx, PDEOPT_ESTATE, "IMEX kappa multiply: batch %d is not (1 + %d) %d", ctx->prob.batch, P, B);
+  int rc;
+  if ((rc = real_fft_exec(ctx, true, ctx->TA, sp.hbuf))) return rc;
+  KappaMulArgs<T> a{};
+  a.c = (C2<T>*)sp.hbuf;
+  a.m = (const C2<T>*)sp.hmult;
+  a.mk = (const C2<T>*)sp.hmultk;
+  a.cells = hc;
+  a.B = B;
+  a.P = P;
+  for (int j = 0; j < P; ++j) a.role[j] = role[j];
+  hipLaunchKernelGGL(sens_imex_mul_kappa_kernel<T>, dim3(grid_for(hc), B), dim3(256), 0, ctx->stream, a);
+  if ((rc = real_fft_exec(ctx, false, sp.hbuf, ctx->TA))) return rc;
+  return axpy_state_t<T>(ctx, dt);
 }
 
 // IMEX on real <-> hermitian transforms.  The reference runs full complex transforms on the real
@@ -777,6 +876,14 @@ int imex_rocfft_solve(pdeopt_ctx* ctx, double dt) {
   return with_dtype(ctx, [&](auto t) { return imex_rocfft_solve_t<decltype(t)>(ctx, dt); });
 }
 
+int imex_rocfft_prepare_kappa(pdeopt_ctx* ctx, double dt, double kappa) {
+  return with_dtype(ctx, [&](auto t) { return imex_rocfft_prepare_kappa_t<decltype(t)>(ctx, dt, kappa); });
+}
+
+int imex_rocfft_solve_kappa(pdeopt_ctx* ctx, double dt, int B, int P, const int* role) {
+  return with_dtype(ctx, [&](auto t) { return imex_rocfft_solve_kappa_t<decltype(t)>(ctx, dt, B, P, role); });
+}
+
 int imex_rocfft_apply(pdeopt_ctx* ctx) {
   return with_dtype(ctx, [&](auto t) { return imex_rocfft_apply_t<decltype(t)>(ctx); });
 }
@@ -818,7 +925,10 @@ int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
 }
 
 void spectral_invalidate(pdeopt_ctx* ctx) {
-  if (ctx->spectral) ctx->spectral->mult_kind = -1;
+  if (ctx->spectral) {
+    ctx->spectral->mult_kind = -1;
+    ctx->spectral->multk_dt = NAN;
+  }
   strang_fused_invalidate(ctx);
   gpe_adjoint_invalidate(ctx);
   gpe_rot_invalidate(ctx);
@@ -846,7 +956,7 @@ void spectral_destroy(pdeopt_ctx* ctx) {
   if (sp->fwd) rocfft_plan_destroy(sp->fwd);
   if (sp->inv) rocfft_plan_destroy(sp->inv);
   if (sp->info) rocfft_execution_info_destroy(sp->info);
-  void* bufs[] = {sp->work, sp->rwork, sp->hbuf, sp->hmult, sp->cbuf, sp->cbuf2, sp->cbuf3, sp->mult, sp->dens, sp->partial, sp->scale};
+  void* bufs[] = {sp->work, sp->rwork, sp->hbuf, sp->hmult, sp->hmultk, sp->cbuf, sp->cbuf2, sp->cbuf3, sp->mult, sp->dens, sp->partial, sp->scale};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete sp;

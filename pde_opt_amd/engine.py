@@ -415,7 +415,8 @@ class HipEngine:
 
     # -- forward-mode sensitivities (batch = (1 + P) B: trajectories, then tangent j of trajectory b at B + j B + b) --
     def sens_configure(self, n_traj: int, params):
-        """``params``: P pairs ``(role, coefficient index)`` with role ``L.SENS_MU`` or ``L.SENS_MOB``"""
+        """``params``: P pairs ``(role, coefficient index)`` with role ``L.SENS_MU``, ``L.SENS_MOB`` or ``L.SENS_KAPPA`` (the
+        scalar kappa of the periodic equations: index 0, at most once)"""
         roles = np.ascontiguousarray([int(r) for r, _ in params], dtype=np.int32)
         index = np.ascontiguousarray([int(k) for _, k in params], dtype=np.int32)
         self._check(self._lib.pdeopt_sens_configure(self._h, int(n_traj), len(roles), roles.ctypes.data_as(C.c_void_p),

@@ -23,6 +23,15 @@ Also covered: the smoothed-boundary classes ``AllenCahn2DSmoothedBoundary`` (``m
 time through ``theta(t)`` and ``flux(t)``: every advance is told its start time, and the tangent kernel evaluates the
 wall term at the stage times of the base solve.  ``f``, ``kappa``, ``theta`` and ``flux`` are fixed data
 (``other_parameters``).
+
+One scalar is trainable: ``kappa`` of the three periodic classes, as ``opt_parameters={"kappa": TrainableScalar(0.002)}``
+(``numerics/functions/scalar.py``), alone or next to any mix of ``mu`` / ``D`` / ``R`` coefficients.  Its tangent is one
+more environment (``L.SENS_KAPPA``); the optimiser's variable is ``log(kappa)`` (``positive=True``, the default), so the
+sums the GPU returns for ``du/dkappa`` are scaled by ``kappa`` (``ParamMap.column_factors``) wherever they become
+Jacobian columns, Gauss-Newton sums or gradients.  Under IMEX kappa moves the implicit operator: the sensitivity advance
+then differentiates the operator too and runs rocFFT's transforms on every grid (csrc/sens.hip).  A plain float among
+``opt_parameters`` stays refused; so does ``TrainableScalar`` for the smoothed-boundary and Butler-Volmer classes, whose
+tangent kernels have no kappa term.
 """
 
 from __future__ import annotations
@@ -37,6 +46,7 @@ from . import _lib as L
 from .integrate import constant_step_plan
 from .numerics.closures import UnsupportedClosureError, is_torch_module
 from .numerics.functions.legendre import ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials
+from .numerics.functions.scalar import TrainableScalar
 
 RTOL = ATOL = 1e-8  # optimistix tolerances of the reference's train (pde_model.py:398-401, 428-431)
 
@@ -47,8 +57,11 @@ MAX_DENSE_BFGS_PARAMS = 4096
 
 # closure classes whose coefficient arrays are trainable, and the constructor argument that holds their role
 # ("D" is Cahn-Hilliard's mobility, "R" Allen-Cahn's rate, "j0" the Butler-Volmer exchange current: the engine's second
-# closure every time).  A scalar role (alpha, kappa, Crate) would be a new entry here and a new pdeopt_sens_role.
+# closure every time).
 _ROLES = {"mu": L.SENS_MU, "D": L.SENS_MOB, "R": L.SENS_MOB, "j0": L.SENS_MOB}
+# scalars of the equation that are trainable as a TrainableScalar, and their pdeopt_sens_role (coefficient index 0).
+# Another scalar (alpha, Crate) would be a new entry here, a new pdeopt_sens_role and its term in the tangent kernels.
+_SCALAR_ROLES = {"kappa": L.SENS_KAPPA}
 
 
 # ---- parameters -----------------------------------------------------------------------------------------------------
@@ -64,7 +77,8 @@ class NotTrainableError(ValueError, NotImplementedError):
 @dataclasses.dataclass
 class ParamMap:
     """The trainable leaves of ``opt_parameters`` as one flat vector ``p``.  Entry ``j`` is coefficient ``index[j]``
-    of the closure in role ``role[j]``.  ``closure_desc()`` folds a polynomial ``prior_fn`` into the series, so the
+    of the closure in role ``role[j]``, or -- for a ``TrainableScalar`` (size 1, role ``L.SENS_KAPPA``, index 0) -- the
+    scalar's variable: ``log(value)`` when ``positive``, else the value.  ``closure_desc()`` folds a polynomial ``prior_fn`` into the series, so the
     kernel's coefficients are ``p`` plus a fixed offset; fitted closures are rebuilt from ``p`` itself (same class,
     same ``prior_fn``), which keeps the offset out of the returned values."""
 
@@ -86,11 +100,22 @@ class ParamMap:
                     f"opt_parameters[{key!r}]: {key} of {equation_type.__name__} is fixed data of the fit (the free energy of "
                     "the wall term, the gradient coefficient, the contact angle theta(t) and the boundary flux flux(t) have "
                     "no tangent kernel); pass it in other_parameters")
+            if key in _SCALAR_ROLES and isinstance(value, TrainableScalar):
+                if _is_butler_volmer(equation_type):
+                    raise NotTrainableError(
+                        f"opt_parameters[{key!r}]: {key} of {equation_type.__name__} is not trainable (the Butler-Volmer tangent "
+                        "kernels have no kappa term: it is trainable for the periodic Cahn-Hilliard and Allen-Cahn classes only); "
+                        "pass a number in other_parameters")
+                keys.append(key)
+                templates.append(value)
+                sizes.append(1)
+                continue
             if key not in _ROLES or not isinstance(value, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
                 raise NotTrainableError(
                     f"opt_parameters[{key!r}]: only the coefficient arrays of ChemicalPotentialLegendrePolynomials / "
                     "DiffusionLegendrePolynomials in the 'mu' and 'D' (Allen-Cahn: 'R', Butler-Volmer: 'j0') roles are trainable "
-                    "(kappa and other scalars would move the implicit operator of the solver); pass them in other_parameters")
+                    "(kappa and other scalars would move the implicit operator of the solver: kappa of the periodic classes is "
+                    "trainable as a TrainableScalar, a plain number is fixed data); pass them in other_parameters")
             keys.append(key)
             templates.append(value)
             sizes.append(len(value.expansion.params))
@@ -104,13 +129,43 @@ class ParamMap:
         return sum(self.sizes)
 
     def all_params(self) -> List[Tuple[int, int]]:
-        return [(_ROLES[k], i) for k, n in zip(self.keys, self.sizes) for i in range(n)]
+        return [(_SCALAR_ROLES[k] if k in _SCALAR_ROLES else _ROLES[k], i) for k, n in zip(self.keys, self.sizes) for i in range(n)]
 
     def active(self) -> np.ndarray:
         """entries whose tangent is not identically zero.  For Cahn-Hilliard mu's constant coefficient is not: only
         grad mu enters the right-hand side, so its tangent is never solved for (its Jacobian column is exactly 0).
-        Allen-Cahn's right-hand side holds mu itself: every entry is active"""
+        Allen-Cahn's right-hand side holds mu itself: every entry is active.  A scalar (kappa) is active on every
+        equation"""
         return np.array([self.mu_constant_active or not (role == L.SENS_MU and i == 0) for role, i in self.all_params()])
+
+    def _scalars(self):
+        """(offset in p, template) of every TrainableScalar entry"""
+        o = 0
+        for tpl, n in zip(self.templates, self.sizes):
+            if isinstance(tpl, TrainableScalar):
+                yield o, tpl
+            o += n
+
+    def column_factors(self, p: np.ndarray) -> np.ndarray:
+        """``d value / d p`` per entry of ``p``: ``kappa`` for a positive scalar (its variable is the logarithm), 1
+        elsewhere.  The tangents the GPU advances are derivatives with respect to the VALUES; multiplied by this they
+        are the optimiser's columns."""
+        s = np.ones(self.size)
+        for o, tpl in self._scalars():
+            s[o] = tpl.with_variable(p[o]).column_factor()
+        return s
+
+    def feasible(self, p: np.ndarray) -> bool:
+        """can an equation be built at ``p``?  False when a ``positive=False`` kappa has a value ``<= 0`` (or any entry
+        is not finite): such a trial is a rejected step / failed line-search point and is never sent to the engine"""
+        if not np.all(np.isfinite(p)):
+            return False
+        return all(tpl.with_variable(p[o]).value > 0.0 for o, tpl in self._scalars())
+
+    def scale_sums(self, p, rdp, G):
+        """the sums over all entries (``expand``) turned from value-derivatives into variable-derivatives"""
+        s = self.column_factors(p)
+        return rdp * s, G * np.outer(s, s)
 
     def sens_params(self) -> List[Tuple[int, int]]:
         """the (role, coefficient) pairs of the tangents the GPU advances"""
@@ -126,18 +181,26 @@ class ParamMap:
         return r, g
 
     def flatten(self, params: dict) -> np.ndarray:
-        return np.concatenate([np.asarray(params[k].expansion.params, dtype=np.float64) for k in self.keys])
+        return np.concatenate([np.array([params[k].variable()]) if isinstance(params[k], TrainableScalar)
+                               else np.asarray(params[k].expansion.params, dtype=np.float64) for k in self.keys])
 
     def build(self, p: np.ndarray) -> dict:
         out, o = {}, 0
         for key, tpl, n in zip(self.keys, self.templates, self.sizes):
             coef = np.array(p[o:o + n], dtype=np.float64)
             o += n
-            if isinstance(tpl, ChemicalPotentialLegendrePolynomials):
+            if isinstance(tpl, TrainableScalar):
+                out[key] = tpl.with_variable(coef[0])
+            elif isinstance(tpl, ChemicalPotentialLegendrePolynomials):
                 out[key] = ChemicalPotentialLegendrePolynomials(coef, tpl.prior_fn)
             else:
                 out[key] = DiffusionLegendrePolynomials(coef)
         return out
+
+
+def plain(parameters: dict) -> dict:
+    """``parameters`` with every ``TrainableScalar`` replaced by its float: what an equation class is built from"""
+    return {k: (float(v) if isinstance(v, TrainableScalar) else v) for k, v in parameters.items()}
 
 
 def _is_allen_cahn(equation_type) -> bool:
@@ -175,6 +238,8 @@ def _leaves(obj) -> list:
         return [flatten_params(obj)]
     if isinstance(obj, (ChemicalPotentialLegendrePolynomials, DiffusionLegendrePolynomials)):
         return [np.asarray(obj.expansion.params, dtype=np.float64)]
+    if isinstance(obj, TrainableScalar):  # the optimiser's variable, as a one-coefficient closure's coefficient
+        return [np.array([obj.variable()])]
     if isinstance(obj, (int, float, np.ndarray, np.number)):
         a = np.asarray(obj)
         return [a.astype(np.float64)] if np.issubdtype(a.dtype, np.inexact) or isinstance(obj, float) else []

@@ -1,4 +1,5 @@
-"""Function representations used as closures: the Legendre family, light spots; ``cnn.PeriodicCNN`` (a torch module, imported on
+"""Function representations used as closures: the Legendre family, light spots, ``TrainableScalar`` (a scalar of the
+equation, such as kappa, as a trainable entry); ``cnn.PeriodicCNN`` (a torch module, imported on
 demand: ``from pde_opt_amd.numerics.functions.cnn import PeriodicCNN``) and ``mixer.Mixer2d`` (likewise:
 ``from pde_opt_amd.numerics.functions.mixer import Mixer2d``) as ``mu`` of CahnHilliard2DPeriodic."""
 
@@ -8,6 +9,7 @@ from .legendre import (
     DiffusionLegendrePolynomials,
     LegendrePolynomialExpansion,
 )
+from .scalar import TrainableScalar
 
 __all__ = [
     "GaussianSpot",
@@ -15,4 +17,5 @@ __all__ = [
     "LegendrePolynomialExpansion",
     "DiffusionLegendrePolynomials",
     "ChemicalPotentialLegendrePolynomials",
+    "TrainableScalar",
 ]

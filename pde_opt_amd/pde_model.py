@@ -5,8 +5,8 @@ keeps the upstream signature and returns ``ys`` of shape ``(len(ts), *y0.shape)`
 it never throws on divergence (``throw=False``: NaNs are returned).  ``adjoint`` is accepted and
 ignored: forward solves need no adjoint.
 
-``train`` / ``residuals`` / ``mse`` / ``regularization`` (pde_model.py:138-460) fit closure coefficients to
-trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
+``train`` / ``residuals`` / ``mse`` / ``regularization`` (pde_model.py:138-460) fit closure coefficients -- and
+``kappa`` of the periodic classes, given as a ``TrainableScalar`` -- to trajectories: the derivative of the solve comes from forward-mode tangents advanced on the GPU next to the
 trajectories (``pde_opt_amd.fit``; csrc/sens.hip) -- periodic Cahn-Hilliard in 2-D or 3-D (``mu`` / ``D``; IMEX or
 Euler), periodic 2-D Allen-Cahn (``mu`` / ``R``; Euler or RK4) and the Butler-Volmer Allen-Cahn classes (``mu`` / ``j0``;
 Euler or RK4; ``voltage_sensitivities`` and ``train(..., voltage_weight=...)`` add the voltage of a constant-current run), with
@@ -30,6 +30,7 @@ and the spots' numbers (csrc/gpe_rot_stir_adjoint.hip) and ``optimize_stirring``
 
 from __future__ import annotations
 
+import math
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -61,6 +62,7 @@ class PDEModel:
         max_steps=1000000,
         stepsize_controller=None,
     ):
+        parameters = fit.plain(parameters)  # a TrainableScalar (train's kappa) is its number to the equation
         equation = self.equation_type(domain=self.domain, **parameters)
         solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
         if getattr(equation, "_mu_module", None) is not None:  # a network as mu: torch evaluates it, the kernels take the field
@@ -255,6 +257,11 @@ class PDEModel:
         ``(nx, ny, nz)`` for CahnHilliard3DPeriodic.  Returns ``{**fitted, **other_parameters}``; each fitted closure is the class it
         started as, with its ``prior_fn``.
 
+        ``opt_parameters["kappa"] = TrainableScalar(value)`` (``numerics/functions/scalar.py``) fits the gradient-energy
+        coefficient of the three periodic classes too, alone or next to closures; the optimiser moves ``log(kappa)`` and the
+        returned dict holds a ``TrainableScalar``, which ``solve`` / ``residuals`` / ``mse`` take as it is.  A plain float
+        among ``opt_parameters`` is refused.
+
         The Butler-Volmer Allen-Cahn classes train ``"mu"`` and ``"j0"`` (Legendre closures; Euler or RK4); their scalars
         ``alpha``, ``kappa``, ``Crate`` / ``v`` are not trainable and go in ``other_parameters``.  With ``data["vs"]`` -- the cell
         voltages aligned with ``data["ys"]`` -- and ``voltage_weight > 0`` a constant-current class fits the voltage curve
@@ -286,7 +293,7 @@ class PDEModel:
             vs = data["vs"]
             v_obs = np.array([[float(vs[ind[i]]) for ind in inds] for i in range(1, len(inds[0]))], dtype=np.float64)
             w_v = float(voltage_weight) * values.size / v_obs.size  # mean(r_V^2) weighed against mean(r_field^2) = ssr / M
-        equation0 = self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters})
+        equation0 = self.equation_type(domain=self.domain, **fit.plain({**opt_parameters, **other_parameters}))
         fit.check_equation(equation0)
         frames = np.ascontiguousarray(np.swapaxes(values, 0, 1))  # (T - 1, B, *spatial)
         frames_key = object()
@@ -295,12 +302,14 @@ class PDEModel:
         eng = self._sens_engine()
 
         def setup(p):
-            params = {**pmap.build(p), **other_parameters}
+            params = fit.plain({**pmap.build(p), **other_parameters})
             equation = self.equation_type(domain=self.domain, **params)
             solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
             return params, equation, solver
 
         def sums(p):
+            if not pmap.feasible(p):  # kappa <= 0 under positive=False: a rejected step, never a solve
+                return math.inf, np.zeros(pmap.size), np.zeros((pmap.size, pmap.size))
             _, equation, solver = setup(p)
             volt = [] if v_obs is not None else None
             s, _ = fit.sensitivity_solve(eng, equation, solver, y0s, ts, sens_params, frames=frames,
@@ -309,9 +318,11 @@ class PDEModel:
             if volt is not None:
                 vd = np.stack(volt[1:])  # (T - 1, B, 1 + P)
                 ssr, rdp, G = fit.add_voltage_sums(ssr, rdp, G, v_obs - vd[..., 0], vd[..., 1:], w_v)
-            return (ssr,) + pmap.expand(rdp, G)
+            return (ssr,) + pmap.scale_sums(p, *pmap.expand(rdp, G))
 
         def ssr(p):
+            if not pmap.feasible(p):
+                return math.inf
             params, equation, _ = setup(p)
             if v_obs is None:
                 r, _ = self.residuals(params, (y0s, values), solver_parameters, ts, {}, 0.0)
@@ -670,7 +681,7 @@ class PDEModel:
             raise ValueError("optimize needs y0, ts and opt_parameters")
         fit.reject_unsupported(self)
         pmap = fit.ParamMap.of(opt_parameters, self.equation_type)
-        fit.check_equation(self.equation_type(domain=self.domain, **{**opt_parameters, **other_parameters}))
+        fit.check_equation(self.equation_type(domain=self.domain, **fit.plain({**opt_parameters, **other_parameters})))
         spatial_ndim = len(self.domain.points)
         if y0.ndim not in (spatial_ndim, spatial_ndim + 1):
             raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points)} or (B,) + that")
@@ -683,10 +694,14 @@ class PDEModel:
             return {**pmap.build(p), **other_parameters}
 
         def value(p):
+            if not pmap.feasible(p):  # kappa <= 0 under positive=False: a failed line-search point, never a solve
+                return math.inf
             return objective.value(self.solve(params_of(p), y0, ts, solver_parameters)) + reg.reg(p)
 
         def value_and_grad(p):
-            params = params_of(p)
+            if not pmap.feasible(p):
+                return math.inf, np.full(pmap.size, np.nan)
+            params = fit.plain(params_of(p))
             equation = self.equation_type(domain=self.domain, **params)
             solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
 
@@ -696,7 +711,7 @@ class PDEModel:
 
             ys = self.solve(params, y0, ts, solver_parameters)
             J, grad = fit.objective_gradient(objective, ys, spatial_ndim, contract, pmap)
-            return J + reg.reg(p), grad + reg.reg_grad(p)
+            return J + reg.reg(p), grad * pmap.column_factors(p) + reg.reg_grad(p)
 
         return value_and_grad, value, pmap
 

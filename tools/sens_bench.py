@@ -18,7 +18,11 @@ synchronise (CahnHilliard2DPeriodic 128^2 x 1, IMEX, P = 3 / 7, `substeps` subst
 ``--sbm`` times the smoothed-boundary classes (AllenCahn2DSmoothedBoundary, CahnHilliard2DSmoothedBoundary inside a disc,
 ramped theta(t), RK4): an RK4 sensitivity substep at P = 3 and P = 7 next to the forward RK4 substep of the same problem
 in the same run, 128^2 x 3 and 1024^2 x 8.
-Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only | --optimize | --sbm]
+``--kappa`` times an IMEX sensitivity substep of CahnHilliard2DPeriodic with kappa among the P = 3 tangents (kappa, mu a1,
+D c0: the rocFFT loop with sens_imex_mul_kappa_kernel on every grid) next to P = 3 without it (mu a1, a2, D c0: the
+parent's code path, the hand-written FFT passes on these grids) in the same run, 128^2 x 3 and 1024^2 x 8, and -- to
+separate the reroute from the new kernels -- the closure-only tangents forced through the rocFFT loop as well.
+Prints one JSON line.  usage: python tools/sens_bench.py [--quick] [--ac-only | --optimize | --sbm | --kappa]
 """
 import json
 import sys
@@ -197,6 +201,37 @@ def sbm_rows(quick):
     return rows
 
 
+def kappa_case(n, B, dtype, nsub):
+    from pde_opt_amd.numerics.functions import TrainableScalar
+
+    dom = P.Domain((n, n), ((0.0, 1.0), (0.0, 1.0)), "dimensionless")
+    rng = np.random.default_rng(0)
+    y0s = np.clip(0.5 + 0.05 * rng.standard_normal((B,) + dom.points), 0.05, 0.95).astype(dtype)
+    row = {"equation": "cahn_hilliard", "integrator": "imex", "n": n, "B": B, "dtype": np.dtype(dtype).name, "P": 3}
+    with_kappa = {"kappa": TrainableScalar(KAPPA), "mu": ChemLeg(np.array([0.0, -3.0]), logit), "D": DiffLeg(np.array([0.0]))}
+    for name, opt, rocfft in (("without_kappa", closures(3), False), ("without_kappa_rocfft", closures(3), True),
+                              ("with_kappa", with_kappa, False)):
+        eq = P.CahnHilliard2DPeriodic(dom, **fit.plain({"kappa": KAPPA, **opt}))
+        solver = P.SemiImplicitFourierSpectral(A=0.5, fourier_symbol=eq.fourier_symbol)
+        sp = fit.ParamMap.of(opt, P.CahnHilliard2DPeriodic).sens_params()
+        assert len(sp) == 3 and ((L.SENS_KAPPA, 0) in sp) == (name == "with_kappa")
+        sens = P.HipEngine()
+        if rocfft:
+            sens._check(sens._lib.pdeopt_set_option(sens._h, L.OPT_IMEX_LDS_FFT, -1))  # rocFFT's transforms on every grid
+        fit._configure(sens, eq, solver, y0s, sp, 0.0, 1.0)
+        row[name + "_us_per_substep"] = 1e3 * timed(sens, lambda: sens.sens_advance(L.INT_IMEX, DT, nsub), 5) / nsub
+        row[name + "_kernel"] = sens.last_kernel
+        sens.close()
+    row["with_over_without"] = row["with_kappa_us_per_substep"] / row["without_kappa_us_per_substep"]
+    row["with_over_without_rocfft"] = row["with_kappa_us_per_substep"] / row["without_kappa_rocfft_us_per_substep"]
+    return row
+
+
+def kappa_rows(quick):
+    return [kappa_case(n, B, dtype, nsub) for n, B, nsub in ((128, 3, 200), (1024, 8, 20)) for dtype in (np.float32, np.float64)
+            if not (quick and n > 128)]
+
+
 class _SecondMoment:
     """J = mean(ys[-1]^2) with its cotangent, in numpy (the objective's own cost stays out of the comparison)"""
 
@@ -236,6 +271,9 @@ def main():
         return
     if "--sbm" in sys.argv:
         print(json.dumps({"tool": "sens_bench", "mode": "sbm", "cases": sbm_rows(quick)}))
+        return
+    if "--kappa" in sys.argv:
+        print(json.dumps({"tool": "sens_bench", "mode": "kappa", "dt": DT, "cases": kappa_rows(quick)}))
         return
     if "--ac-only" in sys.argv:
         print(json.dumps({"tool": "sens_bench", "dt": DT, "cases": ac_rows(quick)}))
