@@ -39,8 +39,8 @@ struct StrangFused {
   // IMEX on the same transforms
   void* cwork = nullptr;      // complex work field [batch][nx][ny]
   size_t cwork_bytes = 0;
-  bool imex_sym_real = true;  // the uploaded fourier_symbol has no imaginary part (per-environment scales need that)
-  void* imex_mult = nullptr;  // 1 / ((1 + A dt symbol) nx ny)
+  void* imex_mult = nullptr;  // symmetrised 1 / ((1 + A dt symbol) nx ny); with per-environment scales A dt symbol
+  bool imex_per_env = false;  // which of the two imex_mult holds
   double imex_dt = NAN, imex_A = NAN;
   bool imex_valid = false;
 };
@@ -140,6 +140,16 @@ __global__ __launch_bounds__(256) void strang_row_reg_kernel(Cx<T>* __restrict__
 #define PDEOPT_COL_WL_MAX 512
 #endif
 constexpr bool col_wave_local(int n) { return PDEOPT_COL_WL && n <= PDEOPT_COL_WL_MAX; }
+
+// 1 / (N (1 + sigma S)) for the complex S = A dt symbol of one frequency: the implicit multiplier of an environment
+// whose fourier_symbol is sigma x the uploaded one
+template <typename T>
+__device__ __forceinline__ Cx<T> imex_env_mult(const Cx<T> s, const T sigma, const T inv_n) {
+  const T dr = T(1) + sigma * s.re, di = sigma * s.im;
+  const T q = inv_n / (dr * dr + di * di);
+  return Cx<T>{dr * q, -di * q};
+}
+
 template <typename T, int N, int C, int PTS, bool SCALED, bool PER_ENV = false>
 __global__ __launch_bounds__(C* N / PTS) void strang_col_reg_kernel(Cx<T>* __restrict__ psi,
                                                                   const Cx<T>* __restrict__ mult,
@@ -192,18 +202,16 @@ __global__ __launch_bounds__(C* N / PTS) void strang_col_reg_kernel(Cx<T>* __res
     E::template dif<-1, false>(v, seq, tw, j);
   T scale = T(1);
   if constexpr (SCALED) scale = (T)scale_sh;
-  // IMEX with a per-environment implicit operator (one environment per complex field): the stored multiplier is
-  // M0 = 1 / (N (1 + A dt symbol)), real; this environment's is 1 / (N (1 + sigma (1 / (N M0) - 1)))
+  // IMEX with a per-environment implicit operator (one environment per complex field): the stored table is
+  // S = A dt symbol, complex and NOT symmetrised (a field with a zero imaginary part needs no real-to-real form:
+  // the row pass keeps Re of the result, solvers.py:63); this environment's multiplier is 1 / (N (1 + sigma S))
   // (a template parameter: as a run-time branch its divisions cost every instantiation 4-5 VGPRs, and the 512^2
   // Strang pass -- two 1024-thread workgroups per CU -- lives at the 64-VGPR limit: 54 -> 71 us)
   const T sigma = PER_ENV ? sigma_ep[env].imex_scale : T(1);
 #pragma unroll
   for (int sl = 0; sl < PTS; ++sl) {
     Cx<T> m = WL ? mb[E::freq(ji, sl)] : mb[E::freq(j, sl) * ny + c];
-    if constexpr (PER_ENV) {
-      m.re = inv_n / (T(1) + sigma * (inv_n / m.re - T(1)));
-      m.im = T(0);
-    }
+    if constexpr (PER_ENV) m = imex_env_mult(m, sigma, inv_n);
     m.re *= scale;
     m.im *= scale;
     v[sl] = cmul(v[sl], m);
@@ -304,10 +312,7 @@ __global__ __launch_bounds__(C * 32, 4) void strang_col32_kernel(Cx<T>* __restri
 #pragma unroll
   for (int sl = 0; sl < PTS; ++sl) {
     Cx<T> m = buf_load_cx(rmul, voff, sl * rstep);
-    if constexpr (PER_ENV) {  // per-environment implicit operator, see strang_col_reg_kernel
-      m.re = inv_n / (T(1) + sigma * (inv_n / m.re - T(1)));
-      m.im = T(0);
-    }
+    if constexpr (PER_ENV) m = imex_env_mult(m, sigma, inv_n);  // per-environment implicit operator, see strang_col_reg_kernel
     m.re *= scale;
     m.im *= scale;
     v[sl] = cmul(v[sl], m);
@@ -685,7 +690,7 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
   }
   if ((rc = ensure_buffer(ctx, &sf.cwork, cwork_need))) return rc;
   sf.cwork_bytes = std::max(sf.cwork_bytes, cwork_need);
-  if (!sf.imex_valid || sf.imex_dt != dt || sf.imex_A != ctx->imex_A) {
+  if (!sf.imex_valid || sf.imex_dt != dt || sf.imex_A != ctx->imex_A || sf.imex_per_env != ctx->imex_per_env) {
     // 1 / ((1 + A dt fourier_symbol) nx ny): solvers.py:62-63 with the 1/N of the inverse folded in
     const AuxField& a = ctx->aux[PDEOPT_AUX_IMEX_SYMBOL];
     std::vector<std::complex<double>> sym((size_t)cells);
@@ -698,20 +703,21 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
     }
     // M(k) = 1 / ((1 + A dt symbol(k)) nx ny), then M_h(k) = (M(k) + conj M(-k)) / 2: the transforms carry
     // two real environments per complex field (imex_row_fwd_reg_kernel), which needs the real-to-real form
+    // With one environment per complex field (per-environment scales) the imaginary part of the field is zero and
+    // the row pass keeps Re of the result: no symmetrisation, and the table is S = A dt symbol itself, from which
+    // the column pass forms 1 / ((1 + sigma_b S) nx ny) (imex_env_mult).  Symmetrising first would be wrong there
+    // for a symbol that is not even: the mirror average of 1 / (1 + S) does not scale with sigma like S does.
     std::vector<std::complex<double>> mfull((size_t)cells);
     const double inv_n = 1.0 / (double)cells;
-    sf.imex_sym_real = true;
-    for (int64_t i = 0; i < cells; ++i) {
-      mfull[i] = inv_n / (1.0 + ctx->imex_A * dt * sym[i]);
-      sf.imex_sym_real = sf.imex_sym_real && sym[i].imag() == 0.0;
-    }
+    for (int64_t i = 0; i < cells; ++i) mfull[i] = inv_n / (1.0 + ctx->imex_A * dt * sym[i]);
     std::vector<Cx<T>> m((size_t)cells);
     for (int kx = 0; kx < p.nx; ++kx) {
       const int mx = (p.nx - kx) % p.nx;
       for (int ky = 0; ky < p.ny; ++ky) {
         const int my = (p.ny - ky) % p.ny;
         const std::complex<double> v =
-            0.5 * (mfull[(size_t)kx * p.ny + ky] + std::conj(mfull[(size_t)mx * p.ny + my]));
+            ctx->imex_per_env ? ctx->imex_A * dt * sym[(size_t)kx * p.ny + ky]
+                              : 0.5 * (mfull[(size_t)kx * p.ny + ky] + std::conj(mfull[(size_t)mx * p.ny + my]));
         m[col_mult_index(kx, ky, p.nx, p.ny)] = Cx<T>{(T)v.real(), (T)v.imag()};
       }
     }
@@ -721,9 +727,8 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
     sf.imex_valid = true;
     sf.imex_dt = dt;
     sf.imex_A = ctx->imex_A;
+    sf.imex_per_env = ctx->imex_per_env;
   }
-  if (ctx->imex_per_env && !sf.imex_sym_real)
-    return fail(ctx, PDEOPT_EINVAL, "per-environment IMEX scales need a real fourier_symbol");
   return PDEOPT_OK;
 }
 
