@@ -392,6 +392,33 @@ enum {
 };
 int pdeopt_gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
                            double* host_out);
+/* Mass, free energy, chemical-potential moments and dissipation of the resident phase-field state, per environment,
+ * computed on the device: host_out is [env_count][PDEOPT_PF_OBS_COUNT].  The sums are discretised so that they are
+ * consistent with the finite-difference right-hand side.  With h = hx hy (hz), mu = mu_h(u) - kappa lap(u) the 5- /
+ * 7-point chemical potential of the stage kernels, grad_f the forward difference to the face, D_f the face average of D(u):
+ *   MASS   h sum u            U2   h sum u^2         F_BULK  h sum f_h(u), f_h the antiderivative of mu_h, f_h(0) = 0
+ *   F_GRAD h sum kappa/2 sum_axes (grad_f u)^2       MU  h sum mu           MU2  h sum mu^2
+ *   DISS   Cahn-Hilliard: h sum_faces D_f (grad_f mu)^2;  Allen-Cahn: h sum R(u) mu^2
+ *   NONFINITE  number of cells whose u or mu is not finite
+ * so that d(F_BULK + F_GRAD)/du_ij = h mu_ij and d(F_BULK + F_GRAD)/dt = -DISS along u_t = rhs.  kappa and the closure
+ * coefficients per environment as pdeopt_set_env_params left them.  The state is not modified; sums in fp64 in a fixed
+ * order, no atomics: a repeat gives identical bits, and a sub-range gives the rows of the full call.
+ * PDEOPT_EQ_CAHN_HILLIARD, PDEOPT_EQ_ALLEN_CAHN and PDEOPT_EQ_CAHN_HILLIARD_3D with derivs = FD on the periodic layout;
+ * mu a polynomial or Legendre series, with or without PDEOPT_CL_LOGIT_PRIOR; D / R any closure of the family.
+ * PDEOPT_ESTATE before pdeopt_configure.  PDEOPT_EINVAL with the reason: any other equation, derivs = FOURIER, the padded
+ * layout, a mu with PDEOPT_CL_MIX_ENTROPY or PDEOPT_CL_EXP_WRAP, run-time-compiled closures, a range outside the batch. */
+enum {
+  PDEOPT_PF_OBS_MASS = 0,
+  PDEOPT_PF_OBS_U2 = 1,
+  PDEOPT_PF_OBS_F_BULK = 2,
+  PDEOPT_PF_OBS_F_GRAD = 3,
+  PDEOPT_PF_OBS_MU = 4,
+  PDEOPT_PF_OBS_MU2 = 5,
+  PDEOPT_PF_OBS_DISS = 6,
+  PDEOPT_PF_OBS_NONFINITE = 7,
+  PDEOPT_PF_OBS_COUNT = 8
+};
+int pdeopt_pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 
 /* ---- domain decomposition of one large field (BASELINE config 5; no reference counterpart) -----
  * With PDEOPT_OPT_HALO_LAYOUT = 4 a ctx holds one rank's tile.  Per RK4 substep the caller runs

@@ -47,11 +47,12 @@ from .numerics.solvers import (
 )
 from .pde_env import PDEEnv, VectorPDEEnv
 from .pde_model import PDEModel
+from .phase_field_observables import PhaseFieldObservables
 
 __all__ = [
     "PDEModel", "PDEEnv", "VectorPDEEnv", "HipEngine", "diffeqsolve", "Solution",
     "BaseEquation", "AllenCahn2DPeriodic", "CahnHilliard2DPeriodic", "AdvectionDiffusion2D", "GPE2DTSControl",
-    "GPE2DTSRot", "RotatingStrangSplitting", "OBSERVABLE_NAMES", "GpeObservables", "GroundState",
+    "GPE2DTSRot", "RotatingStrangSplitting", "OBSERVABLE_NAMES", "GpeObservables", "GroundState", "PhaseFieldObservables",
     "AllenCahn2DSmoothedBoundary", "CahnHilliard2DSmoothedBoundary", "CahnHilliard3DPeriodic",
     "AllenCahn2DPeriodicButlerVolmer", "AllenCahn2DPeriodicButlerVolmerConstantCurrent",
     "AllenCahn2DSmoothedBoundaryButlerVolmerConstantCurrent",

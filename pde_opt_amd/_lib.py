@@ -40,6 +40,9 @@ RED_MEAN, RED_VAR, RED_MIN, RED_MAX, RED_SUMSQ, RED_NONFINITE = 0, 1, 2, 3, 4, 5
 # pdeopt_gpe_observables: entries of a row (PDEOPT_GPE_OBS_*)
 GPE_OBS_NORM, GPE_OBS_E_KIN, GPE_OBS_E_POT, GPE_OBS_E_INT, GPE_OBS_L_Z, GPE_OBS_X2, GPE_OBS_Y2 = range(7)
 GPE_OBS_COUNT = 8
+# pdeopt_pf_observables: entries of a row (PDEOPT_PF_OBS_*)
+PF_OBS_MASS, PF_OBS_U2, PF_OBS_F_BULK, PF_OBS_F_GRAD, PF_OBS_MU, PF_OBS_MU2, PF_OBS_DISS, PF_OBS_NONFINITE = range(8)
+PF_OBS_COUNT = 8
 OPT_KERNEL_PATH = 0
 OPT_TILE_ROWS = 1
 OPT_GROUP_ENVS = 2
@@ -167,6 +170,7 @@ _SIGNATURES = {
     "pdeopt_observe_u8_device": (C.c_int, [_VP, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "pdeopt_detect_vortices": (C.c_int, [_VP, C.c_double, C.c_double, C.c_int, C.c_int, _VP, _VP]),
     "pdeopt_gpe_observables": (C.c_int, [_VP, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP]),
+    "pdeopt_pf_observables": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_tsit5_trial": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_double, _VP]),
     "pdeopt_tsit5_commit": (C.c_int, [_VP, C.c_int]),
     "pdeopt_tsit5_trial_env": (C.c_int, [_VP, C.c_double, _VP, C.c_double, C.c_double, C.POINTER(C.c_double), _VP]),

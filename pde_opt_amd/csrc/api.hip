@@ -286,6 +286,7 @@ int pdeopt_ctx_destroy(pdeopt_ctx* ctx) {
   free_fields(ctx);
   if (ctx->red_dev) (void)hipFree(ctx->red_dev);
   if (ctx->red_mean_dev) (void)hipFree(ctx->red_mean_dev);
+  if (ctx->pf_obs_dev) (void)hipFree(ctx->pf_obs_dev);
   if (ctx->adaptive_blk) (void)hipFree(ctx->adaptive_blk);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -897,6 +898,14 @@ int pdeopt_gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_cou
   if (ctx->halo) return fail(ctx, PDEOPT_EINVAL, "gpe_observables is not available in the padded layout");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return env_count ? gpe_observables(ctx, t, env_first, env_count, x_first, y_first, host_out) : PDEOPT_OK;
+}
+
+int pdeopt_pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out) {
+  if (!ctx || !host_out) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return pf_observables(ctx, env_first, env_count, host_out);  // (its refusals hold for an empty range too)
 }
 
 int pdeopt_tsit5_trial(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol,

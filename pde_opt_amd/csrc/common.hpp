@@ -240,6 +240,8 @@ struct pdeopt_ctx {
   double* red_dev = nullptr;  // reduction scratch
   size_t red_cap = 0;
   double* red_mean_dev = nullptr;
+  double* pf_obs_dev = nullptr;  // pdeopt_pf_observables: the rows [envs][8], then the workgroups' partial rows; grow-only
+  size_t pf_obs_cap = 0;
   std::vector<void*> host_allocs;  // pdeopt_host_alloc
   pdeopt::CommState* comm = nullptr;
   pdeopt::Spectral* spectral = nullptr;
@@ -459,6 +461,9 @@ void gpe_rot_stir_adjoint_destroy(pdeopt_ctx* ctx);
 int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
                     double* host_out);
 void gpe_obs_destroy(pdeopt_ctx* ctx);
+// pf_obs.hip: mass, free energy, chemical-potential moments and dissipation of the resident phase-field state (periodic
+// CH, AC, CH-3D with finite differences), [env_count][PDEOPT_PF_OBS_COUNT] doubles; refuses what it does not cover
+int pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 // gpe_adjoint.hip: its buffers live and die with the spectral state (spectral_destroy / spectral_invalidate)
 void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_adjoint_destroy(pdeopt_ctx* ctx);

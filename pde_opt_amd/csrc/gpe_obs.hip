@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_sums.hpp"
 #include "common.hpp"
 #include "fft_lds.hpp"
 #include "fft_reg.hpp"
@@ -58,29 +59,6 @@ __device__ __forceinline__ int signed_index(int f, int n) { return f < (n + 1) /
 template <typename T>
 __device__ __forceinline__ double abs2(const Cx<T> v) {
   return (double)v.re * (double)v.re + (double)v.im * (double)v.im;
-}
-
-// sum of NV values per lane over the workgroup's NW waves, in a fixed order; the first NV threads store one each at dst
-template <int NV, int NW>
-__device__ __forceinline__ void block_sums(double (&a)[NV], double* __restrict__ dst) {
-  __shared__ double red[NW][NV];
-#pragma unroll
-  for (int c = 0; c < NV; ++c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a[c] += __shfl_down(a[c], o, 64);
-  }
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int c = 0; c < NV; ++c) red[tid >> 6][c] = a[c];
-  }
-  __syncthreads();
-  if (tid < NV) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s += red[w][tid];
-    dst[tid] = s;
-  }
 }
 
 // the five pointwise terms of one cell, added into a[0] norm, a[2] e_pot, a[3] e_int, a[5] x2, a[6] y2

@@ -611,6 +611,16 @@ class HipEngine:
                                                      float(self.gpe_origin[1]), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def pf_observables(self, env_first: int = 0, env_count: Optional[int] = None) -> np.ndarray:
+        """Mass, free energy, chemical-potential moments and dissipation of the resident phase-field state
+        (``pdeopt_pf_observables``), summed on the device: ``(envs, 8)`` float64 in the order of
+        ``phase_field_observables.RAW_NAMES``, 64 bytes per environment instead of the field.  Periodic Cahn-Hilliard
+        (2-D, 3-D) and Allen-Cahn with ``derivs="fd"``; anything else raises ``ValueError`` with the reason."""
+        n = self.batch - env_first if env_count is None else env_count
+        out = np.zeros((n, L.PF_OBS_COUNT), dtype=np.float64)
+        self._check(self._lib.pdeopt_pf_observables(self._h, int(env_first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def tsit5_trial(self, t: float, dt: float, rtol: float, atol: float) -> np.ndarray:
         err = np.empty(self.batch, dtype=np.float64)
         self._check(

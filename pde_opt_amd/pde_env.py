@@ -256,6 +256,10 @@ class _EnvShard:
 
         t_begin = time.perf_counter()
         env, eng = self.env, self.engine
+        if isinstance(env.device_reward, tuple) and env.device_reward[0] == "phase_field":
+            from .phase_field_observables import check_equation
+
+            check_equation(eqs[0])  # derivs, closures: refused before the engine is touched
         eq0 = self._configure(eqs)
         type(eq0)._engine_upload_batch(eng, eqs, 0.0, env.step_dt)
         solver = env.solver_type(**prepare_solver_params(env.solver_type, env.solver_parameters, eq0))
@@ -281,6 +285,12 @@ class _EnvShard:
             else:
                 omega, kappa = equation_weights(eqs, float(env.step_dt))
             rewards = GpeObservables.from_raw(eng.gpe_observables(float(env.step_dt)), omega, kappa)[env.device_reward[1]]
+        elif isinstance(env.device_reward, tuple) and env.device_reward[0] == "phase_field":
+            # ("phase_field", name): a free-energy observable of the state after the step, summed on the device with the
+            # per-environment kappa and coefficients the engine carries (64 bytes per environment come back)
+            from .phase_field_observables import PhaseFieldObservables, volume_of
+
+            rewards = PhaseFieldObservables.from_raw(eng.pf_observables(), volume_of(env.domain))[env.device_reward[1]]
         elif isinstance(env.device_reward, tuple):
             # ("vortices", amp_thresh, tol): rl_utils.detect_vortices' num_vortices per environment, counted on the
             # device (pde_opt/rl_utils.py:19-84): 24 bytes per environment cross PCIe instead of the wavefunction
@@ -342,7 +352,9 @@ class VectorPDEEnv:
     per environment on host copies unless ``device_reward`` names an on-device reduction
     (``"var"``, ``"mean"``, ``"min"``, ``"max"``, ``("vortices", amp_thresh, tol)`` = the number of quantised
     vortices of a GPE state, ``rl_utils.detect_vortices`` on the device, or ``("gpe", name)`` = an observable of a GPE
-    state, ``name`` in ``gpe_observables.OBSERVABLE_NAMES + ("energy", "mu")``), which avoids the D2H of full fields;
+    state, ``name`` in ``gpe_observables.OBSERVABLE_NAMES + ("energy", "mu")``, or ``("phase_field", name)`` = a
+    free-energy observable of a periodic Cahn-Hilliard / Allen-Cahn state, ``name`` in
+    ``phase_field_observables.REWARD_NAMES``, e.g. ``"free_energy"``), which avoids the D2H of full fields;
     ``device_observation=(lo, hi)`` forms the uint8 image observations of the declared
     observation space on the GPU (1 byte per cell crosses PCIe instead of 4 or 8);
     ``device_observation=("probes", cells)`` returns the state at the listed grid cells instead (sensor-style
@@ -393,6 +405,12 @@ class VectorPDEEnv:
             if len(device_reward) != 2 or device_reward[1] not in OBSERVABLE_NAMES + DERIVED_NAMES:
                 raise ValueError(f"unknown device reward {device_reward!r} (\"gpe\" takes one of {OBSERVABLE_NAMES + DERIVED_NAMES})")
             reject_unsupported(equation_type)
+        elif isinstance(device_reward, tuple) and device_reward[0] == "phase_field":
+            from . import phase_field_observables as pfo
+
+            if len(device_reward) != 2 or device_reward[1] not in pfo.REWARD_NAMES:
+                raise ValueError(f"unknown device reward {device_reward!r} (\"phase_field\" takes one of {pfo.REWARD_NAMES})")
+            pfo.reject_unsupported(equation_type)
         elif isinstance(device_reward, tuple) and device_reward[0] != "vortices":
             raise ValueError(f"unknown device reward {device_reward[0]!r}")
         if isinstance(device_reward, str) and device_reward not in self._RED:
