@@ -3,7 +3,7 @@ trap (GPE2DTSRot) whose rotation ramps up, Omega(t) = omega + omega_rate t, whil
 it (``lights``: a GaussianSpots evaluated in-kernel); only the final state is observed.
 ``PDEModel.optimize_stirring`` recovers the spot's ``x_rate`` and ``omega_rate`` with BFGS on the gradient of
 ``PDEModel.stirring_gradient``: a discrete adjoint of the stirred alternating-direction split step on the GPU
-(csrc/gpe_rot_stir_adjoint.hip).
+(csrc/gpe_rot_adjoint.hip).
 
     python examples/gpe_stirring_fit.py [--points 64] [--substeps 20]
 """

@@ -239,7 +239,7 @@ int pdeopt_set_env_gpe_omega(pdeopt_ctx* ctx, int env_first, int env_count, cons
 /* per-environment rate of change of Omega: the step of PDEOPT_INT_STRANG_ROT that starts at local time t (the t of
  * pdeopt_advance's substep, t0 + s dt) uses Omega(t) = omega + rate t in all four of its line operators.
  * pdeopt_set_gpe_rotation resets every rate to 0.  With light spots (pdeopt_set_gpe_spots) or a nonzero rate the step
- * runs its stirred kernels (csrc/gpe_rot_stir.hip); pdeopt_gpe_rot_adjoint_step refuses both, their gradients are
+ * runs its stirred kernels (csrc/gpe_rot.hip); pdeopt_gpe_rot_adjoint_step refuses both, their gradients are
  * pdeopt_gpe_rot_stir_adjoint_step's. */
 int pdeopt_set_env_gpe_omega_rate(pdeopt_ctx* ctx, int env_first, int env_count, const double* rate);
 /* Butler-Volmer equations (PDEOPT_EQ_ALLEN_CAHN_BV / _SBM_BV), after pdeopt_configure: the symmetry factor alpha (shared),

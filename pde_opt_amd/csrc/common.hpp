@@ -129,8 +129,7 @@ struct Sens;         // forward-mode sensitivity configuration + Gauss-Newton bu
 struct GpeAdjoint;   // work fields + multiplier of the Strang step's adjoint (gpe_adjoint.hip)
 struct GpeRot;       // tables + work fields of the rotating-frame ADI split step (gpe_rot.hip)
 struct GpeObs;       // tables + partial sums of the GPE observables (gpe_obs.hip)
-struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint (gpe_rot_adjoint.hip)
-struct GpeRotStirAdjoint;  // the same of the stirred, ramped step's adjoint (gpe_rot_stir_adjoint.hip)
+struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint, frozen or stirred (gpe_rot_adjoint.hip)
 struct BvState;      // parameters, partial sums and voltages of the Butler-Volmer equations (butler_volmer.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
@@ -250,12 +249,12 @@ struct pdeopt_ctx {
   pdeopt::GpeAdjoint* gpe_adjoint = nullptr;
   // rotating-frame GPE (pdeopt_set_gpe_rotation): coordinates of cell (0, 0); Omega itself lives in EnvParams
   bool rot_set = false;
-  bool rot_any_rate = false;  // some environment's gpe_omega_rate is not 0: the step runs gpe_rot_stir.hip
+  bool rot_any_rate = false;  // some environment's gpe_omega_rate is not 0: the step runs the stirred kernels of gpe_rot.hip
   double rot_x_first = 0.0, rot_y_first = 0.0;
   pdeopt::GpeRot* gpe_rot = nullptr;
   pdeopt::GpeObs* gpe_obs = nullptr;
   pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
-  pdeopt::GpeRotStirAdjoint* gpe_rot_stir_adjoint = nullptr;
+  pdeopt::GpeRotAdjoint* gpe_rot_stir_adjoint = nullptr;  // the stirred entry point's own (other partial blocks)
   pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; lives and dies with the field buffers
   // pdeopt_fieldmu_adjoint_step_coef: fp64 partial sums of the mobility's coefficient gradient, one slot per
   // (trajectory, tile, coefficient); lives with the field buffers, zeroed by pdeopt_configure
@@ -453,7 +452,7 @@ void gpe_rot_destroy(pdeopt_ctx* ctx);
 // gpe_rot_adjoint.hip: the adjoint of that step; its buffers live and die with the spectral state too
 void gpe_rot_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_adjoint_destroy(pdeopt_ctx* ctx);
-// gpe_rot_stir_adjoint.hip: the adjoint of the stirred, ramped step (spots and Omega(t)); buffers as above
+// gpe_rot_adjoint.hip too: the adjoint of the stirred, ramped step (spots and Omega(t)); buffers as above
 void gpe_rot_stir_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_stir_adjoint_destroy(pdeopt_ctx* ctx);
 // gpe_obs.hip: energy terms, angular momentum and moments of the resident GPE state, [env_count][PDEOPT_GPE_OBS_COUNT]

@@ -1,5 +1,5 @@
-// The gather-form reductions shared by the two adjoints of the rotating-frame split step (gpe_rot_adjoint.hip,
-// gpe_rot_stir_adjoint.hip): a fixed partition of kRadjBlocks workgroups per environment, every workgroup leaves one
+// The gather-form reductions shared by the frozen and the stirred adjoint of the rotating-frame split step
+// (gpe_rot_adjoint.hip): a fixed partition of kRadjBlocks workgroups per environment, every workgroup leaves one
 // fp64 partial per sum, and whoever needs a total adds the partials in one fixed order.  No atomics: a repeat gives the
 // same bits.
 #pragma once

@@ -1,5 +1,5 @@
 // The line operator of the rotating-frame split step, shared by the step (gpe_rot.hip) and its adjoint
-// (gpe_rot_adjoint.hip, gpe_rot_stir_adjoint.hip): the multiplier of a line is a 1-D kinetic table per axis,
+// (gpe_rot_adjoint.hip), frozen and stirred: the multiplier of a line is a 1-D kinetic table per axis,
 // exp(tau/2 0.5j (2 pi i k)^2) / N, times the rotation factor exp(-/+ Omega coord (2 pi i k) tau/2), evaluated
 // in-kernel from Omega (EnvParams: one per environment), the line's coordinate and k: no N^2 table.
 #pragma once
@@ -32,8 +32,8 @@ __device__ __forceinline__ Cx<T> rot_mult(Cx<T> kin, T a, int f, int n, T sr, T 
   return cmul(kin, Cx<T>{mag * cs, mag * sn});
 }
 
-// Omega(t) of an environment: one fused multiply-add everywhere (the stirred step, gpe_rot_stir.hip, and its adjoint,
-// gpe_rot_stir_adjoint.hip), so every kernel forms the same number
+// Omega(t) of an environment: one fused multiply-add everywhere (the rstir_ kernels of the step and the rsadj_ kernels
+// of its adjoint), so every kernel forms the same number
 __device__ __forceinline__ float rot_omega_at(const EnvParams<float>& e, float t) {
   return __builtin_fmaf(e.gpe_omega_rate, t, e.gpe_omega);
 }

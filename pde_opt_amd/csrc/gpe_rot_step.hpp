@@ -1,6 +1,5 @@
-// What the two translation units of the rotating-frame split step share (gpe_rot.hip: constant Omega and a frozen
-// potential; gpe_rot_stir.hip: light spots and Omega(t)): the step's buffers, the geometry of its passes and the one
-// kernel both run unchanged.  The line operator itself is gpe_rot_line.hpp.
+// What the frozen and the stirred kernels of the rotating-frame split step (gpe_rot.hip) share: the step's buffers, the
+// geometry of its passes and the one kernel both variants run.  The line operator itself is gpe_rot_line.hpp.
 #pragma once
 
 #include <cmath>
@@ -24,11 +23,6 @@ struct GpeRot {
   double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
   bool valid = false;
 };
-
-// gpe_rot.hip: the buffers and tables of a step of dt on the configured grid; *fused: the hand-written passes cover it
-int gpe_rot_prepare(pdeopt_ctx* ctx, double dt, bool* fused);
-// gpe_rot_stir.hip: n steps from local time t0 with the light spots and the rotation ramp of every environment
-int advance_strang_rot_stir(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
 
 // fp64 and 16-point threads: one factor's sincos at a time (interleaved, their temporaries cost more registers than
 // the line itself)

@@ -21,7 +21,7 @@ over the start state.  ``RotControlSolver`` drives it with the same sweep (``Gpe
 split, chunked recomputation, chunk cap); ``PDEModel.rotation_gradient`` / ``optimize_rotation`` are its public entries.
 
 With ``lights`` (Gaussian spots evaluated in-kernel) or ``omega_rate`` the backward substep is
-``pdeopt_gpe_rot_stir_adjoint_step`` (csrc/gpe_rot_stir_adjoint.hip): it adds the gradient over the rate and over the
+``pdeopt_gpe_rot_stir_adjoint_step`` (csrc/gpe_rot_adjoint.hip): it adds the gradient over the rate and over the
 seven numbers of every spot.  ``RotStirControlSolver`` drives it, the sweep carrying the spots' block as a second device
 block; ``PDEModel.stirring_gradient`` / ``optimize_stirring`` are its public entries.
 """
@@ -337,7 +337,7 @@ def reject_time_dependent_lights(equation, t0, t1):
 
 class RotStirControlSolver(RotControlSolver):
     """The backward sweeps of the stirred, ramped rotating-frame GPE (``pdeopt_gpe_rot_stir_adjoint_step``,
-    csrc/gpe_rot_stir_adjoint.hip): ``GpeControlSolver._sweep`` with a second device block for the spots."""
+    csrc/gpe_rot_adjoint.hip): ``GpeControlSolver._sweep`` with a second device block for the spots."""
 
     def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
         """``(grad (B, 4), spot_grad (B, S, 7) or None, lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys``

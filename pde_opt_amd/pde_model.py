@@ -25,7 +25,7 @@ reverse-mode gradient of such an objective over the spots' numbers (a discrete a
 ``omega`` and the start state (a discrete adjoint of the alternating-direction split step, csrc/gpe_rot_adjoint.hip) and
 ``optimize_rotation`` drives BFGS with it; ``control_gradient``, ``optimize`` and ``train`` refuse that pair.
 With ``lights`` or ``omega_rate`` (a stirred or ramped problem) ``stirring_gradient`` adds the gradient over ``omega_rate``
-and the spots' numbers (csrc/gpe_rot_stir_adjoint.hip) and ``optimize_stirring`` drives BFGS with it.
+and the spots' numbers (csrc/gpe_rot_adjoint.hip) and ``optimize_stirring`` drives BFGS with it.
 """
 
 from __future__ import annotations
@@ -601,7 +601,7 @@ class PDEModel:
         of every spot in user units.  A callable ``lights`` that does not depend on time is folded into the potential as
         the forward solve does and gets no entry; one that does is refused.  ``lam0 = dJ/dy0`` in the shape of ``y0``: it
         chains segments as in ``rotation_gradient``.  The objective takes the forms of ``optimize``; ``ys`` is the array
-        ``solve`` returns, bit for bit.  A discrete adjoint of the solve on the GPU (csrc/gpe_rot_stir_adjoint.hip),
+        ``solve`` returns, bit for bit.  A discrete adjoint of the solve on the GPU (csrc/gpe_rot_adjoint.hip),
         constant steps only."""
         from . import gpe_control
         from .numerics.functions.lights import GaussianSpots

@@ -1,4 +1,4 @@
-"""Reference for the adjoint of the stirred, ramped rotating-frame split step (csrc/gpe_rot_stir_adjoint.hip):
+"""Reference for the adjoint of the stirred, ramped rotating-frame split step (csrc/gpe_rot_adjoint.hip):
 ``gpe_rot_adjoint_ref.py``'s torch step on the CPU with light spots in the potential and Omega(t0) = omega + rate t0 in
 the line operators, at complex128 or complex64, differentiated by torch.autograd.  A helper, not a test.
 

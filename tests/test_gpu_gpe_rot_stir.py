@@ -1,4 +1,4 @@
-"""The stirred, ramped rotating-frame split step on the MI355X (csrc/gpe_rot_stir.hip) against
+"""The stirred, ramped rotating-frame split step on the MI355X (csrc/gpe_rot.hip) against
 its numpy reference (tests/gpe_rot_stir_ref.py): every transform path and the JOIN split, the library path, the bitwise
 properties, environment groups, spots only / ramp only / neither, save points, PDEEnv, VectorPDEEnv and the
 observables at Omega(t)."""

@@ -1,4 +1,4 @@
-"""The adjoint of the stirred, ramped rotating-frame split step on the MI355X (csrc/gpe_rot_stir_adjoint.hip,
+"""The adjoint of the stirred, ramped rotating-frame split step on the MI355X (csrc/gpe_rot_adjoint.hip,
 gpe_control.RotStirControlSolver, PDEModel.stirring_gradient / optimize_stirring) against the
 torch autograd reference on the CPU (tests/gpe_rot_stir_adjoint_ref.py): one backward substep with per-environment k, e,
 omega, rate and spots, the gradient of a whole solve with chunked recomputation, its bitwise properties, the frozen case

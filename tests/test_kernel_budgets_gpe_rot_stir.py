@@ -1,4 +1,4 @@
-"""The kernels of the stirred, ramped rotating-frame split step (csrc/gpe_rot_stir.hip) use no scratch, from the
+"""The kernels of the stirred, ramped rotating-frame split step (csrc/gpe_rot.hip) use no scratch, from the
 compiler's own report (the one tests/test_kernel_budgets.py reads).  No GPU needed: hipcc cross-compiles for gfx950."""
 import pytest
 
@@ -18,7 +18,7 @@ def kernels():
     for d in ("float", "double"):
         out += [f"rstir_row_kernel<{d}, {n}>" for n in SIZES]
         for n in SIZES:
-            # FIRST, LAST, JOIN; fp64 at 1024 runs JOIN as LAST + FIRST (rstir_join_fits)
+            # FIRST, LAST, JOIN; fp64 at 1024 runs JOIN as LAST + FIRST (rot_join_fits)
             forms = ["false, true", "true, false"] + ([] if (d, n) == ("double", 1024) else ["true, true"])
             out += [f"rstir_col_kernel<{d}, {n}, {cols(d, n)}, {f}>" for f in forms]
         out += [f"rstir_mul_kernel<{d}, 0, false>", f"rstir_mul_kernel<{d}, 0, true>", f"rstir_mul_kernel<{d}, 1, false>",

@@ -1,4 +1,4 @@
-"""The kernels of the stirred rotating-frame split step's adjoint (csrc/gpe_rot_stir_adjoint.hip) use no scratch and no
+"""The kernels of the stirred rotating-frame split step's adjoint (csrc/gpe_rot_adjoint.hip) use no scratch and no
 AGPRs, from the compiler's own report (the one tests/test_kernel_budgets.py reads).  No GPU needed: hipcc cross-compiles
 for gfx950."""
 import pytest

@@ -10,7 +10,7 @@ The forward step is timed twice: as the solver runs it (n steps per call: 2 fuse
 as the recomputation of a gradient runs it.  The backward substep is 15 batched 1-D rocFFT transforms + 1 copy + 11
 passes over the field (27 launches).  Needs an MI355X.
 
-``--stir`` times the stirred backward substep instead (pdeopt_gpe_rot_stir_adjoint_step, csrc/gpe_rot_stir_adjoint.hip:
+``--stir`` times the stirred backward substep instead (pdeopt_gpe_rot_stir_adjoint_step, csrc/gpe_rot_adjoint.hip:
 two moving spots and a ramp of Omega, device blocks) next to the plain backward substep of the frozen problem, in the
 same run and binary, plain - stirred - plain, so a drift of the clock shows.
 

@@ -4,7 +4,7 @@ environments fp32 and 256^2 x 1.  HIP events around STEPS steps, WARMUP + ROUNDS
 
     python tools/gpe_rot_bench.py [--out profiles/gpe_rot.json]
 
-``--stir``: the stirred, ramped step (two moving ``GaussianSpots`` plus an ``omega_rate``, csrc/gpe_rot_stir.hip) next
+``--stir``: the stirred, ramped step (two moving ``GaussianSpots`` plus an ``omega_rate``, csrc/gpe_rot.hip) next
 to the plain rotating step instead, same shapes, same run:
 
     python tools/gpe_rot_bench.py --stir [--out profiles/gpe_rot_stir.json]
