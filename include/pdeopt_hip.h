@@ -202,7 +202,8 @@ typedef enum {
                                   side by side on two HIP streams, each half the size, so that one group's launch
                                   fills the other's ramp and tail), 1 = one group at a time, 2 = force two */
   PDEOPT_OPT_DEBUG_ABLATE = 3 /* TIMING ONLY, results are wrong: bit0 skip the mu phase, bit1 skip
-                                 the flux phase of the tiled kernel (where does the time go?) */
+                                 the flux phase of the tiled kernel (where does the time go?); 0x10000
+                                 pdeopt_structure_factor skips its binning: the transform, copy and synchronise alone */
 } pdeopt_option;
 
 /* ---- life cycle ------------------------------------------------------------------------- */
@@ -419,6 +420,24 @@ enum {
   PDEOPT_PF_OBS_COUNT = 8
 };
 int pdeopt_pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
+/* Shell sums of the power spectrum of the resident real scalar state (the structure factor S(k) before its
+ * normalisation), per environment, computed on the device.  With u^ = rfftn(u), unnormalised, the last axis halved
+ * (m = 0 .. n_last / 2):
+ *   q = t0[i] + t1[m] (2-D),  (t0[i] + t1[j]) + t2[m] (3-D): fp64 additions in that order
+ *   b = (int)floor(sqrt(q) + 0.5), the root correctly rounded
+ *   P_b = sum over the modes of shell b of w |u^|^2;  w = 1 for m = 0 and, n_last even, m = n_last / 2, else 2;
+ *         0 for the zero mode (the mean drops out)
+ * pdeopt_sk_configure hands over the axis tables -- t_a[i] = (2 pi fftfreq(n_a, h_a)[i] / dk)^2 for shells of width dk,
+ * n_a entries each, finite and >= 0, the last axis' not decreasing over its half range; t2 is NULL in 2-D -- and
+ * n_bins = 1 + floor(sqrt(sum_a max t_a) + 0.5), at most 4096.  They hold until pdeopt_configure changes the grid.
+ * pdeopt_structure_factor transforms the state into the hermitian work field of the IMEX step (scratch between steps:
+ * the next step is unchanged) and writes host_out[env_count][n_bins].  The state is not modified; sums in fp64 in a
+ * fixed order, no atomics: a repeat gives identical bits, and a sub-range gives the rows of the full call.
+ * PDEOPT_ESTATE before pdeopt_configure, or pdeopt_structure_factor without tables for this grid.  PDEOPT_EINVAL with
+ * the reason: a complex (GPE) state, the padded layout, an axis of fewer than 2 points, a range outside the batch,
+ * tables that are not as above, an n_bins that is not the value the tables imply or exceeds 4096. */
+int pdeopt_sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const double* t2, int n_bins);
+int pdeopt_structure_factor(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 
 /* ---- domain decomposition of one large field (BASELINE config 5; no reference counterpart) -----
  * With PDEOPT_OPT_HALO_LAYOUT = 4 a ctx holds one rank's tile.  Per RK4 substep the caller runs

@@ -48,11 +48,12 @@ from .numerics.solvers import (
 from .pde_env import PDEEnv, VectorPDEEnv
 from .pde_model import PDEModel
 from .phase_field_observables import PhaseFieldObservables
+from .structure_factor import StructureFactor
 
 __all__ = [
     "PDEModel", "PDEEnv", "VectorPDEEnv", "HipEngine", "diffeqsolve", "Solution",
     "BaseEquation", "AllenCahn2DPeriodic", "CahnHilliard2DPeriodic", "AdvectionDiffusion2D", "GPE2DTSControl",
-    "GPE2DTSRot", "RotatingStrangSplitting", "OBSERVABLE_NAMES", "GpeObservables", "GroundState", "PhaseFieldObservables",
+    "GPE2DTSRot", "RotatingStrangSplitting", "OBSERVABLE_NAMES", "GpeObservables", "GroundState", "PhaseFieldObservables", "StructureFactor",
     "AllenCahn2DSmoothedBoundary", "CahnHilliard2DSmoothedBoundary", "CahnHilliard3DPeriodic",
     "AllenCahn2DPeriodicButlerVolmer", "AllenCahn2DPeriodicButlerVolmerConstantCurrent",
     "AllenCahn2DSmoothedBoundaryButlerVolmerConstantCurrent",

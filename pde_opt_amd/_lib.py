@@ -171,6 +171,8 @@ _SIGNATURES = {
     "pdeopt_detect_vortices": (C.c_int, [_VP, C.c_double, C.c_double, C.c_int, C.c_int, _VP, _VP]),
     "pdeopt_gpe_observables": (C.c_int, [_VP, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, _VP]),
     "pdeopt_pf_observables": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "pdeopt_sk_configure": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int]),
+    "pdeopt_structure_factor": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "pdeopt_tsit5_trial": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_double, _VP]),
     "pdeopt_tsit5_commit": (C.c_int, [_VP, C.c_int]),
     "pdeopt_tsit5_trial_env": (C.c_int, [_VP, C.c_double, _VP, C.c_double, C.c_double, C.POINTER(C.c_double), _VP]),

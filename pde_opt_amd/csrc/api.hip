@@ -82,6 +82,7 @@ void free_fields(pdeopt_ctx* ctx) {
   strang_fused_destroy(ctx);
   sens_destroy(ctx);
   bv_destroy(ctx);
+  sk_drop(ctx);  // the shell tables belong to one grid
   graph_destroy(ctx);
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
@@ -287,6 +288,7 @@ int pdeopt_ctx_destroy(pdeopt_ctx* ctx) {
   if (ctx->red_dev) (void)hipFree(ctx->red_dev);
   if (ctx->red_mean_dev) (void)hipFree(ctx->red_mean_dev);
   if (ctx->pf_obs_dev) (void)hipFree(ctx->pf_obs_dev);
+  sk_destroy(ctx);
   if (ctx->adaptive_blk) (void)hipFree(ctx->adaptive_blk);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -906,6 +908,21 @@ int pdeopt_pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double*
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return pf_observables(ctx, env_first, env_count, host_out);  // (its refusals hold for an empty range too)
+}
+
+int pdeopt_sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const double* t2, int n_bins) {
+  if (!ctx || !t0 || !t1) return PDEOPT_EINVAL;
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return sk_configure(ctx, t0, t1, t2, n_bins);
+}
+
+int pdeopt_structure_factor(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out) {
+  if (!ctx || !host_out) return PDEOPT_EINVAL;
+  int rc = check_envs(ctx, env_first, env_count);
+  if (rc) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return structure_factor(ctx, env_first, env_count, host_out);  // (its refusals hold for an empty range too)
 }
 
 int pdeopt_tsit5_trial(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol,

@@ -241,6 +241,12 @@ struct pdeopt_ctx {
   double* red_mean_dev = nullptr;
   double* pf_obs_dev = nullptr;  // pdeopt_pf_observables: the rows [envs][8], then the workgroups' partial rows; grow-only
   size_t pf_obs_cap = 0;
+  // pdeopt_structure_factor: the axis tables t_0 | t_1 (| t_2) of pdeopt_sk_configure (dropped with the field buffers;
+  // sk_bins = 0: none), and the call's work block -- the rows [envs][n_bins], then the workgroups' rows; grow-only
+  double* sk_tab_dev = nullptr;
+  int sk_bins = 0;
+  double* sk_dev = nullptr;
+  size_t sk_cap = 0;
   std::vector<void*> host_allocs;  // pdeopt_host_alloc
   pdeopt::CommState* comm = nullptr;
   pdeopt::Spectral* spectral = nullptr;
@@ -441,6 +447,10 @@ int imex_rocfft_solve_kappa(pdeopt_ctx* ctx, double dt, int B, int P, const int*
 // one unnormalised complex transform of a whole-batch field [batch][nx][ny], in place, on the ctx's stream (the C2C
 // plans of the library Strang path: any grid); host copy of a shared complex aux field
 int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf);
+// one unnormalised real-to-hermitian transform of the resident state, whole batch (the plans of the rocFFT IMEX step:
+// any 2-D / 3-D grid), into the hermitian work field, which is scratch between steps: *half is [batch][*half_cells]
+// interleaved complex in the state's dtype, the last axis halved.  The state is not modified
+int spectral_r2c_state(pdeopt_ctx* ctx, void** half, int64_t* half_cells);
 int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<double>>& out);
 // one unnormalised complex transform along ONE axis (0: x, lines of stride ny; 1: y, contiguous lines) of a
 // whole-batch field [batch][nx][ny], in place, on the ctx's stream: rocFFT batched 1-D plans, any grid
@@ -463,6 +473,12 @@ void gpe_obs_destroy(pdeopt_ctx* ctx);
 // pf_obs.hip: mass, free energy, chemical-potential moments and dissipation of the resident phase-field state (periodic
 // CH, AC, CH-3D with finite differences), [env_count][PDEOPT_PF_OBS_COUNT] doubles; refuses what it does not cover
 int pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
+// structure_factor.hip: the shell sums P_b of the resident real state's power spectrum, [env_count][n_bins] doubles, from
+// the axis tables of sk_configure; sk_drop forgets the tables (a new grid), sk_destroy frees the work block too
+int sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const double* t2, int n_bins);
+int structure_factor(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
+void sk_drop(pdeopt_ctx* ctx);
+void sk_destroy(pdeopt_ctx* ctx);
 // gpe_adjoint.hip: its buffers live and die with the spectral state (spectral_destroy / spectral_invalidate)
 void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_adjoint_destroy(pdeopt_ctx* ctx);

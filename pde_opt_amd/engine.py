@@ -61,6 +61,7 @@ class HipEngine:
         self._callback_error = None
         self._cnns: list = []  # open NativeCNN and NativeMixer handles: closed before the ctx they belong to
         self.gpe_origin: Optional[tuple] = None  # coordinates of cell (0, 0) of a GPE problem (gpe_observables)
+        self._n_bins = 0  # shells of the tables the library holds (sk_configure)
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -619,6 +620,32 @@ class HipEngine:
         n = self.batch - env_first if env_count is None else env_count
         out = np.zeros((n, L.PF_OBS_COUNT), dtype=np.float64)
         self._check(self._lib.pdeopt_pf_observables(self._h, int(env_first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sk_configure(self, tables, n_bins: int, key=None):
+        """The axis tables of ``structure_factor`` (``structure_factor.shell_tables``): one float64 array per axis and the
+        number of shells.  They hold until a ``configure`` changes the grid; tables this engine already holds under the
+        same ``key`` are not transferred again."""
+        if key is not None and self._aux_keys.get("sk") == key:
+            return
+        self._aux_keys.pop("sk", None)
+        tabs = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        want = tuple(s for s in self.state_shape)
+        if len(tabs) != len(want) or any(t.shape != (n,) for t, n in zip(tabs, want)):
+            raise ValueError(f"structure-factor tables of lengths {[t.shape for t in tabs]} for a state of shape {want}")
+        ptrs = [t.ctypes.data_as(C.c_void_p) for t in tabs] + [None] * (3 - len(tabs))
+        self._check(self._lib.pdeopt_sk_configure(self._h, *ptrs, int(n_bins)))
+        self._n_bins = int(n_bins)
+        if key is not None:
+            self._aux_keys["sk"] = key
+
+    def structure_factor(self, env_first: int = 0, env_count: Optional[int] = None) -> np.ndarray:
+        """Shell sums ``P_b`` of the power spectrum of the resident real state (``pdeopt_structure_factor``), binned on
+        the device: ``(envs, n_bins)`` float64, ``n_bins * 8`` bytes per environment instead of the field;
+        ``structure_factor.StructureFactor.from_power`` normalises them.  Needs ``sk_configure``."""
+        n = self.batch - env_first if env_count is None else env_count
+        out = np.zeros((n, max(self._n_bins, 1)), dtype=np.float64)
+        self._check(self._lib.pdeopt_structure_factor(self._h, int(env_first), int(n), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def tsit5_trial(self, t: float, dt: float, rtol: float, atol: float) -> np.ndarray:

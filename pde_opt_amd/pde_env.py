@@ -291,6 +291,15 @@ class _EnvShard:
             from .phase_field_observables import PhaseFieldObservables, volume_of
 
             rewards = PhaseFieldObservables.from_raw(eng.pf_observables(), volume_of(env.domain))[env.device_reward[1]]
+        elif isinstance(env.device_reward, tuple) and env.device_reward[0] == "structure_factor":
+            # ("structure_factor", name): the coarsening length, a moment of S(k) or the variance of the state after the
+            # step, transformed and binned on the device (n_bins * 8 bytes per environment come back); the shell tables
+            # travel once per shard engine
+            from . import structure_factor as skm
+
+            tabs = skm.shell_tables(env.domain)
+            skm.upload_tables(eng, tabs)
+            rewards = skm.from_engine(eng, tabs)[env.device_reward[1]]
         elif isinstance(env.device_reward, tuple):
             # ("vortices", amp_thresh, tol): rl_utils.detect_vortices' num_vortices per environment, counted on the
             # device (pde_opt/rl_utils.py:19-84): 24 bytes per environment cross PCIe instead of the wavefunction
@@ -354,7 +363,9 @@ class VectorPDEEnv:
     vortices of a GPE state, ``rl_utils.detect_vortices`` on the device, or ``("gpe", name)`` = an observable of a GPE
     state, ``name`` in ``gpe_observables.OBSERVABLE_NAMES + ("energy", "mu")``, or ``("phase_field", name)`` = a
     free-energy observable of a periodic Cahn-Hilliard / Allen-Cahn state, ``name`` in
-    ``phase_field_observables.REWARD_NAMES``, e.g. ``"free_energy"``), which avoids the D2H of full fields;
+    ``phase_field_observables.REWARD_NAMES``, e.g. ``"free_energy"``, or ``("structure_factor", name)`` = the coarsening
+    length or a moment of S(k) of such a state, ``name`` in ``structure_factor.REWARD_NAMES``), which avoids the D2H of
+    full fields;
     ``device_observation=(lo, hi)`` forms the uint8 image observations of the declared
     observation space on the GPU (1 byte per cell crosses PCIe instead of 4 or 8);
     ``device_observation=("probes", cells)`` returns the state at the listed grid cells instead (sensor-style
@@ -411,6 +422,12 @@ class VectorPDEEnv:
             if len(device_reward) != 2 or device_reward[1] not in pfo.REWARD_NAMES:
                 raise ValueError(f"unknown device reward {device_reward!r} (\"phase_field\" takes one of {pfo.REWARD_NAMES})")
             pfo.reject_unsupported(equation_type)
+        elif isinstance(device_reward, tuple) and device_reward[0] == "structure_factor":
+            from . import structure_factor as skm
+
+            if len(device_reward) != 2 or device_reward[1] not in skm.REWARD_NAMES:
+                raise ValueError(f"unknown device reward {device_reward!r} (\"structure_factor\" takes one of {skm.REWARD_NAMES})")
+            skm.reject_unsupported(equation_type)
         elif isinstance(device_reward, tuple) and device_reward[0] != "vortices":
             raise ValueError(f"unknown device reward {device_reward[0]!r}")
         if isinstance(device_reward, str) and device_reward not in self._RED:

@@ -128,6 +128,27 @@ class PDEModel:
 
         return phase_field_observables.free_energy_trace(self, parameters, y0, ts, solver_parameters, dt0)
 
+    # -- structure factor of the phase-field classes (pde_opt_amd.structure_factor) ------------------------------------------
+    def structure_factor(self, state):
+        """The shell-averaged structure factor ``S(k)`` of a real periodic field (``StructureFactor``: ``k``, ``counts``,
+        ``power``, ``s`` and the scalars ``variance``, ``k1``, ``k2``, ``length = 2 pi / k1``, leading shape ``(B,)``),
+        transformed and binned on the GPU: ``n_bins * 8`` bytes per environment come back instead of the field.  ``state``
+        is one field or a batch; there are no parameters, S(k) depends on the state and the domain only.
+        ``CahnHilliard2DPeriodic``, ``AllenCahn2DPeriodic`` and ``CahnHilliard3DPeriodic``; everything else raises
+        ``NotImplementedError``."""
+        from . import structure_factor
+
+        return structure_factor.structure_factor(self, state)
+
+    def structure_factor_trace(self, parameters, y0, ts, solver_parameters=None, dt0=0.000001):
+        """The same along a solve, leading shape ``(len(ts), B)``: the constant-step solve of ``solve`` (Euler, RK4 or
+        SemiImplicitFourierSpectral) with ``n_bins * 8`` bytes per environment read back at each save point instead of the
+        field -- ``length`` over ``ts`` is the coarsening curve.  Every ``ts`` must lie on a step edge (``ts[0] + k dt0``,
+        or ``ts[-1]``), as for ``free_energy_trace``."""
+        from . import structure_factor
+
+        return structure_factor.structure_factor_trace(self, parameters, y0, ts, solver_parameters, dt0)
+
     # -- fitting (pde_model.py:138-460) ----------------------------------------------------------------------------
     def regularization(self, parameters, weights, lambda_reg):
         """``lambda sum_i w_i p_i^2`` over the coefficient arrays named in ``weights``; None leaves are ignored"""
