@@ -847,12 +847,61 @@ class LocalGroup:
             self._h = None
 
 
-class NativeCNN:
-    """Handle of a periodic CNN inside the library (csrc/cnn.hip), bound to one ``HipEngine``.  Field arguments are
-    device pointers of ``(batch, nx, ny)`` fields in the engine's dtype; everything is ordered on the engine's stream
-    and only ``grad_read`` waits for it.  ``created`` counts the handles ever made (tests of the opt-in switch)."""
+class _NativeNet:
+    """What the handles of a network inside the library share: bound to one ``HipEngine``, the C functions
+    ``pdeopt_<prefix>_*`` behind them.  Field arguments are device pointers of ``(batch, nx, ny)`` fields in the engine's
+    dtype; everything is ordered on the engine's stream and only ``grad_read`` waits for it.  A subclass creates the
+    handle, sets ``n_params`` and calls ``_opened``; its ``created`` counts the handles ever made (tests of the opt-in
+    switch)."""
 
-    created = 0
+    prefix = ""
+
+    def _opened(self, engine: "HipEngine", handle):
+        self._h = handle
+        self.pending = False  # the gradient buffer holds sums that have not been read and reset
+        engine._cnns.append(self)
+        type(self).created += 1
+
+    def _call(self, name: str, *args):
+        self.engine._check(getattr(self.engine._lib, f"pdeopt_{self.prefix}_{name}")(self._h, *args))
+
+    def set_params(self, flat):
+        """the parameters as one flat fp64 vector in torch's order (``fieldmu.flatten_params``)"""
+        p = np.ascontiguousarray(flat, dtype=np.float64)
+        self._call("set_params", p.ctypes.data_as(C.c_void_p), p.size)
+
+    def forward(self, u_ptr: int, mu_ptr: int):
+        self._call("forward", C.c_void_p(u_ptr), C.c_void_p(mu_ptr))
+
+    def vjp(self, u_ptr: int, gmu_ptr: int, lam_ptr: int):
+        """``lam += N'(u)^T gmu``; the parameter gradient accumulates on the device until ``grad_read``"""
+        self.pending = True
+        self._call("vjp", C.c_void_p(u_ptr), C.c_void_p(gmu_ptr), C.c_void_p(lam_ptr))
+
+    def grad_read(self, reset: bool = True) -> np.ndarray:
+        out = np.empty(self.n_params, dtype=np.float64)
+        self._call("grad_read", out.ctypes.data_as(C.c_void_p), out.size, int(bool(reset)))
+        if reset:
+            self.pending = False
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self.engine._lib, f"pdeopt_{self.prefix}_destroy")(self._h)
+            self._h = None
+            self.engine._cnns.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeCNN(_NativeNet):
+    """Handle of a periodic CNN inside the library (csrc/cnn.hip)."""
+
+    prefix, created = "cnn", 0
 
     def __init__(self, engine: "HipEngine", channels, activation: int):
         self.engine = engine
@@ -862,46 +911,13 @@ class NativeCNN:
         ch = (C.c_int * len(self.channels))(*self.channels)
         h = C.c_void_p()
         engine._check(engine._lib.pdeopt_cnn_create(engine._h, len(self.channels) - 1, ch, self.activation, C.byref(h)))
-        self._h = h
-        engine._cnns.append(self)
-        NativeCNN.created += 1
-
-    def set_params(self, flat):
-        """the parameters as one flat fp64 vector in torch's order (``fieldmu.flatten_params``)"""
-        p = np.ascontiguousarray(flat, dtype=np.float64)
-        self.engine._check(self.engine._lib.pdeopt_cnn_set_params(self._h, p.ctypes.data_as(C.c_void_p), p.size))
-
-    def forward(self, u_ptr: int, mu_ptr: int):
-        self.engine._check(self.engine._lib.pdeopt_cnn_forward(self._h, C.c_void_p(u_ptr), C.c_void_p(mu_ptr)))
-
-    def vjp(self, u_ptr: int, gmu_ptr: int, lam_ptr: int):
-        """``lam += N'(u)^T gmu``; the parameter gradient accumulates on the device until ``grad_read``"""
-        self.engine._check(self.engine._lib.pdeopt_cnn_vjp(self._h, C.c_void_p(u_ptr), C.c_void_p(gmu_ptr), C.c_void_p(lam_ptr)))
-
-    def grad_read(self, reset: bool = True) -> np.ndarray:
-        out = np.empty(self.n_params, dtype=np.float64)
-        self.engine._check(self.engine._lib.pdeopt_cnn_grad_read(self._h, out.ctypes.data_as(C.c_void_p), out.size, int(bool(reset))))
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.engine._lib.pdeopt_cnn_destroy(self._h)
-            self._h = None
-            self.engine._cnns.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._opened(engine, h)
 
 
-class NativeMixer:
-    """Handle of an MLP-mixer inside the library (csrc/mixer.hip), bound to one ``HipEngine`` and to the grid it is
-    configured with.  Field arguments are device pointers of ``(batch, nx, ny)`` fields in the engine's dtype; everything
-    is ordered on the engine's stream and only ``grad_read`` waits for it.  ``created`` counts the handles ever made."""
+class NativeMixer(_NativeNet):
+    """Handle of an MLP-mixer inside the library (csrc/mixer.hip), bound also to the grid its engine is configured with."""
 
-    created = 0
+    prefix, created = "mixer", 0
 
     def __init__(self, engine: "HipEngine", patch: int, hidden: int, mix_patch: int, mix_hidden: int, blocks: int, activation: int):
         self.engine = engine
@@ -909,42 +925,11 @@ class NativeMixer:
         self.activation = int(activation)
         h = C.c_void_p()
         engine._check(engine._lib.pdeopt_mixer_create(engine._h, *self.sizes, self.activation, C.byref(h)))
-        self._h = h
         self.grid = (int(engine.problem.nx), int(engine.problem.ny))
         p, c, mp, mh, k = self.sizes
         P = (self.grid[0] // p) * (self.grid[1] // p)
         self.n_params = 2 * c * p * p + c + 1 + k * (2 * mp * P + mp + P + 2 * mh * c + mh + c + 4 * c * P) + 2 * c * P
-        engine._cnns.append(self)
-        NativeMixer.created += 1
-
-    def set_params(self, flat):
-        """the parameters as one flat fp64 vector in torch's order (``fieldmu.flatten_params``)"""
-        p = np.ascontiguousarray(flat, dtype=np.float64)
-        self.engine._check(self.engine._lib.pdeopt_mixer_set_params(self._h, p.ctypes.data_as(C.c_void_p), p.size))
-
-    def forward(self, u_ptr: int, mu_ptr: int):
-        self.engine._check(self.engine._lib.pdeopt_mixer_forward(self._h, C.c_void_p(u_ptr), C.c_void_p(mu_ptr)))
-
-    def vjp(self, u_ptr: int, gmu_ptr: int, lam_ptr: int):
-        """``lam += N'(u)^T gmu``; the parameter gradient accumulates on the device until ``grad_read``"""
-        self.engine._check(self.engine._lib.pdeopt_mixer_vjp(self._h, C.c_void_p(u_ptr), C.c_void_p(gmu_ptr), C.c_void_p(lam_ptr)))
-
-    def grad_read(self, reset: bool = True) -> np.ndarray:
-        out = np.empty(self.n_params, dtype=np.float64)
-        self.engine._check(self.engine._lib.pdeopt_mixer_grad_read(self._h, out.ctypes.data_as(C.c_void_p), out.size, int(bool(reset))))
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.engine._lib.pdeopt_mixer_destroy(self._h)
-            self._h = None
-            self.engine._cnns.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._opened(engine, h)
 
 
 _default_engines: dict = {}

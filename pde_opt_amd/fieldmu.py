@@ -13,9 +13,11 @@ the substep loop; the caller's own stream is ordered against it on entry and exi
 
 Substep and save-point schedule: ``fit.walk_save_points``, the one of ``integrate.diffeqsolve`` and of the forward-mode
 sensitivities (constant steps, a clipped last step, save points inside a step interpolated linearly).  The backward
-sweep needs the state at the start of every substep: the forward pass keeps one state per chunk of substeps, and each
-chunk is run again and held before its sweep.  A chunk holds at most ``PDEOPT_FIELDMU_CHUNK_BYTES`` (default 1 GiB;
-``FieldMuSolver.chunk_bytes`` overrides it), so a long solve costs one extra forward pass instead of unbounded memory.
+sweep needs the state at the start of every substep: the schedule, the split of a save point's cotangent, the chunked
+recomputation and the stream rule are those of ``pde_opt_amd.reverse``, which the GPE's gradients share.  The residuals
+and with them the cotangents come from the states of the forward pass, so that pass runs to the last substep and visits
+every state; ``dJ/dy0`` has no use here and is not formed.  A chunk holds at most ``PDEOPT_FIELDMU_CHUNK_BYTES``
+(default 1 GiB; ``FieldMuSolver.chunk_bytes`` overrides it).
 
 Covered: ``CahnHilliard2DPeriodic`` with ``derivs="fd"``, ``SemiImplicitFourierSpectral`` or ``Euler`` with
 ``ConstantStepSize``, fp32 and fp64, ``D`` a closure of the in-kernel family, ``kappa`` fixed.
@@ -46,18 +48,17 @@ torch is imported when a solver is built, not with the package.
 
 from __future__ import annotations
 
-import contextlib
 import os
 
 import numpy as np
 
 from . import _lib as L
-from .fit import walk_save_points
 from .numerics.closures import is_torch_module as is_module  # noqa: F401  (the detection, for callers of this module)
 from .numerics.equations.phase_field import FIELD_MU_SUPPORT
+from .reverse import StreamSolver, add_save_cotangent, backward_pass, chunk_length, forward_pass, schedule
+from .reverse import split_save_cotangent  # noqa: F401  (with schedule and chunk_length: callers and tests import them from here)
 
 CHUNK_BYTES_ENV = "PDEOPT_FIELDMU_CHUNK_BYTES"
-DEFAULT_CHUNK_BYTES = 1 << 30
 NATIVE_CNN_ENV = "PDEOPT_FIELDMU_NATIVE_CNN"
 NATIVE_MIXER_ENV = "PDEOPT_FIELDMU_NATIVE_MIXER"
 
@@ -114,33 +115,6 @@ def weight_vector(module, w) -> np.ndarray:
     return np.broadcast_to(w, (n,)).copy()
 
 
-# ---- schedule ---------------------------------------------------------------------------------------------------------
-
-
-def schedule(ts, dt0):
-    """``(steps, saves)``: the step sizes of the substeps in order, and per save point ``(i, theta)``: the save is the
-    state after ``i`` substeps (``theta`` None), or ``y[i - 1] + theta (y[i] - y[i - 1])`` inside substep ``i``"""
-    ts = np.asarray(ts, dtype=np.float64)
-    steps, saves = [], []
-    walk_save_points(float(ts[0]), float(ts[-1]), float(dt0), ts,
-                     lambda dt, n, t: steps.extend([float(dt)] * int(n)), lambda: None,
-                     lambda q, theta: saves.append((len(steps), theta)))
-    return steps, saves
-
-
-def split_save_cotangent(g, theta):
-    """cotangents ``(of y[i - 1], of y[i])`` of a save ``(1 - theta) y[i - 1] + theta y[i]`` with cotangent ``g``; a save on
-    a step edge (``theta`` None) belongs to ``y[i]`` alone"""
-    if theta is None:
-        return None, g
-    return (1.0 - theta) * g, theta * g
-
-
-def chunk_length(n_steps: int, state_bytes: int, cap_bytes: int) -> int:
-    """substeps per chunk: as many start states as ``cap_bytes`` holds, at least one"""
-    return max(1, min(max(1, n_steps), int(cap_bytes) // max(1, int(state_bytes))))
-
-
 # ---- the solver ---------------------------------------------------------------------------------------------------------
 
 
@@ -159,64 +133,26 @@ def _reject(equation, solver, controller=None):
         raise NotImplementedError("the adjoint of the IMEX step reuses its operator, which needs a real fourier_symbol")
 
 
-class FieldMuSolver:
-    """One engine for solves whose ``mu`` is a ``torch.nn.Module``, on one torch stream.
-
-    Stream rule.  The engine is bound to ``self.stream`` for its lifetime: torch's current stream at construction, or a
-    stream of the solver's own when that is the legacy default stream (it has no handle the library could borrow).  All
-    of the solver's torch work and every library launch of a call run on ``self.stream``, so nothing synchronises inside
-    the substep loop.  Every call reads the caller's current stream anew: on entry ``self.stream`` waits for it (what
-    the caller has enqueued -- an optimiser step on the parameters, a module it has just modified -- is finished before
-    the solver reads it), on exit it waits for ``self.stream`` (the ``.grad`` the solver wrote is ready for what the
-    caller enqueues next).  Both are device-side waits (``Stream.wait_stream``), not host synchronisation."""
+class FieldMuSolver(StreamSolver):
+    """One engine for solves whose ``mu`` is a ``torch.nn.Module``, on one torch stream (the stream rule of
+    ``reverse.StreamSolver``: the ``.grad`` a call wrote is ready for what the caller enqueues next)."""
 
     def __init__(self, device: int = 0):
-        import torch
-
-        from .engine import HipEngine
-
-        self.torch = torch
-        self.device = torch.device("cuda", int(device))
-        cur = torch.cuda.current_stream(self.device)
-        self.stream = cur if cur.cuda_stream else torch.cuda.Stream(self.device)
-        self.engine = HipEngine(int(device), stream=self.stream.cuda_stream)
-        self.chunk_bytes = None  # None: PDEOPT_FIELDMU_CHUNK_BYTES, else 1 GiB
-        self.last_chunks = 0     # chunks of the last backward sweep
+        super().__init__(device, CHUNK_BYTES_ENV)
         # evaluate and differentiate a PeriodicCNN mu in the library (csrc/cnn.hip) instead of in torch
         self.native_cnn = os.environ.get(NATIVE_CNN_ENV, "0") not in ("", "0")
-        self._cnn = None         # the library's handle of the last native network
-        self._cnn_pending = False  # its gradient buffer holds sums of a sweep that did not finish
+        self._cnn = None  # the library's handle of the last native network
         # the same for a Mixer2d mu (csrc/mixer.hip)
         self.native_mixer = os.environ.get(NATIVE_MIXER_ENV, "0") not in ("", "0")
         self._mixer = None
-        self._mixer_pending = False
         self._coef_pending = False  # the engine's coefficient-gradient slots hold sums of a sweep that did not finish
-
-    @contextlib.contextmanager
-    def _ordered(self):
-        """run the body on ``self.stream``, ordered after and before the caller's current stream (the stream rule)"""
-        torch = self.torch
-        caller = torch.cuda.current_stream(self.device)
-        if caller != self.stream:
-            self.stream.wait_stream(caller)
-        try:
-            with torch.cuda.stream(self.stream):
-                yield
-        finally:
-            if caller != self.stream:
-                caller.wait_stream(self.stream)
-
-    def _cap(self) -> int:
-        if self.chunk_bytes is not None:
-            return int(self.chunk_bytes)
-        return int(os.environ.get(CHUNK_BYTES_ENV, DEFAULT_CHUNK_BYTES))
 
     # -- set-up ---------------------------------------------------------------------------------------------------------
     def _prepare(self, equation, solver, y0s, t0, t1):
         """configure the engine, upload the state; returns ``(Y, mu_of)``: the state as a tensor ``(B, nx, ny)`` over the
         engine's own buffer, and ``mu_of(u) -> mu_h`` ``(B, nx, ny)``, contiguous.  With ``native_cnn`` or ``native_mixer`` the
-        library evaluates the network: ``mu_of`` fills and returns one buffer, and ``self._cnn`` or ``self._mixer`` holds
-        this call's parameters"""
+        library evaluates the network: ``mu_of`` fills and returns one buffer, and ``self._net()`` holds this call's
+        parameters"""
         torch = self.torch
         eng = self.engine
         eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem(field_mu=True))
@@ -229,61 +165,63 @@ class FieldMuSolver:
             if p.dtype != Y.dtype or p.device != Y.device:
                 raise ValueError(f"mu's parameter {name} is {p.dtype} on {p.device}; the solve runs in {Y.dtype} on {Y.device}")
         if self.native_cnn or self.native_mixer:
-            cnn = self._native(module) if self.native_cnn else self._native_mixer(module)
+            net = self._native(module)
             mu_h = torch.empty_like(Y)
 
             def native_mu(u):
-                cnn.forward(u.data_ptr(), mu_h.data_ptr())
+                net.forward(u.data_ptr(), mu_h.data_ptr())
                 return mu_h
 
             return Y, native_mu
         call = as_field_call(module, Y)
         return Y, lambda u: call(u).reshape(u.shape).contiguous()
 
+    def _net(self):
+        """the library's handle of the network it evaluates and differentiates, or None: torch does"""
+        if self.native_cnn:
+            return self._cnn
+        return self._mixer if self.native_mixer else None
+
     def _native(self, module):
-        """the library's handle of ``module`` with its current parameters uploaded; refuses what csrc/cnn.hip does not cover"""
-        from .numerics.functions import cnn as C
+        """the library's handle of ``module`` with its current parameters uploaded; refuses what csrc/cnn.hip (``native_cnn``,
+        asked first) or csrc/mixer.hip (``native_mixer``) does not cover, and a mixer made for another grid than the engine's"""
+        if self.native_cnn:
+            from .numerics.functions import cnn as C
 
-        spec = C.native_spec(module)
-        if spec is None:
-            raise NotImplementedError(f"native_cnn is on and mu is not a network the library evaluates: {C.native_refusal(module)} "
-                                      "(there is no fallback to torch: set native_cnn = False)")
-        channels, act = spec[0], C.NATIVE_ACTIVATIONS.index(spec[1])
-        if self._cnn is None or (self._cnn.channels, self._cnn.activation) != (channels, act):
-            if self._cnn is not None:
-                self._cnn.close()
-            self._cnn, self._cnn_pending = self.engine.cnn(channels, act), False
-        self._cnn.set_params(flatten_params(module))
-        return self._cnn
-
-    def _native_mixer(self, module):
-        """the library's handle of ``module`` with its current parameters uploaded; refuses what csrc/mixer.hip does not
-        cover and a module made for another grid than the engine's"""
+            self._cnn = self._handle(module, self._cnn, C, "native_cnn",
+                                     lambda spec: (spec[0], C.NATIVE_ACTIVATIONS.index(spec[1])),
+                                     lambda net: (net.channels, net.activation), self.engine.cnn)
+            return self._cnn
         from .numerics.functions import mixer as M
 
-        spec = M.native_spec(module)
-        if spec is None:
-            raise NotImplementedError(f"native_mixer is on and mu is not a network the library evaluates: {M.native_refusal(module)} "
-                                      "(there is no fallback to torch: set native_mixer = False)")
-        grid, sizes, act = spec[0], spec[1:6], M.NATIVE_ACTIVATIONS.index(spec[6])
-        if self._mixer is None or (self._mixer.grid, self._mixer.sizes, self._mixer.activation) != (grid, sizes, act):
-            if self._mixer is not None:
-                self._mixer.close()
-                self._mixer = None
+        def make(grid, sizes, act):
             if grid != (self.engine.problem.nx, self.engine.problem.ny):
                 raise ValueError(f"mu is a Mixer2d for a {grid[0]} x {grid[1]} grid; the solve runs on "
                                  f"{self.engine.problem.nx} x {self.engine.problem.ny}")
-            self._mixer, self._mixer_pending = self.engine.mixer(*sizes, act), False
-        self._mixer.set_params(flatten_params(module))
+            return self.engine.mixer(*sizes, act)
+
+        self._mixer = self._handle(module, self._mixer, M, "native_mixer",
+                                   lambda spec: (spec[0], spec[1:6], M.NATIVE_ACTIVATIONS.index(spec[6])),
+                                   lambda net: (net.grid, net.sizes, net.activation), make)
         return self._mixer
 
-    def _native_handle(self):
-        """``(handle, name of its pending flag)`` of the network the library differentiates in this call, or ``(None, None)``"""
-        if self.native_cnn:
-            return self._cnn, "_cnn_pending"
-        if self.native_mixer:
-            return self._mixer, "_mixer_pending"
-        return None, None
+    @staticmethod
+    def _handle(module, held, family, switch, key_of_spec, key_of_handle, make):
+        """``held`` if it is a handle of ``module``'s structure, else a new one from ``make(*key)`` in its place (``held`` is
+        closed once the new one exists: a ``make`` that refuses leaves it as it was); the parameters are uploaded either
+        way.  ``family`` is the module of ``numerics.functions`` that says what the library covers"""
+        spec = family.native_spec(module)
+        if spec is None:
+            raise NotImplementedError(f"{switch} is on and mu is not a network the library evaluates: {family.native_refusal(module)} "
+                                      f"(there is no fallback to torch: set {switch} = False)")
+        key = key_of_spec(spec)
+        if held is None or key_of_handle(held) != key:
+            new = make(*key)
+            if held is not None:
+                held.close()
+            held = new
+        held.set_params(flatten_params(module))
+        return held
 
     # -- forward --------------------------------------------------------------------------------------------------------
     def solve(self, equation, solver, y0s, ts, dt0, controller=None) -> np.ndarray:
@@ -336,11 +274,9 @@ class FieldMuSolver:
                 by_index.setdefault(i, []).append((q, theta))
         with self._ordered(), torch.no_grad(), _deterministic(torch):
             Y, mu_of = self._prepare(equation, solver, y0s, float(ts[0]), float(ts[-1]))
-            cnn, pending = self._native_handle()
-            if cnn is not None:
-                if getattr(self, pending):
-                    cnn.grad_read(reset=True)
-                setattr(self, pending, True)
+            net = self._net()
+            if net is not None and net.pending:
+                net.grad_read(reset=True)
             if coef_grad:  # (a configure zeroes the slots too; this does not rely on _prepare being one)
                 if self._coef_pending:
                     self.engine.fieldmu_coef_grad_read(n_coef, reset=True)
@@ -348,56 +284,44 @@ class FieldMuSolver:
             vals = torch.as_tensor(np.ascontiguousarray(np.swapaxes(values, 0, 1)), dtype=Y.dtype).to(Y.device)  # (T - 1, B, ...)
             M = vals.numel()
             chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
-            starts, cot = {}, {}
+            cot = {}
             ssr = torch.zeros((), dtype=torch.float64, device=Y.device)
             prev = None
-            for i in range(N + 1):
+
+            def step(i):
+                self.engine.fieldmu_step(integ, steps[i], mu_of(Y).data_ptr())
+
+            def residuals(i):
+                """the residuals of the saves on state ``i`` and their cotangents; the state an interpolated save needs"""
+                nonlocal ssr, prev
                 for q, theta in by_index.get(i, ()):
                     pred = Y if theta is None else prev + theta * (Y - prev)
                     r = vals[q - 1] - pred
                     ssr += (r.double() ** 2).sum()
-                    g_prev, g_cur = split_save_cotangent(r * (-2.0 / M), theta)  # d mean(r^2) / d pred
-                    for k, g in ((i - 1, g_prev), (i, g_cur)):
-                        if g is not None:
-                            cot[k] = g if k not in cot else cot[k] + g
-                if i == N:
-                    break
-                if i % chunk == 0:
-                    starts[i] = Y.clone()
+                    add_save_cotangent(cot, i, theta, r * (-2.0 / M))  # d mean(r^2) / d pred
                 if i in need_prev:
                     prev = Y.clone()
-                self.engine.fieldmu_step(integ, steps[i], mu_of(Y).data_ptr())
-            lam = cot[N].clone() if N in cot else torch.zeros_like(Y)
+
+            def adjoint(s, u, lam):
+                """the library's share of the substep, then the network's"""
+                if net is not None:
+                    adjoint_step(integ, steps[s], u.data_ptr(), mu_of(u).data_ptr(), lam.data_ptr(), gmu.data_ptr())
+                    net.vjp(u.data_ptr(), gmu.data_ptr(), lam.data_ptr())
+                    return
+                u.requires_grad_(True)
+                with torch.enable_grad():
+                    mu = mu_of(u)
+                adjoint_step(integ, steps[s], u.data_ptr(), mu.data_ptr(), lam.data_ptr(), gmu.data_ptr())
+                mu.backward(gmu)
+                lam += u.grad
+
+            starts = forward_pass(Y, N, chunk, step, visit=residuals)
             gmu = torch.empty_like(Y)
             self.last_chunks = len(starts)
-            for s0 in sorted(starts, reverse=True):
-                s1 = min(N, s0 + chunk)
-                Y.copy_(starts.pop(s0))
-                held = []
-                for s in range(s0, s1):
-                    held.append(Y.clone())
-                    if s + 1 < s1:
-                        self.engine.fieldmu_step(integ, steps[s], mu_of(Y).data_ptr())
-                for s in range(s1 - 1, s0 - 1, -1):
-                    if cnn is not None:
-                        u = held.pop()
-                        adjoint_step(integ, steps[s], u.data_ptr(), mu_of(u).data_ptr(), lam.data_ptr(), gmu.data_ptr())
-                        cnn.vjp(u.data_ptr(), gmu.data_ptr(), lam.data_ptr())
-                        if s in cot and s > 0:
-                            lam += cot[s]
-                        continue
-                    u = held.pop().requires_grad_(True)
-                    with torch.enable_grad():
-                        mu = mu_of(u)
-                    adjoint_step(integ, steps[s], u.data_ptr(), mu.data_ptr(), lam.data_ptr(), gmu.data_ptr())
-                    mu.backward(gmu)
-                    lam += u.grad
-                    if s in cot and s > 0:
-                        lam += cot[s]
+            backward_pass(Y, starts, N, chunk, step, adjoint, lambda s: cot.get(s) if s > 0 else None)  # dJ/dy0 has no use
             loss = float(ssr.item()) / M
-            if cnn is not None:
-                add_flat_grad(equation._mu_module, cnn.grad_read(reset=True))
-                setattr(self, pending, False)
+            if net is not None:
+                add_flat_grad(equation._mu_module, net.grad_read(reset=True))
             if coef_grad:
                 grad_D = self.engine.fieldmu_coef_grad_read(n_coef, reset=True)
                 self._coef_pending = False

@@ -624,6 +624,14 @@ def as_objective(objective_function, probe=None) -> SolutionObjective:
     return obj
 
 
+def summed_in_order(rows):
+    """the sum of ``rows[b]`` over the environments b = 0, 1, ...: one fixed order, the same bits on every run"""
+    tot = np.zeros(rows.shape[1:])
+    for row in rows:
+        tot = tot + row
+    return tot
+
+
 def objective_gradient(objective: SolutionObjective, ys, spatial_ndim: int, contract: Callable, pmap: ParamMap):
     """``(J, dJ/dp)`` of ``J(ys)`` over all entries of ``p``, for ``ys`` ``(T, *spatial)`` or ``(T, B, *spatial)``.  The
     objective gives ``g = dJ/dys``; ``contract(g[1:] as (T - 1, B, *spatial)) -> (B, n active)``, the sums
@@ -634,11 +642,8 @@ def objective_gradient(objective: SolutionObjective, ys, spatial_ndim: int, cont
     n_active = int(np.count_nonzero(pmap.active()))
     cot = g[1:].reshape((g.shape[0] - 1, -1) + g.shape[g.ndim - spatial_ndim:])
     per_traj = np.asarray(contract(np.ascontiguousarray(cot)), dtype=np.float64).reshape(-1, n_active)
-    tot = np.zeros(n_active)
-    for row in per_traj:
-        tot = tot + row
     grad = np.zeros(pmap.size)
-    grad[np.nonzero(pmap.active())[0]] = tot
+    grad[np.nonzero(pmap.active())[0]] = summed_in_order(per_traj)
     return J, grad
 
 

@@ -7,8 +7,10 @@ One scalar objective, a field-sized state, a few control numbers: reverse mode. 
 step (``pdeopt_advance``), the backward sweep ``pdeopt_gpe_adjoint_step`` (csrc/gpe_adjoint.hip), one call per substep:
 it takes the cotangent of a substep's end state to that of its start state and adds the spots' gradient on the device.
 The backward sweep needs the state every substep started from: substep and save-point schedule, the split of a save
-point's cotangent and the chunked recomputation are those of ``pde_opt_amd.fieldmu`` (one state kept per chunk, each
-chunk run again and held before its sweep).  A chunk holds at most ``PDEOPT_GPE_ADJOINT_CHUNK_BYTES`` (default 1 GiB;
+point's cotangent, the chunked recomputation and the stream rule are those of ``pde_opt_amd.reverse``, which the
+network ``mu`` of ``pde_opt_amd.fieldmu`` shares.  The cotangents of the saved solution are known before the sweep: the
+forward pass stops where the last chunk starts, a cotangent is uploaded when its state is reached, and the sweep ends
+with ``dJ/dy0``.  A chunk holds at most ``PDEOPT_GPE_ADJOINT_CHUNK_BYTES`` (default 1 GiB;
 ``GpeControlSolver.chunk_bytes`` overrides it).
 
 Covered: ``GPE2DTSControl`` whose ``lights`` is a ``GaussianSpots`` evaluated in-kernel, ``StrangSplitting`` with
@@ -17,28 +19,24 @@ and cotangents) is imported when a solver is built, not with the package.
 
 The rotating-frame pair ``GPE2DTSRot`` + ``RotatingStrangSplitting`` has its own backward substep,
 ``pdeopt_gpe_rot_adjoint_step`` (csrc/gpe_rot_adjoint.hip): the gradient over k, e and omega of every environment and
-over the start state.  ``RotControlSolver`` drives it with the same sweep (``GpeControlSolver._sweep``: schedule, cotangent
-split, chunked recomputation, chunk cap); ``PDEModel.rotation_gradient`` / ``optimize_rotation`` are its public entries.
+over the start state.  ``RotControlSolver`` drives it with the same sweep (``GpeControlSolver._sweep``);
+``PDEModel.rotation_gradient`` / ``optimize_rotation`` are its public entries.
 
 With ``lights`` (Gaussian spots evaluated in-kernel) or ``omega_rate`` the backward substep is
 ``pdeopt_gpe_rot_stir_adjoint_step`` (csrc/gpe_rot_adjoint.hip): it adds the gradient over the rate and over the
-seven numbers of every spot.  ``RotStirControlSolver`` drives it, the sweep carrying the spots' block as a second device
-block; ``PDEModel.stirring_gradient`` / ``optimize_stirring`` are its public entries.
+seven numbers of every spot.  ``RotStirControlSolver`` drives it, the sweep carrying the spots' block as a second
+gradient block; ``PDEModel.stirring_gradient`` / ``optimize_stirring`` are its public entries.
 """
 
 from __future__ import annotations
 
-import contextlib
-import os
-
 import numpy as np
 
 from . import _lib as L
-from .fieldmu import chunk_length, schedule, split_save_cotangent
 from .numerics.functions.lights import SPOT_NUMBERS, GaussianSpot, GaussianSpots
+from .reverse import StreamSolver, chunk_length, known_cotangent_sweep, schedule
 
 CHUNK_BYTES_ENV = "PDEOPT_GPE_ADJOINT_CHUNK_BYTES"
-DEFAULT_CHUNK_BYTES = 1 << 30
 
 GPE_CONTROL_SUPPORT = ("gradients of the GPE support GPE2DTSControl whose lights is a GaussianSpots (evaluated in-kernel: "
                        "time_dependent is not False) with StrangSplitting and ConstantStepSize; the optimisation variables are "
@@ -132,135 +130,84 @@ def reject_unsupported(equation_type, solver_type, parameters=None, opt_names=No
             raise NotImplementedError("time_dependent=False folds the spots into the potential: " + GPE_CONTROL_SUPPORT)
 
 
-_ONE_BLOCK = object()  # GpeControlSolver._sweep: no second gradient block
+def _engine_setup(equation, solver, y0s, ts):
+    """``(configure(engine), equations)`` for one equation shared by the batch ``y0s`` or a list with one per environment:
+    ``configure`` sets the problem, the equations' numbers and tables and the solver up"""
+    shared = not isinstance(equation, (list, tuple))
+    eqs = [equation] if shared else list(equation)
+    if not shared and len(eqs) != y0s.shape[0]:
+        raise ValueError(f"{len(eqs)} equations for a batch of {y0s.shape[0]} states")
+    t_first, t_last = float(ts[0]), float(ts[-1])
+
+    def configure(eng):
+        eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **eqs[0]._engine_problem())
+        if shared:
+            equation._engine_upload(eng, t_first, t_last)
+        else:
+            type(eqs[0])._engine_upload_batch(eng, eqs, t_first, t_last)
+        solver.configure_engine(eng, eqs[0])
+
+    return configure, eqs
 
 
-class GpeControlSolver:
-    """One engine for the backward sweeps, bound to one torch stream (the stream rule of ``fieldmu.FieldMuSolver``:
-    every call orders that stream after the caller's current stream on entry and the caller's after it on exit)."""
+class GpeControlSolver(StreamSolver):
+    """One engine for the backward sweeps, bound to one torch stream (the stream rule of ``reverse.StreamSolver``)."""
 
     def __init__(self, device: int = 0):
-        import torch
+        super().__init__(device, CHUNK_BYTES_ENV)
 
-        from .engine import HipEngine
-
-        self.torch = torch
-        self.device = torch.device("cuda", int(device))
-        cur = torch.cuda.current_stream(self.device)
-        self.stream = cur if cur.cuda_stream else torch.cuda.Stream(self.device)
-        self.engine = HipEngine(int(device), stream=self.stream.cuda_stream)
-        self.chunk_bytes = None  # None: PDEOPT_GPE_ADJOINT_CHUNK_BYTES, else 1 GiB
-        self.last_chunks = 0     # chunks of the last backward sweep
-
-    @contextlib.contextmanager
-    def _ordered(self):
-        torch = self.torch
-        caller = torch.cuda.current_stream(self.device)
-        if caller != self.stream:
-            self.stream.wait_stream(caller)
-        try:
-            with torch.cuda.stream(self.stream):
-                yield
-        finally:
-            if caller != self.stream:
-                caller.wait_stream(self.stream)
-
-    def _cap(self) -> int:
-        if self.chunk_bytes is not None:
-            return int(self.chunk_bytes)
-        return int(os.environ.get(CHUNK_BYTES_ENV, DEFAULT_CHUNK_BYTES))
-
-    def _sweep(self, configure, integrator, y0s, ts, dt0, cotangents, grad_tail, adjoint_step, second_tail=_ONE_BLOCK):
-        """The backward sweep the GPE adjoints share: ``configure(engine)`` sets the problem up, the forward pass keeps
-        one state per chunk, every chunk is run again and held, and ``adjoint_step(engine, t0, dt, psi0_ptr, lam_ptr,
-        grad_ptr)`` takes ``lam`` back one substep while it adds into the device block ``grad`` ``(B,) + grad_tail``.
-        Returns ``(grad, lam0)``, fp64 on the host.  With ``second_tail`` the sweep carries a second device block
-        ``(B,) + second_tail`` (``None``: no such block, a null pointer): ``adjoint_step`` gets its pointer as a seventh
-        argument and the sweep returns ``(grad, second or None, lam0)``."""
-        torch = self.torch
+    def _sweep(self, configure, integrator, y0s, ts, dt0, cotangents, tails, adjoint_step):
+        """The backward sweep the GPE adjoints share (``reverse.known_cotangent_sweep``): ``configure(engine)`` sets the
+        problem up and ``adjoint_step(engine, t0, dt, psi0_ptr, lam_ptr, *block_ptrs)`` takes ``lam`` back one substep while
+        it adds into the gradient blocks, one fp64 device block ``(B,) + tail`` per entry of ``tails`` (``None``: no such
+        block, a null pointer).  Returns ``(blocks, lam0)``: the blocks in the order of ``tails`` (``None`` where the tail
+        is) and ``dJ/dy0``, fp64 on the host."""
         eng = self.engine
         ts = np.asarray(ts, dtype=np.float64)
         steps, saves = schedule(ts, dt0)
-        N = len(steps)
         t_of = lambda i: float(ts[0]) + i * float(dt0)  # start time of substep i (integrate.diffeqsolve)
-        cot = {}
-        for q, (i, theta) in enumerate(saves):
-            g_prev, g_cur = split_save_cotangent(np.asarray(cotangents[q], dtype=np.float64), theta)
-            for k, g in ((i - 1, g_prev), (i, g_cur)):
-                if g is not None:
-                    cot[k] = g if k not in cot else cot[k] + g
-        with self._ordered(), torch.no_grad():
+        with self._ordered(), self.torch.no_grad():
             configure(eng)
             eng.set_state(y0s)
             Y = eng.state_device_array().torch()
-            up = lambda g: torch.as_tensor(np.ascontiguousarray(g)).to(device=Y.device, dtype=Y.dtype)
-            chunk = chunk_length(N, Y.numel() * Y.element_size(), self._cap())
-            first = list(range(0, max(N, 1), chunk))  # first substep of every chunk
-            starts = {}
-            for i in range(first[-1] + 1):  # the forward pass ends where the last chunk starts
-                if i % chunk == 0:
-                    starts[i] = Y.clone()
-                if i < first[-1]:
-                    eng.advance(integrator, steps[i], 1, t_of(i))
-            lam = up(cot[N]) if N in cot and N > 0 else torch.zeros_like(Y)
-            grad = torch.zeros((y0s.shape[0],) + tuple(grad_tail), dtype=torch.float64, device=Y.device)
-            blocks = (grad.data_ptr(),)
-            second = None
-            if second_tail is not _ONE_BLOCK:
-                if second_tail is not None:
-                    second = torch.zeros((y0s.shape[0],) + tuple(second_tail), dtype=torch.float64, device=Y.device)
-                blocks += (second.data_ptr() if second is not None else 0,)
-            self.last_chunks = len(first)
-            for s0 in reversed(first):
-                s1 = min(N, s0 + chunk)
-                Y.copy_(starts.pop(s0))
-                held = []
-                for s in range(s0, s1):
-                    held.append(Y.clone())
-                    if s + 1 < s1:
-                        eng.advance(integrator, steps[s], 1, t_of(s))
-                for s in range(s1 - 1, s0 - 1, -1):
-                    psi0 = held.pop()
-                    adjoint_step(eng, t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(), *blocks)
-                    if s in cot:
-                        lam += up(cot[s])
-            if N == 0 and 0 in cot:
-                lam += up(cot[0])
-            out = grad.cpu().numpy(), lam.double().cpu().numpy()
-            if second_tail is not _ONE_BLOCK:
-                out = out[0], (second.cpu().numpy() if second is not None else None), out[1]
-        return out
+            blocks, lam0, self.last_chunks = known_cotangent_sweep(
+                Y, len(steps), chunk_length(len(steps), Y.numel() * Y.element_size(), self._cap()), saves, cotangents, tails,
+                lambda i: eng.advance(integrator, steps[i], 1, t_of(i)),
+                lambda s, psi0, lam, *blocks: adjoint_step(eng, t_of(s), steps[s], psi0.data_ptr(), lam.data_ptr(),
+                                                           *(0 if g is None else g.data_ptr() for g in blocks)))
+            return [None if g is None else g.cpu().numpy() for g in blocks], lam0.double().cpu().numpy()
 
     def gradient(self, equation, solver, y0s, ts, dt0, cotangents):
         """``(grad (B, S, 7), lam0 (B, nx, ny, 2))`` for the cotangents ``dJ/dys`` ``(len(ts), B, nx, ny, 2)`` of the saved
         solution: ``grad`` is the library's block (per environment; last entry d/d inv_two_w2), ``lam0`` is ``dJ/dy0``.
         Both fp64 on the host; the sweep itself runs in the dtype of ``y0s``."""
-        ts = np.asarray(ts, dtype=np.float64)
-
-        def configure(eng):
-            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **equation._engine_problem())
-            equation._engine_upload(eng, float(ts[0]), float(ts[-1]))
-            solver.configure_engine(eng, equation)
-
-        return self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, (len(equation.lights.spots), 7),
-                           lambda eng, t0, dt, psi0, lam, grad: eng.gpe_adjoint_step(t0, dt, psi0, lam, grad))
+        configure, _ = _engine_setup(equation, solver, y0s, ts)
+        (grad,), lam0 = self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, [(len(equation.lights.spots), 7)],
+                                    lambda eng, t0, dt, psi0, lam, g: eng.gpe_adjoint_step(t0, dt, psi0, lam, g))
+        return grad, lam0
 
 
 ROT_NAMES = ("k", "e", "omega")  # the order of the library's gradient block (pdeopt_gpe_rot_adjoint_step)
 
 
-def reject_unsupported_rotation(equation_type, solver_type, opt_names=None, stepsize_controller=None, parameters=None):
-    """``NotImplementedError`` for what the rotating-frame gradient does not cover; needs no engine and no GPU"""
+def _reject_unsupported_rotating(support, allowed, equation_type, solver_type, opt_names, stepsize_controller):
+    """what ``reject_unsupported_rotation`` and ``reject_unsupported_stirring`` share: the pair, the optimisation
+    variables (a non-empty subset of ``allowed``) and the controller, each refused with ``support``"""
     from .numerics.solvers import ConstantStepSize, RotatingStrangSplitting
 
     if not getattr(equation_type, "_rotating_frame", False):
-        raise NotImplementedError(f"{equation_type.__name__}: " + ROTATION_GRADIENT_SUPPORT)
+        raise NotImplementedError(f"{equation_type.__name__}: " + support)
     if solver_type is not RotatingStrangSplitting:
-        raise NotImplementedError(f"{solver_type.__name__}: " + ROTATION_GRADIENT_SUPPORT)
-    if opt_names is not None and (not set(opt_names) or not set(opt_names) <= set(ROT_NAMES)):
-        raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + ROTATION_GRADIENT_SUPPORT)
+        raise NotImplementedError(f"{solver_type.__name__}: " + support)
+    if opt_names is not None and (not set(opt_names) or not set(opt_names) <= set(allowed)):
+        raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + support)
     if stepsize_controller is not None and not isinstance(stepsize_controller, ConstantStepSize):
-        raise NotImplementedError(f"{type(stepsize_controller).__name__}: " + ROTATION_GRADIENT_SUPPORT)
+        raise NotImplementedError(f"{type(stepsize_controller).__name__}: " + support)
+
+
+def reject_unsupported_rotation(equation_type, solver_type, opt_names=None, stepsize_controller=None, parameters=None):
+    """``NotImplementedError`` for what the rotating-frame gradient does not cover; needs no engine and no GPU"""
+    _reject_unsupported_rotating(ROTATION_GRADIENT_SUPPORT, ROT_NAMES, equation_type, solver_type, opt_names, stepsize_controller)
     if parameters is not None:
         if parameters.get("lights") is not None:
             raise NotImplementedError("an equation with lights: " + ROTATION_GRADIENT_SUPPORT)
@@ -278,22 +225,10 @@ class RotControlSolver(GpeControlSolver):
         solution: row b of ``grad`` is ``dJ/d(k, e, omega)`` of environment b, ``lam0`` is ``dJ/dy0``.  ``equation`` is
         one ``GPE2DTSRot`` shared by the batch or a list with one per environment (its own k, e, omega).  Both fp64 on
         the host; the sweep itself runs in the dtype of ``y0s``.  Constant steps only."""
-        ts = np.asarray(ts, dtype=np.float64)
-        eqs = list(equation) if isinstance(equation, (list, tuple)) else None
-        eq0 = eqs[0] if eqs else equation
-        if eqs is not None and len(eqs) != y0s.shape[0]:
-            raise ValueError(f"{len(eqs)} equations for a batch of {y0s.shape[0]} states")
-
-        def configure(eng):
-            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **eq0._engine_problem())
-            if eqs is None:
-                eq0._engine_upload(eng, float(ts[0]), float(ts[-1]))
-            else:
-                type(eq0)._engine_upload_batch(eng, eqs, float(ts[0]), float(ts[-1]))
-            solver.configure_engine(eng, eq0)
-
-        return self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, (3,),
-                           lambda eng, t0, dt, psi0, lam, grad: eng.gpe_rot_adjoint_step(dt, psi0, lam, grad))
+        configure, _ = _engine_setup(equation, solver, y0s, ts)
+        (grad,), lam0 = self._sweep(configure, solver.integrator, y0s, ts, dt0, cotangents, [(3,)],
+                                    lambda eng, t0, dt, psi0, lam, g: eng.gpe_rot_adjoint_step(dt, psi0, lam, g))
+        return grad, lam0
 
 
 STIR_NAMES = ("k", "e", "omega", "omega_rate")  # the order of pdeopt_gpe_rot_stir_adjoint_step's gradient block
@@ -308,16 +243,8 @@ STIRRING_GRADIENT_SUPPORT = ("stirring_gradient and optimize_stirring support GP
 def reject_unsupported_stirring(equation_type, solver_type, opt_names=None, stepsize_controller=None, parameters=None,
                                 opt_parameters=None):
     """``NotImplementedError`` for what the stirred rotating-frame gradient does not cover; needs no engine and no GPU"""
-    from .numerics.solvers import ConstantStepSize, RotatingStrangSplitting
-
-    if not getattr(equation_type, "_rotating_frame", False):
-        raise NotImplementedError(f"{equation_type.__name__}: " + STIRRING_GRADIENT_SUPPORT)
-    if solver_type is not RotatingStrangSplitting:
-        raise NotImplementedError(f"{solver_type.__name__}: " + STIRRING_GRADIENT_SUPPORT)
-    if opt_names is not None and (not set(opt_names) or not set(opt_names) <= set(STIR_NAMES) | {"lights"}):
-        raise NotImplementedError(f"optimisation variables {sorted(opt_names)}: " + STIRRING_GRADIENT_SUPPORT)
-    if stepsize_controller is not None and not isinstance(stepsize_controller, ConstantStepSize):
-        raise NotImplementedError(f"{type(stepsize_controller).__name__}: " + STIRRING_GRADIENT_SUPPORT)
+    _reject_unsupported_rotating(STIRRING_GRADIENT_SUPPORT, STIR_NAMES + ("lights",), equation_type, solver_type, opt_names,
+                                 stepsize_controller)
     if opt_parameters is not None and "lights" in opt_parameters and not isinstance(opt_parameters["lights"], GaussianSpots):
         raise NotImplementedError(f"lights of type {type(opt_parameters['lights']).__name__} as an optimisation variable: "
                                   + STIRRING_GRADIENT_SUPPORT)
@@ -347,27 +274,12 @@ class RotStirControlSolver(RotControlSolver):
         environment (its own k, e, omega, omega_rate and spots): spot tables travel padded to the largest count; where
         the counts differ the padding's rows are dropped and ``spot_grad`` is a list of ``(S_b, 7)`` arrays.  All fp64 on the host;
         the sweep itself runs in the dtype of ``y0s``.  Constant steps only."""
-        ts = np.asarray(ts, dtype=np.float64)
-        eqs = list(equation) if isinstance(equation, (list, tuple)) else None
-        eq0 = eqs[0] if eqs else equation
-        if eqs is not None and len(eqs) != y0s.shape[0]:
-            raise ValueError(f"{len(eqs)} equations for a batch of {y0s.shape[0]} states")
-        t_first, t_last = float(ts[0]), float(ts[-1])
-        kinds = [e._lights_kind(t_first, t_last) for e in (eqs or [eq0])]
-        counts = [len(e.lights.spots) for e in (eqs or [eq0])] if all(k == "spots" for k in kinds) else None
-
-        def configure(eng):
-            eng.configure(dtype=y0s.dtype, batch=y0s.shape[0], **eq0._engine_problem())
-            if eqs is None:
-                eq0._engine_upload(eng, t_first, t_last)
-            else:
-                type(eq0)._engine_upload_batch(eng, eqs, t_first, t_last)
-            solver.configure_engine(eng, eq0)
-
-        grad, spot_grad, lam0 = self._sweep(
-            configure, solver.integrator, y0s, ts, dt0, cotangents, (4,),
-            lambda eng, t0, dt, psi0, lam, g, sg: eng.gpe_rot_stir_adjoint_step(t0, dt, psi0, lam, g, sg),
-            second_tail=(max(counts), 7) if counts else None)
+        configure, eqs = _engine_setup(equation, solver, y0s, ts)
+        kinds = [e._lights_kind(float(ts[0]), float(ts[-1])) for e in eqs]
+        counts = [len(e.lights.spots) for e in eqs] if all(k == "spots" for k in kinds) else None
+        (grad, spot_grad), lam0 = self._sweep(
+            configure, solver.integrator, y0s, ts, dt0, cotangents, [(4,), (max(counts), 7) if counts else None],
+            lambda eng, t0, dt, psi0, lam, g, sg: eng.gpe_rot_stir_adjoint_step(t0, dt, psi0, lam, g, sg))
         if counts and len(set(counts)) > 1:  # drop the padding: zero-amplitude spots that stand for none
             spot_grad = [spot_grad[b, :n].copy() for b, n in enumerate(counts)]
         return grad, spot_grad, lam0

@@ -461,6 +461,16 @@ class PDEModel:
         from . import gpe_control
 
         gpe_control.reject_unsupported(self.equation_type, self.solver_type, parameters)
+        J, (raw,), lam0 = self._reverse_gradient(self.gpe_control_solver, objective_function, y0, ts, parameters,
+                                                 solver_parameters, dt0)
+        grad = gpe_control.SpotMap.user_gradient(parameters["lights"], raw)
+        return J, (grad if per_environment else fit.summed_in_order(grad)), lam0
+
+    def _reverse_gradient(self, get_solver, objective_function, y0, ts, parameters, solver_parameters, dt0, check_equation=None):
+        """What ``control_gradient``, ``rotation_gradient`` and ``stirring_gradient`` share: the solve, the objective and
+        its cotangent, and the backward sweep of ``get_solver()`` (built when the sweep is reached).  Returns ``(J, blocks,
+        lam0)``: ``blocks`` is what that solver's ``gradient`` returns before ``lam0``, per environment, and ``lam0`` has
+        the shape of ``y0``.  ``check_equation(equation, ts)`` may refuse the equation once it is built."""
         y0 = np.asarray(y0)
         if y0.dtype not in (np.float32, np.float64):
             y0 = y0.astype(np.float64)
@@ -469,19 +479,35 @@ class PDEModel:
         if y0.ndim not in (3, 4) or tuple(y0.shape[-3:]) != tuple(self.domain.points) + (2,):
             raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points) + (2,)} or (B,) + that")
         equation = self.equation_type(domain=self.domain, **parameters)
+        if check_equation is not None:
+            check_equation(equation, ts)
         solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
         ys = self.solve(parameters, y0, ts, solver_parameters, dt0=dt0)
         J, g = objective.value_and_grad(ys)
         single = y0.ndim == 3
         cot = g[:, None] if single else g
-        raw, lam0 = self.gpe_control_solver().gradient(equation, solver, y0[None] if single else y0, ts, float(dt0), cot)
-        grad = gpe_control.SpotMap.user_gradient(parameters["lights"], raw)
-        if not per_environment:
-            tot = np.zeros(grad.shape[1:])
-            for row in grad:
-                tot = tot + row
-            grad = tot
-        return J, grad, (lam0[0] if single else lam0)
+        *blocks, lam0 = get_solver().gradient(equation, solver, y0[None] if single else y0, ts, float(dt0), cot)
+        return J, blocks, (lam0[0] if single else lam0)
+
+    def _penalised_bfgs(self, p0, w, lambda_reg, params_of, value_of, value_and_grad_of, max_steps, active=None):
+        """BFGS (``fit.minimize_bfgs``) on ``J(p) + lambda_reg sum(w p^2)`` from ``p0``; the flat vector it ends at.
+        ``value_of(params_of(p))`` is ``J`` from a forward solve (the trial points of the line search),
+        ``value_and_grad_of(params_of(p))`` is ``(J, flat dJ/dp)``; entries outside ``active`` keep a zero gradient.  The
+        objective after every accepted step goes to ``last_optimize_history``."""
+        lam = float(lambda_reg)
+        penalty = lambda p: lam * float(np.sum(w * p * p))
+
+        def value(p):
+            return value_of(params_of(p)) + penalty(p)
+
+        def value_and_grad(p):
+            J, g = value_and_grad_of(params_of(p))
+            g = g + 2.0 * lam * w * p
+            return J + penalty(p), (g if active is None else g * active)
+
+        p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
+        self.last_optimize_history = hist
+        return p
 
     def _optimize_gpe(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters, weights,
                       lambda_reg, max_steps):
@@ -502,22 +528,15 @@ class PDEModel:
                                        opt_names=opt_parameters)
         smap = gpe_control.SpotMap.of(opt_parameters["lights"])
         w = smap.weight_vector(weights.get("lights"))
-        active = smap.active().reshape(-1)
-        lam = float(lambda_reg)
 
-        def params_of(p):
-            return {**other_parameters, "lights": smap.build(p)}
+        def value_and_grad(params):
+            J, grad, _ = self.control_gradient(objective, y0, ts, params, solver_parameters)
+            return J, grad.reshape(-1)
 
-        def value(p):
-            return objective.value(self.solve(params_of(p), y0, ts, solver_parameters)) + lam * float(np.sum(w * p * p))
-
-        def value_and_grad(p):
-            J, grad, _ = self.control_gradient(objective, y0, ts, params_of(p), solver_parameters)
-            g = (grad.reshape(-1) + 2.0 * lam * w * p) * active
-            return J + lam * float(np.sum(w * p * p)), g
-
-        p, hist = fit.minimize_bfgs(value_and_grad, value, smap.flatten(opt_parameters["lights"]), max_steps=max_steps)
-        self.last_optimize_history = hist
+        p = self._penalised_bfgs(smap.flatten(opt_parameters["lights"]), w, lambda_reg,
+                                 lambda p: {**other_parameters, "lights": smap.build(p)},
+                                 lambda params: objective.value(self.solve(params, y0, ts, solver_parameters)),
+                                 value_and_grad, max_steps, active=smap.active().reshape(-1))
         return {"lights": smap.build(p), **other_parameters}
 
     # -- gradients of the rotating-frame GPE (pde_opt_amd.gpe_control.RotControlSolver) -------------------------------
@@ -545,27 +564,9 @@ class PDEModel:
 
         gpe_control.reject_unsupported_rotation(self.equation_type, self.solver_type, stepsize_controller=stepsize_controller,
                                                 parameters=parameters)
-        y0 = np.asarray(y0)
-        if y0.dtype not in (np.float32, np.float64):
-            y0 = y0.astype(np.float64)
-        ts = np.asarray(ts, dtype=np.float64)
-        objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
-        if y0.ndim not in (3, 4) or tuple(y0.shape[-3:]) != tuple(self.domain.points) + (2,):
-            raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points) + (2,)} or (B,) + that")
-        equation = self.equation_type(domain=self.domain, **parameters)
-        solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
-        ys = self.solve(parameters, y0, ts, solver_parameters, dt0=dt0)
-        J, g = objective.value_and_grad(ys)
-        single = y0.ndim == 3
-        cot = g[:, None] if single else g
-        grad, lam0 = self.rot_control_solver().gradient(equation, solver, y0[None] if single else y0, ts, float(dt0), cot)
-        if not per_environment:
-            tot = np.zeros(grad.shape[1:])
-            for row in grad:
-                tot = tot + row
-            grad = tot
-        out = {name: (grad[..., j].copy() if per_environment else float(grad[j])) for j, name in enumerate(gpe_control.ROT_NAMES)}
-        return J, out, (lam0[0] if single else lam0)
+        J, (grad,), lam0 = self._reverse_gradient(self.rot_control_solver, objective_function, y0, ts, parameters,
+                                                  solver_parameters, dt0)
+        return J, _named_gradient(grad, gpe_control.ROT_NAMES, per_environment), lam0
 
     def optimize_rotation(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters=None,
                           weights=None, lambda_reg=0.0, max_steps=100, dt0=0.000001, stepsize_controller=None):
@@ -584,22 +585,18 @@ class PDEModel:
         y0 = np.asarray(y0)
         objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
         names = [n for n in gpe_control.ROT_NAMES if n in opt_parameters]
-        w = np.array([float(weights.get(n, 0.0)) for n in names])
-        lam = float(lambda_reg)
 
         def params_of(p):
             return {**other_parameters, **{n: float(v) for n, v in zip(names, p)}}
 
-        def value(p):
-            return objective.value(self.solve(params_of(p), y0, ts, solver_parameters, dt0=dt0)) + lam * float(np.sum(w * p * p))
+        def value_and_grad(params):
+            J, grad, _ = self.rotation_gradient(objective, y0, ts, params, solver_parameters, dt0=dt0)
+            return J, np.array([grad[n] for n in names])
 
-        def value_and_grad(p):
-            J, grad, _ = self.rotation_gradient(objective, y0, ts, params_of(p), solver_parameters, dt0=dt0)
-            return J + lam * float(np.sum(w * p * p)), np.array([grad[n] for n in names]) + 2.0 * lam * w * p
-
-        p0 = np.array([float(opt_parameters[n]) for n in names], dtype=np.float64)
-        p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
-        self.last_optimize_history = hist
+        p = self._penalised_bfgs(np.array([float(opt_parameters[n]) for n in names], dtype=np.float64),
+                                 np.array([float(weights.get(n, 0.0)) for n in names]), lambda_reg, params_of,
+                                 lambda params: objective.value(self.solve(params, y0, ts, solver_parameters, dt0=dt0)),
+                                 value_and_grad, max_steps)
         return params_of(p)
 
     # -- gradients of the stirred, ramped rotating-frame GPE (pde_opt_amd.gpe_control.RotStirControlSolver) ------------
@@ -629,36 +626,14 @@ class PDEModel:
 
         gpe_control.reject_unsupported_stirring(self.equation_type, self.solver_type, stepsize_controller=stepsize_controller,
                                                 parameters=parameters)
-        y0 = np.asarray(y0)
-        if y0.dtype not in (np.float32, np.float64):
-            y0 = y0.astype(np.float64)
-        ts = np.asarray(ts, dtype=np.float64)
-        objective = fit.as_objective(objective_function, np.broadcast_to(y0.astype(np.float64), (len(ts),) + y0.shape))
-        if y0.ndim not in (3, 4) or tuple(y0.shape[-3:]) != tuple(self.domain.points) + (2,):
-            raise ValueError(f"y0 of shape {y0.shape}: expected {tuple(self.domain.points) + (2,)} or (B,) + that")
-        equation = self.equation_type(domain=self.domain, **parameters)
-        gpe_control.reject_time_dependent_lights(equation, ts[0], ts[-1])
-        solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
-        ys = self.solve(parameters, y0, ts, solver_parameters, dt0=dt0)
-        J, g = objective.value_and_grad(ys)
-        single = y0.ndim == 3
-        cot = g[:, None] if single else g
-        grad, spot_grad, lam0 = self.rot_stir_control_solver().gradient(equation, solver, y0[None] if single else y0, ts,
-                                                                        float(dt0), cot)
-
-        def total(rows):  # summed in order
-            tot = np.zeros(rows.shape[1:])
-            for row in rows:
-                tot = tot + row
-            return tot
-
-        if not per_environment:
-            grad = total(grad)
-        out = {name: (grad[..., j].copy() if per_environment else float(grad[j])) for j, name in enumerate(gpe_control.STIR_NAMES)}
+        J, (grad, spot_grad), lam0 = self._reverse_gradient(
+            self.rot_stir_control_solver, objective_function, y0, ts, parameters, solver_parameters, dt0,
+            check_equation=lambda equation, ts: gpe_control.reject_time_dependent_lights(equation, ts[0], ts[-1]))
+        out = _named_gradient(grad, gpe_control.STIR_NAMES, per_environment)
         if isinstance(parameters.get("lights"), GaussianSpots):
             user = gpe_control.SpotMap.user_gradient(parameters["lights"], spot_grad)
-            out["lights"] = user if per_environment else total(user)
-        return J, out, (lam0[0] if single else lam0)
+            out["lights"] = user if per_environment else fit.summed_in_order(user)
+        return J, out, lam0
 
     def optimize_stirring(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters=None,
                           weights=None, lambda_reg=0.0, max_steps=100, dt0=0.000001, stepsize_controller=None):
@@ -690,7 +665,6 @@ class PDEModel:
             w = np.concatenate([w, smap.weight_vector(weights.get("lights"))])
             active = np.concatenate([active, smap.active().reshape(-1)])
             p0 = np.concatenate([p0, smap.flatten(opt_parameters["lights"])])
-        lam = float(lambda_reg)
 
         def params_of(p):
             out = {**other_parameters, **{n: float(v) for n, v in zip(names, p[:ns])}}
@@ -698,18 +672,16 @@ class PDEModel:
                 out["lights"] = smap.build(p[ns:])
             return out
 
-        def value(p):
-            return objective.value(self.solve(params_of(p), y0, ts, solver_parameters, dt0=dt0)) + lam * float(np.sum(w * p * p))
-
-        def value_and_grad(p):
-            J, grad, _ = self.stirring_gradient(objective, y0, ts, params_of(p), solver_parameters, dt0=dt0)
+        def value_and_grad(params):
+            J, grad, _ = self.stirring_gradient(objective, y0, ts, params, solver_parameters, dt0=dt0)
             g = np.array([grad[n] for n in names], dtype=np.float64)
             if smap is not None:
                 g = np.concatenate([g, np.asarray(grad["lights"]).reshape(-1)])
-            return J + lam * float(np.sum(w * p * p)), (g + 2.0 * lam * w * p) * active
+            return J, g
 
-        p, hist = fit.minimize_bfgs(value_and_grad, value, p0, max_steps=max_steps)
-        self.last_optimize_history = hist
+        p = self._penalised_bfgs(p0, w, lambda_reg, params_of,
+                                 lambda params: objective.value(self.solve(params, y0, ts, solver_parameters, dt0=dt0)),
+                                 value_and_grad, max_steps, active=active)
         return params_of(p)
 
     def _objective_functions(self, objective_function, y0, ts, opt_parameters, other_parameters, solver_parameters, weights,
@@ -758,6 +730,13 @@ class PDEModel:
             return J + reg.reg(p), grad * pmap.column_factors(p) + reg.reg_grad(p)
 
         return value_and_grad, value, pmap
+
+
+def _named_gradient(grad, names, per_environment):
+    """the library's block ``(B, len(names))`` as a dict: ``(B,)`` arrays per environment, floats of the sum in order otherwise"""
+    if not per_environment:
+        grad = fit.summed_in_order(grad)
+    return {name: (grad[..., j].copy() if per_environment else float(grad[j])) for j, name in enumerate(names)}
 
 
 def _array_weights(weights) -> dict:
