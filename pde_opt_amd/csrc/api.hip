@@ -33,6 +33,18 @@ int ensure_buffer(pdeopt_ctx* ctx, void** p, size_t bytes) {
   return PDEOPT_OK;
 }
 
+int grow_device_buffer(pdeopt_ctx* ctx, void** p, size_t* have_bytes, size_t need_bytes, bool sync_first) {
+  if (*p && *have_bytes < need_bytes) {
+    if (sync_first) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(*p);
+    *p = nullptr;
+    *have_bytes = 0;
+  }
+  const int rc = ensure_buffer(ctx, p, need_bytes);
+  if (!rc) *have_bytes = std::max(*have_bytes, need_bytes);
+  return rc;
+}
+
 int ensure_adaptive_block(pdeopt_ctx* ctx, size_t bytes) {
   if (ctx->adaptive_cap >= bytes) return PDEOPT_OK;
   if (ctx->adaptive_blk) {

@@ -313,6 +313,9 @@ inline bool bv_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_BV || eq == 
   } while (0)
 
 int ensure_buffer(pdeopt_ctx* ctx, void** p, size_t bytes);
+// *p holds at least need_bytes afterwards: a block that is too small is freed first (sync_first: after the stream's work,
+// which may still use it); *have_bytes is the capacity of *p, grow-only
+int grow_device_buffer(pdeopt_ctx* ctx, void** p, size_t* have_bytes, size_t need_bytes, bool sync_first);
 // ctx->adaptive_blk holds at least `bytes` afterwards.  Kept with the ctx, grow-only: a solve of a 64^2 grid is a few
 // hundred microseconds, a hipMalloc / hipFree pair is not free
 int ensure_adaptive_block(pdeopt_ctx* ctx, size_t bytes);

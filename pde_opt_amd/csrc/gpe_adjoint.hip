@@ -22,6 +22,7 @@
 #include <cmath>
 #include <complex>
 
+#include "block_sums.hpp"
 #include "common.hpp"
 
 namespace pdeopt {
@@ -90,16 +91,6 @@ __device__ __forceinline__ C2<T> phase_factor(const GpeAdjArgs<T>& a, int env, i
   return C2<T>{mag * cs, -mag * sn};
 }
 
-// sum over the workgroup (256 threads), valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();  // sh may still be read from the previous sum
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // c[b][cell] *= m[cell] or conj(m[cell])
 template <typename T, bool CONJ>
 __global__ __launch_bounds__(256) void gpe_adjoint_mul_kernel(C2<T>* __restrict__ c, const C2<T>* __restrict__ m, int64_t cells) {
@@ -153,7 +144,7 @@ __global__ __launch_bounds__(256) void gpe_adjoint_pointwise_kernel(const GpeAdj
       ss += p[2 * q + 1];
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int off = 32; off > 0; off >>= 1) {  // (two wave_sum calls lengthen this kernel by 14 instructions)
       sn += __shfl_down(sn, off, 64);
       ss += __shfl_down(ss, off, 64);
     }

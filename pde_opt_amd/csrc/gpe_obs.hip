@@ -220,11 +220,7 @@ __global__ __launch_bounds__(64) void gobs_finish_kernel(const double* __restric
                                                          double* __restrict__ out) {
   const int env = blockIdx.x, lane = threadIdx.x;
   double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int q = lane; q < n8; q += 64) {
-    const double* const r = p8 + ((int64_t)env * n8 + q) * kObs;
-#pragma unroll
-    for (int c = 0; c < 7; ++c) s[c] += r[c];
-  }
+  rows_total<7, kObs>(p8 + (int64_t)env * n8 * kObs, n8, lane, s);
   for (int q = lane; q < npy; q += 64) {
     s[1] += py[((int64_t)env * npy + q) * 2];
     s[4] += py[((int64_t)env * npy + q) * 2 + 1];
@@ -234,10 +230,7 @@ __global__ __launch_bounds__(64) void gobs_finish_kernel(const double* __restric
     s[4] += px[((int64_t)env * npx + q) * 2 + 1];
   }
 #pragma unroll
-  for (int c = 0; c < 7; ++c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s[c] += __shfl_down(s[c], o, 64);
-  }
+  for (int c = 0; c < 7; ++c) s[c] = wave_sum(s[c]);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 7; ++c) out[(int64_t)env * kObs + c] = s[c] * h2;

@@ -89,7 +89,7 @@ enum { kNorm = 0, kSigma = 1, kGradK = 2, kGradE = 3, kOmega1 = 4, kOmega2 = 5, 
 // the stirred step: the same, then 4 independent sums per spot (spot_partials)
 constexpr int kSpotSums = 4 * PDEOPT_MAX_SPOTS, kSpot0 = kSlots, kStirSlots = kSpot0 + kSpotSums;
 
-// radj_block_sum, radj_slot_total: gpe_rot_adjoint_sums.hpp
+// block_sum: block_sums.hpp; radj_slot_total: gpe_rot_adjoint_sums.hpp
 __device__ __forceinline__ double radj_slot_total(const double* part, int b, int slot, int lane) {
   return pdeopt::radj_slot_total(part, kSlots, b, slot, lane);
 }
@@ -172,10 +172,10 @@ __device__ __forceinline__ void radj_conj_mul_body(Cx<T>* __restrict__ lam, cons
     lam[o + i] = cmul(l, Cx<T>{m.re, -m.im});
   }
   double* out = part + ((int64_t)b * kBlocks + blockIdx.x) * (STIRRED ? kStirSlots : kSlots);
-  const double so = radj_block_sum(acc_o, sh);
+  const double so = block_sum(acc_o, sh);
   if (threadIdx.x == 0) out[slot] = so;
   if (SIGMA) {
-    const double ss = radj_block_sum(acc_s, sh);
+    const double ss = block_sum(acc_s, sh);
     if (threadIdx.x == 0) out[kSigma] = ss;
   }
 }
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void radj_recompute_kernel(const RadjArgs<T> a
     a.cbuf[o + i] = c;
     acc += (double)c.re * (double)c.re + (double)c.im * (double)c.im;
   }
-  const double s = radj_block_sum(acc, sh);
+  const double s = block_sum(acc, sh);
   if (threadIdx.x == 0) a.part[((int64_t)b * kBlocks + blockIdx.x) * kSlots + kNorm] = s;
 }
 template <typename T>
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void rsadj_recompute_kernel(const RsadjArgs<T>
     a.cbuf[o + i] = c;
     acc += (double)c.re * (double)c.re + (double)c.im * (double)c.im;
   }
-  const double s = radj_block_sum(acc, sh);
+  const double s = block_sum(acc, sh);
   if (threadIdx.x == 0) a.part[((int64_t)b * kBlocks + blockIdx.x) * kStirSlots + kNorm] = s;
 }
 
@@ -309,9 +309,9 @@ __global__ __launch_bounds__(256) void radj_pointwise_kernel(const RadjArgs<T> a
     acc_e += (double)gw * (double)(T(0.5) * (x * x - y * y));
   }
   double* out = a.part + ((int64_t)b * kBlocks + blockIdx.x) * kSlots;
-  const double sk = radj_block_sum(acc_k, sh);
+  const double sk = block_sum(acc_k, sh);
   if (tid == 0) out[kGradK] = sk;
-  const double se = radj_block_sum(acc_e, sh);
+  const double se = block_sum(acc_e, sh);
   if (tid == 0) out[kGradE] = se;
 }
 
@@ -400,14 +400,14 @@ __global__ __launch_bounds__(256) void rsadj_pointwise_kernel(const RsadjArgs<T>
     }
   }
   double* out = a.part + ((int64_t)b * kBlocks + blockIdx.x) * kStirSlots;
-  const double sk = radj_block_sum(acc_k, sh);
+  const double sk = block_sum(acc_k, sh);
   if (tid == 0) out[kGradK] = sk;
-  const double se = radj_block_sum(acc_e, sh);
+  const double se = block_sum(acc_e, sh);
   if (tid == 0) out[kGradE] = se;
 #pragma unroll
   for (int q = 0; q < kSpotSums; ++q) {
     if (q < 4 * ns) {  // uniform over the workgroup
-      const double v = radj_block_sum(acc[q], sh);
+      const double v = block_sum(acc[q], sh);
       if (tid == 0) out[kSpot0 + q] = v;
     }
   }

@@ -1,26 +1,17 @@
 // The gather-form reductions shared by the frozen and the stirred adjoint of the rotating-frame split step
 // (gpe_rot_adjoint.hip): a fixed partition of kRadjBlocks workgroups per environment, every workgroup leaves one
-// fp64 partial per sum, and whoever needs a total adds the partials in one fixed order.  No atomics: a repeat gives the
-// same bits.
+// fp64 partial per sum (block_sum of block_sums.hpp), and whoever needs a total adds the partials in one fixed order.
+// No atomics: a repeat gives the same bits.
 #pragma once
 
 #include <cstdint>
 
+#include "block_sums.hpp"
 #include "common.hpp"
 
 namespace pdeopt {
 
 constexpr int kRadjBlocks = 128;  // workgroups per environment: the fixed partition of every reduction
-
-// sum over the workgroup (256 threads), valid in thread 0
-__device__ __forceinline__ double radj_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();  // sh may still be read from the previous sum
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 
 // the sum of one slot over the partition (part: [batch][kRadjBlocks][slots]), every caller in the same order (one wave:
 // threads 0 .. 63); valid in lane 0
@@ -28,9 +19,7 @@ __device__ __forceinline__ double radj_slot_total(const double* part, int slots,
   const double* p = part + (int64_t)b * kRadjBlocks * slots + slot;
   double v = 0.0;
   for (int q = lane; q < kRadjBlocks; q += 64) v += p[(int64_t)q * slots];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
+  return wave_sum(v);
 }
 
 }  // namespace pdeopt

@@ -240,16 +240,9 @@ __global__ __launch_bounds__(64) void pfobs_finish_kernel(const double* __restri
                                                           double* __restrict__ out) {
   const int env = blockIdx.x, lane = threadIdx.x;
   double s[kObs] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int q = lane; q < slots; q += 64) {
-    const double* const r = partial + ((int64_t)env * slots + q) * kObs;
+  rows_total<kObs>(partial + (int64_t)env * slots * kObs, slots, lane, s);
 #pragma unroll
-    for (int c = 0; c < kObs; ++c) s[c] += r[c];
-  }
-#pragma unroll
-  for (int c = 0; c < kObs; ++c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s[c] += __shfl_down(s[c], o, 64);
-  }
+  for (int c = 0; c < kObs; ++c) s[c] = wave_sum(s[c]);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < kObs; ++c) out[(int64_t)env * kObs + c] = c == PDEOPT_PF_OBS_NONFINITE ? s[c] : s[c] * h;
@@ -293,14 +286,7 @@ int pf_observables_t(pdeopt_ctx* ctx, int env_first, int env_count, double* host
   // one block: the rows [envs][8], the partial rows [envs][slots][8], 3-D: mu [envs][cells], fp32: the fp64 parameters
   const size_t n_out = (size_t)kObs * env_count, n_part = n_out * (size_t)slots, n_mu = is3d ? (size_t)cells * env_count : 0;
   const size_t need = sizeof(double) * (n_out + n_part + n_mu) + sizeof(EnvParams<double>) * (size_t)env_count;
-  if (ctx->pf_obs_cap < need) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->pf_obs_dev) (void)hipFree(ctx->pf_obs_dev);
-    ctx->pf_obs_dev = nullptr;
-    ctx->pf_obs_cap = 0;
-    PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->pf_obs_dev, need));
-    ctx->pf_obs_cap = need;
-  }
+  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->pf_obs_dev, &ctx->pf_obs_cap, need, /*sync_first=*/true)) return rc;
   double* const out = ctx->pf_obs_dev;
   double* const mu3 = out + n_out + n_part;
   PfObsArgs<T> a{};

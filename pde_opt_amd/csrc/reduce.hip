@@ -79,12 +79,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const T* __restrict__ y, in
 int run_pass(pdeopt_ctx* ctx, const double* shift_dev, std::vector<Partial>& host) {
   const int batch = ctx->prob.batch;
   const size_t need = (size_t)batch * kChunks * sizeof(Partial);
-  if (ctx->red_cap < need) {
-    if (ctx->red_dev) (void)hipFree(ctx->red_dev);
-    ctx->red_dev = nullptr;
-    PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->red_dev, need));
-    ctx->red_cap = need;
-  }
+  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false)) return rc;
   dim3 grid(kChunks, batch), block(256);
   with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
@@ -217,14 +212,7 @@ int detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int env_firs
   const size_t cells = (size_t)p.nx * p.ny;
   const size_t wbytes = host_winding ? cells * env_count * sizeof(int32_t) : 0;
   const size_t need = wbytes + (size_t)env_count * 3 * sizeof(long long);
-  if (ctx->vort_dev && ctx->vort_cap < need) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->vort_dev);
-    ctx->vort_dev = nullptr;
-  }
-  int rc = ensure_buffer(ctx, &ctx->vort_dev, need);
-  if (rc) return rc;
-  if (ctx->vort_cap < need) ctx->vort_cap = need;
+  if (const int rc = grow_device_buffer(ctx, &ctx->vort_dev, &ctx->vort_cap, need, /*sync_first=*/true)) return rc;
   long long* counts = reinterpret_cast<long long*>(ctx->vort_dev);
   int32_t* wdev = host_winding ? reinterpret_cast<int32_t*>(counts + (size_t)env_count * 3) : nullptr;
   PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, (size_t)env_count * 3 * sizeof(long long), ctx->stream));
@@ -272,13 +260,7 @@ int probe_state(pdeopt_ctx* ctx, const int32_t* cells, int n_probes, int env_fir
   }
   const int64_t total = (int64_t)env_count * n_probes * ctx->comps;
   const size_t need = (size_t)n_probes * sizeof(int64_t) + (size_t)total * sizeof(double);
-  if (ctx->red_cap < need) {
-    if (ctx->red_dev) (void)hipFree(ctx->red_dev);
-    ctx->red_dev = nullptr;
-    ctx->red_cap = 0;
-    PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->red_dev, need));
-    ctx->red_cap = need;
-  }
+  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false)) return rc;
   double* out_dev = ctx->red_dev;
   int64_t* cell_dev = reinterpret_cast<int64_t*>(ctx->red_dev + total);
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(cell_dev, flat.data(), (size_t)n_probes * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));

@@ -689,19 +689,6 @@ int rk4_substep(pdeopt_ctx* ctx, double dt, double ts, bool timed) {
   return PDEOPT_OK;
 }
 
-// *p holds at least need_bytes afterwards; a block that is too small is freed first (sync_first: after the stream's
-// work, which may still use it) and *have_bytes keeps the largest size asked for
-int grow_device_buffer(pdeopt_ctx* ctx, void** p, size_t* have_bytes, size_t need_bytes, bool sync_first) {
-  if (*p && *have_bytes < need_bytes) {
-    if (sync_first) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  const int rc = ensure_buffer(ctx, p, need_bytes);
-  if (!rc) *have_bytes = std::max(*have_bytes, need_bytes);
-  return rc;
-}
-
 // the buffers of the two-stage reductions below: partial[B][K][nblk] and sums[B][K]
 int ensure_sums(pdeopt_ctx* ctx, int K, int nblk) {
   Sens& s = *ctx->sens;

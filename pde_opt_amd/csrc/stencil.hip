@@ -601,16 +601,7 @@ int rk4_loopback_advance(pdeopt_ctx* ctx, double dt, int64_t n) {
     if ((rc = halo_pack(ctx, 0, nullptr))) return rc;
     // the strip written by substep s (fused pack) is read by substep s + 1 (fused unpack): two buffers
     const size_t bytes = halo_strip_elems(ctx) * ctx->esize;
-    if (ctx->halo_scratch2_bytes < bytes) {  // its own grow-only size: ensure_buffer() keeps any existing pointer
-      if (ctx->halo_scratch2) {
-        PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->halo_scratch2);
-        ctx->halo_scratch2 = nullptr;
-        ctx->halo_scratch2_bytes = 0;
-      }
-      if ((rc = ensure_buffer(ctx, &ctx->halo_scratch2, bytes))) return rc;
-      ctx->halo_scratch2_bytes = bytes;
-    }
+    if ((rc = grow_device_buffer(ctx, &ctx->halo_scratch2, &ctx->halo_scratch2_bytes, bytes, /*sync_first=*/true))) return rc;
     void* cur = ctx->halo_scratch;
     void* nxt = ctx->halo_scratch2;
     for (int64_t s = 0; s < n && !rc; ++s) {
@@ -744,12 +735,7 @@ int tsit5_trial_t(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol
   if (err) {
     double* part = nullptr;
     const size_t need = sizeof(double) * kErrBlocks * ctx->prob.batch;
-    if (ctx->red_cap < need) {
-      if (ctx->red_dev) (void)hipFree(ctx->red_dev);
-      ctx->red_dev = nullptr;
-      PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->red_dev, need));
-      ctx->red_cap = need;
-    }
+    if ((rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false))) return rc;
     part = ctx->red_dev;
     LinComb<T> lc{};
     lc.y = (const T*)ctx->Y;
@@ -809,13 +795,7 @@ int tsit5_dense(pdeopt_ctx* ctx, double theta, double dt, int env_first, int env
 // FSAL slope of environment b *= ratio[b] (its step size changed between two per-environment trials)
 int tsit5_rescale_fsal(pdeopt_ctx* ctx, const double* ratio) {
   const size_t need = sizeof(double) * (size_t)ctx->prob.batch;
-  if (ctx->red_cap < need) {
-    if (ctx->red_dev) (void)hipFree(ctx->red_dev);
-    ctx->red_dev = nullptr;
-    ctx->red_cap = 0;
-    PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->red_dev, need));
-    ctx->red_cap = need;
-  }
+  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false)) return rc;
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->red_dev, ratio, need, hipMemcpyHostToDevice, ctx->stream));
   const int64_t ee = (int64_t)ctx->env_elems;
   const dim3 grid((unsigned)std::min<int64_t>((ee + 255) / 256, 1024), ctx->prob.batch);

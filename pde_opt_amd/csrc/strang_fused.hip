@@ -683,13 +683,7 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
   if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
   // one complex field per PAIR of environments, or per environment when their implicit operators differ
   const size_t cwork_need = (size_t)cells * (ctx->imex_per_env ? (size_t)p.batch : (size_t)((p.batch + 1) / 2)) * sizeof(Cx<T>);
-  if (sf.cwork && sf.cwork_bytes < cwork_need) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(sf.cwork);
-    sf.cwork = nullptr;
-  }
-  if ((rc = ensure_buffer(ctx, &sf.cwork, cwork_need))) return rc;
-  sf.cwork_bytes = std::max(sf.cwork_bytes, cwork_need);
+  if ((rc = grow_device_buffer(ctx, &sf.cwork, &sf.cwork_bytes, cwork_need, /*sync_first=*/true))) return rc;
   if (!sf.imex_valid || sf.imex_dt != dt || sf.imex_A != ctx->imex_A || sf.imex_per_env != ctx->imex_per_env) {
     // 1 / ((1 + A dt fourier_symbol) nx ny): solvers.py:62-63 with the 1/N of the inverse folded in
     const AuxField& a = ctx->aux[PDEOPT_AUX_IMEX_SYMBOL];

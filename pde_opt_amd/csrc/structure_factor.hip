@@ -160,14 +160,7 @@ int structure_factor_t(pdeopt_ctx* ctx, const SkGrid& g, int env_first, int env_
     return fail(ctx, PDEOPT_ESTATE, "structure_factor: the transform's half spectrum has %lld cells, expected %lld", (long long)hc,
                 (long long)g.rows * g.nh);
   const size_t n_out = (size_t)nb * env_count, need = sizeof(double) * n_out * (size_t)(1 + blocks);
-  if (ctx->sk_cap < need) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->sk_dev) (void)hipFree(ctx->sk_dev);
-    ctx->sk_dev = nullptr;
-    ctx->sk_cap = 0;
-    PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sk_dev, need));
-    ctx->sk_cap = need;
-  }
+  if ((rc = grow_device_buffer(ctx, (void**)&ctx->sk_dev, &ctx->sk_cap, need, /*sync_first=*/true))) return rc;
   SkArgs<T> a{};
   a.c = static_cast<const C2<T>*>(half) + (int64_t)env_first * hc;
   a.ta = ctx->sk_tab_dev;

@@ -26,6 +26,7 @@ from typing import Any, Dict, Sequence, Union
 import numpy as np
 
 from . import _lib as L
+from . import diagnostics as D
 from .utils import prepare_solver_params
 
 OBSERVABLE_NAMES = ("norm", "e_kin", "e_pot", "e_int", "l_z", "x2", "y2")
@@ -113,42 +114,18 @@ def equation_weights(eqs, t: float = 0.0):
 
 
 def _states(model, state):
-    y = np.asarray(state)
-    if np.iscomplexobj(y):
-        raise ValueError("complex states are stored as (..., 2) real/imag pairs")
-    if y.dtype not in (np.float32, np.float64):
-        y = y.astype(np.float64)
-    want = tuple(model.domain.points) + (2,)
-    if y.ndim not in (3, 4) or tuple(y.shape[-3:]) != want:
-        raise ValueError(f"state of shape {y.shape}: expected {want} or (B,) + that")
-    return (y[None], True) if y.ndim == 3 else (y, False)
+    return D.batch_states(model, state, trailing=(2,), complex_message="complex states are stored as (..., 2) real/imag pairs")
 
 
 def _equations(model, parameters, batch):
-    plist = [parameters] if isinstance(parameters, dict) else list(parameters)
-    if len(plist) not in (1, batch):
-        raise ValueError(f"{len(plist)} parameter sets for {batch} states: one dict, or one per state")
-    return [model.equation_type(domain=model.domain, **p) for p in plist]
+    return [model.equation_type(domain=model.domain, **p) for p in D.parameter_sets(parameters, batch)]
 
 
 def _load(model, eqs, solver, yb, t, t_end):
     """the model's engine configured for ``eqs`` (one: shared by the batch; else one per environment) and holding
     the states ``yb``"""
-    if model._engine is None:
-        from .engine import HipEngine
-
-        model._engine = HipEngine(model.device)
-    eng = model._engine
-    eq0 = eqs[0]
-    eng.configure(dtype=yb.dtype, batch=yb.shape[0], **eq0._engine_problem())
-    if len(eqs) == 1:
-        eq0._engine_upload(eng, t, t_end)
-    else:
-        type(eq0)._engine_upload_batch(eng, eqs, t, t_end)
-    if solver is not None:
-        solver.configure_engine(eng, eq0)
-    eng.set_state(yb)
-    return eng
+    batch = (lambda eng: type(eqs[0])._engine_upload_batch(eng, eqs, t, t_end)) if len(eqs) > 1 else None
+    return D.load(model, eqs, solver, yb, t, t_end, upload=batch)
 
 
 def observables(model, parameters: Union[Dict[str, Any], Sequence[Dict[str, Any]]], state, t: float = 0.0) -> GpeObservables:
@@ -200,3 +177,21 @@ def ground_state(model, parameters, y0, dt, tol=1e-8, max_steps=100_000, check_e
     steps[~converged] = done
     state = eng.get_state()
     return GroundState(state[0] if single else state, obs, steps, converged, np.stack(history))
+
+
+def _reward(env, eng, eqs, eq0):
+    """``("gpe", name)``: an observable of the GPE state, summed on the device (64 bytes per environment come back); the
+    potential is the one a substep starting at the end of this step would use, energy and mu are in the frame of the
+    step's end: Omega(step_dt) of an equation with an omega_rate"""
+    from .pde_env import _ScalarControlBatch
+
+    if isinstance(eqs, _ScalarControlBatch):
+        omega, kappa = equation_weights([eq0], float(env.step_dt))
+        if eqs.name == "omega":
+            omega = np.asarray(eqs.values, dtype=np.float64)
+    else:
+        omega, kappa = equation_weights(eqs, float(env.step_dt))
+    return GpeObservables.from_raw(eng.gpe_observables(float(env.step_dt)), omega, kappa)[env.device_reward[1]]
+
+
+DEVICE_REWARD = D.DeviceReward(OBSERVABLE_NAMES + DERIVED_NAMES, reject_unsupported, _reward)

@@ -22,6 +22,7 @@ from typing import Any, Callable, Dict, Optional, Sequence, Type
 import numpy as np
 
 from . import _lib as L
+from . import gpe_observables, phase_field_observables, structure_factor
 from .engine import HipEngine
 from .integrate import diffeqsolve
 from .numerics import domains
@@ -36,6 +37,11 @@ if HAVE_GYMNASIUM:  # pragma: no cover
 
     if "PDEEnv-v0" not in registry:
         register(id="PDEEnv-v0", entry_point="pde_opt_amd.pde_env:PDEEnv")
+
+
+# device_reward=(kind, name): the diagnostics summed on the device
+_TUPLE_REWARDS = {"gpe": gpe_observables.DEVICE_REWARD, "phase_field": phase_field_observables.DEVICE_REWARD,
+                  "structure_factor": structure_factor.DEVICE_REWARD}
 
 
 class PDEEnv(EnvBase):
@@ -256,10 +262,9 @@ class _EnvShard:
 
         t_begin = time.perf_counter()
         env, eng = self.env, self.engine
-        if isinstance(env.device_reward, tuple) and env.device_reward[0] == "phase_field":
-            from .phase_field_observables import check_equation
-
-            check_equation(eqs[0])  # derivs, closures: refused before the engine is touched
+        kind = _TUPLE_REWARDS.get(env.device_reward[0]) if isinstance(env.device_reward, tuple) else None
+        if kind is not None and kind.precheck is not None:
+            kind.precheck(eqs[0])
         eq0 = self._configure(eqs)
         type(eq0)._engine_upload_batch(eng, eqs, 0.0, env.step_dt)
         solver = env.solver_type(**prepare_solver_params(env.solver_type, env.solver_parameters, eq0))
@@ -272,34 +277,8 @@ class _EnvShard:
         if rem > 0:
             eng.advance(solver.integrator, rem, 1, n_full * env.numeric_dt)
         rewards = None
-        if isinstance(env.device_reward, tuple) and env.device_reward[0] == "gpe":
-            # ("gpe", name): an observable of the GPE state, summed on the device (64 bytes per environment come back);
-            # the potential is the one a substep starting at the end of this step would use
-            from .gpe_observables import GpeObservables, equation_weights
-
-            # energy and mu in the frame of the step's end: Omega(step_dt) of an equation with an omega_rate
-            if isinstance(eqs, _ScalarControlBatch):
-                omega, kappa = equation_weights([eq0], float(env.step_dt))
-                if eqs.name == "omega":
-                    omega = np.asarray(eqs.values, dtype=np.float64)
-            else:
-                omega, kappa = equation_weights(eqs, float(env.step_dt))
-            rewards = GpeObservables.from_raw(eng.gpe_observables(float(env.step_dt)), omega, kappa)[env.device_reward[1]]
-        elif isinstance(env.device_reward, tuple) and env.device_reward[0] == "phase_field":
-            # ("phase_field", name): a free-energy observable of the state after the step, summed on the device with the
-            # per-environment kappa and coefficients the engine carries (64 bytes per environment come back)
-            from .phase_field_observables import PhaseFieldObservables, volume_of
-
-            rewards = PhaseFieldObservables.from_raw(eng.pf_observables(), volume_of(env.domain))[env.device_reward[1]]
-        elif isinstance(env.device_reward, tuple) and env.device_reward[0] == "structure_factor":
-            # ("structure_factor", name): the coarsening length, a moment of S(k) or the variance of the state after the
-            # step, transformed and binned on the device (n_bins * 8 bytes per environment come back); the shell tables
-            # travel once per shard engine
-            from . import structure_factor as skm
-
-            tabs = skm.shell_tables(env.domain)
-            skm.upload_tables(eng, tabs)
-            rewards = skm.from_engine(eng, tabs)[env.device_reward[1]]
+        if kind is not None:
+            rewards = kind.evaluate(env, eng, eqs, eq0)
         elif isinstance(env.device_reward, tuple):
             # ("vortices", amp_thresh, tol): rl_utils.detect_vortices' num_vortices per environment, counted on the
             # device (pde_opt/rl_utils.py:19-84): 24 bytes per environment cross PCIe instead of the wavefunction
@@ -410,24 +389,11 @@ class VectorPDEEnv:
             raise ValueError("observations_on_device needs device_observation=(lo, hi)")
         if device_observation is not None and isinstance(device_observation[0], str) and device_observation[0] != "probes":
             raise ValueError(f"unknown device observation {device_observation[0]!r}")
-        if isinstance(device_reward, tuple) and device_reward[0] == "gpe":
-            from .gpe_observables import DERIVED_NAMES, OBSERVABLE_NAMES, reject_unsupported
-
-            if len(device_reward) != 2 or device_reward[1] not in OBSERVABLE_NAMES + DERIVED_NAMES:
-                raise ValueError(f"unknown device reward {device_reward!r} (\"gpe\" takes one of {OBSERVABLE_NAMES + DERIVED_NAMES})")
-            reject_unsupported(equation_type)
-        elif isinstance(device_reward, tuple) and device_reward[0] == "phase_field":
-            from . import phase_field_observables as pfo
-
-            if len(device_reward) != 2 or device_reward[1] not in pfo.REWARD_NAMES:
-                raise ValueError(f"unknown device reward {device_reward!r} (\"phase_field\" takes one of {pfo.REWARD_NAMES})")
-            pfo.reject_unsupported(equation_type)
-        elif isinstance(device_reward, tuple) and device_reward[0] == "structure_factor":
-            from . import structure_factor as skm
-
-            if len(device_reward) != 2 or device_reward[1] not in skm.REWARD_NAMES:
-                raise ValueError(f"unknown device reward {device_reward!r} (\"structure_factor\" takes one of {skm.REWARD_NAMES})")
-            skm.reject_unsupported(equation_type)
+        if isinstance(device_reward, tuple) and device_reward[0] in _TUPLE_REWARDS:
+            kind = _TUPLE_REWARDS[device_reward[0]]
+            if len(device_reward) != 2 or device_reward[1] not in kind.names:
+                raise ValueError(f"unknown device reward {device_reward!r} (\"{device_reward[0]}\" takes one of {kind.names})")
+            kind.reject(equation_type)
         elif isinstance(device_reward, tuple) and device_reward[0] != "vortices":
             raise ValueError(f"unknown device reward {device_reward[0]!r}")
         if isinstance(device_reward, str) and device_reward not in self._RED:

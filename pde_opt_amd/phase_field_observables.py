@@ -27,9 +27,9 @@ from typing import Any, Dict, Sequence, Union
 import numpy as np
 
 from . import _lib as L
+from . import diagnostics as D
 from . import fit
 from .numerics import closures as CLS
-from .utils import prepare_solver_params
 
 RAW_NAMES = ("mass", "u2", "f_bulk", "f_grad", "mu", "mu2", "diss", "nonfinite")
 DERIVED_NAMES = ("free_energy", "mean", "mu_mean", "mu_variance", "dissipation", "nonfinite")
@@ -138,22 +138,8 @@ def check_equation(eq) -> None:
 
 # ---- PDEModel.free_energy / free_energy_trace ----------------------------------------------------------------------------
 
-def _states(model, state):
-    y = np.asarray(state)
-    if y.dtype not in (np.float32, np.float64):
-        y = y.astype(np.float64)
-    want = tuple(model.domain.points)
-    nd = len(want)
-    if y.ndim not in (nd, nd + 1) or tuple(y.shape[-nd:]) != want:
-        raise ValueError(f"state of shape {y.shape}: expected {want} or (B,) + that")
-    return (y[None], True) if y.ndim == nd else (y, False)
-
-
 def _equations(model, parameters, batch):
-    plist = [parameters] if isinstance(parameters, dict) else list(parameters)
-    if len(plist) not in (1, batch):
-        raise ValueError(f"{len(plist)} parameter sets for {batch} states: one dict, or one per state")
-    eqs = [model.equation_type(domain=model.domain, **fit.plain(p)) for p in plist]
+    eqs = [model.equation_type(domain=model.domain, **fit.plain(p)) for p in D.parameter_sets(parameters, batch)]
     for eq in eqs:
         check_equation(eq)
     structure = {(e._mu_desc.kind, e._mu_desc.flags, len(e._mu_desc.coef), e._mob_desc.kind, e._mob_desc.flags, len(e._mob_desc.coef))
@@ -165,29 +151,19 @@ def _equations(model, parameters, batch):
 
 
 def _load(model, eqs, solver, yb, t0=0.0, t1=None):
-    """the model's engine configured for ``eqs`` (one: shared by the batch; else one per environment) holding ``yb``"""
-    if model._engine is None:
-        from .engine import HipEngine
-
-        model._engine = HipEngine(model.device)
-    eng = model._engine
-    eq0 = eqs[0]
-    eng.configure(dtype=yb.dtype, batch=yb.shape[0], **eq0._engine_problem())
-    eq0._engine_upload(eng, t0, t1)
-    if solver is not None:
-        solver.configure_engine(eng, eq0)
+    """``diagnostics.load`` with the per-environment kappa and coefficients of ``eqs`` where there is one per environment"""
+    per_env = None
     if len(eqs) > 1:
         probs = [e._engine_problem() for e in eqs]
-        eng.set_env_params(0, kappa=[p["kappa"] for p in probs], mu_coef=[p["mu"].coef for p in probs],
-                           mob_coef=[p["mob"].coef for p in probs])
-    eng.set_state(yb)
-    return eng
+        per_env = lambda eng: eng.set_env_params(0, kappa=[p["kappa"] for p in probs], mu_coef=[p["mu"].coef for p in probs],
+                                                 mob_coef=[p["mob"].coef for p in probs])
+    return D.load(model, eqs, solver, yb, t0, t1, per_env=per_env)
 
 
 def free_energy(model, parameters: Union[Dict[str, Any], Sequence[Dict[str, Any]]], state) -> PhaseFieldObservables:
     """``PDEModel.free_energy``"""
     reject_unsupported(model.equation_type)
-    yb, _ = _states(model, state)
+    yb, _ = D.batch_states(model, state)
     eqs = _equations(model, parameters, yb.shape[0])
     eng = _load(model, eqs, None, yb)
     return PhaseFieldObservables.from_raw(eng.pf_observables(), volume_of(model.domain))
@@ -195,31 +171,20 @@ def free_energy(model, parameters: Union[Dict[str, Any], Sequence[Dict[str, Any]
 
 def free_energy_trace(model, parameters, y0, ts, solver_parameters=None, dt0=1e-6) -> PhaseFieldObservables:
     """``PDEModel.free_energy_trace``"""
-    from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral
-
     reject_unsupported(model.equation_type)
-    if model.solver_type not in (Euler, RK4, SemiImplicitFourierSpectral):
-        raise NotImplementedError(f"free_energy_trace steps with Euler, RK4 or SemiImplicitFourierSpectral (constant steps), "
-                                  f"not {getattr(model.solver_type, '__name__', model.solver_type)}")
-    if not isinstance(parameters, dict):
-        raise ValueError("free_energy_trace runs the solve of PDEModel.solve: one parameter dict for the batch")
-    yb, _ = _states(model, y0)
-    eq = _equations(model, parameters, yb.shape[0])[0]
-    ts = np.asarray(ts, dtype=np.float64)
-    if ts.ndim != 1 or len(ts) < 1:
-        raise ValueError("ts is a non-empty 1-D sequence of save times")
-    t0, t1, dt = float(ts[0]), float(ts[-1]), float(dt0)
+    rows = D.trace_on_step_edges(
+        model, parameters, y0, ts, solver_parameters, dt0, name="free_energy_trace",
+        why="the energy of a linear interpolation of states is not an interpolation of energies",
+        states=lambda y: D.batch_states(model, y)[0], equation=lambda yb: _equations(model, parameters, yb.shape[0])[0],
+        equation_first=True, read=lambda eng: eng.pf_observables())  # 64 bytes per environment come back
+    return PhaseFieldObservables.from_raw(rows, volume_of(model.domain))
 
-    def on_edges(q, theta):
-        if theta is not None:
-            raise ValueError(f"save point ts[{q}] = {ts[q]!r} lies inside a step of dt0 = {dt!r} (at {theta:.6g} of it): the energy "
-                             "of a linear interpolation of states is not an interpolation of energies; put ts on step edges "
-                             "(ts[0] + k dt0, and ts[-1])")
 
-    fit.walk_save_points(t0, t1, dt, ts, lambda *a: None, lambda: None, on_edges)  # dry run: refuse before an engine exists
-    solver = model.solver_type(**prepare_solver_params(model.solver_type, solver_parameters or {}, eq))
-    eng = _load(model, [eq], solver, yb, t0, t1)
-    rows = []
-    fit.walk_save_points(t0, t1, dt, ts, lambda h, n, t: eng.advance(solver.integrator, h, n, t), lambda: None,
-                         lambda q, theta: rows.append(eng.pf_observables()))  # 64 bytes per environment come back
-    return PhaseFieldObservables.from_raw(np.stack(rows), volume_of(model.domain))
+def _reward(env, eng, eqs, eq0):
+    """``("phase_field", name)``: a free-energy observable of the state after the step, summed on the device with the
+    per-environment kappa and coefficients the engine carries (64 bytes per environment come back)"""
+    return PhaseFieldObservables.from_raw(eng.pf_observables(), volume_of(env.domain))[env.device_reward[1]]
+
+
+# precheck: derivs and closures of the equation OBJECT, refused before the engine is touched
+DEVICE_REWARD = D.DeviceReward(REWARD_NAMES, reject_unsupported, _reward, precheck=check_equation)

@@ -27,8 +27,8 @@ from typing import Tuple
 import numpy as np
 
 from . import _lib as L
+from . import diagnostics as D
 from . import fit
-from .utils import prepare_solver_params
 
 REWARD_NAMES = ("length", "k1", "k2", "variance")
 MAX_BINS = 4096  # the four waves' shell arrays of the binning kernel fit in LDS up to here
@@ -150,16 +150,8 @@ def reject_unsupported(equation_type) -> None:
 
 
 def _states(model, state) -> np.ndarray:
-    y = np.asarray(state)
-    if np.iscomplexobj(y):
-        raise ValueError("the structure factor is that of a real field, got a complex state")
-    if y.dtype not in (np.float32, np.float64):
-        y = y.astype(np.float64)
-    want = tuple(model.domain.points)
-    nd = len(want)
-    if y.ndim not in (nd, nd + 1) or tuple(y.shape[-nd:]) != want:
-        raise ValueError(f"state of shape {y.shape}: expected {want} or (B,) + that")
-    return np.ascontiguousarray(y[None] if y.ndim == nd else y)
+    return D.batch_states(model, state, complex_message="the structure factor is that of a real field, got a complex state",
+                          contiguous=True)[0]
 
 
 def from_engine(eng, tabs: ShellTables, rows=None) -> StructureFactor:
@@ -180,11 +172,7 @@ def structure_factor(model, state) -> StructureFactor:
     code = _equation_code(model.equation_type)
     tabs = shell_tables(model.domain)
     yb = _states(model, state)
-    if model._engine is None:
-        from .engine import HipEngine
-
-        model._engine = HipEngine(model.device)
-    eng = model._engine
+    eng = D.engine_of(model)
     n, h = tuple(model.domain.points), tuple(model.domain.dx)
     extra = dict(nz=n[2], hz=h[2]) if len(n) == 3 else {}
     eng.configure(equation=code, dtype=yb.dtype, nx=n[0], ny=n[1], batch=yb.shape[0], hx=h[0], hy=h[1], **extra)
@@ -195,34 +183,28 @@ def structure_factor(model, state) -> StructureFactor:
 
 def structure_factor_trace(model, parameters, y0, ts, solver_parameters=None, dt0=1e-6) -> StructureFactor:
     """``PDEModel.structure_factor_trace``"""
-    from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral
-    from .phase_field_observables import _load
-
     reject_unsupported(model.equation_type)
-    if model.solver_type not in (Euler, RK4, SemiImplicitFourierSpectral):
-        raise NotImplementedError(f"structure_factor_trace steps with Euler, RK4 or SemiImplicitFourierSpectral (constant steps), "
-                                  f"not {getattr(model.solver_type, '__name__', model.solver_type)}")
-    if not isinstance(parameters, dict):
-        raise ValueError("structure_factor_trace runs the solve of PDEModel.solve: one parameter dict for the batch")
-    tabs = shell_tables(model.domain)
-    yb = _states(model, y0)
-    ts = np.asarray(ts, dtype=np.float64)
-    if ts.ndim != 1 or len(ts) < 1:
-        raise ValueError("ts is a non-empty 1-D sequence of save times")
-    t0, t1, dt = float(ts[0]), float(ts[-1]), float(dt0)
 
-    def on_edges(q, theta):
-        if theta is not None:
-            raise ValueError(f"save point ts[{q}] = {ts[q]!r} lies inside a step of dt0 = {dt!r} (at {theta:.6g} of it): the spectrum "
-                             "of a linear interpolation of states is not the state's at that time; put ts on step edges "
-                             "(ts[0] + k dt0, and ts[-1])")
+    def states(y):
+        shell_tables(model.domain)  # the grid is looked at before the state
+        return _states(model, y)
 
-    fit.walk_save_points(t0, t1, dt, ts, lambda *a: None, lambda: None, on_edges)  # dry run: refuse before an engine exists
-    eq = model.equation_type(domain=model.domain, **fit.plain(parameters))
-    solver = model.solver_type(**prepare_solver_params(model.solver_type, solver_parameters or {}, eq))
-    eng = _load(model, [eq], solver, yb, t0, t1)
+    rows = D.trace_on_step_edges(
+        model, parameters, y0, ts, solver_parameters, dt0, name="structure_factor_trace",
+        why="the spectrum of a linear interpolation of states is not the state's at that time", states=states,
+        equation=lambda yb: model.equation_type(domain=model.domain, **fit.plain(parameters)), equation_first=False,
+        prepare=lambda eng: upload_tables(eng, shell_tables(model.domain)),
+        read=lambda eng: eng.structure_factor())  # n_bins * 8 bytes per environment come back
+    return from_engine(None, shell_tables(model.domain), rows)
+
+
+def _reward(env, eng, eqs, eq0):
+    """``("structure_factor", name)``: the coarsening length, a moment of S(k) or the variance of the state after the
+    step, transformed and binned on the device (n_bins * 8 bytes per environment come back); the shell tables travel
+    once per shard engine"""
+    tabs = shell_tables(env.domain)
     upload_tables(eng, tabs)
-    rows = []
-    fit.walk_save_points(t0, t1, dt, ts, lambda h, n, t: eng.advance(solver.integrator, h, n, t), lambda: None,
-                         lambda q, theta: rows.append(eng.structure_factor()))  # n_bins * 8 bytes per environment come back
-    return from_engine(eng, tabs, np.stack(rows))
+    return from_engine(eng, tabs)[env.device_reward[1]]
+
+
+DEVICE_REWARD = D.DeviceReward(REWARD_NAMES, reject_unsupported, _reward)
