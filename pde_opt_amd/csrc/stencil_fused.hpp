@@ -239,6 +239,26 @@ __device__ __forceinline__ Vec flux_divergence(const ClosureSpec& ms, const T* _
   return k;
 }
 
+// ... and for ONE cell, given mu and u at the cell and at its four neighbours: the same face values (face_flux), the
+// same rounded product dFy rhy (div_y) and the same single contraction (div_sum), so the bits are flux_divergence's
+template <typename T, int CL>
+__device__ __forceinline__ T flux_divergence_cell(const ClosureSpec& ms, const T* __restrict__ mcoef, T m_dn, T m_c, T m_up, T ml,
+                                                  T mr, T u_dn, T u_c, T u_up, T ul, T ur, T rhx, T rhy) {
+  const T d_dn = eval_mob<T, CL>(ms, mcoef, u_dn), d_c = eval_mob<T, CL>(ms, mcoef, u_c), d_up = eval_mob<T, CL>(ms, mcoef, u_up);
+  const T dl = eval_mob<T, CL>(ms, mcoef, ul), dr = eval_mob<T, CL>(ms, mcoef, ur);
+  const T fy_lo = face_flux<T>(dl, d_c, ml, m_c, rhy), fy_hi = face_flux<T>(d_c, dr, m_c, mr, rhy);
+  T dy;
+  {
+#if PDEOPT_FLUX_PIN >= 3
+#pragma clang fp contract(off)
+#endif
+    dy = (fy_hi - fy_lo) * rhy;
+  }
+  const T fx_hi = face_flux<T>(d_c, d_up, m_c, m_up, rhx);
+  const T fx_lo = face_flux<T>(d_dn, d_c, m_dn, m_c, rhx);
+  return div_sum<T>(fx_hi - fx_lo, rhx, dy);
+}
+
 template <typename T, int TX>
 constexpr size_t fused_lds_bytes() {
   constexpr int V = VecOf<T>::V;

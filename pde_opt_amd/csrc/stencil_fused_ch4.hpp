@@ -65,7 +65,48 @@ struct Quad4Args {
   const T* nbase[8];
   T* strip;
   int64_t strip_env;
+#ifdef PDEOPT_CH4_STAMPS
+  unsigned long long* stamps;  // PROFILING BUILD ONLY (tools/ch4_phase_profile.py): kCh4StampSlots clock values per wave
+#endif
 };
+
+// Ragged trips (round 5; profiles/r05_ch4_phase_cycles.txt, r05_ch4_tails_ab.txt; same box, interleaved x 3, env-steps/s
+// on the headline, parent 2021-2033):
+//   stage 1's ring is 560 vectors on 512 helpers: the 48 left over were a second trip of ONE wave while 15 waited.  As
+//   192 single cells on three helper waves (flux_divergence_cell: the vector path's face values)        2046-2056  +1.1 %
+//   ... and each thread's first-trip offset of the mu passes formed once per row length, not per pass  2079-2082  +2.6 %
+//   what the first trip of NT whole vectors leaves of a mu pass (632 / 488 / 268 / 132 vectors) as single cells dealt
+//   over all threads: tile + 3 and tile + 1  2024-2033 (0.0 %), all four passes  2000-2010 (-1.2 %) -- a tail of whole
+//   vectors on 3-10 waves already spreads over the four SIMDs, and 9-16 one-cell chains cost more issue slots than 3-5
+//   four-cell ones.  The split point of every mu pass therefore stays "all whole vectors" (no cell path for them here).
+// The two knobs below exist for the A/B and for the profiling build of the parent algorithm (tools/mkvariant.sh).
+#ifndef PDEOPT_CH4_RING_CELLS
+#define PDEOPT_CH4_RING_CELLS 1  // 0 = what a ring leaves after its full trips as whole vectors on a few lanes
+#endif
+#ifndef PDEOPT_CH4_HOIST
+#define PDEOPT_CH4_HOIST 1  // 0 = every mu pass divides its own first-trip index
+#endif
+
+// Per-phase clock stamps (-DPDEOPT_CH4_STAMPS, tools/mkvariant.sh: a profiling build, never the shipped one -- the
+// default build holds no stamp and no extra argument).  Lane 0 of every wave stores s_memtime at entry, when the wave
+// has finished its own work of a phase (its LDS traffic drained), after the barrier that ends the phase, and after the
+// first trip of the mu passes and rings: slots 0 | 1 + 3 p (done), 2 + 3 p (past the barrier), 3 + 3 p (first trip done)
+// for the phases p = 0..8 = load, mu1, k1, mu2, k2, mu3, k3, mu4, k4 + store.
+constexpr int kCh4StampSlots = 32;
+#ifdef PDEOPT_CH4_STAMPS
+__device__ __forceinline__ void ch4_stamp(unsigned long long* w, const int slot, const bool drain) {
+  __builtin_amdgcn_sched_barrier(0);
+  if (drain) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the wave's LDS reads and writes are done
+  unsigned long long t;
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  if ((threadIdx.x & 63) == 0) w[slot] = t;  // an ordinary (vector) global store by one lane
+}
+#define PDEOPT_CH4_STAMP(slot, drain) ch4_stamp(stamps, (slot), (drain))
+inline unsigned long long* g_ch4_stamps = nullptr;
+#else
+#define PDEOPT_CH4_STAMP(slot, drain) ((void)0)
+#endif
 
 #ifndef PDEOPT_CH4_THREADS
 #define PDEOPT_CH4_THREADS 1024
@@ -124,6 +165,11 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
   const int r0 = ly * RPT;
   const int cvo = lx + HV;
   const bool owner = tid < G::NOWN;  // wave-uniform
+#ifdef PDEOPT_CH4_STAMPS
+  // (a wave-uniform pointer: it lives in scalar registers, the kernel has no vector register to spare)
+  unsigned long long* const stamps = a.stamps + ((int64_t)blockIdx.x * (NT / 64) + __builtin_amdgcn_readfirstlane(tid >> 6)) * kCh4StampSlots;
+#endif
+  PDEOPT_CH4_STAMP(0, false);
 
   // ---- y on tile + 8 -> A, one tile row per wave and trip (stencil_generic.hpp: load_rows_per_wave)
   bool edge_tile = false;  // wave-uniform
@@ -183,7 +229,9 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
     auto wrap_col = [&](int gj) { return HALO ? gj : tile_wrap(gj, g.ny, false); };
     load_rows_per_wave<T, V, PV, NT, G::kRowsA, Vec>(A0 - 8 * P, P, in, ld, i0 - 8, j0 - HV * V, wrap_row, wrap_col, tid);
   }
+  PDEOPT_CH4_STAMP(1, true);
   __syncthreads();
+  PDEOPT_CH4_STAMP(2, false);
 
   constexpr bool FOLD_MU = PDEOPT_PAIR_FOLD_MU && CL == CL_LOGIT1;
   T fA = T(0), fB = T(0), q1 = T(0);
@@ -194,7 +242,14 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
   }
 
   // mu(src) -> M on the tile + H region: rows [-H, TX + H), the NCV vectors of ncv(H) (stage_pair_kernel: mu_pass)
-  auto mu_pass = [&](auto h_c, const T* const src0) {
+  // The first trip's (row, vector column) of a thread depends on NCV alone, and the passes on tile + 7 / 5 and on
+  // tile + 3 / 1 share theirs: one offset each, formed once (o_wide, o_narrow), the pass adds a constant.
+  // (slot: the stamp after the first trip in the profiling build)
+  static_assert(G::ncv(7) == G::ncv(5) && G::ncv(3) == G::ncv(1), "two row lengths among the four mu passes");
+#if PDEOPT_CH4_HOIST
+  const int o_wide = (tid / G::ncv(7)) * P + (tid % G::ncv(7)) * V, o_narrow = (tid / G::ncv(3)) * P + (tid % G::ncv(3)) * V;
+#endif
+  auto mu_pass = [&](auto h_c, const T* const src0, const int slot) {
     constexpr int H = decltype(h_c)::value;
 #if defined(PDEOPT_CH4_ABLATE) && (PDEOPT_CH4_ABLATE & 1)  // TIMING ONLY (tools/mkvariant.sh): no mu passes
     return;
@@ -204,10 +259,18 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
     for (int base0 = 0; base0 < NVEC; base0 += NT) {
       const int idx = base0 + tid;
       if (idx >= NVEC) break;
+#if PDEOPT_CH4_HOIST
+      const int rr = idx / NCV;
+      const int o = base0 == 0 ? (H >= 5 ? o_wide : o_narrow) + (CV0 * V - H * P) : (rr - H) * P + (CV0 + (idx - rr * NCV)) * V;
+      const T* c_ = src0 + o;
+      T* const m_ = M0 + o;
+#else
       const int rr = idx / NCV;
       const int cv = CV0 + (idx - rr * NCV);
       const int r = rr - H;
       const T* c_ = src0 + r * P + cv * V;
+      T* const m_ = M0 + r * P + cv * V;
+#endif
       const Vec c = *reinterpret_cast<const Vec*>(c_);
       const Vec xp = *reinterpret_cast<const Vec*>(c_ + P);
       const Vec xm = *reinterpret_cast<const Vec*>(c_ - P);
@@ -222,7 +285,8 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
         else
           m[e] = eval_mu<T, CL>(a.mu, p.mu, c[e]) - kap * lap_at<T>(c[e], xp[e], xm[e], yp, ym, a.rhx2, a.rhy2);
       }
-      *reinterpret_cast<Vec*>(M0 + r * P + cv * V) = m;
+      *reinterpret_cast<Vec*>(m_) = m;
+      if (base0 == 0) PDEOPT_CH4_STAMP(slot, true);
     }
   };
 
@@ -310,20 +374,39 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
   }
 
   // One of the stages 1..3 after its mu pass: k on the ring of tile + H and on the own cells; w = y + cw k into dst0.
-  auto stage = [&](auto h_c, const T* const src0, T* const dst0, const T cw, const T bw) {
+  auto stage = [&](auto h_c, const T* const src0, T* const dst0, const T cw, const T bw, const int slot) {
     constexpr int H = decltype(h_c)::value;
 #if defined(PDEOPT_CH4_ABLATE) && (PDEOPT_CH4_ABLATE & 2)  // TIMING ONLY: no ring work
     if (false) {
 #else
     if (rw >= 0) {
 #endif
-      for (int idx = rw; idx < G::ring(H); idx += kRingWorkers) {
+      // whole vectors for the full trips (and for a remainder too long for one trip of cells), then what is left
+      // over as single cells on the workers' lanes: 48 vectors = 192 cells for stage 1 of the 32 x 128 tile
+      constexpr int REM = G::ring(H) % kRingWorkers;
+      constexpr bool CELLS = PDEOPT_CH4_RING_CELLS && REM > 0 && REM * V <= kRingWorkers;
+      constexpr int NR1 = CELLS ? G::ring(H) - REM : G::ring(H);
+      for (int idx = rw; idx < NR1; idx += kRingWorkers) {
         int rr, rc;
         ring_coord(h_c, idx, &rr, &rc);
         const Vec k = k_at(src0, rr, rc);
         // y of the ring cell: still in A for stages 1 and 2 (stage 2's dst IS A: read, then overwritten by this thread)
         const Vec yr = H == 2 ? yring3 : *reinterpret_cast<const Vec*>(A0 + rr * P + rc * V);
         *reinterpret_cast<Vec*>(dst0 + rr * P + rc * V) = yr + cw * k;
+        if (idx == rw) PDEOPT_CH4_STAMP(slot, true);
+      }
+      if constexpr (CELLS) {
+        static_assert(H != 2, "stage 3's ring is one trip of whole vectors (yring3)");
+        if (rw < REM * V) {
+          int rr, rc;
+          ring_coord(h_c, NR1 + rw / V, &rr, &rc);
+          const int o = rr * P + rc * V + (rw & (V - 1));
+          const T* mp = M0 + o;
+          const T* up = src0 + o;
+          const T k = flux_divergence_cell<T, CL>(a.mob, p.mob, mp[-P], mp[0], mp[P], mp[-1], mp[1], up[-P], up[0], up[P], up[-1],
+                                                  up[1], a.rhx, a.rhy);
+          dst0[o] = A0[o] + cw * k;
+        }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -343,20 +426,34 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
     }
   };
 
-  mu_pass(std::integral_constant<int, 7>{}, A0);
+  mu_pass(std::integral_constant<int, 7>{}, A0, 6);
+  PDEOPT_CH4_STAMP(4, true);
   __syncthreads();
-  stage(std::integral_constant<int, 6>{}, A0, B0, a.h2, a.h6);  // k1 on tile+6, w2 -> B
+  PDEOPT_CH4_STAMP(5, false);
+  stage(std::integral_constant<int, 6>{}, A0, B0, a.h2, a.h6, 9);  // k1 on tile+6, w2 -> B
+  PDEOPT_CH4_STAMP(7, true);
   __syncthreads();
-  mu_pass(std::integral_constant<int, 5>{}, B0);
+  PDEOPT_CH4_STAMP(8, false);
+  mu_pass(std::integral_constant<int, 5>{}, B0, 12);
+  PDEOPT_CH4_STAMP(10, true);
   __syncthreads();
-  stage(std::integral_constant<int, 4>{}, B0, A0, a.h2, a.h3);  // k2 on tile+4, w3 -> A (over y)
+  PDEOPT_CH4_STAMP(11, false);
+  stage(std::integral_constant<int, 4>{}, B0, A0, a.h2, a.h3, 15);  // k2 on tile+4, w3 -> A (over y)
+  PDEOPT_CH4_STAMP(13, true);
   __syncthreads();
-  mu_pass(std::integral_constant<int, 3>{}, A0);
+  PDEOPT_CH4_STAMP(14, false);
+  mu_pass(std::integral_constant<int, 3>{}, A0, 18);
+  PDEOPT_CH4_STAMP(16, true);
   __syncthreads();
-  stage(std::integral_constant<int, 2>{}, A0, B0, a.dt, a.h3);  // k3 on tile+2, w4 -> B
+  PDEOPT_CH4_STAMP(17, false);
+  stage(std::integral_constant<int, 2>{}, A0, B0, a.dt, a.h3, 21);  // k3 on tile+2, w4 -> B
+  PDEOPT_CH4_STAMP(19, true);
   __syncthreads();
-  mu_pass(std::integral_constant<int, 1>{}, B0);
+  PDEOPT_CH4_STAMP(20, false);
+  mu_pass(std::integral_constant<int, 1>{}, B0, 24);
+  PDEOPT_CH4_STAMP(22, true);
   __syncthreads();
+  PDEOPT_CH4_STAMP(23, false);
 
   // ---- stage 4 on the tile, combine, store
   if (owner) {
@@ -392,6 +489,7 @@ __global__ __launch_bounds__(G::NT, G::kWavesPerSimd) void ch_rk4_quad_kernel(co
       }
     }
   }
+  PDEOPT_CH4_STAMP(25, true);
 }
 
 // whether the single-pass Cahn-Hilliard RK4 kernel covers the configured problem (the default where it applies; PDEOPT_OPT_FUSE_STAGES = 1 keeps the stage pairs)
@@ -439,6 +537,11 @@ int launch_ch_quad_g(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, const v
   const int tiles_i = p.nx / G::TX, tiles_j = p.ny / G::TY;
   const int64_t nblk64 = (int64_t)tiles_i * tiles_j * w.n;
   if (nblk64 > 0x7fffffffLL) return fail(ctx, PDEOPT_EINVAL, "too many tiles");
+#ifdef PDEOPT_CH4_STAMPS
+  if (g_ch4_stamps == nullptr) return fail(ctx, PDEOPT_ESTATE, "profiling build: pdeopt_ch4_set_stamps() first");
+  // one slot set per wave of the whole batch: launches of different environment windows may run side by side
+  s.stamps = g_ch4_stamps + (int64_t)w.lo * tiles_i * tiles_j * (G::NT / 64) * kCh4StampSlots;
+#endif
   const int nblk = (int)nblk64;
   ctx->n_stage_launches++;
   const int cl = classify_closures(p.mu, p.mob);
@@ -478,3 +581,9 @@ inline int launch_ch_quad(pdeopt_ctx* ctx, const Window& w, const HaloIo& io, co
 }
 
 }  // namespace pdeopt
+
+#ifdef PDEOPT_CH4_STAMPS
+// the profiling build's one extra entry point: where the launches that follow store their stamps -- device memory
+// of at least (workgroups of a launch) * (waves per workgroup) * kCh4StampSlots 8-byte words
+extern "C" void pdeopt_ch4_set_stamps(void* buf) { pdeopt::g_ch4_stamps = static_cast<unsigned long long*>(buf); }
+#endif
