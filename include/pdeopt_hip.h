@@ -42,7 +42,9 @@ typedef enum {
   PDEOPT_EFFT = 3,         /* rocFFT error */
   PDEOPT_ENONFINITE = 4,   /* reported by pdeopt_reduce(op = NONFINITE) callers */
   PDEOPT_ENOMEM = 5,
-  PDEOPT_ESTATE = 6        /* call order error (e.g. advance before configure) */
+  PDEOPT_ESTATE = 6,       /* call order error (e.g. advance before configure) */
+  PDEOPT_ENOCONVERGE = -1  /* pdeopt_implicit_advance: a Newton or Krylov iteration ran out of its budget; the state is
+                              the one the failing step started from */
 } pdeopt_status;
 
 typedef enum { PDEOPT_F32 = 0, PDEOPT_F64 = 1 } pdeopt_dtype;
@@ -78,7 +80,10 @@ typedef enum {
   PDEOPT_INT_TSIT5 = 4,   /* diffrax.Tsit5 fixed step (adaptive PID driven from the host)  */
   /* alternating-direction split step of the rotating-frame GPE (GPE2DTSRot.A_terms,
    * gross_pitaevskii.py:122-126; Bao & Wang 2006); new, DESIGN.md section 4.10 defines the step */
-  PDEOPT_INT_STRANG_ROT = 5
+  PDEOPT_INT_STRANG_ROT = 5,
+  /* diffrax.ImplicitEuler with a Newton root-find and lineax.GMRES inside (upstream's notebooks/test_implicit.ipynb):
+   * y1 = y0 + dt f(y1), matrix-free Newton-GMRES; pdeopt_implicit_configure first.  DESIGN.md section 4.21 */
+  PDEOPT_INT_IMPLICIT_EULER = 6
 } pdeopt_integrator;
 
 /* Pointwise closure family standing in for the reference's Python callables mu(u), D(u), R(u)
@@ -786,6 +791,30 @@ int pdeopt_gpe_rot_adjoint_step(pdeopt_ctx* ctx, double dt, const void* psi0_dev
  * a device / host mix of the two blocks, misaligned or overlapping pointers. */
 int pdeopt_gpe_rot_stir_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* psi0_dev, void* lam_dev, double* grad,
                                      double* spot_grad);
+
+/* ---- implicit Euler: matrix-free Newton-GMRES (csrc/implicit.hip) -----------------------------
+ * One step solves G(y) = y - y0 - dt f(y) = 0 per environment, f the finite-difference right-hand side of the periodic
+ * 2-D Cahn-Hilliard or Allen-Cahn equation (closures of the in-kernel family, periodic layout):
+ *   Newton  first iterate y0; stops when rms(G) <= atol + rtol rms(y); at most max_newton linear solves
+ *   linear  (I - dt J_f(y)) delta = -G by GMRES restarted every `restart` (<= 64) iterations, classical Gram-Schmidt
+ *           with one re-orthogonalisation; stops when its residual estimate is <= krylov_rtol ||G||_2; at most
+ *           max_krylov iterations per linear solve
+ * Environments converge independently: a finished one is frozen.  configure allocates the workspace,
+ * (restart + 5) fields of the batch plus the fp64 partial sums, freed with the field buffers; it refuses a workspace that
+ * does not fit in free device memory (the message states the bytes). */
+int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double krylov_rtol, int restart, int max_newton,
+                              int max_krylov);
+/* n_steps implicit Euler steps of size dt from the resident state (step s ends at t0 + (s + 1) dt; both equations are
+ * autonomous).  stats_out (may be NULL): [batch][4] totals over the call -- Newton iterations, Krylov iterations,
+ * operator applications, right-hand-side evaluations of that environment.  A step that does not converge returns
+ * PDEOPT_ENOCONVERGE: the message names the environment, the step and the last residual, and the resident state is the
+ * one that step started from.  Synchronous (the iteration reads its flags back). */
+int pdeopt_implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n_steps, int64_t* stats_out);
+/* out = (I - dt J_f(y)) v for the resident state y: v_host and out_host are whole-batch fields in the problem dtype.
+ * J_f is the exact linearisation of the finite-difference right-hand side:
+ *   Cahn-Hilliard  J v = div( avg(D'(u) v) grad(mu) + avg(D(u)) grad(mu_h'(u) v - kappa lap v) ),  mu = mu_h(u) - kappa lap u
+ *   Allen-Cahn     J v = -R'(u) v m - R(u) (mu_h'(u) v - kappa lap v),                              m = mu_h(u) - kappa lap u */
+int pdeopt_implicit_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* out_host);
 
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);

@@ -36,6 +36,8 @@ from .numerics.functions import (
 from .numerics.shapes import Shape
 from .numerics.solvers import (
     RK4,
+    ImplicitEuler,
+    ImplicitSolveError,
     ConstantStepSize,
     Euler,
     PIDController,
@@ -59,7 +61,7 @@ __all__ = [
     "AllenCahn2DSmoothedBoundaryButlerVolmerConstantCurrent",
     "Domain", "Shape", "LegendrePolynomialExpansion", "DiffusionLegendrePolynomials", "ChemicalPotentialLegendrePolynomials",
     "GaussianSpot", "GaussianSpots",
-    "SemiImplicitFourierSpectral", "StrangSplitting", "Euler", "RK4", "Tsit5",
+    "SemiImplicitFourierSpectral", "StrangSplitting", "Euler", "RK4", "Tsit5", "ImplicitEuler", "ImplicitSolveError",
     "ConstantStepSize", "PIDController", "SaveAt",
     "ClosureDesc", "as_closure", "polynomial", "UnsupportedClosureError", "HipUnavailableError", "PdeoptError",
 ]

@@ -19,6 +19,7 @@ MAX_COEF = 16
 
 # enums (mirror include/pdeopt_hip.h)
 OK, EINVAL, EHIP, EFFT, ENONFINITE, ENOMEM, ESTATE = range(7)
+ENOCONVERGE = -1  # pdeopt_implicit_advance: Newton / Krylov budget exhausted
 F32, F64 = 0, 1
 DERIVS_FD, DERIVS_FOURIER = 0, 1
 EQ_CAHN_HILLIARD, EQ_ALLEN_CAHN, EQ_ADVECTION_DIFFUSION, EQ_GPE = 0, 1, 2, 3
@@ -29,6 +30,8 @@ EQ_ALLEN_CAHN_BV, EQ_ALLEN_CAHN_SBM_BV = 8, 9  # Butler-Volmer kinetics (allen_c
 BV_VOLTAGE, BV_CONSTANT_CURRENT = 0, 1  # mode of pdeopt_set_bv_params
 INT_EULER, INT_RK4, INT_IMEX, INT_STRANG, INT_TSIT5 = 0, 1, 2, 3, 4
 INT_STRANG_ROT = 5  # rotating-frame alternating-direction split step (GPE2DTSRot)
+INT_IMPLICIT_EULER = 6  # matrix-free Newton-GMRES implicit Euler (csrc/implicit.hip)
+IMPLICIT_MAX_RESTART = 64
 CL_POLY, CL_LEGENDRE, CL_JIT = 0, 1, 2
 CL_LOGIT_PRIOR, CL_EXP_WRAP = 1, 2
 CL_SQRT_WRAP = 8  # the Butler-Volmer kernels only
@@ -215,6 +218,9 @@ _SIGNATURES = {
     "pdeopt_sens_set_data": (C.c_int, [_VP, C.c_int, _VP]),
     "pdeopt_sens_accumulate": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
     "pdeopt_sens_contract": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, _VP]),
+    "pdeopt_implicit_configure": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "pdeopt_implicit_advance": (C.c_int, [_VP, C.c_double, C.c_double, C.c_int64, _VP]),
+    "pdeopt_implicit_apply": (C.c_int, [_VP, C.c_double, _VP, _VP]),
     "pdeopt_fieldmu_rhs": (C.c_int, [_VP, _VP, _VP]),
     "pdeopt_fieldmu_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP]),
     "pdeopt_fieldmu_adjoint_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),

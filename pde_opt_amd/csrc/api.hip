@@ -94,6 +94,7 @@ void free_fields(pdeopt_ctx* ctx) {
   strang_fused_destroy(ctx);
   sens_destroy(ctx);
   bv_destroy(ctx);
+  implicit_destroy(ctx);
   sk_drop(ctx);  // the shell tables belong to one grid
   graph_destroy(ctx);
   ctx->tsit5_pending = false;
@@ -818,6 +819,8 @@ int pdeopt_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_
       }
       return PDEOPT_OK;
     }
+    case PDEOPT_INT_IMPLICIT_EULER:
+      return implicit_advance(ctx, t0, dt, n_substeps, nullptr);
     default:
       return fail(ctx, PDEOPT_EINVAL, "unknown integrator %d", integrator);
   }

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libpdeopt_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 
-SOURCES = ["api.hip", "stencil.hip", "reduce.hip", "spectral.hip", "halo.hip", "strang_fused.hip", "comm.hip", "jit.hip", "sens.hip", "fieldmu.hip", "gpe_adjoint.hip", "cnn.hip", "mixer.hip", "gpe_rot.hip", "gpe_obs.hip", "gpe_rot_adjoint.hip", "butler_volmer.hip", "sens_sbm.hip", "pf_obs.hip", "structure_factor.hip"]
+SOURCES = ["api.hip", "stencil.hip", "reduce.hip", "spectral.hip", "halo.hip", "strang_fused.hip", "comm.hip", "jit.hip", "sens.hip", "fieldmu.hip", "gpe_adjoint.hip", "cnn.hip", "mixer.hip", "gpe_rot.hip", "gpe_obs.hip", "gpe_rot_adjoint.hip", "butler_volmer.hip", "sens_sbm.hip", "pf_obs.hip", "structure_factor.hip", "implicit.hip"]
 
 
 def _embed_jit_source() -> None:

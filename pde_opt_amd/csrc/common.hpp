@@ -131,6 +131,7 @@ struct GpeRot;       // tables + work fields of the rotating-frame ADI split ste
 struct GpeObs;       // tables + partial sums of the GPE observables (gpe_obs.hip)
 struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint, frozen or stirred (gpe_rot_adjoint.hip)
 struct BvState;      // parameters, partial sums and voltages of the Butler-Volmer equations (butler_volmer.hip)
+struct Implicit;     // tolerances, Krylov workspace and small systems of the implicit Euler step (implicit.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -262,6 +263,7 @@ struct pdeopt_ctx {
   pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
   pdeopt::GpeRotAdjoint* gpe_rot_stir_adjoint = nullptr;  // the stirred entry point's own (other partial blocks)
   pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; lives and dies with the field buffers
+  pdeopt::Implicit* implicit = nullptr;  // pdeopt_implicit_configure; lives and dies with the field buffers
   // pdeopt_fieldmu_adjoint_step_coef: fp64 partial sums of the mobility's coefficient gradient, one slot per
   // (trajectory, tile, coefficient); lives with the field buffers, zeroed by pdeopt_configure
   double* fieldmu_coef = nullptr;
@@ -511,6 +513,9 @@ bool bv_params_set(const pdeopt_ctx* ctx);  // has pdeopt_set_bv_params been cal
 int sbm_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out);
 inline bool sbm_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM; }
 void sens_destroy(pdeopt_ctx* ctx);
+// implicit.hip: n implicit Euler steps (stats: [batch][4] totals or nullptr); its workspace lives and dies with the field buffers
+int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* stats);
+void implicit_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);
 void strang_fused_destroy(pdeopt_ctx* ctx);
 

@@ -1,0 +1,832 @@
+// Implicit Euler by matrix-free Newton-GMRES (PDEOPT_INT_IMPLICIT_EULER): the counterpart of
+// diffrax.ImplicitEuler with a Newton root-find and lineax.GMRES inside (upstream's notebooks/test_implicit.ipynb), for
+// the periodic 2-D Cahn-Hilliard and Allen-Cahn equations with finite differences.
+//
+// One step solves G(y) = y - y0 - dt f(y) = 0 per environment.
+//   Newton   first iterate y0; G and the fp64 partials of |G|^2, |y|^2 in one pass over f = the forward right-hand side
+//            (launch_rhs); one wave per environment adds the partials and decides: rms(G) <= atol + rtol rms(y) freezes
+//            the environment, otherwise it sets up the linear solve (beta = |G|, the scale -1 / beta of the first
+//            basis vector, the tolerance krylov_rtol beta).
+//   GMRES    (I - dt J_f(y)) delta = -G, restarted every m iterations.  Iteration j:
+//              op        w = v - dt J v, v = scale x (the previous iteration's w, or -G / the restart residual): the
+//                        normalisation of v_j is folded into the read, the kernel stores v_j as it goes by
+//              dots      all j + 1 products <w, v_i> in one launch that reads w once; fp64 partials per workgroup
+//              update    every workgroup adds the partials in one fixed order, w -= sum h_i v_i, partials of |w|^2
+//              dots, update again: classical Gram-Schmidt with one re-orthogonalisation (CGS2)
+//              small     one wave per environment: h_{j+1,j} = |w|, Givens rotations, residual estimate, the flag
+//                        LIN_CONV, 1 / |w| for the next op; the triangular solve when the environment's cycle ends
+//            cycle end  delta (+)= V y_k and, where the linear solve has converged, y += delta, in one launch;
+//            restart    r = -G - (I - dt J) delta for the environments that have not converged (one op on delta).
+// The host reads the B flags back once per iteration (4 B bytes) to know when every environment is done.  Environments
+// run in lockstep but converge independently: every kernel returns at once for a frozen environment (flags != 0), whose
+// vectors are then neither normalised nor updated; an environment's arithmetic does not depend on the batch it is in.
+// No atomics, nothing waits on another workgroup; flags and small systems are written by the one-wave kernels only,
+// which run as launches of their own, so no field kernel reads a word another workgroup of the same launch writes.
+#include <algorithm>
+#include <cmath>
+
+#include "block_sums.hpp"
+#include "closures.hpp"
+#include "common.hpp"
+#include "sens_tile.hpp"
+
+namespace pdeopt {
+
+constexpr int kImpMaxRestart = 64;
+constexpr int kImpCellsPerThread = 8, kImpChunk = 256 * kImpCellsPerThread;  // cells per workgroup of the vector kernels
+constexpr int kImpDotCols = 8;                                                // products per sweep over w's registers
+enum : int { IMP_NEWTON_DONE = 1, IMP_LIN_CONV = 2, IMP_FAIL = 4 };
+
+// per-environment words and small systems on the device, m = restart
+struct ImpSmall {
+  double* part_dot;  // [B][m][nblk]  workgroup partials of <w, v_i>
+  double* part_nrm;  // [B][2][nblk]  workgroup partials of |w|^2 (row 0; Newton: |G|^2) and |y|^2 (row 1)
+  double* hcol;      // [B][m]        the column being built: h_i of pass 1 + pass 2
+  double* R;         // [B][m][m]     the rotated upper triangle, column j at [j][i]
+  double* cs;        // [B][m]
+  double* sn;        // [B][m]
+  double* g;         // [B][m + 1]    the rotated right-hand side
+  double* ycoef;     // [B][m]        solution of the triangular system
+  double* gnorm;     // [B]           |G|_2 of the Newton iterate
+  double* tol;       // [B]           krylov_rtol |G|_2
+  double* vscale;    // [B]           factor the next op applies to its source
+  double* res;       // [B]           last residual: rms(G) after a Newton check, the GMRES estimate inside a linear solve
+  int* flags;        // [B]
+  int* kcols;        // [B]           columns of this cycle's triangular system
+  int* conv_cycle;   // [B]           cycle in which LIN_CONV was set (the cycle-end launch applies delta once)
+  int m, nblk;
+};
+
+struct Implicit {
+  double rtol = 0, atol = 0, krylov_rtol = 0;
+  int restart = 0, max_newton = 0, max_krylov = 0;
+  int B = 0, nblk = 0;
+  int64_t cells = 0;
+  void* fields = nullptr;  // Y0 | G | DELTA | W0 | W1 | V[restart], each [B][cells] in the problem dtype
+  size_t field_bytes = 0, fields_bytes = 0;
+  void* small_blk = nullptr;
+  size_t small_bytes = 0;
+  ImpSmall sm{};
+  int* flags_host = nullptr;  // pinned
+  double* res_host = nullptr;
+};
+
+namespace {
+
+// ---- operator application: w = v - dt J_f(y) v, v = scale[b] x src ------------------------------------------------------
+template <typename T>
+struct ImpOpArgs {
+  const T* y;
+  const T* src;
+  T* vout;              // v as formed (the basis vector v_j); nullptr: not stored
+  T* wout;
+  const double* scale;  // [B] or nullptr (1)
+  const int* flags;     // [B] or nullptr: environments with flags != 0 are skipped
+  const EnvParams<T>* ep;
+  ClosureSpec mu, mob;
+  int nx, ny;
+  T rhx, rhy, rhx2, rhy2;
+  T dt;
+};
+
+// Cahn-Hilliard: J v = div( avg(D'(u) v) grad(mu) + avg(D(u)) grad(mu_h'(u) v - kappa lap v) ), mu = mu_h(u) - kappa lap u:
+// the tangent kernel of sens.hip with one tangent and no coefficient term.  u and v on the tile + 2-cell ring, the four
+// face quantities on the tile + 1-cell ring; mu_h' and D' live in the registers of the thread that forms dmu and dD
+template <typename T>
+__global__ __launch_bounds__(256) void imp_op_ch_kernel(ImpOpArgs<T> a) {
+  __shared__ T su[kR2 * kC2], sv[kR2 * kC2];
+  __shared__ T smu[kR1 * kC1], sD[kR1 * kC1], sdmu[kR1 * kC1], sdD[kR1 * kC1];
+  const int b = blockIdx.z;
+  if (a.flags && a.flags[b]) return;
+  const int tid = threadIdx.x;
+  const int i0 = blockIdx.y * kTR, j0 = blockIdx.x * kTC;
+  const int nx = a.nx, ny = a.ny;
+  const int64_t cells = (int64_t)nx * ny;
+  const EnvParams<T>& ep = a.ep[b];
+  const T kappa = ep.kappa;
+  const T sc = a.scale ? T(a.scale[b]) : T(1);
+  const T* __restrict__ u = a.y + (int64_t)b * cells;
+  const T* __restrict__ s = a.src + (int64_t)b * cells;
+  for (int q = tid; q < kR2 * kC2; q += 256) {
+    const int r = q / kC2, c = q - r * kC2;
+    const int64_t g = (int64_t)wrap_idx(i0 + r - 2, nx) * ny + wrap_idx(j0 + c - 2, ny);
+    su[q] = u[g];
+    sv[q] = sc * s[g];
+  }
+  __syncthreads();
+  for (int q = tid; q < kR1 * kC1; q += 256) {
+    const int r = q / kC1, c = q - r * kC1;
+    const int o = (r + 1) * kC2 + (c + 1);
+    const T uc = su[o], vc = sv[o];
+    const T muh = closure_generic<T>(a.mu, ep.mu, uc);
+    const T D = closure_generic<T>(a.mob, ep.mob, uc);
+    smu[q] = muh - kappa * tile_lap5<T>(su, o, kC2, a.rhx2, a.rhy2);
+    sD[q] = D;
+    sdmu[q] = closure_dc<T>(a.mu, ep.mu, uc, muh) * vc - kappa * tile_lap5<T>(sv, o, kC2, a.rhx2, a.rhy2);
+    sdD[q] = closure_dc<T>(a.mob, ep.mob, uc, D) * vc;
+  }
+  __syncthreads();
+  T* __restrict__ vout = a.vout ? a.vout + (int64_t)b * cells : nullptr;
+  T* __restrict__ wout = a.wout + (int64_t)b * cells;
+  for (int q = tid; q < kTR * kTC; q += 256) {
+    const int r = q / kTC, c = q - r * kTC;
+    const int gi = i0 + r, gj = j0 + c;
+    if (gi >= nx || gj >= ny) continue;
+    const int o = (r + 1) * kC1 + (c + 1);
+    const T fxp = tile_tangent_flux<T>(smu, sD, sdmu, sdD, o, o + kC1, a.rhx);
+    const T fxm = tile_tangent_flux<T>(smu, sD, sdmu, sdD, o - kC1, o, a.rhx);
+    const T fyp = tile_tangent_flux<T>(smu, sD, sdmu, sdD, o, o + 1, a.rhy);
+    const T fym = tile_tangent_flux<T>(smu, sD, sdmu, sdD, o - 1, o, a.rhy);
+    const T jv = (fxp - fxm) * a.rhx + (fyp - fym) * a.rhy;
+    const T v = sv[(r + 2) * kC2 + (c + 2)];
+    const int64_t g = (int64_t)gi * ny + gj;
+    if (vout) vout[g] = v;
+    wout[g] = v - a.dt * jv;
+  }
+}
+
+// Allen-Cahn: J v = -R'(u) v m - R(u) (mu_h'(u) v - kappa lap v), m = mu_h(u) - kappa lap u.  Radius 1: u and v on the
+// tile + 1-cell ring, everything else in registers
+template <typename T>
+__global__ __launch_bounds__(256) void imp_op_ac_kernel(ImpOpArgs<T> a) {
+  __shared__ T su[kR1 * kC1], sv[kR1 * kC1];
+  const int b = blockIdx.z;
+  if (a.flags && a.flags[b]) return;
+  const int tid = threadIdx.x;
+  const int i0 = blockIdx.y * kTR, j0 = blockIdx.x * kTC;
+  const int nx = a.nx, ny = a.ny;
+  const int64_t cells = (int64_t)nx * ny;
+  const EnvParams<T>& ep = a.ep[b];
+  const T kappa = ep.kappa;
+  const T sc = a.scale ? T(a.scale[b]) : T(1);
+  const T* __restrict__ u = a.y + (int64_t)b * cells;
+  const T* __restrict__ s = a.src + (int64_t)b * cells;
+  for (int q = tid; q < kR1 * kC1; q += 256) {
+    const int r = q / kC1, c = q - r * kC1;
+    const int64_t g = (int64_t)wrap_idx(i0 + r - 1, nx) * ny + wrap_idx(j0 + c - 1, ny);
+    su[q] = u[g];
+    sv[q] = sc * s[g];
+  }
+  __syncthreads();
+  T* __restrict__ vout = a.vout ? a.vout + (int64_t)b * cells : nullptr;
+  T* __restrict__ wout = a.wout + (int64_t)b * cells;
+  for (int q = tid; q < kTR * kTC; q += 256) {
+    const int r = q / kTC, c = q - r * kTC;
+    const int gi = i0 + r, gj = j0 + c;
+    if (gi >= nx || gj >= ny) continue;
+    const int o = (r + 1) * kC1 + (c + 1);
+    const T uc = su[o], vc = sv[o];
+    const T muh = closure_generic<T>(a.mu, ep.mu, uc);
+    const T R = closure_generic<T>(a.mob, ep.mob, uc);
+    const T m = muh - kappa * tile_lap5<T>(su, o, kC1, a.rhx2, a.rhy2);
+    const T dmu = closure_dc<T>(a.mu, ep.mu, uc, muh) * vc - kappa * tile_lap5<T>(sv, o, kC1, a.rhx2, a.rhy2);
+    const T dR = closure_dc<T>(a.mob, ep.mob, uc, R) * vc;
+    const T jv = -(dR * m) - R * dmu;
+    const int64_t g = (int64_t)gi * ny + gj;
+    if (vout) vout[g] = vc;
+    wout[g] = vc - a.dt * jv;
+  }
+}
+
+// ---- vector kernels: grid (nblk, B), 256 threads, workgroup blk owns the cells [blk kImpChunk, (blk + 1) kImpChunk) ----
+
+// this thread's cell m of the workgroup's chunk
+__device__ __forceinline__ int64_t imp_cell(int m) {
+  return (int64_t)blockIdx.x * kImpChunk + m * 256 + threadIdx.x;
+}
+
+// Newton residual G = y - y0 - dt f and the partials of |G|^2 and |y|^2
+template <typename T>
+__global__ __launch_bounds__(256) void imp_residual_kernel(const T* __restrict__ y, const T* __restrict__ y0, const T* __restrict__ f,
+                                                         T* __restrict__ G, T dt, int64_t cells, ImpSmall sm) {
+  __shared__ double sh[4];
+  const int b = blockIdx.y;
+  if (sm.flags[b] & (IMP_NEWTON_DONE | IMP_FAIL)) return;
+  const int64_t base = (int64_t)b * cells;
+  double g2 = 0.0, y2 = 0.0;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < cells) {
+      const T yv = y[base + c];
+      const T gv = (yv - y0[base + c]) - dt * f[base + c];
+      G[base + c] = gv;
+      g2 += (double)gv * (double)gv;
+      y2 += (double)yv * (double)yv;
+    }
+  }
+  g2 = block_sum(g2, sh);
+  y2 = block_sum(y2, sh);
+  if (threadIdx.x == 0) {
+    sm.part_nrm[((int64_t)b * 2 + 0) * sm.nblk + blockIdx.x] = g2;
+    sm.part_nrm[((int64_t)b * 2 + 1) * sm.nblk + blockIdx.x] = y2;
+  }
+}
+
+// one wave: the sum of row `row` of an environment's norm partials, in lane 0
+__device__ __forceinline__ double imp_norm_total(const ImpSmall& sm, int b, int row) {
+  const double* p = sm.part_nrm + ((int64_t)b * 2 + row) * sm.nblk;
+  double s = 0.0;
+  for (int q = threadIdx.x; q < sm.nblk; q += 64) s += p[q];
+  return wave_sum(s);
+}
+
+// grid B, one wave: the Newton decision of an environment
+__global__ __launch_bounds__(64) void imp_newton_small_kernel(ImpSmall sm, double cells, double rtol, double atol, double krylov_rtol,
+                                                            int newton_it, int max_newton) {
+  const int b = blockIdx.x;
+  if (sm.flags[b] & (IMP_NEWTON_DONE | IMP_FAIL)) return;
+  const double g2 = imp_norm_total(sm, b, 0), y2 = imp_norm_total(sm, b, 1);
+  if (threadIdx.x != 0) return;
+  const double rms_g = sqrt(g2 / cells), thr = atol + rtol * sqrt(y2 / cells);
+  sm.res[b] = rms_g;
+  sm.tol[b] = thr;  // the host's message quotes it when the budget runs out
+  if (rms_g <= thr) {
+    sm.flags[b] = IMP_NEWTON_DONE;
+  } else if (!(g2 > 0.0) || !isfinite(g2) || newton_it >= max_newton) {
+    sm.flags[b] = IMP_FAIL;  // a residual that is not a number, or the budget of linear solves is spent
+  } else {
+    const double beta = sqrt(g2);
+    sm.gnorm[b] = beta;
+    sm.tol[b] = krylov_rtol * beta;
+    sm.vscale[b] = -1.0 / beta;  // v_0 = -G / |G|
+    sm.g[(int64_t)b * (sm.m + 1)] = beta;
+    sm.kcols[b] = 0;
+    sm.conv_cycle[b] = -1;
+    sm.flags[b] = 0;
+  }
+}
+
+template <typename T>
+struct ImpVecArgs {
+  T* w;          // [B][cells]
+  const T* V;    // [m][B][cells]
+  T* y;          // solution launch
+  T* delta;
+  const T* G;    // restart launch
+  int64_t cells;
+  int B, ncols;  // products of this launch: <w, v_i>, i < ncols
+  int pass;      // update: 0 first Gram-Schmidt pass, 1 the re-orthogonalisation
+  int cycle;
+  ImpSmall sm;
+};
+
+// <w, v_i> for i < ncols: w's cells stay in registers, the basis vectors stream past them kImpDotCols at a time
+template <typename T>
+__global__ __launch_bounds__(256) void imp_dots_kernel(ImpVecArgs<T> a) {
+  __shared__ double red[4][kImpDotCols];
+  const int b = blockIdx.y;
+  if (a.sm.flags[b]) return;
+  const int tid = threadIdx.x;
+  const int64_t cells = a.cells;
+  const T* __restrict__ w = a.w + (int64_t)b * cells;
+  double wv[kImpCellsPerThread];
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    wv[m] = c < cells ? (double)w[c] : 0.0;
+  }
+  for (int i0 = 0; i0 < a.ncols; i0 += kImpDotCols) {
+    double acc[kImpDotCols];
+#pragma unroll
+    for (int q = 0; q < kImpDotCols; ++q) {
+      acc[q] = 0.0;
+      if (i0 + q < a.ncols) {
+        const T* __restrict__ v = a.V + ((int64_t)(i0 + q) * a.B + b) * cells;
+#pragma unroll
+        for (int m = 0; m < kImpCellsPerThread; ++m) {
+          const int64_t c = imp_cell(m);
+          if (c < cells) acc[q] += wv[m] * (double)v[c];
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int q = 0; q < kImpDotCols; ++q) red[tid >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid < kImpDotCols && i0 + tid < a.ncols)
+      a.sm.part_dot[((int64_t)b * a.sm.m + i0 + tid) * a.sm.nblk + blockIdx.x] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    __syncthreads();  // red is written again by the next sweep
+  }
+}
+
+// h_i = the partials of <w, v_i> added in one fixed order (every workgroup forms the same bits); w -= sum h_i v_i; the
+// partial of |w|^2.  Workgroup 0 of the environment records the column for the small system
+template <typename T>
+__global__ __launch_bounds__(256) void imp_update_kernel(ImpVecArgs<T> a) {
+  __shared__ double sh_h[kImpMaxRestart];
+  __shared__ double sh[4];
+  const int b = blockIdx.y;
+  if (a.sm.flags[b]) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nblk = a.sm.nblk;
+  for (int i = wave; i < a.ncols; i += 4) {
+    const double* p = a.sm.part_dot + ((int64_t)b * a.sm.m + i) * nblk;
+    double s = 0.0;
+    for (int q = lane; q < nblk; q += 64) s += p[q];
+    s = wave_sum(s);
+    if (lane == 0) sh_h[i] = s;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && tid < a.ncols) {
+    double* h = a.sm.hcol + (int64_t)b * a.sm.m + tid;
+    *h = a.pass ? *h + sh_h[tid] : sh_h[tid];
+  }
+  const int64_t cells = a.cells;
+  T* __restrict__ w = a.w + (int64_t)b * cells;
+  double wv[kImpCellsPerThread];
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    wv[m] = c < cells ? (double)w[c] : 0.0;
+  }
+  for (int i = 0; i < a.ncols; ++i) {
+    const T* __restrict__ v = a.V + ((int64_t)i * a.B + b) * cells;
+    const double h = sh_h[i];
+#pragma unroll
+    for (int m = 0; m < kImpCellsPerThread; ++m) {
+      const int64_t c = imp_cell(m);
+      if (c < cells) wv[m] -= h * (double)v[c];
+    }
+  }
+  double n2 = 0.0;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < cells) {
+      const T r = (T)wv[m];
+      w[c] = r;
+      n2 += (double)r * (double)r;
+    }
+  }
+  n2 = block_sum(n2, sh);
+  if (tid == 0) a.sm.part_nrm[(int64_t)b * 2 * nblk + blockIdx.x] = n2;
+}
+
+// grid B, one wave: column j of the small system of an environment.  `last`: the cycle ends after this iteration
+// whatever the estimate says (j + 1 = m, or the budget max_krylov is spent)
+__global__ __launch_bounds__(64) void imp_gmres_small_kernel(ImpSmall sm, int j, int cycle, int last) {
+  __shared__ double h[kImpMaxRestart + 1];
+  const int b = blockIdx.x;
+  if (sm.flags[b]) return;
+  const int m = sm.m;
+  const double n2 = imp_norm_total(sm, b, 0);
+  if (threadIdx.x != 0) return;
+  const double hn = sqrt(n2);
+  for (int i = 0; i <= j; ++i) h[i] = sm.hcol[(int64_t)b * m + i];
+  double* const cs = sm.cs + (int64_t)b * m;
+  double* const sn = sm.sn + (int64_t)b * m;
+  double* const g = sm.g + (int64_t)b * (m + 1);
+  double* const Rj = sm.R + ((int64_t)b * m + j) * m;
+  for (int i = 0; i < j; ++i) {
+    const double t = cs[i] * h[i] + sn[i] * h[i + 1];
+    h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1];
+    h[i] = t;
+    Rj[i] = t;
+  }
+  // a zero h_{j+1,j} (the Krylov space is exhausted: the estimate below becomes 0) divides nothing
+  const double den = sqrt(h[j] * h[j] + hn * hn);
+  const double c = den > 0.0 ? h[j] / den : 1.0, s = den > 0.0 ? hn / den : 0.0;
+  Rj[j] = den;
+  cs[j] = c;
+  sn[j] = s;
+  const double gj = g[j];
+  g[j] = c * gj;
+  g[j + 1] = -s * gj;
+  const double est = fabs(s * gj);
+  sm.res[b] = est;
+  sm.kcols[b] = j + 1;
+  const bool conv = est <= sm.tol[b];
+  if (conv) {
+    sm.flags[b] = IMP_LIN_CONV;
+    sm.conv_cycle[b] = cycle;
+  } else {
+    sm.vscale[b] = hn > 0.0 ? 1.0 / hn : 0.0;
+  }
+  if (conv || last) {
+    double* const yk = sm.ycoef + (int64_t)b * m;
+    for (int i = j; i >= 0; --i) {
+      double t = g[i];
+      for (int k = i + 1; k <= j; ++k) t -= sm.R[((int64_t)b * m + k) * m + i] * yk[k];
+      const double d = sm.R[((int64_t)b * m + i) * m + i];
+      yk[i] = d != 0.0 ? t / d : 0.0;
+    }
+  }
+}
+
+// end of a cycle: delta (+)= V y_k; where the environment's linear solve converged in this cycle, y += delta
+template <typename T>
+__global__ __launch_bounds__(256) void imp_solution_kernel(ImpVecArgs<T> a) {
+  __shared__ double sh_y[kImpMaxRestart];
+  const int b = blockIdx.y;
+  const int fl = a.sm.flags[b];
+  if (fl & (IMP_NEWTON_DONE | IMP_FAIL)) return;
+  if ((fl & IMP_LIN_CONV) && a.sm.conv_cycle[b] < a.cycle) return;  // applied when it converged
+  const int k = a.sm.kcols[b];
+  if (threadIdx.x < k) sh_y[threadIdx.x] = a.sm.ycoef[(int64_t)b * a.sm.m + threadIdx.x];
+  __syncthreads();
+  const int64_t cells = a.cells;
+  T* __restrict__ delta = a.delta + (int64_t)b * cells;
+  double d[kImpCellsPerThread];
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    d[m] = (a.cycle > 0 && c < cells) ? (double)delta[c] : 0.0;
+  }
+  for (int i = 0; i < k; ++i) {
+    const T* __restrict__ v = a.V + ((int64_t)i * a.B + b) * cells;
+    const double yi = sh_y[i];
+#pragma unroll
+    for (int m = 0; m < kImpCellsPerThread; ++m) {
+      const int64_t c = imp_cell(m);
+      if (c < cells) d[m] += yi * (double)v[c];
+    }
+  }
+  T* __restrict__ y = a.y + (int64_t)b * cells;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < cells) {
+      const T dv = (T)d[m];
+      delta[c] = dv;
+      if (fl & IMP_LIN_CONV) y[c] += dv;
+    }
+  }
+}
+
+// restart: w holds (I - dt J) delta; w = -G - w is the residual of the linear system, with the partial of its norm
+template <typename T>
+__global__ __launch_bounds__(256) void imp_restart_kernel(ImpVecArgs<T> a) {
+  __shared__ double sh[4];
+  const int b = blockIdx.y;
+  if (a.sm.flags[b]) return;
+  const int64_t cells = a.cells, base = (int64_t)b * cells;
+  double n2 = 0.0;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < cells) {
+      const T r = -a.G[base + c] - a.w[base + c];
+      a.w[base + c] = r;
+      n2 += (double)r * (double)r;
+    }
+  }
+  n2 = block_sum(n2, sh);
+  if (threadIdx.x == 0) a.sm.part_nrm[(int64_t)b * 2 * a.sm.nblk + blockIdx.x] = n2;
+}
+
+__global__ __launch_bounds__(64) void imp_restart_small_kernel(ImpSmall sm, int cycle) {
+  const int b = blockIdx.x;
+  if (sm.flags[b]) return;
+  const double n2 = imp_norm_total(sm, b, 0);
+  if (threadIdx.x != 0) return;
+  const double beta = sqrt(n2);
+  sm.g[(int64_t)b * (sm.m + 1)] = beta;
+  sm.kcols[b] = 0;
+  sm.res[b] = beta;
+  if (beta <= sm.tol[b]) {
+    sm.flags[b] = IMP_LIN_CONV;
+    sm.conv_cycle[b] = cycle;
+  } else {
+    sm.vscale[b] = 1.0 / beta;
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------
+
+template <typename T>
+T* imp_field(const Implicit& s, int which) {
+  return reinterpret_cast<T*>(static_cast<char*>(s.fields) + (size_t)which * s.field_bytes);
+}
+enum { F_Y0 = 0, F_G = 1, F_DELTA = 2, F_W0 = 3, F_W1 = 4, F_V = 5 };
+
+bool implicit_equation(const pdeopt_problem& p) {
+  return (p.equation == PDEOPT_EQ_CAHN_HILLIARD || p.equation == PDEOPT_EQ_ALLEN_CAHN) && p.nz <= 1;
+}
+
+// what the implicit step covers, asked before any launch
+int implicit_check_problem(pdeopt_ctx* ctx) {
+  const pdeopt_problem& p = ctx->prob;
+  if (!implicit_equation(p))
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler covers the periodic 2-D Cahn-Hilliard and Allen-Cahn equations: the 3-D, "
+                                    "smoothed-boundary, Butler-Volmer, advection-diffusion and GPE kernels have no Jacobian action "
+                                    "(equation %d)", p.equation);
+  if (p.derivs != PDEOPT_DERIVS_FD)
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler linearises the finite-difference right-hand side: derivs=\"fd\", not \"fourier\"");
+  if (ctx->halo)
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler needs the periodic layout: its sums run over whole environments, the padded "
+                                    "(decomposed) layout holds a tile of one");
+  if (p.mu.kind == PDEOPT_CL_JIT || p.mob.kind == PDEOPT_CL_JIT)
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler needs closures of the in-kernel family (POLY / LEGENDRE): a run-time-compiled "
+                                    "closure has no derivative to linearise with");
+  return PDEOPT_OK;
+}
+
+int check_implicit(pdeopt_ctx* ctx) {
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  const Implicit* s = ctx->implicit;
+  if (!s) return fail(ctx, PDEOPT_ESTATE, "pdeopt_implicit_configure has not been called");
+  const int rc = implicit_check_problem(ctx);
+  if (rc) return rc;
+  if (s->B != ctx->prob.batch || s->cells != (int64_t)ctx->prob.nx * ctx->prob.ny)
+    return fail(ctx, PDEOPT_ESTATE, "the problem changed shape after pdeopt_implicit_configure: configure the implicit step again");
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return PDEOPT_OK;
+}
+
+template <typename T>
+int launch_op(pdeopt_ctx* ctx, const T* src, T* vout, T* wout, const double* scale, const int* flags, double dt) {
+  const pdeopt_problem& p = ctx->prob;
+  ImpOpArgs<T> a{};
+  a.y = static_cast<const T*>(ctx->Y);
+  a.src = src;
+  a.vout = vout;
+  a.wout = wout;
+  a.scale = scale;
+  a.flags = flags;
+  set_closures<T>(a, ctx, 0);
+  a.nx = p.nx;
+  a.ny = p.ny;
+  set_recip_plain(a, grid_recip(p));
+  a.dt = T(dt);
+  const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, p.batch);
+  if (p.equation == PDEOPT_EQ_ALLEN_CAHN) hipLaunchKernelGGL(imp_op_ac_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(imp_op_ch_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  ctx->n_stage_launches++;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+int read_flags(pdeopt_ctx* ctx) {
+  Implicit& s = *ctx->implicit;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.flags_host, s.sm.flags, (size_t)s.B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+// the budget ran out: put the step's start back, say which environment and how far it got
+int implicit_fail(pdeopt_ctx* ctx, int64_t step, const char* what, int iters) {
+  Implicit& s = *ctx->implicit;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->Y, s.fields, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host, s.sm.res, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host + s.B, s.sm.tol, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  int env = 0;
+  for (int b = 0; b < s.B; ++b)
+    if (!(s.flags_host[b] & (IMP_NEWTON_DONE | IMP_LIN_CONV))) { env = b; break; }
+  return fail(ctx, PDEOPT_ENOCONVERGE, "implicit Euler did not converge: environment %d, step %lld: %s after %d iteration(s), last "
+                                       "residual %.6g (threshold %.6g); the state is the one the step started from",
+              env, (long long)step, what, iters, s.res_host[env], s.res_host[s.B + env]);
+}
+
+// one step y <- the solution of y - y0 - dt f(y) = 0; st: [B][4] counters or nullptr
+template <typename T>
+int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* st) {
+  Implicit& s = *ctx->implicit;
+  const int B = s.B, m = s.restart;
+  const int64_t cells = s.cells;
+  T* const y = static_cast<T*>(ctx->Y);
+  T* const W[2] = {imp_field<T>(s, F_W0), imp_field<T>(s, F_W1)};
+  T* const V = imp_field<T>(s, F_V);
+  const dim3 vgrid(s.nblk, B), sgrid(B);
+  ImpVecArgs<T> va{};
+  va.V = V;
+  va.y = y;
+  va.delta = imp_field<T>(s, F_DELTA);
+  va.G = imp_field<T>(s, F_G);
+  va.cells = cells;
+  va.B = B;
+  va.sm = s.sm;
+  int rc;
+  auto count = [&](int which) {  // the environments the next launch works on
+    if (st)
+      for (int b = 0; b < B; ++b)
+        if (!s.flags_host[b]) st[4 * b + which]++;
+  };
+  auto any_active = [&] {
+    for (int b = 0; b < B; ++b)
+      if (!s.flags_host[b]) return true;
+    return false;
+  };
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.fields, y, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.sm.flags, 0, (size_t)B * sizeof(int), ctx->stream));
+  std::fill(s.flags_host, s.flags_host + B, 0);
+  for (int newton_it = 0;; ++newton_it) {
+    // the environments that are not frozen at the Newton level: LIN_CONV is the only other flag alive here
+    for (int b = 0; b < B; ++b) s.flags_host[b] &= IMP_NEWTON_DONE;
+    count(3);
+    if ((rc = launch_rhs(ctx, whole_batch(ctx), y, ctx->TA, t1))) return rc;
+    hipLaunchKernelGGL(imp_residual_kernel<T>, vgrid, dim3(256), 0, ctx->stream, static_cast<const T*>(y),
+                       static_cast<const T*>(imp_field<T>(s, F_Y0)), static_cast<const T*>(ctx->TA), imp_field<T>(s, F_G), (T)dt, cells, s.sm);
+    hipLaunchKernelGGL(imp_newton_small_kernel, sgrid, dim3(64), 0, ctx->stream, s.sm, (double)cells, s.rtol, s.atol, s.krylov_rtol,
+                       newton_it, s.max_newton);
+    ctx->n_stage_launches += 2;
+    PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+    if ((rc = read_flags(ctx))) return rc;
+    for (int b = 0; b < B; ++b)
+      if (s.flags_host[b] & IMP_FAIL) return implicit_fail(ctx, step, "Newton: rms(G) above atol + rtol rms(y)", newton_it);
+    if (!any_active()) return PDEOPT_OK;
+    count(0);
+    int kit = 0;
+    bool spent = false;
+    for (int cycle = 0;; ++cycle) {
+      if (cycle > 0) {  // the residual of the linear system at the delta so far
+        count(2);
+        if ((rc = launch_op<T>(ctx, va.delta, nullptr, W[1], nullptr, s.sm.flags, dt))) return rc;
+        va.w = W[1];
+        va.cycle = cycle;
+        hipLaunchKernelGGL(imp_restart_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+        hipLaunchKernelGGL(imp_restart_small_kernel, sgrid, dim3(64), 0, ctx->stream, s.sm, cycle);
+        ctx->n_stage_launches += 2;
+        PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+        if ((rc = read_flags(ctx))) return rc;
+      }
+      for (int j = 0; j < m && any_active(); ++j) {
+        const T* src = j == 0 ? (cycle == 0 ? va.G : W[1]) : W[(j - 1) & 1];
+        T* const w = W[j & 1];
+        count(1);
+        count(2);
+        if ((rc = launch_op<T>(ctx, src, V + (int64_t)j * B * cells, w, s.sm.vscale, s.sm.flags, dt))) return rc;
+        va.w = w;
+        va.ncols = j + 1;
+        for (int pass = 0; pass < 2; ++pass) {
+          va.pass = pass;
+          hipLaunchKernelGGL(imp_dots_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+          hipLaunchKernelGGL(imp_update_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+        }
+        ++kit;
+        const bool last = j + 1 == m || kit >= s.max_krylov;
+        hipLaunchKernelGGL(imp_gmres_small_kernel, sgrid, dim3(64), 0, ctx->stream, s.sm, j, cycle, (int)last);
+        ctx->n_stage_launches += 5;
+        PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+        if ((rc = read_flags(ctx))) return rc;
+        if (kit >= s.max_krylov && any_active()) {
+          spent = true;
+          break;
+        }
+      }
+      if (spent) return implicit_fail(ctx, step, "GMRES: residual estimate above krylov_rtol |G|", kit);
+      va.cycle = cycle;
+      hipLaunchKernelGGL(imp_solution_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+      ctx->n_stage_launches++;
+      PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+      if (!any_active()) break;
+    }
+  }
+}
+
+}  // namespace
+
+int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* stats) {
+  int rc;
+  if ((rc = check_implicit(ctx))) return rc;
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(ctx, PDEOPT_EINVAL, "implicit Euler: dt = %g", dt);
+  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  const int B = ctx->prob.batch;
+  if (stats) std::fill(stats, stats + 4 * (int64_t)B, (int64_t)0);
+  for (int64_t s = 0; s < n; ++s) {
+    const double t1 = t0 + (double)(s + 1) * dt;
+    rc = with_dtype(ctx, [&](auto t) { return implicit_step<decltype(t)>(ctx, t1, dt, s, stats); });
+    if (rc) return rc;
+  }
+  char buf[96];
+  snprintf(buf, sizeof(buf), "implicit_euler_%s_%s_gmres%d", equation_short_name(ctx->prob.equation),
+           ctx->prob.dtype == PDEOPT_F32 ? "f32" : "f64", ctx->implicit->restart);
+  ctx->last_kernel = buf;
+  return PDEOPT_OK;
+}
+
+void implicit_destroy(pdeopt_ctx* ctx) {
+  Implicit* s = ctx->implicit;
+  if (!s) return;
+  if (s->fields) (void)hipFree(s->fields);
+  if (s->small_blk) (void)hipFree(s->small_blk);
+  if (s->flags_host) (void)hipHostFree(s->flags_host);
+  if (s->res_host) (void)hipHostFree(s->res_host);
+  delete s;
+  ctx->implicit = nullptr;
+}
+
+}  // namespace pdeopt
+
+using namespace pdeopt;
+
+extern "C" {
+
+int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double krylov_rtol, int restart, int max_newton,
+                              int max_krylov) {
+  if (!ctx) return PDEOPT_EINVAL;
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  int rc;
+  if ((rc = implicit_check_problem(ctx))) return rc;
+  if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(rtol) || !std::isfinite(atol) || !(rtol + atol > 0.0))
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler: rtol = %g, atol = %g (non-negative, not both zero)", rtol, atol);
+  if (!(krylov_rtol > 0.0) || !(krylov_rtol < 1.0))
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler: krylov_rtol = %g (0 < krylov_rtol < 1)", krylov_rtol);
+  if (restart < 1 || restart > kImpMaxRestart)
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler: restart = %d (1 .. %d: the small systems live in one workgroup's LDS)", restart,
+                kImpMaxRestart);
+  if (max_newton < 1 || max_krylov < 1)
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler: max_newton = %d, max_krylov = %d (at least 1 each)", max_newton, max_krylov);
+  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const pdeopt_problem& p = ctx->prob;
+  const int B = p.batch, m = restart;
+  const int64_t cells = (int64_t)p.nx * p.ny;
+  const int nblk = (int)((cells + kImpChunk - 1) / kImpChunk);
+  const size_t field_bytes = (size_t)B * cells * ctx->esize;
+  const size_t fields_bytes = (size_t)(F_V + m) * field_bytes;
+  // doubles of the small block, in the order of ImpSmall; then the three int arrays
+  const size_t nd = (size_t)B * ((size_t)m * nblk + 2 * (size_t)nblk + m + (size_t)m * m + m + m + (m + 1) + m + 4);
+  const size_t small_bytes = nd * sizeof(double) + 3 * (size_t)B * sizeof(int);
+  Implicit* s = ctx->implicit;
+  if (s && (s->fields_bytes != fields_bytes || s->small_bytes != small_bytes || s->B != B || s->restart != m)) {
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    implicit_destroy(ctx);
+    s = nullptr;
+  }
+  if (!s) {
+    size_t free_b = 0, total_b = 0;
+    PDEOPT_HIP_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+    const size_t want = fields_bytes + small_bytes + (ctx->TA ? 0 : ctx->total_bytes);
+    if (want > free_b)
+      return fail(ctx, PDEOPT_ENOMEM, "implicit Euler: the workspace of restart = %d needs %zu bytes ((restart + 5) fields of the "
+                                      "batch and the partial sums), %zu are free on the device", m, want, free_b);
+    s = new Implicit();
+    ctx->implicit = s;
+    if ((rc = ensure_buffer(ctx, &s->fields, fields_bytes)) || (rc = ensure_buffer(ctx, &s->small_blk, small_bytes))) {
+      implicit_destroy(ctx);
+      return rc;
+    }
+    hipError_t e = hipHostMalloc((void**)&s->flags_host, (size_t)B * sizeof(int));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&s->res_host, 2 * (size_t)B * sizeof(double));
+    if (e != hipSuccess) {
+      implicit_destroy(ctx);
+      return fail(ctx, PDEOPT_ENOMEM, "hipHostMalloc failed: %s", hipGetErrorString(e));
+    }
+    s->B = B;
+    s->cells = cells;
+    s->nblk = nblk;
+    s->restart = m;
+    s->field_bytes = field_bytes;
+    s->fields_bytes = fields_bytes;
+    s->small_bytes = small_bytes;
+    double* d = static_cast<double*>(s->small_blk);
+    ImpSmall& sm = s->sm;
+    auto take = [&](size_t per_env) { double* q = d; d += (size_t)B * per_env; return q; };
+    sm.part_dot = take((size_t)m * nblk);
+    sm.part_nrm = take(2 * (size_t)nblk);
+    sm.hcol = take(m);
+    sm.R = take((size_t)m * m);
+    sm.cs = take(m);
+    sm.sn = take(m);
+    sm.g = take(m + 1);
+    sm.ycoef = take(m);
+    sm.gnorm = take(1);
+    sm.tol = take(1);
+    sm.vscale = take(1);
+    sm.res = take(1);
+    sm.flags = reinterpret_cast<int*>(d);
+    sm.kcols = sm.flags + B;
+    sm.conv_cycle = sm.kcols + B;
+    sm.m = m;
+    sm.nblk = nblk;
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s->small_blk, 0, small_bytes, ctx->stream));
+  }
+  s->rtol = rtol;
+  s->atol = atol;
+  s->krylov_rtol = krylov_rtol;
+  s->max_newton = max_newton;
+  s->max_krylov = max_krylov;
+  return PDEOPT_OK;
+}
+
+int pdeopt_implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n_steps, int64_t* stats_out) {
+  if (!ctx) return PDEOPT_EINVAL;
+  if (n_steps < 0) return fail(ctx, PDEOPT_EINVAL, "n_steps < 0");
+  ctx->tsit5_fsal_valid = false;
+  ctx->tsit5_pending = false;
+  return implicit_advance(ctx, t0, dt, n_steps, stats_out);
+}
+
+int pdeopt_implicit_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* out_host) {
+  if (!ctx || !v_host || !out_host) return PDEOPT_EINVAL;
+  int rc;
+  if ((rc = check_implicit(ctx))) return rc;
+  Implicit& s = *ctx->implicit;
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    T* const v = imp_field<T>(s, F_W0);
+    T* const w = imp_field<T>(s, F_W1);
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(v, v_host, ctx->total_bytes, hipMemcpyHostToDevice, ctx->stream));
+    int r;
+    if ((r = launch_op<T>(ctx, v, nullptr, w, nullptr, nullptr, dt))) return r;
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out_host, w, ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return (int)PDEOPT_OK;
+  });
+}
+
+}  // extern "C"

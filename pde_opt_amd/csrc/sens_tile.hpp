@@ -18,6 +18,25 @@ __device__ __forceinline__ int wrap_idx(int g, int n) {
   return g;
 }
 
+// ---- stencil primitives on a tile in LDS (row pitch ld): the forward kernels' expressions, in their order -----------
+// Users: the operator kernels of the implicit step (implicit.hip).  The tangent kernels of sens.hip keep these same
+// expressions written out in their bodies, so that they compile to what they always compiled to.
+
+// 5-point Laplacian of s at offset o
+template <typename T>
+__device__ __forceinline__ T tile_lap5(const T* __restrict__ s, int o, int ld, T rhx2, T rhy2) {
+  const T c = s[o];
+  return (s[o + ld] - T(2) * c + s[o - ld]) * rhx2 + (s[o + 1] - T(2) * c + s[o - 1]) * rhy2;
+}
+
+// the linearised Cahn-Hilliard flux through the face between the cells at offsets a (lower index) and b of a tile:
+// avg(dD) grad(mu) + avg(D) grad(dmu)
+template <typename T>
+__device__ __forceinline__ T tile_tangent_flux(const T* __restrict__ smu, const T* __restrict__ sD, const T* __restrict__ sdmu,
+                                               const T* __restrict__ sdD, int a, int b, T rh) {
+  return T(0.5) * (sdD[a] + sdD[b]) * ((smu[b] - smu[a]) * rh) + T(0.5) * (sD[a] + sD[b]) * ((sdmu[b] - sdmu[a]) * rh);
+}
+
 // ---- closure derivatives (the family of include/pdeopt_hip.h; values from closure_generic) ------------------------
 
 // 1 / q of the Legendre recurrence below: a multiply per term instead of a division (the tangent kernels evaluate

@@ -62,6 +62,8 @@ class HipEngine:
         self._cnns: list = []  # open NativeCNN and NativeMixer handles: closed before the ctx they belong to
         self.gpe_origin: Optional[tuple] = None  # coordinates of cell (0, 0) of a GPE problem (gpe_observables)
         self._n_bins = 0  # shells of the tables the library holds (sk_configure)
+        self.halo_layout = 0  # set_halo_layout
+        self.implicit_stats: Optional[np.ndarray] = None  # (batch, 4) totals since implicit_configure (implicit_advance)
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -400,8 +402,46 @@ class HipEngine:
         self._check(self._lib.pdeopt_set_time_table(self._h, len(ts), ts.ctypes.data_as(C.c_void_p), terms.ctypes.data_as(C.c_void_p)))
 
     def advance(self, integrator: int, dt: float, n_substeps: int, t0: float = 0.0):
+        if int(integrator) == L.INT_IMPLICIT_EULER:  # the same steps, with their iteration counts kept
+            self.implicit_advance(dt, n_substeps, t0)
+            return
         self._upload_time_table(int(integrator), dt, int(n_substeps), t0)
         self._check(self._lib.pdeopt_advance(self._h, int(integrator), float(t0), float(dt), int(n_substeps)))
+
+    # -- implicit Euler by Newton-GMRES (csrc/implicit.hip) ------------------------------------------------------------
+    IMPLICIT_STAT_NAMES = ("newton_iterations", "krylov_iterations", "operator_applications", "rhs_evaluations")
+
+    def implicit_configure(self, rtol: float, atol: float, krylov_rtol: float = 1e-3, restart: int = 20, max_newton: int = 20,
+                           max_krylov: int = 200):
+        """tolerances and budgets of ``implicit_advance``; allocates the Krylov workspace ((restart + 5) fields of the batch)
+        and starts the counters ``implicit_stats`` from zero"""
+        self._check(self._lib.pdeopt_implicit_configure(self._h, float(rtol), float(atol), float(krylov_rtol), int(restart),
+                                                        int(max_newton), int(max_krylov)))
+        self.implicit_stats = np.zeros((self.batch, 4), dtype=np.int64)
+
+    def implicit_advance(self, dt: float, n_steps: int, t0: float = 0.0) -> np.ndarray:
+        """``n_steps`` implicit Euler steps; returns this call's ``(batch, 4)`` counters (``IMPLICIT_STAT_NAMES``) and adds
+        them to ``implicit_stats``.  A step that does not converge raises ``solvers.ImplicitSolveError``; the state is then
+        the one that step started from."""
+        st = np.zeros((self.batch, 4), dtype=np.int64)
+        rc = self._lib.pdeopt_implicit_advance(self._h, float(t0), float(dt), int(n_steps), st.ctypes.data_as(C.c_void_p))
+        if rc == L.ENOCONVERGE:
+            from .numerics.solvers import ImplicitSolveError
+
+            raise ImplicitSolveError(self._lib.pdeopt_last_error(self._h).decode())
+        self._check(rc)
+        if self.implicit_stats is not None and self.implicit_stats.shape == st.shape:
+            self.implicit_stats += st
+        return st
+
+    def implicit_apply(self, dt: float, v) -> np.ndarray:
+        """``(I - dt J_f(y)) v`` for the resident state ``y`` (after ``implicit_configure``); ``v``: ``(batch, nx, ny)``"""
+        a = np.ascontiguousarray(np.asarray(v, dtype=self.dtype))
+        if a.shape != (self.batch,) + self.state_shape:
+            raise ValueError(f"v shape {a.shape} does not match (batch,)+{self.state_shape}")
+        out = np.empty_like(a)
+        self._check(self._lib.pdeopt_implicit_apply(self._h, float(dt), a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def snapshot(self):
         self._check(self._lib.pdeopt_snapshot(self._h))
@@ -710,6 +750,7 @@ class HipEngine:
         """0 = periodic field, 4 / 8 = rank-local tile padded by a 4- / 8-cell halo (takes effect at the next
         configure); 8: one halo exchange per RK4 substep instead of two (fused Cahn-Hilliard stage pairs)"""
         self._check(self._lib.pdeopt_set_option(self._h, L.OPT_HALO_LAYOUT, int(halo)))
+        self.halo_layout = int(halo)
         self._aux_keys.clear()  # a layout change re-allocates on the next configure
 
     def halo_strip_elems(self) -> int:

@@ -658,8 +658,9 @@ def reject_unsupported(model):
     FD derivatives.  The equation / domain pair is checked here, before any equation is built.  The tangents always
     advance with constant steps: train / residuals / optimize take no step-size controller."""
     from .numerics.equations.phase_field import AllenCahn2DPeriodic, CahnHilliard2DPeriodic, CahnHilliard3DPeriodic
-    from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral
+    from .numerics.solvers import RK4, Euler, SemiImplicitFourierSpectral, reject_implicit_gradients
 
+    reject_implicit_gradients(model.solver_type, "train / residuals / optimize")
     dims = {CahnHilliard2DPeriodic: 2, CahnHilliard3DPeriodic: 3, AllenCahn2DPeriodic: 2}.get(model.equation_type)
     if _is_butler_volmer(model.equation_type) or _is_smoothed_boundary(model.equation_type):
         dims = 2

@@ -90,6 +90,9 @@ def diffeqsolve(
     saveat = saveat or SaveAt(t1=True)
     controller = stepsize_controller or ConstantStepSize()
     t0, t1 = float(t0), float(t1)
+    check_solve = getattr(solver, "check_solve", None)
+    if check_solve is not None:  # a solver that covers part of the equations / controllers says so before any engine work
+        check_solve(equation, controller, engine)
     eng, single = _prepare(equation, solver, y0, engine, t0, t1)
     take = (lambda a: a[0]) if single else (lambda a: a)
 
@@ -171,6 +174,11 @@ def diffeqsolve(
     finish_inside()
     stats = {"num_steps": total_steps, "num_accepted_steps": total_steps, "num_rejected_steps": 0,
              "kernel": eng.last_kernel}
+    if solver.integrator == L.INT_IMPLICIT_EULER:  # iteration counts of this solve: per environment, and their totals
+        counts = eng.implicit_stats
+        for q, name in enumerate(eng.IMPLICIT_STAT_NAMES):
+            stats[name] = [int(v) for v in counts[:, q]]
+        stats["implicit_totals"] = {name: int(counts[:, q].sum()) for q, name in enumerate(eng.IMPLICIT_STAT_NAMES)}
     return Solution(np.asarray(ts_out), np.stack(ys_out), stats)
 
 

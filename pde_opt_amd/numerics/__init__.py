@@ -17,6 +17,8 @@ from .functions import (
 from .shapes import Shape
 from .solvers import (
     RK4,
+    ImplicitEuler,
+    ImplicitSolveError,
     ConstantStepSize,
     Euler,
     PIDController,

@@ -147,6 +147,88 @@ class RotatingStrangSplitting(AbstractSolver):
         engine.set_integrator_params(time_scale=complex(self.time_scale), strang_dx=float(self.dx))
 
 
+class ImplicitSolveError(RuntimeError):
+    """A step of ``ImplicitEuler`` did not converge within ``max_newton`` / ``max_krylov``.  The message names the
+    environment, the step and the last residual; the engine's state is the one the failing step started from."""
+
+
+IMPLICIT_EULER_SUPPORT = ('CahnHilliard2DPeriodic or AllenCahn2DPeriodic with derivs="fd", closures of the in-kernel family '
+                          "(polynomial / Legendre), ConstantStepSize, fp32 / fp64, the periodic layout")
+
+
+@dataclasses.dataclass
+class ImplicitEuler(AbstractSolver):
+    """Implicit Euler ``y1 = y0 + dt f(y1, t1)`` by matrix-free Newton-GMRES on the GPU: the stand-in for
+    ``diffrax.ImplicitEuler`` with a Newton root-find and ``lineax.GMRES`` inside (upstream's
+    ``notebooks/test_implicit.ipynb``).  DESIGN.md section 4.21.
+
+    Newton on ``G(y) = y - y0 - dt f(y)`` starts at ``y0`` and stops, per environment, when
+    ``rms(G) <= atol + rtol rms(y)``.  Each linear solve ``(I - dt J_f(y)) delta = -G`` is GMRES restarted every ``restart``
+    (at most 64) iterations and stops when its residual estimate is ``<= krylov_rtol ||G||_2``.  A step that needs more than
+    ``max_newton`` linear solves, or a linear solve more than ``max_krylov`` iterations, raises ``ImplicitSolveError``.
+    ``solution.stats`` carries ``newton_iterations``, ``krylov_iterations``, ``operator_applications`` and
+    ``rhs_evaluations``: a list per environment, and their totals under ``"implicit_totals"``.
+
+    Runs ``IMPLICIT_EULER_SUPPORT``; everything else raises ``NotImplementedError`` before any engine work."""
+
+    rtol: float
+    atol: float
+    krylov_rtol: float = 1e-3
+    restart: int = 20
+    max_newton: int = 20
+    max_krylov: int = 200
+
+    integrator = L.INT_IMPLICIT_EULER
+
+    def order(self, terms=None):
+        return 1
+
+    @classmethod
+    def check_equation_type(cls, equation_type):
+        from .equations.phase_field import AllenCahn2DPeriodic, CahnHilliard2DPeriodic
+
+        if equation_type not in (CahnHilliard2DPeriodic, AllenCahn2DPeriodic):
+            raise NotImplementedError(f"ImplicitEuler has a Jacobian action for CahnHilliard2DPeriodic and AllenCahn2DPeriodic only, "
+                                      f"not {getattr(equation_type, '__name__', equation_type)}: the 3-D, smoothed-boundary, "
+                                      "Butler-Volmer, advection-diffusion and GPE classes stay on their explicit or split-step solvers")
+
+    def check_solve(self, equation, stepsize_controller=None, engine=None):
+        """what ``diffeqsolve`` asks before it touches the engine"""
+        self.check_equation_type(type(equation))
+        if isinstance(stepsize_controller, PIDController):
+            raise NotImplementedError("ImplicitEuler steps with ConstantStepSize: it has no error estimate for a PIDController "
+                                      "(an adaptive step for this solver is not implemented)")
+        if getattr(equation, "_mu_module", None) is not None:
+            raise NotImplementedError("ImplicitEuler linearises mu inside the kernel: a torch.nn.Module as mu has no in-kernel "
+                                      "derivative (it runs with SemiImplicitFourierSpectral or Euler)")
+        if getattr(equation, "derivs", "fd") != "fd":
+            raise NotImplementedError('ImplicitEuler linearises the finite-difference right-hand side: derivs="fd", not '
+                                      f'"{equation.derivs}"')
+        for d in (equation._mu_desc, equation._mob_desc):
+            if d is not None and d.kind == L.CL_JIT:
+                raise NotImplementedError("ImplicitEuler needs closures of the in-kernel family (polynomial / Legendre): a "
+                                          "run-time-compiled closure has no derivative to linearise with")
+        if engine is not None and getattr(engine, "halo_layout", 0):
+            raise NotImplementedError("ImplicitEuler needs the periodic layout: its sums run over whole environments, a padded "
+                                      "(decomposed) tile holds a part of one")
+        if not (self.rtol >= 0 and self.atol >= 0 and self.rtol + self.atol > 0):
+            raise ValueError(f"ImplicitEuler: rtol = {self.rtol}, atol = {self.atol} (non-negative, not both zero)")
+        if not 1 <= int(self.restart) <= L.IMPLICIT_MAX_RESTART:
+            raise ValueError(f"ImplicitEuler: restart = {self.restart} (1 .. {L.IMPLICIT_MAX_RESTART})")
+
+    def configure_engine(self, engine, equation):
+        self.check_solve(equation, None, engine)  # call sites that configure an engine themselves (PDEEnv) are refused alike
+        engine.implicit_configure(self.rtol, self.atol, self.krylov_rtol, self.restart, self.max_newton, self.max_krylov)
+
+
+def reject_implicit_gradients(solver_type, what: str) -> None:
+    """``train`` / ``optimize`` / ``mse_backward`` differentiate the solve: there is no tangent or adjoint of the Newton-GMRES step"""
+    if solver_type is ImplicitEuler:
+        raise NotImplementedError(f"{what} differentiates the solve, and sensitivities through the implicit step are not "
+                                  "implemented: ImplicitEuler is a forward solver (fit with Euler, RK4 or "
+                                  "SemiImplicitFourierSpectral)")
+
+
 # ---- step-size controllers / save specification (diffrax stand-ins) ---------------------------
 
 

@@ -65,6 +65,9 @@ class PDEModel:
         parameters = fit.plain(parameters)  # a TrainableScalar (train's kappa) is its number to the equation
         equation = self.equation_type(domain=self.domain, **parameters)
         solver = self.solver_type(**prepare_solver_params(self.solver_type, solver_parameters or {}, equation))
+        check_solve = getattr(solver, "check_solve", None)
+        if check_solve is not None:  # (ImplicitEuler: refuses what it does not cover before any engine exists)
+            check_solve(equation, stepsize_controller, self._engine)
         if getattr(equation, "_mu_module", None) is not None:  # a network as mu: torch evaluates it, the kernels take the field
             return self._fieldmu_solve(equation, solver, y0, ts, dt0, stepsize_controller)
         ts = np.asarray(ts, dtype=np.float64)
@@ -209,7 +212,9 @@ class PDEModel:
         the meaning ``fit.weight_vector`` gives a closure's weights; its share ``lambda sum w p^2`` is in the loss and
         ``2 lambda w p`` in the gradient.  ``.grad`` of the module is the same, bit for bit, with and without."""
         from . import fieldmu
+        from .numerics.solvers import reject_implicit_gradients
 
+        reject_implicit_gradients(self.solver_type, "mse_backward")
         module = parameters.get("mu")
         if not fieldmu.is_module(module):
             raise NotImplementedError("mse_backward differentiates a solve whose mu is a torch.nn.Module (" + fieldmu.FIELD_MU_SUPPORT
