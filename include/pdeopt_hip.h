@@ -815,6 +815,27 @@ int pdeopt_implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n_ste
  *   Cahn-Hilliard  J v = div( avg(D'(u) v) grad(mu) + avg(D(u)) grad(mu_h'(u) v - kappa lap v) ),  mu = mu_h(u) - kappa lap u
  *   Allen-Cahn     J v = -R'(u) v m - R(u) (mu_h'(u) v - kappa lap v),                              m = mu_h(u) - kappa lap u */
 int pdeopt_implicit_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* out_host);
+/* Right preconditioning of the GMRES solves: (A M^-1) z = -G, delta = M^-1 z, A = I - dt J_f(y).  kind 0: none (the
+ * default after every pdeopt_implicit_configure); 1: the spectral M, the symbol of the constant-coefficient part of the
+ * FINITE-DIFFERENCE operator at the Newton iterate y_b,
+ *   s(kx, ky) = (4 / hx^2) sin^2(pi kx / nx) + (4 / hy^2) sin^2(pi ky / ny)
+ *   Cahn-Hilliard  M_b = 1 + dt s (a_b + c_b kappa s),   c_b = mean D(y_b),   a_b = max(mean(D(y_b) mu_h'(y_b)), 0)
+ *   Allen-Cahn     M_b = 1 + dt   (a_b + c_b kappa s),   c_b = mean R(y_b),   a_b = max(mean(R(y_b) mu_h'(y_b)), 0)
+ * (fp64 means in a fixed order, recomputed at every Newton iterate), applied with rocFFT's batched real transforms on
+ * any grid.  The residual estimate of right-preconditioned GMRES is the residual of the original system: tolerances,
+ * flags, failure path and the [batch][4] counters keep their meaning.  Call it after pdeopt_implicit_configure
+ * (PDEOPT_ESTATE otherwise); a problem the implicit step does not cover (another equation, the padded layout, 3-D) gets
+ * PDEOPT_EINVAL.  Kind 1 allocates one more field of the batch, the half-spectrum field and the coefficient sums, and
+ * refuses (PDEOPT_ENOMEM, the message states the bytes) what does not fit. */
+enum { PDEOPT_IMPLICIT_PRECOND_NONE = 0, PDEOPT_IMPLICIT_PRECOND_SPECTRAL = 1 };
+int pdeopt_implicit_set_precond(pdeopt_ctx* ctx, int kind);
+/* a_b, c_b of the resident state: out is [batch][2].  Needs kind 1 (PDEOPT_ESTATE otherwise), like the next call */
+int pdeopt_implicit_precond_coefs(pdeopt_ctx* ctx, double* out);
+/* out = M^-1 v with the coefficients of the resident state and step dt; whole-batch host fields in the problem dtype */
+int pdeopt_implicit_precond_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* out_host);
+/* applications of M^-1 inside the steps, per environment, since pdeopt_implicit_configure / _set_precond: one per Krylov
+ * iteration and one per cycle end the environment took part in.  out is [batch] */
+int pdeopt_implicit_precond_count(pdeopt_ctx* ctx, int64_t* out);
 
 /* ---- timing / sync ------------------------------------------------------------------------- */
 int pdeopt_sync(pdeopt_ctx* ctx);

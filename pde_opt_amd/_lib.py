@@ -31,6 +31,7 @@ BV_VOLTAGE, BV_CONSTANT_CURRENT = 0, 1  # mode of pdeopt_set_bv_params
 INT_EULER, INT_RK4, INT_IMEX, INT_STRANG, INT_TSIT5 = 0, 1, 2, 3, 4
 INT_STRANG_ROT = 5  # rotating-frame alternating-direction split step (GPE2DTSRot)
 INT_IMPLICIT_EULER = 6  # matrix-free Newton-GMRES implicit Euler (csrc/implicit.hip)
+IMPLICIT_PRECOND = {None: 0, "spectral": 1}  # pdeopt_implicit_set_precond
 IMPLICIT_MAX_RESTART = 64
 CL_POLY, CL_LEGENDRE, CL_JIT = 0, 1, 2
 CL_LOGIT_PRIOR, CL_EXP_WRAP = 1, 2
@@ -221,6 +222,10 @@ _SIGNATURES = {
     "pdeopt_implicit_configure": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]),
     "pdeopt_implicit_advance": (C.c_int, [_VP, C.c_double, C.c_double, C.c_int64, _VP]),
     "pdeopt_implicit_apply": (C.c_int, [_VP, C.c_double, _VP, _VP]),
+    "pdeopt_implicit_set_precond": (C.c_int, [_VP, C.c_int]),
+    "pdeopt_implicit_precond_coefs": (C.c_int, [_VP, _VP]),
+    "pdeopt_implicit_precond_apply": (C.c_int, [_VP, C.c_double, _VP, _VP]),
+    "pdeopt_implicit_precond_count": (C.c_int, [_VP, _VP]),
     "pdeopt_fieldmu_rhs": (C.c_int, [_VP, _VP, _VP]),
     "pdeopt_fieldmu_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP]),
     "pdeopt_fieldmu_adjoint_step": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP]),

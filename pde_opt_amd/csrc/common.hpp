@@ -456,6 +456,11 @@ int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf);
 // any 2-D / 3-D grid), into the hermitian work field, which is scratch between steps: *half is [batch][*half_cells]
 // interleaved complex in the state's dtype, the last axis halved.  The state is not modified
 int spectral_r2c_state(pdeopt_ctx* ctx, void** half, int64_t* half_cells);
+// the pieces of that call for a caller that transforms fields of its own (implicit.hip): the plans and the hermitian work
+// field, then one unnormalised transform of a whole-batch field, real `in` to hermitian `out` (forward) or hermitian `in`
+// to real `out`, out of place; the inverse may overwrite its input
+int spectral_real_prepare(pdeopt_ctx* ctx, void** half, int64_t* half_cells);
+int spectral_real_exec(pdeopt_ctx* ctx, bool forward, void* in, void* out);
 int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<double>>& out);
 // one unnormalised complex transform along ONE axis (0: x, lines of stride ny; 1: y, contiguous lines) of a
 // whole-batch field [batch][nx][ny], in place, on the ctx's stream: rocFFT batched 1-D plans, any grid

@@ -17,6 +17,10 @@
 //                        LIN_CONV, 1 / |w| for the next op; the triangular solve when the environment's cycle ends
 //            cycle end  delta (+)= V y_k and, where the linear solve has converged, y += delta, in one launch;
 //            restart    r = -G - (I - dt J) delta for the environments that have not converged (one op on delta).
+// With the spectral preconditioner (pdeopt_implicit_set_precond; off by default) the solve is right-preconditioned:
+// iteration j forms z_j = M^-1 v_j (r2c, one multiply that also carries the normalisation and the 1 / N, c2r) and
+// w = A z_j, the operator storing v_j from the raw field; a cycle ends with delta (+)= M^-1 (V y_k).  The residual
+// estimate is still that of the original system.  Off, the launches and the bits are those of the lines above.
 // The host reads the B flags back once per iteration (4 B bytes) to know when every environment is done.  Environments
 // run in lockstep but converge independently: every kernel returns at once for a frozen environment (flags != 0), whose
 // vectors are then neither normalised nor updated; an environment's arithmetic does not depend on the batch it is in.
@@ -57,6 +61,14 @@ struct ImpSmall {
   int m, nblk;
 };
 
+// coefficients and tables of the spectral preconditioner
+struct ImpPrecond {
+  double* part;   // [B][2][nblk]  workgroup partials of sum D mu_h' (row 0) and sum D (row 1)
+  double* coef;   // [B][2]        a_b (clamped), c_b
+  double* sin2x;  // [nx]          sin^2(pi kx / nx)
+  double* sin2y;  // [ny / 2 + 1]  sin^2(pi ky / ny)
+};
+
 struct Implicit {
   double rtol = 0, atol = 0, krylov_rtol = 0;
   int restart = 0, max_newton = 0, max_krylov = 0;
@@ -69,6 +81,16 @@ struct Implicit {
   ImpSmall sm{};
   int* flags_host = nullptr;  // pinned
   double* res_host = nullptr;
+  // pdeopt_implicit_set_precond: 0 none, 1 spectral.  The workspace of the preconditioner is one more field of the batch
+  // and the small block below; the hermitian work field and the plans are spectral.hip's
+  int precond = 0;
+  void* zfield = nullptr;  // [B][cells]: z_j = M^-1 v_j of an iteration, V y_k at a cycle's end
+  void* pc_blk = nullptr;
+  ImpPrecond pc{};
+  void* hbuf = nullptr;    // borrowed (spectral_real_prepare)
+  int64_t half_cells = 0;
+  std::vector<int64_t> pc_count;   // [B] applications of M^-1 inside the steps since configure
+  std::vector<char> lin_applied;   // [B] this linear solve's delta has been added to y
 };
 
 namespace {
@@ -78,6 +100,7 @@ template <typename T>
 struct ImpOpArgs {
   const T* y;
   const T* src;
+  const T* raw;         // preconditioned operator only: the field v_j = scale x raw is formed from (src is then z_j = M^-1 v_j)
   T* vout;              // v as formed (the basis vector v_j); nullptr: not stored
   T* wout;
   const double* scale;  // [B] or nullptr (1)
@@ -92,8 +115,9 @@ struct ImpOpArgs {
 // Cahn-Hilliard: J v = div( avg(D'(u) v) grad(mu) + avg(D(u)) grad(mu_h'(u) v - kappa lap v) ), mu = mu_h(u) - kappa lap u:
 // the tangent kernel of sens.hip with one tangent and no coefficient term.  u and v on the tile + 2-cell ring, the four
 // face quantities on the tile + 1-cell ring; mu_h' and D' live in the registers of the thread that forms dmu and dD
-template <typename T>
-__global__ __launch_bounds__(256) void imp_op_ch_kernel(ImpOpArgs<T> a) {
+// PRE (right preconditioning): the source is z_j, read as it is, and the basis vector stored for the tile is scale x raw
+template <typename T, bool PRE>
+__device__ __forceinline__ void imp_op_ch_body(const ImpOpArgs<T>& a) {
   __shared__ T su[kR2 * kC2], sv[kR2 * kC2];
   __shared__ T smu[kR1 * kC1], sD[kR1 * kC1], sdmu[kR1 * kC1], sdD[kR1 * kC1];
   const int b = blockIdx.z;
@@ -111,7 +135,7 @@ __global__ __launch_bounds__(256) void imp_op_ch_kernel(ImpOpArgs<T> a) {
     const int r = q / kC2, c = q - r * kC2;
     const int64_t g = (int64_t)wrap_idx(i0 + r - 2, nx) * ny + wrap_idx(j0 + c - 2, ny);
     su[q] = u[g];
-    sv[q] = sc * s[g];
+    sv[q] = PRE ? s[g] : sc * s[g];
   }
   __syncthreads();
   for (int q = tid; q < kR1 * kC1; q += 256) {
@@ -140,15 +164,23 @@ __global__ __launch_bounds__(256) void imp_op_ch_kernel(ImpOpArgs<T> a) {
     const T jv = (fxp - fxm) * a.rhx + (fyp - fym) * a.rhy;
     const T v = sv[(r + 2) * kC2 + (c + 2)];
     const int64_t g = (int64_t)gi * ny + gj;
-    if (vout) vout[g] = v;
+    if (vout) vout[g] = PRE ? sc * a.raw[(int64_t)b * cells + g] : v;
     wout[g] = v - a.dt * jv;
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void imp_op_ch_kernel(ImpOpArgs<T> a) {
+  imp_op_ch_body<T, false>(a);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void precond_op_ch_kernel(ImpOpArgs<T> a) {
+  imp_op_ch_body<T, true>(a);
 }
 
 // Allen-Cahn: J v = -R'(u) v m - R(u) (mu_h'(u) v - kappa lap v), m = mu_h(u) - kappa lap u.  Radius 1: u and v on the
 // tile + 1-cell ring, everything else in registers
-template <typename T>
-__global__ __launch_bounds__(256) void imp_op_ac_kernel(ImpOpArgs<T> a) {
+template <typename T, bool PRE>
+__device__ __forceinline__ void imp_op_ac_body(const ImpOpArgs<T>& a) {
   __shared__ T su[kR1 * kC1], sv[kR1 * kC1];
   const int b = blockIdx.z;
   if (a.flags && a.flags[b]) return;
@@ -165,7 +197,7 @@ __global__ __launch_bounds__(256) void imp_op_ac_kernel(ImpOpArgs<T> a) {
     const int r = q / kC1, c = q - r * kC1;
     const int64_t g = (int64_t)wrap_idx(i0 + r - 1, nx) * ny + wrap_idx(j0 + c - 1, ny);
     su[q] = u[g];
-    sv[q] = sc * s[g];
+    sv[q] = PRE ? s[g] : sc * s[g];
   }
   __syncthreads();
   T* __restrict__ vout = a.vout ? a.vout + (int64_t)b * cells : nullptr;
@@ -183,9 +215,17 @@ __global__ __launch_bounds__(256) void imp_op_ac_kernel(ImpOpArgs<T> a) {
     const T dR = closure_dc<T>(a.mob, ep.mob, uc, R) * vc;
     const T jv = -(dR * m) - R * dmu;
     const int64_t g = (int64_t)gi * ny + gj;
-    if (vout) vout[g] = vc;
+    if (vout) vout[g] = PRE ? sc * a.raw[(int64_t)b * cells + g] : vc;
     wout[g] = vc - a.dt * jv;
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void imp_op_ac_kernel(ImpOpArgs<T> a) {
+  imp_op_ac_body<T, false>(a);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void precond_op_ac_kernel(ImpOpArgs<T> a) {
+  imp_op_ac_body<T, true>(a);
 }
 
 // ---- vector kernels: grid (nblk, B), 256 threads, workgroup blk owns the cells [blk kImpChunk, (blk + 1) kImpChunk) ----
@@ -495,6 +535,162 @@ __global__ __launch_bounds__(64) void imp_restart_small_kernel(ImpSmall sm, int 
   }
 }
 
+// ---- spectral preconditioner (pdeopt_implicit_set_precond) ------------------------------------------------------------
+// M = the symbol of the constant-coefficient part of the finite-difference operator I - dt J at the Newton iterate:
+//   s(kx, ky) = (4 / hx^2) sin^2(pi kx / nx) + (4 / hy^2) sin^2(pi ky / ny)   (the 5-point Laplacian is -s)
+//   Cahn-Hilliard  M = 1 + dt s (a + c kappa s),  c = mean D(y),  a = max(mean(D(y) mu_h'(y)), 0)
+//   Allen-Cahn     M = 1 + dt   (a + c kappa s),  c = mean R(y),  a = max(mean(R(y) mu_h'(y)), 0)
+// M >= 1 and M(0) = 1 (Cahn-Hilliard), so M^-1 keeps the mean of what it is applied to.  M^-1 v = c2r( r2c(v) / (N M) )
+// with the batched rocFFT plans of spectral.hip.  (These kernels' names do not start with imp_: the list of
+// tests/test_kernel_budgets_implicit.py is the unpreconditioned solver's; theirs is tests/test_kernel_budgets_implicit_precond.py.)
+template <typename T>
+struct PrecondCoefArgs {
+  const T* y;
+  const int* flags;  // [B] or nullptr: environments with flags != 0 are skipped
+  const EnvParams<T>* ep;
+  ClosureSpec mu, mob;
+  int64_t cells;
+  int nblk;
+  ImpPrecond pc;
+};
+
+// the two sums of an environment's coefficients, one fp64 partial per workgroup each (the layout of imp_residual_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void precond_coef_kernel(PrecondCoefArgs<T> a) {
+  __shared__ double sh[4];
+  const int b = blockIdx.y;
+  if (a.flags && a.flags[b]) return;
+  const EnvParams<T>& ep = a.ep[b];
+  const T* __restrict__ y = a.y + (int64_t)b * a.cells;
+  double sa = 0.0, sc = 0.0;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < a.cells) {
+      const T uc = y[c];
+      const T muh = closure_generic<T>(a.mu, ep.mu, uc);
+      const T D = closure_generic<T>(a.mob, ep.mob, uc);
+      sa += (double)D * (double)closure_dc<T>(a.mu, ep.mu, uc, muh);
+      sc += (double)D;
+    }
+  }
+  sa = block_sum(sa, sh);
+  sc = block_sum(sc, sh);
+  if (threadIdx.x == 0) {
+    a.pc.part[((int64_t)b * 2 + 0) * a.nblk + blockIdx.x] = sa;
+    a.pc.part[((int64_t)b * 2 + 1) * a.nblk + blockIdx.x] = sc;
+  }
+}
+
+// grid B, one wave: the partials added in the order of imp_norm_total, the means, the clamp
+__global__ __launch_bounds__(64) void precond_coef_finish_kernel(ImpPrecond pc, const int* flags, int nblk, double cells) {
+  const int b = blockIdx.x;
+  if (flags && flags[b]) return;
+  double t[2];
+  for (int row = 0; row < 2; ++row) {
+    const double* p = pc.part + ((int64_t)b * 2 + row) * nblk;
+    double s = 0.0;
+    for (int q = threadIdx.x; q < nblk; q += 64) s += p[q];
+    t[row] = wave_sum(s);
+  }
+  if (threadIdx.x != 0) return;
+  const double a = t[0] / cells;
+  pc.coef[2 * b] = a > 0.0 ? a : 0.0;  // inside the spinodal region mu_h' < 0: M stays >= 1
+  pc.coef[2 * b + 1] = t[1] / cells;
+}
+
+template <typename T>
+struct PrecondMulArgs {
+  T* h;                 // [B][nx][nyh] interleaved complex
+  const double* scale;  // [B] or nullptr (1): the GMRES normalisation of the field that was transformed
+  const int* flags;     // [B] or nullptr: every environment
+  const int* conv_cycle;
+  int cycle;            // < 0: an iteration (flags != 0 skips); >= 0: the end of this cycle (the rule of imp_solution_kernel)
+  const EnvParams<T>* ep;
+  ImpPrecond pc;
+  int nx, nyh, ch;
+  double dt, fx, fy, rn;  // fx = 4 / hx^2, fy = 4 / hy^2, rn = 1 / (nx ny): the transforms are unnormalised
+};
+
+// the environments the launches of a cycle's end work on
+__device__ __forceinline__ bool imp_cycle_end_skips(int fl, const int* conv_cycle, int b, int cycle) {
+  if (fl & (IMP_NEWTON_DONE | IMP_FAIL)) return true;
+  return (fl & IMP_LIN_CONV) && conv_cycle[b] < cycle;  // applied when it converged
+}
+
+// half spectrum *= scale / (N M_b), the factor formed in fp64: grid (cells of the half spectrum / 256, B)
+template <typename T>
+__global__ __launch_bounds__(256) void precond_mul_kernel(PrecondMulArgs<T> a) {
+  const int b = blockIdx.y;
+  if (a.flags) {
+    const int fl = a.flags[b];
+    if (a.cycle < 0 ? fl != 0 : imp_cycle_end_skips(fl, a.conv_cycle, b, a.cycle)) return;
+  }
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t hc = (int64_t)a.nx * a.nyh;
+  if (q >= hc) return;
+  const int kx = (int)(q / a.nyh), ky = (int)(q - (int64_t)kx * a.nyh);
+  const double s = a.fx * a.pc.sin2x[kx] + a.fy * a.pc.sin2y[ky];
+  const double ab = a.pc.coef[2 * b], cb = a.pc.coef[2 * b + 1];
+  const double lin = ab + cb * (double)a.ep[b].kappa * s;
+  const double M = 1.0 + a.dt * (a.ch ? s * lin : lin);
+  const T f = (T)((a.scale ? a.scale[b] : 1.0) * a.rn / M);
+  T* __restrict__ h = a.h + ((int64_t)b * hc + q) * 2;
+  h[0] *= f;
+  h[1] *= f;
+}
+
+// end of a cycle, preconditioned: z = V y_k (precond_combine_kernel), z <- M^-1 z, then delta (+)= z and, where the
+// linear solve converged in this cycle, y += delta (precond_add_kernel): imp_solution_kernel cut in two
+template <typename T>
+__global__ __launch_bounds__(256) void precond_combine_kernel(ImpVecArgs<T> a) {
+  __shared__ double sh_y[kImpMaxRestart];
+  const int b = blockIdx.y;
+  if (imp_cycle_end_skips(a.sm.flags[b], a.sm.conv_cycle, b, a.cycle)) return;
+  const int k = a.sm.kcols[b];
+  if (threadIdx.x < k) sh_y[threadIdx.x] = a.sm.ycoef[(int64_t)b * a.sm.m + threadIdx.x];
+  __syncthreads();
+  const int64_t cells = a.cells;
+  double d[kImpCellsPerThread];
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) d[m] = 0.0;
+  for (int i = 0; i < k; ++i) {
+    const T* __restrict__ v = a.V + ((int64_t)i * a.B + b) * cells;
+    const double yi = sh_y[i];
+#pragma unroll
+    for (int m = 0; m < kImpCellsPerThread; ++m) {
+      const int64_t c = imp_cell(m);
+      if (c < cells) d[m] += yi * (double)v[c];
+    }
+  }
+  T* __restrict__ z = a.w + (int64_t)b * cells;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < cells) z[c] = (T)d[m];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void precond_add_kernel(ImpVecArgs<T> a) {
+  const int b = blockIdx.y;
+  const int fl = a.sm.flags[b];
+  if (imp_cycle_end_skips(fl, a.sm.conv_cycle, b, a.cycle)) return;
+  const int64_t cells = a.cells;
+  const T* __restrict__ z = a.w + (int64_t)b * cells;
+  T* __restrict__ delta = a.delta + (int64_t)b * cells;
+  T* __restrict__ y = a.y + (int64_t)b * cells;
+#pragma unroll
+  for (int m = 0; m < kImpCellsPerThread; ++m) {
+    const int64_t c = imp_cell(m);
+    if (c < cells) {
+      const T dv = a.cycle > 0 ? (T)((double)delta[c] + (double)z[c]) : z[c];
+      delta[c] = dv;
+      if (fl & IMP_LIN_CONV) y[c] += dv;
+    }
+  }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------
 
 template <typename T>
@@ -537,12 +733,15 @@ int check_implicit(pdeopt_ctx* ctx) {
   return PDEOPT_OK;
 }
 
+// raw != nullptr: the preconditioned operator, w = A src with src = z_j as it is, and v_j = scale x raw stored in vout
 template <typename T>
-int launch_op(pdeopt_ctx* ctx, const T* src, T* vout, T* wout, const double* scale, const int* flags, double dt) {
+int launch_op(pdeopt_ctx* ctx, const T* src, T* vout, T* wout, const double* scale, const int* flags, double dt,
+              const T* raw = nullptr) {
   const pdeopt_problem& p = ctx->prob;
   ImpOpArgs<T> a{};
   a.y = static_cast<const T*>(ctx->Y);
   a.src = src;
+  a.raw = raw;
   a.vout = vout;
   a.wout = wout;
   a.scale = scale;
@@ -553,10 +752,69 @@ int launch_op(pdeopt_ctx* ctx, const T* src, T* vout, T* wout, const double* sca
   set_recip_plain(a, grid_recip(p));
   a.dt = T(dt);
   const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, p.batch);
-  if (p.equation == PDEOPT_EQ_ALLEN_CAHN) hipLaunchKernelGGL(imp_op_ac_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(imp_op_ch_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  const bool ac = p.equation == PDEOPT_EQ_ALLEN_CAHN;
+  if (raw) {
+    if (ac) hipLaunchKernelGGL(precond_op_ac_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(precond_op_ch_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  } else if (ac) {
+    hipLaunchKernelGGL(imp_op_ac_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  } else {
+    hipLaunchKernelGGL(imp_op_ch_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
+  }
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+// a_b, c_b of the resident state for the environments with flags == 0 (flags == nullptr: all)
+template <typename T>
+int launch_precond_coefs(pdeopt_ctx* ctx, const int* flags) {
+  Implicit& s = *ctx->implicit;
+  PrecondCoefArgs<T> a{};
+  a.y = static_cast<const T*>(ctx->Y);
+  a.flags = flags;
+  set_closures<T>(a, ctx, 0);
+  a.cells = s.cells;
+  a.nblk = s.nblk;
+  a.pc = s.pc;
+  hipLaunchKernelGGL(precond_coef_kernel<T>, dim3(s.nblk, s.B), dim3(256), 0, ctx->stream, a);
+  hipLaunchKernelGGL(precond_coef_finish_kernel, dim3(s.B), dim3(64), 0, ctx->stream, s.pc, flags, s.nblk, (double)s.cells);
+  ctx->n_stage_launches += 2;
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  return PDEOPT_OK;
+}
+
+// out = M^-1 (scale x in) over the whole batch: r2c, multiply, c2r.  cycle < 0: an iteration's rule for which environments
+// the multiply touches, otherwise a cycle end's; the transforms run over every environment.  A frozen one's vectors are
+// not written while it is frozen and the multiply with the 1 / N skips it, so its z is N x its stale source after an
+// iteration and N^2 x after a cycle end, which the next iteration replaces: finite, bounded, nothing accumulates, and
+// nobody reads it
+template <typename T>
+int launch_precond(pdeopt_ctx* ctx, const T* in, T* out, const double* scale, const int* flags, int cycle, double dt) {
+  Implicit& s = *ctx->implicit;
+  const pdeopt_problem& p = ctx->prob;
+  int rc;
+  if ((rc = spectral_real_exec(ctx, true, const_cast<T*>(in), s.hbuf))) return rc;
+  PrecondMulArgs<T> a{};
+  a.h = static_cast<T*>(s.hbuf);
+  a.scale = scale;
+  a.flags = flags;
+  a.conv_cycle = s.sm.conv_cycle;
+  a.cycle = cycle;
+  a.ep = env_params<T>(ctx, 0);
+  a.pc = s.pc;
+  a.nx = p.nx;
+  a.nyh = p.ny / 2 + 1;
+  a.ch = p.equation == PDEOPT_EQ_CAHN_HILLIARD;
+  a.dt = dt;
+  a.fx = 4.0 / (p.hx * p.hx);
+  a.fy = 4.0 / (p.hy * p.hy);
+  a.rn = 1.0 / ((double)p.nx * (double)p.ny);
+  const int64_t hc = (int64_t)a.nx * a.nyh;
+  hipLaunchKernelGGL(precond_mul_kernel<T>, dim3((unsigned)((hc + 255) / 256), s.B), dim3(256), 0, ctx->stream, a);
+  PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+  if ((rc = spectral_real_exec(ctx, false, s.hbuf, out))) return rc;
+  ctx->n_stage_launches += 3;  // the two transforms count as one each
   return PDEOPT_OK;
 }
 
@@ -600,6 +858,8 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
   va.cells = cells;
   va.B = B;
   va.sm = s.sm;
+  const bool pre = s.precond != 0;
+  T* const Z = static_cast<T*>(s.zfield);
   int rc;
   auto count = [&](int which) {  // the environments the next launch works on
     if (st)
@@ -630,6 +890,10 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
       if (s.flags_host[b] & IMP_FAIL) return implicit_fail(ctx, step, "Newton: rms(G) above atol + rtol rms(y)", newton_it);
     if (!any_active()) return PDEOPT_OK;
     count(0);
+    if (pre) {  // the symbol's coefficients at this Newton iterate
+      if ((rc = launch_precond_coefs<T>(ctx, s.sm.flags))) return rc;
+      std::fill(s.lin_applied.begin(), s.lin_applied.end(), (char)0);
+    }
     int kit = 0;
     bool spent = false;
     for (int cycle = 0;; ++cycle) {
@@ -649,7 +913,14 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
         T* const w = W[j & 1];
         count(1);
         count(2);
-        if ((rc = launch_op<T>(ctx, src, V + (int64_t)j * B * cells, w, s.sm.vscale, s.sm.flags, dt))) return rc;
+        if (pre) {  // z_j = M^-1 v_j, w = A z_j; the operator stores v_j = scale x src as it goes by
+          for (int b = 0; b < B; ++b)
+            if (!s.flags_host[b]) s.pc_count[b]++;
+          if ((rc = launch_precond<T>(ctx, src, Z, s.sm.vscale, s.sm.flags, -1, dt))) return rc;
+          if ((rc = launch_op<T>(ctx, Z, V + (int64_t)j * B * cells, w, s.sm.vscale, s.sm.flags, dt, src))) return rc;
+        } else if ((rc = launch_op<T>(ctx, src, V + (int64_t)j * B * cells, w, s.sm.vscale, s.sm.flags, dt))) {
+          return rc;
+        }
         va.w = w;
         va.ncols = j + 1;
         for (int pass = 0; pass < 2; ++pass) {
@@ -670,8 +941,24 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
       }
       if (spent) return implicit_fail(ctx, step, "GMRES: residual estimate above krylov_rtol |G|", kit);
       va.cycle = cycle;
-      hipLaunchKernelGGL(imp_solution_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
-      ctx->n_stage_launches++;
+      if (pre) {  // delta (+)= M^-1 (V y_k): one application per cycle
+        for (int b = 0; b < B; ++b) {
+          const int fl = s.flags_host[b];
+          if ((fl & (IMP_NEWTON_DONE | IMP_FAIL)) || ((fl & IMP_LIN_CONV) && s.lin_applied[b])) continue;
+          s.pc_count[b]++;
+          if (fl & IMP_LIN_CONV) s.lin_applied[b] = 1;
+        }
+        va.w = Z;
+        hipLaunchKernelGGL(precond_combine_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+        PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+        if ((rc = launch_precond<T>(ctx, Z, Z, nullptr, s.sm.flags, cycle, dt))) return rc;
+        hipLaunchKernelGGL(precond_add_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+        PDEOPT_HIP_CHECK(ctx, hipGetLastError());
+        ctx->n_stage_launches += 2;
+      } else {
+        hipLaunchKernelGGL(imp_solution_kernel<T>, vgrid, dim3(256), 0, ctx->stream, va);
+        ctx->n_stage_launches++;
+      }
       PDEOPT_HIP_CHECK(ctx, hipGetLastError());
       if (!any_active()) break;
     }
@@ -704,6 +991,8 @@ void implicit_destroy(pdeopt_ctx* ctx) {
   if (!s) return;
   if (s->fields) (void)hipFree(s->fields);
   if (s->small_blk) (void)hipFree(s->small_blk);
+  if (s->zfield) (void)hipFree(s->zfield);
+  if (s->pc_blk) (void)hipFree(s->pc_blk);
   if (s->flags_host) (void)hipHostFree(s->flags_host);
   if (s->res_host) (void)hipHostFree(s->res_host);
   delete s;
@@ -795,6 +1084,9 @@ int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double 
     sm.nblk = nblk;
     PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s->small_blk, 0, small_bytes, ctx->stream));
   }
+  s->precond = 0;  // pdeopt_implicit_set_precond comes after this call; its buffers stay with the workspace
+  s->pc_count.assign((size_t)B, 0);
+  s->lin_applied.assign((size_t)B, 0);
   s->rtol = rtol;
   s->atol = atol;
   s->krylov_rtol = krylov_rtol;
@@ -827,6 +1119,110 @@ int pdeopt_implicit_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* 
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return (int)PDEOPT_OK;
   });
+}
+
+int pdeopt_implicit_set_precond(pdeopt_ctx* ctx, int kind) {
+  if (!ctx) return PDEOPT_EINVAL;
+  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
+  int rc;
+  if ((rc = implicit_check_problem(ctx))) return rc;  // another equation, another layout, 3-D: PDEOPT_EINVAL
+  if ((rc = check_implicit(ctx))) return rc;
+  if (kind != PDEOPT_IMPLICIT_PRECOND_NONE && kind != PDEOPT_IMPLICIT_PRECOND_SPECTRAL)
+    return fail(ctx, PDEOPT_EINVAL, "implicit Euler: preconditioner %d (0 none, 1 spectral)", kind);
+  Implicit& s = *ctx->implicit;
+  std::fill(s.pc_count.begin(), s.pc_count.end(), (int64_t)0);
+  if (kind == PDEOPT_IMPLICIT_PRECOND_NONE) {
+    s.precond = 0;
+    return PDEOPT_OK;
+  }
+  const pdeopt_problem& p = ctx->prob;
+  const int nyh = p.ny / 2 + 1;
+  const size_t nd = (size_t)s.B * (2 * (size_t)s.nblk + 2) + (size_t)p.nx + (size_t)nyh;
+  // Set up once per workspace.  The tables and the size of pc_blk belong to one (nx, ny, batch, dtype), and so does this
+  // workspace: pdeopt_configure frees it (implicit_destroy, with the field buffers) on any change of shape or dtype, and
+  // pdeopt_implicit_configure, whose own reuse test compares byte sizes only, cannot see another grid without that.  A
+  // reuse rule that lets a workspace outlive its grid has to rebuild these too.
+  if (!s.zfield || !s.pc_blk) {
+    size_t free_b = 0, total_b = 0;
+    PDEOPT_HIP_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+    const size_t half_bytes = (size_t)s.B * p.nx * nyh * 2 * ctx->esize;
+    const size_t want = s.field_bytes + half_bytes + nd * sizeof(double);
+    if (want > free_b)
+      return fail(ctx, PDEOPT_ENOMEM, "implicit Euler: the spectral preconditioner needs %zu bytes (one more field of the batch, "
+                                      "the half-spectrum field of the transforms and the coefficient sums), %zu are free on the "
+                                      "device", want, free_b);
+    if ((rc = ensure_buffer(ctx, &s.zfield, s.field_bytes)) || (rc = ensure_buffer(ctx, &s.pc_blk, nd * sizeof(double)))) return rc;
+    // the transforms run over every environment, a frozen one's included: what they read there is stale, never garbage
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.zfield, 0, s.field_bytes, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(static_cast<char*>(s.fields) + (size_t)F_W0 * s.field_bytes, 0, 2 * s.field_bytes, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.pc_blk, 0, nd * sizeof(double), ctx->stream));
+    double* d = static_cast<double*>(s.pc_blk);
+    s.pc.part = d;
+    s.pc.coef = s.pc.part + (size_t)s.B * 2 * s.nblk;
+    s.pc.sin2x = s.pc.coef + (size_t)s.B * 2;
+    s.pc.sin2y = s.pc.sin2x + p.nx;
+    std::vector<double> tab((size_t)p.nx + nyh);
+    const double pi = 3.14159265358979323846;
+    for (int k = 0; k < p.nx; ++k) tab[k] = std::pow(std::sin(pi * k / p.nx), 2);
+    for (int k = 0; k < nyh; ++k) tab[(size_t)p.nx + k] = std::pow(std::sin(pi * k / p.ny), 2);
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.pc.sin2x, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if ((rc = spectral_real_prepare(ctx, &s.hbuf, &s.half_cells))) return rc;
+  if (s.half_cells != (int64_t)p.nx * nyh)
+    return fail(ctx, PDEOPT_ESTATE, "implicit Euler: the half spectrum holds %lld cells, %lld expected", (long long)s.half_cells,
+                (long long)p.nx * nyh);
+  s.precond = kind;
+  return PDEOPT_OK;
+}
+
+// the preconditioner entry points need one that is switched on
+static int check_precond(pdeopt_ctx* ctx) {
+  int rc;
+  if ((rc = check_implicit(ctx))) return rc;
+  if (!ctx->implicit->precond)
+    return fail(ctx, PDEOPT_ESTATE, "pdeopt_implicit_set_precond(ctx, PDEOPT_IMPLICIT_PRECOND_SPECTRAL) has not been called");
+  return PDEOPT_OK;
+}
+
+int pdeopt_implicit_precond_coefs(pdeopt_ctx* ctx, double* out) {
+  if (!ctx || !out) return PDEOPT_EINVAL;
+  int rc;
+  if ((rc = check_precond(ctx))) return rc;
+  Implicit& s = *ctx->implicit;
+  if ((rc = with_dtype(ctx, [&](auto t) { return launch_precond_coefs<decltype(t)>(ctx, nullptr); }))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, s.pc.coef, 2 * (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PDEOPT_OK;
+}
+
+int pdeopt_implicit_precond_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* out_host) {
+  if (!ctx || !v_host || !out_host) return PDEOPT_EINVAL;
+  int rc;
+  if ((rc = check_precond(ctx))) return rc;
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(ctx, PDEOPT_EINVAL, "implicit Euler: dt = %g", dt);
+  Implicit& s = *ctx->implicit;
+  return with_dtype(ctx, [&](auto t) {
+    using T = decltype(t);
+    T* const v = imp_field<T>(s, F_W0);
+    T* const z = static_cast<T*>(s.zfield);
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(v, v_host, ctx->total_bytes, hipMemcpyHostToDevice, ctx->stream));
+    int r;
+    if ((r = launch_precond_coefs<T>(ctx, nullptr))) return r;
+    if ((r = launch_precond<T>(ctx, v, z, nullptr, nullptr, -1, dt))) return r;
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out_host, z, ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return (int)PDEOPT_OK;
+  });
+}
+
+int pdeopt_implicit_precond_count(pdeopt_ctx* ctx, int64_t* out) {
+  if (!ctx || !out) return PDEOPT_EINVAL;
+  int rc;
+  if ((rc = check_implicit(ctx))) return rc;
+  const Implicit& s = *ctx->implicit;
+  std::copy(s.pc_count.begin(), s.pc_count.end(), out);
+  return PDEOPT_OK;
 }
 
 }  // extern "C"

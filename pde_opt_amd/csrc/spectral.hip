@@ -897,17 +897,23 @@ int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf) {
   return rc ? rc : fft_exec(ctx, forward, buf);
 }
 
-int spectral_r2c_state(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
+int spectral_real_prepare(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
   if (!ctx->spectral) ctx->spectral = new Spectral();
   std::call_once(g_rocfft_once, [] { rocfft_setup(); });
   int rc = ensure_real_plans(ctx);
   if (rc) return rc;
   Spectral& sp = *ctx->spectral;
   if ((rc = ensure_buffer(ctx, &sp.hbuf, (size_t)sp.half_cells * ctx->prob.batch * 2 * ctx->esize))) return rc;
-  if ((rc = real_fft_exec(ctx, true, ctx->Y, sp.hbuf))) return rc;
   *half = sp.hbuf;
   *half_cells = sp.half_cells;
   return PDEOPT_OK;
+}
+
+int spectral_real_exec(pdeopt_ctx* ctx, bool forward, void* in, void* out) { return real_fft_exec(ctx, forward, in, out); }
+
+int spectral_r2c_state(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
+  const int rc = spectral_real_prepare(ctx, half, half_cells);
+  return rc ? rc : real_fft_exec(ctx, true, ctx->Y, *half);
 }
 
 int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf) {

@@ -64,6 +64,7 @@ class HipEngine:
         self._n_bins = 0  # shells of the tables the library holds (sk_configure)
         self.halo_layout = 0  # set_halo_layout
         self.implicit_stats: Optional[np.ndarray] = None  # (batch, 4) totals since implicit_configure (implicit_advance)
+        self.implicit_precond = None  # implicit_set_precond
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -418,6 +419,38 @@ class HipEngine:
         self._check(self._lib.pdeopt_implicit_configure(self._h, float(rtol), float(atol), float(krylov_rtol), int(restart),
                                                         int(max_newton), int(max_krylov)))
         self.implicit_stats = np.zeros((self.batch, 4), dtype=np.int64)
+        self.implicit_precond = None
+
+    def implicit_set_precond(self, precond):
+        """right preconditioning of the GMRES solves, after ``implicit_configure`` (which switches it off): ``None`` or
+        ``"spectral"``, the symbol of the constant-coefficient part of the finite-difference operator applied with
+        batched real transforms (one more field of the batch and a half-spectrum field)"""
+        if precond not in L.IMPLICIT_PRECOND:
+            raise ValueError(f'precond = {precond!r}: None or "spectral"')
+        self._check(self._lib.pdeopt_implicit_set_precond(self._h, L.IMPLICIT_PRECOND[precond]))
+        self.implicit_precond = precond
+
+    def implicit_precond_coefs(self) -> np.ndarray:
+        """``(batch, 2)``: the coefficients ``a_b`` (clamped at 0) and ``c_b`` of the spectral preconditioner at the resident state"""
+        out = np.zeros((self.batch, 2), dtype=np.float64)
+        self._check(self._lib.pdeopt_implicit_precond_coefs(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def implicit_precond_apply(self, dt: float, v) -> np.ndarray:
+        """``M^-1 v`` of the spectral preconditioner for the resident state and step ``dt``; ``v``: ``(batch, nx, ny)``"""
+        a = np.ascontiguousarray(np.asarray(v, dtype=self.dtype))
+        if a.shape != (self.batch,) + self.state_shape:
+            raise ValueError(f"v shape {a.shape} does not match (batch,)+{self.state_shape}")
+        out = np.empty_like(a)
+        self._check(self._lib.pdeopt_implicit_precond_apply(self._h, float(dt), a.ctypes.data_as(C.c_void_p),
+                                                            out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def implicit_precond_count(self) -> np.ndarray:
+        """``(batch,)``: applications of ``M^-1`` inside the steps since ``implicit_configure`` / ``implicit_set_precond``"""
+        out = np.zeros(self.batch, dtype=np.int64)
+        self._check(self._lib.pdeopt_implicit_precond_count(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def implicit_advance(self, dt: float, n_steps: int, t0: float = 0.0) -> np.ndarray:
         """``n_steps`` implicit Euler steps; returns this call's ``(batch, 4)`` counters (``IMPLICIT_STAT_NAMES``) and adds

@@ -179,6 +179,8 @@ def diffeqsolve(
         for q, name in enumerate(eng.IMPLICIT_STAT_NAMES):
             stats[name] = [int(v) for v in counts[:, q]]
         stats["implicit_totals"] = {name: int(counts[:, q].sum()) for q, name in enumerate(eng.IMPLICIT_STAT_NAMES)}
+        if getattr(solver, "precond", None) is not None:
+            stats["preconditioner_applications"] = [int(v) for v in eng.implicit_precond_count()]
     return Solution(np.asarray(ts_out), np.stack(ys_out), stats)
 
 

@@ -169,6 +169,11 @@ class ImplicitEuler(AbstractSolver):
     ``solution.stats`` carries ``newton_iterations``, ``krylov_iterations``, ``operator_applications`` and
     ``rhs_evaluations``: a list per environment, and their totals under ``"implicit_totals"``.
 
+    ``precond="spectral"`` right-preconditions every GMRES solve with the symbol of the constant-coefficient part of the
+    finite-difference operator at the Newton iterate (two batched real transforms and one multiply per Krylov iteration);
+    ``solution.stats`` then also carries ``preconditioner_applications`` per environment.  The default ``None`` is the
+    unpreconditioned solver.
+
     Runs ``IMPLICIT_EULER_SUPPORT``; everything else raises ``NotImplementedError`` before any engine work."""
 
     rtol: float
@@ -177,8 +182,13 @@ class ImplicitEuler(AbstractSolver):
     restart: int = 20
     max_newton: int = 20
     max_krylov: int = 200
+    precond: Optional[str] = None
 
     integrator = L.INT_IMPLICIT_EULER
+
+    def __post_init__(self):
+        if self.precond not in L.IMPLICIT_PRECOND:
+            raise ValueError(f'ImplicitEuler: precond = {self.precond!r} (None or "spectral")')
 
     def order(self, terms=None):
         return 1
@@ -219,6 +229,8 @@ class ImplicitEuler(AbstractSolver):
     def configure_engine(self, engine, equation):
         self.check_solve(equation, None, engine)  # call sites that configure an engine themselves (PDEEnv) are refused alike
         engine.implicit_configure(self.rtol, self.atol, self.krylov_rtol, self.restart, self.max_newton, self.max_krylov)
+        if self.precond is not None:
+            engine.implicit_set_precond(self.precond)
 
 
 def reject_implicit_gradients(solver_type, what: str) -> None:

@@ -8,7 +8,11 @@
                   holds a NaN (a plain failure of the solve, reported as such), the last good one is timed
 
 Warm-up run first, then REPEATS timed runs: the median and the min / max spread are recorded.  (The shader clock is not: over windows this
-short the reading of ``timer_clock_hz`` is not usable.)  Usage: python tools/implicit_bench.py [--quick] [--out FILE]"""
+short the reading of ``timer_clock_hz`` is not usable.)  Usage: python tools/implicit_bench.py [--quick] [--out FILE]
+
+``--precond``: the same cases with ``precond="spectral"`` next to the unpreconditioned solver in the same run (Krylov
+iterations per Newton iterate and microseconds per Krylov iteration of both), and the 256^2 comparison with both variants
+of ImplicitEuler next to RK4 and SemiImplicitFourierSpectral, written to profiles/implicit_euler_precond.json."""
 import json
 import os
 import sys
@@ -39,7 +43,7 @@ def equation(n):
     return P.CahnHilliard2DPeriodic(P.Domain((n, n), ((0.0, H * n), (0.0, H * n)), "dimensionless"), KAPPA, MU, MOB)
 
 
-def per_iteration(eng, n, batch, dtype):
+def per_iteration(eng, n, batch, dtype, precond=None):
     eq = equation(n)
     y0 = np.clip(0.5 + 0.05 * np.random.default_rng(0).standard_normal((batch, n, n)), 0.1, 0.9).astype(dtype)
     lam = 8.0 / H**2
@@ -48,6 +52,7 @@ def per_iteration(eng, n, batch, dtype):
     tol = (1e-4, 1e-6) if dtype == np.float32 else (1e-8, 1e-10)
     eng.configure(dtype=dtype, batch=batch, **eq._engine_problem())
     eng.implicit_configure(*tol, max_krylov=2000)
+    eng.implicit_set_precond(precond)
     wall, stats = [], None
     for rep in range(REPEATS + 1):
         eng.set_state(y0)
@@ -67,8 +72,8 @@ def per_iteration(eng, n, batch, dtype):
         if rep:
             rk4.append(ms * 1e3 / 50)
     w = spread(wall)
-    return {"grid": n, "batch": batch, "dtype": np.dtype(dtype).name, "dt": dt, "dt_over_euler_limit": 50.0,
-            "newton_iterations": newton, "krylov_iterations": krylov, "step_us": w,
+    return {"grid": n, "batch": batch, "dtype": np.dtype(dtype).name, "precond": precond, "dt": dt, "dt_over_euler_limit": 50.0,
+            "newton_iterations": newton, "krylov_iterations": krylov, "krylov_per_newton": krylov / max(newton, 1), "step_us": w,
             "us_per_krylov_iteration": {k: v / max(krylov, 1) for k, v in w.items()},
             "us_per_newton_iteration": {k: v / max(newton, 1) for k, v in w.items()},
             "rk4_substep_us": spread(rk4)}
@@ -89,11 +94,12 @@ def largest_stable_step(solve, dt0, t_final):
     return good
 
 
-def time_to_final(eng, n, t_final):
+def time_to_final(eng, n, t_final, precond=False):
     eq = equation(n)
     y0 = np.clip(0.5 + 0.05 * np.random.default_rng(1).standard_normal((n, n)), 0.1, 0.9).astype(np.float32)
     solvers = {
         "ImplicitEuler": P.ImplicitEuler(1e-4, 1e-6, max_krylov=2000),
+        **({"ImplicitEuler(precond=spectral)": P.ImplicitEuler(1e-4, 1e-6, max_krylov=2000, precond="spectral")} if precond else {}),
         "RK4": P.RK4(),
         "SemiImplicitFourierSpectral": P.SemiImplicitFourierSpectral(**prepare_solver_params(P.SemiImplicitFourierSpectral, {"A": 0.5}, eq)),
     }
@@ -115,19 +121,21 @@ def time_to_final(eng, n, t_final):
 
 
 def main():
-    quick = "--quick" in sys.argv
+    quick, precond = "--quick" in sys.argv, "--precond" in sys.argv
     eng = HipEngine()
     cases = [(128, 1)] if quick else [(128, 1), (1024, 8)]
     result = {"what": "implicit Euler (Newton-GMRES, restart 20, CGS2) on Cahn-Hilliard, regular-solution mu, D = c (1 - c)",
               "repeats": REPEATS, "per_iteration": [], "time_to_final": None}
     for n, b in cases:
         for dtype in (np.float32, np.float64):
-            row = per_iteration(eng, n, b, dtype)
-            print(json.dumps(row), flush=True)
-            result["per_iteration"].append(row)
-    result["time_to_final"] = time_to_final(eng, 64 if quick else 256, 2e-5 if quick else 2e-4)
+            for pc in ((None, "spectral") if precond else (None,)):
+                row = per_iteration(eng, n, b, dtype, pc)
+                print(json.dumps(row), flush=True)
+                result["per_iteration"].append(row)
+    result["time_to_final"] = time_to_final(eng, 64 if quick else 256, 2e-5 if quick else 2e-4, precond)
     print(json.dumps(result["time_to_final"]), flush=True)
-    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "implicit_euler.json")
+    default = "implicit_euler_precond.json" if precond else "implicit_euler.json"
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", default)
     if not quick or "--out" in sys.argv:
         with open(out, "w") as f:
             json.dump(result, f, indent=1)
