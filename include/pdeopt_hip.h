@@ -849,7 +849,9 @@ typedef enum {
   PDEOPT_CNT_STAGE_LAUNCHES = 0, /* kernel launches of the integrators so far: fused stencil + update launches, and the
                                     FFT passes of the hand-written Strang / IMEX pipelines */
   PDEOPT_CNT_LAST_GROUPS = 1,    /* environment groups the last pdeopt_advance ran the batch in (1 = one sweep) */
-  PDEOPT_CNT_GROUP_STREAMS = 2   /* groups the last pdeopt_advance kept in flight side by side (PDEOPT_OPT_GROUP_STREAMS): 1 or 2 */
+  PDEOPT_CNT_GROUP_STREAMS = 2,  /* groups the last pdeopt_advance kept in flight side by side (PDEOPT_OPT_GROUP_STREAMS): 1 or 2 */
+  PDEOPT_CNT_DEVICE_BYTES = 3    /* device bytes the library holds right now, process-wide: every ctx and network handle
+                                    (not what pdeopt_buffer_alloc handed to the caller) */
 } pdeopt_counter;
 int pdeopt_get_counter(pdeopt_ctx* ctx, int which, int64_t* value);
 /* name of the kernel variant the last advance/rhs dispatched (for tests and profiles) */

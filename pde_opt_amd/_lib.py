@@ -60,6 +60,7 @@ OPT_GROUP_STREAMS = 9
 CNT_STAGE_LAUNCHES = 0
 CNT_LAST_GROUPS = 1
 CNT_GROUP_STREAMS = 2
+CNT_DEVICE_BYTES = 3
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
 FIELD_Y, FIELD_TA, FIELD_TB, FIELD_ACC = 0, 1, 2, 3
 PATH_AUTO, PATH_GENERIC, PATH_TILED = 0, 1, 2

@@ -23,38 +23,24 @@ int fail(pdeopt_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
-int ensure_buffer(pdeopt_ctx* ctx, void** p, size_t bytes) {
-  if (*p) return PDEOPT_OK;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return fail(ctx, PDEOPT_ENOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-  }
+namespace {
+template <typename Buffer>
+int ensure_any(pdeopt_ctx* ctx, Buffer& b, size_t bytes, const char* what) {
+  if (b && b.bytes() < bytes)
+    return fail(ctx, PDEOPT_ESTATE, "a buffer of %zu bytes was asked to hold %zu: its owner did not release or grow it", b.bytes(), bytes);
+  const hipError_t e = b.ensure(bytes);
+  if (e != hipSuccess) return fail(ctx, PDEOPT_ENOMEM, "%s(%zu bytes) failed: %s", what, bytes, hipGetErrorString(e));
   return PDEOPT_OK;
 }
+}  // namespace
 
-int grow_device_buffer(pdeopt_ctx* ctx, void** p, size_t* have_bytes, size_t need_bytes, bool sync_first) {
-  if (*p && *have_bytes < need_bytes) {
-    if (sync_first) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    *have_bytes = 0;
-  }
-  const int rc = ensure_buffer(ctx, p, need_bytes);
-  if (!rc) *have_bytes = std::max(*have_bytes, need_bytes);
-  return rc;
-}
+int ensure_buffer(pdeopt_ctx* ctx, DeviceBuffer& b, size_t bytes) { return ensure_any(ctx, b, bytes, "hipMalloc"); }
+int ensure_buffer(pdeopt_ctx* ctx, PinnedBuffer& b, size_t bytes) { return ensure_any(ctx, b, bytes, "hipHostMalloc"); }
 
-int ensure_adaptive_block(pdeopt_ctx* ctx, size_t bytes) {
-  if (ctx->adaptive_cap >= bytes) return PDEOPT_OK;
-  if (ctx->adaptive_blk) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->adaptive_blk);
-    ctx->adaptive_blk = nullptr;
-    ctx->adaptive_cap = 0;
-  }
-  PDEOPT_HIP_CHECK(ctx, hipMalloc(&ctx->adaptive_blk, bytes));
-  ctx->adaptive_cap = bytes;
+int grow_device_buffer(pdeopt_ctx* ctx, DeviceBuffer& b, size_t need_bytes, bool sync_first) {
+  if (sync_first && b && b.bytes() < need_bytes) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  const hipError_t e = b.reserve(need_bytes);
+  if (e != hipSuccess) return fail(ctx, PDEOPT_ENOMEM, "hipMalloc(%zu bytes) failed: %s", need_bytes, hipGetErrorString(e));
   return PDEOPT_OK;
 }
 
@@ -69,27 +55,16 @@ int ensure_stream2(pdeopt_ctx* ctx) {
 namespace {
 
 void free_fields(pdeopt_ctx* ctx) {
-  void** bufs[] = {&ctx->Y, &ctx->TA, &ctx->TB, &ctx->ACC, &ctx->SNAP, &ctx->KS, &ctx->obs_dev, &ctx->vort_dev, &ctx->env_params_dev,
-                   &ctx->spots_dev};
+  // the members that die with a configuration
   ctx->n_spots = 0;
   ctx->spots_host.clear();
-  ctx->vort_cap = 0;
-  for (void** b : bufs) {
-    if (*b) (void)hipFree(*b);
-    *b = nullptr;
-  }
-  for (auto& k : ctx->K) {
-    if (k) (void)hipFree(k);
-    k = nullptr;
-  }
-  if (ctx->fieldmu_coef) (void)hipFree(ctx->fieldmu_coef);
-  ctx->fieldmu_coef = nullptr;
+  for (DeviceBuffer* b : {&ctx->Y, &ctx->TA, &ctx->TB, &ctx->ACC, &ctx->SNAP, &ctx->KS, &ctx->obs_dev, &ctx->vort_dev,
+                          &ctx->env_params_dev, &ctx->spots_dev})
+    b->reset();
+  for (DeviceBuffer& k : ctx->K) k.reset();
+  ctx->fieldmu_coef.reset();
   ctx->fieldmu_coef_slots = 0;
-  for (auto& a : ctx->aux) {
-    if (a.dev) (void)hipFree(a.dev);
-    if (a.stage) (void)hipHostFree(a.stage);
-    a = AuxField{};
-  }
+  for (auto& a : ctx->aux) a = AuxField{};
   spectral_destroy(ctx);
   strang_fused_destroy(ctx);
   sens_destroy(ctx);
@@ -191,7 +166,7 @@ void patch_kscale(pdeopt_ctx* ctx, const std::vector<double>& sc) {
 }
 
 int upload_env_params(pdeopt_ctx* ctx) {
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->env_params_dev, ctx->env_params_host.data(),
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->env_params_dev.get(), ctx->env_params_host.data(),
                                        ctx->env_params_host.size(), hipMemcpyHostToDevice,
                                        ctx->stream));
   // the host vector may be edited right after this call returns
@@ -217,16 +192,13 @@ size_t aux_bytes(const pdeopt_ctx* ctx, int which, int per_env) {
 int aux_alloc(pdeopt_ctx* ctx, int which, int per_env) {
   const size_t bytes = aux_bytes(ctx, which, per_env);
   AuxField& a = ctx->aux[which];
-  if (a.dev && a.bytes != bytes) {
+  if (a.dev && a.dev.bytes() != bytes) {
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(a.dev);
-    a.dev = nullptr;
-    if (a.stage) (void)hipHostFree(a.stage);
-    a.stage = nullptr;
+    a.dev.reset();
+    a.stage.reset();
   }
-  int rc = ensure_buffer(ctx, &a.dev, bytes);
+  int rc = ensure_buffer(ctx, a.dev, bytes);
   if (rc) return rc;
-  a.bytes = bytes;
   a.per_env = per_env ? 1 : 0;
   return PDEOPT_OK;
 }
@@ -238,9 +210,9 @@ int refresh_time_aux(pdeopt_ctx* ctx, int which, double t) {
   if (!a.fn || (a.loaded && a.t_loaded == t)) return PDEOPT_OK;
   // the staging buffer is reused: the previous upload must have left it
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (a.fn(t, which, a.stage, a.user) != 0)
+  if (a.fn(t, which, a.stage.get(), a.user) != 0)
     return fail(ctx, PDEOPT_EINVAL, "time-dependent source of aux field %d failed at t = %g", which, t);
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(a.dev, a.stage, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(a.dev.get(), a.stage.get(), a.dev.bytes(), hipMemcpyHostToDevice, ctx->stream));
   a.t_loaded = t;
   a.loaded = true;
   return PDEOPT_OK;
@@ -295,24 +267,14 @@ int pdeopt_ctx_destroy(pdeopt_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   comm_destroy(ctx);
-  for (void* h : ctx->host_allocs) (void)hipHostFree(h);
-  ctx->host_allocs.clear();
-  free_fields(ctx);
-  if (ctx->red_dev) (void)hipFree(ctx->red_dev);
-  if (ctx->red_mean_dev) (void)hipFree(ctx->red_mean_dev);
-  if (ctx->pf_obs_dev) (void)hipFree(ctx->pf_obs_dev);
-  sk_destroy(ctx);
-  if (ctx->adaptive_blk) (void)hipFree(ctx->adaptive_blk);
+  free_fields(ctx);  // the feature states and their plans, graphs
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->stream && !ctx->stream_borrowed) (void)hipStreamDestroy(ctx->stream);
-  if (ctx->halo_scratch) (void)hipFree(ctx->halo_scratch);
-  if (ctx->halo_scratch2) (void)hipFree(ctx->halo_scratch2);
-  if (ctx->clock_stamps) (void)hipFree(ctx->clock_stamps);
-  delete ctx;
+  delete ctx;  // the buffers that live with the ctx free themselves here, on ctx->device
   return PDEOPT_OK;
 }
 
@@ -443,15 +405,15 @@ int pdeopt_configure(pdeopt_ctx* ctx, const pdeopt_problem* pr) {
   ctx->total_bytes = ctx->env_elems * pr->batch * ctx->esize;
   int rc;
   if (!same_shape) {
-    if ((rc = ensure_buffer(ctx, &ctx->Y, ctx->total_bytes))) return rc;
-    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->Y, 0, ctx->total_bytes, ctx->stream));
+    if ((rc = ensure_buffer(ctx, ctx->Y, ctx->total_bytes))) return rc;
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->Y.get(), 0, ctx->total_bytes, ctx->stream));
   }
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
   if (ctx->fieldmu_coef)  // a coefficient gradient belongs to one problem: a new one starts from zero
-    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef, 0, ctx->fieldmu_coef_slots * sizeof(double), ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef.as<double>(), 0, ctx->fieldmu_coef_slots * sizeof(double), ctx->stream));
   with_dtype(ctx, [&](auto t) { fill_env_params<decltype(t)>(ctx); });
-  if ((rc = ensure_buffer(ctx, &ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->env_params_dev, ctx->env_params_host.size()))) return rc;
   ctx->imex_per_env = false;
   ctx->rot_set = false;
   ctx->rot_any_rate = false;
@@ -500,11 +462,11 @@ int pdeopt_set_aux(pdeopt_ctx* ctx, int which, const void* host, int per_env) {
   int rc = aux_alloc(ctx, which, per_env);
   if (rc) return rc;
   AuxField& a = ctx->aux[which];
-  const size_t bytes = a.bytes;
+  const size_t bytes = a.dev.bytes();
   a.fn = nullptr;  // a static upload replaces a time-dependent source
   a.loaded = false;
   spectral_invalidate(ctx);  // multipliers derived from the old aux field are stale
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(a.dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(a.dev.get(), host, bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -523,13 +485,7 @@ int pdeopt_set_aux_time_fn(pdeopt_ctx* ctx, int which, pdeopt_aux_fn fn, void* u
   }
   int rc = aux_alloc(ctx, which, per_env);
   if (rc) return rc;
-  if (!a.stage) {
-    hipError_t e = hipHostMalloc(&a.stage, a.bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      a.stage = nullptr;
-      return fail(ctx, PDEOPT_ENOMEM, "hipHostMalloc(%zu bytes) failed: %s", a.bytes, hipGetErrorString(e));
-    }
-  }
+  if ((rc = ensure_buffer(ctx, a.stage, a.dev.bytes()))) return rc;
   a.fn = fn;
   a.user = user;
   a.loaded = false;
@@ -564,7 +520,7 @@ int pdeopt_set_gpe_spots(pdeopt_ctx* ctx, int env_first, int env_count, int n_sp
   const size_t n = ctx->spots_host.size();
   const bool f32 = ctx->prob.dtype == PDEOPT_F32;
   const size_t bytes = n * 7 * (f32 ? sizeof(float) : sizeof(double));
-  if ((rc = ensure_buffer(ctx, &ctx->spots_dev, bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->spots_dev, bytes))) return rc;
   std::vector<char> packed(bytes);
   for (size_t i = 0; i < n; ++i) {
     const pdeopt_light_spot& q = ctx->spots_host[i];
@@ -576,7 +532,7 @@ int pdeopt_set_gpe_spots(pdeopt_ctx* ctx, int env_first, int env_count, int n_sp
         reinterpret_cast<double*>(packed.data())[i * 7 + c] = v[c];
     }
   }
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->spots_dev, packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->spots_dev.get(), packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -644,11 +600,11 @@ int pdeopt_set_state(pdeopt_ctx* ctx, int env_first, int env_count, const void* 
     // interior of each padded tile; halo cells are filled by pdeopt_halo_unpack
     const size_t h = ctx->halo, pny = pad_ld(ctx->prob.ny, ctx->halo), row = (size_t)ctx->prob.ny * ctx->esize;
     for (int e = 0; e < env_count; ++e)
-      PDEOPT_HIP_CHECK(ctx, hipMemcpy2DAsync((char*)ctx->Y + eb * (env_first + e) + (h * pny + h) * ctx->esize,
+      PDEOPT_HIP_CHECK(ctx, hipMemcpy2DAsync(ctx->Y.as<char>() + eb * (env_first + e) + (h * pny + h) * ctx->esize,
                                              pny * ctx->esize, (const char*)host + (size_t)e * row * ctx->prob.nx,
                                              row, row, ctx->prob.nx, hipMemcpyHostToDevice, ctx->stream));
   } else {
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync((char*)ctx->Y + eb * env_first, host, eb * env_count,
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->Y.as<char>() + eb * env_first, host, eb * env_count,
                                          hipMemcpyHostToDevice, ctx->stream));
   }
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -667,11 +623,11 @@ int pdeopt_get_state(pdeopt_ctx* ctx, int env_first, int env_count, void* host) 
     const size_t h = ctx->halo, pny = pad_ld(ctx->prob.ny, ctx->halo), row = (size_t)ctx->prob.ny * ctx->esize;
     for (int e = 0; e < env_count; ++e)
       PDEOPT_HIP_CHECK(ctx, hipMemcpy2DAsync((char*)host + (size_t)e * row * ctx->prob.nx, row,
-                                             (const char*)ctx->Y + eb * (env_first + e) + (h * pny + h) * ctx->esize,
+                                             ctx->Y.as<const char>() + eb * (env_first + e) + (h * pny + h) * ctx->esize,
                                              pny * ctx->esize, row, ctx->prob.nx, hipMemcpyDeviceToHost,
                                              ctx->stream));
   } else {
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host, (char*)ctx->Y + eb * env_first, eb * env_count,
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host, ctx->Y.as<char>() + eb * env_first, eb * env_count,
                                          hipMemcpyDeviceToHost, ctx->stream));
   }
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -681,7 +637,7 @@ int pdeopt_get_state(pdeopt_ctx* ctx, int env_first, int env_count, void* host) 
 int pdeopt_state_device_ptr(pdeopt_ctx* ctx, void** dev_ptr, int64_t* bytes) {
   if (!ctx || !dev_ptr) return PDEOPT_EINVAL;
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
-  *dev_ptr = ctx->Y;
+  *dev_ptr = ctx->Y.get();
   if (bytes) *bytes = (int64_t)ctx->total_bytes;
   return PDEOPT_OK;
 }
@@ -692,11 +648,11 @@ int pdeopt_rhs(pdeopt_ctx* ctx, double t, void* host_out) {
   if (ctx->prob.equation == PDEOPT_EQ_GPE)
     return fail(ctx, PDEOPT_EINVAL, "the GPE has no explicit RHS kernel (use the Strang integrator)");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes);
+  int rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes);
   if (rc) return rc;
-  if ((rc = launch_rhs(ctx, whole_batch(ctx), ctx->Y, ctx->TA, t))) return rc;
+  if ((rc = launch_rhs(ctx, whole_batch(ctx), ctx->Y.get(), ctx->TA.get(), t))) return rc;
   if (host_out) {
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->total_bytes, hipMemcpyDeviceToHost,
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA.get(), ctx->total_bytes, hipMemcpyDeviceToHost,
                                          ctx->stream));
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   }
@@ -830,9 +786,9 @@ int pdeopt_snapshot(pdeopt_ctx* ctx) {
   if (!ctx) return PDEOPT_EINVAL;
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_buffer(ctx, &ctx->SNAP, ctx->total_bytes);
+  int rc = ensure_buffer(ctx, ctx->SNAP, ctx->total_bytes);
   if (rc) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->SNAP, ctx->Y, ctx->total_bytes, hipMemcpyDeviceToDevice,
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->SNAP.get(), ctx->Y.get(), ctx->total_bytes, hipMemcpyDeviceToDevice,
                                        ctx->stream));
   return PDEOPT_OK;
 }
@@ -844,9 +800,9 @@ int pdeopt_get_interpolated(pdeopt_ctx* ctx, double theta, int env_first, int en
   if (rc) return rc;
   if (!ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = launch_lerp(ctx, ctx->SNAP, ctx->Y, ctx->TA, theta, env_first, env_count))) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->env_elems * ctx->esize * env_count,
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = launch_lerp(ctx, ctx->SNAP.get(), ctx->Y.get(), ctx->TA.get(), theta, env_first, env_count))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA.get(), ctx->env_elems * ctx->esize * env_count,
                                        hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
@@ -889,7 +845,7 @@ int pdeopt_observe_u8_device(pdeopt_ctx* ctx, double lo, double hi, int env_firs
   if (ctx->prob.equation == PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "observe_u8 needs a real field");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if ((rc = observe_u8(ctx, lo, hi, env_first, env_count, nullptr))) return rc;
-  *dev_out = ctx->obs_dev;
+  *dev_out = ctx->obs_dev.get();
   if (nbytes) *nbytes = (int64_t)ctx->env_elems * env_count;
   return PDEOPT_OK;
 }
@@ -1040,9 +996,9 @@ int pdeopt_tsit5_dense(pdeopt_ctx* ctx, double theta, double dt, int env_first, 
   if (!(theta >= 0.0 && theta <= 1.0)) return fail(ctx, PDEOPT_EINVAL, "theta = %g outside [0, 1]", theta);
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // TA is free between a trial and its commit (the candidate sits in TB)
-  if ((rc = tsit5_dense(ctx, theta, dt, env_first, env_count, ctx->TA))) return rc;
+  if ((rc = tsit5_dense(ctx, theta, dt, env_first, env_count, ctx->TA.get()))) return rc;
   const size_t eb = ctx->env_elems * ctx->esize;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, (const char*)ctx->TA + eb * env_first, eb * env_count,
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA.as<const char>() + eb * env_first, eb * env_count,
                                        hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
@@ -1059,6 +1015,9 @@ int pdeopt_get_counter(pdeopt_ctx* ctx, int which, int64_t* value) {
       return PDEOPT_OK;
     case PDEOPT_CNT_GROUP_STREAMS:
       *value = ctx->last_group_streams;
+      return PDEOPT_OK;
+    case PDEOPT_CNT_DEVICE_BYTES:
+      *value = g_device_bytes.load();
       return PDEOPT_OK;
     default:
       return fail(ctx, PDEOPT_EINVAL, "unknown counter %d", which);
@@ -1188,21 +1147,18 @@ int pdeopt_host_alloc(pdeopt_ctx* ctx, int64_t bytes, void** host) {
   if (!ctx || !host || bytes <= 0) return PDEOPT_EINVAL;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   *host = nullptr;
-  hipError_t e = hipHostMalloc(host, (size_t)bytes, hipHostMallocDefault);
-  if (e != hipSuccess) {
-    *host = nullptr;
-    return fail(ctx, PDEOPT_ENOMEM, "hipHostMalloc(%lld bytes) failed: %s", (long long)bytes, hipGetErrorString(e));
-  }
-  ctx->host_allocs.push_back(*host);
+  PinnedBuffer b;
+  if (const int rc = ensure_buffer(ctx, b, (size_t)bytes)) return rc;
+  *host = b.get();
+  ctx->host_allocs.push_back(std::move(b));
   return PDEOPT_OK;
 }
 
 int pdeopt_host_free(pdeopt_ctx* ctx, void* host) {
   if (!ctx) return PDEOPT_EINVAL;
   for (size_t i = 0; i < ctx->host_allocs.size(); ++i)
-    if (ctx->host_allocs[i] == host) {
+    if (ctx->host_allocs[i].get() == host) {
       PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipHostFree(host);
       ctx->host_allocs.erase(ctx->host_allocs.begin() + (long)i);
       return PDEOPT_OK;
     }
@@ -1213,7 +1169,12 @@ int pdeopt_buffer_alloc(pdeopt_ctx* ctx, int64_t bytes, void** dev) {
   if (!ctx || !dev || bytes <= 0) return PDEOPT_EINVAL;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   *dev = nullptr;
-  return ensure_buffer(ctx, dev, (size_t)bytes);
+  const hipError_t e = hipMalloc(dev, (size_t)bytes);  // the caller's from here on (pdeopt_buffer_free)
+  if (e != hipSuccess) {
+    *dev = nullptr;
+    return fail(ctx, PDEOPT_ENOMEM, "hipMalloc(%zu bytes) failed: %s", (size_t)bytes, hipGetErrorString(e));
+  }
+  return PDEOPT_OK;
 }
 
 int pdeopt_buffer_free(pdeopt_ctx* ctx, void* dev) {
@@ -1256,9 +1217,9 @@ __global__ void clock_stamp_kernel(unsigned long long* out) {
 int pdeopt_timer_start(pdeopt_ctx* ctx) {
   if (!ctx) return PDEOPT_EINVAL;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (!ctx->clock_stamps) PDEOPT_HIP_CHECK(ctx, hipMalloc(&ctx->clock_stamps, 4 * sizeof(unsigned long long)));
+  if (const int rc = ensure_buffer(ctx, ctx->clock_stamps, 4 * sizeof(unsigned long long))) return rc;
   PDEOPT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  hipLaunchKernelGGL(clock_stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, static_cast<unsigned long long*>(ctx->clock_stamps));
+  hipLaunchKernelGGL(clock_stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->clock_stamps.as<unsigned long long>());
   return PDEOPT_OK;
 }
 
@@ -1269,7 +1230,7 @@ int pdeopt_timer_clock(pdeopt_ctx* ctx, double* shader_hz) {
     // timing a few milliseconds on the wall clock around timer_stop would have booked as run time)
     PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     unsigned long long h[4] = {0, 0, 0, 0};
-    PDEOPT_HIP_CHECK(ctx, hipMemcpy(h, ctx->clock_stamps, sizeof(h), hipMemcpyDeviceToHost));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpy(h, ctx->clock_stamps.get(), sizeof(h), hipMemcpyDeviceToHost));
     ctx->timer_shader_hz = (h[3] > h[1] && h[2] > h[0]) ? (double)(h[2] - h[0]) / (double)(h[3] - h[1]) * 100.0e6 : 0.0;
   }
   *shader_hz = ctx->timer_shader_hz > 0.0 ? ctx->timer_shader_hz : 0.0;
@@ -1279,7 +1240,7 @@ int pdeopt_timer_clock(pdeopt_ctx* ctx, double* shader_hz) {
 int pdeopt_timer_stop(pdeopt_ctx* ctx, double* ms) {
   if (!ctx || !ms) return PDEOPT_EINVAL;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  unsigned long long* const st = static_cast<unsigned long long*>(ctx->clock_stamps);
+  unsigned long long* const st = ctx->clock_stamps.as<unsigned long long>();
   if (st) hipLaunchKernelGGL(clock_stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, st + 2);
   PDEOPT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));

@@ -501,14 +501,13 @@ struct BvState {
   double alpha = 0.5;
   int mode = 0;
   bool set = false;
-  void* par = nullptr;       // [batch][2] doubles
-  void* partials = nullptr;  // [batch][nwg][2] doubles
-  void* v = nullptr;         // [batch] doubles
+  DeviceBuffer par;       // [batch][2] doubles
+  DeviceBuffer partials;  // [batch][nwg][2] doubles
+  DeviceBuffer v;         // [batch] doubles
   int nwg = 0, batch = 0;
   // tangents (bv_sens_slopes / bv_sens_voltage): [B][P][nwg][2] partial sums and [B][1 + P] voltages, grown on demand
-  void* dpart = nullptr;
-  void* dv = nullptr;
-  size_t dpart_bytes = 0, dv_bytes = 0;
+  DeviceBuffer dpart;
+  DeviceBuffer dv;
 };
 
 namespace {
@@ -520,19 +519,18 @@ int bv_ensure(pdeopt_ctx* ctx) {
   const int nwg = ((p.nx + kBvRows - 1) / kBvRows) * ((p.ny + kBvCols - 1) / kBvCols);
   if (st->par && st->nwg == nwg && st->batch == p.batch) return PDEOPT_OK;
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  for (void** q : {&st->par, &st->partials, &st->v}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
+  st->par.reset();
+  st->partials.reset();
+  st->v.reset();
   st->nwg = nwg;
   st->batch = p.batch;
   st->set = false;
   int rc;
-  if ((rc = ensure_buffer(ctx, &st->par, sizeof(double) * 2 * (size_t)p.batch))) return rc;
-  if ((rc = ensure_buffer(ctx, &st->partials, sizeof(double) * 2 * (size_t)nwg * p.batch))) return rc;
-  if ((rc = ensure_buffer(ctx, &st->v, sizeof(double) * (size_t)p.batch))) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(st->par, 0, sizeof(double) * 2 * (size_t)p.batch, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(st->v, 0, sizeof(double) * (size_t)p.batch, ctx->stream));
+  if ((rc = ensure_buffer(ctx, st->par, sizeof(double) * 2 * (size_t)p.batch))) return rc;
+  if ((rc = ensure_buffer(ctx, st->partials, sizeof(double) * 2 * (size_t)nwg * p.batch))) return rc;
+  if ((rc = ensure_buffer(ctx, st->v, sizeof(double) * (size_t)p.batch))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(st->par.get(), 0, sizeof(double) * 2 * (size_t)p.batch, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(st->v.get(), 0, sizeof(double) * (size_t)p.batch, ctx->stream));
   return PDEOPT_OK;
 }
 
@@ -553,10 +551,10 @@ BvArgs<T> bv_args(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   BvState* st = ctx->bv;
   BvArgs<T> a{};
   a.s = s;
-  a.mu = static_cast<T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
-  a.partials = static_cast<double*>(st->partials) + (int64_t)w.lo * st->nwg * 2;
-  a.bv_v = static_cast<double*>(st->v) + w.lo;
-  a.par = static_cast<const double*>(st->par) + 2 * (int64_t)w.lo;
+  a.mu = ctx->KS.as<T>() + (int64_t)w.lo * s.g.bstride;
+  a.partials = st->partials.as<double>() + (int64_t)w.lo * st->nwg * 2;
+  a.bv_v = st->v.as<double>() + w.lo;
+  a.par = st->par.as<const double>() + 2 * (int64_t)w.lo;
   a.alpha = st->alpha;
   a.h2 = ctx->prob.hx * ctx->prob.hy;
   a.v_shift = (double)s.tw_a;
@@ -587,7 +585,7 @@ int launch_bv_stage(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   const bool sbm = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV;
   const dim3 grid = bv_grid(ctx, w.n), block(64, 4, 1);
   if (ctx->bv->mode == 1) {
-    if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
     const BvArgs<T> a = bv_args<T>(ctx, w, s);
     bv_launch_pass1<T>(ctx, w, a);
     hipLaunchKernelGGL((bv_rate_kernel<T, 0>), grid, block, 0, w.stream, a);
@@ -611,15 +609,15 @@ int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env
   if (mode != 0 && mode != 1) return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer mode %d: 0 = voltage given, 1 = constant current", mode);
   if (!std::isfinite(alpha)) return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer symmetry factor alpha must be finite");
   int rc;
-  const void* const par_before = ctx->bv ? ctx->bv->par : nullptr;
+  const void* const par_before = ctx->bv ? ctx->bv->par.get() : nullptr;
   if ((rc = bv_ensure(ctx))) return rc;
   BvState* st = ctx->bv;
   // alpha, the mode and the buffers are kernel arguments of a captured substep graph (the per-environment values are not)
-  if (st->par != par_before || st->alpha != alpha || st->mode != mode) graph_destroy(ctx);
+  if (st->par.get() != par_before || st->alpha != alpha || st->mode != mode) graph_destroy(ctx);
   st->alpha = alpha;
   st->mode = mode;
   const size_t bytes = sizeof(double) * 2 * (size_t)ctx->prob.batch;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(st->par, per_env, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(st->par.get(), per_env, bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // `per_env` is the caller's again
   st->set = true;
   ctx->tsit5_fsal_valid = false;
@@ -632,16 +630,16 @@ int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, 
   BvState* st = ctx->bv;
   if (recompute) {
     if (st->mode != 1) return fail(ctx, PDEOPT_EINVAL, "pdeopt_bv_voltage solves the constant-current constraint: set mode 1");
-    if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
     const Window w{env_first, env_count, ctx->stream};
     rc = with_dtype(ctx, [&](auto tag) -> int {
       using T = decltype(tag);
       StageArgs<T> s{};
       s.g = make_geo(ctx);
-      s.in = static_cast<const T*>(ctx->Y) + (int64_t)w.lo * s.g.bstride;
+      s.in = ctx->Y.as<const T>() + (int64_t)w.lo * s.g.bstride;
       set_recip_plain(s, grid_recip(ctx->prob));
       set_closures<T>(s, ctx, w.lo);
-      s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
+      s.psi = ctx->aux[PDEOPT_AUX_SBM_PSI].dev.as<const T>();
       const BvArgs<T> a = bv_args<T>(ctx, w, s);
       bv_launch_pass1<T>(ctx, w, a);
       hipLaunchKernelGGL(bv_finish_kernel, dim3(w.n), dim3(64), 0, w.stream, a.partials, a.par, a.nwg, a.h2, a.bv_v);
@@ -651,7 +649,7 @@ int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, 
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     ctx->last_kernel = "bv_mu_sums+bv_finish";
   }
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, static_cast<const double*>(st->v) + env_first, sizeof(double) * (size_t)env_count,
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, st->v.as<const double>() + env_first, sizeof(double) * (size_t)env_count,
                                        hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
@@ -670,38 +668,28 @@ int bv_sens_check(pdeopt_ctx* ctx, const BvSensSpec& sp) {
   return PDEOPT_OK;
 }
 
-// a buffer of at least `bytes`; a block that is too small is freed after the stream's work, which may still use it
-int bv_grow(pdeopt_ctx* ctx, void** p, size_t* have, size_t bytes) {
-  if (*p && *have >= bytes) return PDEOPT_OK;
-  if (*p) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    graph_destroy(ctx);
-  }
-  const int rc = ensure_buffer(ctx, p, bytes);
-  if (!rc) *have = bytes;
-  return rc;
-}
-
 template <typename T>
 int bv_sens_args(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out, BvSensArgs<T>* a) {
   BvState* st = ctx->bv;
   int rc;
-  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
-  if ((rc = bv_grow(ctx, &st->dpart, &st->dpart_bytes, sizeof(double) * 2 * (size_t)st->nwg * sp.B * sp.P))) return rc;
-  if ((rc = bv_grow(ctx, &st->dv, &st->dv_bytes, sizeof(double) * (size_t)sp.B * (1 + sp.P)))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
+  // a block that is too small is freed after the stream's work, which may still use it -- and so may a captured graph
+  const size_t dpart_bytes = sizeof(double) * 2 * (size_t)st->nwg * sp.B * sp.P, dv_bytes = sizeof(double) * (size_t)sp.B * (1 + sp.P);
+  const bool regrow = (st->dpart && st->dpart.bytes() < dpart_bytes) || (st->dv && st->dv.bytes() < dv_bytes);
+  if ((rc = grow_device_buffer(ctx, st->dpart, dpart_bytes, /*sync_first=*/true))) return rc;
+  if ((rc = grow_device_buffer(ctx, st->dv, dv_bytes, /*sync_first=*/true))) return rc;
+  if (regrow) graph_destroy(ctx);
   StageArgs<T> s{};
   s.g = make_geo(ctx);
   s.in = static_cast<const T*>(in);
   set_recip_plain(s, grid_recip(ctx->prob));
   set_closures<T>(s, ctx, 0);
-  s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
+  s.psi = ctx->aux[PDEOPT_AUX_SBM_PSI].dev.as<const T>();
   *a = BvSensArgs<T>{};
   a->f = bv_args<T>(ctx, Window{0, sp.B, ctx->stream}, s);
   a->out = static_cast<T*>(out);
-  a->dpart = static_cast<double*>(st->dpart);
-  a->dv = static_cast<double*>(st->dv);
+  a->dpart = st->dpart.as<double>();
+  a->dv = st->dv.as<double>();
   a->B = sp.B;
   a->P = sp.P;
   for (int j = 0; j < sp.P; ++j) {
@@ -757,7 +745,7 @@ int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out) {
   rc = with_dtype(ctx, [&](auto tag) -> int {
     using T = decltype(tag);
     BvSensArgs<T> a;
-    const int r = bv_sens_args<T>(ctx, sp, ctx->Y, nullptr, &a);
+    const int r = bv_sens_args<T>(ctx, sp, ctx->Y.get(), nullptr, &a);
     if (r) return r;
     bv_launch_pass1<T>(ctx, Window{0, sp.B, ctx->stream}, a.f);
     bv_sens_launch_tiles<T, 1>(ctx, a);
@@ -769,7 +757,7 @@ int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out) {
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   ctx->last_kernel = "bv_mu_sums+bvsens_tile+bv_finish+bvsens_finish";
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, st->dv, sizeof(double) * (size_t)sp.B * (1 + sp.P), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, st->dv.get(), sizeof(double) * (size_t)sp.B * (1 + sp.P), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -781,9 +769,6 @@ bool bv_time_dependent(const pdeopt_ctx* ctx) {
 }
 
 void bv_destroy(pdeopt_ctx* ctx) {
-  if (!ctx->bv) return;
-  for (void* q : {ctx->bv->par, ctx->bv->partials, ctx->bv->v, ctx->bv->dpart, ctx->bv->dv})
-    if (q) (void)hipFree(q);
   delete ctx->bv;
   ctx->bv = nullptr;
 }

@@ -45,18 +45,17 @@ struct pdeopt_cnn {
   std::vector<double> params;       // host copy, torch order
   bool have_params = false;
   // packed parameters on the device, in the problem dtype: per layer forward weights, backward weights, bias
-  void* packed = nullptr;
-  size_t packed_bytes = 0;
+  pdeopt::DeviceBuffer packed;  // grow-only
   int packed_dtype = -1;
   bool packed_valid = false;
   int64_t wf_off[kCnnMaxLayers + 1] = {}, wb_off[kCnnMaxLayers + 1] = {}, pb_off[kCnnMaxLayers + 1] = {};  // elements
   // scratch of the configured shape: a_l and z_l of the hidden layers, two delta fields, the wgrad partials
   int s_dtype = -1, s_nx = 0, s_ny = 0, s_batch = 0;
-  void* a[kCnnMaxLayers] = {};
-  void* z[kCnnMaxLayers] = {};
-  void* delta[2] = {};
-  void* partial = nullptr;
-  double* grad = nullptr;  // [n_params], fp64, accumulates until pdeopt_cnn_grad_read(reset)
+  pdeopt::DeviceBuffer a[kCnnMaxLayers];
+  pdeopt::DeviceBuffer z[kCnnMaxLayers];
+  pdeopt::DeviceBuffer delta[2];
+  pdeopt::DeviceBuffer partial;
+  pdeopt::DeviceBuffer grad;  // [n_params], fp64, accumulates until pdeopt_cnn_grad_read(reset)
 };
 
 namespace pdeopt {
@@ -281,17 +280,9 @@ inline int tiles_y(const pdeopt_ctx* ctx) { return (ctx->prob.nx + kPR - 1) / kP
 inline int wgrad_groups(int ntiles, int pairs) { return std::min(ntiles, std::max(1, 512 / pairs)); }
 
 void free_scratch(pdeopt_cnn* n) {
-  for (int l = 0; l < kCnnMaxLayers; ++l) {
-    if (n->a[l]) (void)hipFree(n->a[l]);
-    if (n->z[l]) (void)hipFree(n->z[l]);
-    n->a[l] = n->z[l] = nullptr;
-  }
-  for (void*& d : n->delta) {
-    if (d) (void)hipFree(d);
-    d = nullptr;
-  }
-  if (n->partial) (void)hipFree(n->partial);
-  n->partial = nullptr;
+  for (int l = 0; l < kCnnMaxLayers; ++l) n->a[l].reset(), n->z[l].reset();
+  for (DeviceBuffer& d : n->delta) d.reset();
+  n->partial.reset();
   n->s_dtype = -1;
 }
 
@@ -321,15 +312,9 @@ int upload_packed(pdeopt_cnn* n) {
     for (int o = 0; o < Co; ++o) h[n->pb_off[l] + o] = (T)n->params[n->b_off[l] + o];
   }
   const size_t bytes = (size_t)total * sizeof(T);
-  if (n->packed && n->packed_bytes != bytes) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(n->packed);
-    n->packed = nullptr;
-  }
-  if (const int rc = ensure_buffer(ctx, &n->packed, bytes)) return rc;
-  n->packed_bytes = bytes;
+  if (const int rc = grow_device_buffer(ctx, n->packed, bytes, /*sync_first=*/true)) return rc;
   // the staging vector dies with this call: the copy is complete for the host when it returns (pageable memory)
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(n->packed, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(n->packed.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   n->packed_dtype = ctx->prob.dtype;
   n->packed_valid = true;
@@ -361,12 +346,12 @@ int prepare(pdeopt_cnn* n, bool backward, std::initializer_list<const void*> fie
   int cmax = 16;
   for (int l = 1; l < n->L; ++l) {
     cmax = std::max(cmax, n->Cp[l]);
-    if ((rc = ensure_buffer(ctx, &n->a[l], cells * n->Cp[l] * ctx->esize))) return rc;
-    if (backward && (rc = ensure_buffer(ctx, &n->z[l], cells * n->Cp[l] * ctx->esize))) return rc;
+    if ((rc = ensure_buffer(ctx, n->a[l], cells * n->Cp[l] * ctx->esize))) return rc;
+    if (backward && (rc = ensure_buffer(ctx, n->z[l], cells * n->Cp[l] * ctx->esize))) return rc;
   }
   if (backward) {
-    for (void*& d : n->delta)
-      if ((rc = ensure_buffer(ctx, &d, cells * cmax * ctx->esize))) return rc;
+    for (DeviceBuffer& d : n->delta)
+      if ((rc = ensure_buffer(ctx, d, cells * cmax * ctx->esize))) return rc;
     const int ntiles = p.batch * tiles_x(ctx) * tiles_y(ctx);
     size_t most = 0;
     for (int l = 1; l <= n->L; ++l) {
@@ -374,7 +359,7 @@ int prepare(pdeopt_cnn* n, bool backward, std::initializer_list<const void*> fie
       const size_t G = wgrad_groups(ntiles, pairs);
       most = std::max(most, G * pairs * (9 * 256) + G * (n->Cp[l] / 16) * 16);
     }
-    if ((rc = ensure_buffer(ctx, &n->partial, most * ctx->esize))) return rc;
+    if ((rc = ensure_buffer(ctx, n->partial, most * ctx->esize))) return rc;
   }
   return PDEOPT_OK;
 }
@@ -411,11 +396,11 @@ int launch_conv(pdeopt_ctx* ctx, int act, const ConvArgs<T>& a) {
 template <typename T>
 int forward(pdeopt_cnn* n, const void* u, void* mu, bool keep_z) {
   pdeopt_ctx* ctx = n->ctx;
-  const T* P = static_cast<const T*>(n->packed);
+  const T* P = n->packed.as<const T>();
   for (int l = 1; l <= n->L; ++l) {
     if (l == n->L && !mu) break;
     ConvArgs<T> a{};
-    a.in = l == 1 ? static_cast<const T*>(u) : static_cast<const T*>(n->a[l - 1]);
+    a.in = l == 1 ? static_cast<const T*>(u) : n->a[l - 1].as<const T>();
     a.in_scalar = l == 1;
     a.w = P + n->wf_off[l];
     a.bias = P + n->pb_off[l];
@@ -425,8 +410,8 @@ int forward(pdeopt_cnn* n, const void* u, void* mu, bool keep_z) {
       a.out = static_cast<T*>(mu);
     } else {
       a.epi = EPI_ACT;
-      a.out = static_cast<T*>(n->a[l]);
-      a.z_out = keep_z ? static_cast<T*>(n->z[l]) : nullptr;
+      a.out = n->a[l].as<T>();
+      a.z_out = keep_z ? n->z[l].as<T>() : nullptr;
     }
     if (const int rc = launch_conv<T>(ctx, n->act, a)) return rc;
   }
@@ -437,25 +422,25 @@ template <typename T>
 int backward(pdeopt_cnn* n, const void* u, const void* gmu, void* lam) {
   pdeopt_ctx* ctx = n->ctx;
   const pdeopt_problem& p = ctx->prob;
-  const T* P = static_cast<const T*>(n->packed);
+  const T* P = n->packed.as<const T>();
   const int ntiles = p.batch * tiles_x(ctx) * tiles_y(ctx);
   const T* del = static_cast<const T*>(gmu);  // delta_L
   for (int l = n->L; l >= 1; --l) {
     const int Cip = n->Cp[l - 1], Cop = n->Cp[l];
     const int nti = Cip / 16, nto = Cop / 16;
     WgradArgs<T> w{};
-    w.act = l == 1 ? static_cast<const T*>(u) : static_cast<const T*>(n->a[l - 1]);
+    w.act = l == 1 ? static_cast<const T*>(u) : n->a[l - 1].as<const T>();
     w.act_scalar = l == 1;
     w.del = del;
     w.del_scalar = l == n->L;
-    w.partial = static_cast<T*>(n->partial);
+    w.partial = n->partial.as<T>();
     w.nx = p.nx, w.ny = p.ny, w.Cip = Cip, w.Cop = Cop;
     w.G = wgrad_groups(ntiles, nti * nto);
     w.tiles_x = tiles_x(ctx), w.tiles_y = tiles_y(ctx), w.ntiles = ntiles;
     hipLaunchKernelGGL(cnn_wgrad_kernel<T>, dim3(w.G, nti, nto), dim3(256), 0, ctx->stream, w);
     const int64_t entries = (int64_t)nto * nti * (9 * 256) + nto * 16;
     hipLaunchKernelGGL(cnn_wgrad_reduce_kernel<T>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, ctx->stream,
-                       static_cast<const T*>(n->partial), n->grad + n->w_off[l], n->grad + n->b_off[l], w.G, nto, nti, n->C[l],
+                       n->partial.as<const T>(), n->grad.as<double>() + n->w_off[l], n->grad.as<double>() + n->b_off[l], w.G, nto, nti, n->C[l],
                        n->C[l - 1]);
     ctx->n_stage_launches += 2;
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -470,8 +455,8 @@ int backward(pdeopt_cnn* n, const void* u, const void* gmu, void* lam) {
       a.out = static_cast<T*>(lam);
     } else {
       a.epi = EPI_DACT;
-      a.zaux = static_cast<const T*>(n->z[l - 1]);
-      a.out = static_cast<T*>(n->delta[l & 1]);
+      a.zaux = n->z[l - 1].as<const T>();
+      a.out = n->delta[l & 1].as<T>();
     }
     if (const int rc = launch_conv<T>(ctx, n->act, a)) return rc;
     del = a.out;
@@ -510,14 +495,16 @@ int pdeopt_cnn_create(pdeopt_ctx* ctx, int n_layers, const int* channels, int ac
     n->n_params = n->b_off[l] + n->C[l];
   }
   const auto bail = [&](hipError_t e, const char* what) {
-    if (n->grad) (void)hipFree(n->grad);
     delete n;
     return fail(ctx, PDEOPT_EHIP, "%s failed: %s", what, hipGetErrorString(e));
   };
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return bail(e, "hipSetDevice");
-  if ((e = hipMalloc((void**)&n->grad, n->n_params * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemsetAsync(n->grad, 0, n->n_params * sizeof(double), ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+  if (const int rc = ensure_buffer(ctx, n->grad, n->n_params * sizeof(double))) {
+    delete n;
+    return rc;
+  }
+  if ((e = hipMemsetAsync(n->grad.as<double>(), 0, n->n_params * sizeof(double), ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
   *out = n;
   return PDEOPT_OK;
 }
@@ -565,8 +552,8 @@ int pdeopt_cnn_grad_read(pdeopt_cnn* n, double* out, int64_t count, int reset) {
   if (!out || count != n->n_params)
     return fail(ctx, PDEOPT_EINVAL, "the CNN has %lld parameters (got %lld)", (long long)n->n_params, (long long)count);
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, n->grad, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(n->grad, 0, count * sizeof(double), ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, n->grad.as<double>(), count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(n->grad.as<double>(), 0, count * sizeof(double), ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -575,9 +562,6 @@ int pdeopt_cnn_destroy(pdeopt_cnn* n) {
   if (!n) return PDEOPT_OK;
   (void)hipSetDevice(n->ctx->device);
   if (n->ctx->stream) (void)hipStreamSynchronize(n->ctx->stream);
-  free_scratch(n);
-  if (n->packed) (void)hipFree(n->packed);
-  if (n->grad) (void)hipFree(n->grad);
   delete n;
   return PDEOPT_OK;
 }

@@ -91,12 +91,12 @@ struct CommState {
   int world = 0, rank = 0;
   hipStream_t cstream = nullptr;          // collectives
   hipEvent_t packed = nullptr, gathered = nullptr;
-  void* send = nullptr;                   // strip of this rank
-  void* recv = nullptr;                   // strips of all ranks, rank-major
+  DeviceBuffer send;                      // strip of this rank
+  DeviceBuffer recv;                      // strips of all ranks, rank-major
   size_t strip_bytes = 0;
   // in-process backend (pdeopt_comm_init_local): no RCCL, copies between the ranks' buffers
   pdeopt_local_group* group = nullptr;
-  void* send2 = nullptr;                  // second send buffer (parity 1)
+  DeviceBuffer send2;                     // second send buffer (parity 1)
   uint64_t seq = 0;                       // exchanges done so far
   // peer-mapped backend (pdeopt_comm_ipc_export / _attach): every rank's strip buffers are mapped into every process
   // (hipIpc), a rank's fused-pack epilogue writes its own strip, its neighbours' fused unpack reads it in place; two
@@ -107,7 +107,7 @@ struct CommState {
   std::vector<void*> peer_block;          // every rank's block as mapped here (own: ipc_block)
   unsigned* ipc_err_dev = nullptr;        // time-out flag of the wait kernel (in the own block)
   bool local() const { return group != nullptr; }
-  void* send_buf() const { return local() && (seq & 1) ? send2 : send; }  // where the NEXT exchange's strip goes
+  void* send_buf() const { return local() && (seq & 1) ? send2.get() : send.get(); }  // where the NEXT exchange's strip goes
 };
 
 namespace {
@@ -235,9 +235,7 @@ void comm_destroy(pdeopt_ctx* ctx) {
       c->group->arrived = 0;
     }
   }
-  if (c->send2) (void)hipFree(c->send2);
-  if (c->send) (void)hipFree(c->send);
-  if (c->recv) (void)hipFree(c->recv);
+  c->send2.reset(), c->send.reset(), c->recv.reset();  // before the stream the collectives ran on goes
   if (c->packed) (void)hipEventDestroy(c->packed);
   if (c->gathered) (void)hipEventDestroy(c->gathered);
   if (c->cstream) (void)hipStreamDestroy(c->cstream);
@@ -268,7 +266,7 @@ int local_all_gather(pdeopt_ctx* ctx, CommState& c) {
       return fail(ctx, PDEOPT_EINVAL, "local group: rank %d publishes a strip of %zu bytes, this rank expects %zu", r, bytes, c.strip_bytes);
     }
     if (r != c.rank) PDEOPT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, g.ready[p][r], 0));
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync((char*)c.recv + (size_t)r * bytes, src, bytes, hipMemcpyDefault, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(c.recv.as<char>() + (size_t)r * bytes, src, bytes, hipMemcpyDefault, ctx->stream));
   }
   PDEOPT_HIP_CHECK(ctx, hipEventRecord(g.done[p][c.rank], ctx->stream));
   {
@@ -474,18 +472,15 @@ int rk4_decomposed_advance(pdeopt_ctx* ctx, double dt, int64_t n, const int* nbr
       std::lock_guard<std::mutex> lk(c.group->m);
       c.group->send[0][c.rank] = c.group->send[1][c.rank] = nullptr;
     }
-    if (c.send) (void)hipFree(c.send);
-    if (c.send2) (void)hipFree(c.send2);
-    if (c.recv) (void)hipFree(c.recv);
-    c.send = c.send2 = c.recv = nullptr;
-    if ((rc = ensure_buffer(ctx, &c.send, strip_bytes))) return rc;
-    if (c.local() && (rc = ensure_buffer(ctx, &c.send2, strip_bytes))) return rc;
-    if ((rc = ensure_buffer(ctx, &c.recv, strip_bytes * (size_t)c.world))) return rc;
+    c.send.reset(), c.send2.reset(), c.recv.reset();
+    if ((rc = ensure_buffer(ctx, c.send, strip_bytes))) return rc;
+    if (c.local() && (rc = ensure_buffer(ctx, c.send2, strip_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, c.recv, strip_bytes * (size_t)c.world))) return rc;
     c.strip_bytes = strip_bytes;
     if (c.local()) {
       std::lock_guard<std::mutex> lk(c.group->m);
-      c.group->send[0][c.rank] = c.send;
-      c.group->send[1][c.rank] = c.send2;
+      c.group->send[0][c.rank] = c.send.get();
+      c.group->send[1][c.rank] = c.send2.get();
       c.group->send_bytes[c.rank] = strip_bytes;
     }
   }
@@ -495,7 +490,7 @@ int rk4_decomposed_advance(pdeopt_ctx* ctx, double dt, int64_t n, const int* nbr
   // the collective: all ranks' strips (this rank's in `send`) -> c.recv, rank-major, on `stream`
   auto all_gather = [&](void* send, hipStream_t stream) -> int {
     if (c.local()) return local_all_gather(ctx, c);  // (always on the compute stream)
-    PDEOPT_NCCL_CHECK(ctx, c, c.all_gather(send, c.recv, strip_elems, dtype, c.comm, stream));
+    PDEOPT_NCCL_CHECK(ctx, c, c.all_gather(send, c.recv.get(), strip_elems, dtype, c.comm, stream));
     return PDEOPT_OK;
   };
   auto abort_group = [&](int code) {
@@ -579,7 +574,7 @@ int rk4_decomposed_advance(pdeopt_ctx* ctx, double dt, int64_t n, const int* nbr
       if (more && c.local() && (rc = local_wait_send_free(ctx, c))) return abort_group(rc);
       send = c.send_buf();
       // no unpack launch: the first pair's edge tiles read the halo from c.recv (and fill the field's frame)
-      if ((rc = rk4_substep_h8(ctx, dt, more ? send : nullptr, c.recv, nbr))) return abort_group(rc);
+      if ((rc = rk4_substep_h8(ctx, dt, more ? send : nullptr, c.recv.get(), nbr))) return abort_group(rc);
       if (more && (rc = all_gather(send, ctx->stream))) return abort_group(rc);
     }
     return PDEOPT_OK;
@@ -598,11 +593,11 @@ int rk4_decomposed_advance(pdeopt_ctx* ctx, double dt, int64_t n, const int* nbr
         PDEOPT_HIP_CHECK(ctx, hipEventRecord(c.gathered, c.cstream));
         if ((rc = rk4_phase(ctx, ph, dt, 1))) return rc;  // interior tiles: no halo reads
         PDEOPT_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, c.gathered, 0));
-        if ((rc = halo_unpack(ctx, fields[ph], c.recv, nbr))) return rc;
+        if ((rc = halo_unpack(ctx, fields[ph], c.recv.get(), nbr))) return rc;
         if ((rc = rk4_phase(ctx, ph, dt, 2))) return rc;  // edge tiles
       } else {
         if ((rc = all_gather(send, ctx->stream))) return abort_group(rc);
-        if ((rc = halo_unpack(ctx, fields[ph], c.recv, nbr))) return abort_group(rc);
+        if ((rc = halo_unpack(ctx, fields[ph], c.recv.get(), nbr))) return abort_group(rc);
         if ((rc = rk4_phase(ctx, ph, dt, 0))) return abort_group(rc);
       }
     }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/pdeopt_hip.h"
+#include "device_buffer.hpp"
 
 namespace pdeopt {
 
@@ -111,13 +112,12 @@ struct Geo {
 };
 
 struct AuxField {
-  void* dev = nullptr;
+  DeviceBuffer dev;  // its bytes() is the size of the field in the sharing mode of per_env
   int per_env = 0;
-  size_t bytes = 0;
   // time-dependent source (pdeopt_set_aux_time_fn): host callback, pinned staging buffer, time last uploaded
   pdeopt_aux_fn fn = nullptr;
   void* user = nullptr;
-  void* stage = nullptr;
+  PinnedBuffer stage;
   double t_loaded = 0.0;
   bool loaded = false;
 };
@@ -156,7 +156,7 @@ struct pdeopt_ctx {
   hipStream_t stream = nullptr;
   bool stream_borrowed = false;  // stream belongs to the caller (pdeopt_ctx_create_on_stream)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  void* clock_stamps = nullptr;   // [start, stop] x (s_memtime, s_memrealtime) of the timer pair
+  pdeopt::DeviceBuffer clock_stamps;  // [start, stop] x (s_memtime, s_memrealtime) of the timer pair
   double timer_shader_hz = 0.0;   // shader clock held between the last pdeopt_timer_start / _stop (0: not measured)
   std::string err;
   std::string last_kernel;
@@ -167,16 +167,13 @@ struct pdeopt_ctx {
   size_t env_elems = 0;    // real elements per environment
   size_t total_bytes = 0;  // one field, whole batch
   // field buffers (device).  Y always holds the current state.
-  void* Y = nullptr;
-  void* TA = nullptr;
-  void* TB = nullptr;
-  void* ACC = nullptr;
-  void* SNAP = nullptr;
-  void* obs_dev = nullptr;  // uint8 observation frames
-  void* vort_dev = nullptr; // vortex counters + winding map
-  size_t vort_cap = 0;
-  void* KS = nullptr;  // slope scratch of the spectral-RHS stage path
-  void* K[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // Tsit5 slopes
+  // Every DeviceBuffer / PinnedBuffer member frees itself with the ctx; free_fields (api.hip) resets the ones that die
+  // with a configuration, the others are grow-only and live as long as the ctx.
+  pdeopt::DeviceBuffer Y, TA, TB, ACC, SNAP;
+  pdeopt::DeviceBuffer obs_dev;   // uint8 observation frames
+  pdeopt::DeviceBuffer vort_dev;  // vortex counters + winding map; grow-only
+  pdeopt::DeviceBuffer KS;        // slope scratch of the spectral-RHS stage path
+  pdeopt::DeviceBuffer K[7];      // Tsit5 slopes
   bool tsit5_pending = false;
   bool tsit5_fsal_valid = false;
   bool slope_scaled = false;           // stage launches multiply k by EnvParams::kscale (per-environment dt)
@@ -196,7 +193,7 @@ struct pdeopt_ctx {
   // the three scalars the last right-hand-side launch of a time-dependent equation resolved (make_args): the tangent
   // kernels of the smoothed-boundary equations take theirs from here, so tangent and base see identical numbers
   double time_last[3] = {0.0, 0.0, 0.0};
-  void* env_params_dev = nullptr;
+  pdeopt::DeviceBuffer env_params_dev;
   std::vector<char> env_params_host;
   pdeopt::AuxField aux[pdeopt::kNumAux];
   std::string jit_src[2];  // pdeopt_set_jit_closures: C function bodies of mu / mobility (closure kind PDEOPT_CL_JIT)
@@ -206,9 +203,8 @@ struct pdeopt_ctx {
   int64_t n_stage_launches = 0;  // fused stencil+update launches issued so far
   int64_t opt_halo = 0;          // requested halo width of the NEXT configure (0 periodic, 4 or 8 padded)
   int halo = 0;                  // halo width of the configured layout
-  void* halo_scratch = nullptr;  // single-rank loop-back buffer for pack/unpack
-  void* halo_scratch2 = nullptr; // second loop-back strip (halo-8 loop: fused pack writes one while the next is read)
-  size_t halo_scratch_bytes = 0, halo_scratch2_bytes = 0;
+  pdeopt::DeviceBuffer halo_scratch;   // single-rank loop-back buffer for pack/unpack; grow-only
+  pdeopt::DeviceBuffer halo_scratch2;  // second loop-back strip (halo-8 loop: fused pack writes one while the next is read)
   int64_t opt_imex_lds_fft = 0;  // IMEX transforms: 0 auto (hand-written passes where the size is covered), -1 rocFFT
   int64_t opt_graph = 0;         // hipGraph replay of the substep loop: 0 auto (launch-bound sizes), 1 always, -1 never
   hipGraphExec_t graph_exec = nullptr;
@@ -217,11 +213,11 @@ struct pdeopt_ctx {
   std::string graph_name;
   int64_t opt_fuse_stages = 0;   // RK4 stage-pair fusion: 0 auto, -1 off (one launch per stage), 1 stage pairs (AC: no single-pass kernel)
   int64_t opt_debug_ablate = 0;  // timing-only ablations, results are wrong when set
-  // device work block of the one-launch solves (ensure_adaptive_block): the adaptive solves' save times, statistics and
-  // save slots (small_tsit5_solve, coop_tsit5_solve; the latter also its barrier words and partial sums), the
-  // multi-workgroup fixed step's tags (coop_fixed_advance)
-  void* adaptive_blk = nullptr;
-  size_t adaptive_cap = 0;
+  // device work block of the one-launch solves: the adaptive solves' save times, statistics and save slots
+  // (small_tsit5_solve, coop_tsit5_solve; the latter also its barrier words and partial sums), the multi-workgroup fixed
+  // step's tags (coop_fixed_advance).  Grow-only: a solve of a 64^2 grid is a few hundred microseconds, a hipMalloc /
+  // hipFree pair is not free
+  pdeopt::DeviceBuffer adaptive_blk;
   int64_t opt_group_streams = 0;  // PDEOPT_OPT_GROUP_STREAMS
   // second stream of the two-groups-side-by-side schedule and its fork / join events (created on first use); only
   // run_groups (groups.hpp) names them, launch helpers see the stream as part of a Window
@@ -230,25 +226,22 @@ struct pdeopt_ctx {
   int64_t opt_small_persist = 0; // whole-environment-step kernel for LDS-resident grids: 0 auto, 1 wherever it can, -1 never
   // Gaussian light spots of the GPE (pdeopt_set_gpe_spots)
   int n_spots = 0;
-  void* spots_dev = nullptr;
+  pdeopt::DeviceBuffer spots_dev;
   std::vector<pdeopt_light_spot> spots_host;  // [batch][PDEOPT_MAX_SPOTS]
   double spots_x_first = 0.0, spots_y_first = 0.0;
   bool imex_per_env = false;  // some environment has imex_scale != 1: one environment per complex field
   int64_t last_group_streams = 1;  // PDEOPT_CNT_GROUP_STREAMS
   int64_t last_groups = 1;    // environment groups of the last advance (PDEOPT_CNT_LAST_GROUPS)
   double imex_A = 0.5, ts_re = 1.0, ts_im = 0.0, strang_dx = 1.0;
-  double* red_dev = nullptr;  // reduction scratch
-  size_t red_cap = 0;
-  double* red_mean_dev = nullptr;
-  double* pf_obs_dev = nullptr;  // pdeopt_pf_observables: the rows [envs][8], then the workgroups' partial rows; grow-only
-  size_t pf_obs_cap = 0;
-  // pdeopt_structure_factor: the axis tables t_0 | t_1 (| t_2) of pdeopt_sk_configure (dropped with the field buffers;
+  pdeopt::DeviceBuffer red_dev;  // reduction scratch (doubles); grow-only
+  pdeopt::DeviceBuffer red_mean_dev;
+  pdeopt::DeviceBuffer pf_obs_dev;  // pdeopt_pf_observables: the rows [envs][8], then the workgroups' partial rows; grow-only
+  // pdeopt_structure_factor: the axis tables t_0 | t_1 (| t_2) of pdeopt_sk_configure (reset by free_fields through sk_drop;
   // sk_bins = 0: none), and the call's work block -- the rows [envs][n_bins], then the workgroups' rows; grow-only
-  double* sk_tab_dev = nullptr;
+  pdeopt::DeviceBuffer sk_tab_dev;
   int sk_bins = 0;
-  double* sk_dev = nullptr;
-  size_t sk_cap = 0;
-  std::vector<void*> host_allocs;  // pdeopt_host_alloc
+  pdeopt::DeviceBuffer sk_dev;
+  std::vector<pdeopt::PinnedBuffer> host_allocs;  // pdeopt_host_alloc
   pdeopt::CommState* comm = nullptr;
   pdeopt::Spectral* spectral = nullptr;
   pdeopt::StrangFused* strang_fused = nullptr;
@@ -262,11 +255,11 @@ struct pdeopt_ctx {
   pdeopt::GpeObs* gpe_obs = nullptr;
   pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
   pdeopt::GpeRotAdjoint* gpe_rot_stir_adjoint = nullptr;  // the stirred entry point's own (other partial blocks)
-  pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; lives and dies with the field buffers
-  pdeopt::Implicit* implicit = nullptr;  // pdeopt_implicit_configure; lives and dies with the field buffers
+  pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; owns its buffers, deleted by free_fields
+  pdeopt::Implicit* implicit = nullptr;  // pdeopt_implicit_configure; owns its workspace, deleted by free_fields
   // pdeopt_fieldmu_adjoint_step_coef: fp64 partial sums of the mobility's coefficient gradient, one slot per
-  // (trajectory, tile, coefficient); lives with the field buffers, zeroed by pdeopt_configure
-  double* fieldmu_coef = nullptr;
+  // (trajectory, tile, coefficient); reset by free_fields, zeroed by pdeopt_configure
+  pdeopt::DeviceBuffer fieldmu_coef;
   size_t fieldmu_coef_slots = 0;
 };
 
@@ -314,13 +307,13 @@ inline bool bv_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_BV || eq == 
                           hipGetErrorString(e_), __FILE__, __LINE__);                      \
   } while (0)
 
-int ensure_buffer(pdeopt_ctx* ctx, void** p, size_t bytes);
-// *p holds at least need_bytes afterwards: a block that is too small is freed first (sync_first: after the stream's work,
-// which may still use it); *have_bytes is the capacity of *p, grow-only
-int grow_device_buffer(pdeopt_ctx* ctx, void** p, size_t* have_bytes, size_t need_bytes, bool sync_first);
-// ctx->adaptive_blk holds at least `bytes` afterwards.  Kept with the ctx, grow-only: a solve of a 64^2 grid is a few
-// hundred microseconds, a hipMalloc / hipFree pair is not free
-int ensure_adaptive_block(pdeopt_ctx* ctx, size_t bytes);
+// b holds `bytes` afterwards: allocated when empty; an existing block that is too small is PDEOPT_ESTATE (its owner
+// should have reset it, or the site should grow)
+int ensure_buffer(pdeopt_ctx* ctx, DeviceBuffer& b, size_t bytes);
+int ensure_buffer(pdeopt_ctx* ctx, PinnedBuffer& b, size_t bytes);
+// b holds at least need_bytes afterwards, grow-only: a block that is too small is freed first (sync_first: after the
+// stream's work, which may still use it)
+int grow_device_buffer(pdeopt_ctx* ctx, DeviceBuffer& b, size_t need_bytes, bool sync_first);
 int ensure_stream2(pdeopt_ctx* ctx);  // the ctx's second stream + fork / join events, created on first use
 // api.hip: bring a time-dependent auxiliary field to local time t (no-op for static fields)
 int refresh_time_aux(pdeopt_ctx* ctx, int which, double t);
@@ -360,7 +353,7 @@ template <typename T>
 inline SpotArgs<T> make_spot_args(const pdeopt_ctx* ctx, int first_env, double t) {
   SpotArgs<T> a{};
   a.n = ctx->n_spots;
-  a.table = a.n ? static_cast<const LightSpot<T>*>(ctx->spots_dev) + (size_t)first_env * PDEOPT_MAX_SPOTS : nullptr;
+  a.table = a.n ? ctx->spots_dev.as<const LightSpot<T>>() + (size_t)first_env * PDEOPT_MAX_SPOTS : nullptr;
   a.t = T(t);
   a.x_first = T(ctx->spots_x_first);
   a.y_first = T(ctx->spots_y_first);
@@ -465,18 +458,18 @@ int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::comp
 // one unnormalised complex transform along ONE axis (0: x, lines of stride ny; 1: y, contiguous lines) of a
 // whole-batch field [batch][nx][ny], in place, on the ctx's stream: rocFFT batched 1-D plans, any grid
 int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf);
-// gpe_rot.hip: the rotating-frame ADI split step (PDEOPT_INT_STRANG_ROT); buffers live and die with the spectral state
+// gpe_rot.hip: the rotating-frame ADI split step (PDEOPT_INT_STRANG_ROT); GpeRot owns its buffers, spectral_destroy deletes it
 int advance_strang_rot(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
 void gpe_rot_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_destroy(pdeopt_ctx* ctx);
-// gpe_rot_adjoint.hip: the adjoint of that step; its buffers live and die with the spectral state too
+// gpe_rot_adjoint.hip: the adjoint of that step; its state owns its buffers and is deleted by spectral_destroy too
 void gpe_rot_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_adjoint_destroy(pdeopt_ctx* ctx);
 // gpe_rot_adjoint.hip too: the adjoint of the stirred, ramped step (spots and Omega(t)); buffers as above
 void gpe_rot_stir_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_rot_stir_adjoint_destroy(pdeopt_ctx* ctx);
 // gpe_obs.hip: energy terms, angular momentum and moments of the resident GPE state, [env_count][PDEOPT_GPE_OBS_COUNT]
-// doubles; its buffers live and die with the spectral state
+// doubles; GpeObs owns its buffers, spectral_destroy deletes it
 int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
                     double* host_out);
 void gpe_obs_destroy(pdeopt_ctx* ctx);
@@ -484,16 +477,15 @@ void gpe_obs_destroy(pdeopt_ctx* ctx);
 // CH, AC, CH-3D with finite differences), [env_count][PDEOPT_PF_OBS_COUNT] doubles; refuses what it does not cover
 int pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 // structure_factor.hip: the shell sums P_b of the resident real state's power spectrum, [env_count][n_bins] doubles, from
-// the axis tables of sk_configure; sk_drop forgets the tables (a new grid), sk_destroy frees the work block too
+// the axis tables of sk_configure; sk_drop forgets the tables (a new grid), the work block lives with the ctx
 int sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const double* t2, int n_bins);
 int structure_factor(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 void sk_drop(pdeopt_ctx* ctx);
-void sk_destroy(pdeopt_ctx* ctx);
-// gpe_adjoint.hip: its buffers live and die with the spectral state (spectral_destroy / spectral_invalidate)
+// gpe_adjoint.hip: GpeAdjoint owns its buffers; deleted by spectral_destroy, its multiplier dropped by spectral_invalidate
 void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
 void gpe_adjoint_destroy(pdeopt_ctx* ctx);
 // butler_volmer.hip: parameters of the Butler-Volmer equations; the voltage of the resident state (recompute) or the one
-// the last right-hand side used; its buffers live and die with the field buffers
+// the last right-hand side used; BvState owns its buffers, free_fields deletes it
 int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env);
 int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, bool recompute);
 void bv_destroy(pdeopt_ctx* ctx);
@@ -518,7 +510,7 @@ bool bv_params_set(const pdeopt_ctx* ctx);  // has pdeopt_set_bv_params been cal
 int sbm_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out);
 inline bool sbm_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM; }
 void sens_destroy(pdeopt_ctx* ctx);
-// implicit.hip: n implicit Euler steps (stats: [batch][4] totals or nullptr); its workspace lives and dies with the field buffers
+// implicit.hip: n implicit Euler steps (stats: [batch][4] totals or nullptr); Implicit owns its workspace, free_fields deletes it
 int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* stats);
 void implicit_destroy(pdeopt_ctx* ctx);
 void strang_fused_invalidate(pdeopt_ctx* ctx);

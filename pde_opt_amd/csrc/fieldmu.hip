@@ -260,7 +260,7 @@ int check_fieldmu(pdeopt_ctx* ctx, std::initializer_list<const void*> fields) {
     if (!f || (uintptr_t)f % ctx->esize)
       return fail(ctx, PDEOPT_EINVAL, "field pointer %p: device fields are [batch][nx][ny] in the problem dtype, aligned to it", f);
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return ensure_buffer(ctx, &ctx->TA, ctx->total_bytes);
+  return ensure_buffer(ctx, ctx->TA, ctx->total_bytes);
 }
 
 // the integrators of a field-mu step; IMEX also prepares the multiplier of step dt
@@ -298,7 +298,7 @@ inline dim3 tile_grid(const pdeopt_ctx* ctx) {
 int launch_fieldmu_rhs(pdeopt_ctx* ctx, const void* muh, void* out) {
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(fieldmu_rhs_kernel<T>, tile_grid(ctx), dim3(256), 0, ctx->stream, fieldmu_args<T>(ctx, ctx->Y, muh, out));
+    hipLaunchKernelGGL(fieldmu_rhs_kernel<T>, tile_grid(ctx), dim3(256), 0, ctx->stream, fieldmu_args<T>(ctx, ctx->Y.get(), muh, out));
     ctx->n_stage_launches++;
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     return (int)PDEOPT_OK;
@@ -324,8 +324,8 @@ int check_coef(pdeopt_ctx* ctx) {
   if (ctx->fieldmu_coef) return PDEOPT_OK;
   const dim3 g = tile_grid(ctx);
   ctx->fieldmu_coef_slots = (size_t)g.x * g.y * g.z * kMaxCoef;
-  if (const int rc = ensure_buffer(ctx, reinterpret_cast<void**>(&ctx->fieldmu_coef), ctx->fieldmu_coef_slots * sizeof(double))) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef, 0, ctx->fieldmu_coef_slots * sizeof(double), ctx->stream));
+  if (const int rc = ensure_buffer(ctx, ctx->fieldmu_coef, ctx->fieldmu_coef_slots * sizeof(double))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef.as<double>(), 0, ctx->fieldmu_coef_slots * sizeof(double), ctx->stream));
   return PDEOPT_OK;
 }
 
@@ -345,7 +345,7 @@ int adjoint_step(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, 
       overlap(lam_dev, mu_dev))
     return fail(ctx, PDEOPT_EINVAL, "lam_dev and gmu_dev are written: they must not overlap each other or the inputs");
   // TA = S lambda: the kernel reads lambda on a ring while it updates lambda itself, so it reads the copy
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->TA, lam_dev, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->TA.get(), lam_dev, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
   if (integrator == PDEOPT_INT_IMEX) {
     if ((rc = imex_rocfft_apply(ctx))) return rc;
     ctx->n_stage_launches += 3;
@@ -353,11 +353,11 @@ int adjoint_step(pdeopt_ctx* ctx, int integrator, double dt, const void* u_dev, 
   rc = with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
     FieldMuArgs<T> a = fieldmu_args<T>(ctx, u_dev, mu_dev, gmu_dev);
-    a.lam = static_cast<const T*>(ctx->TA);
+    a.lam = ctx->TA.as<const T>();
     a.lam_io = static_cast<T*>(lam_dev);
     a.scale = (T)dt;
     if (coef)
-      hipLaunchKernelGGL(fieldmu_adjoint_coef_kernel<T>, tile_grid(ctx), dim3(256), 0, ctx->stream, a, ctx->fieldmu_coef);
+      hipLaunchKernelGGL(fieldmu_adjoint_coef_kernel<T>, tile_grid(ctx), dim3(256), 0, ctx->stream, a, ctx->fieldmu_coef.as<double>());
     else
       hipLaunchKernelGGL(fieldmu_adjoint_kernel<T>, tile_grid(ctx), dim3(256), 0, ctx->stream, a);
     ctx->n_stage_launches++;
@@ -391,7 +391,7 @@ int pdeopt_fieldmu_step(pdeopt_ctx* ctx, int integrator, double dt, const void* 
   if (rc || (rc = check_step(ctx, integrator, dt))) return rc;
   ctx->tsit5_pending = false;
   ctx->tsit5_fsal_valid = false;
-  if ((rc = launch_fieldmu_rhs(ctx, mu_dev, ctx->TA))) return rc;
+  if ((rc = launch_fieldmu_rhs(ctx, mu_dev, ctx->TA.get()))) return rc;
   if (integrator == PDEOPT_INT_IMEX) {
     rc = imex_rocfft_solve(ctx, dt);
     ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls, as pdeopt_sens_advance counts them)
@@ -424,8 +424,8 @@ int pdeopt_fieldmu_coef_grad_read(pdeopt_ctx* ctx, double* out_host, int n, int 
   if (!ctx->fieldmu_coef) return PDEOPT_OK;  // no pdeopt_fieldmu_adjoint_step_coef since the buffers were made
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   std::vector<double> slots(ctx->fieldmu_coef_slots);
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(slots.data(), ctx->fieldmu_coef, slots.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef, 0, slots.size() * sizeof(double), ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(slots.data(), ctx->fieldmu_coef.as<double>(), slots.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(ctx->fieldmu_coef.as<double>(), 0, slots.size() * sizeof(double), ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t s = 0; s < slots.size(); s += kMaxCoef)  // trajectories, then tiles: one fixed order
     for (int k = 0; k < n; ++k) out_host[k] += slots[s + k];

@@ -28,12 +28,12 @@
 namespace pdeopt {
 
 struct GpeAdjoint {
-  void* work = nullptr;    // a, then c               [batch][nx][ny] complex
-  void* direct = nullptr;  // -2 k g_beta psi0        same
-  void* mult = nullptr;    // E / (nx ny)             [nx][ny] complex
-  double* part = nullptr;  // [batch][kBlocks][2]
-  double* spart = nullptr; // [batch][kBlocks][kSpotSums]
-  double* gacc = nullptr;  // [batch][PDEOPT_MAX_SPOTS][7]: staging of a host gradient block
+  DeviceBuffer work;    // a, then c               [batch][nx][ny] complex
+  DeviceBuffer direct;  // -2 k g_beta psi0        same
+  DeviceBuffer mult;    // E / (nx ny)             [nx][ny] complex
+  DeviceBuffer part;    // doubles [batch][kBlocks][2]
+  DeviceBuffer spart;   // doubles [batch][kBlocks][kSpotSums]
+  DeviceBuffer gacc;    // doubles [batch][PDEOPT_MAX_SPOTS][7]: staging of a host gradient block
   bool mult_valid = false;
   double key_dt = NAN, key_tr = NAN, key_ti = NAN;
 };
@@ -236,8 +236,8 @@ int ensure_mult(pdeopt_ctx* ctx, GpeAdjoint& ga, double dt) {
     const std::complex<double> e = std::exp(at[i] * 0.5 * tau) * inv_n;
     m[i] = C2<T>{(T)e.real(), (T)e.imag()};
   }
-  if ((rc = ensure_buffer(ctx, &ga.mult, m.size() * sizeof(C2<T>)))) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ga.mult, m.data(), m.size() * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ensure_buffer(ctx, ga.mult, m.size() * sizeof(C2<T>)))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ga.mult.get(), m.data(), m.size() * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ga.mult_valid = true;
   ga.key_dt = dt;
@@ -251,7 +251,7 @@ template <typename T, bool CONJ>
 int round_trip(pdeopt_ctx* ctx, GpeAdjoint& ga, void* buf, dim3 grid, int64_t cells) {
   int rc = spectral_c2c(ctx, true, buf);
   if (rc) return rc;
-  hipLaunchKernelGGL((gpe_adjoint_mul_kernel<T, CONJ>), grid, dim3(256), 0, ctx->stream, (C2<T>*)buf, (const C2<T>*)ga.mult, cells);
+  hipLaunchKernelGGL((gpe_adjoint_mul_kernel<T, CONJ>), grid, dim3(256), 0, ctx->stream, (C2<T>*)buf, ga.mult.as<const C2<T>>(), cells);
   return spectral_c2c(ctx, false, buf);
 }
 
@@ -266,11 +266,11 @@ int adjoint_step_t(pdeopt_ctx* ctx, double t0, double dt, const void* psi0, void
   const AuxField& pot = ctx->aux[PDEOPT_AUX_GPE_POTENTIAL];
   const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
   GpeAdjArgs<T> a{};
-  a.work = (C2<T>*)ga.work;
+  a.work = ga.work.as<C2<T>>();
   a.psi0 = (const C2<T>*)psi0;
   a.lam = (C2<T>*)lam;
-  a.direct = (C2<T>*)ga.direct;
-  a.pot = (const T*)pot.dev;
+  a.direct = ga.direct.as<C2<T>>();
+  a.pot = pot.dev.as<const T>();
   a.pot_stride = pot.per_env ? cells : 0;
   a.ep = env_params<T>(ctx, 0);
   a.tr = (T)tau.real();
@@ -278,20 +278,20 @@ int adjoint_step_t(pdeopt_ctx* ctx, double t0, double dt, const void* psi0, void
   a.cells = cells;
   a.ny = p.ny;
   a.h2 = ctx->strang_dx * ctx->strang_dx;
-  a.part = ga.part;
-  a.spart = ga.spart;
+  a.part = ga.part.as<double>();
+  a.spart = ga.spart.as<double>();
   a.spots = make_spot_args<T>(ctx, 0, t0);
   // a = K psi0
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ga.work, psi0, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  if ((rc = round_trip<T, false>(ctx, ga, ga.work, grid, cells))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ga.work.get(), psi0, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  if ((rc = round_trip<T, false>(ctx, ga, ga.work.get(), grid, cells))) return rc;
   // lambda_d = K^H lambda1
   if ((rc = round_trip<T, true>(ctx, ga, lam, grid, cells))) return rc;
   hipLaunchKernelGGL(gpe_adjoint_recompute_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   hipLaunchKernelGGL(gpe_adjoint_pointwise_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   // lambda0 = K^H lambda_a + direct
   if ((rc = round_trip<T, true>(ctx, ga, lam, grid, cells))) return rc;
-  hipLaunchKernelGGL(gpe_adjoint_finish_kernel<T>, grid, dim3(256), 0, ctx->stream, (C2<T>*)lam, (const C2<T>*)ga.direct, cells,
-                     (const double*)ga.spart, grad_dev, ctx->n_spots, t0);
+  hipLaunchKernelGGL(gpe_adjoint_finish_kernel<T>, grid, dim3(256), 0, ctx->stream, (C2<T>*)lam, ga.direct.as<const C2<T>>(), cells,
+                     ga.spart.as<const double>(), grad_dev, ctx->n_spots, t0);
   ctx->n_stage_launches += 12;  // 6 transforms, 3 multiplies, 3 passes
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -304,12 +304,7 @@ void gpe_adjoint_invalidate(pdeopt_ctx* ctx) {
 }
 
 void gpe_adjoint_destroy(pdeopt_ctx* ctx) {
-  GpeAdjoint* ga = ctx->gpe_adjoint;
-  if (!ga) return;
-  void* bufs[] = {ga->work, ga->direct, ga->mult, ga->part, ga->spart, ga->gacc};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete ga;
+  delete ctx->gpe_adjoint;
   ctx->gpe_adjoint = nullptr;
 }
 
@@ -353,14 +348,14 @@ int pdeopt_gpe_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* p
   if (!ctx->gpe_adjoint) ctx->gpe_adjoint = new GpeAdjoint();
   GpeAdjoint& ga = *ctx->gpe_adjoint;
   int rc;
-  if ((rc = ensure_buffer(ctx, &ga.work, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ga.direct, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&ga.part, sizeof(double) * (size_t)p.batch * kBlocks * 2))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&ga.spart, sizeof(double) * (size_t)p.batch * kBlocks * kSpotSums))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&ga.gacc, sizeof(double) * (size_t)p.batch * PDEOPT_MAX_SPOTS * 7))) return rc;
+  if ((rc = ensure_buffer(ctx, ga.work, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ga.direct, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ga.part, sizeof(double) * (size_t)p.batch * kBlocks * 2))) return rc;
+  if ((rc = ensure_buffer(ctx, ga.spart, sizeof(double) * (size_t)p.batch * kBlocks * kSpotSums))) return rc;
+  if ((rc = ensure_buffer(ctx, ga.gacc, sizeof(double) * (size_t)p.batch * PDEOPT_MAX_SPOTS * 7))) return rc;
   double* gdev = grad;
   if (!grad_on_device) {
-    gdev = ga.gacc;
+    gdev = ga.gacc.as<double>();
     PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(gdev, 0, gbytes, ctx->stream));
   }
   rc = with_dtype(ctx, [&](auto t) { return adjoint_step_t<decltype(t)>(ctx, t0, dt, psi0_dev, lam_dev, gdev); });

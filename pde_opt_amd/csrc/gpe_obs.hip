@@ -34,13 +34,14 @@
 namespace pdeopt {
 
 struct GpeObs {
-  void* tw_x = nullptr;  // twiddle tables exp(-2 pi i n / N) in the problem dtype
-  void* tw_y = nullptr;
-  void* work = nullptr;  // library path: the copy of the state rocFFT transforms in place
-  double* part8 = nullptr;   // [batch][n8][8]: pointwise sums (+ the Py-weighted ones of the hand-written row pass)
-  double* part_y = nullptr;  // [batch][kLibBlocks][2]: (e_kin, l_z) share of the y transform, library path
-  double* part_x = nullptr;  // [batch][nx_blocks][2]: (e_kin, l_z) share of the x transform
-  double* out = nullptr;     // [batch][8]
+  DeviceBuffer tw_x;  // twiddle tables exp(-2 pi i n / N) in the problem dtype
+  DeviceBuffer tw_y;
+  DeviceBuffer work;  // library path: the copy of the state rocFFT transforms in place
+  // doubles:
+  DeviceBuffer part8;   // [batch][n8][8]: pointwise sums (+ the Py-weighted ones of the hand-written row pass)
+  DeviceBuffer part_y;  // [batch][kLibBlocks][2]: (e_kin, l_z) share of the y transform, library path
+  DeviceBuffer part_x;  // [batch][nx_blocks][2]: (e_kin, l_z) share of the x transform
+  DeviceBuffer out;     // [batch][8]
 };
 
 namespace {
@@ -261,10 +262,10 @@ int launch_gobs_row(pdeopt_ctx* ctx, GpeObs& go, int env_first, int env_count, c
   if (rc) return rc;
   const int64_t cells = (int64_t)p.nx * p.ny, w0 = env_first;
   const int blocks = (int)((int64_t)env_count * p.nx / F);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, ctx->stream, (const Cx<T>*)ctx->Y + w0 * cells,
-                     pot.dev ? (const T*)pot.dev + (pot.per_env ? w0 * cells : 0) : nullptr,
-                     pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, env_first), sa, (const Cx<T>*)go.tw_y, p.nx, gm,
-                     go.part8);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, ctx->stream, ctx->Y.as<const Cx<T>>() + w0 * cells,
+                     pot.dev ? pot.dev.as<const T>() + (pot.per_env ? w0 * cells : 0) : nullptr,
+                     pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, env_first), sa, go.tw_y.as<const Cx<T>>(), p.nx, gm,
+                     go.part8.as<double>());
   return PDEOPT_OK;
 }
 
@@ -278,7 +279,7 @@ int launch_gobs_col(pdeopt_ctx* ctx, GpeObs& go, int env_first, int env_count, c
   if (rc) return rc;
   const int64_t cells = (int64_t)p.nx * p.ny;
   hipLaunchKernelGGL(kern, dim3(p.ny / C, env_count), dim3(C * N / reg_default_pts<N>()), lds, ctx->stream,
-                     (const Cx<T>*)ctx->Y + (int64_t)env_first * cells, (const Cx<T>*)go.tw_x, p.ny, gm, go.part_x);
+                     ctx->Y.as<const Cx<T>>() + (int64_t)env_first * cells, go.tw_x.as<const Cx<T>>(), p.ny, gm, go.part_x.as<double>());
   return PDEOPT_OK;
 }
 
@@ -308,12 +309,12 @@ int gobs_library_axis(pdeopt_ctx* ctx, GpeObs& go, int axis, int env_first, int 
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   const size_t bytes = (size_t)cells * p.batch * sizeof(Cx<T>);
-  int rc = ensure_buffer(ctx, &go.work, bytes);
+  int rc = ensure_buffer(ctx, go.work, bytes);
   if (rc) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(go.work, ctx->Y, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  if ((rc = spectral_c2c_axis(ctx, axis, true, go.work))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(go.work.get(), ctx->Y.get(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  if ((rc = spectral_c2c_axis(ctx, axis, true, go.work.get()))) return rc;
   hipLaunchKernelGGL(gobs_spec_kernel<T>, dim3(kLibBlocks, env_count), dim3(256), 0, ctx->stream,
-                     (const Cx<T>*)go.work + (int64_t)env_first * cells, axis, p.nx, p.ny, gm, part);
+                     go.work.as<const Cx<T>>() + (int64_t)env_first * cells, axis, p.nx, p.ny, gm, part);
   return PDEOPT_OK;
 }
 
@@ -332,12 +333,12 @@ int gpe_observables_t(pdeopt_ctx* ctx, double t, int env_first, int env_count, d
   const bool col_fused = ctx->opt_kernel_path != 1 && gobs_size_ok(p.nx) && p.ny % gobs_cols_rt<T>(p.nx) == 0;
   int rc;
   // sized for either path of either axis: at most nx row workgroups and ny column workgroups per environment
-  if ((rc = ensure_buffer(ctx, (void**)&go.part8, sizeof(double) * kObs * (size_t)p.batch * std::max(p.nx, kLibBlocks)))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&go.part_y, sizeof(double) * 2 * (size_t)p.batch * kLibBlocks))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&go.part_x, sizeof(double) * 2 * (size_t)p.batch * std::max(p.ny, kLibBlocks)))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&go.out, sizeof(double) * kObs * (size_t)p.batch))) return rc;
-  if (row_fused && !go.tw_y && (rc = upload_table<T>(ctx, &go.tw_y, p.ny))) return rc;
-  if (col_fused && !go.tw_x && (rc = upload_table<T>(ctx, &go.tw_x, p.nx))) return rc;
+  if ((rc = ensure_buffer(ctx, go.part8, sizeof(double) * kObs * (size_t)p.batch * std::max(p.nx, kLibBlocks)))) return rc;
+  if ((rc = ensure_buffer(ctx, go.part_y, sizeof(double) * 2 * (size_t)p.batch * kLibBlocks))) return rc;
+  if ((rc = ensure_buffer(ctx, go.part_x, sizeof(double) * 2 * (size_t)p.batch * std::max(p.ny, kLibBlocks)))) return rc;
+  if ((rc = ensure_buffer(ctx, go.out, sizeof(double) * kObs * (size_t)p.batch))) return rc;
+  if (row_fused && !go.tw_y && (rc = upload_table<T>(ctx, go.tw_y, p.ny))) return rc;
+  if (col_fused && !go.tw_x && (rc = upload_table<T>(ctx, go.tw_x, p.nx))) return rc;
   if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_GPE_POTENTIAL, t))) return rc;
   const AuxField& pot = ctx->aux[PDEOPT_AUX_GPE_POTENTIAL];
   const SpotArgs<T> sa = make_spot_args<T>(ctx, env_first, t);
@@ -355,10 +356,10 @@ int gpe_observables_t(pdeopt_ctx* ctx, double t, int env_first, int env_count, d
     npy = 0;
   } else {
     hipLaunchKernelGGL(gobs_point_kernel<T>, dim3(kLibBlocks, env_count), dim3(256), 0, ctx->stream,
-                       (const Cx<T>*)ctx->Y + (int64_t)env_first * cells,
-                       pot.dev ? (const T*)pot.dev + (pot.per_env ? (int64_t)env_first * cells : 0) : nullptr,
-                       pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, env_first), sa, p.nx, p.ny, gm, go.part8);
-    if ((rc = gobs_library_axis<T>(ctx, go, 1, env_first, env_count, gm, go.part_y))) return rc;
+                       ctx->Y.as<const Cx<T>>() + (int64_t)env_first * cells,
+                       pot.dev ? pot.dev.as<const T>() + (pot.per_env ? (int64_t)env_first * cells : 0) : nullptr,
+                       pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, env_first), sa, p.nx, p.ny, gm, go.part8.as<double>());
+    if ((rc = gobs_library_axis<T>(ctx, go, 1, env_first, env_count, gm, go.part_y.as<double>()))) return rc;
     n8 = kLibBlocks;
     npy = kLibBlocks;
   }
@@ -366,13 +367,13 @@ int gpe_observables_t(pdeopt_ctx* ctx, double t, int env_first, int env_count, d
     if ((rc = gobs_col_dispatch<T>(ctx, go, env_first, env_count, gm))) return rc;
     npx = p.ny / gobs_cols_rt<T>(p.nx);
   } else {
-    if ((rc = gobs_library_axis<T>(ctx, go, 0, env_first, env_count, gm, go.part_x))) return rc;
+    if ((rc = gobs_library_axis<T>(ctx, go, 0, env_first, env_count, gm, go.part_x.as<double>()))) return rc;
     npx = kLibBlocks;
   }
-  hipLaunchKernelGGL(gobs_finish_kernel, dim3(env_count), dim3(64), 0, ctx->stream, (const double*)go.part8, n8,
-                     (const double*)go.part_y, npy, (const double*)go.part_x, npx, p.hx * p.hy, go.out);
+  hipLaunchKernelGGL(gobs_finish_kernel, dim3(env_count), dim3(64), 0, ctx->stream, go.part8.as<const double>(), n8,
+                     go.part_y.as<const double>(), npy, go.part_x.as<const double>(), npx, p.hx * p.hy, go.out.as<double>());
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, go.out, sizeof(double) * kObs * (size_t)env_count, hipMemcpyDeviceToHost,
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, go.out.as<double>(), sizeof(double) * kObs * (size_t)env_count, hipMemcpyDeviceToHost,
                                        ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->last_kernel = row_fused && col_fused ? "gpe_obs_fused_lds_fft" : row_fused || col_fused ? "gpe_obs_mixed" : "gpe_obs_rocfft_1d";
@@ -389,12 +390,7 @@ int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, dou
 }
 
 void gpe_obs_destroy(pdeopt_ctx* ctx) {
-  GpeObs* go = ctx->gpe_obs;
-  if (!go) return;
-  void* bufs[] = {go->tw_x, go->tw_y, go->work, go->part8, go->part_y, go->part_x, go->out};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete go;
+  delete ctx->gpe_obs;
   ctx->gpe_obs = nullptr;
 }
 

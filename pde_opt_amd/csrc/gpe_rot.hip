@@ -470,12 +470,12 @@ int launch_rot_row(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<do
   auto launch = [&](auto kern, auto... clock_args) -> int {
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (Cx<T>*)ctx->Y + w0 * cells,
-                       (const T*)gr.dens + w0 * cells,
-                       pot.dev ? (const T*)pot.dev + (pot.per_env ? w0 * cells : 0) : nullptr,
-                       pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, w.lo), (const Cx<T>*)gr.tw_y,
-                       (const Cx<T>*)gr.kin_y, (T)tau.real(), (T)tau.imag(), rot_axis<T>(ctx, 1, 0.5 * tau), p.nx,
-                       gr.partial + w0 * gr.partial_per_env, clock_args...);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, ctx->Y.as<Cx<T>>() + w0 * cells,
+                       gr.dens.as<const T>() + w0 * cells,
+                       pot.dev ? pot.dev.as<const T>() + (pot.per_env ? w0 * cells : 0) : nullptr,
+                       pot.per_env ? cells : (int64_t)0, env_params<T>(ctx, w.lo), gr.tw_y.as<const Cx<T>>(),
+                       gr.kin_y.as<const Cx<T>>(), (T)tau.real(), (T)tau.imag(), rot_axis<T>(ctx, 1, 0.5 * tau), p.nx,
+                       gr.partial.as<double>() + w0 * gr.partial_per_env, clock_args...);
     ctx->n_stage_launches++;
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     return PDEOPT_OK;
@@ -505,9 +505,9 @@ int launch_rot_col(pdeopt_ctx* ctx, const Window& w, GpeRot& gr, std::complex<do
       int rc = allow_lds(ctx, kern, lds);
       if (rc) return rc;
       hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * N / reg_default_pts<N>()), lds, w.stream,
-                         (Cx<T>*)ctx->Y + w0 * cells, (T*)gr.dens + w0 * cells, env_params<T>(ctx, w.lo),
-                         (const Cx<T>*)gr.tw_x, (const Cx<T>*)gr.kin_x, rot_axis<T>(ctx, 0, 0.5 * tau), p.ny,
-                         (const double*)gr.partial + w0 * gr.partial_per_env, gr.partial_per_env,
+                         ctx->Y.as<Cx<T>>() + w0 * cells, gr.dens.as<T>() + w0 * cells, env_params<T>(ctx, w.lo),
+                         gr.tw_x.as<const Cx<T>>(), gr.kin_x.as<const Cx<T>>(), rot_axis<T>(ctx, 0, 0.5 * tau), p.ny,
+                         gr.partial.as<const double>() + w0 * gr.partial_per_env, gr.partial_per_env,
                          ctx->strang_dx * ctx->strang_dx, clock_args...);
       ctx->n_stage_launches++;
       PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -547,7 +547,7 @@ int rot_library_step(pdeopt_ctx* ctx, GpeRot& gr, std::complex<double> tau, doub
   const dim3 mgrid(g1, p.batch);
   const EnvParams<T>* ep = env_params<T>(ctx, 0);
   const double dx2 = ctx->strang_dx * ctx->strang_dx;
-  Cx<T>* const y = (Cx<T>*)ctx->Y;
+  Cx<T>* const y = ctx->Y.as<Cx<T>>();
   int rc;
   // one line operator along `axis`: transform, multiply (scaled: by the norm's scale too), transform back
   auto line = [&](auto axis, auto scaled) -> int {
@@ -556,8 +556,8 @@ int rot_library_step(pdeopt_ctx* ctx, GpeRot& gr, std::complex<double> tau, doub
     int r = spectral_c2c_axis(ctx, A, true, y);
     if (r) return r;
     auto launch = [&](auto kern, auto... clock_args) {
-      hipLaunchKernelGGL(kern, mgrid, dim3(256), 0, ctx->stream, y, (const Cx<T>*)(A == 0 ? gr.kin_x : gr.kin_y), ep,
-                         rot_axis<T>(ctx, A, 0.5 * tau), p.nx, p.ny, S ? (const double*)gr.partial : nullptr,
+      hipLaunchKernelGGL(kern, mgrid, dim3(256), 0, ctx->stream, y, (const Cx<T>*)(A == 0 ? gr.kin_x.get() : gr.kin_y.get()), ep,
+                         rot_axis<T>(ctx, A, 0.5 * tau), p.nx, p.ny, S ? gr.partial.as<const double>() : nullptr,
                          S ? kLibNormBlocks : 0, dx2, clock_args...);
     };
     if constexpr (STIRRED) launch(rstir_mul_kernel<T, A, S>, (T)t);
@@ -567,16 +567,16 @@ int rot_library_step(pdeopt_ctx* ctx, GpeRot& gr, std::complex<double> tau, doub
   constexpr std::integral_constant<int, 0> along_x{};
   constexpr std::integral_constant<int, 1> along_y{};
   hipLaunchKernelGGL(rot_density_kernel<T>, dim3((int)std::min<int64_t>(4096, (total + 255) / 256)), dim3(256), 0,
-                     ctx->stream, (const Cx<T>*)y, (T*)gr.dens, total);
+                     ctx->stream, (const Cx<T>*)y, gr.dens.as<T>(), total);
   if ((rc = line(along_x, std::false_type{}))) return rc;
   if ((rc = line(along_y, std::false_type{}))) return rc;
   auto launch_b = [&](auto kern, auto... clock_args) {
-    hipLaunchKernelGGL(kern, dim3(kLibNormBlocks, p.batch), dim3(256), 0, ctx->stream, y, (const T*)gr.dens,
-                       (const T*)pot.dev, pot.per_env ? cells : (int64_t)0, ep, (T)tau.real(), (T)tau.imag(), cells,
+    hipLaunchKernelGGL(kern, dim3(kLibNormBlocks, p.batch), dim3(256), 0, ctx->stream, y, gr.dens.as<const T>(),
+                       pot.dev.as<const T>(), pot.per_env ? cells : (int64_t)0, ep, (T)tau.real(), (T)tau.imag(), cells,
                        clock_args...);
   };
-  if constexpr (STIRRED) launch_b(rstir_b_kernel<T>, p.ny, gr.partial, make_spot_args<T>(ctx, 0, t));
-  else launch_b(rot_b_kernel<T>, gr.partial);
+  if constexpr (STIRRED) launch_b(rstir_b_kernel<T>, p.ny, gr.partial.as<double>(), make_spot_args<T>(ctx, 0, t));
+  else launch_b(rot_b_kernel<T>, gr.partial.as<double>());
   if ((rc = line(along_y, std::false_type{}))) return rc;
   if ((rc = line(along_x, std::true_type{}))) return rc;
   ctx->n_stage_launches += 6;
@@ -596,23 +596,23 @@ int rot_prepare_t(pdeopt_ctx* ctx, double dt, bool* fused_out) {
   int rc;
   if (!gr.dens) {
     if (fused) {
-      if ((rc = upload_table<T>(ctx, &gr.tw_x, p.nx))) return rc;
-      if ((rc = upload_table<T>(ctx, &gr.tw_y, p.ny))) return rc;
+      if ((rc = upload_table<T>(ctx, gr.tw_x, p.nx))) return rc;
+      if ((rc = upload_table<T>(ctx, gr.tw_y, p.ny))) return rc;
     }
-    if ((rc = ensure_buffer(ctx, &gr.dens, (size_t)cells * p.batch * sizeof(T)))) return rc;
+    if ((rc = ensure_buffer(ctx, gr.dens, (size_t)cells * p.batch * sizeof(T)))) return rc;
     const size_t np = (size_t)std::max(p.nx, kLibNormBlocks);
-    if ((rc = ensure_buffer(ctx, (void**)&gr.partial, sizeof(double) * (size_t)p.batch * np))) return rc;
+    if ((rc = ensure_buffer(ctx, gr.partial, sizeof(double) * (size_t)p.batch * np))) return rc;
   }
   if (fused && !gr.tw_x) {  // the library path ran first (PDEOPT_OPT_KERNEL_PATH changed in between)
-    if ((rc = upload_table<T>(ctx, &gr.tw_x, p.nx))) return rc;
-    if ((rc = upload_table<T>(ctx, &gr.tw_y, p.ny))) return rc;
+    if ((rc = upload_table<T>(ctx, gr.tw_x, p.nx))) return rc;
+    if ((rc = upload_table<T>(ctx, gr.tw_y, p.ny))) return rc;
   }
   gr.partial_per_env = fused ? p.nx / rot_row_lines_rt(p.ny) : kLibNormBlocks;
   const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
   if (!gr.valid || gr.key_dt != dt || gr.key_tr != ctx->ts_re || gr.key_ti != ctx->ts_im || gr.key_hx != p.hx ||
       gr.key_hy != p.hy) {
-    if ((rc = upload_kinetic<T>(ctx, &gr.kin_x, p.nx, p.hx, 0.5 * tau))) return rc;
-    if ((rc = upload_kinetic<T>(ctx, &gr.kin_y, p.ny, p.hy, 0.5 * tau))) return rc;
+    if ((rc = upload_kinetic<T>(ctx, gr.kin_x, p.nx, p.hx, 0.5 * tau))) return rc;
+    if ((rc = upload_kinetic<T>(ctx, gr.kin_y, p.ny, p.hy, 0.5 * tau))) return rc;
     gr.valid = true;
     gr.key_dt = dt;
     gr.key_tr = ctx->ts_re;
@@ -680,12 +680,7 @@ void gpe_rot_invalidate(pdeopt_ctx* ctx) {
 }
 
 void gpe_rot_destroy(pdeopt_ctx* ctx) {
-  GpeRot* gr = ctx->gpe_rot;
-  if (!gr) return;
-  void* bufs[] = {gr->tw_x, gr->tw_y, gr->kin_x, gr->kin_y, gr->dens, gr->partial};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete gr;
+  delete ctx->gpe_rot;
   ctx->gpe_rot = nullptr;
 }
 

@@ -69,14 +69,14 @@ namespace pdeopt {
 
 // one per entry point (ctx->gpe_rot_adjoint, ctx->gpe_rot_stir_adjoint): their partial blocks differ in size
 struct GpeRotAdjoint {
-  void* work = nullptr;   // the running primal field, at the end S4     [batch][nx][ny] complex
-  void* cbuf = nullptr;   // c, then the direct term 2 k g_w psi0         same
-  void* spec[3] = {nullptr, nullptr, nullptr};  // S1, S2, S3              same
-  void* kin_x = nullptr;  // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
-  void* kin_y = nullptr;
-  double* part = nullptr; // [batch][kBlocks][kSlots or kStirSlots]
-  double* gacc = nullptr; // [batch][3 or 4]: staging of a host gradient block
-  double* sacc = nullptr; // stirred only: [batch][PDEOPT_MAX_SPOTS][7], staging of a host spot block
+  DeviceBuffer work;     // the running primal field, at the end S4     [batch][nx][ny] complex
+  DeviceBuffer cbuf;     // c, then the direct term 2 k g_w psi0         same
+  DeviceBuffer spec[3];  // S1, S2, S3                                   same
+  DeviceBuffer kin_x;    // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
+  DeviceBuffer kin_y;
+  DeviceBuffer part;     // doubles [batch][kBlocks][kSlots or kStirSlots]
+  DeviceBuffer gacc;     // doubles [batch][3 or 4]: staging of a host gradient block
+  DeviceBuffer sacc;     // doubles, stirred only: [batch][PDEOPT_MAX_SPOTS][7], staging of a host spot block
   double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
   bool valid = false;
 };
@@ -468,8 +468,8 @@ int ensure_tables(pdeopt_ctx* ctx, GpeRotAdjoint& ra, double dt) {
     return PDEOPT_OK;
   const std::complex<double> half_tau = 0.5 * dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
   int rc;
-  if ((rc = upload_kinetic<T>(ctx, &ra.kin_x, p.nx, p.hx, half_tau))) return rc;
-  if ((rc = upload_kinetic<T>(ctx, &ra.kin_y, p.ny, p.hy, half_tau))) return rc;
+  if ((rc = upload_kinetic<T>(ctx, ra.kin_x, p.nx, p.hx, half_tau))) return rc;
+  if ((rc = upload_kinetic<T>(ctx, ra.kin_y, p.ny, p.hy, half_tau))) return rc;
   ra.valid = true;
   ra.key_dt = dt;
   ra.key_tr = ctx->ts_re;
@@ -484,13 +484,13 @@ template <bool STIRRED>
 int ensure_work(pdeopt_ctx* ctx, GpeRotAdjoint& ra) {
   const size_t batch = (size_t)ctx->prob.batch;
   int rc;
-  if ((rc = ensure_buffer(ctx, &ra.work, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ra.cbuf, ctx->total_bytes))) return rc;
-  for (void*& s : ra.spec)
-    if ((rc = ensure_buffer(ctx, &s, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&ra.part, sizeof(double) * batch * kBlocks * (STIRRED ? kStirSlots : kSlots)))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&ra.gacc, sizeof(double) * batch * (STIRRED ? 4 : 3)))) return rc;
-  if (STIRRED && (rc = ensure_buffer(ctx, (void**)&ra.sacc, sizeof(double) * batch * PDEOPT_MAX_SPOTS * 7))) return rc;
+  if ((rc = ensure_buffer(ctx, ra.work, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ra.cbuf, ctx->total_bytes))) return rc;
+  for (DeviceBuffer& s : ra.spec)
+    if ((rc = ensure_buffer(ctx, s, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ra.part, sizeof(double) * batch * kBlocks * (STIRRED ? kStirSlots : kSlots)))) return rc;
+  if ((rc = ensure_buffer(ctx, ra.gacc, sizeof(double) * batch * (STIRRED ? 4 : 3)))) return rc;
+  if (STIRRED && (rc = ensure_buffer(ctx, ra.sacc, sizeof(double) * batch * PDEOPT_MAX_SPOTS * 7))) return rc;
   return PDEOPT_OK;
 }
 
@@ -506,17 +506,17 @@ int rot_adjoint_step_t(pdeopt_ctx* ctx, GpeRotAdjoint& ra, double t0, double dt,
   const dim3 mgrid((unsigned)std::min<int64_t>(4096, (cells + 255) / 256), p.batch), rgrid(kBlocks, p.batch), blk(256);
   const EnvParams<T>* ep = env_params<T>(ctx, 0);
   const RotAxis<T> axes[2] = {rot_axis<T>(ctx, 0, 0.5 * tau), rot_axis<T>(ctx, 1, 0.5 * tau)};
-  const Cx<T>* const kin[2] = {(const Cx<T>*)ra.kin_x, (const Cx<T>*)ra.kin_y};
+  const Cx<T>* const kin[2] = {ra.kin_x.as<const Cx<T>>(), ra.kin_y.as<const Cx<T>>()};
   const AuxField& pot = ctx->aux[PDEOPT_AUX_GPE_POTENTIAL];
-  Cx<T>* const work = (Cx<T>*)ra.work;
+  Cx<T>* const work = ra.work.as<Cx<T>>();
   Cx<T>* const lam = (Cx<T>*)lam_dev;
   const T t = (T)t0;
   std::conditional_t<STIRRED, RsadjArgs<T>, RadjArgs<T>> a{};
   a.work = work;
-  a.cbuf = (Cx<T>*)ra.cbuf;
+  a.cbuf = ra.cbuf.as<Cx<T>>();
   a.psi0 = (const Cx<T>*)psi0;
   a.lam = lam;
-  a.pot = (const T*)pot.dev;
+  a.pot = pot.dev.as<const T>();
   a.pot_stride = pot.per_env ? cells : 0;
   a.ep = ep;
   a.tr = (T)tau.real();
@@ -528,7 +528,7 @@ int rot_adjoint_step_t(pdeopt_ctx* ctx, GpeRotAdjoint& ra, double t0, double dt,
   a.cells = cells;
   a.ny = p.ny;
   a.h2 = ctx->strang_dx * ctx->strang_dx;
-  a.part = ra.part;
+  a.part = ra.part.as<double>();
   if constexpr (STIRRED) a.spots = make_spot_args<T>(ctx, 0, t0);
   // primal: transform along `axis`, multiply (the spectrum kept in `save`), and back unless it is the last one
   auto primal_op = [&](auto axis, Cx<T>* save, bool back) -> int {
@@ -550,10 +550,10 @@ int rot_adjoint_step_t(pdeopt_ctx* ctx, GpeRotAdjoint& ra, double t0, double dt,
     if (r) return r;
     if constexpr (STIRRED)
       hipLaunchKernelGGL((rsadj_conj_mul_kernel<T, A, S>), rgrid, blk, 0, ctx->stream, lam, prim, kin[A], ep, axes[A], p.nx,
-                         p.ny, ra.part, slot, t);
+                         p.ny, ra.part.as<double>(), slot, t);
     else
       hipLaunchKernelGGL((radj_conj_mul_kernel<T, A, S>), rgrid, blk, 0, ctx->stream, lam, prim, kin[A], ep, axes[A], p.nx,
-                         p.ny, ra.part, slot);
+                         p.ny, ra.part.as<double>(), slot);
     return spectral_c2c_axis(ctx, A, false, lam);
   };
   constexpr std::integral_constant<int, 0> along_x{};
@@ -561,24 +561,24 @@ int rot_adjoint_step_t(pdeopt_ctx* ctx, GpeRotAdjoint& ra, double t0, double dt,
   constexpr std::false_type plain{};
   constexpr std::true_type with_sigma{};
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(work, psi0, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  if ((rc = primal_op(along_x, (Cx<T>*)ra.spec[0], true))) return rc;   // u1
-  if ((rc = primal_op(along_y, (Cx<T>*)ra.spec[1], true))) return rc;   // a
+  if ((rc = primal_op(along_x, ra.spec[0].as<Cx<T>>(), true))) return rc;   // u1
+  if ((rc = primal_op(along_y, ra.spec[1].as<Cx<T>>(), true))) return rc;   // a
   if constexpr (STIRRED) hipLaunchKernelGGL(rsadj_recompute_kernel<T>, rgrid, blk, 0, ctx->stream, a);
   else hipLaunchKernelGGL(radj_recompute_kernel<T>, rgrid, blk, 0, ctx->stream, a);
-  if ((rc = primal_op(along_y, (Cx<T>*)ra.spec[2], true))) return rc;   // n e1
+  if ((rc = primal_op(along_y, ra.spec[2].as<Cx<T>>(), true))) return rc;   // n e1
   if ((rc = primal_op(along_x, nullptr, false))) return rc;             // work = S4
   if ((rc = cotangent_op(along_x, plain, work, kOmega4))) return rc;                             // mu1
-  if ((rc = cotangent_op(along_y, with_sigma, (const Cx<T>*)ra.spec[2], kOmega3))) return rc;    // lambda_d, the raw sigma
+  if ((rc = cotangent_op(along_y, with_sigma, ra.spec[2].as<const Cx<T>>(), kOmega3))) return rc;    // lambda_d, the raw sigma
   if constexpr (STIRRED) hipLaunchKernelGGL(rsadj_pointwise_kernel<T>, rgrid, blk, 0, ctx->stream, a);
   else hipLaunchKernelGGL(radj_pointwise_kernel<T>, rgrid, blk, 0, ctx->stream, a);
-  if ((rc = cotangent_op(along_y, plain, (const Cx<T>*)ra.spec[1], kOmega2))) return rc;         // nu
-  if ((rc = cotangent_op(along_x, plain, (const Cx<T>*)ra.spec[0], kOmega1))) return rc;         // Lx^H nu
+  if ((rc = cotangent_op(along_y, plain, ra.spec[1].as<const Cx<T>>(), kOmega2))) return rc;         // nu
+  if ((rc = cotangent_op(along_x, plain, ra.spec[0].as<const Cx<T>>(), kOmega1))) return rc;         // Lx^H nu
   if constexpr (STIRRED)
-    hipLaunchKernelGGL(rsadj_finish_kernel<T>, rgrid, blk, 0, ctx->stream, lam, (const Cx<T>*)ra.cbuf, cells,
-                       (const double*)ra.part, grad_dev, spot_grad_dev, ctx->n_spots, a.h2, t0);
+    hipLaunchKernelGGL(rsadj_finish_kernel<T>, rgrid, blk, 0, ctx->stream, lam, ra.cbuf.as<const Cx<T>>(), cells,
+                       ra.part.as<const double>(), grad_dev, spot_grad_dev, ctx->n_spots, a.h2, t0);
   else
-    hipLaunchKernelGGL(radj_finish_kernel<T>, rgrid, blk, 0, ctx->stream, lam, (const Cx<T>*)ra.cbuf, cells,
-                       (const double*)ra.part, grad_dev, a.h2);
+    hipLaunchKernelGGL(radj_finish_kernel<T>, rgrid, blk, 0, ctx->stream, lam, ra.cbuf.as<const Cx<T>>(), cells,
+                       ra.part.as<const double>(), grad_dev, a.h2);
   ctx->n_stage_launches += 26;  // 15 transforms, 8 multiplies, 3 passes
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -589,10 +589,6 @@ void radj_invalidate(GpeRotAdjoint* ra) {
 }
 
 void radj_destroy(GpeRotAdjoint*& ra) {
-  if (!ra) return;
-  void* bufs[] = {ra->work, ra->cbuf, ra->spec[0], ra->spec[1], ra->spec[2], ra->kin_x, ra->kin_y, ra->part, ra->gacc, ra->sacc};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   delete ra;
   ra = nullptr;
 }
@@ -651,7 +647,7 @@ int pdeopt_gpe_rot_adjoint_step(pdeopt_ctx* ctx, double dt, const void* psi0_dev
   if (rc) return rc;
   double* gdev = grad;
   if (!grad_on_device) {
-    gdev = ra.gacc;
+    gdev = ra.gacc.as<double>();
     PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(gdev, 0, gbytes, ctx->stream));
   }
   rc = with_dtype(ctx, [&](auto t) { return rot_adjoint_step_t<decltype(t), false>(ctx, ra, 0.0, dt, psi0_dev, lam_dev, gdev, nullptr); });
@@ -723,10 +719,10 @@ int pdeopt_gpe_rot_stir_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, cons
   if (rc) return rc;
   double *gdev = grad, *sdev = spot_grad;
   if (!grad_on_device) {
-    gdev = ra.gacc;
+    gdev = ra.gacc.as<double>();
     PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(gdev, 0, gbytes, ctx->stream));
     if (spot_grad) {
-      sdev = ra.sacc;
+      sdev = ra.sacc.as<double>();
       PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(sdev, 0, sbytes, ctx->stream));
     }
   }

@@ -60,7 +60,7 @@ RotAxis<T> rot_axis(const pdeopt_ctx* ctx, int axis, std::complex<double> half_t
 }
 
 template <typename T>
-int upload_kinetic(pdeopt_ctx* ctx, void** dev, int n, double h, std::complex<double> half_tau) {
+int upload_kinetic(pdeopt_ctx* ctx, DeviceBuffer& dev, int n, double h, std::complex<double> half_tau) {
   std::vector<Cx<T>> t((size_t)n);
   for (int f = 0; f < n; ++f) {
     const int ks = f < (n + 1) / 2 ? f : f - n;
@@ -71,7 +71,7 @@ int upload_kinetic(pdeopt_ctx* ctx, void** dev, int n, double h, std::complex<do
   }
   int rc = ensure_buffer(ctx, dev, t.size() * sizeof(Cx<T>));
   if (rc) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(*dev, t.data(), t.size() * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(dev.get(), t.data(), t.size() * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }

@@ -13,12 +13,12 @@
 namespace pdeopt {
 
 struct GpeRot {
-  void* tw_x = nullptr;   // twiddle tables exp(-2 pi i n / N) in the problem dtype
-  void* tw_y = nullptr;
-  void* kin_x = nullptr;  // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
-  void* kin_y = nullptr;
-  void* dens = nullptr;   // |psi0|^2, real [batch][nx][ny]
-  double* partial = nullptr;
+  DeviceBuffer tw_x;   // twiddle tables exp(-2 pi i n / N) in the problem dtype
+  DeviceBuffer tw_y;
+  DeviceBuffer kin_x;  // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
+  DeviceBuffer kin_y;
+  DeviceBuffer dens;   // |psi0|^2, real [batch][nx][ny]
+  DeviceBuffer partial;  // doubles
   int partial_per_env = 0;
   double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
   bool valid = false;

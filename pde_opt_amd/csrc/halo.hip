@@ -119,14 +119,9 @@ __global__ void unpack_kernel(T* __restrict__ field, const T* __restrict__ recv,
 }
 
 int ensure_scratch(pdeopt_ctx* ctx, size_t bytes) {
-  if (ctx->halo_scratch_bytes >= bytes) return PDEOPT_OK;
-  if (ctx->halo_scratch) (void)hipFree(ctx->halo_scratch);
-  if (ctx->halo_scratch2) (void)hipFree(ctx->halo_scratch2);  // sized like the first (stencil.hip: loop-back, halo 8)
-  ctx->halo_scratch = ctx->halo_scratch2 = nullptr;
-  ctx->halo_scratch_bytes = ctx->halo_scratch2_bytes = 0;
-  int rc = ensure_buffer(ctx, &ctx->halo_scratch, bytes);
-  if (!rc) ctx->halo_scratch_bytes = bytes;
-  return rc;
+  if (ctx->halo_scratch.bytes() >= bytes) return PDEOPT_OK;
+  ctx->halo_scratch2.reset();  // sized like the first (stencil.hip: loop-back, halo 8)
+  return grow_device_buffer(ctx, ctx->halo_scratch, bytes, /*sync_first=*/false);
 }
 
 }  // namespace
@@ -137,10 +132,10 @@ size_t halo_strip_elems(const pdeopt_ctx* ctx) {
 
 void* field_ptr(pdeopt_ctx* ctx, int field) {
   switch (field) {
-    case 0: return ctx->Y;
-    case 1: return ctx->TA;
-    case 2: return ctx->TB;
-    case 3: return ctx->ACC;
+    case 0: return ctx->Y.get();
+    case 1: return ctx->TA.get();
+    case 2: return ctx->TB.get();
+    case 3: return ctx->ACC.get();
     default: return nullptr;
   }
 }
@@ -153,7 +148,7 @@ int halo_pack(pdeopt_ctx* ctx, int field, void* dev_send) {
   if (!dev_send) {
     int rc = ensure_scratch(ctx, bytes);
     if (rc) return rc;
-    dev_send = ctx->halo_scratch;
+    dev_send = ctx->halo_scratch.get();
   }
   const int blocks = (int)std::min<int64_t>((g.per_env + 255) / 256, 1024);
   dim3 grid(blocks, ctx->prob.batch);
@@ -171,7 +166,7 @@ int halo_unpack(pdeopt_ctx* ctx, int field, const void* dev_recv, const int* nbr
   const HaloGeo g = halo_geo(ctx);
   if (!dev_recv) {
     if (!ctx->halo_scratch) return fail(ctx, PDEOPT_ESTATE, "loop-back unpack without a preceding pack");
-    dev_recv = ctx->halo_scratch;
+    dev_recv = ctx->halo_scratch.get();
     for (int q = 0; q < 8; ++q)
       if (nbr[q] != 0) return fail(ctx, PDEOPT_EINVAL, "loop-back exchange: every neighbour must be rank 0");
   }

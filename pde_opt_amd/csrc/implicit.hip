@@ -74,18 +74,17 @@ struct Implicit {
   int restart = 0, max_newton = 0, max_krylov = 0;
   int B = 0, nblk = 0;
   int64_t cells = 0;
-  void* fields = nullptr;  // Y0 | G | DELTA | W0 | W1 | V[restart], each [B][cells] in the problem dtype
-  size_t field_bytes = 0, fields_bytes = 0;
-  void* small_blk = nullptr;
-  size_t small_bytes = 0;
+  DeviceBuffer fields;  // Y0 | G | DELTA | W0 | W1 | V[restart], each [B][cells] in the problem dtype
+  size_t field_bytes = 0;  // one of them
+  DeviceBuffer small_blk;
   ImpSmall sm{};
-  int* flags_host = nullptr;  // pinned
-  double* res_host = nullptr;
+  PinnedBuffer flags_host;  // ints
+  PinnedBuffer res_host;    // doubles
   // pdeopt_implicit_set_precond: 0 none, 1 spectral.  The workspace of the preconditioner is one more field of the batch
   // and the small block below; the hermitian work field and the plans are spectral.hip's
   int precond = 0;
-  void* zfield = nullptr;  // [B][cells]: z_j = M^-1 v_j of an iteration, V y_k at a cycle's end
-  void* pc_blk = nullptr;
+  DeviceBuffer zfield;  // [B][cells]: z_j = M^-1 v_j of an iteration, V y_k at a cycle's end
+  DeviceBuffer pc_blk;
   ImpPrecond pc{};
   void* hbuf = nullptr;    // borrowed (spectral_real_prepare)
   int64_t half_cells = 0;
@@ -695,7 +694,7 @@ __global__ __launch_bounds__(256) void precond_add_kernel(ImpVecArgs<T> a) {
 
 template <typename T>
 T* imp_field(const Implicit& s, int which) {
-  return reinterpret_cast<T*>(static_cast<char*>(s.fields) + (size_t)which * s.field_bytes);
+  return reinterpret_cast<T*>(s.fields.as<char>() + (size_t)which * s.field_bytes);
 }
 enum { F_Y0 = 0, F_G = 1, F_DELTA = 2, F_W0 = 3, F_W1 = 4, F_V = 5 };
 
@@ -739,7 +738,7 @@ int launch_op(pdeopt_ctx* ctx, const T* src, T* vout, T* wout, const double* sca
               const T* raw = nullptr) {
   const pdeopt_problem& p = ctx->prob;
   ImpOpArgs<T> a{};
-  a.y = static_cast<const T*>(ctx->Y);
+  a.y = ctx->Y.as<const T>();
   a.src = src;
   a.raw = raw;
   a.vout = vout;
@@ -771,7 +770,7 @@ template <typename T>
 int launch_precond_coefs(pdeopt_ctx* ctx, const int* flags) {
   Implicit& s = *ctx->implicit;
   PrecondCoefArgs<T> a{};
-  a.y = static_cast<const T*>(ctx->Y);
+  a.y = ctx->Y.as<const T>();
   a.flags = flags;
   set_closures<T>(a, ctx, 0);
   a.cells = s.cells;
@@ -820,7 +819,7 @@ int launch_precond(pdeopt_ctx* ctx, const T* in, T* out, const double* scale, co
 
 int read_flags(pdeopt_ctx* ctx) {
   Implicit& s = *ctx->implicit;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.flags_host, s.sm.flags, (size_t)s.B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.flags_host.as<int>(), s.sm.flags, (size_t)s.B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -828,16 +827,16 @@ int read_flags(pdeopt_ctx* ctx) {
 // the budget ran out: put the step's start back, say which environment and how far it got
 int implicit_fail(pdeopt_ctx* ctx, int64_t step, const char* what, int iters) {
   Implicit& s = *ctx->implicit;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->Y, s.fields, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host, s.sm.res, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host + s.B, s.sm.tol, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->Y.get(), s.fields.get(), ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host.as<double>(), s.sm.res, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host.as<double>() + s.B, s.sm.tol, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   int env = 0;
   for (int b = 0; b < s.B; ++b)
-    if (!(s.flags_host[b] & (IMP_NEWTON_DONE | IMP_LIN_CONV))) { env = b; break; }
+    if (!(s.flags_host.as<int>()[b] & (IMP_NEWTON_DONE | IMP_LIN_CONV))) { env = b; break; }
   return fail(ctx, PDEOPT_ENOCONVERGE, "implicit Euler did not converge: environment %d, step %lld: %s after %d iteration(s), last "
                                        "residual %.6g (threshold %.6g); the state is the one the step started from",
-              env, (long long)step, what, iters, s.res_host[env], s.res_host[s.B + env]);
+              env, (long long)step, what, iters, s.res_host.as<double>()[env], s.res_host.as<double>()[s.B + env]);
 }
 
 // one step y <- the solution of y - y0 - dt f(y) = 0; st: [B][4] counters or nullptr
@@ -846,7 +845,7 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
   Implicit& s = *ctx->implicit;
   const int B = s.B, m = s.restart;
   const int64_t cells = s.cells;
-  T* const y = static_cast<T*>(ctx->Y);
+  T* const y = ctx->Y.as<T>();
   T* const W[2] = {imp_field<T>(s, F_W0), imp_field<T>(s, F_W1)};
   T* const V = imp_field<T>(s, F_V);
   const dim3 vgrid(s.nblk, B), sgrid(B);
@@ -859,35 +858,35 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
   va.B = B;
   va.sm = s.sm;
   const bool pre = s.precond != 0;
-  T* const Z = static_cast<T*>(s.zfield);
+  T* const Z = s.zfield.as<T>();
   int rc;
   auto count = [&](int which) {  // the environments the next launch works on
     if (st)
       for (int b = 0; b < B; ++b)
-        if (!s.flags_host[b]) st[4 * b + which]++;
+        if (!s.flags_host.as<int>()[b]) st[4 * b + which]++;
   };
   auto any_active = [&] {
     for (int b = 0; b < B; ++b)
-      if (!s.flags_host[b]) return true;
+      if (!s.flags_host.as<int>()[b]) return true;
     return false;
   };
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.fields, y, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.fields.get(), y, ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.sm.flags, 0, (size_t)B * sizeof(int), ctx->stream));
-  std::fill(s.flags_host, s.flags_host + B, 0);
+  std::fill(s.flags_host.as<int>(), s.flags_host.as<int>() + B, 0);
   for (int newton_it = 0;; ++newton_it) {
     // the environments that are not frozen at the Newton level: LIN_CONV is the only other flag alive here
-    for (int b = 0; b < B; ++b) s.flags_host[b] &= IMP_NEWTON_DONE;
+    for (int b = 0; b < B; ++b) s.flags_host.as<int>()[b] &= IMP_NEWTON_DONE;
     count(3);
-    if ((rc = launch_rhs(ctx, whole_batch(ctx), y, ctx->TA, t1))) return rc;
+    if ((rc = launch_rhs(ctx, whole_batch(ctx), y, ctx->TA.get(), t1))) return rc;
     hipLaunchKernelGGL(imp_residual_kernel<T>, vgrid, dim3(256), 0, ctx->stream, static_cast<const T*>(y),
-                       static_cast<const T*>(imp_field<T>(s, F_Y0)), static_cast<const T*>(ctx->TA), imp_field<T>(s, F_G), (T)dt, cells, s.sm);
+                       static_cast<const T*>(imp_field<T>(s, F_Y0)), ctx->TA.as<const T>(), imp_field<T>(s, F_G), (T)dt, cells, s.sm);
     hipLaunchKernelGGL(imp_newton_small_kernel, sgrid, dim3(64), 0, ctx->stream, s.sm, (double)cells, s.rtol, s.atol, s.krylov_rtol,
                        newton_it, s.max_newton);
     ctx->n_stage_launches += 2;
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     if ((rc = read_flags(ctx))) return rc;
     for (int b = 0; b < B; ++b)
-      if (s.flags_host[b] & IMP_FAIL) return implicit_fail(ctx, step, "Newton: rms(G) above atol + rtol rms(y)", newton_it);
+      if (s.flags_host.as<int>()[b] & IMP_FAIL) return implicit_fail(ctx, step, "Newton: rms(G) above atol + rtol rms(y)", newton_it);
     if (!any_active()) return PDEOPT_OK;
     count(0);
     if (pre) {  // the symbol's coefficients at this Newton iterate
@@ -915,7 +914,7 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
         count(2);
         if (pre) {  // z_j = M^-1 v_j, w = A z_j; the operator stores v_j = scale x src as it goes by
           for (int b = 0; b < B; ++b)
-            if (!s.flags_host[b]) s.pc_count[b]++;
+            if (!s.flags_host.as<int>()[b]) s.pc_count[b]++;
           if ((rc = launch_precond<T>(ctx, src, Z, s.sm.vscale, s.sm.flags, -1, dt))) return rc;
           if ((rc = launch_op<T>(ctx, Z, V + (int64_t)j * B * cells, w, s.sm.vscale, s.sm.flags, dt, src))) return rc;
         } else if ((rc = launch_op<T>(ctx, src, V + (int64_t)j * B * cells, w, s.sm.vscale, s.sm.flags, dt))) {
@@ -943,7 +942,7 @@ int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* 
       va.cycle = cycle;
       if (pre) {  // delta (+)= M^-1 (V y_k): one application per cycle
         for (int b = 0; b < B; ++b) {
-          const int fl = s.flags_host[b];
+          const int fl = s.flags_host.as<int>()[b];
           if ((fl & (IMP_NEWTON_DONE | IMP_FAIL)) || ((fl & IMP_LIN_CONV) && s.lin_applied[b])) continue;
           s.pc_count[b]++;
           if (fl & IMP_LIN_CONV) s.lin_applied[b] = 1;
@@ -971,7 +970,7 @@ int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* 
   int rc;
   if ((rc = check_implicit(ctx))) return rc;
   if (!(dt > 0.0) || !std::isfinite(dt)) return fail(ctx, PDEOPT_EINVAL, "implicit Euler: dt = %g", dt);
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
   const int B = ctx->prob.batch;
   if (stats) std::fill(stats, stats + 4 * (int64_t)B, (int64_t)0);
   for (int64_t s = 0; s < n; ++s) {
@@ -987,15 +986,7 @@ int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* 
 }
 
 void implicit_destroy(pdeopt_ctx* ctx) {
-  Implicit* s = ctx->implicit;
-  if (!s) return;
-  if (s->fields) (void)hipFree(s->fields);
-  if (s->small_blk) (void)hipFree(s->small_blk);
-  if (s->zfield) (void)hipFree(s->zfield);
-  if (s->pc_blk) (void)hipFree(s->pc_blk);
-  if (s->flags_host) (void)hipHostFree(s->flags_host);
-  if (s->res_host) (void)hipHostFree(s->res_host);
-  delete s;
+  delete ctx->implicit;
   ctx->implicit = nullptr;
 }
 
@@ -1031,7 +1022,7 @@ int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double 
   const size_t nd = (size_t)B * ((size_t)m * nblk + 2 * (size_t)nblk + m + (size_t)m * m + m + m + (m + 1) + m + 4);
   const size_t small_bytes = nd * sizeof(double) + 3 * (size_t)B * sizeof(int);
   Implicit* s = ctx->implicit;
-  if (s && (s->fields_bytes != fields_bytes || s->small_bytes != small_bytes || s->B != B || s->restart != m)) {
+  if (s && (s->fields.bytes() != fields_bytes || s->small_blk.bytes() != small_bytes || s->B != B || s->restart != m)) {
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     implicit_destroy(ctx);
     s = nullptr;
@@ -1045,24 +1036,18 @@ int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double 
                                       "batch and the partial sums), %zu are free on the device", m, want, free_b);
     s = new Implicit();
     ctx->implicit = s;
-    if ((rc = ensure_buffer(ctx, &s->fields, fields_bytes)) || (rc = ensure_buffer(ctx, &s->small_blk, small_bytes))) {
+    if ((rc = ensure_buffer(ctx, s->fields, fields_bytes)) || (rc = ensure_buffer(ctx, s->small_blk, small_bytes)) ||
+        (rc = ensure_buffer(ctx, s->flags_host, (size_t)B * sizeof(int))) ||
+        (rc = ensure_buffer(ctx, s->res_host, 2 * (size_t)B * sizeof(double)))) {
       implicit_destroy(ctx);
       return rc;
-    }
-    hipError_t e = hipHostMalloc((void**)&s->flags_host, (size_t)B * sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&s->res_host, 2 * (size_t)B * sizeof(double));
-    if (e != hipSuccess) {
-      implicit_destroy(ctx);
-      return fail(ctx, PDEOPT_ENOMEM, "hipHostMalloc failed: %s", hipGetErrorString(e));
     }
     s->B = B;
     s->cells = cells;
     s->nblk = nblk;
     s->restart = m;
     s->field_bytes = field_bytes;
-    s->fields_bytes = fields_bytes;
-    s->small_bytes = small_bytes;
-    double* d = static_cast<double*>(s->small_blk);
+    double* d = s->small_blk.as<double>();
     ImpSmall& sm = s->sm;
     auto take = [&](size_t per_env) { double* q = d; d += (size_t)B * per_env; return q; };
     sm.part_dot = take((size_t)m * nblk);
@@ -1082,7 +1067,7 @@ int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double 
     sm.conv_cycle = sm.kcols + B;
     sm.m = m;
     sm.nblk = nblk;
-    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s->small_blk, 0, small_bytes, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s->small_blk.get(), 0, small_bytes, ctx->stream));
   }
   s->precond = 0;  // pdeopt_implicit_set_precond comes after this call; its buffers stay with the workspace
   s->pc_count.assign((size_t)B, 0);
@@ -1151,12 +1136,12 @@ int pdeopt_implicit_set_precond(pdeopt_ctx* ctx, int kind) {
       return fail(ctx, PDEOPT_ENOMEM, "implicit Euler: the spectral preconditioner needs %zu bytes (one more field of the batch, "
                                       "the half-spectrum field of the transforms and the coefficient sums), %zu are free on the "
                                       "device", want, free_b);
-    if ((rc = ensure_buffer(ctx, &s.zfield, s.field_bytes)) || (rc = ensure_buffer(ctx, &s.pc_blk, nd * sizeof(double)))) return rc;
+    if ((rc = ensure_buffer(ctx, s.zfield, s.field_bytes)) || (rc = ensure_buffer(ctx, s.pc_blk, nd * sizeof(double)))) return rc;
     // the transforms run over every environment, a frozen one's included: what they read there is stale, never garbage
-    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.zfield, 0, s.field_bytes, ctx->stream));
-    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(static_cast<char*>(s.fields) + (size_t)F_W0 * s.field_bytes, 0, 2 * s.field_bytes, ctx->stream));
-    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.pc_blk, 0, nd * sizeof(double), ctx->stream));
-    double* d = static_cast<double*>(s.pc_blk);
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.zfield.get(), 0, s.field_bytes, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.fields.as<char>() + (size_t)F_W0 * s.field_bytes, 0, 2 * s.field_bytes, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(s.pc_blk.get(), 0, nd * sizeof(double), ctx->stream));
+    double* d = s.pc_blk.as<double>();
     s.pc.part = d;
     s.pc.coef = s.pc.part + (size_t)s.B * 2 * s.nblk;
     s.pc.sin2x = s.pc.coef + (size_t)s.B * 2;
@@ -1205,7 +1190,7 @@ int pdeopt_implicit_precond_apply(pdeopt_ctx* ctx, double dt, const void* v_host
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
     T* const v = imp_field<T>(s, F_W0);
-    T* const z = static_cast<T*>(s.zfield);
+    T* const z = s.zfield.as<T>();
     PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(v, v_host, ctx->total_bytes, hipMemcpyHostToDevice, ctx->stream));
     int r;
     if ((r = launch_precond_coefs<T>(ctx, nullptr))) return r;

@@ -12,7 +12,7 @@ inline ClosureSpec closure_spec(const pdeopt_closure& c) { return ClosureSpec{c.
 // parameters of the environments from first_env on, in the arithmetic type of the path
 template <typename T>
 inline const EnvParams<T>* env_params(const pdeopt_ctx* ctx, int first_env) {
-  return static_cast<const EnvParams<T>*>(ctx->env_params_dev) + first_env;
+  return ctx->env_params_dev.as<const EnvParams<T>>() + first_env;
 }
 // the three members every argument struct sets the same way
 template <typename T, typename Args>

@@ -51,17 +51,17 @@ struct pdeopt_mixer {
   std::vector<double> params;
   bool have_params = false;
   // device copy in the problem dtype: the flat vector as it is, then the packed weights
-  void* packed = nullptr;
+  pdeopt::DeviceBuffer packed;  // grow-only
   int64_t packed_elems = 0;
   int packed_dtype = -1;
   bool packed_valid = false;
   // workspace of the configured dtype and batch
   int s_dtype = -1, s_batch = 0;
-  void* Y[2 * kMixMaxBlocks + 1] = {};
-  void *H1[kMixMaxBlocks] = {}, *Z1[kMixMaxBlocks] = {}, *H2[kMixMaxBlocks] = {}, *Z2[kMixMaxBlocks] = {};
-  void *DY = nullptr, *DN = nullptr, *DZ = nullptr;
-  double* stats = nullptr;  // [2 K + 1 norms][batch][mean, rstd], then [batch][2] sums of a layer norm's backward pass
-  double* grad = nullptr;   // [n_params], fp64, accumulates until pdeopt_mixer_grad_read(reset)
+  pdeopt::DeviceBuffer Y[2 * kMixMaxBlocks + 1];
+  pdeopt::DeviceBuffer H1[kMixMaxBlocks], Z1[kMixMaxBlocks], H2[kMixMaxBlocks], Z2[kMixMaxBlocks];
+  pdeopt::DeviceBuffer DY, DN, DZ;
+  pdeopt::DeviceBuffer stats;  // doubles [2 K + 1 norms][batch][mean, rstd], then [batch][2] sums of a layer norm's backward pass
+  pdeopt::DeviceBuffer grad;   // doubles [n_params], accumulates until pdeopt_mixer_grad_read(reset)
 };
 
 namespace pdeopt {
@@ -313,15 +313,10 @@ __global__ __launch_bounds__(256) void mixer_sum_kernel(const T* __restrict__ g,
 // ---- host ---------------------------------------------------------------------------------------------------------------
 
 void free_workspace(pdeopt_mixer* n) {
-  const auto drop = [](void*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  };
-  for (void*& p : n->Y) drop(p);
-  for (int k = 0; k < kMixMaxBlocks; ++k) drop(n->H1[k]), drop(n->Z1[k]), drop(n->H2[k]), drop(n->Z2[k]);
-  drop(n->DY), drop(n->DN), drop(n->DZ);
-  if (n->stats) (void)hipFree(n->stats);
-  n->stats = nullptr;
+  for (DeviceBuffer& y : n->Y) y.reset();
+  for (int k = 0; k < kMixMaxBlocks; ++k) n->H1[k].reset(), n->Z1[k].reset(), n->H2[k].reset(), n->Z2[k].reset();
+  n->DY.reset(), n->DN.reset(), n->DZ.reset();
+  n->stats.reset();
   n->s_dtype = -1;
 }
 
@@ -381,15 +376,10 @@ int upload_packed(pdeopt_mixer* n) {
     pack_pair<T>(h, p + b.w3, n->Mh, n->C, false, b.f3, b.r3);
     pack_pair<T>(h, p + b.w4, n->C, n->Mh, false, b.f4, b.r4);
   }
-  if (n->packed && n->packed_dtype != ctx->prob.dtype) {
-    PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(n->packed);
-    n->packed = nullptr;
-  }
   const size_t bytes = (size_t)n->packed_elems * sizeof(T);
-  if (const int rc = ensure_buffer(ctx, &n->packed, bytes)) return rc;
+  if (const int rc = grow_device_buffer(ctx, n->packed, bytes, /*sync_first=*/true)) return rc;
   // the staging vector dies with this call: the copy is complete for the host when it returns (pageable memory)
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(n->packed, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(n->packed.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   n->packed_dtype = ctx->prob.dtype;
   n->packed_valid = true;
@@ -421,15 +411,15 @@ int prepare(pdeopt_mixer* n, bool backward, std::initializer_list<const void*> f
   const size_t B = p.batch, cp = (size_t)n->C * n->P, cm = (size_t)n->C * n->Mp, pm = (size_t)n->P * n->Mh, es = ctx->esize;
   int rc = 0;
   for (int j = 0; j <= 2 * n->K; ++j)
-    if ((rc = ensure_buffer(ctx, &n->Y[j], B * cp * es))) return rc;
+    if ((rc = ensure_buffer(ctx, n->Y[j], B * cp * es))) return rc;
   for (int k = 0; k < n->K; ++k) {
-    if ((rc = ensure_buffer(ctx, &n->H1[k], B * cm * es)) || (rc = ensure_buffer(ctx, &n->H2[k], B * pm * es))) return rc;
-    if (backward && ((rc = ensure_buffer(ctx, &n->Z1[k], B * cm * es)) || (rc = ensure_buffer(ctx, &n->Z2[k], B * pm * es)))) return rc;
+    if ((rc = ensure_buffer(ctx, n->H1[k], B * cm * es)) || (rc = ensure_buffer(ctx, n->H2[k], B * pm * es))) return rc;
+    if (backward && ((rc = ensure_buffer(ctx, n->Z1[k], B * cm * es)) || (rc = ensure_buffer(ctx, n->Z2[k], B * pm * es)))) return rc;
   }
-  if ((rc = ensure_buffer(ctx, (void**)&n->stats, (size_t)(2 * n->K + 2) * B * 2 * sizeof(double)))) return rc;
+  if ((rc = ensure_buffer(ctx, n->stats, (size_t)(2 * n->K + 2) * B * 2 * sizeof(double)))) return rc;
   if (backward) {
-    if ((rc = ensure_buffer(ctx, &n->DY, B * cp * es)) || (rc = ensure_buffer(ctx, &n->DN, B * cp * es)) ||
-        (rc = ensure_buffer(ctx, &n->DZ, B * std::max(cm, pm) * es)))
+    if ((rc = ensure_buffer(ctx, n->DY, B * cp * es)) || (rc = ensure_buffer(ctx, n->DN, B * cp * es)) ||
+        (rc = ensure_buffer(ctx, n->DZ, B * std::max(cm, pm) * es)))
       return rc;
   }
   return PDEOPT_OK;
@@ -451,9 +441,9 @@ Operand<T> patches(const pdeopt_mixer* n, const void* field) {
 }
 template <typename T>
 Operand<T> normed(Operand<T> a, const pdeopt_mixer* n, int64_t gamma, int64_t beta, int64_t g0, int64_t g1, int which) {
-  const T* P = static_cast<const T*>(n->packed);
+  const T* P = n->packed.as<const T>();
   a.gamma = P + gamma, a.beta = P + beta, a.g0 = g0, a.g1 = g1;
-  a.stats = n->stats + (size_t)which * n->s_batch * 2;
+  a.stats = n->stats.as<double>() + (size_t)which * n->s_batch * 2;
   return a;
 }
 
@@ -478,13 +468,13 @@ int launch_gemm(pdeopt_mixer* n, const GemmArgs<T>& a) {
 template <typename T>
 GemmArgs<T> gemm(const pdeopt_mixer* n, const Operand<T>& A, int64_t w, int N, void* out, int64_t ob, int64_t o0, int64_t o1) {
   GemmArgs<T> a{};
-  a.A = A, a.w = static_cast<const T*>(n->packed) + w, a.Kp = pad16(A.n1), a.Np = pad16(N), a.M = A.n0, a.N = N;
+  a.A = A, a.w = n->packed.as<const T>() + w, a.Kp = pad16(A.n1), a.Np = pad16(N), a.M = A.n0, a.N = N;
   a.out = static_cast<T*>(out), a.ob = ob, a.o0 = o0, a.o1 = o1;
   return a;
 }
 template <typename T>
 void with_bias(GemmArgs<T>& a, const pdeopt_mixer* n, int64_t bias, int stride = 1) {
-  a.bias = static_cast<const T*>(n->packed) + bias, a.bias_stride = stride;
+  a.bias = n->packed.as<const T>() + bias, a.bias_stride = stride;
 }
 template <typename T>
 void into_field(GemmArgs<T>& a, const pdeopt_mixer* n) {
@@ -494,8 +484,8 @@ void into_field(GemmArgs<T>& a, const pdeopt_mixer* n) {
 template <typename T>
 int launch_stats(pdeopt_mixer* n, int which) {
   pdeopt_ctx* ctx = n->ctx;
-  hipLaunchKernelGGL(mixer_stats_kernel<T>, dim3(ctx->prob.batch), dim3(256), 0, ctx->stream, static_cast<const T*>(n->Y[which]),
-                     (int64_t)n->C * n->P, n->stats + (size_t)which * n->s_batch * 2);
+  hipLaunchKernelGGL(mixer_stats_kernel<T>, dim3(ctx->prob.batch), dim3(256), 0, ctx->stream, n->Y[which].as<const T>(),
+                     (int64_t)n->C * n->P, n->stats.as<double>() + (size_t)which * n->s_batch * 2);
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -508,35 +498,35 @@ int forward(pdeopt_mixer* n, const void* u, void* mu, bool keep_z) {
   const int64_t cp = (int64_t)C * P, cm = (int64_t)C * Mp, pm = (int64_t)P * Mh;
   int rc = 0;
   {
-    GemmArgs<T> a = gemm<T>(n, patches<T>(n, u), n->f_in, C, n->Y[0], cp, 1, P);
+    GemmArgs<T> a = gemm<T>(n, patches<T>(n, u), n->f_in, C, n->Y[0].get(), cp, 1, P);
     with_bias(a, n, n->bin);
     if ((rc = launch_gemm(n, a))) return rc;
   }
   for (int k = 0; k < n->K; ++k) {
     const pdeopt_mixer::Block& b = n->blk[k];
-    void *y = n->Y[2 * k], *ya = n->Y[2 * k + 1], *yb = n->Y[2 * k + 2];
+    void *y = n->Y[2 * k].get(), *ya = n->Y[2 * k + 1].get(), *yb = n->Y[2 * k + 2].get();
     if ((rc = launch_stats<T>(n, 2 * k))) return rc;
-    GemmArgs<T> g1 = gemm<T>(n, normed(plain<T>(y, cp, C, P, P, 1), n, b.g1, b.be1, P, 1, 2 * k), b.f1, Mp, n->H1[k], cm, Mp, 1);
+    GemmArgs<T> g1 = gemm<T>(n, normed(plain<T>(y, cp, C, P, P, 1), n, b.g1, b.be1, P, 1, 2 * k), b.f1, Mp, n->H1[k].get(), cm, Mp, 1);
     with_bias(g1, n, b.b1);
-    g1.epi = EPI_ACT, g1.zout = keep_z ? static_cast<T*>(n->Z1[k]) : nullptr;
+    g1.epi = EPI_ACT, g1.zout = keep_z ? n->Z1[k].as<T>() : nullptr;
     if ((rc = launch_gemm(n, g1))) return rc;
-    GemmArgs<T> g2 = gemm<T>(n, plain<T>(n->H1[k], cm, C, Mp, Mp, 1), b.f2, P, ya, cp, P, 1);
+    GemmArgs<T> g2 = gemm<T>(n, plain<T>(n->H1[k].get(), cm, C, Mp, Mp, 1), b.f2, P, ya, cp, P, 1);
     with_bias(g2, n, b.b2);
     g2.epi = EPI_RES, g2.res = static_cast<const T*>(y);
     if ((rc = launch_gemm(n, g2))) return rc;
     if ((rc = launch_stats<T>(n, 2 * k + 1))) return rc;
-    GemmArgs<T> g3 = gemm<T>(n, normed(plain<T>(ya, cp, P, C, 1, P), n, b.g2, b.be2, C, 1, 2 * k + 1), b.f3, Mh, n->H2[k], pm, Mh, 1);
+    GemmArgs<T> g3 = gemm<T>(n, normed(plain<T>(ya, cp, P, C, 1, P), n, b.g2, b.be2, C, 1, 2 * k + 1), b.f3, Mh, n->H2[k].get(), pm, Mh, 1);
     with_bias(g3, n, b.b3);
-    g3.epi = EPI_ACT, g3.zout = keep_z ? static_cast<T*>(n->Z2[k]) : nullptr;
+    g3.epi = EPI_ACT, g3.zout = keep_z ? n->Z2[k].as<T>() : nullptr;
     if ((rc = launch_gemm(n, g3))) return rc;
-    GemmArgs<T> g4 = gemm<T>(n, plain<T>(n->H2[k], pm, P, Mh, Mh, 1), b.f4, C, yb, cp, 1, P);
+    GemmArgs<T> g4 = gemm<T>(n, plain<T>(n->H2[k].get(), pm, P, Mh, Mh, 1), b.f4, C, yb, cp, 1, P);
     with_bias(g4, n, b.b4);
     g4.epi = EPI_RES, g4.res = static_cast<const T*>(ya);
     if ((rc = launch_gemm(n, g4))) return rc;
   }
   if ((rc = launch_stats<T>(n, 2 * n->K))) return rc;
   if (mu) {
-    GemmArgs<T> a = gemm<T>(n, normed(plain<T>(n->Y[2 * n->K], cp, P, C, 1, P), n, n->gf, n->bef, 1, P, 2 * n->K), n->f_out, n->Q, mu, 0, 0, 0);
+    GemmArgs<T> a = gemm<T>(n, normed(plain<T>(n->Y[2 * n->K].get(), cp, P, C, 1, P), n, n->gf, n->bef, 1, P, 2 * n->K), n->f_out, n->Q, mu, 0, 0, 0);
     with_bias(a, n, n->bout, 0);
     into_field(a, n);
     if ((rc = launch_gemm(n, a))) return rc;
@@ -550,7 +540,7 @@ int launch_wgrad(pdeopt_mixer* n, const Operand<T>& D, const Operand<T>& X, int6
   pdeopt_ctx* ctx = n->ctx;
   WgradArgs<T> a{};
   a.D = D, a.X = X, a.B = ctx->prob.batch, a.K = D.n0, a.O = D.n1, a.I = X.n1, a.ones = bias >= 0;
-  a.gw = n->grad + weight, a.gw_o = X.n1, a.gb = bias >= 0 ? n->grad + bias : nullptr;
+  a.gw = n->grad.as<double>() + weight, a.gw_o = X.n1, a.gb = bias >= 0 ? n->grad.as<double>() + bias : nullptr;
   hipLaunchKernelGGL(mixer_wgrad_kernel<T>, dim3((a.I + a.ones + 15) / 16, (a.O + 15) / 16), dim3(256), 0, ctx->stream, a);
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -562,11 +552,11 @@ template <typename T>
 int launch_ln_bwd(pdeopt_mixer* n, int which, int64_t gamma, int64_t beta, int64_t gc, int64_t gp, bool residual) {
   pdeopt_ctx* ctx = n->ctx;
   LnBwdArgs<T> a{};
-  a.y = static_cast<const T*>(n->Y[which]), a.dn = static_cast<const T*>(n->DN), a.dy = static_cast<T*>(n->DY);
-  a.gamma = static_cast<const T*>(n->packed) + gamma, a.gc = gc, a.gp = gp;
-  a.stats = n->stats + (size_t)which * n->s_batch * 2;
-  a.sums = n->stats + (size_t)(2 * n->K + 1) * n->s_batch * 2;
-  a.ggamma = n->grad + gamma, a.gbeta = n->grad + beta;
+  a.y = n->Y[which].as<const T>(), a.dn = n->DN.as<const T>(), a.dy = n->DY.as<T>();
+  a.gamma = n->packed.as<const T>() + gamma, a.gc = gc, a.gp = gp;
+  a.stats = n->stats.as<double>() + (size_t)which * n->s_batch * 2;
+  a.sums = n->stats.as<double>() + (size_t)(2 * n->K + 1) * n->s_batch * 2;
+  a.ggamma = n->grad.as<double>() + gamma, a.gbeta = n->grad.as<double>() + beta;
   a.B = ctx->prob.batch, a.C = n->C, a.P = n->P, a.residual = residual;
   const int64_t cp = (int64_t)n->C * n->P;
   hipLaunchKernelGGL(mixer_ln_bwd_sums_kernel<T>, dim3(a.B), dim3(256), 0, ctx->stream, a);
@@ -584,39 +574,39 @@ int backward(pdeopt_mixer* n, const void* u, const void* gmu, void* lam) {
   int rc = 0;
   // conv_out and the final norm
   hipLaunchKernelGGL(mixer_sum_kernel<T>, dim3(1), dim3(256), 0, ctx->stream, static_cast<const T*>(gmu),
-                     (int64_t)ctx->prob.batch * n->nx * n->ny, n->grad + n->bout);
+                     (int64_t)ctx->prob.batch * n->nx * n->ny, n->grad.as<double>() + n->bout);
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  if ((rc = launch_wgrad<T>(n, normed(plain<T>(n->Y[last], cp, P, C, 1, P), n, n->gf, n->bef, 1, P, last), patches<T>(n, gmu), n->wout, -1)))
+  if ((rc = launch_wgrad<T>(n, normed(plain<T>(n->Y[last].get(), cp, P, C, 1, P), n, n->gf, n->bef, 1, P, last), patches<T>(n, gmu), n->wout, -1)))
     return rc;
-  if ((rc = launch_gemm(n, gemm<T>(n, patches<T>(n, gmu), n->r_out, C, n->DN, cp, 1, P)))) return rc;
+  if ((rc = launch_gemm(n, gemm<T>(n, patches<T>(n, gmu), n->r_out, C, n->DN.get(), cp, 1, P)))) return rc;
   if ((rc = launch_ln_bwd<T>(n, last, n->gf, n->bef, P, 1, false))) return rc;
   for (int k = n->K - 1; k >= 0; --k) {
     const pdeopt_mixer::Block& b = n->blk[k];
     // the hidden mixer: DY is the cotangent of y_b, as (patch, channel) rows
-    const Operand<T> dyt = plain<T>(n->DY, cp, P, C, 1, P);
-    if ((rc = launch_wgrad<T>(n, dyt, plain<T>(n->H2[k], pm, P, Mh, Mh, 1), b.w4, b.b4))) return rc;
-    GemmArgs<T> g4 = gemm<T>(n, dyt, b.r4, Mh, n->DZ, pm, Mh, 1);
-    g4.epi = EPI_DACT, g4.zaux = static_cast<const T*>(n->Z2[k]);
+    const Operand<T> dyt = plain<T>(n->DY.get(), cp, P, C, 1, P);
+    if ((rc = launch_wgrad<T>(n, dyt, plain<T>(n->H2[k].get(), pm, P, Mh, Mh, 1), b.w4, b.b4))) return rc;
+    GemmArgs<T> g4 = gemm<T>(n, dyt, b.r4, Mh, n->DZ.get(), pm, Mh, 1);
+    g4.epi = EPI_DACT, g4.zaux = n->Z2[k].as<const T>();
     if ((rc = launch_gemm(n, g4))) return rc;
-    const Operand<T> dz2 = plain<T>(n->DZ, pm, P, Mh, Mh, 1);
-    if ((rc = launch_wgrad<T>(n, dz2, normed(plain<T>(n->Y[2 * k + 1], cp, P, C, 1, P), n, b.g2, b.be2, C, 1, 2 * k + 1), b.w3, b.b3)))
+    const Operand<T> dz2 = plain<T>(n->DZ.get(), pm, P, Mh, Mh, 1);
+    if ((rc = launch_wgrad<T>(n, dz2, normed(plain<T>(n->Y[2 * k + 1].get(), cp, P, C, 1, P), n, b.g2, b.be2, C, 1, 2 * k + 1), b.w3, b.b3)))
       return rc;
-    if ((rc = launch_gemm(n, gemm<T>(n, dz2, b.r3, C, n->DN, cp, 1, P)))) return rc;
+    if ((rc = launch_gemm(n, gemm<T>(n, dz2, b.r3, C, n->DN.get(), cp, 1, P)))) return rc;
     if ((rc = launch_ln_bwd<T>(n, 2 * k + 1, b.g2, b.be2, 1, C, true))) return rc;
     // the patch mixer: DY is the cotangent of y_a, as (channel, patch) rows
-    const Operand<T> dy = plain<T>(n->DY, cp, C, P, P, 1);
-    if ((rc = launch_wgrad<T>(n, dy, plain<T>(n->H1[k], cm, C, Mp, Mp, 1), b.w2, b.b2))) return rc;
-    GemmArgs<T> g2 = gemm<T>(n, dy, b.r2, Mp, n->DZ, cm, Mp, 1);
-    g2.epi = EPI_DACT, g2.zaux = static_cast<const T*>(n->Z1[k]);
+    const Operand<T> dy = plain<T>(n->DY.get(), cp, C, P, P, 1);
+    if ((rc = launch_wgrad<T>(n, dy, plain<T>(n->H1[k].get(), cm, C, Mp, Mp, 1), b.w2, b.b2))) return rc;
+    GemmArgs<T> g2 = gemm<T>(n, dy, b.r2, Mp, n->DZ.get(), cm, Mp, 1);
+    g2.epi = EPI_DACT, g2.zaux = n->Z1[k].as<const T>();
     if ((rc = launch_gemm(n, g2))) return rc;
-    const Operand<T> dz1 = plain<T>(n->DZ, cm, C, Mp, Mp, 1);
-    if ((rc = launch_wgrad<T>(n, dz1, normed(plain<T>(n->Y[2 * k], cp, C, P, P, 1), n, b.g1, b.be1, P, 1, 2 * k), b.w1, b.b1))) return rc;
-    if ((rc = launch_gemm(n, gemm<T>(n, dz1, b.r1, P, n->DN, cp, P, 1)))) return rc;
+    const Operand<T> dz1 = plain<T>(n->DZ.get(), cm, C, Mp, Mp, 1);
+    if ((rc = launch_wgrad<T>(n, dz1, normed(plain<T>(n->Y[2 * k].get(), cp, C, P, P, 1), n, b.g1, b.be1, P, 1, 2 * k), b.w1, b.b1))) return rc;
+    if ((rc = launch_gemm(n, gemm<T>(n, dz1, b.r1, P, n->DN.get(), cp, P, 1)))) return rc;
     if ((rc = launch_ln_bwd<T>(n, 2 * k, b.g1, b.be1, P, 1, true))) return rc;
   }
   // conv_in: DY is the cotangent of y_0
-  const Operand<T> dy0 = plain<T>(n->DY, cp, P, C, 1, P);
+  const Operand<T> dy0 = plain<T>(n->DY.get(), cp, P, C, 1, P);
   if ((rc = launch_wgrad<T>(n, dy0, patches<T>(n, u), n->win, n->bin))) return rc;
   GemmArgs<T> a = gemm<T>(n, dy0, n->r_in, Q, lam, 0, 0, 0);
   a.epi = EPI_ADD;
@@ -658,14 +648,16 @@ int pdeopt_mixer_create(pdeopt_ctx* ctx, int patch, int hidden, int mix_patch, i
   n->pw = p.ny / patch, n->P = (int)patches, n->Q = patch * patch;
   lay_out(n);
   const auto bail = [&](hipError_t e, const char* what) {
-    if (n->grad) (void)hipFree(n->grad);
     delete n;
     return fail(ctx, PDEOPT_EHIP, "%s failed: %s", what, hipGetErrorString(e));
   };
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return bail(e, "hipSetDevice");
-  if ((e = hipMalloc((void**)&n->grad, n->n_params * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
-  if ((e = hipMemsetAsync(n->grad, 0, n->n_params * sizeof(double), ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+  if (const int rc = ensure_buffer(ctx, n->grad, n->n_params * sizeof(double))) {
+    delete n;
+    return rc;
+  }
+  if ((e = hipMemsetAsync(n->grad.as<double>(), 0, n->n_params * sizeof(double), ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
   *out = n;
   return PDEOPT_OK;
 }
@@ -713,8 +705,8 @@ int pdeopt_mixer_grad_read(pdeopt_mixer* n, double* out, int64_t count, int rese
   if (!out || count != n->n_params)
     return fail(ctx, PDEOPT_EINVAL, "the mixer has %lld parameters (got %lld)", (long long)n->n_params, (long long)count);
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, n->grad, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(n->grad, 0, count * sizeof(double), ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, n->grad.as<double>(), count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(n->grad.as<double>(), 0, count * sizeof(double), ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -723,9 +715,6 @@ int pdeopt_mixer_destroy(pdeopt_mixer* n) {
   if (!n) return PDEOPT_OK;
   (void)hipSetDevice(n->ctx->device);
   if (n->ctx->stream) (void)hipStreamSynchronize(n->ctx->stream);
-  free_workspace(n);
-  if (n->packed) (void)hipFree(n->packed);
-  if (n->grad) (void)hipFree(n->grad);
   delete n;
   return PDEOPT_OK;
 }

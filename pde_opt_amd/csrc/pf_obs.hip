@@ -286,15 +286,15 @@ int pf_observables_t(pdeopt_ctx* ctx, int env_first, int env_count, double* host
   // one block: the rows [envs][8], the partial rows [envs][slots][8], 3-D: mu [envs][cells], fp32: the fp64 parameters
   const size_t n_out = (size_t)kObs * env_count, n_part = n_out * (size_t)slots, n_mu = is3d ? (size_t)cells * env_count : 0;
   const size_t need = sizeof(double) * (n_out + n_part + n_mu) + sizeof(EnvParams<double>) * (size_t)env_count;
-  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->pf_obs_dev, &ctx->pf_obs_cap, need, /*sync_first=*/true)) return rc;
-  double* const out = ctx->pf_obs_dev;
+  if (const int rc = grow_device_buffer(ctx, ctx->pf_obs_dev, need, /*sync_first=*/true)) return rc;
+  double* const out = ctx->pf_obs_dev.as<double>();
   double* const mu3 = out + n_out + n_part;
   PfObsArgs<T> a{};
   std::vector<EnvParams<double>> widened;
   int rc = params_fp64<T>(ctx, env_first, env_count, reinterpret_cast<EnvParams<double>*>(mu3 + n_mu), widened, &a.ep);
   if (rc) return rc;
   a.bstride = cells;
-  a.u = static_cast<const T*>(ctx->Y) + (int64_t)env_first * cells;
+  a.u = ctx->Y.as<const T>() + (int64_t)env_first * cells;
   a.mu3 = mu3;
   a.mu = closure_spec(p.mu);
   a.mob = closure_spec(p.mob);

@@ -79,16 +79,16 @@ __global__ __launch_bounds__(256) void reduce_kernel(const T* __restrict__ y, in
 int run_pass(pdeopt_ctx* ctx, const double* shift_dev, std::vector<Partial>& host) {
   const int batch = ctx->prob.batch;
   const size_t need = (size_t)batch * kChunks * sizeof(Partial);
-  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false)) return rc;
+  if (const int rc = grow_device_buffer(ctx, ctx->red_dev, need, /*sync_first=*/false)) return rc;
   dim3 grid(kChunks, batch), block(256);
   with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(reduce_kernel<T>, grid, block, 0, ctx->stream, (const T*)ctx->Y, (int64_t)ctx->env_elems, shift_dev,
-                       (Partial*)ctx->red_dev);
+    hipLaunchKernelGGL(reduce_kernel<T>, grid, block, 0, ctx->stream, ctx->Y.as<const T>(), (int64_t)ctx->env_elems, shift_dev,
+                       ctx->red_dev.as<Partial>());
   });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   host.resize((size_t)batch * kChunks);
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), ctx->red_dev, need, hipMemcpyDeviceToHost,
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), ctx->red_dev.get(), need, hipMemcpyDeviceToHost,
                                        ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
@@ -119,19 +119,19 @@ int observe_u8(pdeopt_ctx* ctx, double lo, double hi, int env_first, int env_cou
   if (!(hi > lo)) return fail(ctx, PDEOPT_EINVAL, "observe_u8 needs hi > lo");
   const int64_t n = (int64_t)ctx->env_elems * env_count;
   if (n % 4) return fail(ctx, PDEOPT_EINVAL, "observe_u8 needs a multiple of 4 cells");
-  int rc = ensure_buffer(ctx, &ctx->obs_dev, ctx->env_elems * (size_t)ctx->prob.batch);
+  int rc = ensure_buffer(ctx, ctx->obs_dev, ctx->env_elems * (size_t)ctx->prob.batch);
   if (rc) return rc;
   const int64_t n4 = n / 4;
   const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 4096);
   const size_t off = (size_t)env_first * ctx->env_elems;
   with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(observe_u8_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, (const T*)ctx->Y + off,
-                       (uint32_t*)ctx->obs_dev, n4, (T)lo, (T)(255.0 / (hi - lo)));
+    hipLaunchKernelGGL(observe_u8_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->Y.as<const T>() + off,
+                       ctx->obs_dev.as<uint32_t>(), n4, (T)lo, (T)(255.0 / (hi - lo)));
   });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   if (host_out)  // nullptr: the frames stay in ctx->obs_dev (pdeopt_observe_u8_device)
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->obs_dev, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->obs_dev.get(), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -212,8 +212,8 @@ int detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int env_firs
   const size_t cells = (size_t)p.nx * p.ny;
   const size_t wbytes = host_winding ? cells * env_count * sizeof(int32_t) : 0;
   const size_t need = wbytes + (size_t)env_count * 3 * sizeof(long long);
-  if (const int rc = grow_device_buffer(ctx, &ctx->vort_dev, &ctx->vort_cap, need, /*sync_first=*/true)) return rc;
-  long long* counts = reinterpret_cast<long long*>(ctx->vort_dev);
+  if (const int rc = grow_device_buffer(ctx, ctx->vort_dev, need, /*sync_first=*/true)) return rc;
+  long long* counts = ctx->vort_dev.as<long long>();
   int32_t* wdev = host_winding ? reinterpret_cast<int32_t*>(counts + (size_t)env_count * 3) : nullptr;
   PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, (size_t)env_count * 3 * sizeof(long long), ctx->stream));
   dim3 grid((p.ny + 63) / 64, (p.nx + 3) / 4, env_count), block(256);
@@ -221,7 +221,7 @@ int detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int env_firs
   const size_t off = (size_t)env_first * ctx->env_elems;
   with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(vortex_kernel<T>, grid, block, 0, ctx->stream, (const T*)ctx->Y + off, wdev, counts, p.nx, p.ny,
+    hipLaunchKernelGGL(vortex_kernel<T>, grid, block, 0, ctx->stream, ctx->Y.as<const T>() + off, wdev, counts, p.nx, p.ny,
                        (T)amp_thresh, (T)tol);
   });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -260,13 +260,13 @@ int probe_state(pdeopt_ctx* ctx, const int32_t* cells, int n_probes, int env_fir
   }
   const int64_t total = (int64_t)env_count * n_probes * ctx->comps;
   const size_t need = (size_t)n_probes * sizeof(int64_t) + (size_t)total * sizeof(double);
-  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false)) return rc;
-  double* out_dev = ctx->red_dev;
-  int64_t* cell_dev = reinterpret_cast<int64_t*>(ctx->red_dev + total);
+  if (const int rc = grow_device_buffer(ctx, ctx->red_dev, need, /*sync_first=*/false)) return rc;
+  double* out_dev = ctx->red_dev.as<double>();
+  int64_t* cell_dev = ctx->red_dev.as<int64_t>() + total;  // (8-byte words both)
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(cell_dev, flat.data(), (size_t)n_probes * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   const int blocks = (int)((total + 255) / 256);
   with_dtype(ctx, [&](auto t) {
-    hipLaunchKernelGGL(probe_kernel<decltype(t)>, dim3(blocks), dim3(256), 0, ctx->stream, (const decltype(t)*)ctx->Y, cell_dev,
+    hipLaunchKernelGGL(probe_kernel<decltype(t)>, dim3(blocks), dim3(256), 0, ctx->stream, (const decltype(t)*)ctx->Y.get(), cell_dev,
                        n_probes, ctx->comps, (int64_t)ctx->env_elems, env_first, out_dev, total);
   });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -303,12 +303,11 @@ int reduce_state(pdeopt_ctx* ctx, int op, double* out) {
   }
   if (op == PDEOPT_RED_VAR) {
     // second pass around the mean, like np.var
-    if (!ctx->red_mean_dev)
-      PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->red_mean_dev, sizeof(double) * 65536));
+    if ((rc = ensure_buffer(ctx, ctx->red_mean_dev, sizeof(double) * 65536))) return rc;
     if (batch > 65536) return fail(ctx, PDEOPT_EINVAL, "batch too large for variance");
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->red_mean_dev, mean.data(), sizeof(double) * batch,
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->red_mean_dev.as<double>(), mean.data(), sizeof(double) * batch,
                                          hipMemcpyHostToDevice, ctx->stream));
-    rc = run_pass(ctx, ctx->red_mean_dev, part);
+    rc = run_pass(ctx, ctx->red_mean_dev.as<double>(), part);
     if (rc) return rc;
     for (int b = 0; b < batch; ++b) {
       double q = 0, bad = 0;

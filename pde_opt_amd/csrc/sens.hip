@@ -47,12 +47,10 @@ struct Sens {
   int B = 0, P = 0;
   int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB / PDEOPT_SENS_KAPPA
   int index[kMaxSens] = {};  // coefficient k of that closure
-  void* data = nullptr;      // [n_frames][B][*spatial] observed frames or cotangents, problem dtype
+  DeviceBuffer data;         // [n_frames][B][*spatial] observed frames or cotangents, problem dtype; grow-only
   int n_frames = 0;
-  size_t data_bytes = 0;
-  double* partial = nullptr;  // [B][K][nblk] per-block sums of the accumulation (K = P for the contraction)
-  double* sums = nullptr;     // [B][K]
-  size_t partial_bytes = 0, sums_bytes = 0;
+  DeviceBuffer partial;      // doubles [B][K][nblk] per-block sums of the accumulation (K = P for the contraction); grow-only
+  DeviceBuffer sums;         // doubles [B][K]; grow-only
   bool has_kappa = false;  // some role is PDEOPT_SENS_KAPPA: the KAPPA kernels, and IMEX through the rocFFT loop
 };
 
@@ -616,11 +614,11 @@ int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
 template <typename T>
 int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
   int rc;
-  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
   const GridRecip r = grid_recip(ctx->prob);
   Sens3Args<T> a{};
   fill_tangent_args<T>(a, ctx, in, out);
-  a.w = static_cast<T*>(ctx->KS);
+  a.w = ctx->KS.as<T>();
   a.nz = ctx->prob.nz;
   a.rhz = T(r.rz);
   a.rhz2 = T(r.rz2);
@@ -658,8 +656,8 @@ template <typename T>
 int euler_update(pdeopt_ctx* ctx, double dt) {
   const int64_t n = (int64_t)ctx->env_elems * ctx->prob.batch;
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(sens_axpy_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<T*>(ctx->Y),
-                     static_cast<const T*>(ctx->TA), (T)dt, n);
+  hipLaunchKernelGGL(sens_axpy_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->Y.as<T>(),
+                     ctx->TA.as<const T>(), (T)dt, n);
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -672,10 +670,10 @@ template <typename T>
 int rk4_substep(pdeopt_ctx* ctx, double dt, double ts, bool timed) {
   const int64_t n = (int64_t)ctx->env_elems * ctx->prob.batch;
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  T* const y = static_cast<T*>(ctx->Y);
-  T* const k = static_cast<T*>(ctx->TA);
-  T* const in = static_cast<T*>(ctx->TB);
-  T* const acc = static_cast<T*>(ctx->ACC);
+  T* const y = ctx->Y.as<T>();
+  T* const k = ctx->TA.as<T>();
+  T* const in = ctx->TB.as<T>();
+  T* const acc = ctx->ACC.as<T>();
   const double a[4] = {dt / 2, dt / 2, dt, 0.0}, b[4] = {dt / 6, dt / 3, dt / 3, dt / 6};
   const double tst[4] = {ts, ts + dt / 2, ts + dt / 2, ts + dt};
   for (int st = 0; st < 4; ++st) {
@@ -693,17 +691,17 @@ int rk4_substep(pdeopt_ctx* ctx, double dt, double ts, bool timed) {
 int ensure_sums(pdeopt_ctx* ctx, int K, int nblk) {
   Sens& s = *ctx->sens;
   const size_t pbytes = (size_t)s.B * K * nblk * sizeof(double), sbytes = (size_t)s.B * K * sizeof(double);
-  const int rc = grow_device_buffer(ctx, (void**)&s.partial, &s.partial_bytes, pbytes, /*sync_first=*/true);
-  return rc ? rc : grow_device_buffer(ctx, (void**)&s.sums, &s.sums_bytes, sbytes, /*sync_first=*/true);
+  const int rc = grow_device_buffer(ctx, s.partial, pbytes, /*sync_first=*/true);
+  return rc ? rc : grow_device_buffer(ctx, s.sums, sbytes, /*sync_first=*/true);
 }
 
 // sums[b][k] = the block totals of partial[b][k][.] in block order, copied to the host
 int finish_sums(pdeopt_ctx* ctx, int K, int nblk, double* host_out) {
   Sens& s = *ctx->sens;
   const int n = s.B * K;
-  hipLaunchKernelGGL(sens_gn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.partial, s.sums, n, nblk);
+  hipLaunchKernelGGL(sens_gn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.partial.as<double>(), s.sums.as<double>(), n, nblk);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, s.sums, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, s.sums.as<double>(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -717,9 +715,9 @@ int reduce_frame(pdeopt_ctx* ctx, Kernel kernel, int K, int grid_z, int frame, d
   const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
   int rc;
   if ((rc = ensure_sums(ctx, K, nblk))) return rc;
-  const T* v = static_cast<const T*>(s.data) + (int64_t)frame * s.B * cells;
-  hipLaunchKernelGGL(kernel, dim3(nblk, s.B, grid_z), dim3(kGnThreads), 0, ctx->stream, static_cast<const T*>(ctx->Y),
-                     static_cast<const T*>(ctx->SNAP), v, s.partial, s.B, s.P, cells, (T)theta, interp);
+  const T* v = s.data.as<const T>() + (int64_t)frame * s.B * cells;
+  hipLaunchKernelGGL(kernel, dim3(nblk, s.B, grid_z), dim3(kGnThreads), 0, ctx->stream, ctx->Y.as<const T>(),
+                     ctx->SNAP.as<const T>(), v, s.partial.as<double>(), s.B, s.P, cells, (T)theta, interp);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return finish_sums(ctx, K, nblk, host_out);
 }
@@ -739,11 +737,7 @@ int check_frame(pdeopt_ctx* ctx, int frame, int interp) {
 }  // namespace
 
 void sens_destroy(pdeopt_ctx* ctx) {
-  Sens* s = ctx->sens;
-  if (!s) return;
-  for (void* p : {s->data, (void*)s->partial, (void*)s->sums})
-    if (p) (void)hipFree(p);
-  delete s;
+  delete ctx->sens;
   ctx->sens = nullptr;
 }
 
@@ -812,10 +806,10 @@ int pdeopt_sens_rhs(pdeopt_ctx* ctx, void* host_out) {
   int rc = check_sens(ctx);
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA, 0.0))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = sens_slopes(ctx, ctx->Y.get(), ctx->TA.get(), 0.0))) return rc;
   if (host_out)
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA, ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->TA.get(), ctx->total_bytes, hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }
@@ -867,13 +861,13 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
       if ((rc = imex_rocfft_prepare_kappa(ctx, dt, kappa))) return rc;
     }
   } else if (integrator == PDEOPT_INT_RK4 && ac) {
-    if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
-    if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
   } else if (integrator != PDEOPT_INT_EULER) {
     return fail(ctx, PDEOPT_EINVAL, "sensitivities support the IMEX and Euler integrators for Cahn-Hilliard, Euler and RK4 for "
                                     "Allen-Cahn (got %d)", integrator);
   }
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
   if (sbm) ctx->tt_misses = 0;
   for (int64_t s = 0; s < n_substeps; ++s) {
     const double ts = t0 + (double)s * dt;
@@ -881,7 +875,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
       if ((rc = with_dtype(ctx, [&](auto t) { return rk4_substep<decltype(t)>(ctx, dt, ts, sbm); }))) return rc;
       continue;
     }
-    if ((rc = sens_slopes(ctx, ctx->Y, ctx->TA, sbm ? ts : 0.0))) return rc;
+    if ((rc = sens_slopes(ctx, ctx->Y.get(), ctx->TA.get(), sbm ? ts : 0.0))) return rc;
     if (integrator == PDEOPT_INT_IMEX && fused) {
       rc = imex_fused_passes(ctx, whole_batch(ctx), dt);
     } else if (integrator == PDEOPT_INT_IMEX) {
@@ -923,9 +917,9 @@ int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {
   Sens& s = *ctx->sens;
   const size_t bytes = (size_t)n_frames * s.B * sens_cells(ctx) * ctx->esize;
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = grow_device_buffer(ctx, &s.data, &s.data_bytes, bytes, /*sync_first=*/false))) return rc;  // (synchronised above)
+  if ((rc = grow_device_buffer(ctx, s.data, bytes, /*sync_first=*/false))) return rc;  // (synchronised above)
   s.n_frames = n_frames;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.data, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.data.get(), host, bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }

@@ -211,9 +211,9 @@ int launch_sbm_tangent_rhs(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in
   a.k = static_cast<T*>(out);
   set_closures<T>(a, ctx, 0);
   a.fe = closure_spec(p.fe);
-  a.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
-  a.ngp = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
-  a.mask = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
+  a.psi = ctx->aux[PDEOPT_AUX_SBM_PSI].dev.as<const T>();
+  a.ngp = ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev.as<const T>();
+  a.mask = ctx->aux[PDEOPT_AUX_SBM_MASK].dev.as<const T>();
   a.nx = p.nx;
   a.ny = p.ny;
   a.B = sp.B;

@@ -25,29 +25,29 @@ struct Spectral {
   bool setup = false;
   rocfft_plan fwd = nullptr, inv = nullptr;
   rocfft_execution_info info = nullptr;
-  void* work = nullptr;
-  size_t work_bytes = 0;
-  void* cbuf = nullptr;    // complex work field (IMEX, rhs_fourier)
-  void* cbuf2 = nullptr;   // rhs_fourier work fields
-  void* cbuf3 = nullptr;
-  void* mult = nullptr;    // complex spectral multiplier, shared [nx][ny]
-  void* dens = nullptr;    // real |psi0|^2 (Strang)
-  double* partial = nullptr;  // [batch][kNormBlocks]
-  double* scale = nullptr;    // [batch]
+  DeviceBuffer work;
+  size_t work_bytes = 0;   // what the two plans ask for
+  DeviceBuffer cbuf;       // complex work field (IMEX, rhs_fourier)
+  DeviceBuffer cbuf2;      // rhs_fourier work fields
+  DeviceBuffer cbuf3;
+  DeviceBuffer mult;       // complex spectral multiplier, shared [nx][ny]
+  DeviceBuffer dens;       // real |psi0|^2 (Strang)
+  DeviceBuffer partial;    // doubles [batch][kNormBlocks]
+  DeviceBuffer scale;      // doubles [batch]
   // real <-> hermitian transforms of the IMEX step (half the bytes of C2C)
   rocfft_plan r2c = nullptr, c2r = nullptr;
   rocfft_execution_info rinfo = nullptr;
-  void* rwork = nullptr;
-  void* hbuf = nullptr;    // hermitian half-spectrum work field
-  void* hmult = nullptr;   // multiplier on the half-spectrum
-  void* hmultk = nullptr;  // d hmult / d kappa (sensitivities of kappa), cached on (dt, A, kappa)
+  DeviceBuffer rwork;
+  DeviceBuffer hbuf;       // hermitian half-spectrum work field
+  DeviceBuffer hmult;      // multiplier on the half-spectrum
+  DeviceBuffer hmultk;     // d hmult / d kappa (sensitivities of kappa), cached on (dt, A, kappa)
   double multk_dt = NAN, multk_A = NAN, multk_kappa = NAN;
   int64_t half_cells = 0;  // complex elements of one half-spectrum
   // batched 1-D complex plans along one axis of a [batch][nx][ny] field (the rotating-frame split step on grids the
   // hand-written passes do not cover): [0] along x (stride ny, one environment per execution), [1] along y
   rocfft_plan ax_fwd[2] = {nullptr, nullptr}, ax_inv[2] = {nullptr, nullptr};
   rocfft_execution_info ax_info = nullptr;
-  void* ax_work = nullptr;
+  DeviceBuffer ax_work;
   // cache key of `mult` / `hmult`
   int mult_kind = -1;
   double mult_dt = NAN, mult_A = NAN, mult_tr = NAN, mult_ti = NAN;
@@ -95,9 +95,9 @@ int ensure_plans(pdeopt_ctx* ctx) {
   sp.work_bytes = w1 > w2 ? w1 : w2;
   PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_create(&sp.info));
   if (sp.work_bytes) {
-    int rc = ensure_buffer(ctx, &sp.work, sp.work_bytes);
+    int rc = ensure_buffer(ctx, sp.work, sp.work_bytes);
     if (rc) return rc;
-    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.info, sp.work, sp.work_bytes));
+    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.info, sp.work.get(), sp.work_bytes));
   }
   PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_stream(sp.info, ctx->stream));
   sp.setup = true;
@@ -131,9 +131,9 @@ int ensure_real_plans(pdeopt_ctx* ctx) {
   const size_t wb = w1 > w2 ? w1 : w2;
   PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_create(&sp.rinfo));
   if (wb) {
-    int rc = ensure_buffer(ctx, &sp.rwork, wb);
+    int rc = ensure_buffer(ctx, sp.rwork, wb);
     if (rc) return rc;
-    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.rinfo, sp.rwork, wb));
+    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.rinfo, sp.rwork.get(), wb));
   }
   PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_stream(sp.rinfo, ctx->stream));
   return PDEOPT_OK;
@@ -180,9 +180,9 @@ int ensure_axis_plans(pdeopt_ctx* ctx) {
   }
   PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_create(&sp.ax_info));
   if (wmax) {
-    int rc = ensure_buffer(ctx, &sp.ax_work, wmax);
+    int rc = ensure_buffer(ctx, sp.ax_work, wmax);
     if (rc) return rc;
-    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.ax_info, sp.ax_work, wmax));
+    PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_work_buffer(sp.ax_info, sp.ax_work.get(), wmax));
   }
   PDEOPT_FFT_CHECK(ctx, rocfft_execution_info_set_stream(sp.ax_info, ctx->stream));
   return PDEOPT_OK;
@@ -325,11 +325,11 @@ template <typename T>
 int upload_mult(pdeopt_ctx* ctx, const std::vector<std::complex<double>>& m) {
   Spectral& sp = *ctx->spectral;
   const size_t cells = m.size();
-  int rc = ensure_buffer(ctx, &sp.mult, cells * 2 * sizeof(T));
+  int rc = ensure_buffer(ctx, sp.mult, cells * 2 * sizeof(T));
   if (rc) return rc;
   std::vector<C2<T>> h(cells);
   for (size_t i = 0; i < cells; ++i) h[i] = C2<T>{(T)m[i].real(), (T)m[i].imag()};
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.mult, h.data(), cells * sizeof(C2<T>),
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.mult.get(), h.data(), cells * sizeof(C2<T>),
                                        hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
@@ -343,10 +343,10 @@ int fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::complex<doubl
   if (a.per_env) return fail(ctx, PDEOPT_EINVAL, "spectral aux fields must be shared across the batch");
   if (ctx->prob.dtype == PDEOPT_F32) {
     std::vector<float> h(cells * 2);
-    PDEOPT_HIP_CHECK(ctx, hipMemcpy(h.data(), a.dev, cells * 8, hipMemcpyDeviceToHost));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpy(h.data(), a.dev.get(), cells * 8, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < cells; ++i) out[i] = {h[2 * i], h[2 * i + 1]};
   } else {
-    PDEOPT_HIP_CHECK(ctx, hipMemcpy(out.data(), a.dev, cells * 16, hipMemcpyDeviceToHost));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpy(out.data(), a.dev.get(), cells * 16, hipMemcpyDeviceToHost));
   }
   return PDEOPT_OK;
 }
@@ -392,15 +392,15 @@ int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
   int rc;
   if ((rc = ensure_real_plans(ctx))) return rc;
   const int64_t hc = sp.half_cells;
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &sp.hbuf, (size_t)hc * p.batch * 2 * sizeof(T)))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.hbuf, (size_t)hc * p.batch * 2 * sizeof(T)))) return rc;
   if (sp.mult_kind != 2 || sp.mult_dt != dt || sp.mult_A != ctx->imex_A) {
     std::vector<std::complex<double>> sym;
     if ((rc = fetch_complex_aux(ctx, PDEOPT_AUX_IMEX_SYMBOL, sym))) return rc;
     const double inv_n = 1.0 / (double)cells;
     const std::vector<C2<T>> h = half_spectrum<T>(p, hc, [&](size_t q) { return inv_n / (1.0 + ctx->imex_A * dt * sym[q]); });
-    if ((rc = ensure_buffer(ctx, &sp.hmult, (size_t)hc * sizeof(C2<T>)))) return rc;
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.hmult, h.data(), (size_t)hc * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ensure_buffer(ctx, sp.hmult, (size_t)hc * sizeof(C2<T>)))) return rc;
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.hmult.get(), h.data(), (size_t)hc * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     sp.mult_kind = 2;
     sp.mult_dt = dt;
@@ -415,10 +415,10 @@ int imex_rocfft_apply_t(pdeopt_ctx* ctx) {
   Spectral& sp = *ctx->spectral;
   const int64_t hc = sp.half_cells;
   int rc;
-  if ((rc = real_fft_exec(ctx, true, ctx->TA, sp.hbuf))) return rc;
+  if ((rc = real_fft_exec(ctx, true, ctx->TA.get(), sp.hbuf.get()))) return rc;
   hipLaunchKernelGGL((spectral_mul_kernel<T, false>), dim3(grid_for(hc), ctx->prob.batch), dim3(256), 0,
-                     ctx->stream, (C2<T>*)sp.hbuf, (const C2<T>*)sp.hmult, nullptr, hc);
-  return real_fft_exec(ctx, false, sp.hbuf, ctx->TA);
+                     ctx->stream, sp.hbuf.as<C2<T>>(), sp.hmult.as<const C2<T>>(), nullptr, hc);
+  return real_fft_exec(ctx, false, sp.hbuf.get(), ctx->TA.get());
 }
 
 // y += dt TA over the whole batch
@@ -427,7 +427,7 @@ int axpy_state_t(pdeopt_ctx* ctx, double dt) {
   const pdeopt_problem& p = ctx->prob;
   const int64_t total = (int64_t)p.nx * p.ny * (p.nz > 1 ? p.nz : 1) * p.batch;
   hipLaunchKernelGGL(axpy_real_kernel<T>, dim3(grid_for(total)), dim3(256), 0, ctx->stream,
-                     (T*)ctx->Y, (const T*)ctx->TA, (T)dt, total);
+                     ctx->Y.as<T>(), ctx->TA.as<const T>(), (T)dt, total);
   return PDEOPT_OK;
 }
 
@@ -499,8 +499,8 @@ int imex_rocfft_prepare_kappa_t(pdeopt_ctx* ctx, double dt, double kappa) {
     const std::complex<double> L = 1.0 + adt * sym[q];
     return -inv_n * adt * (sym[q] / kappa) / (L * L);
   });
-  if ((rc = ensure_buffer(ctx, &sp.hmultk, (size_t)hc * sizeof(C2<T>)))) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.hmultk, h.data(), (size_t)hc * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ensure_buffer(ctx, sp.hmultk, (size_t)hc * sizeof(C2<T>)))) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sp.hmultk.get(), h.data(), (size_t)hc * sizeof(C2<T>), hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   sp.multk_dt = dt;
   sp.multk_A = ctx->imex_A;
@@ -515,17 +515,17 @@ int imex_rocfft_solve_kappa_t(pdeopt_ctx* ctx, double dt, int B, int P, const in
   if (P < 1 || P > kMaxSens || (int64_t)(1 + P) * B != ctx->prob.batch)
     return fail(ctx, PDEOPT_ESTATE, "IMEX kappa multiply: batch %d is not (1 + %d) %d", ctx->prob.batch, P, B);
   int rc;
-  if ((rc = real_fft_exec(ctx, true, ctx->TA, sp.hbuf))) return rc;
+  if ((rc = real_fft_exec(ctx, true, ctx->TA.get(), sp.hbuf.get()))) return rc;
   KappaMulArgs<T> a{};
-  a.c = (C2<T>*)sp.hbuf;
-  a.m = (const C2<T>*)sp.hmult;
-  a.mk = (const C2<T>*)sp.hmultk;
+  a.c = sp.hbuf.as<C2<T>>();
+  a.m = sp.hmult.as<const C2<T>>();
+  a.mk = sp.hmultk.as<const C2<T>>();
   a.cells = hc;
   a.B = B;
   a.P = P;
   for (int j = 0; j < P; ++j) a.role[j] = role[j];
   hipLaunchKernelGGL(sens_imex_mul_kappa_kernel<T>, dim3(grid_for(hc), B), dim3(256), 0, ctx->stream, a);
-  if ((rc = real_fft_exec(ctx, false, sp.hbuf, ctx->TA))) return rc;
+  if ((rc = real_fft_exec(ctx, false, sp.hbuf.get(), ctx->TA.get()))) return rc;
   return axpy_state_t<T>(ctx, dt);
 }
 
@@ -539,7 +539,7 @@ int imex_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   int rc;
   if ((rc = imex_rocfft_prepare_t<T>(ctx, dt))) return rc;
   for (int64_t s = 0; s < n; ++s) {
-    if ((rc = launch_rhs(ctx, whole_batch(ctx), ctx->Y, ctx->TA, 0.0))) return rc;
+    if ((rc = launch_rhs(ctx, whole_batch(ctx), ctx->Y.get(), ctx->TA.get(), 0.0))) return rc;
     if ((rc = imex_rocfft_solve_t<T>(ctx, dt))) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -554,9 +554,9 @@ int strang_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   const int64_t cells = (int64_t)p.nx * p.ny;
   const int64_t total = cells * p.batch;
   int rc;
-  if ((rc = ensure_buffer(ctx, &sp.dens, (size_t)total * sizeof(T)))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&sp.partial, sizeof(double) * kNormBlocks * p.batch))) return rc;
-  if ((rc = ensure_buffer(ctx, (void**)&sp.scale, sizeof(double) * p.batch))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.dens, (size_t)total * sizeof(T)))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.partial, sizeof(double) * kNormBlocks * p.batch))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.scale, sizeof(double) * p.batch))) return rc;
   const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
   if (sp.mult_kind != 1 || sp.mult_dt != dt || sp.mult_tr != ctx->ts_re || sp.mult_ti != ctx->ts_im) {
     // E / N,  E = exp(A_term tau / 2)   (solvers.py:105)
@@ -575,24 +575,24 @@ int strang_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   const dim3 mgrid(grid_for(cells), p.batch);
   for (int64_t s = 0; s < n; ++s) {
     hipLaunchKernelGGL(density_kernel<T>, dim3(grid_for(total)), dim3(256), 0, ctx->stream,
-                       (const C2<T>*)ctx->Y, (T*)sp.dens, total);
-    if ((rc = fft_exec(ctx, true, ctx->Y))) return rc;
+                       ctx->Y.as<const C2<T>>(), sp.dens.as<T>(), total);
+    if ((rc = fft_exec(ctx, true, ctx->Y.get()))) return rc;
     hipLaunchKernelGGL((spectral_mul_kernel<T, false>), mgrid, dim3(256), 0, ctx->stream,
-                       (C2<T>*)ctx->Y, (const C2<T>*)sp.mult, nullptr, cells);
-    if ((rc = fft_exec(ctx, false, ctx->Y))) return rc;
+                       ctx->Y.as<C2<T>>(), sp.mult.as<const C2<T>>(), nullptr, cells);
+    if ((rc = fft_exec(ctx, false, ctx->Y.get()))) return rc;
     // b = terms.vf(t0, y0): a time-dependent potential is evaluated at this substep's start time (solvers.py:109)
     if ((rc = refresh_time_aux(ctx, PDEOPT_AUX_GPE_POTENTIAL, t0 + (double)s * dt))) return rc;
     hipLaunchKernelGGL(strang_b_kernel<T>, dim3(kNormBlocks, p.batch), dim3(256), 0, ctx->stream,
-                       (C2<T>*)ctx->Y, (const T*)sp.dens, (const T*)pot.dev, pot_stride,
-                       (const EnvParams<T>*)ctx->env_params_dev, (T)tau.real(), (T)tau.imag(), cells,
-                       sp.partial, make_spot_args<T>(ctx, 0, t0 + (double)s * dt), p.ny);
+                       ctx->Y.as<C2<T>>(), sp.dens.as<const T>(), pot.dev.as<const T>(), pot_stride,
+                       ctx->env_params_dev.as<const EnvParams<T>>(), (T)tau.real(), (T)tau.imag(), cells,
+                       sp.partial.as<double>(), make_spot_args<T>(ctx, 0, t0 + (double)s * dt), p.ny);
     hipLaunchKernelGGL(norm_finalize_kernel, dim3((p.batch + 63) / 64), dim3(64), 0, ctx->stream,
-                       (const double*)sp.partial, kNormBlocks, ctx->strang_dx * ctx->strang_dx,
-                       sp.scale, p.batch);
-    if ((rc = fft_exec(ctx, true, ctx->Y))) return rc;
+                       sp.partial.as<const double>(), kNormBlocks, ctx->strang_dx * ctx->strang_dx,
+                       sp.scale.as<double>(), p.batch);
+    if ((rc = fft_exec(ctx, true, ctx->Y.get()))) return rc;
     hipLaunchKernelGGL((spectral_mul_kernel<T, true>), mgrid, dim3(256), 0, ctx->stream,
-                       (C2<T>*)ctx->Y, (const C2<T>*)sp.mult, (const double*)sp.scale, cells);
-    if ((rc = fft_exec(ctx, false, ctx->Y))) return rc;
+                       ctx->Y.as<C2<T>>(), sp.mult.as<const C2<T>>(), sp.scale.as<const double>(), cells);
+    if ((rc = fft_exec(ctx, false, ctx->Y.get()))) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   ctx->last_kernel = "strang_rocfft_c2c";
@@ -698,12 +698,12 @@ int rhs_fourier_t(pdeopt_ctx* ctx, const void* in, void* out) {
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny, total = cells * p.batch;
   int rc;
-  if ((rc = ensure_buffer(ctx, &sp.cbuf2, (size_t)total * 2 * sizeof(T)))) return rc;
-  if ((rc = ensure_buffer(ctx, &sp.cbuf3, (size_t)total * 2 * sizeof(T)))) return rc;
-  C2<T>* a = (C2<T>*)sp.cbuf2;
-  C2<T>* b = (C2<T>*)sp.cbuf3;
+  if ((rc = ensure_buffer(ctx, sp.cbuf2, (size_t)total * 2 * sizeof(T)))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.cbuf3, (size_t)total * 2 * sizeof(T)))) return rc;
+  C2<T>* a = sp.cbuf2.as<C2<T>>();
+  C2<T>* b = sp.cbuf3.as<C2<T>>();
   const T* u = (const T*)in;
-  const auto* ep = (const EnvParams<T>*)ctx->env_params_dev;
+  const auto* ep = ctx->env_params_dev.as<const EnvParams<T>>();
   const ClosureSpec mu{p.mu.kind, p.mu.flags, p.mu.n}, mob{p.mob.kind, p.mob.flags, p.mob.n};
   const dim3 grid(grid_for(cells), p.batch), blk(256);
   const T inv_lx = T(1.0 / (p.nx * p.hx)), inv_ly = T(1.0 / (p.ny * p.hy)), inv_n = T(1.0 / (double)cells);
@@ -814,14 +814,14 @@ int rhs_fourier3_t(pdeopt_ctx* ctx, const void* in, void* out) {
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny * p.nz, total = cells * p.batch;
   int rc;
-  if ((rc = ensure_buffer(ctx, &sp.cbuf, (size_t)total * 2 * sizeof(T)))) return rc;
-  if ((rc = ensure_buffer(ctx, &sp.cbuf2, (size_t)total * 2 * sizeof(T)))) return rc;
-  if ((rc = ensure_buffer(ctx, &sp.cbuf3, (size_t)total * 2 * sizeof(T)))) return rc;
-  C2<T>* a = (C2<T>*)sp.cbuf2;   // F[u], later the accumulated divergence
-  C2<T>* b = (C2<T>*)sp.cbuf3;   // F[mu_h(u)], then t_hat
-  C2<T>* w = (C2<T>*)sp.cbuf;    // one axis at a time
+  if ((rc = ensure_buffer(ctx, sp.cbuf, (size_t)total * 2 * sizeof(T)))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.cbuf2, (size_t)total * 2 * sizeof(T)))) return rc;
+  if ((rc = ensure_buffer(ctx, sp.cbuf3, (size_t)total * 2 * sizeof(T)))) return rc;
+  C2<T>* a = sp.cbuf2.as<C2<T>>();   // F[u], later the accumulated divergence
+  C2<T>* b = sp.cbuf3.as<C2<T>>();   // F[mu_h(u)], then t_hat
+  C2<T>* w = sp.cbuf.as<C2<T>>();    // one axis at a time
   const T* u = (const T*)in;
-  const auto* ep = (const EnvParams<T>*)ctx->env_params_dev;
+  const auto* ep = ctx->env_params_dev.as<const EnvParams<T>>();
   const ClosureSpec mu{p.mu.kind, p.mu.flags, p.mu.n}, mob{p.mob.kind, p.mob.flags, p.mob.n};
   const dim3 grid(grid_for(cells), p.batch), blk(256);
   const T ilx = T(1.0 / (p.nx * p.hx)), ily = T(1.0 / (p.ny * p.hy)), ilz = T(1.0 / (p.nz * p.hz));
@@ -903,8 +903,8 @@ int spectral_real_prepare(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
   int rc = ensure_real_plans(ctx);
   if (rc) return rc;
   Spectral& sp = *ctx->spectral;
-  if ((rc = ensure_buffer(ctx, &sp.hbuf, (size_t)sp.half_cells * ctx->prob.batch * 2 * ctx->esize))) return rc;
-  *half = sp.hbuf;
+  if ((rc = ensure_buffer(ctx, sp.hbuf, (size_t)sp.half_cells * ctx->prob.batch * 2 * ctx->esize))) return rc;
+  *half = sp.hbuf.get();
   *half_cells = sp.half_cells;
   return PDEOPT_OK;
 }
@@ -913,7 +913,7 @@ int spectral_real_exec(pdeopt_ctx* ctx, bool forward, void* in, void* out) { ret
 
 int spectral_r2c_state(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
   const int rc = spectral_real_prepare(ctx, half, half_cells);
-  return rc ? rc : real_fft_exec(ctx, true, ctx->Y, *half);
+  return rc ? rc : real_fft_exec(ctx, true, ctx->Y.get(), *half);
 }
 
 int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf) {
@@ -968,17 +968,13 @@ void spectral_destroy(pdeopt_ctx* ctx) {
     if (sp->ax_inv[a]) rocfft_plan_destroy(sp->ax_inv[a]);
   }
   if (sp->ax_info) rocfft_execution_info_destroy(sp->ax_info);
-  if (sp->ax_work) (void)hipFree(sp->ax_work);
   if (sp->r2c) rocfft_plan_destroy(sp->r2c);
   if (sp->c2r) rocfft_plan_destroy(sp->c2r);
   if (sp->rinfo) rocfft_execution_info_destroy(sp->rinfo);
   if (sp->fwd) rocfft_plan_destroy(sp->fwd);
   if (sp->inv) rocfft_plan_destroy(sp->inv);
   if (sp->info) rocfft_execution_info_destroy(sp->info);
-  void* bufs[] = {sp->work, sp->rwork, sp->hbuf, sp->hmult, sp->hmultk, sp->cbuf, sp->cbuf2, sp->cbuf3, sp->mult, sp->dens, sp->partial, sp->scale};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete sp;
+  delete sp;  // the work fields go after the plans that were given them
   ctx->spectral = nullptr;
 }
 

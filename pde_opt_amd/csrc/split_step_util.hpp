@@ -45,7 +45,7 @@ int allow_lds(pdeopt_ctx* ctx, K kernel, size_t bytes) {
 
 // exp(-2 pi i k / n), k < n, in the problem dtype
 template <typename T>
-int upload_table(pdeopt_ctx* ctx, void** dev, int n) {
+int upload_table(pdeopt_ctx* ctx, DeviceBuffer& dev, int n) {
   std::vector<Cx<T>> h((size_t)n);
   for (int k = 0; k < n; ++k) {
     const double a = -2.0 * M_PI * (double)k / (double)n;
@@ -53,7 +53,7 @@ int upload_table(pdeopt_ctx* ctx, void** dev, int n) {
   }
   int rc = ensure_buffer(ctx, dev, h.size() * sizeof(Cx<T>));
   if (rc) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(*dev, h.data(), h.size() * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(dev.get(), h.data(), h.size() * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
 }

@@ -46,13 +46,13 @@ StageArgs<T> make_args(pdeopt_ctx* ctx, const Window& w, double t, const void* i
   s.mu3 = nullptr;
   set_closures<T>(s, ctx, w.lo);
   s.vstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? (int64_t)p.nx * p.ny : 0;
-  s.vx = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
-  s.vy = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
+  s.vx = ctx->aux[PDEOPT_AUX_VX_FACE].dev.as<const T>();
+  s.vy = ctx->aux[PDEOPT_AUX_VY_FACE].dev.as<const T>();
   if (s.vx) s.vx += w.lo * s.vstride;
   if (s.vy) s.vy += w.lo * s.vstride;
-  s.psi = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
-  s.ngp = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
-  s.mask = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
+  s.psi = ctx->aux[PDEOPT_AUX_SBM_PSI].dev.as<const T>();
+  s.ngp = ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev.as<const T>();
+  s.mask = ctx->aux[PDEOPT_AUX_SBM_MASK].dev.as<const T>();
   s.fe = closure_spec(p.fe);
   // (Butler-Volmer at a given voltage: tv[0] is the voltage protocol's v(t), added to the per-environment v)
   if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || p.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM || bv_equation(p.equation)) {
@@ -99,10 +99,10 @@ int launch_generic(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
     const int nz = s.g.nz;
     dim3 g3((nz + 63) / 64, (p.ny + 3) / 4, (unsigned)(p.nx * w.n));
     if (g3.y > 65535u || g3.z > 65535u) return fail(ctx, PDEOPT_EINVAL, "grid too large for the 3-D kernels");
-    int rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes);
+    int rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes);
     if (rc) return rc;
     StageArgs<T> s3 = s;
-    s3.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
+    s3.mu3 = ctx->KS.as<const T>() + (int64_t)w.lo * s.g.bstride;
     const int cl = classify_closures(p.mu, p.mob);
     ctx->last_kernel = cl == CL_GENERIC ? "stage_generic<CH-3D>" : std::string("stage_generic<CH-3D,") + closure_class_name(cl) + ">";
     return with_closure_class<CL_GENERIC, CL_POLY, CL_LOGIT>(cl, [&](auto c) -> int {
@@ -155,10 +155,10 @@ int launch_generic(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
       } else {
         // two passes: inner once per cell into the work field, then the psi-weighted flux divergence
         // (1024^2 fp32: 24.8 vs 30.6 us per evaluation; both forms are L2-bound one-thread-per-cell kernels)
-        int rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes);
+        int rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes);
         if (rc) return rc;
         StageArgs<T> s2 = s;
-        s2.mu3 = static_cast<const T*>(ctx->KS) + (int64_t)w.lo * s.g.bstride;
+        s2.mu3 = ctx->KS.as<const T>() + (int64_t)w.lo * s.g.bstride;
         hipLaunchKernelGGL(sbm_inner_kernel<T>, grid, block, 0, w.stream, s2, const_cast<T*>(s2.mu3));
         hipLaunchKernelGGL(sbm_ch_stage_kernel<T>, grid, block, 0, w.stream, s2);
         ctx->last_kernel = "stage_two_pass<CH-SBM>";
@@ -194,11 +194,11 @@ int launch_stage_fourier(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s
     return fail(ctx, PDEOPT_EINVAL, "spectral RHS works on the whole batch");
   int rc;
   if (s.out_mode == OUT_K && s.acc_mode == ACC_NONE && !s.scaled) return rhs_fourier(ctx, in, out);
-  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
-  if ((rc = rhs_fourier(ctx, in, ctx->KS))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
+  if ((rc = rhs_fourier(ctx, in, ctx->KS.get()))) return rc;
   const int64_t total = (int64_t)(ctx->env_elems * ctx->prob.batch);
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(stage_update_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, (const T*)ctx->KS, total,
+  hipLaunchKernelGGL(stage_update_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, s, ctx->KS.as<const T>(), total,
                      (int64_t)ctx->env_elems);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   return PDEOPT_OK;
@@ -243,12 +243,12 @@ int launch_stage(pdeopt_ctx* ctx, const Window& w, double t, const void* in, con
 
 // k = rhs(in) -> kout, and  next = y + sum_{j<n} c[j] K[j] + c[n] k  in the same pass (OUT_K_LC)
 template <typename T>
-int launch_stage_lc(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* kout, void* const* ks, const double* c,
+int launch_stage_lc(pdeopt_ctx* ctx, const Window& w, double t, const void* in, const void* y, void* kout, const DeviceBuffer* ks, const double* c,
                     int n, void* next) {
   return launch_stage_path<T>(ctx, w, t, in, y, kout, nullptr, 0.0, 0.0, OUT_K_LC, ACC_NONE, /*refuse_forced_tiled=*/false, [&](StageArgs<T>& s) {
     const int64_t woff = (int64_t)w.lo * s.g.bstride;
     for (int j = 0; j < n; ++j) {
-      s.lc.k[j] = static_cast<const T*>(ks[j]) + woff;
+      s.lc.k[j] = ks[j].as<const T>() + woff;
       s.lc.c[j] = T(c[j]);
     }
     s.lc.c[n] = T(c[n]);
@@ -343,21 +343,21 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     ctx->last_groups = 1;
     return with_dtype(ctx, [&](auto t) { return launch_small<decltype(t)>(ctx, all, integrator, dt, n); });
   }
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
   // Euler: two substeps per launch through the stage-pair kernels where they exist
   //   PAIR_12 with aA = bA = bB = dt:  w = y + dt f(y),  ACC = y + dt f(y) + dt f(w) = two Euler steps
   const bool euler2 = integrator == PDEOPT_INT_EULER && ctx->opt_kernel_path != 1 &&
                       ctx->prob.derivs == PDEOPT_DERIVS_FD && n >= 2 &&
                       fused_supported_dt(ctx);
   if (integrator == PDEOPT_INT_RK4 || euler2) {
-    if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
-    if (integrator == PDEOPT_INT_RK4 && (rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
+    if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
+    if (integrator == PDEOPT_INT_RK4 && (rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
   } else if (integrator != PDEOPT_INT_EULER) {
     return fail(ctx, PDEOPT_EINVAL, "integrator %d is not an explicit fixed-step integrator", integrator);
   }
   // work field of the two-pass 3-D right-hand side: allocated here, never inside a stream capture
   if ((ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D || bv_equation(ctx->prob.equation)) &&
-      (rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes)))
+      (rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes)))
     return rc;
   // Environments are independent, so the substep loop may run group by group: a group whose
   // working set (4 fields x group x nx x ny) fits the 256 MiB Infinity Cache keeps every stage's
@@ -411,8 +411,8 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
   // writes the other buffer; the per-stage RK4 updates y in place.  Every group performs the same launches, so which
   // buffer holds the state before substep s depends on s alone: `base` is where the buffers were as the ctx has them.
   const bool rotates = integrator == PDEOPT_INT_EULER || quad || chquad || fused;
-  void* const Y0 = ctx->Y;
-  void* const TA0 = ctx->TA;
+  void* const Y0 = ctx->Y.get();
+  void* const TA0 = ctx->TA.get();
   auto rotations = [&](int64_t s, int64_t base) -> int64_t { return !rotates ? 0 : euler2 ? (s - base + 1) / 2 : s - base; };
   const HaloIo none{};
 
@@ -425,7 +425,7 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     if (euler2 && s + 1 < n) {
       // result into TA, TB takes the kernel's unused y + dt k2 output
       took = 2;
-      return launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB, TA, dt, dt, dt, dt);
+      return launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB.get(), TA, dt, dt, dt, dt);
     }
     if (integrator == PDEOPT_INT_EULER) return launch_stage(ctx, w, ts, Y, Y, TA, nullptr, dt, 0.0, OUT_Y_PLUS_AK, ACC_NONE);
     if (quad) return launch_ac_quad(ctx, w, Y, TA, dt);
@@ -433,18 +433,18 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     int r;
     if (fused) {
       // stages 1+2 and 3+4 as two temporally fused launches (7 words/cell instead of 16)
-      r = launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB, ctx->ACC, dt / 2, dt / 6, dt / 2, dt / 3);
-      if (!r) r = launch_pair_dt(ctx, w, none, PAIR_34, ctx->TB, Y, ctx->ACC, TA, nullptr, dt, dt / 3, 0.0, dt / 6);
+      r = launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 6, dt / 2, dt / 3);
+      if (!r) r = launch_pair_dt(ctx, w, none, PAIR_34, ctx->TB.get(), Y, ctx->ACC.get(), TA, nullptr, dt, dt / 3, 0.0, dt / 6);
       return r;
     }
     // stage 1: k1 = f(y);        TA = y + dt/2 k1;  ACC = y + dt/6 k1
-    r = launch_stage(ctx, w, ts, Y, Y, TA, ctx->ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
+    r = launch_stage(ctx, w, ts, Y, Y, TA, ctx->ACC.get(), dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
     // stage 2: k2 = f(TA);       TB = y + dt/2 k2;  ACC += dt/3 k2
-    if (!r) r = launch_stage(ctx, w, ts + dt / 2, TA, Y, ctx->TB, ctx->ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    if (!r) r = launch_stage(ctx, w, ts + dt / 2, TA, Y, ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
     // stage 3: k3 = f(TB);       TA = y + dt k3;    ACC += dt/3 k3
-    if (!r) r = launch_stage(ctx, w, ts + dt / 2, ctx->TB, Y, TA, ctx->ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    if (!r) r = launch_stage(ctx, w, ts + dt / 2, ctx->TB.get(), Y, TA, ctx->ACC.get(), dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
     // stage 4: k4 = f(TA);       y  = ACC + dt/6 k4   (in place: y is only touched pointwise)
-    if (!r) r = launch_stage(ctx, w, ts + dt, TA, Y, Y, ctx->ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
+    if (!r) r = launch_stage(ctx, w, ts + dt, TA, Y, Y, ctx->ACC.get(), 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
     return r;
   };
 
@@ -462,9 +462,9 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     key.integrator = integrator;
     key.fused = quad ? 100 : chquad ? 101 : (euler2 ? 50 : (fused ? (int)(1 + ctx->opt_fuse_stages) : 0));
     key.dt = dt;
-    key.Y = ctx->Y; key.TA = ctx->TA; key.TB = ctx->TB; key.ACC = ctx->ACC; key.KS = ctx->KS;
-    key.ep = ctx->env_params_dev;
-    key.vx = ctx->aux[PDEOPT_AUX_VX_FACE].dev; key.vy = ctx->aux[PDEOPT_AUX_VY_FACE].dev;
+    key.Y = ctx->Y.get(); key.TA = ctx->TA.get(); key.TB = ctx->TB.get(); key.ACC = ctx->ACC.get(); key.KS = ctx->KS.get();
+    key.ep = ctx->env_params_dev.get();
+    key.vx = ctx->aux[PDEOPT_AUX_VX_FACE].dev.get(); key.vy = ctx->aux[PDEOPT_AUX_VY_FACE].dev.get();
     key.kernel_path = ctx->opt_kernel_path; key.tile_rows = ctx->opt_tile_rows; key.ablate = ctx->opt_debug_ablate;
     key.structure = graph_structure(ctx->prob);
     if (!ctx->graph_exec || memcmp(&key, &ctx->graph_key, sizeof(key)) != 0) {
@@ -546,9 +546,9 @@ static int rk4_phase_io(pdeopt_ctx* ctx, int phase, double dt, int part, HaloIo 
   if (ctx->prob.equation == PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "no explicit RHS for the GPE");
   if (part < 0 || part > 2) return fail(ctx, PDEOPT_EINVAL, "part %d outside 0..2", part);
   int rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
   int fields[4], n = 0;
   rk4_phase_plan(ctx, fields, &n);
   if (phase < 0 || phase >= n) return fail(ctx, PDEOPT_EINVAL, "phase %d outside 0..%d", phase, n - 1);
@@ -559,7 +559,7 @@ static int rk4_phase_io(pdeopt_ctx* ctx, int phase, double dt, int part, HaloIo 
   if (ctx->halo == 8 && part != 0)
     return fail(ctx, PDEOPT_EINVAL, "interior / edge launches belong to the halo-4 layout (two exchanges per substep)");
   if (n == 1) {  // the whole substep in one pass: y (+ halo) -> y'
-    rc = launch_ch_quad(ctx, w, io, ctx->Y, ctx->TA, dt);
+    rc = launch_ch_quad(ctx, w, io, ctx->Y.get(), ctx->TA.get(), dt);
     std::swap(ctx->Y, ctx->TA);
     return rc;
   }
@@ -567,9 +567,9 @@ static int rk4_phase_io(pdeopt_ctx* ctx, int phase, double dt, int part, HaloIo 
     io.part = part;
     if (phase == 0) {
       io.ext = ctx->halo == 8 ? 4 : 0;
-      return launch_pair_dt(ctx, w, io, PAIR_12, ctx->Y, nullptr, nullptr, ctx->TB, ctx->ACC, dt / 2, dt / 6, dt / 2, dt / 3);
+      return launch_pair_dt(ctx, w, io, PAIR_12, ctx->Y.get(), nullptr, nullptr, ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 6, dt / 2, dt / 3);
     }
-    rc = launch_pair_dt(ctx, w, io, PAIR_34, ctx->TB, ctx->Y, ctx->ACC, ctx->TA, nullptr, dt, dt / 3, 0.0, dt / 6);
+    rc = launch_pair_dt(ctx, w, io, PAIR_34, ctx->TB.get(), ctx->Y.get(), ctx->ACC.get(), ctx->TA.get(), nullptr, dt, dt / 3, 0.0, dt / 6);
     if (part != 1) std::swap(ctx->Y, ctx->TA);
     return rc;
   }
@@ -577,10 +577,10 @@ static int rk4_phase_io(pdeopt_ctx* ctx, int phase, double dt, int part, HaloIo 
     return fail(ctx, PDEOPT_EINVAL, "interior / edge launches exist for the fused stage pairs only (this problem runs one kernel per stage)");
   // a phase call carries no time: the decomposed driver runs autonomous equations, t = 0 for any time-dependent term
   switch (phase) {
-    case 0: return launch_stage(ctx, w, 0.0, ctx->Y, ctx->Y, ctx->TA, ctx->ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
-    case 1: return launch_stage(ctx, w, 0.0, ctx->TA, ctx->Y, ctx->TB, ctx->ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    case 2: return launch_stage(ctx, w, 0.0, ctx->TB, ctx->Y, ctx->TA, ctx->ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    default: return launch_stage(ctx, w, 0.0, ctx->TA, ctx->Y, ctx->Y, ctx->ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
+    case 0: return launch_stage(ctx, w, 0.0, ctx->Y.get(), ctx->Y.get(), ctx->TA.get(), ctx->ACC.get(), dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
+    case 1: return launch_stage(ctx, w, 0.0, ctx->TA.get(), ctx->Y.get(), ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    case 2: return launch_stage(ctx, w, 0.0, ctx->TB.get(), ctx->Y.get(), ctx->TA.get(), ctx->ACC.get(), dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
+    default: return launch_stage(ctx, w, 0.0, ctx->TA.get(), ctx->Y.get(), ctx->Y.get(), ctx->ACC.get(), 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
   }
 }
 
@@ -601,9 +601,9 @@ int rk4_loopback_advance(pdeopt_ctx* ctx, double dt, int64_t n) {
     if ((rc = halo_pack(ctx, 0, nullptr))) return rc;
     // the strip written by substep s (fused pack) is read by substep s + 1 (fused unpack): two buffers
     const size_t bytes = halo_strip_elems(ctx) * ctx->esize;
-    if ((rc = grow_device_buffer(ctx, &ctx->halo_scratch2, &ctx->halo_scratch2_bytes, bytes, /*sync_first=*/true))) return rc;
-    void* cur = ctx->halo_scratch;
-    void* nxt = ctx->halo_scratch2;
+    if ((rc = grow_device_buffer(ctx, ctx->halo_scratch2, bytes, /*sync_first=*/true))) return rc;
+    void* cur = ctx->halo_scratch.get();
+    void* nxt = ctx->halo_scratch2.get();
     for (int64_t s = 0; s < n && !rc; ++s) {
       rc = rk4_substep_h8(ctx, dt, s + 1 < n ? nxt : nullptr, cur, nbr);
       std::swap(cur, nxt);
@@ -702,50 +702,50 @@ __global__ __launch_bounds__(256) void tsit5_err_kernel(const LinComb<T> a, cons
 template <typename T>
 int tsit5_trial_t(pdeopt_ctx* ctx, double t, double dt, double rtol, double atol, double* err) {
   int rc;
-  for (auto& k : ctx->K)
-    if ((rc = ensure_buffer(ctx, &k, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
+  for (DeviceBuffer& k : ctx->K)
+    if ((rc = ensure_buffer(ctx, k, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
   const int64_t total = (int64_t)(ctx->env_elems * ctx->prob.batch);
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
   const Window w = whole_batch(ctx);
-  if (!ctx->tsit5_fsal_valid && (rc = launch_stage(ctx, w, t, ctx->Y, ctx->Y, ctx->K[0], nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
+  if (!ctx->tsit5_fsal_valid && (rc = launch_stage(ctx, w, t, ctx->Y.get(), ctx->Y.get(), ctx->K[0].get(), nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
   // stage 2 input from k1 alone (k1 is the previous step's k7 under FSAL, so nothing could form it earlier)
   {
     LinComb<T> lc{};
-    lc.y = (const T*)ctx->Y;
+    lc.y = ctx->Y.as<const T>();
     lc.n = 1;
-    lc.k[0] = (const T*)ctx->K[0];
+    lc.k[0] = ctx->K[0].as<const T>();
     lc.c[0] = T(dt * kTsA[0][0]);
-    lc.out = (T*)ctx->TA;
+    lc.out = ctx->TA.as<T>();
     hipLaunchKernelGGL(lincomb_kernel<T>, dim3(blocks), dim3(256), 0, ctx->stream, lc, total);
   }
   // stages 2..6: k_s = f(in_s) and, in the same pass, in_{s+1} = y + dt sum_j a_{s+1,j} k_j  (ping-pong
   // TA / TB; in_7 -- the 5th-order solution -- lands in TB).  Stage 7 evaluates k7 = f(in_7) for the
   // error estimate and the next step's FSAL.  8 launches per step instead of 13.
   for (int s = 1; s <= 5; ++s) {
-    void* in_s = (s & 1) ? ctx->TA : ctx->TB;
-    void* in_next = (s & 1) ? ctx->TB : ctx->TA;
+    void* in_s = (s & 1) ? ctx->TA.get() : ctx->TB.get();
+    void* in_next = (s & 1) ? ctx->TB.get() : ctx->TA.get();
     double c[kMaxLc + 1];
     for (int j = 0; j <= s; ++j) c[j] = dt * kTsA[s][j];
-    if ((rc = launch_stage_lc<T>(ctx, w, t + kTsC[s - 1] * dt, in_s, ctx->Y, ctx->K[s], ctx->K, c, s, in_next))) return rc;
+    if ((rc = launch_stage_lc<T>(ctx, w, t + kTsC[s - 1] * dt, in_s, ctx->Y.get(), ctx->K[s].get(), ctx->K, c, s, in_next))) return rc;
   }
-  if ((rc = launch_stage(ctx, w, t + kTsC[5] * dt, ctx->TB, ctx->TB, ctx->K[6], nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
+  if ((rc = launch_stage(ctx, w, t + kTsC[5] * dt, ctx->TB.get(), ctx->TB.get(), ctx->K[6].get(), nullptr, 0, 0, OUT_K, ACC_NONE))) return rc;
   ctx->tsit5_pending = true;
   if (err) {
     double* part = nullptr;
     const size_t need = sizeof(double) * kErrBlocks * ctx->prob.batch;
-    if ((rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false))) return rc;
-    part = ctx->red_dev;
+    if ((rc = grow_device_buffer(ctx, ctx->red_dev, need, /*sync_first=*/false))) return rc;
+    part = ctx->red_dev.as<double>();
     LinComb<T> lc{};
-    lc.y = (const T*)ctx->Y;
+    lc.y = ctx->Y.as<const T>();
     lc.n = 7;
     for (int j = 0; j < 7; ++j) {
-      lc.k[j] = (const T*)ctx->K[j];
+      lc.k[j] = ctx->K[j].as<const T>();
       lc.c[j] = T(dt * kTsE[j]);
     }
     hipLaunchKernelGGL(tsit5_err_kernel<T>, dim3(kErrBlocks, ctx->prob.batch), dim3(256), 0,
-                       ctx->stream, lc, (const T*)ctx->TB, (T)rtol, (T)atol,
+                       ctx->stream, lc, ctx->TB.as<const T>(), (T)rtol, (T)atol,
                        (int64_t)ctx->env_elems, part);
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     std::vector<double> h((size_t)kErrBlocks * ctx->prob.batch);
@@ -773,10 +773,10 @@ static int tsit5_dense_t(pdeopt_ctx* ctx, double theta, double dt, int env_first
   tsit5_dense_weights(theta, b);
   const int64_t o = (int64_t)env_first * (int64_t)ctx->env_elems;
   LinComb<T> lc{};
-  lc.y = (const T*)ctx->Y + o;
+  lc.y = ctx->Y.as<const T>() + o;
   lc.n = 7;
   for (int j = 0; j < 7; ++j) {
-    lc.k[j] = (const T*)ctx->K[j] + o;
+    lc.k[j] = ctx->K[j].as<const T>() + o;
     lc.c[j] = T(dt * b[j]);
   }
   lc.out = (T*)dev_out + o;
@@ -795,13 +795,13 @@ int tsit5_dense(pdeopt_ctx* ctx, double theta, double dt, int env_first, int env
 // FSAL slope of environment b *= ratio[b] (its step size changed between two per-environment trials)
 int tsit5_rescale_fsal(pdeopt_ctx* ctx, const double* ratio) {
   const size_t need = sizeof(double) * (size_t)ctx->prob.batch;
-  if (const int rc = grow_device_buffer(ctx, (void**)&ctx->red_dev, &ctx->red_cap, need, /*sync_first=*/false)) return rc;
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->red_dev, ratio, need, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = grow_device_buffer(ctx, ctx->red_dev, need, /*sync_first=*/false)) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->red_dev.as<double>(), ratio, need, hipMemcpyHostToDevice, ctx->stream));
   const int64_t ee = (int64_t)ctx->env_elems;
   const dim3 grid((unsigned)std::min<int64_t>((ee + 255) / 256, 1024), ctx->prob.batch);
   with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(env_scale_kernel<T>, grid, dim3(256), 0, ctx->stream, (T*)ctx->K[0], (const double*)ctx->red_dev, ee);
+    hipLaunchKernelGGL(env_scale_kernel<T>, grid, dim3(256), 0, ctx->stream, ctx->K[0].as<T>(), ctx->red_dev.as<const double>(), ee);
   });
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // `ratio` is the caller's again
@@ -819,8 +819,8 @@ int tsit5_commit_env(pdeopt_ctx* ctx, const uint8_t* accept) {
   for (int b = 0; b < batch; ++b) {
     if (accept[b]) continue;
     // rejected: the old state / slope (now in TB / K[6]) go back
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync((char*)ctx->Y + eb * b, (const char*)ctx->TB + eb * b, eb, hipMemcpyDeviceToDevice, ctx->stream));
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync((char*)ctx->K[0] + eb * b, (const char*)ctx->K[6] + eb * b, eb, hipMemcpyDeviceToDevice, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->Y.as<char>() + eb * b, ctx->TB.as<const char>() + eb * b, eb, hipMemcpyDeviceToDevice, ctx->stream));
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->K[0].as<char>() + eb * b, ctx->K[6].as<const char>() + eb * b, eb, hipMemcpyDeviceToDevice, ctx->stream));
   }
   ctx->tsit5_fsal_valid = true;
   return PDEOPT_OK;

@@ -1190,9 +1190,9 @@ CoopArgs<T> coop_common_args(const pdeopt_ctx* ctx, const CoopPlan& pl, const Co
   s.rows = pl.rows; s.pitch = pl.pitch; s.red_off = pl.red_off;
   s.xs = sh.xs; s.wpx = sh.wpx;
   if (eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM) {
-    s.s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_PSI].dev);
-    s.s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev);
-    s.s2 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_SBM_MASK].dev);
+    s.s0 = ctx->aux[PDEOPT_AUX_SBM_PSI].dev.as<const T>();
+    s.s1 = ctx->aux[PDEOPT_AUX_SBM_NORM_GRAD].dev.as<const T>();
+    s.s2 = ctx->aux[PDEOPT_AUX_SBM_MASK].dev.as<const T>();
     const bool poly_const = ctx->time_poly_valid && ctx->time_theta[1] == 0.0 && ctx->time_theta[2] == 0.0 && ctx->time_theta[3] == 0.0 &&
                             ctx->time_flux[1] == 0.0 && ctx->time_flux[2] == 0.0 && ctx->time_flux[3] == 0.0;
     if (fold_const_poly && poly_const) {
@@ -1208,8 +1208,8 @@ CoopArgs<T> coop_common_args(const pdeopt_ctx* ctx, const CoopPlan& pl, const Co
       for (int i = 0; i < 3; ++i) s.tw[i] = ctx->time_const[i];
     }
   } else if (eq == PDEOPT_EQ_ADVECTION_DIFFUSION) {
-    s.s0 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VX_FACE].dev);
-    s.s1 = static_cast<const T*>(ctx->aux[PDEOPT_AUX_VY_FACE].dev);
+    s.s0 = ctx->aux[PDEOPT_AUX_VX_FACE].dev.as<const T>();
+    s.s1 = ctx->aux[PDEOPT_AUX_VY_FACE].dev.as<const T>();
     s.sstride = ctx->aux[PDEOPT_AUX_VX_FACE].per_env ? (int64_t)p.nx * p.ny : 0;
   }
   return s;
@@ -1232,7 +1232,7 @@ int coop_run(pdeopt_ctx* ctx, const CoopKernel& kern, const CoopPlan& pl, const 
   for (int e0 = 0; e0 < batch; e0 += sh.envs_per_launch) {
     CoopArgs<T> c = s;
     c.nenv = std::min(sh.envs_per_launch, batch - e0);
-    c.y = static_cast<T*>(ctx->Y) + (int64_t)e0 * s.bstride;
+    c.y = ctx->Y.as<T>() + (int64_t)e0 * s.bstride;
     c.ep = env_params<T>(ctx, e0);
     c.s0 = s.s0 ? s.s0 + (int64_t)e0 * s.sstride : nullptr;
     c.s1 = s.s1 ? s.s1 + (int64_t)e0 * s.sstride : nullptr;
@@ -1267,10 +1267,10 @@ int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pd
     return fail(ctx, PDEOPT_EINVAL, "%d workgroups per environment exceed the device's %d compute units", nwg, ctx->num_cus);
   int rc;
   // exchange buffers: the integrators' work fields
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->ACC, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->KS, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
 
   CoopArgs<T> s = coop_common_args<T>(ctx, pl, sh, /*fold_const_poly=*/true);
   s.t0 = t0; s.t1 = t1; s.dt0 = dt0;
@@ -1285,8 +1285,8 @@ int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pd
   const size_t bar_bytes = ((size_t)(2 * batch + 1) * sizeof(unsigned) + 255) / 256 * 256;
   const size_t part_bytes = ((size_t)2 * batch * nwg * 2 * sizeof(double) + 255) / 256 * 256;  // [parity][env][workgroup][2 words]
   const size_t out_bytes = (size_t)n_save * batch * cells * sizeof(T);
-  if ((rc = ensure_adaptive_block(ctx, ts_bytes + st_bytes + bar_bytes + part_bytes + out_bytes + 256))) return rc;
-  char* const blk = static_cast<char*>(ctx->adaptive_blk);
+  if ((rc = grow_device_buffer(ctx, ctx->adaptive_blk, ts_bytes + st_bytes + bar_bytes + part_bytes + out_bytes + 256, /*sync_first=*/true))) return rc;
+  char* const blk = ctx->adaptive_blk.as<char>();
   s.save_ts = reinterpret_cast<const double*>(blk);
   pdeopt_tsit5_stats* const stats_dev = reinterpret_cast<pdeopt_tsit5_stats*>(blk + ts_bytes);
   unsigned* const bar_dev = reinterpret_cast<unsigned*>(blk + ts_bytes + st_bytes);
@@ -1307,8 +1307,8 @@ int coop_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const pd
       [&](CoopArgs<T>& c, int e0) {
         c.save_out = out_dev + (int64_t)e0 * cells;
         c.stats = stats_dev + e0;
-        c.xy[0] = static_cast<T*>(ctx->TA) + (int64_t)e0 * cells; c.xy[1] = static_cast<T*>(ctx->TB) + (int64_t)e0 * cells;
-        c.xk[0] = static_cast<T*>(ctx->ACC) + (int64_t)e0 * cells; c.xk[1] = static_cast<T*>(ctx->KS) + (int64_t)e0 * cells;
+        c.xy[0] = ctx->TA.as<T>() + (int64_t)e0 * cells; c.xy[1] = ctx->TB.as<T>() + (int64_t)e0 * cells;
+        c.xk[0] = ctx->ACC.as<T>() + (int64_t)e0 * cells; c.xk[1] = ctx->KS.as<T>() + (int64_t)e0 * cells;
         c.part = part_dev + (size_t)2 * e0 * nwg * 2;
         c.bar = bar_dev + 2 * e0;
       },
@@ -1363,14 +1363,14 @@ int coop_fixed_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, in
     return fail(ctx, PDEOPT_EINVAL, "the multi-workgroup fixed-step kernel does not cover this problem");
   const int nwg = pl.px * pl.py;
   int rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, &ctx->TB, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
   CoopArgs<T> s = coop_common_args<T>(ctx, pl, sh, /*fold_const_poly=*/false);
   s.t0 = t0; s.dt = dt; s.n_sub = n; s.fixed_rk4 = rk4 ? 1 : 0;
   // device block: the published round numbers of every workgroup + the abort flag
   const size_t tag_bytes = ((size_t)batch * nwg + 1) * sizeof(unsigned);
-  if ((rc = ensure_adaptive_block(ctx, tag_bytes + 256))) return rc;
-  unsigned* const tags_dev = static_cast<unsigned*>(ctx->adaptive_blk);
+  if ((rc = grow_device_buffer(ctx, ctx->adaptive_blk, tag_bytes + 256, /*sync_first=*/true))) return rc;
+  unsigned* const tags_dev = ctx->adaptive_blk.as<unsigned>();
   s.abort_flag = tags_dev + (size_t)batch * nwg;
   PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(tags_dev, 0, tag_bytes, ctx->stream));
 
@@ -1378,7 +1378,7 @@ int coop_fixed_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, in
   return coop_run<T>(
       ctx, kern, pl, sh, s, "fixed-step advance",
       [&](CoopArgs<T>& c, int e0) {
-        c.xy[0] = static_cast<T*>(ctx->TA) + (int64_t)e0 * cells; c.xy[1] = static_cast<T*>(ctx->TB) + (int64_t)e0 * cells;
+        c.xy[0] = ctx->TA.as<T>() + (int64_t)e0 * cells; c.xy[1] = ctx->TB.as<T>() + (int64_t)e0 * cells;
         c.tags = tags_dev + (size_t)e0 * nwg;
       },
       []() -> int { return PDEOPT_OK; });

@@ -341,7 +341,7 @@ int launch_small(pdeopt_ctx* ctx, const Window& w, int integrator, double dt, in
   const pdeopt_problem& p = ctx->prob;
   SmallArgs<T> s{};
   const Geo g = make_geo(ctx);
-  s.y = static_cast<T*>(ctx->Y) + (int64_t)w.lo * g.bstride;
+  s.y = ctx->Y.as<T>() + (int64_t)w.lo * g.bstride;
   const SmallDims d = small_dims(p);
   s.nx = d.nx;
   s.ny = d.ny;

@@ -316,7 +316,7 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   const int64_t cells = (int64_t)p.nx * p.ny;
   SmallTsit5Args<T> s{};
   const Geo g = make_geo(ctx);
-  s.y = static_cast<T*>(ctx->Y);
+  s.y = ctx->Y.as<T>();
   const SmallDims d = small_dims(p);
   s.nx = d.nx;
   s.ny = d.ny;
@@ -334,8 +334,8 @@ int small_tsit5_solve(pdeopt_ctx* ctx, double t0, double t1, double dt0, const p
   const size_t st_bytes = ((size_t)batch * sizeof(pdeopt_tsit5_stats) + 255) / 256 * 256;
   const size_t out_bytes = (size_t)n_save * batch * cells * sizeof(T);
   int rc;
-  if ((rc = ensure_adaptive_block(ctx, ts_bytes + st_bytes + out_bytes + 256))) return rc;
-  char* const blk = static_cast<char*>(ctx->adaptive_blk);
+  if ((rc = grow_device_buffer(ctx, ctx->adaptive_blk, ts_bytes + st_bytes + out_bytes + 256, /*sync_first=*/true))) return rc;
+  char* const blk = ctx->adaptive_blk.as<char>();
   s.save_ts = reinterpret_cast<const double*>(blk);
   s.stats = reinterpret_cast<pdeopt_tsit5_stats*>(blk + ts_bytes);
   s.save_out = reinterpret_cast<T*>(blk + ts_bytes + st_bytes);

@@ -29,17 +29,16 @@
 namespace pdeopt {
 
 struct StrangFused {
-  void* tw_x = nullptr;  // twiddle tables exp(-2 pi i n / N) in the problem dtype
-  void* tw_y = nullptr;
-  void* mult = nullptr;  // E / (nx ny), complex, laid out by col_mult_index()
-  void* dens = nullptr;  // |psi0|^2, real [batch][nx][ny]
-  double* partial = nullptr;
+  DeviceBuffer tw_x;  // twiddle tables exp(-2 pi i n / N) in the problem dtype
+  DeviceBuffer tw_y;
+  DeviceBuffer mult;  // E / (nx ny), complex, laid out by col_mult_index()
+  DeviceBuffer dens;  // |psi0|^2, real [batch][nx][ny]
+  DeviceBuffer partial;  // doubles
   double key_dt = NAN, key_tr = NAN, key_ti = NAN;
   bool mult_valid = false;
   // IMEX on the same transforms
-  void* cwork = nullptr;      // complex work field [batch][nx][ny]
-  size_t cwork_bytes = 0;
-  void* imex_mult = nullptr;  // symmetrised 1 / ((1 + A dt symbol) nx ny); with per-environment scales A dt symbol
+  DeviceBuffer cwork;      // complex work field [batch][nx][ny]; grow-only
+  DeviceBuffer imex_mult;  // symmetrised 1 / ((1 + A dt symbol) nx ny); with per-environment scales A dt symbol
   bool imex_per_env = false;  // which of the two imex_mult holds
   double imex_dt = NAN, imex_A = NAN;
   bool imex_valid = false;
@@ -364,10 +363,10 @@ int launch_row(pdeopt_ctx* ctx, const Window& w, StrangFused& sf, double tr, dou
   // environment window [w.lo, w.lo + w.n): all pointers pre-offset, the kernel sees w.n environments
   const int64_t cells = (int64_t)p.nx * p.ny, w0 = w.lo;
   const int blocks = (int)((int64_t)w.n * p.nx / F);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (Cx<T>*)ctx->Y + w0 * cells,
-                     (T*)sf.dens + w0 * cells, pot.dev ? (const T*)pot.dev + (pot.per_env ? w0 * cells : 0) : nullptr,
-                     pot.per_env ? cells : (int64_t)0, (const EnvParams<T>*)ctx->env_params_dev + w0,
-                     (const Cx<T>*)sf.tw_y, (T)tr, (T)ti, p.nx, sf.partial + w0 * (p.nx / F),
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, ctx->Y.as<Cx<T>>() + w0 * cells,
+                     sf.dens.as<T>() + w0 * cells, pot.dev ? pot.dev.as<const T>() + (pot.per_env ? w0 * cells : 0) : nullptr,
+                     pot.per_env ? cells : (int64_t)0, ctx->env_params_dev.as<const EnvParams<T>>() + w0,
+                     sf.tw_y.as<const Cx<T>>(), (T)tr, (T)ti, p.nx, sf.partial.as<double>() + w0 * (p.nx / F),
                      MODE == ROW_MID ? make_spot_args<T>(ctx, w.lo, t) : SpotArgs<T>{});
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -386,8 +385,8 @@ int launch_col(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
     auto kern = strang_col32_kernel<T, C, SCALED, false>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * 32), lds, w.stream, (Cx<T>*)ctx->Y + w0 * cells,
-                       (const Cx<T>*)sf.mult, (const Cx<T>*)sf.tw_x, p.ny, (const double*)sf.partial + w0 * bpe, bpe,
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * 32), lds, w.stream, ctx->Y.as<Cx<T>>() + w0 * cells,
+                       sf.mult.as<const Cx<T>>(), sf.tw_x.as<const Cx<T>>(), p.ny, sf.partial.as<const double>() + w0 * bpe, bpe,
                        ctx->strang_dx * ctx->strang_dx, (const EnvParams<T>*)nullptr, T(0));
   } else {
     const size_t lds = (size_t)C * fft_lds_pitch<N>() * sizeof(Cx<T>);
@@ -395,8 +394,8 @@ int launch_col(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(p.ny / C, w.n), dim3(C * N / PTS), lds, w.stream,
-                       (Cx<T>*)ctx->Y + w0 * cells, (const Cx<T>*)sf.mult, (const Cx<T>*)sf.tw_x, p.ny,
-                       (const double*)sf.partial + w0 * bpe, bpe, ctx->strang_dx * ctx->strang_dx,
+                       ctx->Y.as<Cx<T>>() + w0 * cells, sf.mult.as<const Cx<T>>(), sf.tw_x.as<const Cx<T>>(), p.ny,
+                       sf.partial.as<const double>() + w0 * bpe, bpe, ctx->strang_dx * ctx->strang_dx,
                        (const EnvParams<T>*)nullptr, T(0));
   }
   ctx->n_stage_launches++;
@@ -436,10 +435,10 @@ int strang_fused_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   const int64_t cells = (int64_t)p.nx * p.ny;
   int rc;
   if (!sf.tw_x) {
-    if ((rc = upload_table<T>(ctx, &sf.tw_x, p.nx))) return rc;
-    if ((rc = upload_table<T>(ctx, &sf.tw_y, p.ny))) return rc;
-    if ((rc = ensure_buffer(ctx, &sf.dens, (size_t)cells * p.batch * sizeof(T)))) return rc;
-    if ((rc = ensure_buffer(ctx, (void**)&sf.partial, sizeof(double) * (size_t)p.batch * p.nx))) return rc;
+    if ((rc = upload_table<T>(ctx, sf.tw_x, p.nx))) return rc;
+    if ((rc = upload_table<T>(ctx, sf.tw_y, p.ny))) return rc;
+    if ((rc = ensure_buffer(ctx, sf.dens, (size_t)cells * p.batch * sizeof(T)))) return rc;
+    if ((rc = ensure_buffer(ctx, sf.partial, sizeof(double) * (size_t)p.batch * p.nx))) return rc;
   }
   const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
   if (!sf.mult_valid || sf.key_dt != dt || sf.key_tr != ctx->ts_re || sf.key_ti != ctx->ts_im) {
@@ -448,10 +447,10 @@ int strang_fused_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
     std::vector<std::complex<double>> at((size_t)cells);
     if (p.dtype == PDEOPT_F32) {
       std::vector<float> h((size_t)cells * 2);
-      PDEOPT_HIP_CHECK(ctx, hipMemcpy(h.data(), a.dev, (size_t)cells * 8, hipMemcpyDeviceToHost));
+      PDEOPT_HIP_CHECK(ctx, hipMemcpy(h.data(), a.dev.get(), (size_t)cells * 8, hipMemcpyDeviceToHost));
       for (int64_t i = 0; i < cells; ++i) at[i] = {h[2 * i], h[2 * i + 1]};
     } else {
-      PDEOPT_HIP_CHECK(ctx, hipMemcpy(at.data(), a.dev, (size_t)cells * 16, hipMemcpyDeviceToHost));
+      PDEOPT_HIP_CHECK(ctx, hipMemcpy(at.data(), a.dev.get(), (size_t)cells * 16, hipMemcpyDeviceToHost));
     }
     std::vector<Cx<T>> m((size_t)cells);
     const double inv_n = 1.0 / (double)cells;
@@ -459,8 +458,8 @@ int strang_fused_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
       const std::complex<double> e = std::exp(at[i] * 0.5 * tau) * inv_n;
       m[col_mult_index(i / p.ny, i % p.ny, p.nx, p.ny)] = Cx<T>{(T)e.real(), (T)e.imag()};
     }
-    if ((rc = ensure_buffer(ctx, &sf.mult, (size_t)cells * sizeof(Cx<T>)))) return rc;
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sf.mult, m.data(), (size_t)cells * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ensure_buffer(ctx, sf.mult, (size_t)cells * sizeof(Cx<T>)))) return rc;
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sf.mult.get(), m.data(), (size_t)cells * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     sf.mult_valid = true;
     sf.key_dt = dt;
@@ -617,19 +616,19 @@ int imex_rows(pdeopt_ctx* ctx, const Window& w, StrangFused& sf, bool forward, d
   const int npairs = (w.n + pack - 1) / pack;
   const size_t lds = (size_t)F * E::NP * sizeof(typename E::LdsT);
   const int blocks = (int)((int64_t)npairs * p.nx / F);
-  Cx<T>* const cw = (Cx<T>*)sf.cwork + (w0 / pack) * cells;
+  Cx<T>* const cw = sf.cwork.as<Cx<T>>() + (w0 / pack) * cells;
   if (forward) {
     auto kern = imex_row_fwd_reg_kernel<T, N>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (const T*)ctx->TA + w0 * cells, cw,
-                       (const Cx<T>*)sf.tw_y, p.nx, w.n, pack);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, ctx->TA.as<const T>() + w0 * cells, cw,
+                       sf.tw_y.as<const Cx<T>>(), p.nx, w.n, pack);
   } else {
     auto kern = imex_row_inv_reg_kernel<T, N>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (const Cx<T>*)cw, (T*)ctx->Y + w0 * cells,
-                       (const Cx<T>*)sf.tw_y, (T)dt, p.nx, w.n, pack);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, w.stream, (const Cx<T>*)cw, ctx->Y.as<T>() + w0 * cells,
+                       sf.tw_y.as<const Cx<T>>(), (T)dt, p.nx, w.n, pack);
   }
   ctx->n_stage_launches++;
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -643,8 +642,8 @@ int imex_cols(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
   const pdeopt_problem& p = ctx->prob;
   const int pack = ctx->imex_per_env ? 1 : 2;
   const int npairs = (w.n + pack - 1) / pack;
-  Cx<T>* const cw = (Cx<T>*)sf.cwork + (int64_t)(w.lo / pack) * p.nx * p.ny;
-  const EnvParams<T>* const ep = ctx->imex_per_env ? (const EnvParams<T>*)ctx->env_params_dev + w.lo : nullptr;
+  Cx<T>* const cw = sf.cwork.as<Cx<T>>() + (int64_t)(w.lo / pack) * p.nx * p.ny;
+  const EnvParams<T>* const ep = ctx->imex_per_env ? ctx->env_params_dev.as<const EnvParams<T>>() + w.lo : nullptr;
   const T inv_n = (T)(1.0 / ((double)p.nx * p.ny));
   // FFT_x -> * multiplier -> IFFT_x, in place
   if constexpr (col_use32<T, N>()) {
@@ -652,15 +651,15 @@ int imex_cols(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
     auto kern = ep ? strang_col32_kernel<T, C, false, true> : strang_col32_kernel<T, C, false, false>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * 32), lds, w.stream, cw, (const Cx<T>*)sf.imex_mult,
-                       (const Cx<T>*)sf.tw_x, p.ny, (const double*)nullptr, 0, 1.0, ep, inv_n);
+    hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * 32), lds, w.stream, cw, sf.imex_mult.as<const Cx<T>>(),
+                       sf.tw_x.as<const Cx<T>>(), p.ny, (const double*)nullptr, 0, 1.0, ep, inv_n);
   } else {
     const size_t lds = (size_t)C * fft_lds_pitch<N>() * sizeof(Cx<T>);
     auto kern = ep ? strang_col_reg_kernel<T, N, C, PTS, false, true> : strang_col_reg_kernel<T, N, C, PTS, false, false>;
     int rc = allow_lds(ctx, kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(p.ny / C, npairs), dim3(C * N / PTS), lds, w.stream, cw,
-                       (const Cx<T>*)sf.imex_mult, (const Cx<T>*)sf.tw_x, p.ny, (const double*)nullptr, 0, 1.0, ep,
+                       sf.imex_mult.as<const Cx<T>>(), sf.tw_x.as<const Cx<T>>(), p.ny, (const double*)nullptr, 0, 1.0, ep,
                        inv_n);
   }
   ctx->n_stage_launches++;
@@ -677,23 +676,23 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
   const int64_t cells = (int64_t)p.nx * p.ny;
   int rc;
   if (!sf.tw_x) {
-    if ((rc = upload_table<T>(ctx, &sf.tw_x, p.nx))) return rc;
-    if ((rc = upload_table<T>(ctx, &sf.tw_y, p.ny))) return rc;
+    if ((rc = upload_table<T>(ctx, sf.tw_x, p.nx))) return rc;
+    if ((rc = upload_table<T>(ctx, sf.tw_y, p.ny))) return rc;
   }
-  if ((rc = ensure_buffer(ctx, &ctx->TA, ctx->total_bytes))) return rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
   // one complex field per PAIR of environments, or per environment when their implicit operators differ
   const size_t cwork_need = (size_t)cells * (ctx->imex_per_env ? (size_t)p.batch : (size_t)((p.batch + 1) / 2)) * sizeof(Cx<T>);
-  if ((rc = grow_device_buffer(ctx, &sf.cwork, &sf.cwork_bytes, cwork_need, /*sync_first=*/true))) return rc;
+  if ((rc = grow_device_buffer(ctx, sf.cwork, cwork_need, /*sync_first=*/true))) return rc;
   if (!sf.imex_valid || sf.imex_dt != dt || sf.imex_A != ctx->imex_A || sf.imex_per_env != ctx->imex_per_env) {
     // 1 / ((1 + A dt fourier_symbol) nx ny): solvers.py:62-63 with the 1/N of the inverse folded in
     const AuxField& a = ctx->aux[PDEOPT_AUX_IMEX_SYMBOL];
     std::vector<std::complex<double>> sym((size_t)cells);
     if (p.dtype == PDEOPT_F32) {
       std::vector<float> h((size_t)cells * 2);
-      PDEOPT_HIP_CHECK(ctx, hipMemcpy(h.data(), a.dev, (size_t)cells * 8, hipMemcpyDeviceToHost));
+      PDEOPT_HIP_CHECK(ctx, hipMemcpy(h.data(), a.dev.get(), (size_t)cells * 8, hipMemcpyDeviceToHost));
       for (int64_t i = 0; i < cells; ++i) sym[i] = {h[2 * i], h[2 * i + 1]};
     } else {
-      PDEOPT_HIP_CHECK(ctx, hipMemcpy(sym.data(), a.dev, (size_t)cells * 16, hipMemcpyDeviceToHost));
+      PDEOPT_HIP_CHECK(ctx, hipMemcpy(sym.data(), a.dev.get(), (size_t)cells * 16, hipMemcpyDeviceToHost));
     }
     // M(k) = 1 / ((1 + A dt symbol(k)) nx ny), then M_h(k) = (M(k) + conj M(-k)) / 2: the transforms carry
     // two real environments per complex field (imex_row_fwd_reg_kernel), which needs the real-to-real form
@@ -715,8 +714,8 @@ int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
         m[col_mult_index(kx, ky, p.nx, p.ny)] = Cx<T>{(T)v.real(), (T)v.imag()};
       }
     }
-    if ((rc = ensure_buffer(ctx, &sf.imex_mult, (size_t)cells * sizeof(Cx<T>)))) return rc;
-    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sf.imex_mult, m.data(), (size_t)cells * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ensure_buffer(ctx, sf.imex_mult, (size_t)cells * sizeof(Cx<T>)))) return rc;
+    PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(sf.imex_mult.get(), m.data(), (size_t)cells * sizeof(Cx<T>), hipMemcpyHostToDevice, ctx->stream));
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     sf.imex_valid = true;
     sf.imex_dt = dt;
@@ -772,7 +771,7 @@ int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   if (side_by_side && group >= 4 && p.batch >= 4 && ctx->opt_group_envs == 0) group = std::max(2, (group / 2 + 1) & ~1);
   rc = run_groups(ctx, group, side_by_side, 0, n, [](const Window&) { return PDEOPT_OK; },
                   [&](const Window& w, int64_t, int&) -> int {
-                    const int r = launch_rhs_slope(ctx, w, ctx->Y, ctx->TA, 0.0);
+                    const int r = launch_rhs_slope(ctx, w, ctx->Y.get(), ctx->TA.get(), 0.0);
                     return r ? r : imex_passes_t<T>(ctx, w, sf, dt);
                   });
   if (rc) return rc;
@@ -827,12 +826,7 @@ void strang_fused_invalidate(pdeopt_ctx* ctx) {
 }
 
 void strang_fused_destroy(pdeopt_ctx* ctx) {
-  StrangFused* sf = ctx->strang_fused;
-  if (!sf) return;
-  void* bufs[] = {sf->tw_x, sf->tw_y, sf->mult, sf->dens, sf->partial, sf->cwork, sf->imex_mult};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete sf;
+  delete ctx->strang_fused;
   ctx->strang_fused = nullptr;
 }
 

@@ -160,29 +160,29 @@ int structure_factor_t(pdeopt_ctx* ctx, const SkGrid& g, int env_first, int env_
     return fail(ctx, PDEOPT_ESTATE, "structure_factor: the transform's half spectrum has %lld cells, expected %lld", (long long)hc,
                 (long long)g.rows * g.nh);
   const size_t n_out = (size_t)nb * env_count, need = sizeof(double) * n_out * (size_t)(1 + blocks);
-  if ((rc = grow_device_buffer(ctx, (void**)&ctx->sk_dev, &ctx->sk_cap, need, /*sync_first=*/true))) return rc;
+  if ((rc = grow_device_buffer(ctx, ctx->sk_dev, need, /*sync_first=*/true))) return rc;
   SkArgs<T> a{};
   a.c = static_cast<const C2<T>*>(half) + (int64_t)env_first * hc;
-  a.ta = ctx->sk_tab_dev;
-  a.tb = g.dims == 3 ? ctx->sk_tab_dev + g.n[0] : nullptr;
-  a.tl = ctx->sk_tab_dev + (g.dims == 3 ? g.n[0] + g.n[1] : g.n[0]);
+  a.ta = ctx->sk_tab_dev.as<double>();
+  a.tb = g.dims == 3 ? ctx->sk_tab_dev.as<double>() + g.n[0] : nullptr;
+  a.tl = ctx->sk_tab_dev.as<double>() + (g.dims == 3 ? g.n[0] + g.n[1] : g.n[0]);
   a.rows = g.rows;
   a.n1 = g.dims == 3 ? g.n[1] : 0;
   a.nh = g.nh;
   a.n_last = g.n[g.dims - 1];
   a.n_bins = nb;
   a.estride = hc;
-  a.partial = ctx->sk_dev + n_out;
+  a.partial = ctx->sk_dev.as<double>() + n_out;
   const size_t lds = sizeof(double) * 4 * (size_t)nb;
   if (lds > 32768)
     PDEOPT_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sk_bin_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   if (!(ctx->opt_debug_ablate & kAblateBinning)) {
     hipLaunchKernelGGL(sk_bin_kernel<T>, dim3(blocks, env_count), dim3(256), lds, ctx->stream, a);
     hipLaunchKernelGGL(sk_finish_kernel, dim3((nb + 63) / 64, env_count), dim3(256), 0, ctx->stream, (const double*)a.partial, blocks, nb,
-                       ctx->sk_dev);
+                       ctx->sk_dev.as<double>());
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->sk_dev, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(host_out, ctx->sk_dev.as<double>(), sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->last_kernel = std::string("structure_factor<") + (g.dims == 3 ? "3-D," : "2-D,") + dtype_name<T>() + ">";
   return PDEOPT_OK;
@@ -191,16 +191,8 @@ int structure_factor_t(pdeopt_ctx* ctx, const SkGrid& g, int env_first, int env_
 }  // namespace
 
 void sk_drop(pdeopt_ctx* ctx) {
-  if (ctx->sk_tab_dev) (void)hipFree(ctx->sk_tab_dev);
-  ctx->sk_tab_dev = nullptr;
+  ctx->sk_tab_dev.reset();
   ctx->sk_bins = 0;
-}
-
-void sk_destroy(pdeopt_ctx* ctx) {
-  sk_drop(ctx);
-  if (ctx->sk_dev) (void)hipFree(ctx->sk_dev);
-  ctx->sk_dev = nullptr;
-  ctx->sk_cap = 0;
 }
 
 int sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const double* t2, int n_bins) {
@@ -235,8 +227,8 @@ int sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const doub
                 "of the 160 KiB of LDS of a compute unit", n_bins, kMaxBins);
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   sk_drop(ctx);
-  PDEOPT_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sk_tab_dev, sizeof(double) * tab.size()));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->sk_tab_dev, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = ensure_buffer(ctx, ctx->sk_tab_dev, sizeof(double) * tab.size())) return rc;
+  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->sk_tab_dev.as<double>(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->sk_bins = n_bins;
   return PDEOPT_OK;

@@ -873,6 +873,12 @@ class HipEngine:
         self._check(self._lib.pdeopt_get_counter(self._h, L.CNT_STAGE_LAUNCHES, C.byref(v)))
         return v.value
 
+    def device_bytes(self) -> int:
+        """device bytes the library holds right now, over every engine and network of the process"""
+        v = C.c_int64()
+        self._check(self._lib.pdeopt_get_counter(self._h, L.CNT_DEVICE_BYTES, C.byref(v)))
+        return v.value
+
     def last_groups(self) -> int:
         """environment groups the last ``advance`` ran the batch in (1 = the whole batch per sweep)"""
         v = C.c_int64()
