@@ -140,8 +140,7 @@ struct GraphStructure {
   int mu_kind, mu_flags, mu_n, mob_kind, mob_flags, mob_n;
 };
 struct GraphKey {
-  int integrator;
-  int fused;
+  int kernel, fuse_stages;  // the plan's kernel family (ExplicitPlan, stencil.hip: it implies the integrator) and the fusion option it ran under
   double dt;
   void *Y, *TA, *TB, *ACC, *KS, *ep, *vx, *vy;
   int64_t kernel_path, tile_rows, ablate;
@@ -318,6 +317,33 @@ int ensure_stream2(pdeopt_ctx* ctx);  // the ctx's second stream + fork / join e
 // api.hip: bring a time-dependent auxiliary field to local time t (no-op for static fields)
 int refresh_time_aux(pdeopt_ctx* ctx, int which, double t);
 inline bool has_time_aux(const pdeopt_ctx* ctx, int which) { return ctx->aux[which].fn != nullptr; }
+// a caller who turned one of the tiled path's knobs is asking for that path (the automatic choice of the one-launch kernels)
+inline bool tiled_knobs_untouched(const pdeopt_ctx* ctx) {
+  return ctx->opt_fuse_stages == 0 && ctx->opt_kernel_path == 0 && ctx->opt_graph == 0 && ctx->opt_group_envs == 0 && ctx->opt_tile_rows == 0;
+}
+
+// The table of pdeopt_set_time_table belongs to the advance it was sampled for: it is gone when that call returns,
+// however it returns (a table left behind would override the constants of a later right-hand side).  on = false: this
+// advance evaluates no time-dependent terms and leaves the table alone.
+struct TimeTableScope {
+  pdeopt_ctx* ctx;
+  bool on;
+  explicit TimeTableScope(pdeopt_ctx* c, bool on_ = true) : ctx(c), on(on_) { if (on) ctx->tt_misses = 0; }
+  TimeTableScope(const TimeTableScope&) = delete;
+  ~TimeTableScope() {
+    if (!on) return;
+    ctx->tt_times.clear();
+    ctx->tt_terms.clear();
+    ctx->tt_cursor = 0;
+  }
+  // rc of an advance that succeeded, unless stage times were missing from a table it was given (make_args counts them)
+  int missed() const {
+    if (!on || ctx->tt_times.empty() || !ctx->tt_misses) return PDEOPT_OK;
+    return fail(ctx, PDEOPT_EINVAL, "pdeopt_set_time_table: %lld stage time(s) of this advance are not in the table and no "
+                "pdeopt_set_time_terms callback is registered (times must be formed as t0 + (double) s * dt, + dt / 2, + dt)",
+                (long long)ctx->tt_misses);
+  }
+};
 
 // What a launch operates on: the environments [lo, lo + n) of the batch, on this stream.  Launch helpers pre-offset
 // their pointers by lo and size their grid by n; kernels see a batch of n.

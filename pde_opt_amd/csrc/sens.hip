@@ -826,18 +826,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
   // the smoothed-boundary equations: theta(t) and flux(t) at every stage time t0 + s dt (+ dt / 2, + dt); all others
   // are autonomous and keep passing 0.0
   const bool sbm = sbm_equation(ctx->prob.equation);
-  // a table of pdeopt_set_time_table belongs to the advance it was sampled for, as in pdeopt_advance: it is gone when
-  // this call returns, however it returns (a table left behind would override the constants of a later pdeopt_sens_rhs)
-  struct TableGuard {
-    pdeopt_ctx* c;
-    bool on;
-    ~TableGuard() {
-      if (!on) return;
-      c->tt_times.clear();
-      c->tt_terms.clear();
-      c->tt_cursor = 0;
-    }
-  } table_guard{ctx, sbm};
+  TimeTableScope table(ctx, sbm);  // as in pdeopt_advance (a table left behind would override the constants of a later pdeopt_sens_rhs)
   const bool ac = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN || bv || sbm;  // Euler and RK4, no fourier_symbol
   bool fused = false, kap = false;
   if (integrator == PDEOPT_INT_IMEX) {
@@ -868,7 +857,6 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
                                     "Allen-Cahn (got %d)", integrator);
   }
   if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
-  if (sbm) ctx->tt_misses = 0;
   for (int64_t s = 0; s < n_substeps; ++s) {
     const double ts = t0 + (double)s * dt;
     if (integrator == PDEOPT_INT_RK4) {
@@ -887,10 +875,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     if (rc) return rc;
   }
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
-  if (sbm && !ctx->tt_times.empty() && ctx->tt_misses)
-      return fail(ctx, PDEOPT_EINVAL, "pdeopt_set_time_table: %lld stage time(s) of this advance are not in the table and no "
-                  "pdeopt_set_time_terms callback is registered (times must be formed as t0 + (double) s * dt, + dt / 2, + dt)",
-                  (long long)ctx->tt_misses);
+  if ((rc = table.missed())) return rc;
   // after the loop: the base slope launches name their own kernel
   const int eq = ctx->prob.equation;
   ctx->last_kernel = eq == PDEOPT_EQ_CAHN_HILLIARD_3D ? "sens3d_dmu+sens3d_flux" : eq == PDEOPT_EQ_ALLEN_CAHN_SBM ? "sens_sbm_ac_tangent_rhs"

@@ -294,19 +294,32 @@ int launch_rhs_slope(pdeopt_ctx* ctx, const Window& w, const void* in, void* out
 namespace {
 constexpr int kGraphUnit = 16;  // substeps per captured graph (even: ping-pong buffers return)
 
-// the part of a problem that is baked into kernel arguments (not the per-env parameter values)
-GraphStructure graph_structure(const pdeopt_problem& p) {
-  GraphStructure g{};
-  g.equation = p.equation; g.dtype = p.dtype; g.nx = p.nx; g.ny = p.ny; g.batch = p.batch; g.derivs = p.derivs;
-  g.nz = p.nz; g.hx = p.hx; g.hy = p.hy; g.hz = p.hz;
-  g.mu_kind = p.mu.kind; g.mu_flags = p.mu.flags; g.mu_n = p.mu.n;
-  g.mob_kind = p.mob.kind; g.mob_flags = p.mob.flags; g.mob_n = p.mob.n;
-  return g;
-}
-}  // namespace
+// The kernel families of the explicit fixed-step path: what runs a substep.
+enum ExplicitKernel {
+  EK_COOP_FIXED, EK_SMALL_STEP,  // all substeps in one launch: several compute units per environment (stencil_coop_adaptive.hpp, MODE 1) / one (stencil_small.hpp)
+  EK_EULER_STAGE, EK_EULER_PAIR,  // one launch per Euler substep / per two of them (the stage-pair kernel), an odd last one on its own
+  EK_RK4_STAGE, EK_RK4_PAIRS,  // one launch per RK4 stage / stages 1+2 and 3+4 as two temporally fused launches (7 words/cell instead of 16)
+  EK_AC_SINGLE,  // Allen-Cahn fp32: the whole RK4 substep in one pass (2 words per cell instead of 7)
+  EK_CH_SINGLE,  // Cahn-Hilliard fp32, periodic divisible grids: the same (stencil_fused_ch4.hpp)
+};
+inline bool is_rk4(ExplicitKernel k) { return k >= EK_RK4_STAGE; }
+// launches of one RK4 substep = the points at which a phase-wise caller may do work of its own
+inline int rk4_phases(ExplicitKernel k) { return k == EK_RK4_STAGE ? 4 : k == EK_RK4_PAIRS ? 2 : 1; }
 
-static bool fused_supported_dt(const pdeopt_ctx* ctx) {
-  return with_dtype(ctx, [&](auto t) { return fused_supported<decltype(t)>(ctx); });
+// do the fused stage-pair kernels (stencil_fused.hpp, stencil_fused_ac.hpp) cover the configured problem?
+bool stage_pairs_available(const pdeopt_ctx* ctx) {
+  return ctx->opt_kernel_path != 1 && ctx->prob.derivs == PDEOPT_DERIVS_FD &&
+         with_dtype(ctx, [&](auto t) { return fused_supported<decltype(t)>(ctx); });
+}
+
+// Which family runs an RK4 substep of the configured problem.  phased: the substep is driven phase by phase (pdeopt_rk4_phase,
+// the decomposed drivers) -- a single-pass kernel exists there for the halo-8 layout only, whose 8-cell halo is that kernel's
+// tile + 8 input, and that layout has stage pairs for Cahn-Hilliard only.  PDEOPT_OPT_FUSE_STAGES = 1 keeps the stage pairs.
+ExplicitKernel rk4_family(const pdeopt_ctx* ctx, bool phased) {
+  if (!phased && ac_quad_supported(ctx)) return EK_AC_SINGLE;
+  if ((!phased || ctx->halo == 8) && ch_quad_chosen(ctx)) return EK_CH_SINGLE;
+  if (stage_pairs_available(ctx) && (ctx->halo != 8 || ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD)) return EK_RK4_PAIRS;
+  return EK_RK4_STAGE;
 }
 
 // Does the whole-environment-step kernel (stencil_small.hpp) take this advance?  PDEOPT_OPT_SMALL_PERSIST: 1 = wherever
@@ -314,106 +327,184 @@ static bool fused_supported_dt(const pdeopt_ctx* ctx) {
 // dependent ones, measured 2.7-4.8 x faster per environment step), and larger LDS-resident grids once enough
 // environments run side by side to fill the chip's compute units (>= 192) -- a single 128^2 environment is faster on
 // the tiled kernels, which spread it over 8+ CUs, than on one CU.
-static bool small_chosen(const pdeopt_ctx* ctx, int integrator, int64_t n) {
+bool small_chosen(const pdeopt_ctx* ctx, int integrator, int64_t n) {
   if (ctx->opt_small_persist < 0 || ctx->opt_kernel_path == 1 || ctx->opt_debug_ablate) return false;
   if (integrator != PDEOPT_INT_EULER && integrator != PDEOPT_INT_RK4) return false;
   if (!with_dtype(ctx, [&](auto t) { return small_supported<decltype(t)>(ctx); })) return false;
   if (ctx->opt_small_persist > 0) return true;
-  // a caller who turned one of the tiled path's knobs is asking for that path
-  if (ctx->opt_fuse_stages != 0 || ctx->opt_kernel_path != 0 || ctx->opt_graph != 0 || ctx->opt_group_envs != 0 || ctx->opt_tile_rows != 0)
-    return false;
+  if (!tiled_knobs_untouched(ctx)) return false;
   const int64_t cells = (int64_t)ctx->prob.nx * ctx->prob.ny;
   if (n < 2) return false;
   return cells <= kSmallAutoCells || ctx->prob.batch >= kSmallAutoBatch;
 }
 
-int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n) {
-  int rc;
+// Everything advance_explicit decides before it launches: the kernel family and the schedule.  plan_explicit fills it;
+// it allocates nothing, launches nothing and writes nothing into the ctx.
+struct ExplicitPlan {
+  ExplicitKernel kernel;
+  int fuse_stages;    // PDEOPT_OPT_FUSE_STAGES the stage pairs were chosen under (part of a captured graph's key), else 0
+  int group;          // environments per group (groups.hpp); the batch: one sweep
+  bool side_by_side;  // two groups in flight on two streams
+  bool graph;         // capture kGraphUnit substeps into a hipGraph and replay it
+  bool timed;         // time-dependent terms evaluated by the host per stage (smoothed-boundary scalars, advection velocities)
+};
+ExplicitPlan plan_explicit(const pdeopt_ctx* ctx, int integrator, int64_t n) {
+  const int batch = ctx->prob.batch;
+  ExplicitPlan p{};
+  p.group = batch;
   // one environment (or a few) of a mid-sized grid: several compute units per environment, all substeps in one launch
-  // (stencil_coop_adaptive.hpp, MODE 1)
   const bool coop = with_dtype(ctx, [&](auto t) { return coop_fixed_chosen<decltype(t)>(ctx, integrator, n); });
   const bool small = small_chosen(ctx, integrator, n);
   const bool f64 = ctx->prob.dtype == PDEOPT_F64;  // (64^2 fp64: 0.70 ms against the one-CU kernel's 1.14, which small_chosen would pick)
-  if (coop && (ctx->opt_small_persist == 2 || f64 || !small)) {
-    ctx->last_groups = 1;
-    return with_dtype(ctx, [&](auto t) { return coop_fixed_advance<decltype(t)>(ctx, integrator, t0, dt, n); });
-  }
-  const Window all = whole_batch(ctx);
-  if (small) {
-    ctx->last_groups = 1;
-    return with_dtype(ctx, [&](auto t) { return launch_small<decltype(t)>(ctx, all, integrator, dt, n); });
-  }
-  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
   // Euler: two substeps per launch through the stage-pair kernels where they exist
   //   PAIR_12 with aA = bA = bB = dt:  w = y + dt f(y),  ACC = y + dt f(y) + dt f(w) = two Euler steps
-  const bool euler2 = integrator == PDEOPT_INT_EULER && ctx->opt_kernel_path != 1 &&
-                      ctx->prob.derivs == PDEOPT_DERIVS_FD && n >= 2 &&
-                      fused_supported_dt(ctx);
-  if (integrator == PDEOPT_INT_RK4 || euler2) {
-    if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
-    if (integrator == PDEOPT_INT_RK4 && (rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
-  } else if (integrator != PDEOPT_INT_EULER) {
-    return fail(ctx, PDEOPT_EINVAL, "integrator %d is not an explicit fixed-step integrator", integrator);
-  }
-  // work field of the two-pass 3-D right-hand side: allocated here, never inside a stream capture
-  if ((ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D || bv_equation(ctx->prob.equation)) &&
-      (rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes)))
-    return rc;
-  // Environments are independent, so the substep loop may run group by group: a group whose
-  // working set (4 fields x group x nx x ny) fits the 256 MiB Infinity Cache keeps every stage's
-  // reads and writes on-die for all n substeps instead of streaming the whole batch through HBM
-  // once per stage.
-  const int batch = ctx->prob.batch;
-  // time-dependent terms evaluated by the host per stage (smoothed-boundary scalars, advection velocities)
-  const bool timed = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM ||
-                     has_time_aux(ctx, PDEOPT_AUX_VX_FACE) || has_time_aux(ctx, PDEOPT_AUX_VY_FACE) ||
-                     bv_time_dependent(ctx);  // (a voltage protocol v(t): the whole batch per sweep, no graph)
-  int group = batch;
-  bool side_by_side = false;
-  if (ctx->prob.derivs == PDEOPT_DERIVS_FOURIER || timed) {
-    group = batch;  // batched rocFFT plans cover the whole batch; host callbacks run once per stage time
-  } else if (ctx->opt_group_envs > 0) {
-    group = (int)std::min<int64_t>(ctx->opt_group_envs, batch);
-  } else if (ctx->opt_group_envs == 0) {
-    // auto: largest balanced group whose 4 fields fit the Infinity Cache (measured on MI355X:
-    // 32 x 1024^2 fp32 runs 13-16 % faster as 2 groups of 16 = 256 MiB than as one 512 MiB sweep;
-    // smaller groups lose more to per-launch ramp/tail than they gain)
-    if (n > 1) group = cache_group(batch, 4 * ctx->env_elems * ctx->esize, 256ull << 20, false);
-    if (group < batch) {
-      // Two groups side by side on two streams, each half the size (the same resident working set): a launch of the
-      // stage kernels is 3-6 rounds of resident workgroups, its ramp and its tail leave compute units idle, and the
-      // next launch of the SAME group depends on it -- the other group's does not.
-      if (ctx->opt_group_streams != 1 && group >= 2 && ctx->prob.equation != PDEOPT_EQ_CAHN_HILLIARD_3D) {
-        group = (group + 1) / 2;
-        side_by_side = true;
-      }
+  if (coop && (ctx->opt_small_persist == 2 || f64 || !small)) p.kernel = EK_COOP_FIXED;
+  else if (small) p.kernel = EK_SMALL_STEP;
+  else if (integrator == PDEOPT_INT_EULER) p.kernel = n >= 2 && stage_pairs_available(ctx) ? EK_EULER_PAIR : EK_EULER_STAGE;
+  else p.kernel = rk4_family(ctx, /*phased=*/false);
+  if (p.kernel <= EK_SMALL_STEP) return p;  // one launch holds every environment and every substep
+  if (p.kernel == EK_RK4_PAIRS) p.fuse_stages = (int)ctx->opt_fuse_stages;
+
+  // Environments are independent, so the substep loop may run group by group: a group whose working set (4 fields x
+  // group x nx x ny) fits the 256 MiB Infinity Cache keeps every stage's reads and writes on-die for all n substeps
+  // instead of streaming the whole batch through HBM once per stage.
+  p.timed = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM || ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_SBM ||
+            has_time_aux(ctx, PDEOPT_AUX_VX_FACE) || has_time_aux(ctx, PDEOPT_AUX_VY_FACE) ||
+            bv_time_dependent(ctx);  // (a voltage protocol v(t): the whole batch per sweep, no graph)
+  const bool fd = ctx->prob.derivs == PDEOPT_DERIVS_FD;
+  const bool ch3d = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D;
+  if (!fd || p.timed) p.group = batch;  // batched rocFFT plans cover the whole batch; host callbacks run once per stage time
+  else if (ctx->opt_group_envs > 0) p.group = (int)std::min<int64_t>(ctx->opt_group_envs, batch);
+  else if (ctx->opt_group_envs == 0) {
+    // auto: largest balanced group whose 4 fields fit the Infinity Cache (measured on MI355X: 32 x 1024^2 fp32 runs
+    // 13-16 % faster as 2 groups of 16 = 256 MiB than as one 512 MiB sweep; smaller groups lose more to per-launch
+    // ramp/tail than they gain)
+    if (n > 1) p.group = cache_group(batch, 4 * ctx->env_elems * ctx->esize, 256ull << 20, false);
+    // Two groups side by side on two streams, each half the size (the same resident working set): a launch of the
+    // stage kernels is 3-6 rounds of resident workgroups, its ramp and its tail leave compute units idle, and the
+    // next launch of the SAME group depends on it -- the other group's does not.
+    if (p.group < batch && ctx->opt_group_streams != 1 && p.group >= 2 && !ch3d) {
+      p.group = (p.group + 1) / 2;
+      p.side_by_side = true;
     }
   }
-  const bool can_pair = !timed && ctx->prob.derivs == PDEOPT_DERIVS_FD && ctx->prob.equation != PDEOPT_EQ_CAHN_HILLIARD_3D;
-  if (ctx->opt_group_streams == 2 && can_pair && group < batch) side_by_side = true;
+  const bool can_pair = !p.timed && fd && !ch3d;
+  if (ctx->opt_group_streams == 2 && can_pair && p.group < batch) p.side_by_side = true;
   // ... and a batch that fits the cache as one group runs as two halves side by side for the same reason (measured
   // 512^2 x 64 Allen-Cahn: 20.1 k env-steps/s against 18.9 k), unless it is small enough for the hipGraph replay below
-  if (ctx->opt_group_streams == 0 && ctx->opt_group_envs == 0 && can_pair && group >= batch && batch >= 2 && n > 1 &&
+  if (ctx->opt_group_streams == 0 && ctx->opt_group_envs == 0 && can_pair && p.group >= batch && batch >= 2 && n > 1 &&
       ctx->opt_graph <= 0 && (int64_t)ctx->prob.nx * ctx->prob.ny * batch > (1 << 21)) {
-    group = (batch + 1) / 2;
-    side_by_side = true;
+    p.group = (batch + 1) / 2;
+    p.side_by_side = true;
   }
-  const bool fused = integrator == PDEOPT_INT_RK4 && ctx->opt_kernel_path != 1 &&
-                     ctx->prob.derivs == PDEOPT_DERIVS_FD &&
-                     fused_supported_dt(ctx);
+  // launch-bound regime (small grids / few environments: a stage kernel runs for a few microseconds, the host needs ~3.5 us to issue one): replay_graph
+  const int64_t cells_per_launch = (int64_t)ctx->prob.nx * ctx->prob.ny * p.group;
+  p.graph = !p.timed && ctx->opt_graph >= 0 && p.group >= batch && fd && n >= 2 * kGraphUnit &&
+            (ctx->opt_graph > 0 || cells_per_launch <= (1 << 20));
+  return p;
+}
 
-  // Allen-Cahn fp32: the whole RK4 substep in one pass (2 words per cell instead of 7)
-  const bool quad = integrator == PDEOPT_INT_RK4 && ac_quad_supported(ctx);
-  // Cahn-Hilliard fp32, periodic divisible grids: the same (stencil_fused_ch4.hpp); PDEOPT_OPT_FUSE_STAGES = 1 keeps the stage pairs
-  const bool chquad = integrator == PDEOPT_INT_RK4 && ch_quad_chosen(ctx);
+// The work fields the launches of a family use, allocated before the first of them.
+int ensure_work_fields(pdeopt_ctx* ctx, ExplicitKernel k) {
+  int rc;
+  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
+  if ((is_rk4(k) || k == EK_EULER_PAIR) && (rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
+  if (is_rk4(k) && (rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
+  // work field of the two-pass 3-D right-hand side: allocated here, never inside a stream capture
+  const bool ks = ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD_3D || bv_equation(ctx->prob.equation);
+  return ks ? ensure_buffer(ctx, ctx->KS, ctx->total_bytes) : PDEOPT_OK;
+}
+
+// Launch `ph` of an RK4 substep of family k on the window: Y holds the state, TA takes the new one (one launch per stage: TA
+// is a stage input and stage 4 puts the new state into Y in place -- y is only touched pointwise); TB and ACC are the ctx's.
+// t is the time of the stage launched; it only matters to time-dependent equations, which run one launch per stage.
+int launch_rk4_phase(pdeopt_ctx* ctx, ExplicitKernel k, int ph, const Window& w, const HaloIo& io, void* Y, void* TA, double t, double dt) {
+  void *const TB = ctx->TB.get(), *const ACC = ctx->ACC.get();
+  if (k == EK_AC_SINGLE) return launch_ac_quad(ctx, w, Y, TA, dt);
+  if (k == EK_CH_SINGLE) return launch_ch_quad(ctx, w, io, Y, TA, dt);
+  if (k == EK_RK4_PAIRS) {
+    if (ph == 0) return launch_pair_dt(ctx, w, io, PAIR_12, Y, nullptr, nullptr, TB, ACC, dt / 2, dt / 6, dt / 2, dt / 3);
+    return launch_pair_dt(ctx, w, io, PAIR_34, TB, Y, ACC, TA, nullptr, dt, dt / 3, 0.0, dt / 6);
+  }
+  switch (ph) {
+    case 0: return launch_stage(ctx, w, t, Y, Y, TA, ACC, dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);   // k1 = f(y);   TA = y + dt/2 k1;  ACC = y + dt/6 k1
+    case 1: return launch_stage(ctx, w, t, TA, Y, TB, ACC, dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);   // k2 = f(TA);  TB = y + dt/2 k2;  ACC += dt/3 k2
+    case 2: return launch_stage(ctx, w, t, TB, Y, TA, ACC, dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);       // k3 = f(TB);  TA = y + dt k3;    ACC += dt/3 k3
+    default: return launch_stage(ctx, w, t, TA, Y, Y, ACC, 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);  // k4 = f(TA);  y = ACC + dt/6 k4
+  }
+}
+
+// Capture kGraphUnit substeps of the whole batch once into a hipGraph and replay it while n has that many left;
+// *done = the substeps replayed.  Kernel arguments baked into the graph are the field pointers, dt and the problem
+// structure; per-environment parameter VALUES live in device memory and may change between replays.
+template <typename Step>
+int replay_graph(pdeopt_ctx* ctx, const ExplicitPlan& plan, double dt, int64_t n, Step&& step, int64_t* done) {
+  GraphKey key;
+  memset(&key, 0, sizeof(key));  // padding bytes take part in the memcmp below
+  key.kernel = plan.kernel; key.fuse_stages = plan.fuse_stages; key.dt = dt;
+  key.Y = ctx->Y.get(); key.TA = ctx->TA.get(); key.TB = ctx->TB.get(); key.ACC = ctx->ACC.get(); key.KS = ctx->KS.get();
+  key.ep = ctx->env_params_dev.get();
+  key.vx = ctx->aux[PDEOPT_AUX_VX_FACE].dev.get(); key.vy = ctx->aux[PDEOPT_AUX_VY_FACE].dev.get();
+  key.kernel_path = ctx->opt_kernel_path; key.tile_rows = ctx->opt_tile_rows; key.ablate = ctx->opt_debug_ablate;
+  // the part of a problem that is baked into kernel arguments (not the per-env parameter values)
+  const pdeopt_problem& p = ctx->prob;
+  GraphStructure& g = key.structure;
+  g.equation = p.equation; g.dtype = p.dtype; g.nx = p.nx; g.ny = p.ny; g.batch = p.batch; g.derivs = p.derivs;
+  g.nz = p.nz; g.hx = p.hx; g.hy = p.hy; g.hz = p.hz;
+  g.mu_kind = p.mu.kind; g.mu_flags = p.mu.flags; g.mu_n = p.mu.n;
+  g.mob_kind = p.mob.kind; g.mob_flags = p.mob.flags; g.mob_n = p.mob.n;
+  if (!ctx->graph_exec || memcmp(&key, &ctx->graph_key, sizeof(key)) != 0) {
+    graph_destroy(ctx);
+    const int64_t launches_before = ctx->n_stage_launches;
+    hipGraph_t graph = nullptr;
+    int rc = PDEOPT_OK;
+    PDEOPT_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    for (int u = 0; u < kGraphUnit && !rc;) {
+      int took = 1;
+      rc = step(whole_batch(ctx), u, 0, took);
+      u += took;
+    }
+    const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
+    ctx->graph_launches_per_replay = ctx->n_stage_launches - launches_before;
+    ctx->n_stage_launches = launches_before;
+    if (rc) {
+      if (graph) (void)hipGraphDestroy(graph);
+      return rc;
+    }
+    PDEOPT_HIP_CHECK(ctx, e_end);
+    const hipError_t e_inst = hipGraphInstantiate(&ctx->graph_exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    PDEOPT_HIP_CHECK(ctx, e_inst);
+    ctx->graph_key = key;
+    ctx->graph_name = ctx->last_kernel + "+hipGraph";
+    // kGraphUnit is even: the ping-pong buffers are back in place after one replay
+  }
+  for (; *done + kGraphUnit <= n; *done += kGraphUnit) {
+    PDEOPT_HIP_CHECK(ctx, hipGraphLaunch(ctx->graph_exec, ctx->stream));
+    ctx->n_stage_launches += ctx->graph_launches_per_replay;
+  }
+  ctx->last_kernel = ctx->graph_name;
+  return PDEOPT_OK;
+}
+
+}  // namespace
+
+int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int64_t n) {
+  if (integrator != PDEOPT_INT_EULER && integrator != PDEOPT_INT_RK4)
+    return fail(ctx, PDEOPT_EINVAL, "integrator %d is not an explicit fixed-step integrator", integrator);
+  const ExplicitPlan plan = plan_explicit(ctx, integrator, n);
+  const ExplicitKernel kernel = plan.kernel;
+  ctx->last_groups = 1;  // (run_groups sets it for the families that come to it)
+  if (kernel == EK_COOP_FIXED) return with_dtype(ctx, [&](auto t) { return coop_fixed_advance<decltype(t)>(ctx, integrator, t0, dt, n); });
+  if (kernel == EK_SMALL_STEP) return with_dtype(ctx, [&](auto t) { return launch_small<decltype(t)>(ctx, whole_batch(ctx), integrator, dt, n); });
+  int rc;
+  if ((rc = ensure_work_fields(ctx, kernel))) return rc;
 
   // The state ping-pongs between Y and TA: every launch that advances it (an Euler step or pair, a fused RK4 substep)
   // writes the other buffer; the per-stage RK4 updates y in place.  Every group performs the same launches, so which
   // buffer holds the state before substep s depends on s alone: `base` is where the buffers were as the ctx has them.
-  const bool rotates = integrator == PDEOPT_INT_EULER || quad || chquad || fused;
-  void* const Y0 = ctx->Y.get();
-  void* const TA0 = ctx->TA.get();
-  auto rotations = [&](int64_t s, int64_t base) -> int64_t { return !rotates ? 0 : euler2 ? (s - base + 1) / 2 : s - base; };
+  void *const Y0 = ctx->Y.get(), *const TA0 = ctx->TA.get();
+  auto rotations = [&](int64_t s, int64_t base) -> int64_t { return kernel == EK_RK4_STAGE ? 0 : kernel == EK_EULER_PAIR ? (s - base + 1) / 2 : s - base; };
   const HaloIo none{};
 
   // substep s (and s + 1, where two Euler substeps go into one launch: took = 2) of the window
@@ -422,89 +513,25 @@ int advance_explicit(pdeopt_ctx* ctx, int integrator, double t0, double dt, int6
     void* const Y = odd ? TA0 : Y0;
     void* const TA = odd ? Y0 : TA0;
     const double ts = t0 + (double)s * dt;  // stage times only matter to time-dependent equations
-    if (euler2 && s + 1 < n) {
+    if (kernel == EK_EULER_PAIR && s + 1 < n) {
       // result into TA, TB takes the kernel's unused y + dt k2 output
       took = 2;
       return launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB.get(), TA, dt, dt, dt, dt);
     }
-    if (integrator == PDEOPT_INT_EULER) return launch_stage(ctx, w, ts, Y, Y, TA, nullptr, dt, 0.0, OUT_Y_PLUS_AK, ACC_NONE);
-    if (quad) return launch_ac_quad(ctx, w, Y, TA, dt);
-    if (chquad) return launch_ch_quad(ctx, w, none, Y, TA, dt);
-    int r;
-    if (fused) {
-      // stages 1+2 and 3+4 as two temporally fused launches (7 words/cell instead of 16)
-      r = launch_pair_dt(ctx, w, none, PAIR_12, Y, nullptr, nullptr, ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 6, dt / 2, dt / 3);
-      if (!r) r = launch_pair_dt(ctx, w, none, PAIR_34, ctx->TB.get(), Y, ctx->ACC.get(), TA, nullptr, dt, dt / 3, 0.0, dt / 6);
-      return r;
-    }
-    // stage 1: k1 = f(y);        TA = y + dt/2 k1;  ACC = y + dt/6 k1
-    r = launch_stage(ctx, w, ts, Y, Y, TA, ctx->ACC.get(), dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
-    // stage 2: k2 = f(TA);       TB = y + dt/2 k2;  ACC += dt/3 k2
-    if (!r) r = launch_stage(ctx, w, ts + dt / 2, TA, Y, ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    // stage 3: k3 = f(TB);       TA = y + dt k3;    ACC += dt/3 k3
-    if (!r) r = launch_stage(ctx, w, ts + dt / 2, ctx->TB.get(), Y, TA, ctx->ACC.get(), dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    // stage 4: k4 = f(TA);       y  = ACC + dt/6 k4   (in place: y is only touched pointwise)
-    if (!r) r = launch_stage(ctx, w, ts + dt, TA, Y, Y, ctx->ACC.get(), 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
+    if (!is_rk4(kernel)) return launch_stage(ctx, w, ts, Y, Y, TA, nullptr, dt, 0.0, OUT_Y_PLUS_AK, ACC_NONE);
+    int r = PDEOPT_OK;
+    for (int ph = 0; ph < rk4_phases(kernel) && !r; ++ph)  // stage times: ts, ts + dt/2 twice, ts + dt
+      r = launch_rk4_phase(ctx, kernel, ph, w, none, Y, TA, ph == 0 ? ts : ph == 3 ? ts + dt : ts + dt / 2, dt);
     return r;
   };
 
-  // Launch-bound regime (small grids / few environments: a stage kernel runs for a few microseconds,
-  // the host needs ~3.5 us to issue one): capture kGraphUnit substeps once into a hipGraph and replay
-  // it.  Kernel arguments baked into the graph are the field pointers, dt and the problem structure;
-  // per-environment parameter VALUES live in device memory and may change between replays.
   int64_t done = 0;
-  const int64_t cells_per_launch = (int64_t)ctx->prob.nx * ctx->prob.ny * group;
-  const bool want_graph = !timed && ctx->opt_graph >= 0 && group >= batch && ctx->prob.derivs == PDEOPT_DERIVS_FD &&
-                          n >= 2 * kGraphUnit && (ctx->opt_graph > 0 || cells_per_launch <= (1 << 20));
-  if (want_graph) {
-    GraphKey key;
-    memset(&key, 0, sizeof(key));  // padding bytes take part in the memcmp below
-    key.integrator = integrator;
-    key.fused = quad ? 100 : chquad ? 101 : (euler2 ? 50 : (fused ? (int)(1 + ctx->opt_fuse_stages) : 0));
-    key.dt = dt;
-    key.Y = ctx->Y.get(); key.TA = ctx->TA.get(); key.TB = ctx->TB.get(); key.ACC = ctx->ACC.get(); key.KS = ctx->KS.get();
-    key.ep = ctx->env_params_dev.get();
-    key.vx = ctx->aux[PDEOPT_AUX_VX_FACE].dev.get(); key.vy = ctx->aux[PDEOPT_AUX_VY_FACE].dev.get();
-    key.kernel_path = ctx->opt_kernel_path; key.tile_rows = ctx->opt_tile_rows; key.ablate = ctx->opt_debug_ablate;
-    key.structure = graph_structure(ctx->prob);
-    if (!ctx->graph_exec || memcmp(&key, &ctx->graph_key, sizeof(key)) != 0) {
-      graph_destroy(ctx);
-      const int64_t launches_before = ctx->n_stage_launches;
-      hipGraph_t graph = nullptr;
-      PDEOPT_HIP_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      for (int u = 0; u < kGraphUnit && !rc;) {
-        int took = 1;
-        rc = step(all, u, 0, took);
-        u += took;
-      }
-      const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
-      ctx->graph_launches_per_replay = ctx->n_stage_launches - launches_before;
-      ctx->n_stage_launches = launches_before;
-      if (rc) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      PDEOPT_HIP_CHECK(ctx, e_end);
-      const hipError_t e_inst = hipGraphInstantiate(&ctx->graph_exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      PDEOPT_HIP_CHECK(ctx, e_inst);
-      ctx->graph_key = key;
-      ctx->graph_name = ctx->last_kernel + "+hipGraph";
-      // kGraphUnit is even: the ping-pong buffers are back in place after one replay
-    }
-    for (; done + kGraphUnit <= n; done += kGraphUnit) {
-      PDEOPT_HIP_CHECK(ctx, hipGraphLaunch(ctx->graph_exec, ctx->stream));
-      ctx->n_stage_launches += ctx->graph_launches_per_replay;
-    }
-    ctx->last_kernel = ctx->graph_name;
-  }
-
+  if (plan.graph && (rc = replay_graph(ctx, plan, dt, n, step, &done))) return rc;
   // the substeps the graph did not take, group by group
-  rc = run_groups(ctx, group, side_by_side, done, n, [](const Window&) { return PDEOPT_OK; },
+  rc = run_groups(ctx, plan.group, plan.side_by_side, done, n, [](const Window&) { return PDEOPT_OK; },
                   [&](const Window& w, int64_t s, int& took) { return step(w, s, done, took); });
-  if (rc) return rc;
-  if (rotations(n, done) & 1) std::swap(ctx->Y, ctx->TA);
-  return PDEOPT_OK;
+  if (!rc && (rotations(n, done) & 1)) std::swap(ctx->Y, ctx->TA);
+  return rc;
 }
 
 void graph_destroy(pdeopt_ctx* ctx) {
@@ -515,26 +542,14 @@ void graph_destroy(pdeopt_ctx* ctx) {
 // One phase of an RK4 substep for callers that interleave their own work between phases (the
 // domain-decomposed driver exchanges halos of `fields[phase]` before `rk4_phase(phase)`).
 int rk4_phase_plan(pdeopt_ctx* ctx, int* fields, int* nphases) {
-  const bool fused = ctx->opt_kernel_path != 1 && ctx->prob.derivs == PDEOPT_DERIVS_FD &&
-                     fused_supported_dt(ctx);
-  if (ctx->halo == 8 && ch_quad_chosen(ctx)) {
-    // halo-8 layout, the whole substep in one kernel (stencil_fused_ch4.hpp): its tile + 8 input is the halo
-    *nphases = 1;
-    fields[0] = 0;
-  } else if (fused && ctx->halo == 8 && ctx->prob.equation == PDEOPT_EQ_CAHN_HILLIARD) {
-    // halo-8 layout: ONE exchange per substep.  Pair 1+2 runs on the tile + 4 ring (it reads y on tile + 8), so
-    // pair 3+4 finds TB on its tile + 4 input region without an exchange of TB.
-    *nphases = 2;
-    fields[0] = 0;
-    fields[1] = -1;  // no exchange before phase 1
-  } else if (fused && ctx->halo != 8) {
-    *nphases = 2;
-    fields[0] = 0;  // Y  (stage pair 1+2 differentiates y)
-    fields[1] = 2;  // TB (stage pair 3+4 differentiates y + dt/2 k2)
-  } else {
-    *nphases = 4;
-    fields[0] = 0; fields[1] = 1; fields[2] = 2; fields[3] = 1;  // Y, TA, TB, TA
-  }
+  const ExplicitKernel k = rk4_family(ctx, /*phased=*/true);
+  *nphases = rk4_phases(k);
+  // one launch per stage: Y, TA, TB, TA.  The single-pass kernel (halo-8 layout: its tile + 8 input is the halo): Y
+  fields[0] = 0; fields[1] = 1; fields[2] = 2; fields[3] = 1;
+  // Stage pairs: Y (pair 1+2 differentiates y), then TB (pair 3+4 differentiates y + dt/2 k2) -- but the halo-8 layout
+  // has ONE exchange per substep: pair 1+2 runs on the tile + 4 ring (it reads y on tile + 8), so pair 3+4 finds TB on
+  // its tile + 4 input region without an exchange of TB (-1: no exchange before phase 1)
+  if (k == EK_RK4_PAIRS) fields[1] = ctx->halo == 8 ? -1 : 2;
   return PDEOPT_OK;
 }
 
@@ -545,43 +560,25 @@ int rk4_phase_plan(pdeopt_ctx* ctx, int* fields, int* nphases) {
 static int rk4_phase_io(pdeopt_ctx* ctx, int phase, double dt, int part, HaloIo io) {
   if (ctx->prob.equation == PDEOPT_EQ_GPE) return fail(ctx, PDEOPT_EINVAL, "no explicit RHS for the GPE");
   if (part < 0 || part > 2) return fail(ctx, PDEOPT_EINVAL, "part %d outside 0..2", part);
-  int rc;
-  if ((rc = ensure_buffer(ctx, ctx->TA, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, ctx->TB, ctx->total_bytes))) return rc;
-  if ((rc = ensure_buffer(ctx, ctx->ACC, ctx->total_bytes))) return rc;
-  int fields[4], n = 0;
-  rk4_phase_plan(ctx, fields, &n);
+  const ExplicitKernel k = rk4_family(ctx, /*phased=*/true);
+  const int n = rk4_phases(k);
+  if (const int rc = ensure_work_fields(ctx, k)) return rc;
   if (phase < 0 || phase >= n) return fail(ctx, PDEOPT_EINVAL, "phase %d outside 0..%d", phase, n - 1);
-  const Window w = whole_batch(ctx);
-  if (ctx->halo == 8 && n != 2 && n != 1)
+  if (ctx->halo == 8 && k == EK_RK4_STAGE)
     return fail(ctx, PDEOPT_EINVAL, "the halo-8 layout needs the fused Cahn-Hilliard kernels (closure class / tile shape / "
                                     "PDEOPT_OPT_FUSE_STAGES rule them out here): use halo layout 4");
   if (ctx->halo == 8 && part != 0)
     return fail(ctx, PDEOPT_EINVAL, "interior / edge launches belong to the halo-4 layout (two exchanges per substep)");
-  if (n == 1) {  // the whole substep in one pass: y (+ halo) -> y'
-    rc = launch_ch_quad(ctx, w, io, ctx->Y.get(), ctx->TA.get(), dt);
-    std::swap(ctx->Y, ctx->TA);
-    return rc;
-  }
-  if (n == 2) {
-    io.part = part;
-    if (phase == 0) {
-      io.ext = ctx->halo == 8 ? 4 : 0;
-      return launch_pair_dt(ctx, w, io, PAIR_12, ctx->Y.get(), nullptr, nullptr, ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 6, dt / 2, dt / 3);
-    }
-    rc = launch_pair_dt(ctx, w, io, PAIR_34, ctx->TB.get(), ctx->Y.get(), ctx->ACC.get(), ctx->TA.get(), nullptr, dt, dt / 3, 0.0, dt / 6);
-    if (part != 1) std::swap(ctx->Y, ctx->TA);
-    return rc;
-  }
-  if (part != 0)
+  if (k == EK_RK4_STAGE && part != 0)
     return fail(ctx, PDEOPT_EINVAL, "interior / edge launches exist for the fused stage pairs only (this problem runs one kernel per stage)");
-  // a phase call carries no time: the decomposed driver runs autonomous equations, t = 0 for any time-dependent term
-  switch (phase) {
-    case 0: return launch_stage(ctx, w, 0.0, ctx->Y.get(), ctx->Y.get(), ctx->TA.get(), ctx->ACC.get(), dt / 2, dt / 6, OUT_Y_PLUS_AK, ACC_INIT);
-    case 1: return launch_stage(ctx, w, 0.0, ctx->TA.get(), ctx->Y.get(), ctx->TB.get(), ctx->ACC.get(), dt / 2, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    case 2: return launch_stage(ctx, w, 0.0, ctx->TB.get(), ctx->Y.get(), ctx->TA.get(), ctx->ACC.get(), dt, dt / 3, OUT_Y_PLUS_AK, ACC_ADD);
-    default: return launch_stage(ctx, w, 0.0, ctx->TA.get(), ctx->Y.get(), ctx->Y.get(), ctx->ACC.get(), 0.0, dt / 6, OUT_ACC_PLUS_BK, ACC_NONE);
+  if (k == EK_RK4_PAIRS) {
+    io.part = part;
+    if (phase == 0) io.ext = ctx->halo == 8 ? 4 : 0;
   }
+  // a phase call carries no time: the decomposed driver runs autonomous equations, t = 0 for any time-dependent term
+  const int rc = launch_rk4_phase(ctx, k, phase, whole_batch(ctx), io, ctx->Y.get(), ctx->TA.get(), 0.0, dt);
+  if (k != EK_RK4_STAGE && phase == n - 1 && part != 1) std::swap(ctx->Y, ctx->TA);
+  return rc;
 }
 
 int rk4_phase(pdeopt_ctx* ctx, int phase, double dt, int part) { return rk4_phase_io(ctx, phase, dt, part, HaloIo{}); }
@@ -623,7 +620,7 @@ int rk4_loopback_advance(pdeopt_ctx* ctx, double dt, int64_t n) {
 // halo as io says (in the field already, from gathered strips, from the neighbours' own buffers); the last writes the
 // NEW state's halo strip into io.strip (nullptr: not wanted)
 static int rk4_substep_h8_io(pdeopt_ctx* ctx, double dt, const HaloIo& io) {
-  if (ch_quad_chosen(ctx)) return rk4_phase_io(ctx, 0, dt, 0, io);  // one kernel: halo in, the new strip out
+  if (rk4_family(ctx, /*phased=*/true) == EK_CH_SINGLE) return rk4_phase_io(ctx, 0, dt, 0, io);  // one kernel: halo in, the new strip out
   HaloIo in = io, out{};
   in.strip = nullptr;
   out.strip = io.strip;

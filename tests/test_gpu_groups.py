@@ -22,7 +22,8 @@ from util import MOB, MU, rel_l2, std_domain, white_noise_state
 pytestmark = pytest.mark.gpu
 
 
-def _advance(eq, solver, y0, integ, dt, n, group, **opts):
+def _advance(eq, solver, y0, integ, dt, n, group, counters=None, **opts):
+    """counters: a dict that takes last_group_streams and the stage launches of the advance (test_gpu_explicit_plan.py)"""
     eng = P.HipEngine()
     eng.set_group_envs(group)
     for k, v in opts.items():
@@ -32,8 +33,11 @@ def _advance(eq, solver, y0, integ, dt, n, group, **opts):
     if solver is not None:
         solver.configure_engine(eng, eq)
     eng.set_state(y0)
+    before = eng.stage_launches()
     eng.advance(integ, dt, n)
     out, groups, kernel = eng.get_state(), eng.last_groups(), eng.last_kernel
+    if counters is not None:
+        counters.update(streams=eng.last_group_streams(), launches=eng.stage_launches() - before)
     eng.close()
     return out, groups, kernel
 
