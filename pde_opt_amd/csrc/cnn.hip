@@ -30,32 +30,24 @@
 
 #include "common.hpp"
 #include "nn_device.hpp"
+#include "nn_host.hpp"
 
-enum { CNN_ACT_NONE = -1 };
 constexpr int kCnnMaxLayers = 7;  // convolutions: 1 to 6 hidden layers + the output layer
 
-struct pdeopt_cnn {
-  pdeopt_ctx* ctx = nullptr;
+struct pdeopt_cnn : pdeopt::NativeNet {
   int L = 0;                        // convolutions
   int C[kCnnMaxLayers + 1] = {};    // channels: C[0] = C[L] = 1
   int Cp[kCnnMaxLayers + 1] = {};   // padded to 16
   int act = 0;
-  int64_t n_params = 0;
   int64_t w_off[kCnnMaxLayers + 1] = {}, b_off[kCnnMaxLayers + 1] = {};  // torch order, layer l = 1 ... L
-  std::vector<double> params;       // host copy, torch order
-  bool have_params = false;
-  // packed parameters on the device, in the problem dtype: per layer forward weights, backward weights, bias
-  pdeopt::DeviceBuffer packed;  // grow-only
-  int packed_dtype = -1;
-  bool packed_valid = false;
+  // the packed block, per layer: forward weights, backward weights, bias
   int64_t wf_off[kCnnMaxLayers + 1] = {}, wb_off[kCnnMaxLayers + 1] = {}, pb_off[kCnnMaxLayers + 1] = {};  // elements
   // scratch of the configured shape: a_l and z_l of the hidden layers, two delta fields, the wgrad partials
-  int s_dtype = -1, s_nx = 0, s_ny = 0, s_batch = 0;
+  int s_nx = 0, s_ny = 0, s_batch = 0;
   pdeopt::DeviceBuffer a[kCnnMaxLayers];
   pdeopt::DeviceBuffer z[kCnnMaxLayers];
   pdeopt::DeviceBuffer delta[2];
   pdeopt::DeviceBuffer partial;
-  pdeopt::DeviceBuffer grad;  // [n_params], fp64, accumulates until pdeopt_cnn_grad_read(reset)
 };
 
 namespace pdeopt {
@@ -112,7 +104,7 @@ struct ConvArgs {
   int nx, ny, Cip, Cop, in_scalar, epi;
 };
 
-// One 3 x 3 periodic convolution layer with its epilogue; NT = Cop / 16.  ACT == CNN_ACT_NONE: the scalar epilogues.
+// One 3 x 3 periodic convolution layer with its epilogue; NT = Cop / 16.  ACT == NN_ACT_NONE: the scalar epilogues.
 template <typename T, int ACT, int NT>
 __global__ __launch_bounds__(256) void cnn_conv3x3_kernel(ConvArgs<T> a) {
   __shared__ T s[kRR * kRC * kLd];
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(256) void cnn_conv3x3_kernel(ConvArgs<T> a) {
         if (gi >= nx || gj >= ny) continue;
         const int64_t cell = ((int64_t)b * nx + gi) * ny + gj;
         const T v = acc[m][nt][reg] + bias;
-        if (ACT == CNN_ACT_NONE) {
+        if (ACT == NN_ACT_NONE) {
           if (co == 0) {
             if (a.epi == EPI_SCALAR) a.out[cell] = v;
             else a.out[cell] += v;
@@ -273,23 +265,14 @@ __global__ __launch_bounds__(256) void cnn_wgrad_reduce_kernel(const T* __restri
   }
 }
 
-inline int pad16(int c) { return (c + 15) / 16 * 16; }
 inline int tiles_x(const pdeopt_ctx* ctx) { return (ctx->prob.ny + kPC - 1) / kPC; }
 inline int tiles_y(const pdeopt_ctx* ctx) { return (ctx->prob.nx + kPR - 1) / kPR; }
 // pixel-tile groups of the weight gradient of a layer with `pairs` 16 x 16 blocks: about 512 workgroups in all
 inline int wgrad_groups(int ntiles, int pairs) { return std::min(ntiles, std::max(1, 512 / pairs)); }
 
-void free_scratch(pdeopt_cnn* n) {
-  for (int l = 0; l < kCnnMaxLayers; ++l) n->a[l].reset(), n->z[l].reset();
-  for (DeviceBuffer& d : n->delta) d.reset();
-  n->partial.reset();
-  n->s_dtype = -1;
-}
-
 // parameters in torch order -> the packed device block, in the problem dtype
 template <typename T>
 int upload_packed(pdeopt_cnn* n) {
-  pdeopt_ctx* ctx = n->ctx;
   int64_t total = 0;
   for (int l = 1; l <= n->L; ++l) {
     const int64_t m = 9 * (int64_t)n->Cp[l - 1] * n->Cp[l];
@@ -311,36 +294,13 @@ int upload_packed(pdeopt_cnn* n) {
         }
     for (int o = 0; o < Co; ++o) h[n->pb_off[l] + o] = (T)n->params[n->b_off[l] + o];
   }
-  const size_t bytes = (size_t)total * sizeof(T);
-  if (const int rc = grow_device_buffer(ctx, n->packed, bytes, /*sync_first=*/true)) return rc;
-  // the staging vector dies with this call: the copy is complete for the host when it returns (pageable memory)
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(n->packed.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  n->packed_dtype = ctx->prob.dtype;
-  n->packed_valid = true;
-  return PDEOPT_OK;
+  return net_upload(n, h);
 }
 
-// what every call asks of the ctx's problem and of the fields it is given; packs parameters and sizes the scratch
-int prepare(pdeopt_cnn* n, bool backward, std::initializer_list<const void*> fields) {
+// the scratch of the shape in the handle's key: what a forward pass writes, and for the backward pass z, delta, the partials
+int size_scratch(pdeopt_cnn* n, bool backward) {
   pdeopt_ctx* ctx = n->ctx;
-  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   const pdeopt_problem& p = ctx->prob;
-  if (p.nz > 1 || ctx->comps != 1 || ctx->halo)
-    return fail(ctx, PDEOPT_EINVAL, "the CNN runs on periodic 2-D real fields [batch][nx][ny]");
-  if (p.nx < 4 || p.ny < 4) return fail(ctx, PDEOPT_EINVAL, "the CNN needs a grid of at least 4 x 4 (got %d x %d)", p.nx, p.ny);
-  if (!n->have_params) return fail(ctx, PDEOPT_ESTATE, "pdeopt_cnn_set_params has not been called");
-  for (const void* f : fields)
-    if (!f || (uintptr_t)f % ctx->esize)
-      return fail(ctx, PDEOPT_EINVAL, "field pointer %p: device fields are [batch][nx][ny] in the problem dtype, aligned to it", f);
-  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (!n->packed_valid || n->packed_dtype != p.dtype)
-    if (const int rc = with_dtype(ctx, [&](auto t) { return upload_packed<decltype(t)>(n); })) return rc;
-  if (n->s_dtype != p.dtype || n->s_nx != p.nx || n->s_ny != p.ny || n->s_batch != p.batch) {
-    if (n->s_dtype >= 0) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    free_scratch(n);
-    n->s_dtype = p.dtype, n->s_nx = p.nx, n->s_ny = p.ny, n->s_batch = p.batch;
-  }
   const size_t cells = (size_t)p.batch * p.nx * p.ny;
   int rc = 0;
   int cmax = 16;
@@ -380,15 +340,15 @@ int launch_conv_nt(pdeopt_ctx* ctx, const ConvArgs<T>& a) {
 template <typename T>
 int launch_conv(pdeopt_ctx* ctx, int act, const ConvArgs<T>& a) {
   if (a.epi == EPI_SCALAR || a.epi == EPI_SCALAR_ADD) {
-    hipLaunchKernelGGL((cnn_conv3x3_kernel<T, CNN_ACT_NONE, 1>), dim3(tiles_x(ctx), tiles_y(ctx), ctx->prob.batch), dim3(256), 0,
+    hipLaunchKernelGGL((cnn_conv3x3_kernel<T, NN_ACT_NONE, 1>), dim3(tiles_x(ctx), tiles_y(ctx), ctx->prob.batch), dim3(256), 0,
                        ctx->stream, a);
     ctx->n_stage_launches++;
     PDEOPT_HIP_CHECK(ctx, hipGetLastError());
     return PDEOPT_OK;
   }
-  if (act == PDEOPT_CNN_GELU) return launch_conv_nt<T, PDEOPT_CNN_GELU>(ctx, a);
-  if (act == PDEOPT_CNN_GELU_TANH) return launch_conv_nt<T, PDEOPT_CNN_GELU_TANH>(ctx, a);
-  return launch_conv_nt<T, PDEOPT_CNN_TANH>(ctx, a);
+  if (act == PDEOPT_CNN_GELU) return launch_conv_nt<T, NN_ACT_GELU>(ctx, a);
+  if (act == PDEOPT_CNN_GELU_TANH) return launch_conv_nt<T, NN_ACT_GELU_TANH>(ctx, a);
+  return launch_conv_nt<T, NN_ACT_TANH>(ctx, a);
 }
 
 // mu = N(u), or the hidden layers alone when mu == nullptr; keep_z: their z_l stay in the handle's scratch for the
@@ -464,6 +424,28 @@ int backward(pdeopt_cnn* n, const void* u, const void* gmu, void* lam) {
   return PDEOPT_OK;
 }
 
+// the CNN as the shared steps of nn_host.hpp see it
+struct CnnFamily {
+  static constexpr const char *forward_kernels = "cnn_conv3x3", *vjp_kernels = "cnn_conv3x3+cnn_wgrad";
+  static int refuse(pdeopt_cnn* n, const pdeopt_problem& p) {
+    return p.nx >= 4 && p.ny >= 4 ? PDEOPT_OK : fail(n->ctx, PDEOPT_EINVAL, "the CNN needs a grid of at least 4 x 4 (got %d x %d)", p.nx, p.ny);
+  }
+  static bool keyed_for(const pdeopt_cnn* n, const pdeopt_problem& p) {
+    return n->s_dtype == p.dtype && n->s_nx == p.nx && n->s_ny == p.ny && n->s_batch == p.batch;
+  }
+  static void rekey(pdeopt_cnn* n, const pdeopt_problem& p) {
+    for (int l = 0; l < kCnnMaxLayers; ++l) n->a[l].reset(), n->z[l].reset();
+    for (DeviceBuffer& d : n->delta) d.reset();
+    n->partial.reset();
+    n->s_dtype = p.dtype, n->s_nx = p.nx, n->s_ny = p.ny, n->s_batch = p.batch;
+  }
+  static int size_workspace(pdeopt_cnn* n, bool backward) { return size_scratch(n, backward); }
+  // in the problem dtype, t = T(): pack(t, n), forward(t, n, u, mu, keep_z), backward(t, n, u, gmu, lam)
+  static constexpr auto pack = [](auto t, auto... a) { return upload_packed<decltype(t)>(a...); };
+  static constexpr auto forward = [](auto t, auto... a) { return pdeopt::forward<decltype(t)>(a...); };
+  static constexpr auto backward = [](auto t, auto... a) { return pdeopt::backward<decltype(t)>(a...); };
+};
+
 }  // namespace
 }  // namespace pdeopt
 
@@ -485,7 +467,7 @@ int pdeopt_cnn_create(pdeopt_ctx* ctx, int n_layers, const int* channels, int ac
   if (activation != PDEOPT_CNN_GELU && activation != PDEOPT_CNN_GELU_TANH && activation != PDEOPT_CNN_TANH)
     return fail(ctx, PDEOPT_EINVAL, "activation %d: supported are gelu (erf form), gelu (tanh form) and tanh", activation);
   pdeopt_cnn* n = new pdeopt_cnn();
-  n->ctx = ctx;
+  n->what = "CNN";
   n->L = n_layers;
   n->act = activation;
   for (int l = 0; l <= n_layers; ++l) n->C[l] = channels[l], n->Cp[l] = pad16(channels[l]);
@@ -494,76 +476,19 @@ int pdeopt_cnn_create(pdeopt_ctx* ctx, int n_layers, const int* channels, int ac
     n->b_off[l] = n->n_params + 9 * (int64_t)n->C[l] * n->C[l - 1];
     n->n_params = n->b_off[l] + n->C[l];
   }
-  const auto bail = [&](hipError_t e, const char* what) {
-    delete n;
-    return fail(ctx, PDEOPT_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return bail(e, "hipSetDevice");
-  if (const int rc = ensure_buffer(ctx, n->grad, n->n_params * sizeof(double))) {
-    delete n;
-    return rc;
-  }
-  if ((e = hipMemsetAsync(n->grad.as<double>(), 0, n->n_params * sizeof(double), ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-  *out = n;
-  return PDEOPT_OK;
+  return net_open(ctx, n, out);
 }
 
-int pdeopt_cnn_set_params(pdeopt_cnn* n, const double* params, int64_t count) {
-  if (!n) return PDEOPT_EINVAL;
-  if (!params || count != n->n_params)
-    return fail(n->ctx, PDEOPT_EINVAL, "the CNN has %lld parameters (got %lld)", (long long)n->n_params, (long long)count);
-  n->params.assign(params, params + count);
-  n->have_params = true;
-  n->packed_valid = false;  // packed in the problem dtype by the next forward / vjp
-  return PDEOPT_OK;
-}
+int pdeopt_cnn_set_params(pdeopt_cnn* n, const double* params, int64_t count) { return net_set_params(n, params, count); }
 
-int pdeopt_cnn_forward(pdeopt_cnn* n, const void* u_dev, void* mu_dev) {
-  if (!n) return PDEOPT_EINVAL;
-  pdeopt_ctx* ctx = n->ctx;
-  if (const int rc = prepare(n, false, {u_dev, mu_dev})) return rc;
-  ctx->last_kernel = "cnn_conv3x3";
-  return with_dtype(ctx, [&](auto t) { return forward<decltype(t)>(n, u_dev, mu_dev, false); });
-}
+int pdeopt_cnn_forward(pdeopt_cnn* n, const void* u_dev, void* mu_dev) { return net_forward<CnnFamily>(n, u_dev, mu_dev); }
 
 int pdeopt_cnn_vjp(pdeopt_cnn* n, const void* u_dev, const void* gmu_dev, void* lam_dev) {
-  if (!n) return PDEOPT_EINVAL;
-  pdeopt_ctx* ctx = n->ctx;
-  if (const int rc = prepare(n, true, {u_dev, gmu_dev, lam_dev})) return rc;
-  const auto overlap = [&](const void* a, const void* b) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + ctx->total_bytes && y < x + ctx->total_bytes;
-  };
-  if (overlap(lam_dev, u_dev) || overlap(lam_dev, gmu_dev))
-    return fail(ctx, PDEOPT_EINVAL, "lam_dev is written: it must not overlap u_dev or gmu_dev");
-  ctx->last_kernel = "cnn_conv3x3+cnn_wgrad";
-  return with_dtype(ctx, [&](auto t) {
-    using T = decltype(t);
-    // the value mu itself is not needed: the forward pass stops below the last layer
-    if (const int rc = forward<T>(n, u_dev, nullptr, true)) return rc;
-    return backward<T>(n, u_dev, gmu_dev, lam_dev);
-  });
+  return net_vjp<CnnFamily>(n, u_dev, gmu_dev, lam_dev);
 }
 
-int pdeopt_cnn_grad_read(pdeopt_cnn* n, double* out, int64_t count, int reset) {
-  if (!n) return PDEOPT_EINVAL;
-  pdeopt_ctx* ctx = n->ctx;
-  if (!out || count != n->n_params)
-    return fail(ctx, PDEOPT_EINVAL, "the CNN has %lld parameters (got %lld)", (long long)n->n_params, (long long)count);
-  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, n->grad.as<double>(), count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(n->grad.as<double>(), 0, count * sizeof(double), ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return PDEOPT_OK;
-}
+int pdeopt_cnn_grad_read(pdeopt_cnn* n, double* out, int64_t count, int reset) { return net_grad_read(n, out, count, reset); }
 
-int pdeopt_cnn_destroy(pdeopt_cnn* n) {
-  if (!n) return PDEOPT_OK;
-  (void)hipSetDevice(n->ctx->device);
-  if (n->ctx->stream) (void)hipStreamSynchronize(n->ctx->stream);
-  delete n;
-  return PDEOPT_OK;
-}
+int pdeopt_cnn_destroy(pdeopt_cnn* n) { return net_close(n); }
 
 }  // extern "C"

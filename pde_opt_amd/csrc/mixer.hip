@@ -33,14 +33,13 @@
 
 #include "common.hpp"
 #include "nn_device.hpp"
+#include "nn_host.hpp"
 
 constexpr int kMixMaxBlocks = 8;
 
-struct pdeopt_mixer {
-  pdeopt_ctx* ctx = nullptr;
+struct pdeopt_mixer : pdeopt::NativeNet {
   int nx = 0, ny = 0, ps = 0, C = 0, Mp = 0, Mh = 0, K = 0, act = 0;
   int pw = 0, P = 0, Q = 0;  // patches per row of the patch grid, patches, pixels per patch
-  int64_t n_params = 0;
   // offsets in the flat parameter vector
   int64_t win = 0, bin = 0, wout = 0, bout = 0, gf = 0, bef = 0;
   struct Block {
@@ -48,28 +47,19 @@ struct pdeopt_mixer {
     int64_t f1, r1, f2, r2, f3, r3, f4, r4;  // packed weights: forward and backward-data (reverse) products
   } blk[kMixMaxBlocks] = {};
   int64_t f_in = 0, r_in = 0, f_out = 0, r_out = 0;
-  std::vector<double> params;
-  bool have_params = false;
-  // device copy in the problem dtype: the flat vector as it is, then the packed weights
-  pdeopt::DeviceBuffer packed;  // grow-only
-  int64_t packed_elems = 0;
-  int packed_dtype = -1;
-  bool packed_valid = false;
+  int64_t packed_elems = 0;  // the packed block: the flat vector as it is, then the packed weights
   // workspace of the configured dtype and batch
-  int s_dtype = -1, s_batch = 0;
+  int s_batch = 0;
   pdeopt::DeviceBuffer Y[2 * kMixMaxBlocks + 1];
   pdeopt::DeviceBuffer H1[kMixMaxBlocks], Z1[kMixMaxBlocks], H2[kMixMaxBlocks], Z2[kMixMaxBlocks];
   pdeopt::DeviceBuffer DY, DN, DZ;
   pdeopt::DeviceBuffer stats;  // doubles [2 K + 1 norms][batch][mean, rstd], then [batch][2] sums of a layer norm's backward pass
-  pdeopt::DeviceBuffer grad;   // doubles [n_params], accumulates until pdeopt_mixer_grad_read(reset)
 };
 
 namespace pdeopt {
 namespace {
 
 constexpr double kLnEps = 1e-5;
-
-inline int pad16(int c) { return (c + 15) / 16 * 16; }
 
 // An activation as a matrix (i0, i1) of n0 x n1 real entries per field: two strides, or the (patch, pixel-of-patch)
 // view of a field [nx][ny]; gamma != nullptr: the layer norm of its field is applied to what is loaded
@@ -312,14 +302,6 @@ __global__ __launch_bounds__(256) void mixer_sum_kernel(const T* __restrict__ g,
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 
-void free_workspace(pdeopt_mixer* n) {
-  for (DeviceBuffer& y : n->Y) y.reset();
-  for (int k = 0; k < kMixMaxBlocks; ++k) n->H1[k].reset(), n->Z1[k].reset(), n->H2[k].reset(), n->Z2[k].reset();
-  n->DY.reset(), n->DN.reset(), n->DZ.reset();
-  n->stats.reset();
-  n->s_dtype = -1;
-}
-
 // offsets of the flat vector and of the packed weights behind it
 void lay_out(pdeopt_mixer* n) {
   const int64_t C = n->C, P = n->P, Q = n->Q, Mp = n->Mp, Mh = n->Mh;
@@ -363,7 +345,6 @@ void pack_pair(std::vector<T>& h, const double* w, int O, int I, bool stored_io,
 
 template <typename T>
 int upload_packed(pdeopt_mixer* n) {
-  pdeopt_ctx* ctx = n->ctx;
   std::vector<T> h((size_t)n->packed_elems, T(0));
   for (int64_t q = 0; q < n->n_params; ++q) h[q] = (T)n->params[q];
   const double* p = n->params.data();
@@ -376,38 +357,13 @@ int upload_packed(pdeopt_mixer* n) {
     pack_pair<T>(h, p + b.w3, n->Mh, n->C, false, b.f3, b.r3);
     pack_pair<T>(h, p + b.w4, n->C, n->Mh, false, b.f4, b.r4);
   }
-  const size_t bytes = (size_t)n->packed_elems * sizeof(T);
-  if (const int rc = grow_device_buffer(ctx, n->packed, bytes, /*sync_first=*/true)) return rc;
-  // the staging vector dies with this call: the copy is complete for the host when it returns (pageable memory)
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(n->packed.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  n->packed_dtype = ctx->prob.dtype;
-  n->packed_valid = true;
-  return PDEOPT_OK;
+  return net_upload(n, h);
 }
 
-// what every call asks of the ctx's problem and of the fields it is given; packs parameters and sizes the workspace
-int prepare(pdeopt_mixer* n, bool backward, std::initializer_list<const void*> fields) {
+// the workspace of the batch in the handle's key: what a forward pass writes, and for the backward pass z and the cotangents
+int size_workspace(pdeopt_mixer* n, bool backward) {
   pdeopt_ctx* ctx = n->ctx;
-  if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
   const pdeopt_problem& p = ctx->prob;
-  if (p.nz > 1 || ctx->comps != 1 || ctx->halo)
-    return fail(ctx, PDEOPT_EINVAL, "the mixer runs on periodic 2-D real fields [batch][nx][ny]");
-  if (p.nx != n->nx || p.ny != n->ny)
-    return fail(ctx, PDEOPT_EINVAL, "the mixer was created for a %d x %d grid, the problem is now %d x %d: its parameter shapes "
-                "depend on the grid", n->nx, n->ny, p.nx, p.ny);
-  if (!n->have_params) return fail(ctx, PDEOPT_ESTATE, "pdeopt_mixer_set_params has not been called");
-  for (const void* f : fields)
-    if (!f || (uintptr_t)f % ctx->esize)
-      return fail(ctx, PDEOPT_EINVAL, "field pointer %p: device fields are [batch][nx][ny] in the problem dtype, aligned to it", f);
-  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (!n->packed_valid || n->packed_dtype != p.dtype)
-    if (const int rc = with_dtype(ctx, [&](auto t) { return upload_packed<decltype(t)>(n); })) return rc;
-  if (n->s_dtype != p.dtype || n->s_batch != p.batch) {
-    if (n->s_dtype >= 0) PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    free_workspace(n);
-    n->s_dtype = p.dtype, n->s_batch = p.batch;
-  }
   const size_t B = p.batch, cp = (size_t)n->C * n->P, cm = (size_t)n->C * n->Mp, pm = (size_t)n->P * n->Mh, es = ctx->esize;
   int rc = 0;
   for (int j = 0; j <= 2 * n->K; ++j)
@@ -614,6 +570,29 @@ int backward(pdeopt_mixer* n, const void* u, const void* gmu, void* lam) {
   return launch_gemm(n, a);
 }
 
+// the mixer as the shared steps of nn_host.hpp see it
+struct MixerFamily {
+  static constexpr const char *forward_kernels = "mixer_gemm+mixer_stats", *vjp_kernels = "mixer_gemm+mixer_wgrad";
+  static int refuse(pdeopt_mixer* n, const pdeopt_problem& p) {
+    if (p.nx == n->nx && p.ny == n->ny) return PDEOPT_OK;
+    return fail(n->ctx, PDEOPT_EINVAL, "the mixer was created for a %d x %d grid, the problem is now %d x %d: its parameter shapes "
+                "depend on the grid", n->nx, n->ny, p.nx, p.ny);
+  }
+  static bool keyed_for(const pdeopt_mixer* n, const pdeopt_problem& p) { return n->s_dtype == p.dtype && n->s_batch == p.batch; }
+  static void rekey(pdeopt_mixer* n, const pdeopt_problem& p) {
+    for (DeviceBuffer& y : n->Y) y.reset();
+    for (int k = 0; k < kMixMaxBlocks; ++k) n->H1[k].reset(), n->Z1[k].reset(), n->H2[k].reset(), n->Z2[k].reset();
+    n->DY.reset(), n->DN.reset(), n->DZ.reset();
+    n->stats.reset();
+    n->s_dtype = p.dtype, n->s_batch = p.batch;
+  }
+  static int size_workspace(pdeopt_mixer* n, bool backward) { return pdeopt::size_workspace(n, backward); }
+  // in the problem dtype, t = T(): pack(t, n), forward(t, n, u, mu, keep_z), backward(t, n, u, gmu, lam)
+  static constexpr auto pack = [](auto t, auto... a) { return upload_packed<decltype(t)>(a...); };
+  static constexpr auto forward = [](auto t, auto... a) { return pdeopt::forward<decltype(t)>(a...); };
+  static constexpr auto backward = [](auto t, auto... a) { return pdeopt::backward<decltype(t)>(a...); };
+};
+
 }  // namespace
 }  // namespace pdeopt
 
@@ -643,80 +622,23 @@ int pdeopt_mixer_create(pdeopt_ctx* ctx, int patch, int hidden, int mix_patch, i
       activation != PDEOPT_MIXER_TANH)
     return fail(ctx, PDEOPT_EINVAL, "activation %d: supported are relu, gelu (erf form), gelu (tanh form) and tanh", activation);
   pdeopt_mixer* n = new pdeopt_mixer();
-  n->ctx = ctx;
+  n->what = "mixer";
   n->nx = p.nx, n->ny = p.ny, n->ps = patch, n->C = hidden, n->Mp = mix_patch, n->Mh = mix_hidden, n->K = blocks, n->act = activation;
   n->pw = p.ny / patch, n->P = (int)patches, n->Q = patch * patch;
   lay_out(n);
-  const auto bail = [&](hipError_t e, const char* what) {
-    delete n;
-    return fail(ctx, PDEOPT_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return bail(e, "hipSetDevice");
-  if (const int rc = ensure_buffer(ctx, n->grad, n->n_params * sizeof(double))) {
-    delete n;
-    return rc;
-  }
-  if ((e = hipMemsetAsync(n->grad.as<double>(), 0, n->n_params * sizeof(double), ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-  *out = n;
-  return PDEOPT_OK;
+  return net_open(ctx, n, out);
 }
 
-int pdeopt_mixer_set_params(pdeopt_mixer* n, const double* params, int64_t count) {
-  if (!n) return PDEOPT_EINVAL;
-  if (!params || count != n->n_params)
-    return fail(n->ctx, PDEOPT_EINVAL, "the mixer has %lld parameters (got %lld)", (long long)n->n_params, (long long)count);
-  n->params.assign(params, params + count);
-  n->have_params = true;
-  n->packed_valid = false;  // packed in the problem dtype by the next forward / vjp
-  return PDEOPT_OK;
-}
+int pdeopt_mixer_set_params(pdeopt_mixer* n, const double* params, int64_t count) { return net_set_params(n, params, count); }
 
-int pdeopt_mixer_forward(pdeopt_mixer* n, const void* u_dev, void* mu_dev) {
-  if (!n) return PDEOPT_EINVAL;
-  pdeopt_ctx* ctx = n->ctx;
-  if (const int rc = prepare(n, false, {u_dev, mu_dev})) return rc;
-  ctx->last_kernel = "mixer_gemm+mixer_stats";
-  return with_dtype(ctx, [&](auto t) { return forward<decltype(t)>(n, u_dev, mu_dev, false); });
-}
+int pdeopt_mixer_forward(pdeopt_mixer* n, const void* u_dev, void* mu_dev) { return net_forward<MixerFamily>(n, u_dev, mu_dev); }
 
 int pdeopt_mixer_vjp(pdeopt_mixer* n, const void* u_dev, const void* gmu_dev, void* lam_dev) {
-  if (!n) return PDEOPT_EINVAL;
-  pdeopt_ctx* ctx = n->ctx;
-  if (const int rc = prepare(n, true, {u_dev, gmu_dev, lam_dev})) return rc;
-  const auto overlap = [&](const void* a, const void* b) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + ctx->total_bytes && y < x + ctx->total_bytes;
-  };
-  if (overlap(lam_dev, u_dev) || overlap(lam_dev, gmu_dev))
-    return fail(ctx, PDEOPT_EINVAL, "lam_dev is written: it must not overlap u_dev or gmu_dev");
-  ctx->last_kernel = "mixer_gemm+mixer_wgrad";
-  return with_dtype(ctx, [&](auto t) {
-    using T = decltype(t);
-    // the value mu itself is not needed: the forward pass stops below conv_out
-    if (const int rc = forward<T>(n, u_dev, nullptr, true)) return rc;
-    return backward<T>(n, u_dev, gmu_dev, lam_dev);
-  });
+  return net_vjp<MixerFamily>(n, u_dev, gmu_dev, lam_dev);
 }
 
-int pdeopt_mixer_grad_read(pdeopt_mixer* n, double* out, int64_t count, int reset) {
-  if (!n) return PDEOPT_EINVAL;
-  pdeopt_ctx* ctx = n->ctx;
-  if (!out || count != n->n_params)
-    return fail(ctx, PDEOPT_EINVAL, "the mixer has %lld parameters (got %lld)", (long long)n->n_params, (long long)count);
-  PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, n->grad.as<double>(), count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (reset) PDEOPT_HIP_CHECK(ctx, hipMemsetAsync(n->grad.as<double>(), 0, count * sizeof(double), ctx->stream));
-  PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return PDEOPT_OK;
-}
+int pdeopt_mixer_grad_read(pdeopt_mixer* n, double* out, int64_t count, int reset) { return net_grad_read(n, out, count, reset); }
 
-int pdeopt_mixer_destroy(pdeopt_mixer* n) {
-  if (!n) return PDEOPT_OK;
-  (void)hipSetDevice(n->ctx->device);
-  if (n->ctx->stream) (void)hipStreamSynchronize(n->ctx->stream);
-  delete n;
-  return PDEOPT_OK;
-}
+int pdeopt_mixer_destroy(pdeopt_mixer* n) { return net_close(n); }
 
 }  // extern "C"
