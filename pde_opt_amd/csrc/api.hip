@@ -65,11 +65,7 @@ void free_fields(pdeopt_ctx* ctx) {
   ctx->fieldmu_coef.reset();
   ctx->fieldmu_coef_slots = 0;
   for (auto& a : ctx->aux) a = AuxField{};
-  spectral_destroy(ctx);
-  strang_fused_destroy(ctx);
-  sens_destroy(ctx);
-  bv_destroy(ctx);
-  implicit_destroy(ctx);
+  ctx->features.clear();
   sk_drop(ctx);  // the shell tables belong to one grid
   graph_destroy(ctx);
   ctx->tsit5_pending = false;
@@ -465,7 +461,7 @@ int pdeopt_set_aux(pdeopt_ctx* ctx, int which, const void* host, int per_env) {
   const size_t bytes = a.dev.bytes();
   a.fn = nullptr;  // a static upload replaces a time-dependent source
   a.loaded = false;
-  spectral_invalidate(ctx);  // multipliers derived from the old aux field are stale
+  ctx->features.invalidate_all();  // multipliers derived from the old aux field are stale
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(a.dev.get(), host, bytes, hipMemcpyHostToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;

@@ -497,7 +497,7 @@ __global__ __launch_bounds__(64) void bvsens_finish_kernel(const double* __restr
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct BvState {
+struct BvState : Feature {
   double alpha = 0.5;
   int mode = 0;
   bool set = false;
@@ -509,12 +509,13 @@ struct BvState {
   DeviceBuffer dpart;
   DeviceBuffer dv;
 };
+// nullptr until pdeopt_set_bv_params
+inline BvState* bv_of(const pdeopt_ctx* ctx) { return ctx->features.get<BvState>(FS_BV); }
 
 namespace {
 
 int bv_ensure(pdeopt_ctx* ctx) {
-  if (!ctx->bv) ctx->bv = new BvState;
-  BvState* st = ctx->bv;
+  BvState* st = &ctx->features.ensure<BvState>(FS_BV);
   const pdeopt_problem& p = ctx->prob;
   const int nwg = ((p.nx + kBvRows - 1) / kBvRows) * ((p.ny + kBvCols - 1) / kBvCols);
   if (st->par && st->nwg == nwg && st->batch == p.batch) return PDEOPT_OK;
@@ -537,7 +538,7 @@ int bv_ensure(pdeopt_ctx* ctx) {
 int bv_check(pdeopt_ctx* ctx) {
   const pdeopt_problem& p = ctx->prob;
   if (!bv_equation(p.equation)) return fail(ctx, PDEOPT_EINVAL, "equation %d is not a Butler-Volmer equation", p.equation);
-  if (!ctx->bv || !ctx->bv->set || ctx->bv->batch != p.batch)
+  if (!bv_of(ctx) || !bv_of(ctx)->set || bv_of(ctx)->batch != p.batch)
     return fail(ctx, PDEOPT_ESTATE, "the Butler-Volmer equations need pdeopt_set_bv_params after pdeopt_configure");
   if (p.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV && !ctx->aux[PDEOPT_AUX_SBM_PSI].dev)
     return fail(ctx, PDEOPT_ESTATE, "the smoothed-boundary Butler-Volmer equation needs the SBM_PSI aux field");
@@ -548,7 +549,7 @@ int bv_check(pdeopt_ctx* ctx) {
 
 template <typename T>
 BvArgs<T> bv_args(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
-  BvState* st = ctx->bv;
+  BvState* st = bv_of(ctx);
   BvArgs<T> a{};
   a.s = s;
   a.mu = ctx->KS.as<T>() + (int64_t)w.lo * s.g.bstride;
@@ -584,7 +585,7 @@ int launch_bv_stage(pdeopt_ctx* ctx, const Window& w, const StageArgs<T>& s) {
   if ((rc = bv_check(ctx))) return rc;
   const bool sbm = ctx->prob.equation == PDEOPT_EQ_ALLEN_CAHN_SBM_BV;
   const dim3 grid = bv_grid(ctx, w.n), block(64, 4, 1);
-  if (ctx->bv->mode == 1) {
+  if (bv_of(ctx)->mode == 1) {
     if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
     const BvArgs<T> a = bv_args<T>(ctx, w, s);
     bv_launch_pass1<T>(ctx, w, a);
@@ -609,9 +610,9 @@ int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env
   if (mode != 0 && mode != 1) return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer mode %d: 0 = voltage given, 1 = constant current", mode);
   if (!std::isfinite(alpha)) return fail(ctx, PDEOPT_EINVAL, "Butler-Volmer symmetry factor alpha must be finite");
   int rc;
-  const void* const par_before = ctx->bv ? ctx->bv->par.get() : nullptr;
+  const void* const par_before = bv_of(ctx) ? bv_of(ctx)->par.get() : nullptr;
   if ((rc = bv_ensure(ctx))) return rc;
-  BvState* st = ctx->bv;
+  BvState* st = bv_of(ctx);
   // alpha, the mode and the buffers are kernel arguments of a captured substep graph (the per-environment values are not)
   if (st->par.get() != par_before || st->alpha != alpha || st->mode != mode) graph_destroy(ctx);
   st->alpha = alpha;
@@ -627,7 +628,7 @@ int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env
 int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, bool recompute) {
   int rc;
   if ((rc = bv_check(ctx))) return rc;
-  BvState* st = ctx->bv;
+  BvState* st = bv_of(ctx);
   if (recompute) {
     if (st->mode != 1) return fail(ctx, PDEOPT_EINVAL, "pdeopt_bv_voltage solves the constant-current constraint: set mode 1");
     if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
@@ -670,7 +671,7 @@ int bv_sens_check(pdeopt_ctx* ctx, const BvSensSpec& sp) {
 
 template <typename T>
 int bv_sens_args(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out, BvSensArgs<T>* a) {
-  BvState* st = ctx->bv;
+  BvState* st = bv_of(ctx);
   int rc;
   if ((rc = ensure_buffer(ctx, ctx->KS, ctx->total_bytes))) return rc;
   // a block that is too small is freed after the stream's work, which may still use it -- and so may a captured graph
@@ -715,7 +716,7 @@ void bv_sens_launch_tiles(pdeopt_ctx* ctx, const BvSensArgs<T>& a) {
 int bv_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out) {
   int rc;
   if ((rc = bv_sens_check(ctx, sp))) return rc;
-  const bool current = ctx->bv->mode == 1;
+  const bool current = bv_of(ctx)->mode == 1;
   rc = with_dtype(ctx, [&](auto tag) -> int {
     using T = decltype(tag);
     BvSensArgs<T> a;
@@ -740,7 +741,7 @@ int bv_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* 
 int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out) {
   int rc;
   if ((rc = bv_sens_check(ctx, sp))) return rc;
-  BvState* st = ctx->bv;
+  BvState* st = bv_of(ctx);
   if (st->mode != 1) return fail(ctx, PDEOPT_EINVAL, "pdeopt_sens_bv_voltage differentiates the constant-current constraint: set mode 1");
   rc = with_dtype(ctx, [&](auto tag) -> int {
     using T = decltype(tag);
@@ -762,15 +763,10 @@ int bv_sens_voltage(pdeopt_ctx* ctx, const BvSensSpec& sp, double* host_out) {
   return PDEOPT_OK;
 }
 
-bool bv_params_set(const pdeopt_ctx* ctx) { return ctx->bv && ctx->bv->set && ctx->bv->batch == ctx->prob.batch; }
+bool bv_params_set(const pdeopt_ctx* ctx) { return bv_of(ctx) && bv_of(ctx)->set && bv_of(ctx)->batch == ctx->prob.batch; }
 
 bool bv_time_dependent(const pdeopt_ctx* ctx) {
-  return bv_equation(ctx->prob.equation) && ctx->bv && ctx->bv->mode == 0 && (ctx->time_fn != nullptr || !ctx->tt_times.empty());
-}
-
-void bv_destroy(pdeopt_ctx* ctx) {
-  delete ctx->bv;
-  ctx->bv = nullptr;
+  return bv_equation(ctx->prob.equation) && bv_of(ctx) && bv_of(ctx)->mode == 0 && (ctx->time_fn != nullptr || !ctx->tt_times.empty());
 }
 
 }  // namespace pdeopt

@@ -13,6 +13,7 @@
 
 #include "../../include/pdeopt_hip.h"
 #include "device_buffer.hpp"
+#include "feature_slot.hpp"
 
 namespace pdeopt {
 
@@ -123,15 +124,6 @@ struct AuxField {
 };
 
 struct CommState;    // RCCL / in-process communicator + strip buffers of the decomposed driver (comm.hip)
-struct Spectral;     // rocFFT plans + work buffers (spectral.hip)
-struct StrangFused;  // LDS-FFT split-step state (strang_fused.hip)
-struct Sens;         // forward-mode sensitivity configuration + Gauss-Newton buffers (sens.hip)
-struct GpeAdjoint;   // work fields + multiplier of the Strang step's adjoint (gpe_adjoint.hip)
-struct GpeRot;       // tables + work fields of the rotating-frame ADI split step (gpe_rot.hip)
-struct GpeObs;       // tables + partial sums of the GPE observables (gpe_obs.hip)
-struct GpeRotAdjoint;  // work fields + tables of the rotating-frame split step's adjoint, frozen or stirred (gpe_rot_adjoint.hip)
-struct BvState;      // parameters, partial sums and voltages of the Butler-Volmer equations (butler_volmer.hip)
-struct Implicit;     // tolerances, Krylov workspace and small systems of the implicit Euler step (implicit.hip)
 
 // what a captured substep graph depends on (explicit integrators, stencil.hip)
 struct GraphStructure {
@@ -242,20 +234,14 @@ struct pdeopt_ctx {
   pdeopt::DeviceBuffer sk_dev;
   std::vector<pdeopt::PinnedBuffer> host_allocs;  // pdeopt_host_alloc
   pdeopt::CommState* comm = nullptr;
-  pdeopt::Spectral* spectral = nullptr;
-  pdeopt::StrangFused* strang_fused = nullptr;
-  pdeopt::Sens* sens = nullptr;
-  pdeopt::GpeAdjoint* gpe_adjoint = nullptr;
+  // The feature states (feature_slot.hpp names them; each is defined in the file that uses it and owns its buffers).  A
+  // state lives from its first use to the next shape-changing pdeopt_configure or to pdeopt_ctx_destroy (free_fields,
+  // api.hip); a same-shape configure keeps it, and pdeopt_set_aux invalidates the multipliers the states cache.
+  pdeopt::FeatureTable features;
   // rotating-frame GPE (pdeopt_set_gpe_rotation): coordinates of cell (0, 0); Omega itself lives in EnvParams
   bool rot_set = false;
   bool rot_any_rate = false;  // some environment's gpe_omega_rate is not 0: the step runs the stirred kernels of gpe_rot.hip
   double rot_x_first = 0.0, rot_y_first = 0.0;
-  pdeopt::GpeRot* gpe_rot = nullptr;
-  pdeopt::GpeObs* gpe_obs = nullptr;
-  pdeopt::GpeRotAdjoint* gpe_rot_adjoint = nullptr;
-  pdeopt::GpeRotAdjoint* gpe_rot_stir_adjoint = nullptr;  // the stirred entry point's own (other partial blocks)
-  pdeopt::BvState* bv = nullptr;  // pdeopt_set_bv_params; owns its buffers, deleted by free_fields
-  pdeopt::Implicit* implicit = nullptr;  // pdeopt_implicit_configure; owns its workspace, deleted by free_fields
   // pdeopt_fieldmu_adjoint_step_coef: fp64 partial sums of the mobility's coefficient gradient, one slot per
   // (trajectory, tile, coefficient); reset by free_fields, zeroed by pdeopt_configure
   pdeopt::DeviceBuffer fieldmu_coef;
@@ -440,8 +426,6 @@ int detect_vortices(pdeopt_ctx* ctx, double amp_thresh, double tol, int env_firs
 int advance_imex(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
 int rhs_fourier(pdeopt_ctx* ctx, const void* in, void* out);
 int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
-void spectral_destroy(pdeopt_ctx* ctx);
-void spectral_invalidate(pdeopt_ctx* ctx);
 // jit.hip: do these closure bodies compile (hiprtc, gfx950)?
 int jit_check(int dtype, const char* mu_body, const char* mob_body, char* log_out, int log_cap);
 // strang_fused.hip
@@ -484,21 +468,12 @@ int spectral_fetch_complex_aux(pdeopt_ctx* ctx, int which, std::vector<std::comp
 // one unnormalised complex transform along ONE axis (0: x, lines of stride ny; 1: y, contiguous lines) of a
 // whole-batch field [batch][nx][ny], in place, on the ctx's stream: rocFFT batched 1-D plans, any grid
 int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf);
-// gpe_rot.hip: the rotating-frame ADI split step (PDEOPT_INT_STRANG_ROT); GpeRot owns its buffers, spectral_destroy deletes it
+// gpe_rot.hip: the rotating-frame ADI split step (PDEOPT_INT_STRANG_ROT)
 int advance_strang_rot(pdeopt_ctx* ctx, double t0, double dt, int64_t n);
-void gpe_rot_invalidate(pdeopt_ctx* ctx);
-void gpe_rot_destroy(pdeopt_ctx* ctx);
-// gpe_rot_adjoint.hip: the adjoint of that step; its state owns its buffers and is deleted by spectral_destroy too
-void gpe_rot_adjoint_invalidate(pdeopt_ctx* ctx);
-void gpe_rot_adjoint_destroy(pdeopt_ctx* ctx);
-// gpe_rot_adjoint.hip too: the adjoint of the stirred, ramped step (spots and Omega(t)); buffers as above
-void gpe_rot_stir_adjoint_invalidate(pdeopt_ctx* ctx);
-void gpe_rot_stir_adjoint_destroy(pdeopt_ctx* ctx);
 // gpe_obs.hip: energy terms, angular momentum and moments of the resident GPE state, [env_count][PDEOPT_GPE_OBS_COUNT]
-// doubles; GpeObs owns its buffers, spectral_destroy deletes it
+// doubles
 int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
                     double* host_out);
-void gpe_obs_destroy(pdeopt_ctx* ctx);
 // pf_obs.hip: mass, free energy, chemical-potential moments and dissipation of the resident phase-field state (periodic
 // CH, AC, CH-3D with finite differences), [env_count][PDEOPT_PF_OBS_COUNT] doubles; refuses what it does not cover
 int pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
@@ -507,14 +482,10 @@ int pf_observables(pdeopt_ctx* ctx, int env_first, int env_count, double* host_o
 int sk_configure(pdeopt_ctx* ctx, const double* t0, const double* t1, const double* t2, int n_bins);
 int structure_factor(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out);
 void sk_drop(pdeopt_ctx* ctx);
-// gpe_adjoint.hip: GpeAdjoint owns its buffers; deleted by spectral_destroy, its multiplier dropped by spectral_invalidate
-void gpe_adjoint_invalidate(pdeopt_ctx* ctx);
-void gpe_adjoint_destroy(pdeopt_ctx* ctx);
 // butler_volmer.hip: parameters of the Butler-Volmer equations; the voltage of the resident state (recompute) or the one
-// the last right-hand side used; BvState owns its buffers, free_fields deletes it
+// the last right-hand side used
 int bv_set_params(pdeopt_ctx* ctx, double alpha, int mode, const double* per_env);
 int bv_voltage(pdeopt_ctx* ctx, int env_first, int env_count, double* host_out, bool recompute);
-void bv_destroy(pdeopt_ctx* ctx);
 // does the right-hand side depend on t?  (a voltage protocol v(t) registered for the given-voltage mode)
 bool bv_time_dependent(const pdeopt_ctx* ctx);
 // the tangent-linear right-hand side of those equations (sens.hip drives it): the P parameters of B trajectories in the
@@ -535,12 +506,8 @@ bool bv_params_set(const pdeopt_ctx* ctx);  // has pdeopt_set_bv_params been cal
 // ctx->time_last of the base block's own slope launch of the same `in` (which sens.hip issues first)
 int sbm_sens_slopes(pdeopt_ctx* ctx, const BvSensSpec& sp, const void* in, void* out);
 inline bool sbm_equation(int eq) { return eq == PDEOPT_EQ_ALLEN_CAHN_SBM || eq == PDEOPT_EQ_CAHN_HILLIARD_SBM; }
-void sens_destroy(pdeopt_ctx* ctx);
-// implicit.hip: n implicit Euler steps (stats: [batch][4] totals or nullptr); Implicit owns its workspace, free_fields deletes it
+// implicit.hip: n implicit Euler steps (stats: [batch][4] totals or nullptr)
 int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* stats);
-void implicit_destroy(pdeopt_ctx* ctx);
-void strang_fused_invalidate(pdeopt_ctx* ctx);
-void strang_fused_destroy(pdeopt_ctx* ctx);
 
 }  // namespace pdeopt
 

@@ -27,7 +27,7 @@
 
 namespace pdeopt {
 
-struct GpeAdjoint {
+struct GpeAdjoint : Feature {
   DeviceBuffer work;    // a, then c               [batch][nx][ny] complex
   DeviceBuffer direct;  // -2 k g_beta psi0        same
   DeviceBuffer mult;    // E / (nx ny)             [nx][ny] complex
@@ -36,6 +36,8 @@ struct GpeAdjoint {
   DeviceBuffer gacc;    // doubles [batch][PDEOPT_MAX_SPOTS][7]: staging of a host gradient block
   bool mult_valid = false;
   double key_dt = NAN, key_tr = NAN, key_ti = NAN;
+
+  void invalidate() override { mult_valid = false; }
 };
 
 namespace {
@@ -257,7 +259,7 @@ int round_trip(pdeopt_ctx* ctx, GpeAdjoint& ga, void* buf, dim3 grid, int64_t ce
 
 template <typename T>
 int adjoint_step_t(pdeopt_ctx* ctx, double t0, double dt, const void* psi0, void* lam, double* grad_dev) {
-  GpeAdjoint& ga = *ctx->gpe_adjoint;
+  GpeAdjoint& ga = *ctx->features.get<GpeAdjoint>(FS_GPE_ADJOINT);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   int rc = ensure_mult<T>(ctx, ga, dt);
@@ -299,15 +301,6 @@ int adjoint_step_t(pdeopt_ctx* ctx, double t0, double dt, const void* psi0, void
 
 }  // namespace
 
-void gpe_adjoint_invalidate(pdeopt_ctx* ctx) {
-  if (ctx->gpe_adjoint) ctx->gpe_adjoint->mult_valid = false;
-}
-
-void gpe_adjoint_destroy(pdeopt_ctx* ctx) {
-  delete ctx->gpe_adjoint;
-  ctx->gpe_adjoint = nullptr;
-}
-
 }  // namespace pdeopt
 
 using namespace pdeopt;
@@ -345,8 +338,7 @@ int pdeopt_gpe_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, const void* p
   if (overlap(lam_dev, ctx->total_bytes, psi0_dev, ctx->total_bytes) ||
       (grad_on_device && (overlap(grad, gbytes, lam_dev, ctx->total_bytes) || overlap(grad, gbytes, psi0_dev, ctx->total_bytes))))
     return fail(ctx, PDEOPT_EINVAL, "lam_dev and grad are written: they must not overlap each other or psi0_dev");
-  if (!ctx->gpe_adjoint) ctx->gpe_adjoint = new GpeAdjoint();
-  GpeAdjoint& ga = *ctx->gpe_adjoint;
+  GpeAdjoint& ga = ctx->features.ensure<GpeAdjoint>(FS_GPE_ADJOINT);
   int rc;
   if ((rc = ensure_buffer(ctx, ga.work, ctx->total_bytes))) return rc;
   if ((rc = ensure_buffer(ctx, ga.direct, ctx->total_bytes))) return rc;

@@ -33,7 +33,7 @@
 
 namespace pdeopt {
 
-struct GpeObs {
+struct GpeObs : Feature {
   DeviceBuffer tw_x;  // twiddle tables exp(-2 pi i n / N) in the problem dtype
   DeviceBuffer tw_y;
   DeviceBuffer work;  // library path: the copy of the state rocFFT transforms in place
@@ -321,8 +321,7 @@ int gobs_library_axis(pdeopt_ctx* ctx, GpeObs& go, int axis, int env_first, int 
 template <typename T>
 int gpe_observables_t(pdeopt_ctx* ctx, double t, int env_first, int env_count, double x_first, double y_first,
                       double* host_out) {
-  if (!ctx->gpe_obs) ctx->gpe_obs = new GpeObs();
-  GpeObs& go = *ctx->gpe_obs;
+  GpeObs& go = ctx->features.ensure<GpeObs>(FS_GPE_OBS);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   // The two axes choose independently, so unlike the rotating step a hand-written pass may meet an uncovered length on
@@ -387,11 +386,6 @@ int gpe_observables(pdeopt_ctx* ctx, double t, int env_first, int env_count, dou
   return with_dtype(ctx, [&](auto tag) {
     return gpe_observables_t<decltype(tag)>(ctx, t, env_first, env_count, x_first, y_first, host_out);
   });
-}
-
-void gpe_obs_destroy(pdeopt_ctx* ctx) {
-  delete ctx->gpe_obs;
-  ctx->gpe_obs = nullptr;
 }
 
 }  // namespace pdeopt

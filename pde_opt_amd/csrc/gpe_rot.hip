@@ -587,8 +587,7 @@ int rot_library_step(pdeopt_ctx* ctx, GpeRot& gr, std::complex<double> tau, doub
 // buffers, twiddles and the kinetic tables of a step of dt (rebuilt when dt, time_scale or the mesh changed)
 template <typename T>
 int rot_prepare_t(pdeopt_ctx* ctx, double dt, bool* fused_out) {
-  if (!ctx->gpe_rot) ctx->gpe_rot = new GpeRot();
-  GpeRot& gr = *ctx->gpe_rot;
+  GpeRot& gr = ctx->features.ensure<GpeRot>(FS_GPE_ROT);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   const bool fused = ctx->opt_kernel_path != 1 && rot_size_ok(p.nx) && rot_size_ok(p.ny);
@@ -629,7 +628,7 @@ int strang_rot_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   bool fused;
   int rc = rot_prepare_t<T>(ctx, dt, &fused);
   if (rc) return rc;
-  GpeRot& gr = *ctx->gpe_rot;
+  GpeRot& gr = *ctx->features.get<GpeRot>(FS_GPE_ROT);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   const std::complex<double> tau = dt * std::complex<double>(ctx->ts_re, ctx->ts_im);
@@ -673,15 +672,6 @@ int advance_strang_rot(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
     using T = decltype(t);
     return stirred ? strang_rot_t<T, true>(ctx, t0, dt, n) : strang_rot_t<T, false>(ctx, t0, dt, n);
   });
-}
-
-void gpe_rot_invalidate(pdeopt_ctx* ctx) {
-  if (ctx->gpe_rot) ctx->gpe_rot->valid = false;
-}
-
-void gpe_rot_destroy(pdeopt_ctx* ctx) {
-  delete ctx->gpe_rot;
-  ctx->gpe_rot = nullptr;
 }
 
 }  // namespace pdeopt

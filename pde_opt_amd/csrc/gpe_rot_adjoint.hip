@@ -67,8 +67,8 @@
 
 namespace pdeopt {
 
-// one per entry point (ctx->gpe_rot_adjoint, ctx->gpe_rot_stir_adjoint): their partial blocks differ in size
-struct GpeRotAdjoint {
+// one per entry point (slots FS_GPE_ROT_ADJOINT, FS_GPE_ROT_STIR_ADJOINT): their partial blocks differ in size
+struct GpeRotAdjoint : Feature {
   DeviceBuffer work;     // the running primal field, at the end S4     [batch][nx][ny] complex
   DeviceBuffer cbuf;     // c, then the direct term 2 k g_w psi0         same
   DeviceBuffer spec[3];  // S1, S2, S3                                   same
@@ -79,6 +79,8 @@ struct GpeRotAdjoint {
   DeviceBuffer sacc;     // doubles, stirred only: [batch][PDEOPT_MAX_SPOTS][7], staging of a host spot block
   double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
   bool valid = false;
+
+  void invalidate() override { valid = false; }
 };
 
 namespace {
@@ -584,21 +586,7 @@ int rot_adjoint_step_t(pdeopt_ctx* ctx, GpeRotAdjoint& ra, double t0, double dt,
   return PDEOPT_OK;
 }
 
-void radj_invalidate(GpeRotAdjoint* ra) {
-  if (ra) ra->valid = false;
-}
-
-void radj_destroy(GpeRotAdjoint*& ra) {
-  delete ra;
-  ra = nullptr;
-}
-
 }  // namespace
-
-void gpe_rot_adjoint_invalidate(pdeopt_ctx* ctx) { radj_invalidate(ctx->gpe_rot_adjoint); }
-void gpe_rot_adjoint_destroy(pdeopt_ctx* ctx) { radj_destroy(ctx->gpe_rot_adjoint); }
-void gpe_rot_stir_adjoint_invalidate(pdeopt_ctx* ctx) { radj_invalidate(ctx->gpe_rot_stir_adjoint); }
-void gpe_rot_stir_adjoint_destroy(pdeopt_ctx* ctx) { radj_destroy(ctx->gpe_rot_stir_adjoint); }
 
 }  // namespace pdeopt
 
@@ -641,8 +629,7 @@ int pdeopt_gpe_rot_adjoint_step(pdeopt_ctx* ctx, double dt, const void* psi0_dev
   if (overlap(lam_dev, ctx->total_bytes, psi0_dev, ctx->total_bytes) ||
       (grad_on_device && (overlap(grad, gbytes, lam_dev, ctx->total_bytes) || overlap(grad, gbytes, psi0_dev, ctx->total_bytes))))
     return fail(ctx, PDEOPT_EINVAL, "lam_dev and grad are written: they must not overlap each other or psi0_dev");
-  if (!ctx->gpe_rot_adjoint) ctx->gpe_rot_adjoint = new GpeRotAdjoint();
-  GpeRotAdjoint& ra = *ctx->gpe_rot_adjoint;
+  GpeRotAdjoint& ra = ctx->features.ensure<GpeRotAdjoint>(FS_GPE_ROT_ADJOINT);
   int rc = ensure_work<false>(ctx, ra);
   if (rc) return rc;
   double* gdev = grad;
@@ -713,8 +700,7 @@ int pdeopt_gpe_rot_stir_adjoint_step(pdeopt_ctx* ctx, double t0, double dt, cons
   }
   if (bad)
     return fail(ctx, PDEOPT_EINVAL, "lam_dev, grad and spot_grad are written: they must not overlap each other or psi0_dev");
-  if (!ctx->gpe_rot_stir_adjoint) ctx->gpe_rot_stir_adjoint = new GpeRotAdjoint();
-  GpeRotAdjoint& ra = *ctx->gpe_rot_stir_adjoint;
+  GpeRotAdjoint& ra = ctx->features.ensure<GpeRotAdjoint>(FS_GPE_ROT_STIR_ADJOINT);
   int rc = ensure_work<true>(ctx, ra);
   if (rc) return rc;
   double *gdev = grad, *sdev = spot_grad;

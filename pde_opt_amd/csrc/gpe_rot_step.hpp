@@ -12,7 +12,7 @@
 
 namespace pdeopt {
 
-struct GpeRot {
+struct GpeRot : Feature {
   DeviceBuffer tw_x;   // twiddle tables exp(-2 pi i n / N) in the problem dtype
   DeviceBuffer tw_y;
   DeviceBuffer kin_x;  // exp(tau/2 0.5j (2 pi i kx)^2) / nx, complex [nx]
@@ -22,6 +22,8 @@ struct GpeRot {
   int partial_per_env = 0;
   double key_dt = NAN, key_tr = NAN, key_ti = NAN, key_hx = NAN, key_hy = NAN;
   bool valid = false;
+
+  void invalidate() override { valid = false; }
 };
 
 // fp64 and 16-point threads: one factor's sincos at a time (interleaved, their temporaries cost more registers than

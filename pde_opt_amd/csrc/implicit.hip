@@ -69,7 +69,7 @@ struct ImpPrecond {
   double* sin2y;  // [ny / 2 + 1]  sin^2(pi ky / ny)
 };
 
-struct Implicit {
+struct Implicit : Feature {
   double rtol = 0, atol = 0, krylov_rtol = 0;
   int restart = 0, max_newton = 0, max_krylov = 0;
   int B = 0, nblk = 0;
@@ -91,6 +91,8 @@ struct Implicit {
   std::vector<int64_t> pc_count;   // [B] applications of M^-1 inside the steps since configure
   std::vector<char> lin_applied;   // [B] this linear solve's delta has been added to y
 };
+// nullptr until pdeopt_implicit_configure
+inline Implicit* implicit_of(const pdeopt_ctx* ctx) { return ctx->features.get<Implicit>(FS_IMPLICIT); }
 
 namespace {
 
@@ -722,7 +724,7 @@ int implicit_check_problem(pdeopt_ctx* ctx) {
 
 int check_implicit(pdeopt_ctx* ctx) {
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
-  const Implicit* s = ctx->implicit;
+  const Implicit* s = implicit_of(ctx);
   if (!s) return fail(ctx, PDEOPT_ESTATE, "pdeopt_implicit_configure has not been called");
   const int rc = implicit_check_problem(ctx);
   if (rc) return rc;
@@ -768,7 +770,7 @@ int launch_op(pdeopt_ctx* ctx, const T* src, T* vout, T* wout, const double* sca
 // a_b, c_b of the resident state for the environments with flags == 0 (flags == nullptr: all)
 template <typename T>
 int launch_precond_coefs(pdeopt_ctx* ctx, const int* flags) {
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   PrecondCoefArgs<T> a{};
   a.y = ctx->Y.as<const T>();
   a.flags = flags;
@@ -790,7 +792,7 @@ int launch_precond_coefs(pdeopt_ctx* ctx, const int* flags) {
 // nobody reads it
 template <typename T>
 int launch_precond(pdeopt_ctx* ctx, const T* in, T* out, const double* scale, const int* flags, int cycle, double dt) {
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   const pdeopt_problem& p = ctx->prob;
   int rc;
   if ((rc = spectral_real_exec(ctx, true, const_cast<T*>(in), s.hbuf))) return rc;
@@ -818,7 +820,7 @@ int launch_precond(pdeopt_ctx* ctx, const T* in, T* out, const double* scale, co
 }
 
 int read_flags(pdeopt_ctx* ctx) {
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.flags_host.as<int>(), s.sm.flags, (size_t)s.B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PDEOPT_OK;
@@ -826,7 +828,7 @@ int read_flags(pdeopt_ctx* ctx) {
 
 // the budget ran out: put the step's start back, say which environment and how far it got
 int implicit_fail(pdeopt_ctx* ctx, int64_t step, const char* what, int iters) {
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(ctx->Y.get(), s.fields.get(), ctx->total_bytes, hipMemcpyDeviceToDevice, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host.as<double>(), s.sm.res, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(s.res_host.as<double>() + s.B, s.sm.tol, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -842,7 +844,7 @@ int implicit_fail(pdeopt_ctx* ctx, int64_t step, const char* what, int iters) {
 // one step y <- the solution of y - y0 - dt f(y) = 0; st: [B][4] counters or nullptr
 template <typename T>
 int implicit_step(pdeopt_ctx* ctx, double t1, double dt, int64_t step, int64_t* st) {
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   const int B = s.B, m = s.restart;
   const int64_t cells = s.cells;
   T* const y = ctx->Y.as<T>();
@@ -980,14 +982,9 @@ int implicit_advance(pdeopt_ctx* ctx, double t0, double dt, int64_t n, int64_t* 
   }
   char buf[96];
   snprintf(buf, sizeof(buf), "implicit_euler_%s_%s_gmres%d", equation_short_name(ctx->prob.equation),
-           ctx->prob.dtype == PDEOPT_F32 ? "f32" : "f64", ctx->implicit->restart);
+           ctx->prob.dtype == PDEOPT_F32 ? "f32" : "f64", implicit_of(ctx)->restart);
   ctx->last_kernel = buf;
   return PDEOPT_OK;
-}
-
-void implicit_destroy(pdeopt_ctx* ctx) {
-  delete ctx->implicit;
-  ctx->implicit = nullptr;
 }
 
 }  // namespace pdeopt
@@ -1021,10 +1018,10 @@ int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double 
   // doubles of the small block, in the order of ImpSmall; then the three int arrays
   const size_t nd = (size_t)B * ((size_t)m * nblk + 2 * (size_t)nblk + m + (size_t)m * m + m + m + (m + 1) + m + 4);
   const size_t small_bytes = nd * sizeof(double) + 3 * (size_t)B * sizeof(int);
-  Implicit* s = ctx->implicit;
+  Implicit* s = implicit_of(ctx);
   if (s && (s->fields.bytes() != fields_bytes || s->small_blk.bytes() != small_bytes || s->B != B || s->restart != m)) {
     PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    implicit_destroy(ctx);
+    ctx->features.drop(FS_IMPLICIT);
     s = nullptr;
   }
   if (!s) {
@@ -1034,12 +1031,11 @@ int pdeopt_implicit_configure(pdeopt_ctx* ctx, double rtol, double atol, double 
     if (want > free_b)
       return fail(ctx, PDEOPT_ENOMEM, "implicit Euler: the workspace of restart = %d needs %zu bytes ((restart + 5) fields of the "
                                       "batch and the partial sums), %zu are free on the device", m, want, free_b);
-    s = new Implicit();
-    ctx->implicit = s;
+    s = &ctx->features.ensure<Implicit>(FS_IMPLICIT);
     if ((rc = ensure_buffer(ctx, s->fields, fields_bytes)) || (rc = ensure_buffer(ctx, s->small_blk, small_bytes)) ||
         (rc = ensure_buffer(ctx, s->flags_host, (size_t)B * sizeof(int))) ||
         (rc = ensure_buffer(ctx, s->res_host, 2 * (size_t)B * sizeof(double)))) {
-      implicit_destroy(ctx);
+      ctx->features.drop(FS_IMPLICIT);
       return rc;
     }
     s->B = B;
@@ -1092,7 +1088,7 @@ int pdeopt_implicit_apply(pdeopt_ctx* ctx, double dt, const void* v_host, void* 
   if (!ctx || !v_host || !out_host) return PDEOPT_EINVAL;
   int rc;
   if ((rc = check_implicit(ctx))) return rc;
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
     T* const v = imp_field<T>(s, F_W0);
@@ -1114,7 +1110,7 @@ int pdeopt_implicit_set_precond(pdeopt_ctx* ctx, int kind) {
   if ((rc = check_implicit(ctx))) return rc;
   if (kind != PDEOPT_IMPLICIT_PRECOND_NONE && kind != PDEOPT_IMPLICIT_PRECOND_SPECTRAL)
     return fail(ctx, PDEOPT_EINVAL, "implicit Euler: preconditioner %d (0 none, 1 spectral)", kind);
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   std::fill(s.pc_count.begin(), s.pc_count.end(), (int64_t)0);
   if (kind == PDEOPT_IMPLICIT_PRECOND_NONE) {
     s.precond = 0;
@@ -1124,7 +1120,7 @@ int pdeopt_implicit_set_precond(pdeopt_ctx* ctx, int kind) {
   const int nyh = p.ny / 2 + 1;
   const size_t nd = (size_t)s.B * (2 * (size_t)s.nblk + 2) + (size_t)p.nx + (size_t)nyh;
   // Set up once per workspace.  The tables and the size of pc_blk belong to one (nx, ny, batch, dtype), and so does this
-  // workspace: pdeopt_configure frees it (implicit_destroy, with the field buffers) on any change of shape or dtype, and
+  // workspace: pdeopt_configure frees it (features.clear(), with the field buffers) on any change of shape or dtype, and
   // pdeopt_implicit_configure, whose own reuse test compares byte sizes only, cannot see another grid without that.  A
   // reuse rule that lets a workspace outlive its grid has to rebuild these too.
   if (!s.zfield || !s.pc_blk) {
@@ -1165,7 +1161,7 @@ int pdeopt_implicit_set_precond(pdeopt_ctx* ctx, int kind) {
 static int check_precond(pdeopt_ctx* ctx) {
   int rc;
   if ((rc = check_implicit(ctx))) return rc;
-  if (!ctx->implicit->precond)
+  if (!implicit_of(ctx)->precond)
     return fail(ctx, PDEOPT_ESTATE, "pdeopt_implicit_set_precond(ctx, PDEOPT_IMPLICIT_PRECOND_SPECTRAL) has not been called");
   return PDEOPT_OK;
 }
@@ -1174,7 +1170,7 @@ int pdeopt_implicit_precond_coefs(pdeopt_ctx* ctx, double* out) {
   if (!ctx || !out) return PDEOPT_EINVAL;
   int rc;
   if ((rc = check_precond(ctx))) return rc;
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   if ((rc = with_dtype(ctx, [&](auto t) { return launch_precond_coefs<decltype(t)>(ctx, nullptr); }))) return rc;
   PDEOPT_HIP_CHECK(ctx, hipMemcpyAsync(out, s.pc.coef, 2 * (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1186,7 +1182,7 @@ int pdeopt_implicit_precond_apply(pdeopt_ctx* ctx, double dt, const void* v_host
   int rc;
   if ((rc = check_precond(ctx))) return rc;
   if (!(dt > 0.0) || !std::isfinite(dt)) return fail(ctx, PDEOPT_EINVAL, "implicit Euler: dt = %g", dt);
-  Implicit& s = *ctx->implicit;
+  Implicit& s = *implicit_of(ctx);
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
     T* const v = imp_field<T>(s, F_W0);
@@ -1205,7 +1201,7 @@ int pdeopt_implicit_precond_count(pdeopt_ctx* ctx, int64_t* out) {
   if (!ctx || !out) return PDEOPT_EINVAL;
   int rc;
   if ((rc = check_implicit(ctx))) return rc;
-  const Implicit& s = *ctx->implicit;
+  const Implicit& s = *implicit_of(ctx);
   std::copy(s.pc_count.begin(), s.pc_count.end(), out);
   return PDEOPT_OK;
 }

@@ -43,7 +43,7 @@
 
 namespace pdeopt {
 
-struct Sens {
+struct Sens : Feature {
   int B = 0, P = 0;
   int role[kMaxSens] = {};   // PDEOPT_SENS_MU / PDEOPT_SENS_MOB / PDEOPT_SENS_KAPPA
   int index[kMaxSens] = {};  // coefficient k of that closure
@@ -53,6 +53,8 @@ struct Sens {
   DeviceBuffer sums;         // doubles [B][K]; grow-only
   bool has_kappa = false;  // some role is PDEOPT_SENS_KAPPA: the KAPPA kernels, and IMEX through the rocFFT loop
 };
+// nullptr until pdeopt_sens_configure
+inline Sens* sens_of(const pdeopt_ctx* ctx) { return ctx->features.get<Sens>(FS_SENS); }
 
 namespace {
 
@@ -557,7 +559,7 @@ int sens_kappa_check(pdeopt_ctx* ctx, int B, double* kappa) {
 
 int check_sens(pdeopt_ctx* ctx) {
   if (!ctx->configured) return fail(ctx, PDEOPT_ESTATE, "pdeopt_configure has not been called");
-  const Sens* s = ctx->sens;
+  const Sens* s = sens_of(ctx);
   if (!s) return fail(ctx, PDEOPT_ESTATE, "pdeopt_sens_configure has not been called");
   if ((int64_t)(1 + s->P) * s->B != ctx->prob.batch)
     return fail(ctx, PDEOPT_ESTATE, "batch %d is not (1 + P) B = %d: configure again before pdeopt_sens_configure",
@@ -575,7 +577,7 @@ int check_sens(pdeopt_ctx* ctx) {
 template <typename T, typename Args>
 void fill_tangent_args(Args& a, const pdeopt_ctx* ctx, const void* in, void* out) {
   const pdeopt_problem& p = ctx->prob;
-  const Sens& s = *ctx->sens;
+  const Sens& s = *sens_of(ctx);
   a.y = static_cast<const T*>(in);
   a.k = static_cast<T*>(out);
   set_closures<T>(a, ctx, 0);
@@ -597,7 +599,7 @@ int launch_tangent_rhs(pdeopt_ctx* ctx, const void* in, void* out) {
   fill_tangent_args<T>(a, ctx, in, out);
   const dim3 grid((p.ny + kTC - 1) / kTC, (p.nx + kTR - 1) / kTR, a.B);
   // the KAPPA instantiations only when a kappa role is configured: every other fit runs the kernels it always ran
-  const bool kap = ctx->sens->has_kappa;
+  const bool kap = sens_of(ctx)->has_kappa;
   if (p.equation == PDEOPT_EQ_ALLEN_CAHN) {
     if (kap) hipLaunchKernelGGL((sens_ac_tangent_rhs_kernel<T, true>), grid, dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL((sens_ac_tangent_rhs_kernel<T, false>), grid, dim3(256), 0, ctx->stream, a);
@@ -623,7 +625,7 @@ int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
   a.rhz = T(r.rz);
   a.rhz2 = T(r.rz2);
   const dim3 grid((unsigned)((sens_cells(ctx) + 255) / 256), a.B);
-  if (ctx->sens->has_kappa) hipLaunchKernelGGL((sens3d_dmu_kernel<T, true>), grid, dim3(256), 0, ctx->stream, a);
+  if (sens_of(ctx)->has_kappa) hipLaunchKernelGGL((sens3d_dmu_kernel<T, true>), grid, dim3(256), 0, ctx->stream, a);
   else hipLaunchKernelGGL((sens3d_dmu_kernel<T, false>), grid, dim3(256), 0, ctx->stream, a);
   hipLaunchKernelGGL(sens3d_flux_kernel<T>, grid, dim3(256), 0, ctx->stream, a);
   ctx->n_stage_launches += 2;
@@ -636,14 +638,14 @@ int launch_tangent_rhs3d(pdeopt_ctx* ctx, const void* in, void* out) {
 int sens_slopes(pdeopt_ctx* ctx, const void* in, void* out, double t) {
   int rc;
   // the base block's slope; the tangent blocks' slopes come from the kernels below
-  if ((rc = launch_rhs_slope(ctx, Window{0, ctx->sens->B, ctx->stream}, in, out, t))) return rc;
+  if ((rc = launch_rhs_slope(ctx, Window{0, sens_of(ctx)->B, ctx->stream}, in, out, t))) return rc;
   if (sbm_equation(ctx->prob.equation)) {
     // the tangent kernel reads the time terms that launch resolved (ctx->time_last): the same numbers, whatever their source
-    const Sens& s = *ctx->sens;
+    const Sens& s = *sens_of(ctx);
     return sbm_sens_slopes(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, in, out);
   }
   if (bv_equation(ctx->prob.equation)) {
-    const Sens& s = *ctx->sens;
+    const Sens& s = *sens_of(ctx);
     return bv_sens_slopes(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, in, out);
   }
   return with_dtype(ctx, [&](auto t) {
@@ -689,7 +691,7 @@ int rk4_substep(pdeopt_ctx* ctx, double dt, double ts, bool timed) {
 
 // the buffers of the two-stage reductions below: partial[B][K][nblk] and sums[B][K]
 int ensure_sums(pdeopt_ctx* ctx, int K, int nblk) {
-  Sens& s = *ctx->sens;
+  Sens& s = *sens_of(ctx);
   const size_t pbytes = (size_t)s.B * K * nblk * sizeof(double), sbytes = (size_t)s.B * K * sizeof(double);
   const int rc = grow_device_buffer(ctx, s.partial, pbytes, /*sync_first=*/true);
   return rc ? rc : grow_device_buffer(ctx, s.sums, sbytes, /*sync_first=*/true);
@@ -697,7 +699,7 @@ int ensure_sums(pdeopt_ctx* ctx, int K, int nblk) {
 
 // sums[b][k] = the block totals of partial[b][k][.] in block order, copied to the host
 int finish_sums(pdeopt_ctx* ctx, int K, int nblk, double* host_out) {
-  Sens& s = *ctx->sens;
+  Sens& s = *sens_of(ctx);
   const int n = s.B * K;
   hipLaunchKernelGGL(sens_gn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s.partial.as<double>(), s.sums.as<double>(), n, nblk);
   PDEOPT_HIP_CHECK(ctx, hipGetLastError());
@@ -710,7 +712,7 @@ int finish_sums(pdeopt_ctx* ctx, int K, int nblk, double* host_out) {
 // (blocks per field, B, grid_z) leaves K block totals per trajectory, finish_sums adds them up for the host
 template <typename T, typename Kernel>
 int reduce_frame(pdeopt_ctx* ctx, Kernel kernel, int K, int grid_z, int frame, double theta, int interp, double* host_out) {
-  Sens& s = *ctx->sens;
+  Sens& s = *sens_of(ctx);
   const int64_t cells = sens_cells(ctx);
   const int nblk = (int)((cells + kGnCellsPerBlock - 1) / kGnCellsPerBlock);
   int rc;
@@ -726,7 +728,7 @@ int reduce_frame(pdeopt_ctx* ctx, Kernel kernel, int K, int grid_z, int frame, d
 int check_frame(pdeopt_ctx* ctx, int frame, int interp) {
   const int rc = check_sens(ctx);
   if (rc) return rc;
-  const Sens& s = *ctx->sens;
+  const Sens& s = *sens_of(ctx);
   if (!s.data || frame < 0 || frame >= s.n_frames)
     return fail(ctx, PDEOPT_EINVAL, "frame %d of %d uploaded (pdeopt_sens_set_data)", frame, s.n_frames);
   if (interp && !ctx->SNAP) return fail(ctx, PDEOPT_ESTATE, "pdeopt_snapshot has not been called");
@@ -735,11 +737,6 @@ int check_frame(pdeopt_ctx* ctx, int frame, int interp) {
 }
 
 }  // namespace
-
-void sens_destroy(pdeopt_ctx* ctx) {
-  delete ctx->sens;
-  ctx->sens = nullptr;
-}
 
 }  // namespace pdeopt
 
@@ -789,8 +786,7 @@ int pdeopt_sens_configure(pdeopt_ctx* ctx, int n_traj, int n_params, const int32
     if (coef_index[j] < 0 || coef_index[j] >= cl.n)
       return fail(ctx, PDEOPT_EINVAL, "sensitivity %d: coefficient %d of a closure with %d coefficients", j, coef_index[j], cl.n);
   }
-  if (!ctx->sens) ctx->sens = new Sens();
-  Sens& s = *ctx->sens;
+  Sens& s = ctx->features.ensure<Sens>(FS_SENS);
   s.B = n_traj;
   s.P = n_params;
   s.has_kappa = has_kappa;
@@ -841,12 +837,12 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
                                       "IMEX scales)");
     // the hand-written FFT passes where they exist (power-of-two 2-D grids 64..1024), rocFFT's real transforms elsewhere;
     // a kappa tangent needs the base spectrum next to its own (m'), which only the rocFFT loop's multiply can give it
-    kap = ctx->sens->has_kappa;
+    kap = sens_of(ctx)->has_kappa;
     fused = !kap && imex_fused_supported(ctx);
     if ((rc = fused ? imex_fused_prepare(ctx, dt) : imex_rocfft_prepare(ctx, dt))) return rc;
     if (kap) {
       double kappa = 0.0;
-      if ((rc = sens_kappa_check(ctx, ctx->sens->B, &kappa))) return rc;
+      if ((rc = sens_kappa_check(ctx, sens_of(ctx)->B, &kappa))) return rc;
       if ((rc = imex_rocfft_prepare_kappa(ctx, dt, kappa))) return rc;
     }
   } else if (integrator == PDEOPT_INT_RK4 && ac) {
@@ -867,7 +863,7 @@ int pdeopt_sens_advance(pdeopt_ctx* ctx, int integrator, double t0, double dt, i
     if (integrator == PDEOPT_INT_IMEX && fused) {
       rc = imex_fused_passes(ctx, whole_batch(ctx), dt);
     } else if (integrator == PDEOPT_INT_IMEX) {
-      rc = kap ? imex_rocfft_solve_kappa(ctx, dt, ctx->sens->B, ctx->sens->P, ctx->sens->role) : imex_rocfft_solve(ctx, dt);
+      rc = kap ? imex_rocfft_solve_kappa(ctx, dt, sens_of(ctx)->B, sens_of(ctx)->P, sens_of(ctx)->role) : imex_rocfft_solve(ctx, dt);
       ctx->n_stage_launches += 4;  // r2c, multiply, c2r, axpy (host calls; rocFFT may run more than one kernel per transform)
     } else {
       rc = with_dtype(ctx, [&](auto t) { return euler_update<decltype(t)>(ctx, dt); });
@@ -890,7 +886,7 @@ int pdeopt_sens_bv_voltage(pdeopt_ctx* ctx, double* out) {
   if (rc) return rc;
   if (!bv_equation(ctx->prob.equation)) return fail(ctx, PDEOPT_EINVAL, "pdeopt_sens_bv_voltage belongs to the Butler-Volmer equations");
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const Sens& s = *ctx->sens;
+  const Sens& s = *sens_of(ctx);
   return bv_sens_voltage(ctx, BvSensSpec{s.B, s.P, s.role, s.index}, out);
 }
 
@@ -899,7 +895,7 @@ int pdeopt_sens_set_data(pdeopt_ctx* ctx, int n_frames, const void* host) {
   int rc = check_sens(ctx);
   if (rc) return rc;
   PDEOPT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  Sens& s = *ctx->sens;
+  Sens& s = *sens_of(ctx);
   const size_t bytes = (size_t)n_frames * s.B * sens_cells(ctx) * ctx->esize;
   PDEOPT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = grow_device_buffer(ctx, s.data, bytes, /*sync_first=*/false))) return rc;  // (synchronised above)
@@ -913,7 +909,7 @@ int pdeopt_sens_accumulate(pdeopt_ctx* ctx, int frame, double theta, int interp,
   if (!ctx || !out) return PDEOPT_EINVAL;
   const int rc = check_frame(ctx, frame, interp);
   if (rc) return rc;
-  const int P = ctx->sens->P;
+  const int P = sens_of(ctx)->P;
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
     return reduce_frame<T>(ctx, sens_gn_partial_kernel<T>, 1 + P + P * (P + 1) / 2, 1 + P, frame, theta, interp, out);
@@ -926,7 +922,7 @@ int pdeopt_sens_contract(pdeopt_ctx* ctx, int frame, double theta, int interp, d
   if (rc) return rc;
   return with_dtype(ctx, [&](auto t) {
     using T = decltype(t);
-    return reduce_frame<T>(ctx, sens_contract_partial_kernel<T>, ctx->sens->P, 1, frame, theta, interp, out);
+    return reduce_frame<T>(ctx, sens_contract_partial_kernel<T>, sens_of(ctx)->P, 1, frame, theta, interp, out);
   });
 }
 

@@ -21,7 +21,7 @@
 
 namespace pdeopt {
 
-struct Spectral {
+struct Spectral : Feature {
   bool setup = false;
   rocfft_plan fwd = nullptr, inv = nullptr;
   rocfft_execution_info info = nullptr;
@@ -51,6 +51,25 @@ struct Spectral {
   // cache key of `mult` / `hmult`
   int mult_kind = -1;
   double mult_dt = NAN, mult_A = NAN, mult_tr = NAN, mult_ti = NAN;
+
+  void invalidate() override {
+    mult_kind = -1;
+    multk_dt = NAN;
+  }
+  // the body runs before the members go: the work fields are freed after the plans that were given them
+  ~Spectral() override {
+    for (int a = 0; a < 2; ++a) {
+      if (ax_fwd[a]) rocfft_plan_destroy(ax_fwd[a]);
+      if (ax_inv[a]) rocfft_plan_destroy(ax_inv[a]);
+    }
+    if (ax_info) rocfft_execution_info_destroy(ax_info);
+    if (r2c) rocfft_plan_destroy(r2c);
+    if (c2r) rocfft_plan_destroy(c2r);
+    if (rinfo) rocfft_execution_info_destroy(rinfo);
+    if (fwd) rocfft_plan_destroy(fwd);
+    if (inv) rocfft_plan_destroy(inv);
+    if (info) rocfft_execution_info_destroy(info);
+  }
 };
 
 namespace {
@@ -68,8 +87,7 @@ constexpr int kNormBlocks = 128;
 std::once_flag g_rocfft_once;
 
 int ensure_plans(pdeopt_ctx* ctx) {
-  if (!ctx->spectral) ctx->spectral = new Spectral();
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = ctx->features.ensure<Spectral>(FS_SPECTRAL);
   if (sp.setup) return PDEOPT_OK;
   std::call_once(g_rocfft_once, [] { rocfft_setup(); });
   const pdeopt_problem& p = ctx->prob;
@@ -106,7 +124,7 @@ int ensure_plans(pdeopt_ctx* ctx) {
 
 // real-to-hermitian plans.  The fastest non-trivial dimension is the one rocFFT halves.
 int ensure_real_plans(pdeopt_ctx* ctx) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   if (sp.r2c) return PDEOPT_OK;
   const pdeopt_problem& p = ctx->prob;
   size_t lengths[3];
@@ -140,7 +158,7 @@ int ensure_real_plans(pdeopt_ctx* ctx) {
 }
 
 int real_fft_exec(pdeopt_ctx* ctx, bool forward, void* in, void* out) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   void* ib[1] = {in};
   void* ob[1] = {out};
   PDEOPT_FFT_CHECK(ctx, rocfft_execute(forward ? sp.r2c : sp.c2r, ib, ob, sp.rinfo));
@@ -151,8 +169,7 @@ int real_fft_exec(pdeopt_ctx* ctx, bool forward, void* in, void* out) {
 // line has stride ny and the ny lines of an environment start one element apart; the next environment's do not
 // continue that pattern, so the plan covers one environment and is executed once per environment.
 int ensure_axis_plans(pdeopt_ctx* ctx) {
-  if (!ctx->spectral) ctx->spectral = new Spectral();
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = ctx->features.ensure<Spectral>(FS_SPECTRAL);
   if (sp.ax_info) return PDEOPT_OK;
   std::call_once(g_rocfft_once, [] { rocfft_setup(); });
   const pdeopt_problem& p = ctx->prob;
@@ -189,7 +206,7 @@ int ensure_axis_plans(pdeopt_ctx* ctx) {
 }
 
 int fft_exec(pdeopt_ctx* ctx, bool forward, void* buf) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   void* in[1] = {buf};
   PDEOPT_FFT_CHECK(ctx, rocfft_execute(forward ? sp.fwd : sp.inv, in, nullptr, sp.info));
   return PDEOPT_OK;
@@ -323,7 +340,7 @@ inline int grid_for(int64_t n) {
 
 template <typename T>
 int upload_mult(pdeopt_ctx* ctx, const std::vector<std::complex<double>>& m) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const size_t cells = m.size();
   int rc = ensure_buffer(ctx, sp.mult, cells * 2 * sizeof(T));
   if (rc) return rc;
@@ -384,8 +401,7 @@ std::vector<C2<T>> half_spectrum(const pdeopt_problem& p, int64_t hc, F m) {
 // plans, work fields and the half-spectrum multiplier of step dt (kept while dt and A hold)
 template <typename T>
 int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
-  if (!ctx->spectral) ctx->spectral = new Spectral();
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = ctx->features.ensure<Spectral>(FS_SPECTRAL);
   const pdeopt_problem& p = ctx->prob;
   const int nzz = p.nz > 1 ? p.nz : 1;
   const int64_t cells = (int64_t)p.nx * p.ny * nzz;
@@ -412,7 +428,7 @@ int imex_rocfft_prepare_t(pdeopt_ctx* ctx, double dt) {
 // TA = Re ifftn(fftn(TA) m) over the whole batch: r2c, multiply, c2r
 template <typename T>
 int imex_rocfft_apply_t(pdeopt_ctx* ctx) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const int64_t hc = sp.half_cells;
   int rc;
   if ((rc = real_fft_exec(ctx, true, ctx->TA.get(), sp.hbuf.get()))) return rc;
@@ -487,7 +503,7 @@ __global__ __launch_bounds__(256) void sens_imex_mul_kappa_kernel(KappaMulArgs<T
 
 template <typename T>
 int imex_rocfft_prepare_kappa_t(pdeopt_ctx* ctx, double dt, double kappa) {
-  Spectral& sp = *ctx->spectral;  // (imex_rocfft_prepare has run: plans, hbuf, hmult)
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);  // (imex_rocfft_prepare has run: plans, hbuf, hmult)
   const pdeopt_problem& p = ctx->prob;
   const int64_t hc = sp.half_cells;
   if (sp.hmultk && sp.multk_dt == dt && sp.multk_A == ctx->imex_A && sp.multk_kappa == kappa) return PDEOPT_OK;
@@ -510,7 +526,7 @@ int imex_rocfft_prepare_kappa_t(pdeopt_ctx* ctx, double dt, double kappa) {
 
 template <typename T>
 int imex_rocfft_solve_kappa_t(pdeopt_ctx* ctx, double dt, int B, int P, const int* role) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const int64_t hc = sp.half_cells;
   if (P < 1 || P > kMaxSens || (int64_t)(1 + P) * B != ctx->prob.batch)
     return fail(ctx, PDEOPT_ESTATE, "IMEX kappa multiply: batch %d is not (1 + %d) %d", ctx->prob.batch, P, B);
@@ -549,7 +565,7 @@ int imex_t(pdeopt_ctx* ctx, double dt, int64_t n) {
 
 template <typename T>
 int strang_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   const int64_t total = cells * p.batch;
@@ -694,7 +710,7 @@ __global__ void fourier_out_kernel(const T* __restrict__ u, const C2<T>* __restr
 
 template <typename T>
 int rhs_fourier_t(pdeopt_ctx* ctx, const void* in, void* out) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny, total = cells * p.batch;
   int rc;
@@ -810,7 +826,7 @@ __global__ void fourier3_div_kernel(C2<T>* __restrict__ acc, const C2<T>* __rest
 
 template <typename T>
 int rhs_fourier3_t(pdeopt_ctx* ctx, const void* in, void* out) {
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny * p.nz, total = cells * p.batch;
   int rc;
@@ -898,11 +914,10 @@ int spectral_c2c(pdeopt_ctx* ctx, bool forward, void* buf) {
 }
 
 int spectral_real_prepare(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
-  if (!ctx->spectral) ctx->spectral = new Spectral();
+  Spectral& sp = ctx->features.ensure<Spectral>(FS_SPECTRAL);
   std::call_once(g_rocfft_once, [] { rocfft_setup(); });
   int rc = ensure_real_plans(ctx);
   if (rc) return rc;
-  Spectral& sp = *ctx->spectral;
   if ((rc = ensure_buffer(ctx, sp.hbuf, (size_t)sp.half_cells * ctx->prob.batch * 2 * ctx->esize))) return rc;
   *half = sp.hbuf.get();
   *half_cells = sp.half_cells;
@@ -919,7 +934,7 @@ int spectral_r2c_state(pdeopt_ctx* ctx, void** half, int64_t* half_cells) {
 int spectral_c2c_axis(pdeopt_ctx* ctx, int axis, bool forward, void* buf) {
   int rc = ensure_axis_plans(ctx);
   if (rc) return rc;
-  Spectral& sp = *ctx->spectral;
+  Spectral& sp = *ctx->features.get<Spectral>(FS_SPECTRAL);
   const pdeopt_problem& p = ctx->prob;
   rocfft_plan plan = forward ? sp.ax_fwd[axis] : sp.ax_inv[axis];
   const size_t env_bytes = (size_t)p.nx * p.ny * 2 * ctx->esize;
@@ -941,41 +956,6 @@ int advance_strang(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   int rc = ensure_plans(ctx);
   if (rc) return rc;
   return with_dtype(ctx, [&](auto t) { return strang_t<decltype(t)>(ctx, t0, dt, n); });
-}
-
-void spectral_invalidate(pdeopt_ctx* ctx) {
-  if (ctx->spectral) {
-    ctx->spectral->mult_kind = -1;
-    ctx->spectral->multk_dt = NAN;
-  }
-  strang_fused_invalidate(ctx);
-  gpe_adjoint_invalidate(ctx);
-  gpe_rot_invalidate(ctx);
-  gpe_rot_adjoint_invalidate(ctx);
-  gpe_rot_stir_adjoint_invalidate(ctx);
-}
-
-void spectral_destroy(pdeopt_ctx* ctx) {
-  gpe_adjoint_destroy(ctx);
-  gpe_rot_destroy(ctx);
-  gpe_rot_adjoint_destroy(ctx);
-  gpe_rot_stir_adjoint_destroy(ctx);
-  gpe_obs_destroy(ctx);
-  Spectral* sp = ctx->spectral;
-  if (!sp) return;
-  for (int a = 0; a < 2; ++a) {
-    if (sp->ax_fwd[a]) rocfft_plan_destroy(sp->ax_fwd[a]);
-    if (sp->ax_inv[a]) rocfft_plan_destroy(sp->ax_inv[a]);
-  }
-  if (sp->ax_info) rocfft_execution_info_destroy(sp->ax_info);
-  if (sp->r2c) rocfft_plan_destroy(sp->r2c);
-  if (sp->c2r) rocfft_plan_destroy(sp->c2r);
-  if (sp->rinfo) rocfft_execution_info_destroy(sp->rinfo);
-  if (sp->fwd) rocfft_plan_destroy(sp->fwd);
-  if (sp->inv) rocfft_plan_destroy(sp->inv);
-  if (sp->info) rocfft_execution_info_destroy(sp->info);
-  delete sp;  // the work fields go after the plans that were given them
-  ctx->spectral = nullptr;
 }
 
 }  // namespace pdeopt

@@ -28,7 +28,7 @@
 
 namespace pdeopt {
 
-struct StrangFused {
+struct StrangFused : Feature {
   DeviceBuffer tw_x;  // twiddle tables exp(-2 pi i n / N) in the problem dtype
   DeviceBuffer tw_y;
   DeviceBuffer mult;  // E / (nx ny), complex, laid out by col_mult_index()
@@ -42,6 +42,11 @@ struct StrangFused {
   bool imex_per_env = false;  // which of the two imex_mult holds
   double imex_dt = NAN, imex_A = NAN;
   bool imex_valid = false;
+
+  void invalidate() override {
+    mult_valid = false;
+    imex_valid = false;
+  }
 };
 
 namespace {
@@ -429,8 +434,7 @@ bool size_ok(int n, bool) { return n == 64 || n == 128 || n == 256 || n == 512 |
 
 template <typename T>
 int strang_fused_t(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
-  if (!ctx->strang_fused) ctx->strang_fused = new StrangFused();
-  StrangFused& sf = *ctx->strang_fused;
+  StrangFused& sf = ctx->features.ensure<StrangFused>(FS_STRANG_FUSED);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   int rc;
@@ -670,8 +674,7 @@ int imex_cols(pdeopt_ctx* ctx, const Window& w, StrangFused& sf) {
 // twiddle tables, work field and implicit multiplier of the IMEX passes for step dt (kept while dt and A hold)
 template <typename T>
 int imex_prepare_t(pdeopt_ctx* ctx, double dt) {
-  if (!ctx->strang_fused) ctx->strang_fused = new StrangFused();
-  StrangFused& sf = *ctx->strang_fused;
+  StrangFused& sf = ctx->features.ensure<StrangFused>(FS_STRANG_FUSED);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   int rc;
@@ -754,7 +757,7 @@ template <typename T>
 int imex_fused_t(pdeopt_ctx* ctx, double dt, int64_t n) {
   int rc = imex_prepare_t<T>(ctx, dt);
   if (rc) return rc;
-  StrangFused& sf = *ctx->strang_fused;
+  StrangFused& sf = *ctx->features.get<StrangFused>(FS_STRANG_FUSED);
   const pdeopt_problem& p = ctx->prob;
   const int64_t cells = (int64_t)p.nx * p.ny;
   // group by group (an even number of environments each): state + slope + spectrum work field are 12 B/cell
@@ -801,7 +804,7 @@ int imex_fused_prepare(pdeopt_ctx* ctx, double dt) {
 }
 
 int imex_fused_passes(pdeopt_ctx* ctx, const Window& w, double dt) {
-  StrangFused& sf = *ctx->strang_fused;
+  StrangFused& sf = *ctx->features.get<StrangFused>(FS_STRANG_FUSED);
   return with_dtype(ctx, [&](auto t) { return imex_passes_t<decltype(t)>(ctx, w, sf, dt); });
 }
 
@@ -816,18 +819,6 @@ bool strang_fused_supported(const pdeopt_ctx* ctx) {
 
 int advance_strang_fused(pdeopt_ctx* ctx, double t0, double dt, int64_t n) {
   return with_dtype(ctx, [&](auto t) { return strang_fused_t<decltype(t)>(ctx, t0, dt, n); });
-}
-
-void strang_fused_invalidate(pdeopt_ctx* ctx) {
-  if (ctx->strang_fused) {
-    ctx->strang_fused->mult_valid = false;
-    ctx->strang_fused->imex_valid = false;
-  }
-}
-
-void strang_fused_destroy(pdeopt_ctx* ctx) {
-  delete ctx->strang_fused;
-  ctx->strang_fused = nullptr;
 }
 
 }  // namespace pdeopt

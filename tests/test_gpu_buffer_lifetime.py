@@ -9,6 +9,7 @@ import pde_opt_amd as P
 from pde_opt_amd import _lib as L
 from pde_opt_amd.numerics.functions.legendre import ChemicalPotentialLegendrePolynomials as ChemLeg
 from pde_opt_amd.numerics.functions.legendre import DiffusionLegendrePolynomials as DiffLeg
+from pde_opt_amd.numerics.functions.lights import GaussianSpot, GaussianSpots
 from pde_opt_amd.structure_factor import shell_tables
 from pde_opt_amd.utils import prepare_solver_params
 
@@ -64,6 +65,52 @@ def _gpe_strang(eng, n, batch, steps=2):
     X, Y = dom.mesh()
     eng.gpe_origin = (float(X[0, 0]), float(Y[0, 0]))
     return dom
+
+
+def _adjoint_call(eng, call, *grad_shapes):
+    """one backward substep from the resident state: a white-noise cotangent on the device, host gradient blocks;
+    `call(psi0_ptr, lam_ptr, *grad_ptrs)`.  Returns the new cotangent and the blocks."""
+    shape = (eng.batch,) + eng.state_shape
+    lam = np.random.default_rng(12).standard_normal(shape).astype(eng.dtype)
+    lam_dev = eng.buffer_alloc(lam.nbytes)
+    eng.buffer_copy(lam_dev, lam, lam.nbytes, L.COPY_H2D)
+    grads = [np.zeros(s) for s in grad_shapes]
+    call(eng.state_device_ptr()[0], lam_dev, *[g.ctypes.data for g in grads])
+    eng.sync()
+    eng.buffer_copy(lam, lam_dev, lam.nbytes, L.COPY_D2H)
+    eng.buffer_free(lam_dev)
+    assert all(np.all(np.isfinite(g)) for g in grads) and np.all(np.isfinite(lam))
+    return (lam,) + tuple(grads)
+
+
+def _gpe_strang_library_and_adjoint(eng, batch):
+    """after _gpe_strang: one Strang step through rocFFT (the Spectral state), then one step of the Strang step's adjoint,
+    which differentiates one light spot"""
+    eng.set_kernel_path(1)
+    eng.advance(L.INT_STRANG, 1e-3, 1)
+    assert eng.last_kernel == "strang_rocfft_c2c"
+    eng.set_kernel_path(0)
+    tab = GaussianSpots([GaussianSpot(1.5, -0.8, 0.4, 0.9, -0.3, 0.5, 0.6)]).table(1)
+    eng.set_gpe_spots(np.broadcast_to(tab, (batch,) + tab.shape), *eng.gpe_origin)
+    _adjoint_call(eng, lambda psi0, lam, g: eng.gpe_adjoint_step(0.0, 1e-3, psi0, lam, g), (batch, 1, 7))
+    assert eng.last_kernel == "strang_adjoint_rocfft_c2c"
+    eng.set_gpe_spots(None)
+
+
+def _gpe_rot_stirred_adjoint(eng, n, batch):
+    """one step of the adjoint of the stirred, ramped rotating-frame split step (the set-up of
+    test_gpu_gpe_rot_stir_adjoint.py: two moving spots and a rotation ramp per environment)"""
+    dom = P.Domain((n, n), ((-2.0, 2.0), (-1.5, 1.5)), "dimensionless")
+    spots = lambda b: GaussianSpots([GaussianSpot(3.0 + b, 0.5, -0.6 + 0.1 * b, 0.8, 0.3 - 0.07 * b, -0.4, 0.35),  # noqa: E731
+                                     GaussianSpot(-2.0, 1.0 + b, 0.7, -0.5 - 0.2 * b, -0.45, 0.6 + 0.1 * b, 0.25 + 0.05 * b)])
+    eqs = [P.GPE2DTSRot(dom, k=50.0 + 7.0 * b, e=0.1 + 0.05 * b, omega=0.5 - 0.3 * b, lights=spots(b), omega_rate=0.9 - 0.7 * b)
+           for b in range(batch)]
+    eng.configure(dtype=np.float32, batch=batch, **eqs[0]._engine_problem())
+    P.GPE2DTSRot._engine_upload_batch(eng, eqs, 0.3, 1.3)
+    P.RotatingStrangSplitting(**prepare_solver_params(P.RotatingStrangSplitting, {"time_scale": 1.0}, eqs[0])).configure_engine(eng, eqs[0])
+    eng.set_state(np.random.default_rng(13).standard_normal((batch, n, n, 2)).astype(np.float32))
+    _adjoint_call(eng, lambda psi0, lam, g, sg: eng.gpe_rot_stir_adjoint_step(0.3, 0.02, psi0, lam, g, sg), (batch, 4), (batch, 2, 7))
+    assert eng.last_kernel == "strang_rot_stir_adjoint_rocfft_1d"
 
 
 def _gpe_rot(eng, n, batch):
@@ -164,20 +211,28 @@ def _network(eng, net):
         eng.buffer_free(d)
 
 
+def _tour(eng):
+    """after _explicit_and_diagnostics(eng, 32, 2): every feature state of the ctx (csrc/feature_slot.hpp) is created on
+    the way; the engine ends on the 32 x 32 fp32 batch-2 Cahn-Hilliard shape, holding the implicit workspace"""
+    _imex(eng, 32, 2)  # Spectral (32 is no size of the hand-written transforms)
+    _gpe_strang(eng, 64, 2)  # StrangFused
+    _gpe_strang_library_and_adjoint(eng, 2)  # Spectral, GpeAdjoint
+    eng.gpe_observables()  # GpeObs
+    eng.detect_vortices(0.01, 0.5, want_winding=False)
+    _gpe_rot(eng, 64, 2)  # GpeRot, GpeRotAdjoint (frozen)
+    _gpe_rot_stirred_adjoint(eng, 64, 2)  # GpeRotAdjoint (stirred)
+    _sensitivities(eng, 32, 2)  # Sens
+    _butler_volmer(eng, 32, 2)  # BvState
+    _implicit(eng, 32, 2)  # Implicit
+
+
 def test_everything_is_released():
     probe = P.HipEngine()  # never configured: holds nothing, reads the process-wide counter
     before = probe.device_bytes()
     eng = P.HipEngine()
     _explicit_and_diagnostics(eng, 32, 2)
     assert probe.device_bytes() > before
-    _imex(eng, 32, 2)
-    _gpe_strang(eng, 64, 2)
-    eng.gpe_observables()
-    eng.detect_vortices(0.01, 0.5, want_winding=False)
-    _gpe_rot(eng, 64, 2)
-    _sensitivities(eng, 32, 2)
-    _butler_volmer(eng, 32, 2)
-    _implicit(eng, 32, 2)
+    _tour(eng)
     # the networks on a second engine, while the first still holds the implicit workspace
     nets_eng = P.HipEngine()
     nets_eng.configure(dtype=np.float32, batch=2, **_problem(32))
@@ -193,6 +248,135 @@ def test_everything_is_released():
     eng.close()
     assert probe.device_bytes() == before
     probe.close()
+
+
+def test_a_shape_change_drops_every_feature_state():
+    """An engine that has held every feature state and one that never held any hold the same bytes once both run the plain
+    32 x 32 fp32 batch-2 Cahn-Hilliard problem: a state some slot left behind would show as a byte difference.  Both end
+    with _explicit_and_diagnostics, so the grow-only work blocks of its reductions and diagnostics (and its shell tables)
+    have the same sizes on both; the tour grows none of them any further."""
+    probe = P.HipEngine()
+    base = probe.device_bytes()
+
+    def life(tour):
+        eng = P.HipEngine()
+        if tour:
+            _explicit_and_diagnostics(eng, 32, 2)
+            _tour(eng)
+            # the tour ends on the shape of the last part, which a configure keeps: one more shape change (fp64) that drops
+            # the implicit workspace and leaves the Butler-Volmer state for the last configure to drop
+            _butler_volmer(eng, 32, 2)
+        _explicit_and_diagnostics(eng, 32, 2)  # configure, a state, RK4 steps, the diagnostics
+        eng.set_state(_state(32, 2, 11))
+        eng.advance(L.INT_RK4, DT, 2)
+        state, held = eng.get_state(), probe.device_bytes() - base
+        eng.close()
+        assert probe.device_bytes() == base
+        return state, held
+
+    state_a, held_a = life(True)
+    state_b, held_b = life(False)
+    print(f"bytes held: after the tour {held_a}, fresh {held_b}")
+    assert held_b > 0 and held_a == held_b
+    assert np.all(np.isfinite(state_b)) and np.array_equal(state_a, state_b)
+    probe.close()
+
+
+def _gpe_control(n):
+    dom = P.Domain((n, n), GPE_BOX, "dimensionless")
+    return dom, P.GPE2DTSControl(dom, 500.0, 0.2, GaussianSpots([GaussianSpot(1.5, -0.8, 0.4, 0.9, -0.3, 0.5, 0.6)]),
+                                 trap_factor=1.0, kinetic=True)
+
+
+def _strang_case(kernel_path, kernel):
+    """(set up with the A_term scaled by s, run from the starting state) of a Strang advance on one kernel path"""
+    dom, eq = _gpe_control(64)
+
+    def setup(eng, s):
+        eng.set_kernel_path(kernel_path)
+        eng.configure(dtype=np.float32, batch=2, **eq._engine_problem())
+        eq._engine_upload(eng, 0.0, 1.0)
+        eng.set_integrator_params(time_scale=1.0, strang_dx=float(eq.dx))
+        eng.set_aux(L.AUX_GPE_A_TERM, s * np.asarray(eq.A_term))
+
+    def run(eng):
+        eng.set_state(_psi(dom, 2))
+        eng.advance(L.INT_STRANG, 1e-3, 2)
+        assert eng.last_kernel == kernel
+        return (eng.get_state(),)
+
+    return L.AUX_GPE_A_TERM, np.asarray(eq.A_term), setup, run
+
+
+def _strang_adjoint_case():
+    dom, eq = _gpe_control(64)
+
+    def setup(eng, s):
+        eng.configure(dtype=np.float32, batch=2, **eq._engine_problem())
+        eq._engine_upload(eng, 0.0, 1.0)
+        eng.set_integrator_params(time_scale=1.0, strang_dx=float(eq.dx))
+        eng.set_aux(L.AUX_GPE_A_TERM, s * np.asarray(eq.A_term))
+
+    def run(eng):
+        eng.set_state(_psi(dom, 2))
+        return _adjoint_call(eng, lambda psi0, lam, g: eng.gpe_adjoint_step(0.0, 1e-3, psi0, lam, g), (2, 1, 7))
+
+    return L.AUX_GPE_A_TERM, np.asarray(eq.A_term), setup, run
+
+
+def _imex_case(n, kernel_path, kernel):
+    eq = _ch(n)
+    symbol = np.asarray(eq.fourier_symbol)
+
+    def setup(eng, s):
+        eng.set_kernel_path(kernel_path)
+        eng.configure(dtype=np.float32, batch=2, **eq._engine_problem())
+        eng.set_integrator_params(imex_A=0.5)
+        eng.set_aux(L.AUX_IMEX_SYMBOL, s * symbol)
+
+    def run(eng):
+        eng.set_state(_state(n, 2, 1))
+        eng.advance(L.INT_IMEX, 1e-6, 2)
+        assert eng.last_kernel.endswith(kernel)
+        return (eng.get_state(),)
+
+    return L.AUX_IMEX_SYMBOL, symbol, setup, run
+
+
+AUX_CASES = {
+    "strang_fused": lambda: _strang_case(0, "strang_fused_lds_fft"),  # StrangFused::mult_valid
+    "strang_rocfft": lambda: _strang_case(1, "strang_rocfft_c2c"),  # Spectral::mult_kind
+    # 64 x 64: the smallest grid the hand-written transforms cover (at 32 x 32 the step below would run instead)
+    "imex_fused": lambda: _imex_case(64, 0, "+imex_fused_lds_fft"),  # StrangFused::imex_valid
+    "imex_rocfft": lambda: _imex_case(32, 1, "+imex_rocfft_r2c"),  # Spectral::mult_kind
+    "strang_adjoint": _strang_adjoint_case,  # GpeAdjoint::mult_valid
+}
+
+
+@pytest.mark.parametrize("case", sorted(AUX_CASES))
+def test_set_aux_invalidates_every_cached_multiplier(case):
+    """A state that caches a multiplier keys it on the step size and the integrator's parameters, not on the aux field it
+    was built from: only pdeopt_set_aux's invalidation makes the second advance below, with the same dt, rebuild it.
+    Engine A advances with the field V1, uploads V2 = 1.5 V1 and advances again from the same state; engine B sees only V2.
+
+    The rotating-frame step and its two adjoints have no case: their cached tables (GpeRot, GpeRotAdjoint: kin_x / kin_y)
+    are functions of dt, the time scale and the mesh alone, formed in-kernel from no aux field (upload_kinetic in
+    gpe_rot.hip / gpe_rot_adjoint.hip); the potential, their only aux field, is read by the kernels directly."""
+    which, v1, setup, run = AUX_CASES[case]()
+    a = P.HipEngine()
+    setup(a, 1.0)
+    first = run(a)
+    a.set_aux(which, 1.5 * v1)
+    again = run(a)
+    a.close()
+    b = P.HipEngine()
+    setup(b, 1.5)
+    want = run(b)
+    b.close()
+    assert all(np.all(np.isfinite(w)) for w in want)
+    assert not np.array_equal(first[0], want[0]), "V1 and V2 give the same result: the case shows nothing"
+    for g, w in zip(again, want):
+        assert np.array_equal(g, w)
 
 
 def _configure(eng, kind, n, batch, seed):
